@@ -3,14 +3,23 @@
 (new 20 % supervision mask + fwd + weighted-MAE loss + bwd + Adam) of ``predict_lab_values`` on a synthetic eICU-shape
 hetero-graph.
 
-    python bench.py --gpus N --steps K --warmup W [--scale S] [--dim D] [--strong] [--no-strong-x1000]
+    python bench.py --gpus N --steps K --warmup W [--scale S] [--dim D] [--strong] [--dump-outputs DIR]
+                    [--full [--no-strong-x1000] [--no-kernels] [--no-extras] [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps of the headline, writes the outputs of its last timed step if
+--dump-outputs is given, and prints the result line.  Every other record below (fixed_supervision_mask, trainer_epoch,
+chain_overhead_ms, roofline, kernels, strong_x1000, cpu_baseline) needs --full; the --no-* options switch parts of it off.
+--dump-outputs DIR: after the timed region, DIR/<name>.npy (float32, or float64 where the step computes in fp64) for what
+the caller of the timed step receives from its LAST step -- `loss`, `pred` (the train pairs' predictions) and
+`param.<name>` for every parameter the optimizer updates; an array of more than DUMP_MAX_ELEMS elements is written as a
+fixed seeded sample of that many.  The inputs are seeded: equal arguments give equal inputs from run to run.
 
 One process per GPU (N>1: launched by torch.distributed.run, RCCL).  Workload at N GPUs:
   headline (weak) : every GPU holds an  x<scale>  eICU-shape shard (1,834*scale patients, 61,484*scale
                     has_lab edges, 128-d) of ONE global graph of N shards; vocab nodes shared.
                     N=1, scale=100 is BASELINE.json configs[2].
   --strong        : ONE global x<scale> graph, patient-sharded over the N GPUs (headline becomes the strong run).
-  strong_x1000    : in the same invocation, unless --no-strong-x1000: BASELINE.json config 4 -- ONE x1000 graph (1.83 M
+  strong_x1000    : with --full, in the same invocation, unless --no-strong-x1000: BASELINE.json config 4 -- ONE x1000 graph (1.83 M
                     patients, 61.5 M has_lab edges) at 256-d, patient-sharded over the N GPUs, RCCL all-reduces on the
                     shared vocab-side sums / gradients -- and the same graph at 128-d (north_star's 1 -> 8 curve).
                     Reported as objects of the same JSON line, so the per-N lines of a 1/2/4/8 sweep give the curves.
@@ -65,8 +74,14 @@ def self_launch():
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("OMP_NUM_THREADS", "4")
+    argv = list(sys.argv[1:])
+    for i, a in enumerate(argv):             # the ranks run in REPO: a relative DIR names the caller's directory
+        if a == "--dump-outputs" and i + 1 < len(argv):
+            argv[i + 1] = os.path.abspath(argv[i + 1])
+        elif a.startswith("--dump-outputs="):
+            argv[i] = "--dump-outputs=" + os.path.abspath(a.split("=", 1)[1])
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
+           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), *argv]
     proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, env=env, cwd=REPO)
     line = None
     for raw in proc.stdout:                  # rank 0 prints exactly one JSON line; anything else goes to stderr
@@ -87,6 +102,7 @@ if __name__ == "__main__":
     if _rc is not None:
         sys.exit(_rc)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 sys.path.insert(0, REPO)
@@ -126,11 +142,16 @@ def parse():
                     help="vocabulary of the synthetic graph: eicu = 50 / 114 / 100 (BASELINE configs 1-4), mimic = 50 / 200 / "
                          "100 (config 5: conf/config.yaml's MIMIC vocabulary caps)")
     ap.add_argument("--strong", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the records beside the headline: fixed-mask / Trainer / segment-chain replays, the per-kernel "
+                         "probe pass (roofline, kernels), the x1000 strong sub-records and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy")
     ap.add_argument("--no-strong-x1000", action="store_true", help="skip the x1000 patient-sharded sub-records")
     ap.add_argument("--strong-scale", type=int, default=1000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-scale", type=int, default=10, help="largest CPU sample (x1 is always timed as well)")
-    ap.add_argument("--profile-ops", action="store_true", help="print the per-kernel table to stderr")
+    ap.add_argument("--profile-ops", action="store_true", help="print the per-kernel table to stderr (--full)")
     ap.add_argument("--no-graph", action="store_true", help="time eager launches instead of hipGraph replays")
     ap.add_argument("--no-kernels", action="store_true", help="skip the per-kernel probe pass (profiler runs)")
     ap.add_argument("--no-extras", action="store_true",
@@ -226,11 +247,41 @@ def train_step(w):
     model.train()
     model.zero_grad(set_to_none=True)    # all parameters (the frozen embedding tables too): .grad adopted, not accumulated
     pred = model.predict_lab_values(w["plan"], w["pi"], w["li"])
+    w["pred"] = pred
     # weighted MAE over the supervision subset (train.py:366-386), global mean over all shards: one fused pass
     loss = ops.weighted_pair_loss(pred, w["y"], w["wpair"], w["supf"], 1.0 / w["n_sup"], "mae")
     loss.backward()
     opt.step()
     return loss
+
+
+# 32 MB of float32 per array: only `pred` can reach it (4.3 M at x100), the parameters are 7 MB at 256-d -> under 64 MB in all
+DUMP_MAX_ELEMS = 1 << 23
+
+
+def step_outputs(w, gstep, loss):
+    """--dump-outputs: what the caller of the timed step receives from its last step, on the host -- the loss, the
+    predictions of the train pairs (the graphed step's `pred` is 0 outside that step's supervision subset) and every
+    parameter the optimizer updated.  An array of more than DUMP_MAX_ELEMS elements -> a fixed seeded sample of them."""
+    arrays = {"loss": loss, "pred": gstep.pred if gstep is not None else w["pred"]}
+    for n, p in w["model"].named_parameters():
+        if not n.startswith("embeddings."):      # F5: the embedding tables are not in the optimizer
+            arrays["param." + n] = p
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+            t = t[idx.to(t.device)]
+        out[name] = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    out["loss"] = out["loss"].reshape(())
+    return out
+
+
+def write_outputs(path, outputs):
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def host_cores():
@@ -476,7 +527,7 @@ def make_graphed_step(w, world, warmup_capture, mask_fraction, capture_collectiv
 
 
 def measure(args, world, rank, dev, scale, strong, dim, steps, warmup, want_kernels, want_fixed=False, force_comm=False,
-            capture_collectives=None):
+            capture_collectives=None, want_outputs=False):
     w = build_workload(args, world, rank, dev, scale, strong, dim, force_comm=force_comm)
 
     def barrier():
@@ -519,6 +570,7 @@ def measure(args, world, rank, dev, scale, strong, dim, steps, warmup, want_kern
 
     # ---- timed region: exactly K steps
     dt, loss = timed_steps(step_fn, steps, barrier)
+    outputs = step_outputs(w, gstep, loss) if want_outputs else None      # before any later pass moves the model on
     loss_value = float(loss.detach())
     n_items = (sum(1 for k, _ in gstep.items if k == "graph"), sum(1 for k, _ in gstep.items if k == "all_reduce"),
                int(gstep.n_collectives)) if gstep is not None else (0, 0, 0)
@@ -574,7 +626,8 @@ def measure(args, world, rank, dev, scale, strong, dim, steps, warmup, want_kern
               f"{n_items[0]} hipGraph segments + {n_items[1]} all-reduces per step")
     rec = dict(dt=float(tmax), edges=float(edges), loss=loss_value, rows=rows, rows_shared=rows_shared, n_probe=n_probe,
                launch=launch,
-               dt_fixed=dt_fixed, P_loc=int(w["plan"].n_rows), pairs=int(w["pi"].numel()), extra=agg_extra(w, dim))
+               dt_fixed=dt_fixed, P_loc=int(w["plan"].n_rows), pairs=int(w["pi"].numel()),
+               extra=agg_extra(w, dim) if want_kernels else None, outputs=outputs)
     if w["comm"] is not None:          # the captured step goes before anything else of this group does (ShardComm.close)
         w["comm"].close(*([gstep] if gstep is not None else []), destroy=False)
     del w, gstep, step_fn
@@ -666,17 +719,20 @@ def main():
     if args.next_bn is not None:
         mmodel.set_next_bn([] if args.next_bn == "none" else [t for t in args.next_bn.split(",") if t])
     world, rank, dev = setup_dist(args)
-    head = measure(args, world, rank, dev, args.scale, args.strong, args.dim, args.steps, args.warmup, not args.no_kernels,
-                   want_fixed=not args.no_extras)
+    head = measure(args, world, rank, dev, args.scale, args.strong, args.dim, args.steps, args.warmup,
+                   args.full and not args.no_kernels, want_fixed=args.full and not args.no_extras,
+                   want_outputs=args.dump_outputs is not None and rank == 0)
+    if head["outputs"] is not None:
+        write_outputs(args.dump_outputs, head["outputs"])
     strong_recs = {}
-    if not args.no_strong_x1000 and not (args.strong and args.scale == args.strong_scale):
+    if args.full and not args.no_strong_x1000 and not (args.strong and args.scale == args.strong_scale):
         s_steps = max(3, min(args.steps, 5))
         for d in sorted({256, args.dim}, reverse=True):          # config 4 (256-d) and north_star's 128-d curve
             r = measure(args, world, rank, dev, args.strong_scale, True, d, s_steps, 2, False)
             r["steps"] = s_steps
             strong_recs[d] = r
     trainer_rec = chain_rec = None
-    if world == 1 and not args.no_extras and not args.no_graph:
+    if args.full and world == 1 and not args.no_extras and not args.no_graph:
         try:
             trainer_rec = measure_trainer(args, dev, args.scale, args.dim, max(5, min(args.steps, 30)))
         except Exception as e:
@@ -838,7 +894,7 @@ def main():
             ck = f"strong_x{args.strong_scale}" + ("" if d_ == 256 else f"_d{d_}")
             out["config"][ck + "_ms_per_step"] = out[key]["ms_per_step"]
             out["config"][ck + "_edges_per_s"] = out[key]["value"]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())

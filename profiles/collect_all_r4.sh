@@ -19,8 +19,8 @@ for t in $TAGS; do
   a=$(args_of $t)
   echo "##### $t ($a)"
   bash profiles/collect_r4.sh $t $a 2>&1 | grep -v "^rc=0" | tail -3
-  extra="--no-strong-x1000"
-  [ "$t" = "eicu_x100_d128" ] && extra=""
+  extra="--full --no-strong-x1000"
+  [ "$t" = "eicu_x100_d128" ] && extra="--full"
   [ "$t" = "eicu_x100_d128" ] || extra="$extra --no-cpu-baseline"
   timeout -k 10 900 python3 bench.py $a $extra > gpurun_out/r4_final/bench_$t.json 2> gpurun_out/r4_final/bench_$t.err
   echo "bench rc $?  $(python3 -c "import json;d=json.load(open('gpurun_out/r4_final/bench_$t.json'));print(d['ms_per_step'], d['roofline']['frac'])" 2>&1)"

@@ -13,7 +13,7 @@ step() { # name timeout cmd...
   echo "rc=$rc"
   if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "step $name timed out: stopping"; exit 1; fi
 }
-BA="--no-cpu-baseline --no-kernels --no-strong-x1000"
+BA="--full --no-cpu-baseline --no-kernels --no-strong-x1000"
 step stats_eager 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c_stats_eager -- python3 $R/bench.py --steps 5 --warmup 2 --no-graph $BA
 step stats_graph 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c_stats_graph -- python3 $R/bench.py --steps 40 --warmup 2 $BA
 step stats_mimic 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c_stats_mimic -- python3 $R/bench.py --steps 40 --warmup 2 --shape mimic $BA
