@@ -357,6 +357,7 @@ int mmg_gather_rows_next_bn(const mmg_rel_t* rels, int n_rel, int64_t n_rows, in
 #define MMG_PROBE_BN_BWD_STATS 9
 #define MMG_PROBE_BN_BWD_APPLY 10
 #define MMG_PROBE_ELEMENTWISE 11
+#define MMG_PROBE_PAIR_DENSE_FWD 12
 int mmg_probe_arm(int n_launches);
 #define MMG_PROBE_NAME_LEN 128
 /* names (nullable): cap * MMG_PROBE_NAME_LEN bytes; entry i receives the instantiated kernel symbol of launch i, e.g.
@@ -471,6 +472,17 @@ int mmg_pair_head_fwd_save(const mmg_head_t* head, const int32_t* pi, const int3
                            float drop_p, uint64_t seed, const uint64_t* seed_ptr, const int64_t* pair_id,
                            float* pred, const int32_t* sel, const int32_t* n_sel, const int64_t* io_perm,
                            const mmg_pair_saved_t* saved, void* stream);
+/* Dense imputation: ONE head over every lab of a list of patient rows, no pair list --
+ *   out[out_rows[r] * ld_out + l] = head(A[rows[r]], B[l])   for r < n_rows, l < n_labs  (inference: no dropout).
+ * Bitwise what mmg_pair_head_fwd returns for the pair (rows[r], l) with drop_p = 0 on the same head: same arithmetic in
+ * the same order (the caller applies the degree gate by choosing the head per row).  rows index A ([n_patients, 64]);
+ * out is [n_out, ld_out] fp32; other rows and the columns n_labs .. ld_out-1 are left untouched.  Every indexed access
+ * is range-checked: a rows[r] outside [0, n_patients) or an out_rows[r] outside [0, n_out) skips that row (rows /
+ * out_rows / A / B through buffer descriptors; out in 64-bit offsets, so it may exceed 4 GiB).  Requests of 2^31 cells
+ * or more are split into several launches on `stream`.  Limits: n_patients < 2^24, n_labs < 2^24, ld_out >= n_labs.
+ * Argument errors (MMG_E_ARG) are found on the host before anything is enqueued. */
+int mmg_pair_head_dense_fwd(const mmg_head_t* head, const int32_t* rows, const int32_t* out_rows, int64_t n_rows,
+                            int64_t n_patients, int n_labs, float* out, int64_t n_out, int64_t ld_out, void* stream);
 /* Backward: the weight-side gradients (dW2, db2, dW3, db3, dB) leave every workgroup as ONE partial slab in `ws` and are
  * summed in fixed order (bitwise reproducible); dA rows are flushed per patient run (pairs sorted by patient: a row
  * receives at most two partial sums unless one patient holds more than 32 listed pairs). */

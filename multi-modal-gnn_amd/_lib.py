@@ -166,6 +166,7 @@ SIGNATURES = {
                                     _vp, _vp, _vp, _vp, _vp]),
     "mmg_pair_head_fwd_save": (C.c_int, [_P(HeadT), _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i32, _f32, _u64, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _P(PairSavedT), _vp]),
+    "mmg_pair_head_dense_fwd": (C.c_int, [_P(HeadT), _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp]),
     "mmg_pair_head_bwd_saved": (C.c_int, [_P(HeadT), _P(HeadGradT), _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i32, _f32,
                                           _u64, _vp, _vp, _vp, _vp, _vp, _vp, _P(PairSavedT), _vp, _sz, _vp]),
     "mmg_pair_head_bwd_ws_bytes": (_sz, [_i64, _i32]),

@@ -1405,6 +1405,139 @@ __global__ __launch_bounds__(256, 2) void k_pair_fwd_mfma(HeadDev H, const int32
   }
 }
 
+// ---------------------------------------------------------------------------- dense forward: every lab of listed rows
+// One head over the full cross product of a list of patient rows and ALL n_labs labs: cell k = r * n_labs + l of a launch
+// lands in out[out_rows[r] * ld + l].  The cell coordinates are implicit -- no pair, list, permutation or id array is read,
+// there is no metadata pipeline -- and the 32 cells of a tile span at most ceil(32 / n_labs) + 1 patient rows, so a tile
+// reads a handful of A rows through L1 instead of one per cell.
+// The arithmetic is k_pair_fwd_mfma's with drop_p = 0, step for step: h1 = relu(A[p] + B[l]) in fp32, the 64 x 32 layer
+// as the same six-term bf16 split in the same matrix-instruction order, + b2, ReLU, the 32 -> 1 layer in the same fmaf
+// order, the cross-half add, + b3.  Every accumulator column depends on its own cell only, so each cell is BITWISE what
+// the pair path returns for the same (patient, lab) on the same head (tests/test_impute_gpu.py holds it to that).  Any
+// change to the arithmetic of one kernel has to be made in both.
+// Range checks: rows / out_rows / A / B go through buffer descriptors sized on the host; a row id outside A or an output
+// row outside [0, n_out) is skipped.  out itself is addressed in 64 bits after that check: [n_out, ld] can pass the
+// descriptors' 32-bit byte range (1.83 M rows x a few hundred labs).  The host splits a request into launches of
+// < 2^31 cells, so the cell index is 32-bit.
+template <bool B_LDS>
+__global__ __launch_bounds__(256, 2) void k_pair_dense_fwd(HeadDev H, const int32_t* __restrict__ rows,
+                                                           const int32_t* __restrict__ out_rows, uint32_t n_rows,
+                                                           uint32_t n_labs, int n_pat, float* __restrict__ out,
+                                                           int64_t n_out, int64_t ld) {
+  extern __shared__ __attribute__((aligned(16))) float Bs[];
+  if (B_LDS) {
+    for (uint32_t i = threadIdx.x; i < n_labs * 16u; i += 256)
+      *reinterpret_cast<f32x4*>(Bs + (i >> 4) * PF_LDB + (i & 15) * 4) = *reinterpret_cast<const f32x4*>(H.B + (size_t)i * 4);
+    __syncthreads();
+  }
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int h = lane >> 5, l31 = lane & 31;
+  pbf16x8 w2p[4][3];                 // W2 as three exact bf16 pieces, the A operand of k_pair_fwd_mfma
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float v = H.W2[l31 * 64 + 16 * ks + 8 * h + j];
+      const __bf16 a = (__bf16)v;
+      const float r1 = v - (float)a;
+      const __bf16 b = (__bf16)r1;
+      w2p[ks][0][j] = a; w2p[ks][1][j] = b; w2p[ks][2][j] = (__bf16)(r1 - (float)b);
+    }
+  float b2r[16], w3r[16];            // this lane's 16 units: crow(r, h)
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { b2r[r] = H.b2[crow(r, h)]; w3r[r] = H.W3[crow(r, h)]; }
+  const float b3 = H.b3[0];
+
+  const uint32_t n_cells = n_rows * n_labs;
+  const int64_t n_tiles = (n_cells + TP - 1) / TP;
+  const int64_t wave_id = (int64_t)blockIdx.x * 4 + wid, n_waves = (int64_t)gridDim.x * 4;
+  const __amdgpu_buffer_rsrc_t rows_d = pair_rsrc(rows, n_rows * 4u), orow_d = pair_rsrc(out_rows, n_rows * 4u);
+  const __amdgpu_buffer_rsrc_t A_d = pair_rsrc(H.A, (uint32_t)n_pat * 256u), B_d = pair_rsrc(H.B, n_labs * 256u);
+  // Two-deep pipeline, one dependent load per stage:  tile t+2: cell -> (row, lab); patient row id, output row
+  //                                                   tile t+1: patient -> A row (lab -> B row without LDS)
+  // (loads are unconditional, as in k_pair_fwd_mfma: a stage only issues them, the next one finalises what came back)
+  struct Cell { int p, o, l; bool in; };     // after fin_idx: p = -1 -- not a cell (past the end, or an id out of range)
+  auto issue_idx = [&](int64_t t) {
+    const uint32_t k = t < n_tiles ? (uint32_t)t * TP + (uint32_t)l31 : n_cells;
+    Cell c;
+    c.in = k < n_cells;
+    const uint32_t r = c.in ? k / n_labs : 0u;
+    c.p = pair_ld_i32(rows_d, r * 4u);
+    c.o = pair_ld_i32(orow_d, r * 4u);
+    c.l = c.in ? (int)(k - r * n_labs) : 0;
+    return c;
+  };
+  auto fin_idx = [&](const Cell& c) {
+    Cell m = c;
+    if (!c.in || (unsigned)c.p >= (unsigned)n_pat || (uint64_t)(uint32_t)c.o >= (uint64_t)n_out) m.p = -1;
+    return m;
+  };
+  auto load_rows = [&](const Cell& m, f32x4* ra, f32x4* rb) {
+    const unsigned ao = (m.p >= 0 ? (unsigned)m.p : 0u) * 256u + 32u * h, bo = (unsigned)m.l * 256u + 32u * h;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      ra[q] = pair_ld_f4(A_d, ao + (q >> 1) * 64u + (q & 1) * 16u);
+      if (!B_LDS) rb[q] = pair_ld_f4(B_d, bo + (q >> 1) * 64u + (q & 1) * 16u);
+    }
+  };
+  const Cell c0 = issue_idx(wave_id);
+  Cell c1 = issue_idx(wave_id + n_waves);
+  Cell m0 = fin_idx(c0);
+  f32x4 ra[8], rb[8];
+  load_rows(m0, ra, rb);
+  for (int64_t t = wave_id; t < n_tiles; t += n_waves) {
+    const Cell mc = m0;
+    f32x4 ca[8], cb[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) { ca[q] = ra[q]; cb[q] = rb[q]; }
+    const Cell m1 = fin_idx(c1);                     // issued one iteration ago
+    c1 = issue_idx(t + 2 * n_waves);
+    load_rows(m1, ra, rb);
+    __builtin_amdgcn_sched_barrier(0);         // the next tiles' loads stay ahead of this tile's arithmetic
+    m0 = m1;
+    const bool active = mc.p >= 0;
+    if (__ballot(active) == 0ull) continue;
+    if (B_LDS) {
+      const float* bl = Bs + mc.l * PF_LDB + 8 * h;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) cb[q] = *reinterpret_cast<const f32x4*>(bl + (q >> 1) * 16 + (q & 1) * 4);
+    }
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {                 // 16 h1 columns per k-step, this lane: 16 ks + 8 h + 0..7
+      float x8[8];
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x8[4 * c + j] = fmaxf(ca[2 * ks + c][j] + cb[2 * ks + c][j], 0.f);
+      pbf16x8 x1, x2, x3;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const __bf16 a = (__bf16)x8[j];
+        const float r1 = x8[j] - (float)a;
+        const __bf16 b = (__bf16)r1;
+        x1[j] = a; x2[j] = b; x3[j] = (__bf16)(r1 - (float)b);
+      }
+      // C^T: lane = cell, reg = unit.  The order of k_pair_fwd_mfma
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][2], x1, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][0], x3, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][1], x2, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][1], x1, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][0], x2, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][0], x1, acc, 0, 0, 0);
+    }
+    float part = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) part = fmaf(w3r[4 * i + e], fmaxf(acc[4 * i + e] + b2r[4 * i + e], 0.f), part);
+    part += __shfl_xor(part, 32, 64);
+    if (h == 0 && active) out[(int64_t)mc.o * ld + mc.l] = part + b3;
+  }
+}
+
 // ---------------------------------------------------------------------------- pair selection (stable compaction)
 constexpr int SEL_PER = 8, SEL_CH = 256 * SEL_PER;      // pairs per thread / per workgroup
 
@@ -1625,6 +1758,44 @@ extern "C" int mmg_pair_head_fwd_save(const mmg_head_t* head, const int32_t* pi,
   }
 #undef MMG_LAUNCH_PFWD
   MMG_CHECK_LAUNCH("pair_head_fwd");
+  return MMG_OK;
+}
+
+extern "C" int mmg_pair_head_dense_fwd(const mmg_head_t* head, const int32_t* rows, const int32_t* out_rows,
+                                       int64_t n_rows, int64_t n_patients, int n_labs, float* out, int64_t n_out,
+                                       int64_t ld_out, void* stream) {
+  MMG_CHECK_ARG(n_rows >= 0, "pair_head_dense_fwd: n_rows < 0");
+  MMG_CHECK_ARG(n_labs >= 1 && n_labs < (1 << 24), "pair_head_dense_fwd: %d lab rows outside [1, 2^24)", n_labs);
+  MMG_CHECK_ARG(ld_out >= n_labs, "pair_head_dense_fwd: ld_out %lld < n_labs %d", (long long)ld_out, n_labs);
+  MMG_CHECK_ARG(n_patients >= 1 && n_patients < (1ll << 24), "pair_head_dense_fwd: %lld patient rows outside [1, 2^24)",
+                (long long)n_patients);
+  MMG_CHECK_ARG(n_out >= 0, "pair_head_dense_fwd: n_out < 0");
+  if (n_rows == 0) return MMG_OK;
+  int rc = check_head(head, "pair_head_dense_fwd");
+  if (rc) return rc;
+  MMG_CHECK_ARG(rows && out_rows && out, "pair_head_dense_fwd: null buffer");
+  HeadDev H{head->A, head->B, head->W2, head->b2, head->W3, head->b3};
+  const bool b_lds = n_labs <= 256;                        // the pair kernel's LDS table: 68 KB at most
+  const size_t lds = b_lds ? (size_t)n_labs * PF_LDB * sizeof(float) : 0;
+  if (b_lds)
+    MMG_CHECK_HIP((MmgMaxLds<&k_pair_dense_fwd<true>, 256 * PF_LDB * (int)sizeof(float)>::set()), "pair_head_dense_fwd(attr)");
+  int64_t per = ((1ll << 31) - 1) / n_labs;                // rows per launch: < 2^31 cells (32-bit cell index) ...
+  if (per > (1ll << 29)) per = 1ll << 29;                   // ... and < 2^31 bytes of rows / out_rows (descriptors)
+  for (int64_t r0 = 0; r0 < n_rows; r0 += per) {
+    const int64_t nr = n_rows - r0 < per ? n_rows - r0 : per;
+    int64_t g = ((nr * n_labs + TP - 1) / TP + 3) / 4;
+    if (g > 2048) g = 2048;
+    if (g < 1) g = 1;
+    if (b_lds)
+      MMG_LAUNCH(MMG_PROBE_PAIR_DENSE_FWD, nr * n_labs, n_labs, 0, 0, k_pair_dense_fwd<true>, dim3((unsigned)g), dim3(256),
+                 lds, (hipStream_t)stream, H, rows + r0, out_rows + r0, (uint32_t)nr, (uint32_t)n_labs, (int)n_patients,
+                 out, n_out, ld_out);
+    else
+      MMG_LAUNCH(MMG_PROBE_PAIR_DENSE_FWD, nr * n_labs, n_labs, 0, 0, k_pair_dense_fwd<false>, dim3((unsigned)g),
+                 dim3(256), 0, (hipStream_t)stream, H, rows + r0, out_rows + r0, (uint32_t)nr, (uint32_t)n_labs,
+                 (int)n_patients, out, n_out, ld_out);
+    MMG_CHECK_LAUNCH("pair_head_dense_fwd");
+  }
   return MMG_OK;
 }
 

@@ -1,0 +1,139 @@
+"""Lab imputation reports (reference ``src/inference.py:53-178``, ``predict_for_patient``).
+
+The reference answers "what are this patient's labs" with two whole-graph forwards per patient: ``predict_lab_values``
+over the labs the patient has, then again over the ones never measured.  Here one ``HeteroRGCN.impute_lab_matrix``
+forward gives every lab of every requested patient (bit for bit the pair path's predictions), and the report of each
+patient is assembled on the host from its row of that matrix:
+
+  impute_missing        the dense matrix and which of its cells are observed ``has_lab`` edges
+  predict_for_patient   the reference's signature and result dict (measured / masked / truly missing labs)
+  predict_for_patients  the same dicts for many patients from one forward
+  lab_report            the host-side assembly of one patient's dict (no device, no model)
+
+Printing, config loading and the command line of the reference script (``print_patient_report``, ``run_inference``)
+are not part of this module.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .data import LAB_EDGE, ROW_TYPE
+
+
+def impute_missing(model, data, patient_indices: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (pred [n, L] fp32, observed [n, L] bool) for the requested patients (all when None), in the requested order:
+    pred = model.impute_lab_matrix(data, patient_indices); observed[i, l] = patient i has a has_lab edge to lab l."""
+    pred = model.impute_lab_matrix(data, patient_indices)
+    dev = pred.device
+    P = int(data[ROW_TYPE].num_nodes)
+    rows = torch.arange(P, device=dev) if patient_indices is None else patient_indices.to(torch.int64)
+    observed = torch.zeros(pred.shape, dtype=torch.bool, device=dev)
+    if rows.numel() == 0:
+        return pred, observed
+    ei = data[LAB_EDGE].edge_index.to(dev)
+    uniq, inv = torch.unique(rows, return_inverse=True)        # (a request may repeat a patient)
+    upos = torch.full((P,), -1, dtype=torch.int64, device=dev)
+    upos[uniq] = torch.arange(uniq.numel(), device=dev)
+    e_row = upos[ei[0]]
+    keep = e_row >= 0
+    obs_u = torch.zeros(uniq.numel(), pred.shape[1], dtype=torch.bool, device=dev)
+    obs_u[e_row[keep], ei[1][keep]] = True
+    return pred, obs_u[inv]
+
+
+def _lab_stats_rows(lab_stats, names):
+    # the reference's own lookup (inference.py:120): the first row of lab_stats whose ITEMID is the lab's name
+    return {name: lab_stats[lab_stats['ITEMID'] == name].iloc[0] for name in names}
+
+
+def lab_report(pred_row: np.ndarray, lab_indices: np.ndarray, values: np.ndarray, in_test: np.ndarray,
+               lab_stats, lab_indexer: Dict, stats_rows: Optional[Dict] = None) -> Dict:
+    """One patient's report, reference inference.py:107-178, from host data only.
+    pred_row: [L] normalised predictions of every lab (a row of impute_lab_matrix); lab_indices / values / in_test: the
+    patient's has_lab edges in edge order -- lab index, normalised value, edge in the test split.  Values are
+    denormalised as value * std + mean with the lab's row of lab_stats (columns ITEMID, mean, std).
+    -> {'measured_labs', 'masked_labs', 'truly_missing_labs'} with the reference's keys."""
+    lab_idx_to_name = {v: k for k, v in lab_indexer.items()}
+    if stats_rows is None:
+        stats_rows = _lab_stats_rows(lab_stats, lab_indexer.keys())
+    measured_labs, masked_labs = {}, {}
+    for lab_idx, actual, test in zip(lab_indices, values, in_test):
+        lab_name = lab_idx_to_name[lab_idx]
+        pred = pred_row[lab_idx]
+        lab_stat = stats_rows[lab_name]
+        mean_val = lab_stat['mean']
+        std_val = lab_stat['std']
+        actual_original = actual * std_val + mean_val
+        pred_original = pred * std_val + mean_val
+        if test:
+            masked_labs[lab_name] = {
+                'predicted': float(pred_original),
+                'actual': float(actual_original),
+                'error': float(abs(pred_original - actual_original)),
+                'normalized_predicted': float(pred),
+                'normalized_actual': float(actual)
+            }
+        else:
+            measured_labs[lab_name] = {
+                'value': float(actual_original),
+                'normalized': float(actual)
+            }
+    patient_lab_names = set(lab_idx_to_name[idx] for idx in lab_indices)
+    truly_missing_labs = {}
+    for lab_name, lab_idx in lab_indexer.items():
+        if lab_name in patient_lab_names:
+            continue
+        pred = pred_row[lab_idx]
+        lab_stat = stats_rows[lab_name]
+        pred_original = pred * lab_stat['std'] + lab_stat['mean']
+        truly_missing_labs[lab_name] = {
+            'predicted': float(pred_original),
+            'normalized_predicted': float(pred),
+            'note': 'Lab was never measured for this patient'
+        }
+    return {
+        'measured_labs': measured_labs,
+        'masked_labs': masked_labs,
+        'truly_missing_labs': truly_missing_labs
+    }
+
+
+def predict_for_patients(patient_ids: Sequence, data, model, device, labs_df, lab_stats, masker, patient_indexer: Dict,
+                         lab_indexer: Dict) -> List[Dict]:
+    """predict_for_patient for many patients from ONE impute_lab_matrix forward -> one dict per id, in order."""
+    idx = [patient_indexer[str(pid)] for pid in patient_ids]
+    data_device = data.to(device)
+    rows = torch.tensor(idx, dtype=torch.int64, device=device)
+    pred = model.impute_lab_matrix(data_device, rows).cpu().numpy()
+    if not idx:
+        return []
+    # the requested patients' edges, grouped by patient in edge order (torch.where(edge_index[0] == p) of the reference)
+    ei = data_device[LAB_EDGE].edge_index
+    attr = data_device[LAB_EDGE].edge_attr.reshape(-1)
+    want = torch.zeros(int(data_device[ROW_TYPE].num_nodes), dtype=torch.bool, device=ei.device)
+    want[rows.to(ei.device)] = True
+    pos = torch.nonzero(want[ei[0]]).squeeze(1)
+    e_pat, e_lab, e_val = ei[0][pos].cpu().numpy(), ei[1][pos].cpu().numpy(), attr[pos].cpu().numpy()
+    pos = pos.cpu().numpy()
+    order = np.argsort(e_pat, kind="stable")
+    e_pat, e_lab, e_val, pos = e_pat[order], e_lab[order], e_val[order], pos[order]
+    test_mask = masker.test_mask.cpu().numpy()
+    stats_rows = _lab_stats_rows(lab_stats, lab_indexer.keys())
+    out = []
+    for i, p in enumerate(idx):
+        lo, hi = np.searchsorted(e_pat, p, "left"), np.searchsorted(e_pat, p, "right")
+        out.append(lab_report(pred[i], e_lab[lo:hi], e_val[lo:hi], test_mask[pos[lo:hi]], lab_stats, lab_indexer,
+                              stats_rows))
+    return out
+
+
+def predict_for_patient(patient_id: int, data, model, device, labs_df, lab_stats, masker, patient_indexer: Dict,
+                        lab_indexer: Dict) -> Dict:
+    """Reference inference.py:53-178 (same arguments, same result): the patient's measured labs, the labs held out in
+    the test split (predicted vs actual) and the labs never measured (predicted), denormalised through lab_stats --
+    from one row of impute_lab_matrix instead of two whole-graph forwards."""
+    return predict_for_patients([patient_id], data, model, device, labs_df, lab_stats, masker, patient_indexer,
+                                lab_indexer)[0]

@@ -229,6 +229,23 @@ class HeteroRGCN(nn.Module):
         run = _Run(self, data)
         return run.apply("predict", patient_indices, lab_indices)
 
+    def impute_lab_matrix(self, data, patient_indices: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The degree-gated prediction of EVERY lab for the requested patients (all of them when None), in the requested
+        order -> [n, L].  Bit for bit predict_lab_values(data, p.repeat_interleave(L), lab.repeat(n)).view(n, L) in eval
+        mode: the same encoder, layers and head tables, then one dense head launch per head instead of an n * L pair
+        list.  Inference only: no autograd, BatchNorm buffers untouched."""
+        if self.training:
+            raise RuntimeError("impute_lab_matrix is inference-only: call model.eval() first (the heads' dropout is "
+                               "keyed by pair id and has no dense meaning)")
+        if self._comm is not None:
+            raise NotImplementedError("impute_lab_matrix on a patient-sharded model (dist.shard_model) is not supported: "
+                                      "the forward's collectives need every rank; impute with an unsharded model")
+        if len(self.embeddings) == 0:
+            self._init_embeddings(data)
+        with torch.no_grad():
+            run = _Run(self, data)
+            return run.apply("impute", patient_indices)
+
     def configure_execution(self, overlap: Optional[str] = None, next_bn=None, save_pair_state: Optional[bool] = None):
         """Per-model execution switches (None = keep / fall back to the module-level default): `overlap` 'auto' | 'off' |
         'on' (vocab-side work of a layer on a side stream), `next_bn` = the BatchNorm-backward statistics taken from
@@ -451,6 +468,19 @@ class _Run:
                                        getattr(self.comm, "pair_ids", None) if self.comm else None,
                                        self.plan.lab_deg, int(self.m.degree_threshold))
             self.n_pairs = pi.numel()
+        elif mode == "impute":
+            P, L = self.plan.n_rows, self.plan.num_nodes["lab"]
+            if pi is None:
+                pi = torch.arange(P, device=self.dev)
+            if pi.device != self.dev:
+                raise ops._lib.MmgError("patient_indices must live on the model's device")
+            if pi.dtype.is_floating_point or pi.dtype == torch.bool or pi.dim() != 1:
+                raise TypeError(f"patient_indices: expected a 1-D integer tensor, got {pi.dtype} {list(pi.shape)}")
+            if pi.numel() == 0:
+                return torch.empty(0, L, device=self.dev)
+            if int(pi.min()) < 0 or int(pi.max()) >= P:
+                raise IndexError("patient_indices out of range")
+            self.impute_rows = pi.to(torch.int64)
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.params.values())
         self.need_grad = need_grad
         self.m._last_run = self if need_grad else None      # (tests drive run_backward by hand through this)
@@ -459,7 +489,7 @@ class _Run:
             outs = _StepFn.apply(self, mode, 0, *plist)
         else:
             outs = tuple(self.run_forward(mode))
-        if mode == "predict":
+        if mode in ("predict", "impute"):
             return outs[0]
         return {t: o for t, o in zip(self.out_types, outs)}
 
@@ -490,6 +520,10 @@ class _Run:
             self.out_types = list(x.keys())
             return [x[t] for t in self.out_types]
         self.lazy_final = True
+        if mode == "impute":             # eval predict up to the head tables (the p == 0 branch below), then dense heads
+            enc = self.enc_fwd(0, 2)
+            fin, _ = self.layers_fwd(self.enc_dict(enc))
+            return [self.heads_dense(self.enc_dict(enc), fin, self.impute_rows)]
         # predict: encode_nodes runs twice (model.py:294 and :301->251).  The two passes differ only by
         # their dropout masks, so with p == 0 (or eval) one pass is computed and BN running stats are
         # advanced twice.
@@ -1325,6 +1359,32 @@ class _Run:
                               sel=sel, n_sel=n_sel, n_bound=nb, io_perm=perm, save=save)   # written in the caller's pair order
             rec[which] = (head, w1a, w1b, xP, save)
         return pred, rec
+
+    def heads_dense(self, init, fin, rows):
+        """Both heads over every lab of the patients `rows` -> [n, L]: the head tables of heads_fwd (edge_predictor on all
+        patients, tabular_mlp on the compacted low-degree ones), each row routed to its head by the degree gate."""
+        plan = self.plan
+        if LAB_EDGE not in plan.rels:
+            raise KeyError(f"graph has no {LAB_EDGE} relation (model.py:297)")
+        thr = int(self.m.degree_threshold)
+        low = plan.lab_deg < thr
+        low_rows = torch.nonzero(low).squeeze(1)
+        low_pos = torch.full((plan.n_rows,), -1, dtype=torch.int32, device=self.dev)
+        low_pos[low_rows] = torch.arange(low_rows.numel(), dtype=torch.int32, device=self.dev)
+        out = torch.empty(rows.numel(), plan.num_nodes["lab"], device=self.dev)
+        pos = torch.arange(rows.numel(), dtype=torch.int32, device=self.dev)
+        row_low = low[rows]
+        halves = self.head_weight_halves()
+        for which, src, want_low in (("edge_predictor", fin, False), ("tabular_mlp", init, True)):
+            sel = row_low if want_low else ~row_low
+            r, o = rows[sel], pos[sel].contiguous()
+            if o.numel() == 0:
+                continue
+            xP = src[ROW_TYPE].index_select(0, low_rows) if want_low else src[ROW_TYPE]
+            head, _, _ = self.head_tensors(which, xP, src["lab"], *halves[which])
+            r = (low_pos[r] if want_low else r.to(torch.int32)).contiguous()
+            ops.pair_head_dense_fwd(head, r, o, out)
+        return out
 
     def heads_bwd(self, rec, dpred):
         plan, D = self.plan, self.D

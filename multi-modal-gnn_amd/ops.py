@@ -89,7 +89,7 @@ def _pe(tok, name, nbytes=0, flops=0):
 
 PROBE_TAGS = {1: "linear_fwd", 2: "linear_wgrad", 3: "linear_wgrad_reduce", 4: "gather_rows", 5: "scatter_rows",
               6: "scatter_reduce", 7: "pair_head_fwd", 8: "pair_head_bwd", 9: "bn_bwd_stats", 10: "bn_bwd_apply",
-              11: "elementwise"}
+              11: "elementwise", 12: "pair_head_dense_fwd"}
 
 
 def probe_arm(n: int):
@@ -854,6 +854,31 @@ def pair_head_fwd(head: Head, pi, li, deg, thr: int, want_low: bool, p: float, s
           "mmg_pair_head_fwd_save")
     _pe(_tok, "pair_head_fwd", n * (12 + (136 if sv is not None else 0)) + 256 * (head.A.shape[0] + head.B.shape[0]),
         n * 2 * (64 * 32 + 32 + 64))
+
+
+def pair_head_dense_fwd(head: Head, rows, out_rows, out):
+    """Every lab of every listed patient row through one head (mmg_pair_head_dense_fwd, inference: no dropout):
+    out[out_rows[r], l] = the prediction for (A row rows[r], lab l), l < B.shape[0] -- bitwise what pair_head_fwd returns
+    for that pair with p = 0.  rows / out_rows: int32 [n]; out: fp32 [n_out, W] with W >= the number of labs (columns
+    beyond it and unlisted rows are left as they are).  Returns out."""
+    lib = _lib.load()
+    n = rows.numel()
+    if out_rows.numel() != n:
+        raise ValueError(f"pair_head_dense_fwd: out_rows has {out_rows.numel()} entries, rows has {n}")
+    if head.A.dim() != 2 or head.A.shape[1] != 64 or head.B.dim() != 2 or head.B.shape[1] != 64:
+        raise ValueError("pair head: A and B must be [rows, 64]")
+    n_labs = int(head.B.shape[0])
+    if out.dim() != 2 or out.shape[1] < n_labs:
+        raise ValueError(f"pair_head_dense_fwd: out must be [rows, >= {n_labs}], got {list(out.shape)}")
+    if n == 0:
+        return out
+    h = head.c()
+    _tok = _pb("pair_head_dense_fwd")
+    check(lib.mmg_pair_head_dense_fwd(C.byref(h), _p(rows, torch.int32), _p(out_rows, torch.int32), n,
+                                      int(head.A.shape[0]), n_labs, _p(out), int(out.shape[0]), int(out.shape[1]),
+                                      _stream()), "mmg_pair_head_dense_fwd")
+    _pe(_tok, "pair_head_dense_fwd", n * (8 + 256 + 4 * n_labs) + 256 * n_labs, n * n_labs * 2 * (64 * 32 + 32 + 64))
+    return out
 
 
 def pair_head_bwd(head: Head, grads: Head, pi, li, deg, thr: int, want_low: bool, n_labs: int, p: float, seed: int,
