@@ -338,6 +338,42 @@ int mmg_linear_bnbwd_rows_next_bn(const float* G_rows, const int32_t* row_pos, i
 int mmg_gather_rows_next_bn(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D, float* out, int accumulate,
                             const mmg_next_bn_t* next, void* stream);
 
+/* The weight gradient of the same layer inside the BatchNorm-backward data-gradient GEMMs: what the plain entry point
+ * (or its _next_bn form; next may be NULL) computes, and in the same launch what
+ *   mmg_linear_wgrad_deferred(dZ, X, wg->pro, wg->dW, wg->dbias, M, K, N, wg->accumulate, wg->ws, wg->ws_bytes, ., wg->job)
+ * would: dW [K, N] (+)= dZ^T . pro(X), dbias [K] (+)= the column sums of dZ, while dZ is still on chip.  The slabs are
+ * left in ws and described in *wg->job for mmg_wgrad_reduce_group; job == NULL sums them before returning.  dZ may be
+ * NULL: it is then not written (nothing else reads it).  X [M, N] is the layer input; its prologue takes relu only.
+ * mmg_linear_bnbwd_wgrad_supported: mmg_linear_bnbwd_supported and K = N = 128. */
+typedef struct {
+  const float* X;                 /* [M, N] input of the linear */
+  const mmg_prologue_t* pro;      /* its prologue (BatchNorm fold, relu, dropout) or NULL */
+  float* dW;                      /* [K, N] */
+  float* dbias;                   /* [K] or NULL */
+  int accumulate;
+  void* ws;                       /* >= mmg_linear_bnbwd_wgrad_ws_bytes(M, N, K) */
+  size_t ws_bytes;
+  mmg_wgrad_reduce_t* job;        /* deferred slab sum, or NULL */
+} mmg_bnbwd_wgrad_t;
+int mmg_linear_bnbwd_wgrad_supported(int64_t M, int N, int K);
+size_t mmg_linear_bnbwd_wgrad_ws_bytes(int64_t M, int N, int K);
+int mmg_linear_bnbwd_wgrad(const float* G, const float* Y, const mmg_prologue_t* pro, const float* mean, const float* rstd,
+                           const double* sums, double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ,
+                           float* dX, int64_t M, int N, int K, const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg,
+                           void* stream);
+int mmg_linear_bnbwd2_wgrad(const float* G, const float* G2, const float* Y, const mmg_prologue_t* pro,
+                            const mmg_prologue_t* pro2, const float* mean, const float* rstd, const double* sums,
+                            double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ, float* dX, int64_t M,
+                            int N, int K, const mmg_bnbwd_wgrad_t* wg, void* stream);
+int mmg_linear_bnbwd_rows_wgrad(const float* G_rows, const int32_t* row_pos, int64_t n_sel, const float* Y,
+                                const mmg_prologue_t* pro, const float* mean, const float* rstd, const double* sums,
+                                double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ, float* dX,
+                                int64_t M, int N, int K, const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg,
+                                void* stream);
+int mmg_linear_l2bwd_wgrad(const float* G, const float* out, const float* rnorm, const float* W, float* dZ, float* dX,
+                           int64_t M, int N, int K, float eps, const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg,
+                           void* stream);
+
 /* Measurement hook (bench.py).  After mmg_probe_arm(n) the next n launches of the big kernels (from any host thread: the
  * backward of a step runs on the autograd engine's thread) carry a HIP start / stop event pair on the kernel itself (hipExtLaunchKernelGGL: the kernel's own begin / end
  * timestamps on its stream -- what rocprofv3 reports -- not a pair of extra queue entries around it).  mmg_probe_read

@@ -84,6 +84,12 @@ class WgradReduceT(C.Structure):
                 ("nk4", C.c_int64), ("accumulate", C.c_int)]
 
 
+class BnBwdWgradT(C.Structure):
+    _fields_ = [("X", C.c_void_p), ("pro", C.POINTER(PrologueT)), ("dW", C.c_void_p), ("dbias", C.c_void_p),
+                ("accumulate", C.c_int), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+                ("job", C.POINTER(WgradReduceT))]
+
+
 class SumJobT(C.Structure):
     _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p * 4), ("n_src", C.c_int), ("len", C.c_int),
                 ("cols", C.c_int), ("ld_dst", C.c_int), ("ld_src", C.c_int * 4)]
@@ -140,6 +146,16 @@ SIGNATURES = {
     "mmg_linear_fwd_l2norm_supported": (C.c_int, [_i64, _i32, _i32]),
     "mmg_linear_fwd_l2norm": (C.c_int, [_vp, _P(PrologueT), _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp]),
     "mmg_linear_bnbwd_supported": (C.c_int, [_i64, _i32, _i32]),
+    "mmg_linear_bnbwd_wgrad_supported": (C.c_int, [_i64, _i32, _i32]),
+    "mmg_linear_bnbwd_wgrad_ws_bytes": (_sz, [_i64, _i32, _i32]),
+    "mmg_linear_bnbwd_wgrad": (C.c_int, [_vp, _vp, _P(PrologueT), _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp,
+                                         _i64, _i32, _i32, _P(NextBnT), _P(BnBwdWgradT), _vp]),
+    "mmg_linear_bnbwd2_wgrad": (C.c_int, [_vp, _vp, _vp, _P(PrologueT), _P(PrologueT), _vp, _vp, _vp, C.c_double, _vp, _vp,
+                                          _vp, _vp, _vp, _i64, _i32, _i32, _P(BnBwdWgradT), _vp]),
+    "mmg_linear_bnbwd_rows_wgrad": (C.c_int, [_vp, _vp, _i64, _vp, _P(PrologueT), _vp, _vp, _vp, C.c_double, _vp, _vp, _vp,
+                                              _vp, _vp, _i64, _i32, _i32, _P(NextBnT), _P(BnBwdWgradT), _vp]),
+    "mmg_linear_l2bwd_wgrad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _P(NextBnT), _P(BnBwdWgradT),
+                                         _vp]),
     "mmg_linear_l2bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp]),
     "mmg_next_bn_ws_bytes": (_sz, [_i64, _i32]),
     "mmg_linear_fwd_next_bn": (C.c_int, [_vp, _P(PrologueT), _vp, _vp, _vp, _i64, _i32, _i32, _i32, _P(NextBnT), _vp]),

@@ -710,6 +710,17 @@ int launch_fwd_x6(const float* X, const ProDev& pr, const float* W, const float*
              : launch_fwd_x6_v<K, WN, false, false>(X, pr, W, bias, Y, M, N, flags, st, stat_partial);
 }
 
+// the gfx950 transposing LDS read of an MFMA operand that is contracted over its ROW index (see the wgrad section)
+typedef short xs16x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ xbf16x8 tr_frag(const __bf16* p, int row_stride) {   // rows +0..3 and +4..7 of this lane's column
+  const xs16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) xs16x4*)p);
+  const xs16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) xs16x4*)(p + 4 * row_stride));
+  typedef short s16x8 __attribute__((ext_vector_type(8)));
+  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(xbf16x8, v);
+}
+
 // ---------------------------------------------------------------------------- BatchNorm backward inside the data-gradient GEMM
 // dX = dZ . W  with  dZ = the backward of  dropout(relu(BN(y)))  at the upstream gradient G  (mmg_bn_bwd_apply's
 // arithmetic), computed WHILE the tile is staged: the kernel reads G and Y once, writes dZ once (the weight gradient of
@@ -732,20 +743,42 @@ struct BnBwdDev {
 
 // NBN: the statistics of the NEXT BatchNorm backward -- the one that consumes DX -- from the epilogue (NextBnDev),
 // partial[row-set][2][N] -> mmg_partial_sum.
-template <int K, int WN, int MODE = 0, bool NBN = false>
-__global__ __launch_bounds__(64 * WN, WN == 4 ? 2 : 1) void k_linear_bnbwd_x6(const float* __restrict__ G, BnBwdDev bb, ProDev pr,
-                                                                const float* __restrict__ W, float* __restrict__ DX,
-                                                                int64_t M, ProDev pr2, NextBnDev nb,
-                                                                double* __restrict__ stat_partial) {
+// FW: the weight gradient of the same layer rides along (K = N = 128 only): dW[K, N] = dZ^T . pro(X) and db = sum dZ,
+// contracted from the dZ planes while they are in LDS -- the separate weight-gradient kernel read dZ back from HBM and
+// split it again.  The workgroup doubles to eight waves, one per CU: waves 0..3 are the ones above (dZ staging, dX
+// products, NBN epilogue), waves 4..7 stage the matching 32-row tile of X (prologue: BN affine + ReLU + dropout with
+// the masks regenerated from the counter RNG, as k_linear_wgrad_x6<..., PRO = true>; split into three bf16 planes beside
+// dZ's) and each hold one 64 x 64 dW quadrant, read through the transposing LDS read like k_linear_wgrad_x6.  Tiles are
+// dealt round-robin over gridDim.y = plan_wgrad's n_split, so a workgroup reduces exactly the row set of the separate
+// kernel's slab, in the same order; one slab per workgroup (dW + column sums of dZ), summed by the grouped reduce.
+// Both sums are taken in the separate kernels' own order, so the slabs are theirs bit for bit: dW with the same six
+// products per accumulator and 16-row step, the column sums of dZ (reassembled exactly from the three planes: hi + mid +
+// lo is the fp32 value) with the partial sums of the kernel linear_wgrad picks for that X -- bias_order 0:
+// k_linear_wgrad_ws (four 8-row groups, ((g0 + g1) + g2) + g3), 1: k_linear_wgrad_x6<128, 128, 4, 2, true> (16 row
+// residues mod 16 of every 32-row tile, summed in order).
+// dZ is stored only where bb.dZ is set (a zero-sized descriptor drops the stores otherwise).
+struct BnWgDev {
+  const float* X; ProDev xpr; float* slab; int64_t slab_stride; int bias_order;
+};
+static inline BnWgDev bn_wg_none() { return BnWgDev{nullptr, mmg_pro_dev(nullptr), nullptr, 0, 0}; }
+
+template <int K, int WN, int MODE = 0, bool NBN = false, bool FW = false>
+__global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) void k_linear_bnbwd_x6(
+    const float* __restrict__ G, BnBwdDev bb, ProDev pr, const float* __restrict__ W, float* __restrict__ DX, int64_t M,
+    ProDev pr2, NextBnDev nb, double* __restrict__ stat_partial, BnWgDev wg) {
+  static_assert(!FW || (K == 128 && WN == 4), "the fused weight gradient covers K = N = 128");
   if (MODE != 1) pr.resolve();
   if (MODE == 2) pr2.resolve();
+  if (FW) wg.xpr.resolve();
   constexpr int LDP = K + 8, N = 32 * WN, NK = K / 16, NTHR = 64 * WN, BM = 32;
-  extern __shared__ __attribute__((aligned(16))) __bf16 planes[];     // [2 buffers][3 pieces][BM][LDP]
+  constexpr int SX = N + 32;               // X plane row stride (FW): +64 B puts the 4 rows of a transposing read on disjoint banks
+  extern __shared__ __attribute__((aligned(16))) __bf16 planes[];     // [2 buffers][3 pieces][BM][LDP] (FW: + [2][3][BM][SX] of X)
   const int tid = threadIdx.x, lane = tid & 63, wn = tid >> 6;
   const int h = lane >> 5, l31 = lane & 31;
   const int col = wn * 32 + l31;
+  const bool xrole = FW && tid >= NTHR;    // (wave-uniform) the X stagers / dW multipliers
   xbf16x8 wb[NK][3];                       // W stored [K, N] (the forward weight, read in place)
-  {
+  if (!xrole) {
     const float* wp = W + (size_t)(8 * h) * N + col;
 #pragma unroll
     for (int ks = 0; ks < NK; ++ks)
@@ -760,7 +793,7 @@ __global__ __launch_bounds__(64 * WN, WN == 4 ? 2 : 1) void k_linear_bnbwd_x6(co
   }
   NextBnCol nbc = {};
   double cs1 = 0.0, cs2 = 0.0;
-  if constexpr (NBN) nbc = next_bn_col(nb, col);
+  if constexpr (NBN) if (!xrole) nbc = next_bn_col(nb, col);
   constexpr int K4 = K / 4;
   const int kc4 = tid % K4, c = kc4 * 4;    // this thread always touches the same 4 columns of G / Y / dZ
   constexpr int ROWS_PER_PASS = NTHR / K4;
@@ -844,7 +877,7 @@ __global__ __launch_bounds__(64 * WN, WN == 4 ? 2 : 1) void k_linear_bnbwd_x6(co
     const int64_t row0 = tile * BM;
     const int rows = rows_of(tile);
     const __amdgpu_buffer_rsrc_t zs = __builtin_amdgcn_make_buffer_rsrc(
-        bb.dZ + (size_t)(rows ? tile : 0) * BM * K, 0, rows * K * 4, 0x00020000);
+        bb.dZ + (size_t)(rows && bb.dZ ? tile : 0) * BM * K, 0, bb.dZ ? rows * K * 4 : 0, 0x00020000);
     __bf16* pb = planes + (size_t)buf * 3 * BM * LDP;
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
@@ -888,6 +921,8 @@ __global__ __launch_bounds__(64 * WN, WN == 4 ? 2 : 1) void k_linear_bnbwd_x6(co
         }
         v[j] = g;
       }
+      if constexpr (FW)
+        if (r >= rows) v = zero;           // rows past the end: nothing to the weight gradient (their stores are dropped)
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(xu32x4, v), zs, xvo, p * ROWS_PER_PASS * K * 4, 0);
       xbf16x4 q0, q1, q2;
 #pragma unroll
@@ -902,62 +937,232 @@ __global__ __launch_bounds__(64 * WN, WN == 4 ? 2 : 1) void k_linear_bnbwd_x6(co
       *reinterpret_cast<xbf16x4*>(pb + (2 * BM + r) * LDP + kc4 * 4) = q2;
     }
   };
-  if constexpr (MODE == 3) fetch_idx(t0);
-  fetch(t0);
-  stage(t0, 0);
-  fetch(t0 + GY);
-  __syncthreads();
-  const int yvo = ((4 * h) * N + wn * 32 + l31) * 4;     // C/D map: col = lane&31, row = (i&3) + 8*(i>>2) + 4*(lane>>5)
-  auto tile_body = [&](int64_t tt, int buf) __attribute__((always_inline)) {
-    const int rows = rows_of(tt);
-    const __amdgpu_buffer_rsrc_t xs = __builtin_amdgcn_make_buffer_rsrc(
-        DX + (size_t)(rows ? tt : 0) * BM * N, 0, rows * N * 4, 0x00020000);
-    f32x16 acc;
+  if (xrole) {
+    // ---------------------------------------------------------------- FW: X stagers and dW multipliers (waves 4..7)
+    const int t = tid - NTHR, w = wn - WN;
+    const int xc4 = t & 31, xr = t >> 5;            // a thread stages the column quad xc4 of rows xr + 8 u
+    constexpr int XU = BM * N / 4 / NTHR;           // 16-B loads per thread per tile
+    const int xvo2 = (xr * N + xc4 * 4) * 4;
+    f32x4 nx[XU];                                   // the NEXT tile of X
+    auto xfetch = [&](int64_t tile) __attribute__((always_inline)) {
+      const int rows = rows_of(tile);
+      const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<float*>(wg.X) + (size_t)(rows ? tile : 0) * BM * N, 0, rows * N * 4, 0x00020000);
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    stage(tt + GY, buf ^ 1);                   // the other buffer: its readers passed the barrier of the last tile
-    fetch(tt + 2 * GY);
-    float nby[NBN ? 16 : 1];
-    if constexpr (NBN) next_bn_load(nb, tt, rows, N, 0, yvo, nby);   // in flight under the products
-    __builtin_amdgcn_sched_barrier(0);         // keep the fetch ahead of the matrix loop
-    const __bf16* ap = planes + (size_t)buf * 3 * BM * LDP + l31 * LDP + 8 * h;
-#pragma unroll
-    for (int ks = 0; ks < NK; ++ks) {
-      const xbf16x8 a1f = *reinterpret_cast<const xbf16x8*>(ap + ks * 16);
-      const xbf16x8 a2f = *reinterpret_cast<const xbf16x8*>(ap + BM * LDP + ks * 16);
-      const xbf16x8 a3f = *reinterpret_cast<const xbf16x8*>(ap + 2 * BM * LDP + ks * 16);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3f, wb[ks][0], acc, 0, 0, 0);   // small terms first
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1f, wb[ks][2], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2f, wb[ks][1], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2f, wb[ks][0], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1f, wb[ks][1], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1f, wb[ks][0], acc, 0, 0, 0);
+      for (int u = 0; u < XU; ++u)
+        nx[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xvo2, u * (NTHR / 32) * N * 4, MMG_NT_LD));
+    };
+    f32x4 xsc = one, xsh = zero;
+    float xfloor = -__builtin_inff();
+    const bool xaff = wg.xpr.scale != nullptr || wg.xpr.relu, xdrop = wg.xpr.p > 0.f;
+    if (wg.xpr.scale) {
+      xsc = *reinterpret_cast<const f32x4*>(wg.xpr.scale + xc4 * 4);
+      xsh = *reinterpret_cast<const f32x4*>(wg.xpr.shift + xc4 * 4);
     }
-    float vv[16];
+    if (wg.xpr.relu) xfloor = 0.f;
+    __bf16* xplanes = planes + 2 * 3 * BM * LDP;
+    auto xstage = [&](int64_t tile, int buf) __attribute__((always_inline)) {
+      __bf16* xb = xplanes + (size_t)buf * 3 * BM * SX;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      vv[i] = acc[i];                        // (a bit_cast straight from the vector element stored element 0 sixteen times)
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[i]), xs, yvo, ((i & 3) + 8 * (i >> 2)) * N * 4,
-                                            MMG_NT_ST);
-    }
-    if constexpr (NBN) next_bn_tile(nb, nbc, vv, nby, rows, tt * BM, N, col, lane, cs1, cs2);
-    __syncthreads();                         // buf fully read, buf^1 fully written
-  };
-  tile_body(t0, 0);
-  tile_body(t0 + GY, 1);
-  for (int i = 2; i < n_my; i += 2) {
-    tile_body(t0 + (int64_t)i * GY, 0);
-    tile_body(t0 + (int64_t)(i + 1) * GY, 1);
-  }
-  if constexpr (NBN) {
-    // two partials per column (the lane halves) -> one: partial[row-set][2][N], fixed order
-    double* red = reinterpret_cast<double*>(planes);          // the planes are dead: every wave passed the last barrier
-    red[(h * 2 + 0) * N + col] = cs1;
-    red[(h * 2 + 1) * N + col] = cs2;
+      for (int u = 0; u < XU; ++u) {
+        const int r = xr + u * (NTHR / 32);
+        f32x4 v = nx[u];
+        if (xaff) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = fmaxf(fmaf(v[j], xsc[j], xsh[j]), xfloor);
+        }
+        if (xdrop)
+          mmg_drop4(v, wg.xpr.key, (uint64_t)(wg.xpr.row_offset + tile * BM + r) * (uint64_t)N + (uint64_t)(xc4 * 4),
+                    wg.xpr.thr, wg.xpr.inv_keep);
+        // rows past the end need no zeroing: their dZ rows are zero
+        xbf16x4 q0, q1, q2;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const __bf16 a = (__bf16)v[j];
+          const float r1 = v[j] - (float)a;
+          const __bf16 b = (__bf16)r1;
+          q0[j] = a; q1[j] = b; q2[j] = (__bf16)(r1 - (float)b);
+        }
+        *reinterpret_cast<xbf16x4*>(xb + (0 * BM + r) * SX + xc4 * 4) = q0;
+        *reinterpret_cast<xbf16x4*>(xb + (1 * BM + r) * SX + xc4 * 4) = q1;
+        *reinterpret_cast<xbf16x4*>(xb + (2 * BM + r) * SX + xc4 * 4) = q2;
+      }
+    };
+    // wave w owns the quadrant (w >> 1, w & 1) of dW [K, N]; transposing-read lane roles as in k_linear_wgrad_x6
+    const int qn = w >> 1, qk = w & 1;
+    const int g4 = lane >> 4, q = (lane >> 2) & 3, p4 = lane & 3;
+    const int tr_row = 8 * (g4 >> 1) + q, tr_col = 16 * (g4 & 1) + 4 * p4;
+    f32x16 wacc[2][2];
+    // the column sums of dZ (the bias gradient) as the partial sums the separate kernel keeps (see BnWgDev), each row
+    // reassembled from the three planes.  bias_order 0: thread t owns group t >> 6 and the columns 2 (t & 63) + 0..1;
+    // 1: thread t owns residue t >> 4 and the columns 8 (t & 15) + 0..7 (one ds_read_b128 per plane and row)
+    const bool has_bias = wg.slab_stride > (int64_t)K * N;
+    const int bg = wg.bias_order == 0 ? t >> 6 : t >> 4;
+    const int bc0 = wg.bias_order == 0 ? 2 * (t & 63) : 8 * (t & 15);
+    float bacc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+      for (int y = 0; y < 2; ++y)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) wacc[x][y][i] = 0.f;
+    xfetch(t0);
+    xstage(t0, 0);
+    xfetch(t0 + GY);
     __syncthreads();
-    for (int e = tid; e < 2 * N; e += NTHR) {
-      const int which = e / N, cc = e % N;
-      stat_partial[((size_t)by_u * 2 + which) * N + cc] = red[which * N + cc] + red[(2 + which) * N + cc];
+    auto wbody = [&](int64_t tt, int buf) __attribute__((always_inline)) {
+      xstage(tt + GY, buf ^ 1);
+      xfetch(tt + 2 * GY);
+      __builtin_amdgcn_sched_barrier(0);
+      const __bf16* zb = planes + (size_t)buf * 3 * BM * LDP + tr_row * LDP + qn * 64 + tr_col;
+      const __bf16* xb = xplanes + (size_t)buf * 3 * BM * SX + tr_row * SX + qk * 64 + tr_col;
+#pragma unroll
+      for (int ks = 0; ks < BM / 16; ++ks) {
+        xbf16x8 fa[2][3], fb[2][3];
+#pragma unroll
+        for (int x = 0; x < 2; ++x)
+#pragma unroll
+          for (int pc = 0; pc < 3; ++pc) {
+            fa[x][pc] = tr_frag(zb + pc * BM * LDP + ks * 16 * LDP + x * 32, LDP);
+            fb[x][pc] = tr_frag(xb + pc * BM * SX + ks * 16 * SX + x * 32, SX);
+          }
+        // small terms first, the order of k_linear_wgrad_ws / k_linear_wgrad_x6 for every accumulator
+        constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+        for (int tm = 0; tm < 6; ++tm)
+#pragma unroll
+          for (int x = 0; x < 2; ++x)
+#pragma unroll
+            for (int y = 0; y < 2; ++y)
+              wacc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[x][PA[tm]], fb[y][PB[tm]], wacc[x][y], 0, 0, 0);
+      }
+      if (has_bias) {
+        const __bf16* zp = planes + (size_t)buf * 3 * BM * LDP + bc0;
+        if (wg.bias_order == 0) {              // k_linear_wgrad_ws: group g, rows 8 g .. 8 g + 7 in order
+          typedef __bf16 xbf16x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const int r = 8 * bg + j;
+            const xbf16x2 a = *reinterpret_cast<const xbf16x2*>(zp + r * LDP);
+            const xbf16x2 b = *reinterpret_cast<const xbf16x2*>(zp + (BM + r) * LDP);
+            const xbf16x2 c = *reinterpret_cast<const xbf16x2*>(zp + (2 * BM + r) * LDP);
+#pragma unroll
+            for (int e = 0; e < 2; ++e) bacc[e] += ((float)a[e] + (float)b[e]) + (float)c[e];
+          }
+        } else {                               // k_linear_wgrad_x6: residue q, rows q then q + 16
+#pragma unroll
+          for (int u = 0; u < 2; ++u) {
+            const int r = bg + 16 * u;
+            const xbf16x8 a = *reinterpret_cast<const xbf16x8*>(zp + r * LDP);
+            const xbf16x8 b = *reinterpret_cast<const xbf16x8*>(zp + (BM + r) * LDP);
+            const xbf16x8 c = *reinterpret_cast<const xbf16x8*>(zp + (2 * BM + r) * LDP);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) bacc[e] += ((float)a[e] + (float)b[e]) + (float)c[e];
+          }
+        }
+      }
+      __syncthreads();                         // buf fully read, buf^1 fully written
+    };
+    wbody(t0, 0);
+    wbody(t0 + GY, 1);
+    for (int i = 2; i < n_my; i += 2) {
+      wbody(t0 + (int64_t)i * GY, 0);
+      wbody(t0 + (int64_t)(i + 1) * GY, 1);
+    }
+    if constexpr (NBN) __syncthreads();        // pairs with the barrier of the statistics epilogue below
+    if (has_bias) {                            // the partial sums -> the X planes (dead: every wave passed the last barrier)
+      float* red = reinterpret_cast<float*>(xplanes);          // [group / residue][K]
+      const int np = wg.bias_order == 0 ? 2 : 8;
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (e < np) red[bg * K + bc0 + e] = bacc[e];
+    }
+    // slab[row-set][K * N (+ K column sums of dZ)]
+    float* dst = wg.slab + (size_t)by_u * wg.slab_stride;
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+      for (int y = 0; y < 2; ++y)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int n = qn * 64 + x * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+          const int k = qk * 64 + y * 32 + l31;
+          dst[(size_t)n * N + k] = wacc[x][y][i];
+        }
+  } else {
+    if constexpr (MODE == 3) fetch_idx(t0);
+    fetch(t0);
+    stage(t0, 0);
+    fetch(t0 + GY);
+    __syncthreads();
+    const int yvo = ((4 * h) * N + wn * 32 + l31) * 4;     // C/D map: col = lane&31, row = (i&3) + 8*(i>>2) + 4*(lane>>5)
+    auto tile_body = [&](int64_t tt, int buf) __attribute__((always_inline)) {
+      const int rows = rows_of(tt);
+      const __amdgpu_buffer_rsrc_t xs = __builtin_amdgcn_make_buffer_rsrc(
+          DX + (size_t)(rows ? tt : 0) * BM * N, 0, rows * N * 4, 0x00020000);
+      f32x16 acc;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+      stage(tt + GY, buf ^ 1);                   // the other buffer: its readers passed the barrier of the last tile
+      fetch(tt + 2 * GY);
+      float nby[NBN ? 16 : 1];
+      if constexpr (NBN) next_bn_load(nb, tt, rows, N, 0, yvo, nby);   // in flight under the products
+      __builtin_amdgcn_sched_barrier(0);         // keep the fetch ahead of the matrix loop
+      const __bf16* ap = planes + (size_t)buf * 3 * BM * LDP + l31 * LDP + 8 * h;
+#pragma unroll
+      for (int ks = 0; ks < NK; ++ks) {
+        const xbf16x8 a1f = *reinterpret_cast<const xbf16x8*>(ap + ks * 16);
+        const xbf16x8 a2f = *reinterpret_cast<const xbf16x8*>(ap + BM * LDP + ks * 16);
+        const xbf16x8 a3f = *reinterpret_cast<const xbf16x8*>(ap + 2 * BM * LDP + ks * 16);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3f, wb[ks][0], acc, 0, 0, 0);   // small terms first
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1f, wb[ks][2], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2f, wb[ks][1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2f, wb[ks][0], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1f, wb[ks][1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1f, wb[ks][0], acc, 0, 0, 0);
+      }
+      float vv[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        vv[i] = acc[i];                        // (a bit_cast straight from the vector element stored element 0 sixteen times)
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[i]), xs, yvo, ((i & 3) + 8 * (i >> 2)) * N * 4,
+                                              MMG_NT_ST);
+      }
+      if constexpr (NBN) next_bn_tile(nb, nbc, vv, nby, rows, tt * BM, N, col, lane, cs1, cs2);
+      __syncthreads();                         // buf fully read, buf^1 fully written
+    };
+    tile_body(t0, 0);
+    tile_body(t0 + GY, 1);
+    for (int i = 2; i < n_my; i += 2) {
+      tile_body(t0 + (int64_t)i * GY, 0);
+      tile_body(t0 + (int64_t)(i + 1) * GY, 1);
+    }
+    if constexpr (NBN) {
+      // two partials per column (the lane halves) -> one: partial[row-set][2][N], fixed order
+      double* red = reinterpret_cast<double*>(planes);          // the planes are dead: every wave passed the last barrier
+      red[(h * 2 + 0) * N + col] = cs1;
+      red[(h * 2 + 1) * N + col] = cs2;
+      __syncthreads();
+      for (int e = tid; e < 2 * N; e += NTHR) {
+        const int which = e / N, cc = e % N;
+        stat_partial[((size_t)by_u * 2 + which) * N + cc] = red[which * N + cc] + red[(2 + which) * N + cc];
+      }
+    }
+  }
+  if constexpr (FW) {
+    __syncthreads();                           // the partial column sums of dZ are in LDS
+    const int cc = tid - NTHR;
+    if (xrole && cc < K && wg.slab_stride > (int64_t)K * N) {
+      const float* red = reinterpret_cast<const float*>(planes + 2 * 3 * BM * LDP);
+      float v;
+      if (wg.bias_order == 0) {
+        v = ((red[cc] + red[K + cc]) + red[2 * K + cc]) + red[3 * K + cc];
+      } else {
+        v = 0.f;
+#pragma unroll
+        for (int qq = 0; qq < 16; ++qq) v += red[qq * K + cc];
+      }
+      wg.slab[(size_t)by_u * wg.slab_stride + (size_t)K * N + cc] = v;
     }
   }
 }
@@ -978,7 +1183,7 @@ int launch_bnbwd_x6(const float* G, const BnBwdDev& bb, const ProDev& pr, const 
   MMG_CHECK_HIP((MmgMaxLds<&k_linear_bnbwd_x6<K, WN, MODE, NBN>, lds>::set()), "linear_bnbwd(attr)");
   MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, N, K, (MODE == 1 ? 64 : (MODE == 2 ? 16 | 128 : (MODE == 3 ? 16 | 256 : 16))) | (NBN ? 512 : 0),
              (k_linear_bnbwd_x6<K, WN, MODE, NBN>), dim3(1u, (unsigned)gy),
-             dim3(64 * WN), lds, st, G, bb, pr, W, DX, M, pr2, nb, stat_partial);
+             dim3(64 * WN), lds, st, G, bb, pr, W, DX, M, pr2, nb, stat_partial, bn_wg_none());
   return 0;
 }
 
@@ -1057,15 +1262,6 @@ constexpr int WG_ROWS = 32;   // rows reduced per LDS stage
 // through the gfx950 transposing LDS read (ds_read_b64_tr_b16: a 16-lane group fetches 4 rows x 16 columns and
 // each lane receives 4 consecutive rows of ITS column).  Row stride = tile bytes + 64: the 4 rows of a group then
 // sit on 4 disjoint 16-bank spans (conflict-free).  32-row stages, double-buffered, one barrier per stage.
-typedef short xs16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ xbf16x8 tr_frag(const __bf16* p, int row_stride) {   // rows +0..3 and +4..7 of this lane's column
-  const xs16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) xs16x4*)p);
-  const xs16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) xs16x4*)(p + 4 * row_stride));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(xbf16x8, v);
-}
 
 template <int TN, int TK, int WNN, int WNK, bool PRO>      // WNN x WNK waves over the [TN, TK] output tile
 __global__ __launch_bounds__(64 * WNN * WNK) void k_linear_wgrad_x6(const float* __restrict__ dY, const float* __restrict__ X,
@@ -1484,6 +1680,22 @@ WgradPlan plan_wgrad(int64_t M, int N, int K) {
   return p;
 }
 
+// the FW form (K = N = 128): grid.y = plan_wgrad's n_split, one eight-wave workgroup per CU
+inline int64_t bnbwd_fw_rows(int64_t M) { return plan_wgrad(M, 128, 128).n_split; }
+
+template <int MODE>
+int launch_bnbwd_fw(const float* G, const BnBwdDev& bb, const ProDev& pr, const ProDev& pr2, const float* W, float* DX,
+                    int64_t M, const BnWgDev& wg, hipStream_t st) {
+  constexpr int K = 128, N = 128;
+  const int64_t gy = bnbwd_fw_rows(M);
+  constexpr int lds = 2 * 3 * 32 * (K + 8) * 2 + 2 * 3 * 32 * (N + 32) * 2;    // dZ planes + X planes: 111 KB
+  MMG_CHECK_HIP((MmgMaxLds<&k_linear_bnbwd_x6<K, 4, MODE, false, true>, lds>::set()), "linear_bnbwd_wgrad(attr)");
+  MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, N, K, (MODE == 1 ? 64 : (MODE == 2 ? 16 | 128 : (MODE == 3 ? 16 | 256 : 16))) | 1024,
+             (k_linear_bnbwd_x6<K, 4, MODE, false, true>), dim3(1u, (unsigned)gy), dim3(512), lds, st, G, bb, pr, W, DX, M,
+             pr2, next_bn_none(), nullptr, wg);
+  return 0;
+}
+
 template <int K>
 int launch_small(const float* X, const ProDev& pr, const float* W, const float* bias, float* Y, int64_t M, int N,
                  int accumulate, hipStream_t st) {
@@ -1700,6 +1912,56 @@ extern "C" int mmg_linear_bnbwd_supported(int64_t M, int N, int K) {
   return (M > 512 && (K == 64 || K == 128) && (N == 64 || N == 128)) ? 1 : 0;
 }
 
+extern "C" int mmg_linear_bnbwd_wgrad_supported(int64_t M, int N, int K) {
+  return (mmg_linear_bnbwd_supported(M, N, K) && N == 128 && K == 128) ? 1 : 0;
+}
+
+extern "C" size_t mmg_linear_bnbwd_wgrad_ws_bytes(int64_t M, int N, int K) {
+  return mmg_linear_wgrad_ws_bytes(M, K, N);            // the slabs of the separate weight gradient of dZ [M, K], X [M, N]
+}
+
+// the FW launch of one mode (k_linear_bnbwd_x6<128, 4, MODE, NBN, true>): the weight-gradient descriptor, the next
+// BatchNorm's statistics (fused, or the separate pass over dX), the slab sum (deferred to wg->job, or now)
+template <int MODE>
+static int bnbwd_wgrad_run(const float* G, const BnBwdDev& bb, const ProDev& pr, const ProDev& pr2, const float* W, float* dX,
+                           int64_t M, const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, const char* what,
+                           hipStream_t st) {
+  constexpr int N = 128, K = 128;
+  mmg_wgrad_reduce_t* job = wg->job;
+  if (job) { job->slab = nullptr; job->n4 = 0; job->n_split = 0; job->dW = wg->dW; job->dbias = wg->dbias; job->nk4 = (int64_t)K * N / 4; job->accumulate = wg->accumulate; }
+  MMG_CHECK_ARG(wg->X && wg->dW && wg->ws, "%s: null weight-gradient buffer", what);
+  MMG_CHECK_ARG(!wg->pro || wg->pro->relu == MMG_ACT_NONE || wg->pro->relu == MMG_ACT_RELU, "%s: the X prologue takes relu only", what);
+  MMG_CHECK_ARG(!wg->pro || !wg->pro->scale || wg->pro->shift, "%s: X prologue: scale without shift", what);
+  const size_t need = mmg_linear_bnbwd_wgrad_ws_bytes(M, N, K);
+  if (wg->ws_bytes < need) {
+    mmg_set_error("%s: weight-gradient workspace %zu < %zu", what, wg->ws_bytes, need);
+    return MMG_E_WS;
+  }
+  float* slab = (float*)(((uintptr_t)wg->ws + 255) & ~(uintptr_t)255);
+  const int64_t stride = (int64_t)K * N + (wg->dbias ? K : 0);
+  const int n_split = (int)bnbwd_fw_rows(M);
+  const ProDev xpr = mmg_pro_dev(wg->pro);
+  // the column sums of dZ in the order of the kernel linear_wgrad runs for this X (see linear_wgrad_impl)
+  const BnWgDev wd{wg->X, xpr, slab, stride, (xpr.scale || xpr.relu || xpr.p > 0.f) ? 1 : 0};
+  // the next BatchNorm's statistics always come from the separate pass over dX: the epilogue that sums them does not fit
+  // beside the dW waves (k_linear_bnbwd_x6<128, 4, MODE, true, true> spills 124..220 B per lane at the 256-register budget
+  // of two waves per SIMD, which the plain NBN instances already exceed by 40..136 B)
+  int rc = launch_bnbwd_fw<MODE>(G, bb, pr, pr2, W, dX, M, wd, st);
+  if (rc) return rc;
+  MMG_CHECK_LAUNCH(what);
+  rc = next ? mmg_next_bn_fallback(dX, M, N, next, what, st) : MMG_OK;
+  if (rc) return rc;
+  if (job) {                        // the caller sums the slabs later, together with those of other layers
+    job->slab = slab; job->n4 = stride / 4; job->n_split = n_split;
+  } else {
+    MMG_LAUNCH(MMG_PROBE_LINEAR_WGRAD_REDUCE, M, K, N, 0, (mmg_k_reduce_slabs<EpiStore>),
+               dim3((unsigned)((stride / 4 + 15) / 16)), dim3(256), 0, st, slab, stride / 4, n_split,
+               EpiStore{wg->dW, wg->accumulate, wg->dbias, (int64_t)K * N / 4});
+    MMG_CHECK_LAUNCH(what);
+  }
+  return MMG_OK;
+}
+
 extern "C" int mmg_linear_bnbwd_next_bn(const float* G, const float* Y, const mmg_prologue_t* pro, const float* mean,
                                         const float* rstd, const double* sums, double inv_count, float* dbeta, float* dgamma,
                                         const float* W, float* dZ, float* dX, int64_t M, int N, int K,
@@ -1711,19 +1973,21 @@ extern "C" int mmg_linear_bnbwd(const float* G, const float* Y, const mmg_prolog
   return mmg_linear_bnbwd_next_bn(G, Y, pro, mean, rstd, sums, inv_count, dbeta, dgamma, W, dZ, dX, M, N, K, nullptr, stream);
 }
 
-extern "C" int mmg_linear_bnbwd_next_bn(const float* G, const float* Y, const mmg_prologue_t* pro, const float* mean,
-                                        const float* rstd, const double* sums, double inv_count, float* dbeta, float* dgamma,
-                                        const float* W, float* dZ, float* dX, int64_t M, int N, int K,
-                                        const mmg_next_bn_t* next, void* stream) {
+static int linear_bnbwd_impl(const float* G, const float* Y, const mmg_prologue_t* pro, const float* mean,
+                             const float* rstd, const double* sums, double inv_count, float* dbeta, float* dgamma,
+                             const float* W, float* dZ, float* dX, int64_t M, int N, int K,
+                             const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, void* stream) {
   MMG_CHECK_ARG(mmg_linear_bnbwd_supported(M, N, K), "linear_bnbwd: M=%lld N=%d K=%d unsupported (M > 512, K and N in {64,128})",
                 (long long)M, N, K);
-  MMG_CHECK_ARG(G && Y && W && dZ && dX, "linear_bnbwd: null buffer");
+  MMG_CHECK_ARG(!wg || (K == 128 && N == 128), "linear_bnbwd_wgrad: N=%d K=%d unsupported (K = N = 128)", N, K);
+  MMG_CHECK_ARG(G && Y && W && (dZ || wg) && dX, "linear_bnbwd: null buffer");
   MMG_CHECK_ARG(!pro || !pro->scale || (pro->shift && mean && rstd), "linear_bnbwd: BatchNorm fold without shift / mean / rstd");
   MMG_CHECK_ARG(!pro || pro->relu == MMG_ACT_NONE || pro->relu == MMG_ACT_RELU, "linear_bnbwd: relu only");
   MMG_CHECK_ARG(!sums || (pro && pro->scale), "linear_bnbwd: sums without a BatchNorm fold");
   const ProDev pr = mmg_pro_dev(pro);
   BnBwdDev bb{Y, mean, rstd, sums, inv_count, dZ, dbeta, dgamma, 0.f, nullptr, nullptr, 0};
   hipStream_t st = (hipStream_t)stream;
+  if (wg) return bnbwd_wgrad_run<0>(G, bb, pr, mmg_pro_dev(nullptr), W, dX, M, next, wg, "linear_bnbwd_wgrad", st);
   int rc;
   if (next && K == 128 && N == 128 && next_bn_fusable(next)) {
     NextBnDev nb;
@@ -1742,22 +2006,54 @@ extern "C" int mmg_linear_bnbwd_next_bn(const float* G, const float* Y, const mm
   return next ? mmg_next_bn_fallback(dX, M, N, next, "linear_bnbwd", stream) : MMG_OK;
 }
 
-extern "C" int mmg_linear_bnbwd2(const float* G, const float* G2, const float* Y, const mmg_prologue_t* pro,
-                                 const mmg_prologue_t* pro2, const float* mean, const float* rstd, const double* sums,
-                                 double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ, float* dX,
-                                 int64_t M, int N, int K, void* stream) {
+extern "C" int mmg_linear_bnbwd_next_bn(const float* G, const float* Y, const mmg_prologue_t* pro, const float* mean,
+                                        const float* rstd, const double* sums, double inv_count, float* dbeta, float* dgamma,
+                                        const float* W, float* dZ, float* dX, int64_t M, int N, int K,
+                                        const mmg_next_bn_t* next, void* stream) {
+  return linear_bnbwd_impl(G, Y, pro, mean, rstd, sums, inv_count, dbeta, dgamma, W, dZ, dX, M, N, K, next, nullptr, stream);
+}
+
+extern "C" int mmg_linear_bnbwd_wgrad(const float* G, const float* Y, const mmg_prologue_t* pro, const float* mean,
+                                      const float* rstd, const double* sums, double inv_count, float* dbeta, float* dgamma,
+                                      const float* W, float* dZ, float* dX, int64_t M, int N, int K,
+                                      const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, void* stream) {
+  MMG_CHECK_ARG(wg, "linear_bnbwd_wgrad: null weight-gradient descriptor");
+  return linear_bnbwd_impl(G, Y, pro, mean, rstd, sums, inv_count, dbeta, dgamma, W, dZ, dX, M, N, K, next, wg, stream);
+}
+
+static int linear_bnbwd2_impl(const float* G, const float* G2, const float* Y, const mmg_prologue_t* pro,
+                              const mmg_prologue_t* pro2, const float* mean, const float* rstd, const double* sums,
+                              double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ, float* dX,
+                              int64_t M, int N, int K, const mmg_bnbwd_wgrad_t* wg, void* stream) {
   MMG_CHECK_ARG(mmg_linear_bnbwd_supported(M, N, K) && K == 128 && N == 128,
                 "linear_bnbwd2: M=%lld N=%d K=%d unsupported (M > 512, K = N = 128)", (long long)M, N, K);
-  MMG_CHECK_ARG(G && G2 && Y && W && dZ && dX && pro && pro2, "linear_bnbwd2: null buffer");
+  MMG_CHECK_ARG(G && G2 && Y && W && (dZ || wg) && dX && pro && pro2, "linear_bnbwd2: null buffer");
   MMG_CHECK_ARG(!pro->scale || (pro->shift && mean && rstd), "linear_bnbwd2: BatchNorm fold without shift / mean / rstd");
   MMG_CHECK_ARG(pro->relu == MMG_ACT_NONE || pro->relu == MMG_ACT_RELU, "linear_bnbwd2: relu only");
   MMG_CHECK_ARG(!sums || pro->scale, "linear_bnbwd2: sums without a BatchNorm fold");
   const ProDev pr = mmg_pro_dev(pro), pr2 = mmg_pro_dev(pro2);
   BnBwdDev bb{Y, mean, rstd, sums, inv_count, dZ, dbeta, dgamma, 0.f, G2, nullptr, 0};
+  if (wg) return bnbwd_wgrad_run<2>(G, bb, pr, pr2, W, dX, M, nullptr, wg, "linear_bnbwd2_wgrad", (hipStream_t)stream);
   int rc = launch_bnbwd_x6<128, 4, 2>(G, bb, pr, W, dX, M, (hipStream_t)stream, pr2);
   if (rc) return rc;
   MMG_CHECK_LAUNCH("linear_bnbwd2");
   return MMG_OK;
+}
+
+extern "C" int mmg_linear_bnbwd2(const float* G, const float* G2, const float* Y, const mmg_prologue_t* pro,
+                                 const mmg_prologue_t* pro2, const float* mean, const float* rstd, const double* sums,
+                                 double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ, float* dX,
+                                 int64_t M, int N, int K, void* stream) {
+  return linear_bnbwd2_impl(G, G2, Y, pro, pro2, mean, rstd, sums, inv_count, dbeta, dgamma, W, dZ, dX, M, N, K, nullptr,
+                            stream);
+}
+
+extern "C" int mmg_linear_bnbwd2_wgrad(const float* G, const float* G2, const float* Y, const mmg_prologue_t* pro,
+                                       const mmg_prologue_t* pro2, const float* mean, const float* rstd, const double* sums,
+                                       double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ, float* dX,
+                                       int64_t M, int N, int K, const mmg_bnbwd_wgrad_t* wg, void* stream) {
+  MMG_CHECK_ARG(wg, "linear_bnbwd2_wgrad: null weight-gradient descriptor");
+  return linear_bnbwd2_impl(G, G2, Y, pro, pro2, mean, rstd, sums, inv_count, dbeta, dgamma, W, dZ, dX, M, N, K, wg, stream);
 }
 
 extern "C" int mmg_linear_bnbwd_rows_next_bn(const float* G_rows, const int32_t* row_pos, int64_t n_sel, const float* Y,
@@ -1774,20 +2070,23 @@ extern "C" int mmg_linear_bnbwd_rows(const float* G_rows, const int32_t* row_pos
                                        N, K, nullptr, stream);
 }
 
-extern "C" int mmg_linear_bnbwd_rows_next_bn(const float* G_rows, const int32_t* row_pos, int64_t n_sel, const float* Y,
-                                             const mmg_prologue_t* pro, const float* mean, const float* rstd,
-                                             const double* sums, double inv_count, float* dbeta, float* dgamma, const float* W,
-                                             float* dZ, float* dX, int64_t M, int N, int K, const mmg_next_bn_t* next,
-                                             void* stream) {
+static int linear_bnbwd_rows_impl(const float* G_rows, const int32_t* row_pos, int64_t n_sel, const float* Y,
+                                  const mmg_prologue_t* pro, const float* mean, const float* rstd,
+                                  const double* sums, double inv_count, float* dbeta, float* dgamma, const float* W,
+                                  float* dZ, float* dX, int64_t M, int N, int K, const mmg_next_bn_t* next,
+                                  const mmg_bnbwd_wgrad_t* wg, void* stream) {
   MMG_CHECK_ARG(mmg_linear_bnbwd_supported(M, N, K) && K == 128 && N == 128,
                 "linear_bnbwd_rows: M=%lld N=%d K=%d unsupported (M > 512, K = N = 128)", (long long)M, N, K);
-  MMG_CHECK_ARG(Y && W && dZ && dX && pro && row_pos, "linear_bnbwd_rows: null buffer");
+  MMG_CHECK_ARG(Y && W && (dZ || wg) && dX && pro && row_pos, "linear_bnbwd_rows: null buffer");
   MMG_CHECK_ARG(n_sel >= 0 && n_sel * (int64_t)K * 4 < (int64_t)0x7FFFFFFF && (G_rows || n_sel == 0), "linear_bnbwd_rows: bad row list");
   MMG_CHECK_ARG(!pro->scale || (pro->shift && mean && rstd), "linear_bnbwd_rows: BatchNorm fold without shift / mean / rstd");
   MMG_CHECK_ARG(pro->relu == MMG_ACT_NONE || pro->relu == MMG_ACT_RELU, "linear_bnbwd_rows: relu only");
   MMG_CHECK_ARG(!sums || pro->scale, "linear_bnbwd_rows: sums without a BatchNorm fold");
   const ProDev pr = mmg_pro_dev(pro);
   BnBwdDev bb{Y, mean, rstd, sums, inv_count, dZ, dbeta, dgamma, 0.f, nullptr, row_pos, n_sel};
+  if (wg)
+    return bnbwd_wgrad_run<3>(G_rows ? G_rows : Y, bb, pr, mmg_pro_dev(nullptr), W, dX, M, next, wg, "linear_bnbwd_rows_wgrad",
+                              (hipStream_t)stream);
   if (next && next_bn_fusable(next)) {
     NextBnDev nb;
     double* partial;
@@ -1804,6 +2103,25 @@ extern "C" int mmg_linear_bnbwd_rows_next_bn(const float* G_rows, const int32_t*
   return next ? mmg_next_bn_fallback(dX, M, N, next, "linear_bnbwd_rows", stream) : MMG_OK;
 }
 
+extern "C" int mmg_linear_bnbwd_rows_next_bn(const float* G_rows, const int32_t* row_pos, int64_t n_sel, const float* Y,
+                                             const mmg_prologue_t* pro, const float* mean, const float* rstd,
+                                             const double* sums, double inv_count, float* dbeta, float* dgamma, const float* W,
+                                             float* dZ, float* dX, int64_t M, int N, int K, const mmg_next_bn_t* next,
+                                             void* stream) {
+  return linear_bnbwd_rows_impl(G_rows, row_pos, n_sel, Y, pro, mean, rstd, sums, inv_count, dbeta, dgamma, W, dZ, dX, M, N, K,
+                                next, nullptr, stream);
+}
+
+extern "C" int mmg_linear_bnbwd_rows_wgrad(const float* G_rows, const int32_t* row_pos, int64_t n_sel, const float* Y,
+                                           const mmg_prologue_t* pro, const float* mean, const float* rstd,
+                                           const double* sums, double inv_count, float* dbeta, float* dgamma, const float* W,
+                                           float* dZ, float* dX, int64_t M, int N, int K, const mmg_next_bn_t* next,
+                                           const mmg_bnbwd_wgrad_t* wg, void* stream) {
+  MMG_CHECK_ARG(wg, "linear_bnbwd_rows_wgrad: null weight-gradient descriptor");
+  return linear_bnbwd_rows_impl(G_rows, row_pos, n_sel, Y, pro, mean, rstd, sums, inv_count, dbeta, dgamma, W, dZ, dX, M, N, K,
+                                next, wg, stream);
+}
+
 extern "C" int mmg_linear_l2bwd_next_bn(const float* G, const float* out, const float* rnorm, const float* W, float* dZ,
                                         float* dX, int64_t M, int N, int K, float eps, const mmg_next_bn_t* next, void* stream);
 
@@ -1812,14 +2130,17 @@ extern "C" int mmg_linear_l2bwd(const float* G, const float* out, const float* r
   return mmg_linear_l2bwd_next_bn(G, out, rnorm, W, dZ, dX, M, N, K, eps, nullptr, stream);
 }
 
-extern "C" int mmg_linear_l2bwd_next_bn(const float* G, const float* out, const float* rnorm, const float* W, float* dZ,
-                                        float* dX, int64_t M, int N, int K, float eps, const mmg_next_bn_t* next, void* stream) {
+static int linear_l2bwd_impl(const float* G, const float* out, const float* rnorm, const float* W, float* dZ, float* dX,
+                             int64_t M, int N, int K, float eps, const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg,
+                             void* stream) {
   MMG_CHECK_ARG(mmg_linear_bnbwd_supported(M, N, K), "linear_l2bwd: M=%lld N=%d K=%d unsupported (M > 512, K and N in {64,128})",
                 (long long)M, N, K);
-  MMG_CHECK_ARG(G && out && rnorm && W && dZ && dX, "linear_l2bwd: null buffer");
+  MMG_CHECK_ARG(!wg || (K == 128 && N == 128), "linear_l2bwd_wgrad: N=%d K=%d unsupported (K = N = 128)", N, K);
+  MMG_CHECK_ARG(G && out && rnorm && W && (dZ || wg) && dX, "linear_l2bwd: null buffer");
   const ProDev pr = mmg_pro_dev(nullptr);
   BnBwdDev bb{out, rnorm, nullptr, nullptr, 0.0, dZ, nullptr, nullptr, eps, nullptr, nullptr, 0};
   hipStream_t st = (hipStream_t)stream;
+  if (wg) return bnbwd_wgrad_run<1>(G, bb, pr, mmg_pro_dev(nullptr), W, dX, M, next, wg, "linear_l2bwd_wgrad", st);
   int rc;
   if (next && K == 128 && N == 128 && next_bn_fusable(next)) {
     NextBnDev nb;
@@ -1836,6 +2157,18 @@ extern "C" int mmg_linear_l2bwd_next_bn(const float* G, const float* out, const 
   if (rc) return rc;
   MMG_CHECK_LAUNCH("linear_l2bwd");
   return next ? mmg_next_bn_fallback(dX, M, N, next, "linear_l2bwd", stream) : MMG_OK;
+}
+
+extern "C" int mmg_linear_l2bwd_next_bn(const float* G, const float* out, const float* rnorm, const float* W, float* dZ,
+                                        float* dX, int64_t M, int N, int K, float eps, const mmg_next_bn_t* next, void* stream) {
+  return linear_l2bwd_impl(G, out, rnorm, W, dZ, dX, M, N, K, eps, next, nullptr, stream);
+}
+
+extern "C" int mmg_linear_l2bwd_wgrad(const float* G, const float* out, const float* rnorm, const float* W, float* dZ,
+                                      float* dX, int64_t M, int N, int K, float eps, const mmg_next_bn_t* next,
+                                      const mmg_bnbwd_wgrad_t* wg, void* stream) {
+  MMG_CHECK_ARG(wg, "linear_l2bwd_wgrad: null weight-gradient descriptor");
+  return linear_l2bwd_impl(G, out, rnorm, W, dZ, dX, M, N, K, eps, next, wg, stream);
 }
 
 extern "C" size_t mmg_linear_wgrad_ws_bytes(int64_t M, int N, int K) {

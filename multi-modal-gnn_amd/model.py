@@ -67,6 +67,18 @@ def set_next_bn(sites):
     NEXT_BN_SITES = sites
 
 
+# The weight gradient of a layer whose data gradient comes out of a BatchNorm-backward GEMM (ops.linear_bnbwd*,
+# ops.linear_l2bwd) rides in the same launch (ops.FusedWgrad) instead of a second kernel that reads dz back: the GNN
+# patient self-loop and the encoder's three linears.  set_fused_wgrad(False) restores the separate ops.linear_wgrad.
+FUSED_WGRAD = True
+
+
+def set_fused_wgrad(on: bool):
+    """True (default) | False -- see FUSED_WGRAD (the tests switch it)."""
+    global FUSED_WGRAD
+    FUSED_WGRAD = bool(on)
+
+
 def _mangle(et: EdgeType) -> str:
     return "<" + "___".join(et) + ">"
 
@@ -405,6 +417,7 @@ class _Run:
         mode = ex.get("overlap") or OVERLAP_MODE
         self.next_bn_sites = ex["next_bn"] if ex.get("next_bn") is not None else NEXT_BN_SITES
         self.save_pair_state = ex["save_pair_state"] if ex.get("save_pair_state") is not None else SAVE_PAIR_STATE
+        self.fused_wgrad = FUSED_WGRAD
         self.overlap = mode == "on" or (mode == "auto" and self.plan.n_rows >= 16384)
         if self.overlap:
             if getattr(model, "_side_stream", None) is None:
@@ -742,11 +755,12 @@ class _Run:
         return dy
 
     def bn_lin_bwd(self, g, y, pro: Pro, fold: Optional[ops.BNFold], bn_prefix: Optional[str], sharded: bool, sums, W,
-                   nxt: Optional[Tuple["_NextStats", Pro]] = None):
+                   nxt: Optional[Tuple["_NextStats", Pro]] = None, wgrad: Optional[ops.FusedWgrad] = None):
         """bn_bwd followed by the data gradient  dz @ W  through the linear in front of that BatchNorm, as ONE kernel
         (mmg_linear_bnbwd: g and y are read once, dz is written once for the weight gradient).  -> (dz, dx), or None where
         the fused kernel does not apply (the caller then runs bn_bwd and the GEMM).
-        nxt = (stats holder, prologue) of the BatchNorm below, whose backward consumes dx: its statistics ride along."""
+        nxt = (stats holder, prologue) of the BatchNorm below, whose backward consumes dx: its statistics ride along.
+        wgrad: the weight gradient of that linear in the same launch (ops.FusedWgrad; only used where the result is not None)."""
         if g is None or pro.relu not in (0, 1) or not ops.linear_bnbwd_supported(y.shape[0], W.shape[1], y.shape[1]):
             return None
         nb = nxt[0].next(nxt[1]) if nxt is not None else None
@@ -757,15 +771,15 @@ class _Run:
             return out[0], out[1]
 
         if fold is None:
-            return done(ops.linear_bnbwd(g, y, pro, None, W, next_bn=nb))
+            return done(ops.linear_bnbwd(g, y, pro, None, W, next_bn=nb, wgrad=wgrad))
         if sums is None:
             sums = self.bn_bwd_sums(g, y, pro, fold, sharded)
         dbg = torch.empty(2, y.shape[1], device=y.device)       # d beta | d gamma, written by the kernel
         if fold.training:
-            out = ops.linear_bnbwd(g, y, pro, fold, W, sums, fold.count, dbg[0], dbg[1], next_bn=nb)
+            out = ops.linear_bnbwd(g, y, pro, fold, W, sums, fold.count, dbg[0], dbg[1], next_bn=nb, wgrad=wgrad)
         else:
             dbg.copy_(sums)
-            out = ops.linear_bnbwd(g, y, pro, fold, W, next_bn=nb)
+            out = ops.linear_bnbwd(g, y, pro, fold, W, next_bn=nb, wgrad=wgrad)
         self.acc(bn_prefix + ".bias", dbg[0])
         self.acc(bn_prefix + ".weight", dbg[1])
         return done(out)
@@ -790,6 +804,27 @@ class _Run:
             return ops.linear_fwd(dy, self.W(wname), w_kn=True)          # dX = dY . W, W read in place
         return None
 
+    def fused_wgrad_for(self, x, pro, wname, bname, keep_dz, M, N, K, next_bn=False) -> Optional[ops.FusedWgrad]:
+        """The weight gradient lin_bwd(dz, x, pro, wname, bname, need_dx=False) would compute, as an ops.FusedWgrad for the
+        GEMM that produces dz [M, K] (the linear maps N -> K); None where that form does not apply.
+        next_bn: the GEMM also takes the next BatchNorm's statistics in its epilogue.  The fused kernel has no room for that
+        epilogue (the statistics would come from a separate pass over dx), and at the x100 shape that pass costs more than
+        the fused weight gradient saves (L2 backward: 96.7 + 56.1 us separate, 112.0 + 45.9 fused + pass): not taken."""
+        if next_bn or not self.fused_wgrad or not ops.linear_bnbwd_wgrad_supported(M, N, K):
+            return None
+        gw = self.grads.get(wname)
+        if bname is not None:
+            gb = self.grads.get(bname)
+            both = gw is not None and gb is not None
+            return ops.FusedWgrad(x, pro, out=gw if both else None, accumulate=both, with_bias=True,
+                                  bias_out=gb if both else None, defer=self.wgrad_jobs, keep_dz=keep_dz)
+        return ops.FusedWgrad(x, pro, out=gw, accumulate=gw is not None, defer=self.wgrad_jobs, keep_dz=keep_dz)
+
+    def fused_wgrad_done(self, fw: ops.FusedWgrad, wname, bname, partial=False):
+        self.acc(wname, fw.dW, partial)
+        if bname is not None:
+            self.acc(bname, fw.db, partial)
+
     def enc_bwd_a(self, enc, g_x0):
         """Backward of one encoder pass down to the statistics of its last BatchNorm (local sums, not yet all-reduced):
         -> (upstream gradient of that BatchNorm [dense, or the listed rows], fp64 sums) or None."""
@@ -804,14 +839,21 @@ class _Run:
             sums = ops.bn_bwd_stats_rows(g, enc["z2"], rows, enc["pro2"], enc["f2"])
         else:
             # the statistics of the second BatchNorm's backward come out of the epilogue of the GEMM that produces its
-            # upstream gradient (the separate pass read g and z2 once more)
+            # upstream gradient (the separate pass read g and z2 once more); the weight gradient of the third linear
+            # rides in the same launch where it can (dz3 is then never written)
+            W8 = self.W(f"{pt}.8.weight")
+            fw = self.fused_wgrad_for(enc["z2"], enc["pro2"], f"{pt}.8.weight", f"{pt}.8.bias", False,
+                                      enc["x0"].shape[0], W8.shape[1], W8.shape[0], next_bn="enc2" in self.next_bn_sites)
             if "enc2" in self.next_bn_sites:
-                dz3, g, sums = ops.linear_l2bwd(g_x0.contiguous(), enc["x0"], enc["rn"], self.W(f"{pt}.8.weight"),
-                                                next_bn=ops.NextBN(enc["z2"], enc["pro2"], enc["f2"]))
+                dz3, g, sums = ops.linear_l2bwd(g_x0.contiguous(), enc["x0"], enc["rn"], W8,
+                                                next_bn=ops.NextBN(enc["z2"], enc["pro2"], enc["f2"]), wgrad=fw)
             else:
-                dz3, g = ops.linear_l2bwd(g_x0.contiguous(), enc["x0"], enc["rn"], self.W(f"{pt}.8.weight"))
+                dz3, g = ops.linear_l2bwd(g_x0.contiguous(), enc["x0"], enc["rn"], W8, wgrad=fw)
                 sums = ops.bn_bwd_stats(g, enc["z2"], enc["pro2"], enc["f2"])
-            self.lin_bwd(dz3, enc["z2"], enc["pro2"], f"{pt}.8.weight", f"{pt}.8.bias", need_dx=False, partial=True)
+            if fw is not None:
+                self.fused_wgrad_done(fw, f"{pt}.8.weight", f"{pt}.8.bias", partial=True)
+            else:
+                self.lin_bwd(dz3, enc["z2"], enc["pro2"], f"{pt}.8.weight", f"{pt}.8.bias", need_dx=False, partial=True)
         return g, sums
 
     def enc_bwd_b(self, enc, state, nstats: Optional["_NextStats"] = None):
@@ -830,26 +872,38 @@ class _Run:
             W4 = self.W(f"{pt}.4.weight")
             if enc.get("row_pos") is not None and pro.relu in (0, 1) and fold.training and \
                     ops.linear_bnbwd2_supported(y.shape[0], W4.shape[1], y.shape[1]):
-                # dense pass, row patch and the data-gradient GEMM of the second linear in ONE kernel
+                # dense pass, row patch and the data-gradient GEMM of the second linear in ONE kernel (+ its weight gradient)
+                fw = self.fused_wgrad_for(enc["z1"], enc["pro1"], f"{pt}.4.weight", f"{pt}.4.bias", False,
+                                          y.shape[0], W4.shape[1], W4.shape[0], next_bn=nxt is not None)
                 if nxt is not None:
                     dz2, dx, nsums = ops.linear_bnbwd_rows(g, enc["row_pos"], y, pro, fold, W4, sums, fold.count, dbg[0], dbg[1],
-                                                           next_bn=nstats.next(enc["pro1"]))
+                                                           next_bn=nstats.next(enc["pro1"]), wgrad=fw)
                     nstats.took(nsums)
                 else:
-                    dz2, dx = ops.linear_bnbwd_rows(g, enc["row_pos"], y, pro, fold, W4, sums, fold.count, dbg[0], dbg[1])
+                    dz2, dx = ops.linear_bnbwd_rows(g, enc["row_pos"], y, pro, fold, W4, sums, fold.count, dbg[0], dbg[1],
+                                                    wgrad=fw)
                 self.acc(f"{pt}.5.bias", dbg[0])
                 self.acc(f"{pt}.5.weight", dbg[1])
-                self.lin_bwd(dz2, enc["z1"], enc["pro1"], f"{pt}.4.weight", f"{pt}.4.bias", need_dx=False, partial=True)
+                if fw is not None:
+                    self.fused_wgrad_done(fw, f"{pt}.4.weight", f"{pt}.4.bias", partial=True)
+                else:
+                    self.lin_bwd(dz2, enc["z1"], enc["pro1"], f"{pt}.4.weight", f"{pt}.4.bias", need_dx=False, partial=True)
                 return dx
             dz2 = ops.bn_bwd_apply(None, y, pro, fold, sums, fold.count, dbg[0], dbg[1])
             ops.bn_bwd_apply_rows(g, y, enc["rows"], pro, dz2)
             self.acc(f"{pt}.5.bias", dbg[0])
             self.acc(f"{pt}.5.weight", dbg[1])
         else:
-            fused = self.bn_lin_bwd(g, y, pro, fold, f"{pt}.5", True, sums, self.W(f"{pt}.4.weight"), nxt=nxt)
+            W4 = self.W(f"{pt}.4.weight")
+            fw = self.fused_wgrad_for(enc["z1"], enc["pro1"], f"{pt}.4.weight", f"{pt}.4.bias", False,
+                                      y.shape[0], W4.shape[1], W4.shape[0], next_bn=nxt is not None)
+            fused = self.bn_lin_bwd(g, y, pro, fold, f"{pt}.5", True, sums, W4, nxt=nxt, wgrad=fw)
             if fused is not None:                # BatchNorm backward inside the data-gradient GEMM of the second linear
                 dz2, dx = fused
-                self.lin_bwd(dz2, enc["z1"], enc["pro1"], f"{pt}.4.weight", f"{pt}.4.bias", need_dx=False, partial=True)
+                if fw is not None:
+                    self.fused_wgrad_done(fw, f"{pt}.4.weight", f"{pt}.4.bias", partial=True)
+                else:
+                    self.lin_bwd(dz2, enc["z1"], enc["pro1"], f"{pt}.4.weight", f"{pt}.4.bias", need_dx=False, partial=True)
                 return dx
             dz2 = self.bn_bwd(g, y, pro, fold, f"{pt}.5", sharded=True, sums=sums)
         return self.lin_bwd(dz2, enc["z1"], enc["pro1"], f"{pt}.4.weight", f"{pt}.4.bias", partial=True)
@@ -898,12 +952,17 @@ class _Run:
             ename, W0 = f"embeddings.{ROW_TYPE}.weight", self.W(f"{pt}.0.weight")
             if self.params[ename].requires_grad and ename not in self.grads and \
                     ops.linear_bnbwd2_supported(y.shape[0], W0.shape[1], y.shape[1]):
-                # the joint BatchNorm backward inside the data-gradient GEMM of the first linear (dE)
+                # the joint BatchNorm backward inside the data-gradient GEMM of the first linear (dE, + its weight gradient)
+                fw = self.fused_wgrad_for(enc_a["E"], None, f"{pt}.0.weight", f"{pt}.0.bias", False,
+                                          y.shape[0], W0.shape[1], W0.shape[0])
                 dz1, dE = ops.linear_bnbwd2(g_a, g_b, y, enc_a["pro1"], enc_b["pro1"], fold, W0, sums, fold.count,
-                                            dbg[0], dbg[1])
+                                            dbg[0], dbg[1], wgrad=fw)
                 self.acc(f"{pt}.1.bias", dbg[0])
                 self.acc(f"{pt}.1.weight", dbg[1])
-                self.lin_bwd(dz1, enc_a["E"], None, f"{pt}.0.weight", f"{pt}.0.bias", need_dx=False, partial=True)
+                if fw is not None:
+                    self.fused_wgrad_done(fw, f"{pt}.0.weight", f"{pt}.0.bias", partial=True)
+                else:
+                    self.lin_bwd(dz1, enc_a["E"], None, f"{pt}.0.weight", f"{pt}.0.bias", need_dx=False, partial=True)
                 self.acc(ename, dE)
                 return
             dz1 = ops.bn_bwd_apply2(g_a, g_b, y, enc_a["pro1"], enc_b["pro1"], fold, sums, fold.count, dbg[0], dbg[1])
@@ -1190,12 +1249,17 @@ class _Run:
 
         def patient_1(sums=None, reduce=True):
             """BN backward of the patient rows, their weight / data gradients, scatter of dy_P onto the vocab rows."""
-            gt, fused = g_out.get(ROW_TYPE), None
+            gt, fused, fw = g_out.get(ROW_TYPE), None, None
             if gt is not None and ROW_TYPE in y and rec["rin"] and g_in[ROW_TYPE] is None:
-                # BatchNorm backward inside the data-gradient GEMM of the self-loop weights (sum of the three lin_r)
+                # BatchNorm backward inside the data-gradient GEMM of the self-loop weights (sum of the three lin_r), with
+                # the weight gradient of that sum in the same launch (dy_P is still written: the scatter below reads it)
+                xP, Wsum = x[ROW_TYPE], rec["Wsum"]
+                if self.fused_wgrad and isinstance(xP, torch.Tensor) and xP.is_contiguous() and \
+                        ops.linear_bnbwd_wgrad_supported(xP.shape[0], Wsum.shape[1], Wsum.shape[0]):
+                    fw = ops.FusedWgrad(xP, None, with_bias=True, defer=self.wgrad_jobs, keep_dz=True)
                 fused = self.bn_lin_bwd(gt.contiguous(), y[ROW_TYPE], rec["pros"][ROW_TYPE], rec["folds"][ROW_TYPE],
                                         f"batch_norms.{l}.{ROW_TYPE}" if self.m.use_batch_norm else None, True, sums,
-                                        rec["Wsum"])
+                                        Wsum, wgrad=fw)
             if fused is not None:
                 dy[ROW_TYPE], g_in[ROW_TYPE] = fused
             else:
@@ -1204,7 +1268,10 @@ class _Run:
             if dyP is None or not rec["rin"]:
                 return None
             xP = x[ROW_TYPE]
-            dWsum, dbsum = ops.linear_wgrad(dyP, xP, with_bias=True, defer=self.wgrad_jobs)
+            if fused is not None and fw is not None:
+                dWsum, dbsum = fw.dW, fw.db
+            else:
+                dWsum, dbsum = ops.linear_wgrad(dyP, xP, with_bias=True, defer=self.wgrad_jobs)
             if fused is None:
                 add_dgrad(ROW_TYPE, dyP, rec["Wsum"])
             rels, dTs, off = [], [], 0

@@ -13,7 +13,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import _lib
-from ._lib import (BnFinT, HeadGradT, HeadT, NextBnT, PairSavedT, PrologueT, RelT, SmallBnBwdT, SmallBnT, SmallFwdT, SmallWgradT, SumJobT, WgradReduceT,
+from ._lib import (BnFinT, HeadGradT, HeadT, NextBnT, PairSavedT, PrologueT, RelT, SmallBnBwdT, SmallBnT, SmallFwdT, SmallWgradT, SumJobT, WgradReduceT, BnBwdWgradT,
                    check)
 
 BN_MOMENTUM = 0.1
@@ -626,17 +626,85 @@ def linear_bnbwd_supported(M: int, N: int, K: int) -> bool:
     return bool(_lib.load().mmg_linear_bnbwd_supported(int(M), int(N), int(K)))
 
 
+def linear_bnbwd_wgrad_supported(M: int, N: int, K: int) -> bool:
+    return bool(_lib.load().mmg_linear_bnbwd_wgrad_supported(int(M), int(N), int(K)))
+
+
+@dataclass
+class FusedWgrad:
+    """The weight gradient of the layer whose data gradient a linear_bnbwd / linear_bnbwd2 / linear_bnbwd_rows /
+    linear_l2bwd call computes, in the same launch (mmg_*_wgrad): out[K,N] (+)= dz^T @ pro(x), and with with_bias the
+    column sums of dz; the arguments mean what they mean for linear_wgrad(dz, x, pro, out, accumulate, with_bias, bias_out,
+    defer).  keep_dz=False: dz is not written (the call returns None in its place).  The call fills .dW and .db."""
+    x: torch.Tensor
+    pro: Optional[Pro] = None
+    out: Optional[torch.Tensor] = None
+    accumulate: bool = False
+    with_bias: bool = False
+    bias_out: Optional[torch.Tensor] = None
+    defer: Optional[list] = None
+    keep_dz: bool = True
+    dW: Optional[torch.Tensor] = None
+    db: Optional[torch.Tensor] = None
+
+
+def _fused_wgrad(fw: FusedWgrad, M: int, N: int, K: int):
+    """-> BnBwdWgradT for the C call (keeps its prologue, job and workspace alive); sets fw.dW / fw.db."""
+    lib = _lib.load()
+    if tuple(fw.x.shape) != (M, N):
+        raise ValueError(f"fused wgrad: x is {tuple(fw.x.shape)}, expected [{M},{N}]")
+    dev = fw.x.device
+    acc = fw.accumulate and fw.out is not None
+    fw.dW = fw.out if fw.out is not None else torch.empty(K, N, dtype=torch.float32, device=dev)
+    fw.db = None
+    if fw.with_bias:
+        fw.db = fw.bias_out if (fw.bias_out is not None and acc) else torch.empty(K, dtype=torch.float32, device=dev)
+    nb = max(int(lib.mmg_linear_bnbwd_wgrad_ws_bytes(M, N, K)), 256)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)      # its own slabs (the shared workspace may hold a NextBN's partials)
+    job = WgradReduceT()
+    pc = fw.pro.c() if fw.pro is not None else None
+    t = BnBwdWgradT(_p(fw.x).value, C.pointer(pc) if pc is not None else None, _p(fw.dW).value,
+                    _p(fw.db).value if fw.db is not None else None, int(acc), _p(ws, torch.uint8).value, ws.numel(),
+                    C.pointer(job) if fw.defer is not None else None)
+    t._keep = (pc, ws, job)
+    return t
+
+
+def _fused_wgrad_done(fw: FusedWgrad, t):
+    if fw.defer is not None:
+        fw.defer.append((t._keep[2], t._keep[1], fw.dW, fw.db))
+
+
+def _fused_wgrad_bytes(M: int, N: int, K: int) -> int:      # x read once, one slab per workgroup written
+    return 4 * M * N + 4 * int(_lib.load().mmg_linear_bnbwd_wgrad_ws_bytes(M, N, K))
+
+
 def linear_bnbwd(g: torch.Tensor, y: torch.Tensor, pro: Pro, fold: Optional[BNFold], W: torch.Tensor, sums=None,
-                 count: float = 1.0, dbeta=None, dgamma=None, next_bn: Optional["NextBN"] = None):
+                 count: float = 1.0, dbeta=None, dgamma=None, next_bn: Optional["NextBN"] = None,
+                 wgrad: Optional[FusedWgrad] = None):
     """bn_bwd_apply(g, y, ...) and the data gradient dz @ W of the linear in front of that BatchNorm in ONE pass over g and
-    y (mmg_linear_bnbwd): -> (dz [M,K], dx [M,N]).  W [K, N] is the forward weight of the linear, read in place."""
+    y (mmg_linear_bnbwd): -> (dz [M,K], dx [M,N]).  W [K, N] is the forward weight of the linear, read in place.
+    wgrad: the layer's weight gradient in the same launch (mmg_linear_bnbwd_wgrad, see FusedWgrad)."""
     lib = _lib.load()
     M, K = y.shape
     if W.shape[0] != K:
         raise ValueError(f"linear_bnbwd: W has {W.shape[0]} rows, y has {K} columns")
     N = W.shape[1]
-    dz = torch.empty_like(y)
+    dz = torch.empty_like(y) if wgrad is None or wgrad.keep_dz else None
     dx = torch.empty(M, N, device=y.device)
+    if wgrad is not None:
+        _tok = _pb("linear_bnbwd_wgrad")
+        nbt, nsums = _next_bn(next_bn, M, N) if next_bn is not None else (None, None)
+        wt = _fused_wgrad(wgrad, M, N, K)
+        check(lib.mmg_linear_bnbwd_wgrad(_p(g), _p(y), _pro(pro), _p(fold.mean) if fold else None,
+                                         _p(fold.rstd) if fold else None, _p(sums, torch.float64), 1.0 / float(count),
+                                         _p(dbeta), _p(dgamma), _p(W), _p(dz), _p(dx), M, N, K,
+                                         C.byref(nbt) if nbt is not None else None, C.byref(wt), _stream()),
+              "mmg_linear_bnbwd_wgrad")
+        _fused_wgrad_done(wgrad, wt)
+        _pe(_tok, "linear_bnbwd_wgrad", 4 * (2 * M * K + (M * K if dz is not None else 0) + M * N)
+            + _fused_wgrad_bytes(M, N, K), 4 * M * N * K)
+        return (dz, dx, nsums) if next_bn is not None else (dz, dx)
     _tok = _pb("linear_bnbwd")
     if next_bn is not None:       # -> (dz, dx, the statistics of the BatchNorm backward that consumes dx), see NextBN
         nbt, nsums = _next_bn(next_bn, M, N)
@@ -658,13 +726,24 @@ def linear_bnbwd2_supported(M: int, N: int, K: int) -> bool:
 
 
 def linear_bnbwd2(g: torch.Tensor, g2: torch.Tensor, y: torch.Tensor, pro: Pro, pro2: Pro, fold: BNFold, W: torch.Tensor,
-                  sums, count, dbeta=None, dgamma=None):
-    """bn_bwd_apply2 (two upstream gradients, own dropout masks) + the data gradient dz @ W in one pass -> (dz, dx)."""
+                  sums, count, dbeta=None, dgamma=None, wgrad: Optional[FusedWgrad] = None):
+    """bn_bwd_apply2 (two upstream gradients, own dropout masks) + the data gradient dz @ W in one pass -> (dz, dx).
+    wgrad: the layer's weight gradient in the same launch (mmg_linear_bnbwd2_wgrad, see FusedWgrad)."""
     lib = _lib.load()
     M, K = y.shape
     N = W.shape[1]
-    dz = torch.empty_like(y)
+    dz = torch.empty_like(y) if wgrad is None or wgrad.keep_dz else None
     dx = torch.empty(M, N, device=y.device)
+    if wgrad is not None:
+        _tok = _pb("linear_bnbwd_wgrad")
+        wt = _fused_wgrad(wgrad, M, N, K)
+        check(lib.mmg_linear_bnbwd2_wgrad(_p(g), _p(g2), _p(y), _pro(pro), _pro(pro2), _p(fold.mean), _p(fold.rstd),
+                                          _p(sums, torch.float64), 1.0 / float(count), _p(dbeta), _p(dgamma), _p(W), _p(dz),
+                                          _p(dx), M, N, K, C.byref(wt), _stream()), "mmg_linear_bnbwd2_wgrad")
+        _fused_wgrad_done(wgrad, wt)
+        _pe(_tok, "linear_bnbwd_wgrad", 4 * (3 * M * K + (M * K if dz is not None else 0) + M * N)
+            + _fused_wgrad_bytes(M, N, K), 4 * M * N * K)
+        return dz, dx
     _tok = _pb("linear_bnbwd")
     check(lib.mmg_linear_bnbwd2(_p(g), _p(g2), _p(y), _pro(pro), _pro(pro2), _p(fold.mean), _p(fold.rstd),
                                 _p(sums, torch.float64), 1.0 / float(count), _p(dbeta), _p(dgamma), _p(W), _p(dz), _p(dx),
@@ -674,14 +753,29 @@ def linear_bnbwd2(g: torch.Tensor, g2: torch.Tensor, y: torch.Tensor, pro: Pro, 
 
 
 def linear_bnbwd_rows(g_rows: torch.Tensor, row_pos: torch.Tensor, y: torch.Tensor, pro: Pro, fold: BNFold, W: torch.Tensor,
-                      sums, count, dbeta=None, dgamma=None, next_bn: Optional["NextBN"] = None):
+                      sums, count, dbeta=None, dgamma=None, next_bn: Optional["NextBN"] = None,
+                      wgrad: Optional[FusedWgrad] = None):
     """bn_bwd_apply(None, ...) + bn_bwd_apply_rows(g_rows, ...) + the data gradient dz @ W in one pass -> (dz, dx): the
-    upstream gradient is zero outside the listed rows; row_pos [M] int32 = position of a row in the list or -1."""
+    upstream gradient is zero outside the listed rows; row_pos [M] int32 = position of a row in the list or -1.
+    wgrad: the layer's weight gradient in the same launch (mmg_linear_bnbwd_rows_wgrad, see FusedWgrad)."""
     lib = _lib.load()
     M, K = y.shape
     N = W.shape[1]
-    dz = torch.empty_like(y)
+    dz = torch.empty_like(y) if wgrad is None or wgrad.keep_dz else None
     dx = torch.empty(M, N, device=y.device)
+    if wgrad is not None:
+        _tok = _pb("linear_bnbwd_wgrad")
+        nbt, nsums = _next_bn(next_bn, M, N) if next_bn is not None else (None, None)
+        wt = _fused_wgrad(wgrad, M, N, K)
+        check(lib.mmg_linear_bnbwd_rows_wgrad(_p(g_rows) if g_rows.numel() else None, _p(row_pos, torch.int32),
+                                              g_rows.shape[0], _p(y), _pro(pro), _p(fold.mean), _p(fold.rstd),
+                                              _p(sums, torch.float64), 1.0 / float(count), _p(dbeta), _p(dgamma), _p(W),
+                                              _p(dz), _p(dx), M, N, K, C.byref(nbt) if nbt is not None else None,
+                                              C.byref(wt), _stream()), "mmg_linear_bnbwd_rows_wgrad")
+        _fused_wgrad_done(wgrad, wt)
+        _pe(_tok, "linear_bnbwd_wgrad", 4 * (M * K + (M * K if dz is not None else 0) + M * N)
+            + _fused_wgrad_bytes(M, N, K), 4 * M * N * K)
+        return (dz, dx, nsums) if next_bn is not None else (dz, dx)
     _tok = _pb("linear_bnbwd")
     if next_bn is not None:       # -> (dz, dx, the statistics of the BatchNorm backward that consumes dx), see NextBN
         nbt, nsums = _next_bn(next_bn, M, N)
@@ -700,14 +794,32 @@ def linear_bnbwd_rows(g_rows: torch.Tensor, row_pos: torch.Tensor, y: torch.Tens
     return dz, dx
 
 
-def linear_l2bwd(g: torch.Tensor, out: torch.Tensor, rn: torch.Tensor, W: torch.Tensor, next_bn: Optional["NextBN"] = None):
+def linear_l2bwd(g: torch.Tensor, out: torch.Tensor, rn: torch.Tensor, W: torch.Tensor, next_bn: Optional["NextBN"] = None,
+                 wgrad: Optional[FusedWgrad] = None):
     """l2norm_bwd(g, out, rn) and the data gradient dz @ W of the linear in front of the normalisation -> (dz, dx): ONE
-    kernel where mmg_linear_bnbwd_supported (W [K, N] = the forward weight in place), the two launches elsewhere."""
+    kernel where mmg_linear_bnbwd_supported (W [K, N] = the forward weight in place), the two launches elsewhere.
+    wgrad: the layer's weight gradient in the same launch (mmg_linear_l2bwd_wgrad, see FusedWgrad; the caller checks
+    linear_bnbwd_wgrad_supported)."""
     lib = _lib.load()
     M, K = out.shape
     N = W.shape[1]
     if W.shape[0] != K:
         raise ValueError(f"linear_l2bwd: W has {W.shape[0]} rows, out has {K} columns")
+    if wgrad is not None:
+        if not lib.mmg_linear_bnbwd_wgrad_supported(M, N, K):
+            raise ValueError(f"linear_l2bwd: no fused weight gradient for M={M} N={N} K={K}")
+        dz = torch.empty_like(out) if wgrad.keep_dz else None
+        dx = torch.empty(M, N, device=out.device)
+        _tok = _pb("linear_l2bwd_wgrad")
+        nbt, nsums = _next_bn(next_bn, M, N) if next_bn is not None else (None, None)
+        wt = _fused_wgrad(wgrad, M, N, K)
+        check(lib.mmg_linear_l2bwd_wgrad(_p(g), _p(out), _p(rn), _p(W), _p(dz), _p(dx), M, N, K, L2_EPS,
+                                         C.byref(nbt) if nbt is not None else None, C.byref(wt), _stream()),
+              "mmg_linear_l2bwd_wgrad")
+        _fused_wgrad_done(wgrad, wt)
+        _pe(_tok, "linear_l2bwd_wgrad", 4 * (2 * M * K + (M * K if dz is not None else 0) + M * N + M)
+            + _fused_wgrad_bytes(M, N, K), 4 * M * N * K)
+        return (dz, dx, nsums) if next_bn is not None else (dz, dx)
     if not lib.mmg_linear_bnbwd_supported(M, N, K):
         dz = l2norm_bwd(g, out, rn)
         if next_bn is not None:
