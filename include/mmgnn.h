@@ -246,34 +246,6 @@ int mmg_bn_bwd_apply(const float* G, const float* Y, const mmg_prologue_t* pro, 
                      const float* rstd, const double* sums, double inv_count, float* dbeta, float* dgamma,
                      float* dY, int64_t M, int N, int accumulate, void* stream);
 
-/* mmg_bn_bwd_apply folded into the data-gradient GEMM that follows it (autograd of nn.Linear behind BatchNorm1d + relu +
- * dropout, src/model.py:93-101,258-269):  dZ = pass 2 above at (G, Y)  and  dX[M,N] = dZ[M,K] . W  with W stored [K,N] (the
- * forward weight in place, as MMG_LIN_W_KN), in ONE pass over G and Y -- dZ is written once for the weight gradient of
- * the same layer.  Arguments as mmg_bn_bwd_apply (sums NULL: eval mode; pro->scale NULL: no BatchNorm, relu / dropout only);
- * relu only.  mmg_linear_bnbwd_supported: M > 512, K and N in {64, 128} (one workgroup spans all N columns). */
-int mmg_linear_bnbwd_supported(int64_t M, int N, int K);
-int mmg_linear_bnbwd(const float* G, const float* Y, const mmg_prologue_t* pro, const float* mean, const float* rstd,
-                     const double* sums, double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ,
-                     float* dX, int64_t M, int N, int K, void* stream);
-
-/* ... and mmg_bn_bwd_apply2 (two upstream gradients, own dropout masks) the same way; K = N = 128. */
-int mmg_linear_bnbwd2(const float* G, const float* G2, const float* Y, const mmg_prologue_t* pro, const mmg_prologue_t* pro2,
-                      const float* mean, const float* rstd, const double* sums, double inv_count, float* dbeta,
-                      float* dgamma, const float* W, float* dZ, float* dX, int64_t M, int N, int K, void* stream);
-
-/* ... and the row-list form (mmg_bn_bwd_apply with G = NULL + mmg_bn_bwd_apply_rows): G_rows [n_sel, K] holds the listed
- * rows of the upstream gradient back to back, row_pos[row] (int32, [M]) = position of `row` in that list or -1. */
-int mmg_linear_bnbwd_rows(const float* G_rows, const int32_t* row_pos, int64_t n_sel, const float* Y,
-                          const mmg_prologue_t* pro, const float* mean, const float* rstd, const double* sums,
-                          double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ, float* dX, int64_t M,
-                          int N, int K, void* stream);
-
-/* mmg_l2norm_bwd folded into the data-gradient GEMM of the linear in front of the normalisation the same way:
- * dZ = rnorm * (G - out * <G, out>) (0 dot product where the norm was clamped), dX = dZ . W, W stored [K,N].  Shapes as
- * mmg_linear_bnbwd_supported. */
-int mmg_linear_l2bwd(const float* G, const float* out, const float* rnorm, const float* W, float* dZ, float* dX,
-                     int64_t M, int N, int K, float eps, void* stream);
-
 /* Two upstream gradients through the SAME BatchNorm + ReLU, each with its own dropout mask (pro2: only its dropout fields
  * are used) -- the two encode_nodes passes of a training step (src/model.py:294 and :301 -> :251) see the same
  * Linear + BatchNorm1d in front of their first Dropout (model.py:93-96), i.e. they share that layer:
@@ -307,12 +279,10 @@ int mmg_bn_bwd_apply_rows(const float* G_rows, const float* Y, const int64_t* ro
  * hands down is the upstream gradient of the BatchNorm below it.
  *   mmg_linear_fwd_next_bn          dX = dY . W  (MMG_LIN_W_KN) of a plain linear, e.g. the heads' first layer; no prologue,
  *                                   no accumulate;  M > 512, N % 128 == 0, K in {64, 128}
- *   mmg_linear_l2bwd_next_bn        dX of mmg_linear_l2bwd;  K = N = 128
- *   mmg_linear_bnbwd_next_bn        dX of mmg_linear_bnbwd;  K = N = 128
- *   mmg_linear_bnbwd_rows_next_bn   dX of mmg_linear_bnbwd_rows;  K = N = 128
+ *   mmg_linear_bnbwd                dX;  K = N = 128 without a weight gradient (not MMG_BNBWD_BN2: refused)
  *   mmg_gather_rows_next_bn         the final `out` of mmg_gather_rows (accumulate or not);  the bit-plane layouts, D >= 128
- * next == NULL: the plain entry point.  A shape (or activation) outside the list above runs the producer followed by
- * the separate statistics pass: the result is defined for everything the plain entry point accepts. */
+ * next == NULL: the producer alone.  A shape (or activation) outside the list above runs the producer followed by
+ * the separate statistics pass: the result is defined for everything the producer accepts. */
 typedef struct {
   const float* y;                 /* [M, N] pre-BatchNorm activation of the layer below */
   const mmg_prologue_t* pro;      /* its fold (scale / shift), activation (none | relu) and dropout */
@@ -326,25 +296,53 @@ typedef struct {
 size_t mmg_next_bn_ws_bytes(int64_t M, int N);
 int mmg_linear_fwd_next_bn(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias, float* Y, int64_t M,
                            int N, int K, int flags, const mmg_next_bn_t* next, void* stream);
-int mmg_linear_l2bwd_next_bn(const float* G, const float* out, const float* rnorm, const float* W, float* dZ, float* dX,
-                             int64_t M, int N, int K, float eps, const mmg_next_bn_t* next, void* stream);
-int mmg_linear_bnbwd_next_bn(const float* G, const float* Y, const mmg_prologue_t* pro, const float* mean, const float* rstd,
-                             const double* sums, double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ,
-                             float* dX, int64_t M, int N, int K, const mmg_next_bn_t* next, void* stream);
-int mmg_linear_bnbwd_rows_next_bn(const float* G_rows, const int32_t* row_pos, int64_t n_sel, const float* Y,
-                                  const mmg_prologue_t* pro, const float* mean, const float* rstd, const double* sums,
-                                  double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ, float* dX,
-                                  int64_t M, int N, int K, const mmg_next_bn_t* next, void* stream);
 int mmg_gather_rows_next_bn(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D, float* out, int accumulate,
                             const mmg_next_bn_t* next, void* stream);
 
-/* The weight gradient of the same layer inside the BatchNorm-backward data-gradient GEMMs: what the plain entry point
- * (or its _next_bn form; next may be NULL) computes, and in the same launch what
+/* The BatchNorm (or L2-norm) backward folded into the data-gradient GEMM of the linear in front of it -- autograd of
+ * nn.Linear behind BatchNorm1d + relu + dropout (src/model.py:93-101,258-269) or behind F.normalize.  In ONE pass over the
+ * upstream gradient and the activation: dZ [M, K] = that backward, written once for the weight gradient of the layer,
+ * and dX [M, N] = dZ . W with W stored [K, N] (the forward weight in place, as MMG_LIN_W_KN).  a->mode:
+ *   MMG_BNBWD_BN    pass 2 of mmg_bn_bwd_apply at (G, y): pro, mean, rstd, sums, inv_count, dbeta, dgamma as there (sums
+ *                   NULL: eval mode; pro or pro->scale NULL: no BatchNorm, relu / dropout only)
+ *   MMG_BNBWD_L2    mmg_l2norm_bwd: dZ = rnorm * (G - y * <G, y>), y = the normalised rows (0 dot product where the norm
+ *                   was clamped at eps)
+ *   MMG_BNBWD_BN2   mmg_bn_bwd_apply2: G and G2 through the same BatchNorm + relu, pro2 = the dropout of G2
+ *   MMG_BNBWD_ROWS  mmg_bn_bwd_apply with G = NULL + mmg_bn_bwd_apply_rows: an upstream gradient that is zero outside a
+ *                   list of rows; G [n_sel, K] holds the listed rows back to back (NULL allowed iff n_sel == 0) and
+ *                   row_pos [M] the position of a row in that list or -1
+ * The BatchNorm modes take relu only.  Fields a mode does not name are ignored.
+ * next (nullable; refused with MMG_BNBWD_BN2): the statistics of the BatchNorm backward that consumes dX, see
+ *   mmg_next_bn_t.
+ * wg (nullable): the weight gradient of the same layer in the same launch -- what
  *   mmg_linear_wgrad_deferred(dZ, X, wg->pro, wg->dW, wg->dbias, M, K, N, wg->accumulate, wg->ws, wg->ws_bytes, ., wg->job)
- * would: dW [K, N] (+)= dZ^T . pro(X), dbias [K] (+)= the column sums of dZ, while dZ is still on chip.  The slabs are
- * left in ws and described in *wg->job for mmg_wgrad_reduce_group; job == NULL sums them before returning.  dZ may be
- * NULL: it is then not written (nothing else reads it).  X [M, N] is the layer input; its prologue takes relu only.
- * mmg_linear_bnbwd_wgrad_supported: mmg_linear_bnbwd_supported and K = N = 128. */
+ *   would compute: dW [K, N] (+)= dZ^T . pro(X), dbias [K] (+)= the column sums of dZ, taken while dZ is still on chip.
+ *   The slabs are left in ws and described in *wg->job for mmg_wgrad_reduce_group; job == NULL sums them before
+ *   returning.  With wg, dZ may be NULL: it is then not written.  X [M, N] is the layer input; its prologue takes relu
+ *   only.
+ * mmg_linear_bnbwd_supported: M > 512, and K, N in {64, 128} for BN and L2 without wg; K = N = 128 otherwise. */
+#define MMG_BNBWD_BN 0
+#define MMG_BNBWD_L2 1
+#define MMG_BNBWD_BN2 2
+#define MMG_BNBWD_ROWS 3
+typedef struct {
+  int mode;                       /* MMG_BNBWD_* */
+  const float* G;                 /* [M, K] upstream gradient; ROWS: [n_sel, K], the listed rows */
+  const float* G2;                /* BN2: [M, K] the second upstream gradient */
+  const int32_t* row_pos;         /* ROWS: [M] */
+  int64_t n_sel;                  /* ROWS */
+  const float* y;                 /* [M, K] BN / BN2 / ROWS: pre-BatchNorm activation; L2: the normalised rows */
+  const mmg_prologue_t* pro;      /* BN / BN2 / ROWS: its fold, activation and dropout (BN: may be NULL) */
+  const mmg_prologue_t* pro2;     /* BN2: the dropout of G2 (only its dropout fields are used) */
+  const float* mean;              /* BN / BN2 / ROWS, with pro->scale: [K] */
+  const float* rstd;              /* [K] */
+  const double* sums;             /* [2, K] of mmg_bn_bwd_stats, or NULL (eval mode) */
+  double inv_count;
+  float* dbeta;                   /* [K] or NULL */
+  float* dgamma;                  /* [K] or NULL */
+  const float* rnorm;             /* L2: [M] */
+  float eps;                      /* L2 */
+} mmg_bnbwd_t;
 typedef struct {
   const float* X;                 /* [M, N] input of the linear */
   const mmg_prologue_t* pro;      /* its prologue (BatchNorm fold, relu, dropout) or NULL */
@@ -355,24 +353,10 @@ typedef struct {
   size_t ws_bytes;
   mmg_wgrad_reduce_t* job;        /* deferred slab sum, or NULL */
 } mmg_bnbwd_wgrad_t;
-int mmg_linear_bnbwd_wgrad_supported(int64_t M, int N, int K);
+int mmg_linear_bnbwd_supported(int mode, int64_t M, int N, int K, int with_wgrad);
 size_t mmg_linear_bnbwd_wgrad_ws_bytes(int64_t M, int N, int K);
-int mmg_linear_bnbwd_wgrad(const float* G, const float* Y, const mmg_prologue_t* pro, const float* mean, const float* rstd,
-                           const double* sums, double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ,
-                           float* dX, int64_t M, int N, int K, const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg,
-                           void* stream);
-int mmg_linear_bnbwd2_wgrad(const float* G, const float* G2, const float* Y, const mmg_prologue_t* pro,
-                            const mmg_prologue_t* pro2, const float* mean, const float* rstd, const double* sums,
-                            double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ, float* dX, int64_t M,
-                            int N, int K, const mmg_bnbwd_wgrad_t* wg, void* stream);
-int mmg_linear_bnbwd_rows_wgrad(const float* G_rows, const int32_t* row_pos, int64_t n_sel, const float* Y,
-                                const mmg_prologue_t* pro, const float* mean, const float* rstd, const double* sums,
-                                double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ, float* dX,
-                                int64_t M, int N, int K, const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg,
-                                void* stream);
-int mmg_linear_l2bwd_wgrad(const float* G, const float* out, const float* rnorm, const float* W, float* dZ, float* dX,
-                           int64_t M, int N, int K, float eps, const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg,
-                           void* stream);
+int mmg_linear_bnbwd(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
+                     const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, void* stream);
 
 /* Measurement hook (bench.py).  After mmg_probe_arm(n) the next n launches of the big kernels (from any host thread: the
  * backward of a step runs on the autograd engine's thread) carry a HIP start / stop event pair on the kernel itself (hipExtLaunchKernelGGL: the kernel's own begin / end

@@ -84,6 +84,13 @@ class WgradReduceT(C.Structure):
                 ("nk4", C.c_int64), ("accumulate", C.c_int)]
 
 
+class BnBwdT(C.Structure):
+    _fields_ = [("mode", C.c_int), ("G", C.c_void_p), ("G2", C.c_void_p), ("row_pos", C.c_void_p), ("n_sel", C.c_int64),
+                ("y", C.c_void_p), ("pro", C.POINTER(PrologueT)), ("pro2", C.POINTER(PrologueT)), ("mean", C.c_void_p),
+                ("rstd", C.c_void_p), ("sums", C.c_void_p), ("inv_count", C.c_double), ("dbeta", C.c_void_p),
+                ("dgamma", C.c_void_p), ("rnorm", C.c_void_p), ("eps", C.c_float)]
+
+
 class BnBwdWgradT(C.Structure):
     _fields_ = [("X", C.c_void_p), ("pro", C.POINTER(PrologueT)), ("dW", C.c_void_p), ("dbias", C.c_void_p),
                 ("accumulate", C.c_int), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
@@ -145,32 +152,12 @@ SIGNATURES = {
     "mmg_bn_bwd_apply": (C.c_int, [_vp, _vp, _P(PrologueT), _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "mmg_linear_fwd_l2norm_supported": (C.c_int, [_i64, _i32, _i32]),
     "mmg_linear_fwd_l2norm": (C.c_int, [_vp, _P(PrologueT), _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp]),
-    "mmg_linear_bnbwd_supported": (C.c_int, [_i64, _i32, _i32]),
-    "mmg_linear_bnbwd_wgrad_supported": (C.c_int, [_i64, _i32, _i32]),
+    "mmg_linear_bnbwd_supported": (C.c_int, [_i32, _i64, _i32, _i32, _i32]),
     "mmg_linear_bnbwd_wgrad_ws_bytes": (_sz, [_i64, _i32, _i32]),
-    "mmg_linear_bnbwd_wgrad": (C.c_int, [_vp, _vp, _P(PrologueT), _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp,
-                                         _i64, _i32, _i32, _P(NextBnT), _P(BnBwdWgradT), _vp]),
-    "mmg_linear_bnbwd2_wgrad": (C.c_int, [_vp, _vp, _vp, _P(PrologueT), _P(PrologueT), _vp, _vp, _vp, C.c_double, _vp, _vp,
-                                          _vp, _vp, _vp, _i64, _i32, _i32, _P(BnBwdWgradT), _vp]),
-    "mmg_linear_bnbwd_rows_wgrad": (C.c_int, [_vp, _vp, _i64, _vp, _P(PrologueT), _vp, _vp, _vp, C.c_double, _vp, _vp, _vp,
-                                              _vp, _vp, _i64, _i32, _i32, _P(NextBnT), _P(BnBwdWgradT), _vp]),
-    "mmg_linear_l2bwd_wgrad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _P(NextBnT), _P(BnBwdWgradT),
-                                         _vp]),
-    "mmg_linear_l2bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp]),
+    "mmg_linear_bnbwd": (C.c_int, [_P(BnBwdT), _vp, _vp, _vp, _i64, _i32, _i32, _P(NextBnT), _P(BnBwdWgradT), _vp]),
     "mmg_next_bn_ws_bytes": (_sz, [_i64, _i32]),
     "mmg_linear_fwd_next_bn": (C.c_int, [_vp, _P(PrologueT), _vp, _vp, _vp, _i64, _i32, _i32, _i32, _P(NextBnT), _vp]),
-    "mmg_linear_l2bwd_next_bn": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _P(NextBnT), _vp]),
-    "mmg_linear_bnbwd_next_bn": (C.c_int, [_vp, _vp, _P(PrologueT), _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp,
-                                           _i64, _i32, _i32, _P(NextBnT), _vp]),
-    "mmg_linear_bnbwd_rows_next_bn": (C.c_int, [_vp, _vp, _i64, _vp, _P(PrologueT), _vp, _vp, _vp, C.c_double, _vp, _vp, _vp,
-                                                _vp, _vp, _i64, _i32, _i32, _P(NextBnT), _vp]),
     "mmg_gather_rows_next_bn": (C.c_int, [_P(RelT), _i32, _i64, _i32, _vp, _i32, _P(NextBnT), _vp]),
-    "mmg_linear_bnbwd_rows": (C.c_int, [_vp, _vp, _i64, _vp, _P(PrologueT), _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp,
-                                        _i64, _i32, _i32, _vp]),
-    "mmg_linear_bnbwd2": (C.c_int, [_vp, _vp, _vp, _P(PrologueT), _P(PrologueT), _vp, _vp, _vp, C.c_double, _vp, _vp, _vp,
-                                    _vp, _vp, _i64, _i32, _i32, _vp]),
-    "mmg_linear_bnbwd": (C.c_int, [_vp, _vp, _P(PrologueT), _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _i64, _i32,
-                                   _i32, _vp]),
     "mmg_l2norm_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _vp]),
     "mmg_l2norm_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp]),
     "mmg_pair_loss_ws_bytes": (_sz, [_i64]),

@@ -1908,12 +1908,11 @@ extern "C" int mmg_linear_fwd_l2norm(const float* X, const mmg_prologue_t* pro, 
   return MMG_OK;
 }
 
-extern "C" int mmg_linear_bnbwd_supported(int64_t M, int N, int K) {
-  return (M > 512 && (K == 64 || K == 128) && (N == 64 || N == 128)) ? 1 : 0;
-}
-
-extern "C" int mmg_linear_bnbwd_wgrad_supported(int64_t M, int N, int K) {
-  return (mmg_linear_bnbwd_supported(M, N, K) && N == 128 && K == 128) ? 1 : 0;
+extern "C" int mmg_linear_bnbwd_supported(int mode, int64_t M, int N, int K, int with_wgrad) {
+  if (mode < MMG_BNBWD_BN || mode > MMG_BNBWD_ROWS || M <= 512) return 0;
+  // BN and L2 have instances for K, N in {64, 128}; BN2, ROWS and the FW form only K = N = 128
+  if (mode == MMG_BNBWD_BN2 || mode == MMG_BNBWD_ROWS || with_wgrad) return (K == 128 && N == 128) ? 1 : 0;
+  return ((K == 64 || K == 128) && (N == 64 || N == 128)) ? 1 : 0;
 }
 
 extern "C" size_t mmg_linear_bnbwd_wgrad_ws_bytes(int64_t M, int N, int K) {
@@ -1962,213 +1961,80 @@ static int bnbwd_wgrad_run(const float* G, const BnBwdDev& bb, const ProDev& pr,
   return MMG_OK;
 }
 
-extern "C" int mmg_linear_bnbwd_next_bn(const float* G, const float* Y, const mmg_prologue_t* pro, const float* mean,
-                                        const float* rstd, const double* sums, double inv_count, float* dbeta, float* dgamma,
-                                        const float* W, float* dZ, float* dX, int64_t M, int N, int K,
-                                        const mmg_next_bn_t* next, void* stream);
-
-extern "C" int mmg_linear_bnbwd(const float* G, const float* Y, const mmg_prologue_t* pro, const float* mean,
-                                const float* rstd, const double* sums, double inv_count, float* dbeta, float* dgamma,
-                                const float* W, float* dZ, float* dX, int64_t M, int N, int K, void* stream) {
-  return mmg_linear_bnbwd_next_bn(G, Y, pro, mean, rstd, sums, inv_count, dbeta, dgamma, W, dZ, dX, M, N, K, nullptr, stream);
-}
-
-static int linear_bnbwd_impl(const float* G, const float* Y, const mmg_prologue_t* pro, const float* mean,
-                             const float* rstd, const double* sums, double inv_count, float* dbeta, float* dgamma,
-                             const float* W, float* dZ, float* dX, int64_t M, int N, int K,
-                             const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, void* stream) {
-  MMG_CHECK_ARG(mmg_linear_bnbwd_supported(M, N, K), "linear_bnbwd: M=%lld N=%d K=%d unsupported (M > 512, K and N in {64,128})",
-                (long long)M, N, K);
-  MMG_CHECK_ARG(!wg || (K == 128 && N == 128), "linear_bnbwd_wgrad: N=%d K=%d unsupported (K = N = 128)", N, K);
-  MMG_CHECK_ARG(G && Y && W && (dZ || wg) && dX, "linear_bnbwd: null buffer");
-  MMG_CHECK_ARG(!pro || !pro->scale || (pro->shift && mean && rstd), "linear_bnbwd: BatchNorm fold without shift / mean / rstd");
-  MMG_CHECK_ARG(!pro || pro->relu == MMG_ACT_NONE || pro->relu == MMG_ACT_RELU, "linear_bnbwd: relu only");
-  MMG_CHECK_ARG(!sums || (pro && pro->scale), "linear_bnbwd: sums without a BatchNorm fold");
-  const ProDev pr = mmg_pro_dev(pro);
-  BnBwdDev bb{Y, mean, rstd, sums, inv_count, dZ, dbeta, dgamma, 0.f, nullptr, nullptr, 0};
-  hipStream_t st = (hipStream_t)stream;
-  if (wg) return bnbwd_wgrad_run<0>(G, bb, pr, mmg_pro_dev(nullptr), W, dX, M, next, wg, "linear_bnbwd_wgrad", st);
+// one mode: the FW instance when the weight gradient rides along; else the NBN instance when the next BatchNorm's
+// statistics fit its epilogue; else the plain instance of the shape (+ the separate statistics pass over dX)
+template <int MODE>
+static int bnbwd_run(const float* G, const BnBwdDev& bb, const ProDev& pr, const ProDev& pr2, const float* W, float* dX,
+                     int64_t M, int N, int K, const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, const char* what,
+                     hipStream_t st) {
+  if (wg) return bnbwd_wgrad_run<MODE>(G, bb, pr, pr2, W, dX, M, next, wg, what, st);
   int rc;
-  if (next && K == 128 && N == 128 && next_bn_fusable(next)) {
-    NextBnDev nb;
-    double* partial;
-    rc = mmg_next_bn_dev(next, M, N, "linear_bnbwd", &nb, &partial);
-    if (rc) return rc;
-    rc = launch_bnbwd_x6<128, 4, 0, true>(G, bb, pr, W, dX, M, st, mmg_pro_dev(nullptr), nb, partial);
-    if (rc) return rc;
-    MMG_CHECK_LAUNCH("linear_bnbwd");
-    return mmg_next_bn_finish(next, partial, N, (int)bnbwd_x6_rows(M, K), stream);
+  if constexpr (MODE != MMG_BNBWD_BN2) {          // no NBN instance (the entry point refuses next)
+    if (next && K == 128 && N == 128 && next_bn_fusable(next)) {
+      NextBnDev nb;
+      double* partial;
+      rc = mmg_next_bn_dev(next, M, N, what, &nb, &partial);
+      if (rc) return rc;
+      rc = launch_bnbwd_x6<128, 4, MODE, true>(G, bb, pr, W, dX, M, st, pr2, nb, partial);
+      if (rc) return rc;
+      MMG_CHECK_LAUNCH(what);
+      return mmg_next_bn_finish(next, partial, N, (int)bnbwd_x6_rows(M, K), st);
+    }
   }
-  if (K == 128) rc = N == 128 ? launch_bnbwd_x6<128, 4>(G, bb, pr, W, dX, M, st) : launch_bnbwd_x6<128, 2>(G, bb, pr, W, dX, M, st);
-  else rc = N == 128 ? launch_bnbwd_x6<64, 4>(G, bb, pr, W, dX, M, st) : launch_bnbwd_x6<64, 2>(G, bb, pr, W, dX, M, st);
+  if constexpr (MODE == MMG_BNBWD_BN2 || MODE == MMG_BNBWD_ROWS) rc = launch_bnbwd_x6<128, 4, MODE>(G, bb, pr, W, dX, M, st, pr2);
+  else if (K == 128) rc = N == 128 ? launch_bnbwd_x6<128, 4, MODE>(G, bb, pr, W, dX, M, st) : launch_bnbwd_x6<128, 2, MODE>(G, bb, pr, W, dX, M, st);
+  else rc = N == 128 ? launch_bnbwd_x6<64, 4, MODE>(G, bb, pr, W, dX, M, st) : launch_bnbwd_x6<64, 2, MODE>(G, bb, pr, W, dX, M, st);
   if (rc) return rc;
-  MMG_CHECK_LAUNCH("linear_bnbwd");
-  return next ? mmg_next_bn_fallback(dX, M, N, next, "linear_bnbwd", stream) : MMG_OK;
+  MMG_CHECK_LAUNCH(what);
+  return next ? mmg_next_bn_fallback(dX, M, N, next, what, st) : MMG_OK;
 }
 
-extern "C" int mmg_linear_bnbwd_next_bn(const float* G, const float* Y, const mmg_prologue_t* pro, const float* mean,
-                                        const float* rstd, const double* sums, double inv_count, float* dbeta, float* dgamma,
-                                        const float* W, float* dZ, float* dX, int64_t M, int N, int K,
-                                        const mmg_next_bn_t* next, void* stream) {
-  return linear_bnbwd_impl(G, Y, pro, mean, rstd, sums, inv_count, dbeta, dgamma, W, dZ, dX, M, N, K, next, nullptr, stream);
-}
+// what each mode requires of the descriptor besides y (the fields a mode does not name are ignored)
+static const struct {
+  const char* name;
+  bool G, G2, row_pos, pro, pro2, rnorm;
+} kBnBwdMode[4] = {
+    //                       G      G2     row_pos pro    pro2   rnorm
+    {"linear_bnbwd",         true,  false, false,  false, false, false},    // pro NULL: relu only, no BatchNorm
+    {"linear_l2bwd",         true,  false, false,  false, false, true},
+    {"linear_bnbwd2",        true,  true,  false,  true,  true,  false},
+    {"linear_bnbwd_rows",    false, false, true,   true,  false, false},    // G NULL iff n_sel == 0 (checked below)
+};
 
-extern "C" int mmg_linear_bnbwd_wgrad(const float* G, const float* Y, const mmg_prologue_t* pro, const float* mean,
-                                      const float* rstd, const double* sums, double inv_count, float* dbeta, float* dgamma,
-                                      const float* W, float* dZ, float* dX, int64_t M, int N, int K,
-                                      const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, void* stream) {
-  MMG_CHECK_ARG(wg, "linear_bnbwd_wgrad: null weight-gradient descriptor");
-  return linear_bnbwd_impl(G, Y, pro, mean, rstd, sums, inv_count, dbeta, dgamma, W, dZ, dX, M, N, K, next, wg, stream);
-}
-
-static int linear_bnbwd2_impl(const float* G, const float* G2, const float* Y, const mmg_prologue_t* pro,
-                              const mmg_prologue_t* pro2, const float* mean, const float* rstd, const double* sums,
-                              double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ, float* dX,
-                              int64_t M, int N, int K, const mmg_bnbwd_wgrad_t* wg, void* stream) {
-  MMG_CHECK_ARG(mmg_linear_bnbwd_supported(M, N, K) && K == 128 && N == 128,
-                "linear_bnbwd2: M=%lld N=%d K=%d unsupported (M > 512, K = N = 128)", (long long)M, N, K);
-  MMG_CHECK_ARG(G && G2 && Y && W && (dZ || wg) && dX && pro && pro2, "linear_bnbwd2: null buffer");
-  MMG_CHECK_ARG(!pro->scale || (pro->shift && mean && rstd), "linear_bnbwd2: BatchNorm fold without shift / mean / rstd");
-  MMG_CHECK_ARG(pro->relu == MMG_ACT_NONE || pro->relu == MMG_ACT_RELU, "linear_bnbwd2: relu only");
-  MMG_CHECK_ARG(!sums || pro->scale, "linear_bnbwd2: sums without a BatchNorm fold");
-  const ProDev pr = mmg_pro_dev(pro), pr2 = mmg_pro_dev(pro2);
-  BnBwdDev bb{Y, mean, rstd, sums, inv_count, dZ, dbeta, dgamma, 0.f, G2, nullptr, 0};
-  if (wg) return bnbwd_wgrad_run<2>(G, bb, pr, pr2, W, dX, M, nullptr, wg, "linear_bnbwd2_wgrad", (hipStream_t)stream);
-  int rc = launch_bnbwd_x6<128, 4, 2>(G, bb, pr, W, dX, M, (hipStream_t)stream, pr2);
-  if (rc) return rc;
-  MMG_CHECK_LAUNCH("linear_bnbwd2");
-  return MMG_OK;
-}
-
-extern "C" int mmg_linear_bnbwd2(const float* G, const float* G2, const float* Y, const mmg_prologue_t* pro,
-                                 const mmg_prologue_t* pro2, const float* mean, const float* rstd, const double* sums,
-                                 double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ, float* dX,
-                                 int64_t M, int N, int K, void* stream) {
-  return linear_bnbwd2_impl(G, G2, Y, pro, pro2, mean, rstd, sums, inv_count, dbeta, dgamma, W, dZ, dX, M, N, K, nullptr,
-                            stream);
-}
-
-extern "C" int mmg_linear_bnbwd2_wgrad(const float* G, const float* G2, const float* Y, const mmg_prologue_t* pro,
-                                       const mmg_prologue_t* pro2, const float* mean, const float* rstd, const double* sums,
-                                       double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ, float* dX,
-                                       int64_t M, int N, int K, const mmg_bnbwd_wgrad_t* wg, void* stream) {
-  MMG_CHECK_ARG(wg, "linear_bnbwd2_wgrad: null weight-gradient descriptor");
-  return linear_bnbwd2_impl(G, G2, Y, pro, pro2, mean, rstd, sums, inv_count, dbeta, dgamma, W, dZ, dX, M, N, K, wg, stream);
-}
-
-extern "C" int mmg_linear_bnbwd_rows_next_bn(const float* G_rows, const int32_t* row_pos, int64_t n_sel, const float* Y,
-                                             const mmg_prologue_t* pro, const float* mean, const float* rstd,
-                                             const double* sums, double inv_count, float* dbeta, float* dgamma, const float* W,
-                                             float* dZ, float* dX, int64_t M, int N, int K, const mmg_next_bn_t* next,
-                                             void* stream);
-
-extern "C" int mmg_linear_bnbwd_rows(const float* G_rows, const int32_t* row_pos, int64_t n_sel, const float* Y,
-                                     const mmg_prologue_t* pro, const float* mean, const float* rstd, const double* sums,
-                                     double inv_count, float* dbeta, float* dgamma, const float* W, float* dZ, float* dX,
-                                     int64_t M, int N, int K, void* stream) {
-  return mmg_linear_bnbwd_rows_next_bn(G_rows, row_pos, n_sel, Y, pro, mean, rstd, sums, inv_count, dbeta, dgamma, W, dZ, dX, M,
-                                       N, K, nullptr, stream);
-}
-
-static int linear_bnbwd_rows_impl(const float* G_rows, const int32_t* row_pos, int64_t n_sel, const float* Y,
-                                  const mmg_prologue_t* pro, const float* mean, const float* rstd,
-                                  const double* sums, double inv_count, float* dbeta, float* dgamma, const float* W,
-                                  float* dZ, float* dX, int64_t M, int N, int K, const mmg_next_bn_t* next,
-                                  const mmg_bnbwd_wgrad_t* wg, void* stream) {
-  MMG_CHECK_ARG(mmg_linear_bnbwd_supported(M, N, K) && K == 128 && N == 128,
-                "linear_bnbwd_rows: M=%lld N=%d K=%d unsupported (M > 512, K = N = 128)", (long long)M, N, K);
-  MMG_CHECK_ARG(Y && W && (dZ || wg) && dX && pro && row_pos, "linear_bnbwd_rows: null buffer");
-  MMG_CHECK_ARG(n_sel >= 0 && n_sel * (int64_t)K * 4 < (int64_t)0x7FFFFFFF && (G_rows || n_sel == 0), "linear_bnbwd_rows: bad row list");
-  MMG_CHECK_ARG(!pro->scale || (pro->shift && mean && rstd), "linear_bnbwd_rows: BatchNorm fold without shift / mean / rstd");
-  MMG_CHECK_ARG(pro->relu == MMG_ACT_NONE || pro->relu == MMG_ACT_RELU, "linear_bnbwd_rows: relu only");
-  MMG_CHECK_ARG(!sums || pro->scale, "linear_bnbwd_rows: sums without a BatchNorm fold");
-  const ProDev pr = mmg_pro_dev(pro);
-  BnBwdDev bb{Y, mean, rstd, sums, inv_count, dZ, dbeta, dgamma, 0.f, nullptr, row_pos, n_sel};
-  if (wg)
-    return bnbwd_wgrad_run<3>(G_rows ? G_rows : Y, bb, pr, mmg_pro_dev(nullptr), W, dX, M, next, wg, "linear_bnbwd_rows_wgrad",
-                              (hipStream_t)stream);
-  if (next && next_bn_fusable(next)) {
-    NextBnDev nb;
-    double* partial;
-    int rc0 = mmg_next_bn_dev(next, M, N, "linear_bnbwd_rows", &nb, &partial);
-    if (rc0) return rc0;
-    rc0 = launch_bnbwd_x6<128, 4, 3, true>(G_rows ? G_rows : Y, bb, pr, W, dX, M, (hipStream_t)stream, mmg_pro_dev(nullptr), nb, partial);
-    if (rc0) return rc0;
-    MMG_CHECK_LAUNCH("linear_bnbwd_rows");
-    return mmg_next_bn_finish(next, partial, N, (int)bnbwd_x6_rows(M, K), stream);
+extern "C" int mmg_linear_bnbwd(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
+                                const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, void* stream) {
+  MMG_CHECK_ARG(a, "linear_bnbwd: null descriptor");
+  MMG_CHECK_ARG(a->mode >= MMG_BNBWD_BN && a->mode <= MMG_BNBWD_ROWS, "linear_bnbwd: unknown mode %d", a->mode);
+  const auto& m = kBnBwdMode[a->mode];
+  const char* what = m.name;
+  MMG_CHECK_ARG(!next || a->mode != MMG_BNBWD_BN2, "%s: no next-BatchNorm statistics with two upstream gradients", what);
+  MMG_CHECK_ARG(mmg_linear_bnbwd_supported(a->mode, M, N, K, wg != nullptr), "%s: M=%lld N=%d K=%d%s unsupported", what,
+                (long long)M, N, K, wg ? " with a weight gradient" : "");
+  MMG_CHECK_ARG(a->y && W && (dZ || wg) && dX && (a->G || !m.G) && (a->G2 || !m.G2) && (a->row_pos || !m.row_pos) &&
+                    (a->pro || !m.pro) && (a->pro2 || !m.pro2) && (a->rnorm || !m.rnorm),
+                "%s: null buffer", what);
+  const bool l2 = a->mode == MMG_BNBWD_L2, rows = a->mode == MMG_BNBWD_ROWS;
+  if (rows)
+    MMG_CHECK_ARG(a->n_sel >= 0 && a->n_sel * (int64_t)K * 4 < (int64_t)0x7FFFFFFF && (a->G || a->n_sel == 0),
+                  "%s: bad row list", what);
+  if (!l2) {
+    const mmg_prologue_t* pro = a->pro;
+    MMG_CHECK_ARG(!pro || !pro->scale || (pro->shift && a->mean && a->rstd), "%s: BatchNorm fold without shift / mean / rstd", what);
+    MMG_CHECK_ARG(!pro || pro->relu == MMG_ACT_NONE || pro->relu == MMG_ACT_RELU, "%s: relu only", what);
+    MMG_CHECK_ARG(!a->sums || (pro && pro->scale), "%s: sums without a BatchNorm fold", what);
   }
-  int rc = launch_bnbwd_x6<128, 4, 3>(G_rows ? G_rows : Y, bb, pr, W, dX, M, (hipStream_t)stream);
-  if (rc) return rc;
-  MMG_CHECK_LAUNCH("linear_bnbwd_rows");
-  return next ? mmg_next_bn_fallback(dX, M, N, next, "linear_bnbwd_rows", stream) : MMG_OK;
-}
-
-extern "C" int mmg_linear_bnbwd_rows_next_bn(const float* G_rows, const int32_t* row_pos, int64_t n_sel, const float* Y,
-                                             const mmg_prologue_t* pro, const float* mean, const float* rstd,
-                                             const double* sums, double inv_count, float* dbeta, float* dgamma, const float* W,
-                                             float* dZ, float* dX, int64_t M, int N, int K, const mmg_next_bn_t* next,
-                                             void* stream) {
-  return linear_bnbwd_rows_impl(G_rows, row_pos, n_sel, Y, pro, mean, rstd, sums, inv_count, dbeta, dgamma, W, dZ, dX, M, N, K,
-                                next, nullptr, stream);
-}
-
-extern "C" int mmg_linear_bnbwd_rows_wgrad(const float* G_rows, const int32_t* row_pos, int64_t n_sel, const float* Y,
-                                           const mmg_prologue_t* pro, const float* mean, const float* rstd,
-                                           const double* sums, double inv_count, float* dbeta, float* dgamma, const float* W,
-                                           float* dZ, float* dX, int64_t M, int N, int K, const mmg_next_bn_t* next,
-                                           const mmg_bnbwd_wgrad_t* wg, void* stream) {
-  MMG_CHECK_ARG(wg, "linear_bnbwd_rows_wgrad: null weight-gradient descriptor");
-  return linear_bnbwd_rows_impl(G_rows, row_pos, n_sel, Y, pro, mean, rstd, sums, inv_count, dbeta, dgamma, W, dZ, dX, M, N, K,
-                                next, wg, stream);
-}
-
-extern "C" int mmg_linear_l2bwd_next_bn(const float* G, const float* out, const float* rnorm, const float* W, float* dZ,
-                                        float* dX, int64_t M, int N, int K, float eps, const mmg_next_bn_t* next, void* stream);
-
-extern "C" int mmg_linear_l2bwd(const float* G, const float* out, const float* rnorm, const float* W, float* dZ, float* dX,
-                                int64_t M, int N, int K, float eps, void* stream) {
-  return mmg_linear_l2bwd_next_bn(G, out, rnorm, W, dZ, dX, M, N, K, eps, nullptr, stream);
-}
-
-static int linear_l2bwd_impl(const float* G, const float* out, const float* rnorm, const float* W, float* dZ, float* dX,
-                             int64_t M, int N, int K, float eps, const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg,
-                             void* stream) {
-  MMG_CHECK_ARG(mmg_linear_bnbwd_supported(M, N, K), "linear_l2bwd: M=%lld N=%d K=%d unsupported (M > 512, K and N in {64,128})",
-                (long long)M, N, K);
-  MMG_CHECK_ARG(!wg || (K == 128 && N == 128), "linear_l2bwd_wgrad: N=%d K=%d unsupported (K = N = 128)", N, K);
-  MMG_CHECK_ARG(G && out && rnorm && W && (dZ || wg) && dX, "linear_l2bwd: null buffer");
-  const ProDev pr = mmg_pro_dev(nullptr);
-  BnBwdDev bb{out, rnorm, nullptr, nullptr, 0.0, dZ, nullptr, nullptr, eps, nullptr, nullptr, 0};
+  const BnBwdDev bb = l2 ? BnBwdDev{a->y, a->rnorm, nullptr, nullptr, 0.0, dZ, nullptr, nullptr, a->eps, nullptr, nullptr, 0}
+                         : BnBwdDev{a->y, a->mean, a->rstd, a->sums, a->inv_count, dZ, a->dbeta, a->dgamma, 0.f,
+                                    a->mode == MMG_BNBWD_BN2 ? a->G2 : nullptr, rows ? a->row_pos : nullptr, rows ? a->n_sel : 0};
+  const ProDev pr = mmg_pro_dev(l2 ? nullptr : a->pro), pr2 = mmg_pro_dev(a->mode == MMG_BNBWD_BN2 ? a->pro2 : nullptr);
+  const float* G = rows && !a->G ? a->y : a->G;   // an empty row list: no row of G is read
   hipStream_t st = (hipStream_t)stream;
-  if (wg) return bnbwd_wgrad_run<1>(G, bb, pr, mmg_pro_dev(nullptr), W, dX, M, next, wg, "linear_l2bwd_wgrad", st);
-  int rc;
-  if (next && K == 128 && N == 128 && next_bn_fusable(next)) {
-    NextBnDev nb;
-    double* partial;
-    rc = mmg_next_bn_dev(next, M, N, "linear_l2bwd", &nb, &partial);
-    if (rc) return rc;
-    rc = launch_bnbwd_x6<128, 4, 1, true>(G, bb, pr, W, dX, M, st, mmg_pro_dev(nullptr), nb, partial);
-    if (rc) return rc;
-    MMG_CHECK_LAUNCH("linear_l2bwd");
-    return mmg_next_bn_finish(next, partial, N, (int)bnbwd_x6_rows(M, K), stream);
+  switch (a->mode) {
+    case MMG_BNBWD_BN: return bnbwd_run<MMG_BNBWD_BN>(G, bb, pr, pr2, W, dX, M, N, K, next, wg, what, st);
+    case MMG_BNBWD_L2: return bnbwd_run<MMG_BNBWD_L2>(G, bb, pr, pr2, W, dX, M, N, K, next, wg, what, st);
+    case MMG_BNBWD_BN2: return bnbwd_run<MMG_BNBWD_BN2>(G, bb, pr, pr2, W, dX, M, N, K, next, wg, what, st);
+    default: return bnbwd_run<MMG_BNBWD_ROWS>(G, bb, pr, pr2, W, dX, M, N, K, next, wg, what, st);
   }
-  if (K == 128) rc = N == 128 ? launch_bnbwd_x6<128, 4, 1>(G, bb, pr, W, dX, M, st) : launch_bnbwd_x6<128, 2, 1>(G, bb, pr, W, dX, M, st);
-  else rc = N == 128 ? launch_bnbwd_x6<64, 4, 1>(G, bb, pr, W, dX, M, st) : launch_bnbwd_x6<64, 2, 1>(G, bb, pr, W, dX, M, st);
-  if (rc) return rc;
-  MMG_CHECK_LAUNCH("linear_l2bwd");
-  return next ? mmg_next_bn_fallback(dX, M, N, next, "linear_l2bwd", stream) : MMG_OK;
-}
-
-extern "C" int mmg_linear_l2bwd_next_bn(const float* G, const float* out, const float* rnorm, const float* W, float* dZ,
-                                        float* dX, int64_t M, int N, int K, float eps, const mmg_next_bn_t* next, void* stream) {
-  return linear_l2bwd_impl(G, out, rnorm, W, dZ, dX, M, N, K, eps, next, nullptr, stream);
-}
-
-extern "C" int mmg_linear_l2bwd_wgrad(const float* G, const float* out, const float* rnorm, const float* W, float* dZ,
-                                      float* dX, int64_t M, int N, int K, float eps, const mmg_next_bn_t* next,
-                                      const mmg_bnbwd_wgrad_t* wg, void* stream) {
-  MMG_CHECK_ARG(wg, "linear_l2bwd_wgrad: null weight-gradient descriptor");
-  return linear_l2bwd_impl(G, out, rnorm, W, dZ, dX, M, N, K, eps, next, wg, stream);
 }
 
 extern "C" size_t mmg_linear_wgrad_ws_bytes(int64_t M, int N, int K) {

@@ -871,7 +871,7 @@ class _Run:
             dbg = torch.empty(2, y.shape[1], device=y.device)   # d beta | d gamma, written by the apply kernel
             W4 = self.W(f"{pt}.4.weight")
             if enc.get("row_pos") is not None and pro.relu in (0, 1) and fold.training and \
-                    ops.linear_bnbwd2_supported(y.shape[0], W4.shape[1], y.shape[1]):
+                    ops.linear_bnbwd_supported(y.shape[0], W4.shape[1], y.shape[1], ops.BNBWD_ROWS):
                 # dense pass, row patch and the data-gradient GEMM of the second linear in ONE kernel (+ its weight gradient)
                 fw = self.fused_wgrad_for(enc["z1"], enc["pro1"], f"{pt}.4.weight", f"{pt}.4.bias", False,
                                           y.shape[0], W4.shape[1], W4.shape[0], next_bn=nxt is not None)

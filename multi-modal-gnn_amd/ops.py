@@ -13,7 +13,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import _lib
-from ._lib import (BnFinT, HeadGradT, HeadT, NextBnT, PairSavedT, PrologueT, RelT, SmallBnBwdT, SmallBnT, SmallFwdT, SmallWgradT, SumJobT, WgradReduceT, BnBwdWgradT,
+from ._lib import (BnFinT, HeadGradT, HeadT, NextBnT, PairSavedT, PrologueT, RelT, SmallBnBwdT, SmallBnT, SmallFwdT, SmallWgradT, SumJobT, WgradReduceT, BnBwdT, BnBwdWgradT,
                    check)
 
 BN_MOMENTUM = 0.1
@@ -622,18 +622,21 @@ def linear_l2norm_fwd(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Ten
     return out, rn
 
 
-def linear_bnbwd_supported(M: int, N: int, K: int) -> bool:
-    return bool(_lib.load().mmg_linear_bnbwd_supported(int(M), int(N), int(K)))
+BNBWD_BN, BNBWD_L2, BNBWD_BN2, BNBWD_ROWS = range(4)        # mmg_bnbwd_t.mode: linear_bnbwd / _l2bwd / _bnbwd2 / _bnbwd_rows
+
+
+def linear_bnbwd_supported(M: int, N: int, K: int, mode: int = BNBWD_BN, wgrad: bool = False) -> bool:
+    return bool(_lib.load().mmg_linear_bnbwd_supported(int(mode), int(M), int(N), int(K), int(wgrad)))
 
 
 def linear_bnbwd_wgrad_supported(M: int, N: int, K: int) -> bool:
-    return bool(_lib.load().mmg_linear_bnbwd_wgrad_supported(int(M), int(N), int(K)))
+    return linear_bnbwd_supported(M, N, K, wgrad=True)
 
 
 @dataclass
 class FusedWgrad:
     """The weight gradient of the layer whose data gradient a linear_bnbwd / linear_bnbwd2 / linear_bnbwd_rows /
-    linear_l2bwd call computes, in the same launch (mmg_*_wgrad): out[K,N] (+)= dz^T @ pro(x), and with with_bias the
+    linear_l2bwd call computes, in the same launch (mmg_bnbwd_wgrad_t): out[K,N] (+)= dz^T @ pro(x), and with with_bias the
     column sums of dz; the arguments mean what they mean for linear_wgrad(dz, x, pro, out, accumulate, with_bias, bias_out,
     defer).  keep_dz=False: dz is not written (the call returns None in its place).  The call fills .dW and .db."""
     x: torch.Tensor
@@ -679,77 +682,72 @@ def _fused_wgrad_bytes(M: int, N: int, K: int) -> int:      # x read once, one s
     return 4 * M * N + 4 * int(_lib.load().mmg_linear_bnbwd_wgrad_ws_bytes(M, N, K))
 
 
+# mode -> (profiler name, [M,K] tensors the kernel reads): g and y; g, g2 and y; y (the listed rows are not counted);
+# g and out
+_BNBWD_PROF = {BNBWD_BN: ("linear_bnbwd", 2), BNBWD_BN2: ("linear_bnbwd", 3), BNBWD_ROWS: ("linear_bnbwd", 1),
+               BNBWD_L2: ("linear_l2bwd", 2)}
+
+
+def _addr(t: Optional[torch.Tensor], dtype=torch.float32):
+    return t.data_ptr() if _p(t, dtype) is not None else None
+
+
+def _linear_bnbwd(mode: int, y: torch.Tensor, W: torch.Tensor, next_bn: Optional["NextBN"], wgrad: Optional[FusedWgrad],
+                  g=None, g2=None, row_pos=None, n_sel=0, pro: Optional[Pro] = None, pro2: Optional[Pro] = None,
+                  fold: Optional[BNFold] = None, sums=None, count: float = 1.0, dbeta=None, dgamma=None, rn=None):
+    """The one call behind linear_bnbwd / linear_bnbwd2 / linear_bnbwd_rows / linear_l2bwd (mmg_linear_bnbwd; the
+    descriptor fields as mmg_bnbwd_t names them).  -> (dz, dx), + the next BatchNorm's sums with next_bn."""
+    lib = _lib.load()
+    M, K = y.shape
+    if W.shape[0] != K:
+        raise ValueError(f"{_BNBWD_PROF[mode][0]}: W has {W.shape[0]} rows, y has {K} columns")
+    N = W.shape[1]
+    dz = torch.empty_like(y) if wgrad is None or wgrad.keep_dz else None
+    dx = torch.empty(M, N, device=y.device)
+    name, reads = _BNBWD_PROF[mode]
+    nbytes = 4 * (reads * M * K + (M * K if dz is not None else 0) + M * N)
+    if wgrad is not None:
+        name += "_wgrad"
+        nbytes += _fused_wgrad_bytes(M, N, K) + (4 * M if mode == BNBWD_L2 else 0)       # + rn
+    elif next_bn is not None:
+        nbytes += 4 * M * N                                                              # + the next BatchNorm's y
+    _tok = _pb(name)
+    nbt, nsums = _next_bn(next_bn, M, N) if next_bn is not None else (None, None)
+    wt = _fused_wgrad(wgrad, M, N, K) if wgrad is not None else None
+    pcs = [q.c() if q is not None else None for q in (pro, pro2)]          # alive until the call returns
+    desc = BnBwdT(mode, _addr(g), _addr(g2), _addr(row_pos, torch.int32), n_sel, _addr(y),
+                  *[C.pointer(pc) if pc is not None else None for pc in pcs],
+                  _addr(fold.mean) if fold else None, _addr(fold.rstd) if fold else None, _addr(sums, torch.float64),
+                  1.0 / float(count), _addr(dbeta), _addr(dgamma), _addr(rn), L2_EPS)
+    check(lib.mmg_linear_bnbwd(C.byref(desc), _p(W), _p(dz), _p(dx), M, N, K, C.byref(nbt) if nbt is not None else None,
+                               C.byref(wt) if wt is not None else None, _stream()), "mmg_linear_bnbwd")
+    if wgrad is not None:
+        _fused_wgrad_done(wgrad, wt)
+    _pe(_tok, name, nbytes, (4 if wgrad is not None else 2) * M * N * K)
+    return (dz, dx, nsums) if next_bn is not None else (dz, dx)
+
+
 def linear_bnbwd(g: torch.Tensor, y: torch.Tensor, pro: Pro, fold: Optional[BNFold], W: torch.Tensor, sums=None,
                  count: float = 1.0, dbeta=None, dgamma=None, next_bn: Optional["NextBN"] = None,
                  wgrad: Optional[FusedWgrad] = None):
     """bn_bwd_apply(g, y, ...) and the data gradient dz @ W of the linear in front of that BatchNorm in ONE pass over g and
     y (mmg_linear_bnbwd): -> (dz [M,K], dx [M,N]).  W [K, N] is the forward weight of the linear, read in place.
-    wgrad: the layer's weight gradient in the same launch (mmg_linear_bnbwd_wgrad, see FusedWgrad)."""
-    lib = _lib.load()
-    M, K = y.shape
-    if W.shape[0] != K:
-        raise ValueError(f"linear_bnbwd: W has {W.shape[0]} rows, y has {K} columns")
-    N = W.shape[1]
-    dz = torch.empty_like(y) if wgrad is None or wgrad.keep_dz else None
-    dx = torch.empty(M, N, device=y.device)
-    if wgrad is not None:
-        _tok = _pb("linear_bnbwd_wgrad")
-        nbt, nsums = _next_bn(next_bn, M, N) if next_bn is not None else (None, None)
-        wt = _fused_wgrad(wgrad, M, N, K)
-        check(lib.mmg_linear_bnbwd_wgrad(_p(g), _p(y), _pro(pro), _p(fold.mean) if fold else None,
-                                         _p(fold.rstd) if fold else None, _p(sums, torch.float64), 1.0 / float(count),
-                                         _p(dbeta), _p(dgamma), _p(W), _p(dz), _p(dx), M, N, K,
-                                         C.byref(nbt) if nbt is not None else None, C.byref(wt), _stream()),
-              "mmg_linear_bnbwd_wgrad")
-        _fused_wgrad_done(wgrad, wt)
-        _pe(_tok, "linear_bnbwd_wgrad", 4 * (2 * M * K + (M * K if dz is not None else 0) + M * N)
-            + _fused_wgrad_bytes(M, N, K), 4 * M * N * K)
-        return (dz, dx, nsums) if next_bn is not None else (dz, dx)
-    _tok = _pb("linear_bnbwd")
-    if next_bn is not None:       # -> (dz, dx, the statistics of the BatchNorm backward that consumes dx), see NextBN
-        nbt, nsums = _next_bn(next_bn, M, N)
-        check(lib.mmg_linear_bnbwd_next_bn(_p(g), _p(y), _pro(pro), _p(fold.mean) if fold else None,
-                                           _p(fold.rstd) if fold else None, _p(sums, torch.float64), 1.0 / float(count),
-                                           _p(dbeta), _p(dgamma), _p(W), _p(dz), _p(dx), M, N, K, C.byref(nbt), _stream()),
-              "mmg_linear_bnbwd_next_bn")
-        _pe(_tok, "linear_bnbwd", 4 * (3 * M * K + 2 * M * N), 2 * M * N * K)
-        return dz, dx, nsums
-    check(lib.mmg_linear_bnbwd(_p(g), _p(y), _pro(pro), _p(fold.mean) if fold else None, _p(fold.rstd) if fold else None,
-                               _p(sums, torch.float64), 1.0 / float(count), _p(dbeta), _p(dgamma), _p(W), _p(dz), _p(dx),
-                               M, N, K, _stream()), "mmg_linear_bnbwd")
-    _pe(_tok, "linear_bnbwd", 4 * (3 * M * K + M * N), 2 * M * N * K)
-    return dz, dx
+    next_bn: + the statistics of the BatchNorm backward that consumes dx (see NextBN).
+    wgrad: the layer's weight gradient in the same launch (see FusedWgrad)."""
+    return _linear_bnbwd(BNBWD_BN, y, W, next_bn, wgrad, g=g, pro=pro, fold=fold, sums=sums, count=count, dbeta=dbeta,
+                         dgamma=dgamma)
 
 
 def linear_bnbwd2_supported(M: int, N: int, K: int) -> bool:
-    return N == 128 and K == 128 and linear_bnbwd_supported(M, N, K)
+    return linear_bnbwd_supported(M, N, K, BNBWD_BN2)
 
 
 def linear_bnbwd2(g: torch.Tensor, g2: torch.Tensor, y: torch.Tensor, pro: Pro, pro2: Pro, fold: BNFold, W: torch.Tensor,
                   sums, count, dbeta=None, dgamma=None, wgrad: Optional[FusedWgrad] = None):
     """bn_bwd_apply2 (two upstream gradients, own dropout masks) + the data gradient dz @ W in one pass -> (dz, dx).
-    wgrad: the layer's weight gradient in the same launch (mmg_linear_bnbwd2_wgrad, see FusedWgrad)."""
-    lib = _lib.load()
-    M, K = y.shape
-    N = W.shape[1]
-    dz = torch.empty_like(y) if wgrad is None or wgrad.keep_dz else None
-    dx = torch.empty(M, N, device=y.device)
-    if wgrad is not None:
-        _tok = _pb("linear_bnbwd_wgrad")
-        wt = _fused_wgrad(wgrad, M, N, K)
-        check(lib.mmg_linear_bnbwd2_wgrad(_p(g), _p(g2), _p(y), _pro(pro), _pro(pro2), _p(fold.mean), _p(fold.rstd),
-                                          _p(sums, torch.float64), 1.0 / float(count), _p(dbeta), _p(dgamma), _p(W), _p(dz),
-                                          _p(dx), M, N, K, C.byref(wt), _stream()), "mmg_linear_bnbwd2_wgrad")
-        _fused_wgrad_done(wgrad, wt)
-        _pe(_tok, "linear_bnbwd_wgrad", 4 * (3 * M * K + (M * K if dz is not None else 0) + M * N)
-            + _fused_wgrad_bytes(M, N, K), 4 * M * N * K)
-        return dz, dx
-    _tok = _pb("linear_bnbwd")
-    check(lib.mmg_linear_bnbwd2(_p(g), _p(g2), _p(y), _pro(pro), _pro(pro2), _p(fold.mean), _p(fold.rstd),
-                                _p(sums, torch.float64), 1.0 / float(count), _p(dbeta), _p(dgamma), _p(W), _p(dz), _p(dx),
-                                M, N, K, _stream()), "mmg_linear_bnbwd2")
-    _pe(_tok, "linear_bnbwd", 4 * (4 * M * K + M * N), 2 * M * N * K)
-    return dz, dx
+    wgrad: the layer's weight gradient in the same launch (see FusedWgrad)."""
+    return _linear_bnbwd(BNBWD_BN2, y, W, None, wgrad, g=g, g2=g2, pro=pro, pro2=pro2, fold=fold, sums=sums, count=count,
+                         dbeta=dbeta, dgamma=dgamma)
 
 
 def linear_bnbwd_rows(g_rows: torch.Tensor, row_pos: torch.Tensor, y: torch.Tensor, pro: Pro, fold: BNFold, W: torch.Tensor,
@@ -757,86 +755,28 @@ def linear_bnbwd_rows(g_rows: torch.Tensor, row_pos: torch.Tensor, y: torch.Tens
                       wgrad: Optional[FusedWgrad] = None):
     """bn_bwd_apply(None, ...) + bn_bwd_apply_rows(g_rows, ...) + the data gradient dz @ W in one pass -> (dz, dx): the
     upstream gradient is zero outside the listed rows; row_pos [M] int32 = position of a row in the list or -1.
-    wgrad: the layer's weight gradient in the same launch (mmg_linear_bnbwd_rows_wgrad, see FusedWgrad)."""
-    lib = _lib.load()
-    M, K = y.shape
-    N = W.shape[1]
-    dz = torch.empty_like(y) if wgrad is None or wgrad.keep_dz else None
-    dx = torch.empty(M, N, device=y.device)
-    if wgrad is not None:
-        _tok = _pb("linear_bnbwd_wgrad")
-        nbt, nsums = _next_bn(next_bn, M, N) if next_bn is not None else (None, None)
-        wt = _fused_wgrad(wgrad, M, N, K)
-        check(lib.mmg_linear_bnbwd_rows_wgrad(_p(g_rows) if g_rows.numel() else None, _p(row_pos, torch.int32),
-                                              g_rows.shape[0], _p(y), _pro(pro), _p(fold.mean), _p(fold.rstd),
-                                              _p(sums, torch.float64), 1.0 / float(count), _p(dbeta), _p(dgamma), _p(W),
-                                              _p(dz), _p(dx), M, N, K, C.byref(nbt) if nbt is not None else None,
-                                              C.byref(wt), _stream()), "mmg_linear_bnbwd_rows_wgrad")
-        _fused_wgrad_done(wgrad, wt)
-        _pe(_tok, "linear_bnbwd_wgrad", 4 * (M * K + (M * K if dz is not None else 0) + M * N)
-            + _fused_wgrad_bytes(M, N, K), 4 * M * N * K)
-        return (dz, dx, nsums) if next_bn is not None else (dz, dx)
-    _tok = _pb("linear_bnbwd")
-    if next_bn is not None:       # -> (dz, dx, the statistics of the BatchNorm backward that consumes dx), see NextBN
-        nbt, nsums = _next_bn(next_bn, M, N)
-        check(lib.mmg_linear_bnbwd_rows_next_bn(_p(g_rows) if g_rows.numel() else None, _p(row_pos, torch.int32),
-                                                g_rows.shape[0], _p(y), _pro(pro), _p(fold.mean), _p(fold.rstd),
-                                                _p(sums, torch.float64), 1.0 / float(count), _p(dbeta), _p(dgamma), _p(W),
-                                                _p(dz), _p(dx), M, N, K, C.byref(nbt), _stream()),
-              "mmg_linear_bnbwd_rows_next_bn")
-        _pe(_tok, "linear_bnbwd", 4 * (2 * M * K + 2 * M * N), 2 * M * N * K)
-        return dz, dx, nsums
-    check(lib.mmg_linear_bnbwd_rows(_p(g_rows) if g_rows.numel() else None, _p(row_pos, torch.int32), g_rows.shape[0], _p(y),
-                                    _pro(pro), _p(fold.mean), _p(fold.rstd), _p(sums, torch.float64), 1.0 / float(count),
-                                    _p(dbeta), _p(dgamma), _p(W), _p(dz), _p(dx), M, N, K, _stream()),
-          "mmg_linear_bnbwd_rows")
-    _pe(_tok, "linear_bnbwd", 4 * (2 * M * K + M * N), 2 * M * N * K)
-    return dz, dx
+    next_bn / wgrad: as for linear_bnbwd."""
+    return _linear_bnbwd(BNBWD_ROWS, y, W, next_bn, wgrad, g=g_rows if g_rows.numel() else None, row_pos=row_pos,
+                         n_sel=g_rows.shape[0], pro=pro, fold=fold, sums=sums, count=count, dbeta=dbeta, dgamma=dgamma)
 
 
 def linear_l2bwd(g: torch.Tensor, out: torch.Tensor, rn: torch.Tensor, W: torch.Tensor, next_bn: Optional["NextBN"] = None,
                  wgrad: Optional[FusedWgrad] = None):
     """l2norm_bwd(g, out, rn) and the data gradient dz @ W of the linear in front of the normalisation -> (dz, dx): ONE
-    kernel where mmg_linear_bnbwd_supported (W [K, N] = the forward weight in place), the two launches elsewhere.
-    wgrad: the layer's weight gradient in the same launch (mmg_linear_l2bwd_wgrad, see FusedWgrad; the caller checks
-    linear_bnbwd_wgrad_supported)."""
-    lib = _lib.load()
+    kernel where linear_bnbwd_supported (W [K, N] = the forward weight in place), the two launches elsewhere.
+    next_bn / wgrad: as for linear_bnbwd (the caller checks linear_bnbwd_wgrad_supported)."""
     M, K = out.shape
     N = W.shape[1]
     if W.shape[0] != K:
         raise ValueError(f"linear_l2bwd: W has {W.shape[0]} rows, out has {K} columns")
-    if wgrad is not None:
-        if not lib.mmg_linear_bnbwd_wgrad_supported(M, N, K):
+    if not linear_bnbwd_supported(M, N, K, BNBWD_L2, wgrad is not None):
+        if wgrad is not None:
             raise ValueError(f"linear_l2bwd: no fused weight gradient for M={M} N={N} K={K}")
-        dz = torch.empty_like(out) if wgrad.keep_dz else None
-        dx = torch.empty(M, N, device=out.device)
-        _tok = _pb("linear_l2bwd_wgrad")
-        nbt, nsums = _next_bn(next_bn, M, N) if next_bn is not None else (None, None)
-        wt = _fused_wgrad(wgrad, M, N, K)
-        check(lib.mmg_linear_l2bwd_wgrad(_p(g), _p(out), _p(rn), _p(W), _p(dz), _p(dx), M, N, K, L2_EPS,
-                                         C.byref(nbt) if nbt is not None else None, C.byref(wt), _stream()),
-              "mmg_linear_l2bwd_wgrad")
-        _fused_wgrad_done(wgrad, wt)
-        _pe(_tok, "linear_l2bwd_wgrad", 4 * (2 * M * K + (M * K if dz is not None else 0) + M * N + M)
-            + _fused_wgrad_bytes(M, N, K), 4 * M * N * K)
-        return (dz, dx, nsums) if next_bn is not None else (dz, dx)
-    if not lib.mmg_linear_bnbwd_supported(M, N, K):
         dz = l2norm_bwd(g, out, rn)
         if next_bn is not None:
             return (dz,) + tuple(linear_fwd(dz, W, w_kn=True, next_bn=next_bn))
         return dz, linear_fwd(dz, W, w_kn=True)
-    dz = torch.empty_like(out)
-    dx = torch.empty(M, N, device=out.device)
-    _tok = _pb("linear_l2bwd")
-    if next_bn is not None:       # -> (dz, dx, the statistics of the BatchNorm backward that consumes dx), see NextBN
-        nbt, nsums = _next_bn(next_bn, M, N)
-        check(lib.mmg_linear_l2bwd_next_bn(_p(g), _p(out), _p(rn), _p(W), _p(dz), _p(dx), M, N, K, L2_EPS, C.byref(nbt),
-                                           _stream()), "mmg_linear_l2bwd_next_bn")
-        _pe(_tok, "linear_l2bwd", 4 * (3 * M * K + 2 * M * N), 2 * M * N * K)
-        return dz, dx, nsums
-    check(lib.mmg_linear_l2bwd(_p(g), _p(out), _p(rn), _p(W), _p(dz), _p(dx), M, N, K, L2_EPS, _stream()), "mmg_linear_l2bwd")
-    _pe(_tok, "linear_l2bwd", 4 * (3 * M * K + M * N), 2 * M * N * K)
-    return dz, dx
+    return _linear_bnbwd(BNBWD_L2, out, W, next_bn, wgrad, g=g, rn=rn)
 
 
 def l2norm_fwd(z: torch.Tensor):

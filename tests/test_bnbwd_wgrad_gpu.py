@@ -1,5 +1,5 @@
-"""The weight gradient inside the BatchNorm-backward data-gradient GEMMs (mmg_linear_bnbwd_wgrad, mmg_linear_bnbwd2_wgrad,
-mmg_linear_bnbwd_rows_wgrad, mmg_linear_l2bwd_wgrad) against the plain GEMM followed by mmg_linear_wgrad.
+"""The weight gradient inside the BatchNorm-backward data-gradient GEMMs (mmg_linear_bnbwd with a mmg_bnbwd_wgrad_t, every
+mode) against the plain GEMM followed by mmg_linear_wgrad.
 
 dZ, dX and d beta / d gamma bit for bit; dW and db bit for bit what mmg_linear_wgrad computes (the fused kernel takes
 its sums over the same row sets in the same order), and within the bars of test_ops_gpu.py::test_linear_wgrad_shapes

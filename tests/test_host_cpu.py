@@ -44,6 +44,39 @@ def test_argument_errors_are_reported_without_a_gpu():
     rc = lib.mmg_csr_build(None, 10, 4, 2, None, None, None, None, 0, None)
     assert rc == -1
     assert lib.mmg_csr_build_ws_bytes(1000, 100) > 3 * 4000
+    # the BatchNorm / L2-norm backward GEMM: the shape rules of every mode live in one query ...
+    BN, L2, BN2, ROWS = 0, 1, 2, 3
+    sup = lib.mmg_linear_bnbwd_supported
+    assert sup(BN, 600, 64, 64, 0) and sup(L2, 600, 128, 64, 0) and sup(BN2, 600, 128, 128, 0) and sup(ROWS, 513, 128, 128, 1)
+    assert not sup(BN, 512, 128, 128, 0) and not sup(BN2, 600, 64, 128, 0) and not sup(ROWS, 600, 128, 64, 0)
+    assert not sup(BN, 600, 64, 128, 1) and not sup(L2, 600, 128, 256, 0) and not sup(4, 600, 128, 128, 0)
+    # ... and the entry point refuses a bad descriptor on the host side (the buffers are never touched)
+    fake = ctypes.c_void_p(256)
+    pro = _lib.PrologueT()
+
+    def bnbwd(mode, M=1000, N=128, K=128, nxt=None, **fields):
+        d = _lib.BnBwdT(mode, fake, fake, fake, 0, fake, ctypes.pointer(pro), ctypes.pointer(pro), fake, fake, None, 1.0,
+                        None, None, fake, 1e-12)
+        for k, v in fields.items():
+            setattr(d, k, v)
+        rc = lib.mmg_linear_bnbwd(ctypes.byref(d), fake, fake, fake, M, N, K, nxt, None, None)
+        return rc, lib.mmg_last_error()
+
+    assert lib.mmg_linear_bnbwd(None, fake, fake, fake, 1000, 128, 128, None, None, None) == -1
+    assert b"null descriptor" in lib.mmg_last_error()
+    for mode in (-1, 4):
+        rc, msg = bnbwd(mode)
+        assert rc == -1 and b"unknown mode" in msg
+    rc, msg = bnbwd(BN2, nxt=ctypes.byref(_lib.NextBnT()))
+    assert rc == -1 and b"next-BatchNorm" in msg
+    for mode, M, N, K in ((BN, 512, 128, 128), (L2, 1000, 256, 128), (BN2, 1000, 64, 128), (ROWS, 1000, 128, 64)):
+        rc, msg = bnbwd(mode, M, N, K)
+        assert rc == -1 and b"unsupported" in msg
+    for mode, field in ((BN, "G"), (BN, "y"), (L2, "rnorm"), (BN2, "G2"), (BN2, "pro2"), (ROWS, "row_pos"), (ROWS, "pro")):
+        rc, msg = bnbwd(mode, **{field: None})
+        assert rc == -1 and b"null buffer" in msg, (mode, field)
+    rc, msg = bnbwd(ROWS, G=None, n_sel=5)
+    assert rc == -1 and b"bad row list" in msg
 
 
 def test_cpu_model_fails_loudly():

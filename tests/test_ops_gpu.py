@@ -627,7 +627,7 @@ def test_l2_norm_inside_the_dense_forward(ops, dev, M, K, N, with_pro):
 @pytest.mark.parametrize("p", [0.0, 0.3])
 @pytest.mark.parametrize("n_sel", [0, 1, 157])
 def test_row_list_bn_backward_inside_the_data_gradient_gemm(ops, dev, p, n_sel):
-    """mmg_linear_bnbwd_rows == mmg_bn_bwd_apply(G = NULL) + mmg_bn_bwd_apply_rows + mmg_linear_fwd(W_KN): the upstream
+    """mmg_linear_bnbwd, mode ROWS == mmg_bn_bwd_apply(G = NULL) + mmg_bn_bwd_apply_rows + mmg_linear_fwd(W_KN): the upstream
     gradient is zero outside a row list (rows of the last, partial tile included)."""
     gen = torch.Generator().manual_seed(321 + n_sel)
     M, K, N = 4999, 128, 128
@@ -660,7 +660,7 @@ def test_row_list_bn_backward_inside_the_data_gradient_gemm(ops, dev, p, n_sel):
 
 @pytest.mark.parametrize("p", [0.0, 0.3])
 def test_joint_bn_backward_inside_the_data_gradient_gemm(ops, dev, p):
-    """mmg_linear_bnbwd2 == mmg_bn_bwd_apply2 followed by mmg_linear_fwd(W_KN), bit for bit."""
+    """mmg_linear_bnbwd, mode BN2 == mmg_bn_bwd_apply2 followed by mmg_linear_fwd(W_KN), bit for bit."""
     gen = torch.Generator().manual_seed(123)
     M, K, N = 4999, 128, 128
     y = (torch.randn(M, K, generator=gen) * 1.5 + 0.2).to(dev)
@@ -681,7 +681,7 @@ def test_joint_bn_backward_inside_the_data_gradient_gemm(ops, dev, p):
 
 @pytest.mark.parametrize("M,K,N", [(5003, 128, 128), (4100, 128, 64), (3333, 64, 128), (600, 64, 64), (300, 128, 128)])
 def test_l2_norm_backward_inside_the_data_gradient_gemm(ops, dev, M, K, N):
-    """mmg_linear_l2bwd == mmg_l2norm_bwd followed by mmg_linear_fwd(W_KN) (the row dot product is summed in another
+    """mmg_linear_bnbwd, mode L2 == mmg_l2norm_bwd followed by mmg_linear_fwd(W_KN) (the row dot product is summed in another
     order), against fp64 autograd of F.normalize; a clamped (all-zero) row keeps dz = g / eps."""
     gen = torch.Generator().manual_seed(9 + M)
     z = torch.randn(M, K, generator=gen)
@@ -1290,7 +1290,7 @@ def test_next_bn_statistics_from_the_linear_epilogue(ops, dev, M, N, K, relu, p)
 @pytest.mark.parametrize("p", [0.0, 0.3])
 @pytest.mark.parametrize("M,K,N", [(5003, 128, 128), (3000, 64, 128)])
 def test_next_bn_statistics_from_the_l2_and_bn_backward_gemms(ops, dev, M, K, N, p):
-    """mmg_linear_l2bwd_next_bn / mmg_linear_bnbwd_next_bn / mmg_linear_bnbwd_rows_next_bn: dz and dx unchanged, the statistics
+    """mmg_linear_bnbwd with next, modes L2 / BN / ROWS: dz and dx unchanged, the statistics
     of the BatchNorm that consumes dx from the epilogue; two producers ADD into one set of sums (== mmg_bn_bwd_stats2)."""
     gen = torch.Generator().manual_seed(5 * M + K)
     W = (torch.randn(K, N, generator=gen) / K ** 0.5).to(dev)
