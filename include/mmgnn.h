@@ -104,28 +104,7 @@ size_t mmg_rel_mask_words(int64_t n_rows, int32_t n_cols);
 int mmg_rel_mask_build(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int32_t n_cols,
                        uint64_t* mask_t, uint16_t* mask_r, void* stream);
 
-int mmg_gather_rows(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D,
-                    float* out, int accumulate, void* stream);
-/* the same, plus col_sums[2,D] (fp64) = (sum_rows out, sum_rows out^2) of the FINAL output: the batch statistics of
- * the per-type BatchNorm that follows the HeteroConv sum (src/model.py:258-262), from the gather epilogue */
-/* Training-mode BatchNorm1d fold (what mmg_bn_finalize computes from the column sums: scale / shift / mean / rstd, running
- * statistics advanced n_updates times) taken in the SAME launch that sums the producers' partial statistics rows:
- * mmg_linear_fwd_stats_bn / mmg_gather_rows_stats_bn = mmg_linear_fwd_stats / mmg_gather_rows_stats + mmg_bn_finalize
- * (training = 1) with one launch less (col_sums still receives the sums).  Single-GPU form: a patient-sharded run has to
- * all-reduce the sums between the two. */
-typedef struct {
-  int64_t count;
-  const float* gamma; const float* beta;      /* [N], nullable: 1 / 0 */
-  float* running_mean; float* running_var;    /* [N], nullable: not advanced */
-  int n_updates;
-  float momentum; float eps;
-  float* scale; float* shift; float* mean; float* rstd;   /* [N] outputs; mean / rstd nullable */
-} mmg_bn_fin_t;
-size_t mmg_gather_rows_stats_ws_bytes(int64_t n_rows, int D);
-int mmg_gather_rows_stats(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D, float* out, int accumulate,
-                          double* col_sums, void* ws, size_t ws_bytes, void* stream);
-int mmg_gather_rows_stats_bn(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D, float* out, int accumulate,
-                             double* col_sums, void* ws, size_t ws_bytes, const mmg_bn_fin_t* fin, void* stream);
+/* mmg_gather_rows: below, with the producer epilogues */
 
 size_t mmg_scatter_rows_ws_bytes(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D);
 int mmg_scatter_rows(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D,
@@ -164,23 +143,74 @@ typedef struct {
  * weight in place instead of a transposed copy. */
 #define MMG_LIN_ACCUMULATE 1
 #define MMG_LIN_W_KN 2
-int mmg_linear_fwd(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias,
-                   float* Y, int64_t M, int N, int K, int flags, void* stream);
-/* the same, plus col_sums[2,N] (fp64) = (sum_m Y, sum_m Y^2): the batch statistics of the BatchNorm that follows
- * (src/model.py:95,99), taken in the GEMM epilogue instead of a second pass over Y */
-/* the same layer followed by the row L2 normalisation (patient_transform's last Linear + F.normalize(p=2, dim=1),
- * src/model.py:103,232) in one kernel: Y = y / max(|y|_2, eps) per row, rnorm[row] = 1 / max(|y|_2, eps) (what
- * mmg_l2norm_fwd returns; mmg_l2norm_bwd takes exactly these two).  Supported for M > 512, N and K in {64, 128}. */
-int mmg_linear_fwd_l2norm_supported(int64_t M, int N, int K);
-int mmg_linear_fwd_l2norm(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias, float* Y,
-                          float* rnorm, int64_t M, int N, int K, float eps, void* stream);
-size_t mmg_linear_fwd_stats_ws_bytes(int64_t M, int N);
-int mmg_linear_fwd_stats(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias,
-                         float* Y, int64_t M, int N, int K, int flags, double* col_sums, void* ws,
-                         size_t ws_bytes, void* stream);
-int mmg_linear_fwd_stats_bn(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias, float* Y,
-                            int64_t M, int N, int K, int flags, double* col_sums, void* ws, size_t ws_bytes,
-                            const mmg_bn_fin_t* fin, void* stream);
+/* Training-mode BatchNorm1d fold (what mmg_bn_finalize computes from the column sums, training = 1: scale / shift / mean /
+ * rstd, running statistics advanced n_updates times) taken in the launch that sums a producer's partial statistics rows.
+ * Single-GPU form: a patient-sharded run has to all-reduce the sums first. */
+typedef struct {
+  int64_t count;
+  const float* gamma; const float* beta;      /* [N], nullable: 1 / 0 */
+  float* running_mean; float* running_var;    /* [N], nullable: not advanced */
+  int n_updates;
+  float momentum; float eps;
+  float* scale; float* shift; float* mean; float* rstd;   /* [N] outputs; mean / rstd nullable */
+} mmg_bn_fin_t;
+/* The statistics pass of a BatchNorm backward taken from the kernel that PRODUCES its upstream gradient.
+ * mmg_bn_bwd_stats (and _stats2) read the [M, N] upstream gradient and the [M, N] pre-BatchNorm activation once more; a
+ * producer that is handed this descriptor sums them from its output tile while it is still in registers and only reads
+ * Y.  `sums` receives exactly what mmg_bn_bwd_stats(G = the producer's output, y, pro, mean, rstd) would, summed in a
+ * fixed order (16 rows in fp32, the rest in fp64); with accumulate != 0 that is ADDED to `sums` -- the two sums are
+ * linear in G, so two producers whose outputs go through the same BatchNorm with their own dropout masks (the two
+ * encode_nodes passes of a training step, mmg_bn_bwd_stats2) each add their share.
+ * Autograd of  nn.Linear -> BatchNorm1d -> ReLU -> Dropout  chains (src/model.py:93-101, 258-269): the gradient a layer
+ * hands down is the upstream gradient of the BatchNorm below it.  Fused (activation none or relu) in:
+ *   mmg_linear_fwd                  dX = dY . W  (MMG_LIN_W_KN) of a plain linear, e.g. the heads' first layer; no prologue,
+ *                                   no accumulate;  M > 512, N % 128 == 0, K in {64, 128}
+ *   mmg_linear_bnbwd                dX;  K = N = 128 without a weight gradient (not MMG_BNBWD_BN2: refused)
+ *   mmg_gather_rows                 the final `out` (accumulate or not);  the bit-plane layouts, D >= 128
+ * elsewhere the producer is followed by the separate statistics pass: defined for everything the producer accepts. */
+typedef struct {
+  const float* y;                 /* [M, N] pre-BatchNorm activation of the layer below */
+  const mmg_prologue_t* pro;      /* its fold (scale / shift), activation and dropout */
+  const float* mean;              /* [N] */
+  const float* rstd;              /* [N] */
+  double* sums;                   /* [2, N] out (in / out with accumulate) */
+  int accumulate;
+  void* ws;                       /* >= mmg_epi_ws_bytes(M, N) */
+  size_t ws_bytes;
+} mmg_next_bn_t;
+/* The epilogue of a producer (mmg_linear_fwd, mmg_gather_rows), computed from its output tile in registers instead of a
+ * second pass over the output.  epi->mode (epi == NULL: MMG_EPI_NONE):
+ *   MMG_EPI_NONE     the producer alone
+ *   MMG_EPI_STATS    col_sums [2, N] (fp64) = (sum_m Y, sum_m Y^2) of the FINAL output, the batch statistics of the
+ *                    BatchNorm that follows (src/model.py:95,99,258-262); fin (nullable) folds it in the same launch.
+ *                    M > 0.  The bf16-split GEMM (M > 512) and the bit-plane gathers sum them in their epilogue; other
+ *                    launches are followed by a separate column reduction.
+ *   MMG_EPI_NEXT_BN  the statistics of the BatchNorm backward that consumes the output, see mmg_next_bn_t
+ *   MMG_EPI_L2       linear only, no flags: the row L2 normalisation of the output (patient_transform's last Linear +
+ *                    F.normalize(p=2, dim=1), src/model.py:103,232) in the same kernel: Y = y / max(|y|_2, eps) per row,
+ *                    rnorm [M] = 1 / max(|y|_2, eps) (what mmg_l2norm_fwd returns and mmg_l2norm_bwd takes)
+ * Fields a mode does not name are ignored; a descriptor with both col_sums and next is refused.  The workspace of STATS
+ * and of every mmg_next_bn_t: mmg_epi_ws_bytes(M, N).
+ * mmg_linear_fwd_supported: L2 needs M > 512 and N, K in {64, 128}; the other modes take every shape of the plain GEMM
+ *   (M >= 0, K in {64, 128, 256}, N a multiple of 64 up to 4096). */
+#define MMG_EPI_NONE 0
+#define MMG_EPI_STATS 1
+#define MMG_EPI_NEXT_BN 2
+#define MMG_EPI_L2 3
+typedef struct {
+  int mode;                       /* MMG_EPI_* */
+  double* col_sums;               /* STATS: [2, N] out */
+  const mmg_bn_fin_t* fin;        /* STATS: the BatchNorm fold, or NULL */
+  void* ws; size_t ws_bytes;      /* STATS */
+  const mmg_next_bn_t* next;      /* NEXT_BN */
+  float* rnorm; float eps;        /* L2: [M] out, eps */
+} mmg_fwd_epi_t;
+size_t mmg_epi_ws_bytes(int64_t M, int N);
+int mmg_linear_fwd_supported(int mode, int64_t M, int N, int K);
+int mmg_linear_fwd(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias, float* Y, int64_t M, int N,
+                   int K, int flags, const mmg_fwd_epi_t* epi, void* stream);
+int mmg_gather_rows(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D, float* out, int accumulate,
+                    const mmg_fwd_epi_t* epi, void* stream);
 
 /* dW[N,K] (+)= dY[M,N]^T . prologue(X)[M,K]   (reduction over the M rows);
  * dbias (nullable, [N]) (+)= the column sums of dY -- the bias gradient of the same layer, from the same pass */
@@ -267,37 +297,6 @@ int mmg_bn_bwd_stats_rows(const float* G_rows, const float* Y, const int64_t* ro
                           void* ws, size_t ws_bytes, void* stream);
 int mmg_bn_bwd_apply_rows(const float* G_rows, const float* Y, const int64_t* rows, int64_t n_sel,
                           const mmg_prologue_t* pro, float* dY, int N, void* stream);
-
-/* The statistics pass of a BatchNorm backward taken from the kernel that PRODUCES its upstream gradient.
- * mmg_bn_bwd_stats (and _stats2) read the [M, N] upstream gradient and the [M, N] pre-BatchNorm activation once more; a
- * producer that is handed this descriptor sums them from its output tile while it is still in registers and only reads
- * Y.  `sums` receives exactly what mmg_bn_bwd_stats(G = the producer's output, y, pro, mean, rstd) would, summed in a
- * fixed order (16 rows in fp32, the rest in fp64); with accumulate != 0 that is ADDED to `sums` -- the two sums are
- * linear in G, so two producers whose outputs go through the same BatchNorm with their own dropout masks (the two
- * encode_nodes passes of a training step, mmg_bn_bwd_stats2) each add their share.
- * Autograd of  nn.Linear -> BatchNorm1d -> ReLU -> Dropout  chains (src/model.py:93-101, 258-269): the gradient a layer
- * hands down is the upstream gradient of the BatchNorm below it.
- *   mmg_linear_fwd_next_bn          dX = dY . W  (MMG_LIN_W_KN) of a plain linear, e.g. the heads' first layer; no prologue,
- *                                   no accumulate;  M > 512, N % 128 == 0, K in {64, 128}
- *   mmg_linear_bnbwd                dX;  K = N = 128 without a weight gradient (not MMG_BNBWD_BN2: refused)
- *   mmg_gather_rows_next_bn         the final `out` of mmg_gather_rows (accumulate or not);  the bit-plane layouts, D >= 128
- * next == NULL: the producer alone.  A shape (or activation) outside the list above runs the producer followed by
- * the separate statistics pass: the result is defined for everything the producer accepts. */
-typedef struct {
-  const float* y;                 /* [M, N] pre-BatchNorm activation of the layer below */
-  const mmg_prologue_t* pro;      /* its fold (scale / shift), activation (none | relu) and dropout */
-  const float* mean;              /* [N] */
-  const float* rstd;              /* [N] */
-  double* sums;                   /* [2, N] out (in / out with accumulate) */
-  int accumulate;
-  void* ws;                       /* >= mmg_next_bn_ws_bytes(M, N) */
-  size_t ws_bytes;
-} mmg_next_bn_t;
-size_t mmg_next_bn_ws_bytes(int64_t M, int N);
-int mmg_linear_fwd_next_bn(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias, float* Y, int64_t M,
-                           int N, int K, int flags, const mmg_next_bn_t* next, void* stream);
-int mmg_gather_rows_next_bn(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D, float* out, int accumulate,
-                            const mmg_next_bn_t* next, void* stream);
 
 /* The BatchNorm (or L2-norm) backward folded into the data-gradient GEMM of the linear in front of it -- autograd of
  * nn.Linear behind BatchNorm1d + relu + dropout (src/model.py:93-101,258-269) or behind F.normalize.  In ONE pass over the

@@ -75,6 +75,11 @@ class NextBnT(C.Structure):
                 ("sums", C.c_void_p), ("accumulate", C.c_int), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
 
 
+class FwdEpiT(C.Structure):
+    _fields_ = [("mode", C.c_int), ("col_sums", C.c_void_p), ("fin", C.POINTER(BnFinT)), ("ws", C.c_void_p),
+                ("ws_bytes", C.c_size_t), ("next", C.POINTER(NextBnT)), ("rnorm", C.c_void_p), ("eps", C.c_float)]
+
+
 class PairSavedT(C.Structure):
     _fields_ = [("h1_bits", C.c_void_p), ("h2", C.c_void_p), ("by_position", C.c_int), ("n_entries", C.c_int64)]
 
@@ -118,16 +123,12 @@ SIGNATURES = {
     "mmg_col_degree": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "mmg_rel_mask_words": (_sz, [_i64, C.c_int32]),
     "mmg_rel_mask_build": (C.c_int, [_vp, _vp, _i64, C.c_int32, _vp, _vp, _vp]),
-    "mmg_gather_rows": (C.c_int, [_P(RelT), _i32, _i64, _i32, _vp, _i32, _vp]),
-    "mmg_gather_rows_stats_ws_bytes": (_sz, [_i64, _i32]),
-    "mmg_gather_rows_stats": (C.c_int, [_P(RelT), _i32, _i64, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
-    "mmg_gather_rows_stats_bn": (C.c_int, [_P(RelT), _i32, _i64, _i32, _vp, _i32, _vp, _vp, _sz, _P(BnFinT), _vp]),
+    "mmg_gather_rows": (C.c_int, [_P(RelT), _i32, _i64, _i32, _vp, _i32, _P(FwdEpiT), _vp]),
     "mmg_scatter_rows_ws_bytes": (_sz, [_P(RelT), _i32, _i64, _i32]),
     "mmg_scatter_rows": (C.c_int, [_P(RelT), _i32, _i64, _i32, _vp, _vp, _sz, _vp]),
-    "mmg_linear_fwd": (C.c_int, [_vp, _P(PrologueT), _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
-    "mmg_linear_fwd_stats_ws_bytes": (_sz, [_i64, _i32]),
-    "mmg_linear_fwd_stats": (C.c_int, [_vp, _P(PrologueT), _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
-    "mmg_linear_fwd_stats_bn": (C.c_int, [_vp, _P(PrologueT), _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _sz, _P(BnFinT), _vp]),
+    "mmg_epi_ws_bytes": (_sz, [_i64, _i32]),
+    "mmg_linear_fwd_supported": (C.c_int, [_i32, _i64, _i32, _i32]),
+    "mmg_linear_fwd": (C.c_int, [_vp, _P(PrologueT), _vp, _vp, _vp, _i64, _i32, _i32, _i32, _P(FwdEpiT), _vp]),
     "mmg_linear_wgrad_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "mmg_linear_wgrad": (C.c_int, [_vp, _vp, _P(PrologueT), _vp, _vp, _i64, _i32, _i32, _i32, _vp, _sz, _vp]),
     "mmg_linear_wgrad_deferred": (C.c_int, [_vp, _vp, _P(PrologueT), _vp, _vp, _i64, _i32, _i32, _i32, _vp, _sz, _vp,
@@ -150,14 +151,9 @@ SIGNATURES = {
     "mmg_bn_bwd_apply_rows": (C.c_int, [_vp, _vp, _vp, _i64, _P(PrologueT), _vp, _i32, _vp]),
     "mmg_bn_bwd_stats": (C.c_int, [_vp, _vp, _P(PrologueT), _vp, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
     "mmg_bn_bwd_apply": (C.c_int, [_vp, _vp, _P(PrologueT), _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
-    "mmg_linear_fwd_l2norm_supported": (C.c_int, [_i64, _i32, _i32]),
-    "mmg_linear_fwd_l2norm": (C.c_int, [_vp, _P(PrologueT), _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp]),
     "mmg_linear_bnbwd_supported": (C.c_int, [_i32, _i64, _i32, _i32, _i32]),
     "mmg_linear_bnbwd_wgrad_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "mmg_linear_bnbwd": (C.c_int, [_P(BnBwdT), _vp, _vp, _vp, _i64, _i32, _i32, _P(NextBnT), _P(BnBwdWgradT), _vp]),
-    "mmg_next_bn_ws_bytes": (_sz, [_i64, _i32]),
-    "mmg_linear_fwd_next_bn": (C.c_int, [_vp, _P(PrologueT), _vp, _vp, _vp, _i64, _i32, _i32, _i32, _P(NextBnT), _vp]),
-    "mmg_gather_rows_next_bn": (C.c_int, [_P(RelT), _i32, _i64, _i32, _vp, _i32, _P(NextBnT), _vp]),
     "mmg_l2norm_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _vp]),
     "mmg_l2norm_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp]),
     "mmg_pair_loss_ws_bytes": (_sz, [_i64]),

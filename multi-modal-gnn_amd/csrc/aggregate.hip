@@ -1538,6 +1538,27 @@ __global__ __launch_bounds__(256) void k_scatter_atomic(RelPack rp, int64_t n_ro
   }
 }
 
+// the bit-plane gather of one static relation layout (k_gather_bits<NK, K1, K2, ...>): nbn = the next BatchNorm's
+// statistics in the epilogue (into `partial`), else the forward statistics when `partial` is set.  -> grid.x = the rows
+// of partial statistics it writes
+template <int NK, int K1, int K2>
+int launch_gather_bits(const RelPack& rp, int64_t n_rows, int D, int total_cols, float* out, int accumulate, bool nbn,
+                       double* partial, const NextBnDev& nbd, hipStream_t st) {
+  const int n_tiles = (int)((n_rows + 31) / 32);
+  const int n_dchunks = D / 128;
+  int g = 256 / n_dchunks;
+  if (g > n_tiles) g = n_tiles;
+  dim3 grid((unsigned)g, (unsigned)n_dchunks);
+  if (nbn) {
+    if (accumulate) MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 1 | 512, (k_gather_bits<NK, K1, K2, true, true>), grid, dim3(512), 0, st, rp, n_rows, n_tiles, D, out, partial, nbd);
+    else MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 512, (k_gather_bits<NK, K1, K2, false, true>), grid, dim3(512), 0, st, rp, n_rows, n_tiles, D, out, partial, nbd);
+  } else {
+    if (accumulate) MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 1, (k_gather_bits<NK, K1, K2, true, false>), grid, dim3(512), 0, st, rp, n_rows, n_tiles, D, out, partial, next_bn_none());
+    else MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 0, (k_gather_bits<NK, K1, K2, false, false>), grid, dim3(512), 0, st, rp, n_rows, n_tiles, D, out, partial, next_bn_none());
+  }
+  return g;
+}
+
 int pack(const mmg_rel_t* rels, int n_rel, RelPack* rp, bool need_table, bool need_out, bool pad_cols = false) {
   MMG_CHECK_ARG(rels && n_rel >= 1 && n_rel <= MMG_MAX_REL, "aggregate: n_rel must be 1..%d", MMG_MAX_REL);
   rp->n = n_rel;
@@ -1555,141 +1576,55 @@ int pack(const mmg_rel_t* rels, int n_rel, RelPack* rp, bool need_table, bool ne
 
 }  // namespace
 
-extern "C" int mmg_partial_sum(const double* partial, double* out, int n, int n_rows, void* stream);
-extern "C" int mmg_partial_sum_bn(const double* partial, double* col_sums, int N, int n_rows, const mmg_bn_fin_t* fin, void* stream);
-extern "C" int mmg_bn_finalize(const double* sums, int64_t count, const float* gamma, const float* beta, float* running_mean,
-                               float* running_var, int training, int n_updates, float momentum, float eps, float* scale,
-                               float* shift, float* mean, float* rstd, int N, void* stream);
-extern "C" int mmg_gather_rows_stats(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D, float* out, int accumulate,
-                                     double* col_sums, void* ws, size_t ws_bytes, void* stream);
-
-extern "C" size_t mmg_gather_rows_stats_ws_bytes(int64_t n_rows, int D) {
-  if (n_rows < 0 || D <= 0) return 0;
-  const size_t a = (size_t)256 * 2 * D * sizeof(double) + 256, b = mmg_col_reduce2_ws_bytes(n_rows, D);
-  return a > b ? a : b;
-}
-
-extern "C" int mmg_gather_rows(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D, float* out, int accumulate,
-                               void* stream) {
-  return mmg_gather_rows_stats(rels, n_rel, n_rows, D, out, accumulate, nullptr, nullptr, 0, stream);
-}
-
-extern "C" int mmg_next_bn_dev(const mmg_next_bn_t* next, int64_t M, int N, const char* what, NextBnDev* d, double** partial);
-extern "C" int mmg_next_bn_finish(const mmg_next_bn_t* next, const double* partial, int N, int rows, void* stream);
-extern "C" int mmg_next_bn_fallback(const float* G, int64_t M, int N, const mmg_next_bn_t* next, const char* what, void* stream);
-
-// next (nullable, exclusive with col_sums): the statistics of the BatchNorm backward that consumes `out` (mmg_next_bn_t)
-static int gather_rows_stats_impl(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D, float* out, int accumulate,
-                                  double* col_sums, void* ws, size_t ws_bytes, void* stream, const mmg_bn_fin_t* fin,
-                                  const mmg_next_bn_t* next = nullptr) {
-  MMG_CHECK_ARG(!(next && col_sums), "gather_rows: forward statistics and next-BatchNorm statistics are exclusive");
-  NextBnDev nbd = next_bn_none();
-  double* nb_partial = nullptr;
-  const bool nb_fused = next && next->pro && (next->pro->relu == MMG_ACT_NONE || next->pro->relu == MMG_ACT_RELU);
-  if (next) {
-    int rcn = mmg_next_bn_dev(next, n_rows, D, "gather_rows_next_bn", &nbd, &nb_partial);
-    if (rcn) return rcn;
-  }
-  if (col_sums) {
-    MMG_CHECK_ARG(n_rows > 0 && ws && ws_bytes >= mmg_gather_rows_stats_ws_bytes(n_rows, D),
-                  "gather_rows_stats: workspace too small");
-  }
-  double* partial = col_sums ? (double*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) : nullptr;
-#define MMG_GATHER_TAIL(what)                                                                                 \
-  do {                                                                                                        \
-    MMG_CHECK_LAUNCH(what);                                                                                   \
-    if (next) return mmg_next_bn_fallback(out, n_rows, D, next, "gather_rows_next_bn", stream);               \
-    if (col_sums) {                                                                                           \
-      int rc_ = mmg_col_reduce2(out, nullptr, col_sums, n_rows, D, ws, ws_bytes, stream);                     \
-      if (rc_ || !fin) return rc_;                                                                            \
-      return mmg_bn_finalize(col_sums, fin->count, fin->gamma, fin->beta, fin->running_mean, fin->running_var, 1, \
-                             fin->n_updates, fin->momentum, fin->eps, fin->scale, fin->shift, fin->mean, fin->rstd, D, stream); \
-    }                                                                                                         \
-    return MMG_OK;                                                                                            \
-  } while (0)
-  MMG_CHECK_ARG(mmg_valid_D(D), "gather_rows: D=%d unsupported (64|128|256)", D);
-  MMG_CHECK_ARG(n_rows >= 0 && n_rows < 2147483647LL / 64, "gather_rows: n_rows out of range");
-  MMG_CHECK_ARG(out || n_rows == 0, "gather_rows: out is null");
-  RelPack rp;
-  int rc = pack(rels, n_rel, &rp, true, false);
-  if (rc) return rc;
-  if (n_rows == 0) return MMG_OK;
-  hipStream_t st = (hipStream_t)stream;
+// the launch of one relation layout; *fused / *rows: whether it took the epilogue itself and how many partial rows it
+// wrote into `partial`
+static int gather_launch(const mmg_rel_t* rels, int n_rel, const RelPack& rp, int64_t n_rows, int D, float* out, int accumulate,
+                         const mmg_fwd_epi_t* epi, double* partial, const NextBnDev& nbd, hipStream_t st, bool* fused, int* rows) {
+  const int mode = epi ? epi->mode : MMG_EPI_NONE;
+  double* stat_partial = mode == MMG_EPI_STATS ? partial : nullptr;
+  *fused = false;
   int total_cols = 0;
   for (int r = 0; r < n_rel; ++r) total_cols += rels[r].n_cols;
   // bit-plane matrix-core kernel: simple relations in a layout with a static instance -- the eICU vocabulary
   // (64 | 128 | 128 padded items) or its first relation alone (the last layer's backward only reaches the labs)
-  {
-    bool okb = (n_rel == 3 || n_rel == 1) && D >= 128 && n_rows >= 32 &&
-               (uint64_t)n_rows * (uint64_t)D * 4u < (1ull << 32);     // `out` sits behind one 32-bit buffer descriptor
-    for (int r = 0; r < n_rel && okb; ++r) okb = (rels[r].flags & MMG_REL_SIMPLE) != 0 && rels[r].mask_r != nullptr;
-    okb = okb && ((rels[0].n_cols + 31) & ~31) == 64;
-    if (n_rel == 3) okb = okb && ((rels[1].n_cols + 31) & ~31) == 128 && ((rels[2].n_cols + 31) & ~31) == 128;
-    if (okb && n_rel == 1) {
-      const int n_tiles = (int)((n_rows + 31) / 32);
-      const int n_dchunks = D / 128;
-      int g = 256 / n_dchunks;
-      if (g > n_tiles) g = n_tiles;
-      dim3 grid((unsigned)g, (unsigned)n_dchunks);
-      if (nb_fused) {
-        if (accumulate) MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 1 | 512, (k_gather_bits<4, 4, 4, true, true>), grid, dim3(512), 0, st, rp, n_rows, n_tiles, D, out, nb_partial, nbd);
-        else MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 512, (k_gather_bits<4, 4, 4, false, true>), grid, dim3(512), 0, st, rp, n_rows, n_tiles, D, out, nb_partial, nbd);
-        MMG_CHECK_LAUNCH("gather_rows(bits)");
-        return mmg_next_bn_finish(next, nb_partial, D, g, stream);
-      }
-      if (accumulate) MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 1, (k_gather_bits<4, 4, 4, true, false>), grid, dim3(512), 0, st, rp, n_rows, n_tiles, D, out, partial, next_bn_none());
-      else MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 0, (k_gather_bits<4, 4, 4, false, false>), grid, dim3(512), 0, st, rp, n_rows, n_tiles, D, out, partial, next_bn_none());
-      MMG_CHECK_LAUNCH("gather_rows(bits)");
-      if (next) return mmg_next_bn_fallback(out, n_rows, D, next, "gather_rows_next_bn", stream);
-      if (col_sums) return mmg_partial_sum_bn(partial, col_sums, D, g, fin, stream);
-      return MMG_OK;
-    }
-    if (okb) {
-      const int n_tiles = (int)((n_rows + 31) / 32);
-      const int n_dchunks = D / 128;
-      int g = 256 / n_dchunks;
-      if (g > n_tiles) g = n_tiles;
-      dim3 grid((unsigned)g, (unsigned)n_dchunks);
-      if (nb_fused) {
-        if (accumulate) MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 1 | 512, (k_gather_bits<20, 4, 12, true, true>), grid, dim3(512), 0, st, rp, n_rows, n_tiles, D, out, nb_partial, nbd);
-        else MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 512, (k_gather_bits<20, 4, 12, false, true>), grid, dim3(512), 0, st, rp, n_rows, n_tiles, D, out, nb_partial, nbd);
-        MMG_CHECK_LAUNCH("gather_rows(bits)");
-        return mmg_next_bn_finish(next, nb_partial, D, g, stream);
-      }
-      if (accumulate) MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 1, (k_gather_bits<20, 4, 12, true, false>), grid, dim3(512), 0, st, rp, n_rows, n_tiles, D, out, partial, next_bn_none());
-      else MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 0, (k_gather_bits<20, 4, 12, false, false>), grid, dim3(512), 0, st, rp, n_rows, n_tiles, D, out, partial, next_bn_none());
-      MMG_CHECK_LAUNCH("gather_rows(bits)");
-      if (next) return mmg_next_bn_fallback(out, n_rows, D, next, "gather_rows_next_bn", stream);
-      if (col_sums) return mmg_partial_sum_bn(partial, col_sums, D, g, fin, stream);
-      return MMG_OK;
-    }
+  bool okb = (n_rel == 3 || n_rel == 1) && D >= 128 && n_rows >= 32 &&
+             (uint64_t)n_rows * (uint64_t)D * 4u < (1ull << 32);     // `out` sits behind one 32-bit buffer descriptor
+  for (int r = 0; r < n_rel && okb; ++r) okb = (rels[r].flags & MMG_REL_SIMPLE) != 0 && rels[r].mask_r != nullptr;
+  okb = okb && ((rels[0].n_cols + 31) & ~31) == 64;
+  if (n_rel == 3) okb = okb && ((rels[1].n_cols + 31) & ~31) == 128 && ((rels[2].n_cols + 31) & ~31) == 128;
+  if (okb) {
+    const bool nbn = mode == MMG_EPI_NEXT_BN && mmg_next_bn_fusable(epi->next);
+    double* p = nbn ? partial : stat_partial;
+    *rows = n_rel == 1 ? launch_gather_bits<4, 4, 4>(rp, n_rows, D, total_cols, out, accumulate, nbn, p, nbd, st)
+                       : launch_gather_bits<20, 4, 12>(rp, n_rows, D, total_cols, out, accumulate, nbn, p, nbd, st);
+    *fused = nbn || stat_partial;
+    MMG_CHECK_LAUNCH("gather_rows(bits)");
+    return MMG_OK;
   }
   // any other layout of simple relations with bit planes: one unit (<= 128 items of one relation) per wave
-  {
-    const GaPlan gp = plan_gather_units(rels, n_rel, n_rows, D);
-    if (gp.ok) {
-      const int n_tiles = (int)((n_rows + 31) / 32);
-      const int gy = (D / 32) / gp.gu.FT;
-      int g = 256 / gy;
-      if (g < 1) g = 1;
-      if (g > n_tiles) g = n_tiles;
-      if (g > 256) g = 256;                              // <= 256 partial statistic rows (workspace)
-      dim3 grid((unsigned)g, (unsigned)gy);
-      constexpr int lds_max = 4096 + 8 * 32 * 4 + 2 * 6 * 16 * 64 * 4;     // FT * (U - 1) <= 6 exchange tiles, double-buffered
-      if (accumulate) {
-        MMG_CHECK_HIP((MmgMaxLds<&k_gather_units<true>, lds_max>::set()), "gather_rows(attr)");
-        MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 1 | 32, k_gather_units<true>, grid, dim3(64 * gp.waves), gp.lds, st,
-                   gp.gu, rp, n_rows, n_tiles, D, out, partial);
-      } else {
-        MMG_CHECK_HIP((MmgMaxLds<&k_gather_units<false>, lds_max>::set()), "gather_rows(attr)");
-        MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 32, k_gather_units<false>, grid, dim3(64 * gp.waves), gp.lds, st,
-                   gp.gu, rp, n_rows, n_tiles, D, out, partial);
-      }
-      MMG_CHECK_LAUNCH("gather_rows(units)");
-      if (next) return mmg_next_bn_fallback(out, n_rows, D, next, "gather_rows_next_bn", stream);
-      if (col_sums) return mmg_partial_sum_bn(partial, col_sums, D, g, fin, stream);
-      return MMG_OK;
+  const GaPlan gp = plan_gather_units(rels, n_rel, n_rows, D);
+  if (gp.ok) {
+    const int n_tiles = (int)((n_rows + 31) / 32);
+    const int gy = (D / 32) / gp.gu.FT;
+    int g = 256 / gy;
+    if (g < 1) g = 1;
+    if (g > n_tiles) g = n_tiles;
+    if (g > 256) g = 256;                              // <= 256 partial statistic rows (workspace)
+    dim3 grid((unsigned)g, (unsigned)gy);
+    constexpr int lds_max = 4096 + 8 * 32 * 4 + 2 * 6 * 16 * 64 * 4;     // FT * (U - 1) <= 6 exchange tiles, double-buffered
+    if (accumulate) {
+      MMG_CHECK_HIP((MmgMaxLds<&k_gather_units<true>, lds_max>::set()), "gather_rows(attr)");
+      MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 1 | 32, k_gather_units<true>, grid, dim3(64 * gp.waves), gp.lds, st,
+                 gp.gu, rp, n_rows, n_tiles, D, out, stat_partial);
+    } else {
+      MMG_CHECK_HIP((MmgMaxLds<&k_gather_units<false>, lds_max>::set()), "gather_rows(attr)");
+      MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, 32, k_gather_units<false>, grid, dim3(64 * gp.waves), gp.lds, st,
+                 gp.gu, rp, n_rows, n_tiles, D, out, stat_partial);
     }
+    *fused = stat_partial != nullptr;
+    *rows = g;
+    MMG_CHECK_LAUNCH("gather_rows(units)");
+    return MMG_OK;
   }
   // LDS-resident tables when a column chunk of every table fits; else the L2-served kernel
   int dc = D >= 128 ? 128 : 64;
@@ -1711,30 +1646,36 @@ static int gather_rows_stats_impl(const mmg_rel_t* rels, int n_rel, int64_t n_ro
       MMG_CHECK_HIP((MmgMaxLds<&k_gather_lds<1>, (int)GL_LDS_BUDGET>::set()), "gather_rows(attr)");
       MMG_LAUNCH(MMG_PROBE_GATHER, n_rows, D, total_cols, accumulate | 16, k_gather_lds<1>, grid, dim3(GL_THREADS), lds, st, rp, n_rows, rows_per_blk, D, out, accumulate);
     }
-    MMG_GATHER_TAIL("gather_rows(lds)");
+    MMG_CHECK_LAUNCH("gather_rows(lds)");
+    return MMG_OK;
   }
   const unsigned nb = (unsigned)((n_rows + 3) / 4);
   if (D == 64) hipLaunchKernelGGL(k_gather<1>, dim3(nb), dim3(256), 0, st, rp, n_rows, out, accumulate);
   else if (D == 128) hipLaunchKernelGGL(k_gather<2>, dim3(nb), dim3(256), 0, st, rp, n_rows, out, accumulate);
   else hipLaunchKernelGGL(k_gather<4>, dim3(nb), dim3(256), 0, st, rp, n_rows, out, accumulate);
-  MMG_GATHER_TAIL("gather_rows");
-#undef MMG_GATHER_TAIL
+  MMG_CHECK_LAUNCH("gather_rows");
+  return MMG_OK;
 }
 
-extern "C" int mmg_gather_rows_next_bn(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D, float* out, int accumulate,
-                                       const mmg_next_bn_t* next, void* stream) {
-  return gather_rows_stats_impl(rels, n_rel, n_rows, D, out, accumulate, nullptr, nullptr, 0, stream, nullptr, next);
-}
-
-extern "C" int mmg_gather_rows_stats(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D, float* out, int accumulate,
-                                     double* col_sums, void* ws, size_t ws_bytes, void* stream) {
-  return gather_rows_stats_impl(rels, n_rel, n_rows, D, out, accumulate, col_sums, ws, ws_bytes, stream, nullptr);
-}
-
-extern "C" int mmg_gather_rows_stats_bn(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D, float* out, int accumulate,
-                                        double* col_sums, void* ws, size_t ws_bytes, const mmg_bn_fin_t* fin, void* stream) {
-  MMG_CHECK_ARG(col_sums && fin && fin->count > 0 && fin->scale && fin->shift, "gather_rows_stats_bn: col_sums and a fold descriptor are required");
-  return gather_rows_stats_impl(rels, n_rel, n_rows, D, out, accumulate, col_sums, ws, ws_bytes, stream, fin);
+extern "C" int mmg_gather_rows(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D, float* out, int accumulate,
+                               const mmg_fwd_epi_t* epi, void* stream) {
+  const char* what = "gather_rows";
+  MMG_CHECK_ARG(!epi || epi->mode != MMG_EPI_L2, "%s: the L2 epilogue is the linear's only", what);
+  double* partial;
+  NextBnDev nbd;
+  int rc = mmg_epi_prepare(epi, n_rows, D, what, &partial, &nbd);
+  if (rc) return rc;
+  MMG_CHECK_ARG(mmg_valid_D(D), "%s: D=%d unsupported (64|128|256)", what, D);
+  MMG_CHECK_ARG(n_rows >= 0 && n_rows < 2147483647LL / 64, "%s: n_rows out of range", what);
+  MMG_CHECK_ARG(out || n_rows == 0, "%s: out is null", what);
+  RelPack rp;
+  rc = pack(rels, n_rel, &rp, true, false);
+  if (rc) return rc;
+  if (n_rows == 0) return MMG_OK;
+  bool fused;
+  int rows = 0;
+  rc = gather_launch(rels, n_rel, rp, n_rows, D, out, accumulate, epi, partial, nbd, (hipStream_t)stream, &fused, &rows);
+  return rc ? rc : mmg_epi_finish(epi, out, n_rows, D, fused, partial, rows, what, stream);
 }
 
 extern "C" size_t mmg_scatter_rows_ws_bytes(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D) {

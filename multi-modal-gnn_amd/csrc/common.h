@@ -283,6 +283,31 @@ __device__ __forceinline__ void next_bn_tile(const NextBnDev& nb, const NextBnCo
   cs1 += (double)t1; cs2 += (double)t2;
 }
 
+// ---- host helpers shared by the producers (gemm.hip, aggregate.hip) and the reductions (elementwise.hip)
+// out[i] (= add[i] +) the sum over n_rows partial rows [n_rows][n], fixed order (add nullable, may alias out)
+extern "C" int mmg_partial_sum(const double* partial, double* out, int n, int n_rows, void* stream);
+extern "C" int mmg_partial_sum_add(const double* partial, double* out, int n, int n_rows, const double* add, void* stream);
+// partial [n_rows][2][N] -> col_sums, + the BatchNorm fold of the sums (fin != NULL)
+extern "C" int mmg_partial_sum_bn(const double* partial, double* col_sums, int N, int n_rows, const mmg_bn_fin_t* fin,
+                                  void* stream);
+// mmg_next_bn_t: validates the descriptor, fills the device view, *partial = the aligned workspace
+extern "C" int mmg_next_bn_dev(const mmg_next_bn_t* next, int64_t M, int N, const char* what, NextBnDev* d, double** partial);
+// the fused producer's partial rows -> next->sums (or +=)
+extern "C" int mmg_next_bn_finish(const mmg_next_bn_t* next, const double* partial, int N, int rows, void* stream);
+// no fused form: the separate statistics pass over the producer's finished output G
+extern "C" int mmg_next_bn_fallback(const float* G, int64_t M, int N, const mmg_next_bn_t* next, const char* what, void* stream);
+// relu / none only in the fused epilogues (the separate pass takes every activation mmg_bn_bwd_stats does)
+static inline bool mmg_next_bn_fusable(const mmg_next_bn_t* next) {
+  return next->pro && (next->pro->relu == MMG_ACT_NONE || next->pro->relu == MMG_ACT_RELU);
+}
+// mmg_fwd_epi_t: validates the descriptor of a producer writing [M, N]; *partial = where a fused STATS / NEXT_BN epilogue
+// writes its partial rows, *nb = the NEXT_BN device view
+int mmg_epi_prepare(const mmg_fwd_epi_t* epi, int64_t M, int N, const char* what, double** partial, NextBnDev* nb);
+// after the producer's launch: a fused epilogue sums the `rows` partial rows it wrote (+ the BatchNorm fold, or into
+// next->sums); an unfused STATS / NEXT_BN runs its separate pass over the output Y [M, N]
+int mmg_epi_finish(const mmg_fwd_epi_t* epi, const float* Y, int64_t M, int N, bool fused, const double* partial, int rows,
+                   const char* what, void* stream);
+
 __device__ static inline float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

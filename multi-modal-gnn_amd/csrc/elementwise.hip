@@ -528,21 +528,21 @@ int run_col_reduce(const float* A, const float* B, const ProDev& pr, const float
 
 }  // namespace
 
-// internal (gemm.hip): out[i] = sum over n_rows partial rows, one wave per output, fixed order
+// internal (common.h): out[i] = sum over n_rows partial rows, one wave per output, fixed order
 extern "C" int mmg_partial_sum(const double* partial, double* out, int n, int n_rows, void* stream) {
   hipLaunchKernelGGL(k_partial_sum, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, partial, out, n, n_rows);
   MMG_CHECK_LAUNCH("partial_sum");
   return MMG_OK;
 }
 
-// internal (gemm.hip, aggregate.hip): out[i] = add[i] + the sum (add nullable, may alias out)
+// internal (common.h): out[i] = add[i] + the sum (add nullable, may alias out)
 extern "C" int mmg_partial_sum_add(const double* partial, double* out, int n, int n_rows, const double* add, void* stream) {
   hipLaunchKernelGGL(k_partial_sum, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, partial, out, n, n_rows, add);
   MMG_CHECK_LAUNCH("partial_sum");
   return MMG_OK;
 }
 
-// internal (gemm.hip, aggregate.hip): the same with the BatchNorm fold of the summed statistics (fin != NULL)
+// internal (common.h): the same with the BatchNorm fold of the summed statistics (fin != NULL)
 extern "C" int mmg_partial_sum_bn(const double* partial, double* col_sums, int N, int n_rows, const mmg_bn_fin_t* fin,
                                   void* stream) {
   if (!fin) return mmg_partial_sum(partial, col_sums, 2 * N, n_rows, stream);

@@ -89,8 +89,6 @@ inline int ev_blocks(int64_t n) {
 
 }  // namespace
 
-extern "C" int mmg_partial_sum(const double* partial, double* out, int n, int n_rows, void* stream);
-
 extern "C" size_t mmg_seg_reduce_ws_bytes(int64_t n, int n_seg) {
   if (n < 0 || n_seg <= 0 || n_seg > EV_MAXSEG) return 0;
   return (size_t)EV_BLOCKS * n_seg * 8 * sizeof(double) + 256;

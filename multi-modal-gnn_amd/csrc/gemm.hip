@@ -700,10 +700,21 @@ int launch_fwd_x6_v(const float* X, const ProDev& pr, const float* W, const floa
   return 0;
 }
 
+// PRO / ACC from the prologue and the flags; the forward statistics when stat_partial is set.  epi = MMG_EPI_L2 / _NEXT_BN
+// (the caller checked that the launch takes them) pick the instances with that epilogue: K <= 128, no accumulate, and for
+// NEXT_BN no prologue and 128-column slices, stat_partial then receiving the next BatchNorm's partial rows
 template <int K, int WN>
 int launch_fwd_x6(const float* X, const ProDev& pr, const float* W, const float* bias, float* Y, int64_t M, int N,
-                  int flags, hipStream_t st, double* stat_partial = nullptr) {
+                  int flags, hipStream_t st, double* stat_partial, int epi, float* rn_out, float l2_eps, const NextBnDev& nb) {
   const bool pro = pr.scale || pr.relu || pr.p > 0.f, acc = (flags & MMG_LIN_ACCUMULATE) != 0;
+  if constexpr (K <= 128) {
+    if (epi == MMG_EPI_L2)
+      return pro ? launch_fwd_x6_v<K, WN, true, false, true>(X, pr, W, bias, Y, M, N, flags, st, nullptr, rn_out, l2_eps)
+                 : launch_fwd_x6_v<K, WN, false, false, true>(X, pr, W, bias, Y, M, N, flags, st, nullptr, rn_out, l2_eps);
+    if constexpr (WN == 4)
+      if (epi == MMG_EPI_NEXT_BN)
+        return launch_fwd_x6_v<K, 4, false, false, false, true>(X, pr, W, bias, Y, M, N, flags, st, stat_partial, nullptr, 0.f, nb);
+  }
   if (pro) return acc ? launch_fwd_x6_v<K, WN, true, true>(X, pr, W, bias, Y, M, N, flags, st, stat_partial)
                       : launch_fwd_x6_v<K, WN, true, false>(X, pr, W, bias, Y, M, N, flags, st, stat_partial);
   return acc ? launch_fwd_x6_v<K, WN, false, true>(X, pr, W, bias, Y, M, N, flags, st, stat_partial)
@@ -1706,42 +1717,28 @@ int launch_small(const float* X, const ProDev& pr, const float* W, const float* 
 
 }  // namespace
 
-extern "C" int mmg_col_reduce2(const float* A, const float* B, double* out, int64_t M, int N, void* ws, size_t ws_bytes,
-                               void* stream);
-extern "C" int mmg_partial_sum(const double* partial, double* out, int n, int n_rows, void* stream);
-extern "C" int mmg_partial_sum_bn(const double* partial, double* col_sums, int N, int n_rows, const mmg_bn_fin_t* fin, void* stream);
-extern "C" int mmg_bn_finalize(const double* sums, int64_t count, const float* gamma, const float* beta, float* running_mean,
-                               float* running_var, int training, int n_updates, float momentum, float eps, float* scale,
-                               float* shift, float* mean, float* rstd, int N, void* stream);
-
-// ---- mmg_next_bn_t (include/mmgnn.h): host side shared by the producers (this file and aggregate.hip)
-extern "C" int mmg_partial_sum_add(const double* partial, double* out, int n, int n_rows, const double* add, void* stream);
-extern "C" int mmg_bn_bwd_stats(const float* G, const float* Y, const mmg_prologue_t* pro, const float* mean, const float* rstd,
-                                double* sums, int64_t M, int N, void* ws, size_t ws_bytes, void* stream);
+// ---- producer epilogues (mmg_fwd_epi_t, mmg_next_bn_t; include/mmgnn.h): host side shared with aggregate.hip
 
 // workspace: <= 768 partial rows of a fused producer, or (fallback) one row of sums + the separate statistics pass
-extern "C" size_t mmg_next_bn_ws_bytes(int64_t M, int N) {
+extern "C" size_t mmg_epi_ws_bytes(int64_t M, int N) {
   if (M < 0 || N <= 0) return 0;
   const size_t a = (size_t)768 * 2 * N * sizeof(double) + 256;
   const size_t b = (size_t)2 * N * sizeof(double) + 512 + mmg_col_reduce2_ws_bytes(M, N);
   return a > b ? a : b;
 }
 
-// internal: validates the descriptor and fills the device view; *partial = the aligned workspace
 extern "C" int mmg_next_bn_dev(const mmg_next_bn_t* next, int64_t M, int N, const char* what, NextBnDev* d, double** partial) {
   MMG_CHECK_ARG(next->y && next->pro && next->mean && next->rstd && next->sums, "%s: next-BatchNorm descriptor with a null field", what);
   MMG_CHECK_ARG(!next->pro->scale || next->pro->shift, "%s: next BatchNorm: scale without shift", what);
-  MMG_CHECK_ARG(next->ws && next->ws_bytes >= mmg_next_bn_ws_bytes(M, N), "%s: next BatchNorm: workspace too small", what);
+  MMG_CHECK_ARG(next->ws && next->ws_bytes >= mmg_epi_ws_bytes(M, N), "%s: next BatchNorm: workspace too small", what);
   d->Y = next->y; d->mean = next->mean; d->rstd = next->rstd;
   d->pr = mmg_pro_dev(next->pro);
   *partial = (double*)(((uintptr_t)next->ws + 255) & ~(uintptr_t)255);
   return MMG_OK;
 }
-// internal: partial[rows][2][N] -> sums (or sums += when the descriptor says so), fixed order
 extern "C" int mmg_next_bn_finish(const mmg_next_bn_t* next, const double* partial, int N, int rows, void* stream) {
   return mmg_partial_sum_add(partial, next->sums, 2 * N, rows, next->accumulate ? next->sums : nullptr, stream);
 }
-// internal: the producer has no fused form for this shape -- the separate statistics pass over its finished output G
 extern "C" int mmg_next_bn_fallback(const float* G, int64_t M, int N, const mmg_next_bn_t* next, const char* what, void* stream) {
   NextBnDev d;
   double* tmp;
@@ -1754,158 +1751,108 @@ extern "C" int mmg_next_bn_fallback(const float* G, int64_t M, int N, const mmg_
   if (rc || !next->accumulate) return rc;
   return mmg_partial_sum_add(tmp, next->sums, 2 * N, 1, next->sums, stream);
 }
-// relu / none only in the fused epilogues (the fallback takes every activation mmg_bn_bwd_stats does)
-static inline bool next_bn_fusable(const mmg_next_bn_t* next) {
-  return next->pro && (next->pro->relu == MMG_ACT_NONE || next->pro->relu == MMG_ACT_RELU);
+
+// what each mode requires of the descriptor (the fields a mode does not name are ignored)
+static const struct {
+  bool col_sums, next, rnorm;
+} kFwdEpiMode[4] = {
+    // col_sums next   rnorm
+    {false,     false, false},    // NONE
+    {true,      false, false},    // STATS (fin nullable)
+    {false,     true,  false},    // NEXT_BN
+    {false,     false, true},     // L2
+};
+
+int mmg_epi_prepare(const mmg_fwd_epi_t* e, int64_t M, int N, const char* what, double** partial, NextBnDev* nb) {
+  *partial = nullptr;
+  *nb = next_bn_none();
+  if (!e) return MMG_OK;
+  MMG_CHECK_ARG(e->mode >= MMG_EPI_NONE && e->mode <= MMG_EPI_L2, "%s: unknown epilogue mode %d", what, e->mode);
+  const auto& m = kFwdEpiMode[e->mode];
+  MMG_CHECK_ARG((e->col_sums || !m.col_sums) && (e->next || !m.next) && (e->rnorm || !m.rnorm),
+                "%s: epilogue descriptor with a null field", what);
+  MMG_CHECK_ARG(!(e->col_sums && e->next), "%s: forward statistics and next-BatchNorm statistics are exclusive", what);
+  if (e->mode == MMG_EPI_NEXT_BN) return mmg_next_bn_dev(e->next, M, N, what, nb, partial);
+  if (e->mode != MMG_EPI_STATS) return MMG_OK;
+  MMG_CHECK_ARG(M > 0, "%s: statistics of an empty output", what);
+  MMG_CHECK_ARG(!e->fin || (e->fin->count > 0 && e->fin->scale && e->fin->shift),
+                "%s: BatchNorm fold without count, scale or shift", what);
+  MMG_CHECK_ARG(e->ws && e->ws_bytes >= mmg_epi_ws_bytes(M, N), "%s: statistics workspace too small", what);
+  *partial = (double*)(((uintptr_t)e->ws + 255) & ~(uintptr_t)255);
+  return MMG_OK;
 }
 
-extern "C" size_t mmg_linear_fwd_stats_ws_bytes(int64_t M, int N) {
-  if (M < 0 || N <= 0) return 0;
-  const size_t a = (size_t)768 * 2 * N * sizeof(double) + 256;       // <= 768 partial rows from the GEMM epilogue
-  const size_t b = mmg_col_reduce2_ws_bytes(M, N);                   // fallback: a separate column reduction
-  return a > b ? a : b;
+int mmg_epi_finish(const mmg_fwd_epi_t* e, const float* Y, int64_t M, int N, bool fused, const double* partial, int rows,
+                   const char* what, void* stream) {
+  if (!e || e->mode == MMG_EPI_NONE || e->mode == MMG_EPI_L2) return MMG_OK;
+  if (e->mode == MMG_EPI_NEXT_BN)
+    return fused ? mmg_next_bn_finish(e->next, partial, N, rows, stream) : mmg_next_bn_fallback(Y, M, N, e->next, what, stream);
+  if (fused) return mmg_partial_sum_bn(partial, e->col_sums, N, rows, e->fin, stream);
+  const int rc = mmg_col_reduce2(Y, nullptr, e->col_sums, M, N, e->ws, e->ws_bytes, stream);
+  const mmg_bn_fin_t* f = e->fin;
+  if (rc || !f) return rc;
+  return mmg_bn_finalize(e->col_sums, f->count, f->gamma, f->beta, f->running_mean, f->running_var, 1, f->n_updates, f->momentum,
+                         f->eps, f->scale, f->shift, f->mean, f->rstd, N, stream);
 }
 
-extern "C" int mmg_linear_fwd_stats(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias,
-                                    float* Y, int64_t M, int N, int K, int flags, double* col_sums, void* ws,
-                                    size_t ws_bytes, void* stream);
+extern "C" int mmg_linear_fwd_supported(int mode, int64_t M, int N, int K) {
+  if (mode < MMG_EPI_NONE || mode > MMG_EPI_L2) return 0;
+  if (mode == MMG_EPI_L2) return (M > 512 && (N == 64 || N == 128) && (K == 64 || K == 128)) ? 1 : 0;
+  return (M >= 0 && (K == 64 || K == 128 || K == 256) && N > 0 && N % 64 == 0 && N <= 4096) ? 1 : 0;
+}
+
+// the launch of a shape, whichever the epilogue: the fp32 kernel for the vocab-side tables (M <= 512), else the exact-product
+// 6-term bf16 split on the bf16 matrix cores; epi = the epilogue the launch fuses (mmg_linear_fwd checked that it can)
+static int linear_fwd_launch(const float* X, const ProDev& pr, const float* W, const float* bias, float* Y, int64_t M, int N,
+                             int K, int flags, int epi, double* partial, float* rnorm, float eps, const NextBnDev& nb,
+                             hipStream_t st) {
+  if (M <= 512) {
+    if (K == 64) return launch_small<64>(X, pr, W, bias, Y, M, N, flags, st);
+    if (K == 128) return launch_small<128>(X, pr, W, bias, Y, M, N, flags, st);
+    return launch_small<256>(X, pr, W, bias, Y, M, N, flags, st);
+  }
+  if (K == 64)
+    return N % 128 == 0 ? launch_fwd_x6<64, 4>(X, pr, W, bias, Y, M, N, flags, st, partial, epi, rnorm, eps, nb)
+                        : launch_fwd_x6<64, 2>(X, pr, W, bias, Y, M, N, flags, st, partial, epi, rnorm, eps, nb);
+  if (K == 128)
+    return N % 128 == 0 ? launch_fwd_x6<128, 4>(X, pr, W, bias, Y, M, N, flags, st, partial, epi, rnorm, eps, nb)
+                        : launch_fwd_x6<128, 2>(X, pr, W, bias, Y, M, N, flags, st, partial, epi, rnorm, eps, nb);
+  if (N % 256 == 0) return launch_fwd_h3_k256(X, pr, W, bias, Y, M, N, flags, st, partial);   // one workgroup spans 256 columns
+  // (K = 256 with a 64-wide output: the heads' first layer at 256-d)
+  return N % 128 == 0 ? launch_fwd_x6<256, 4>(X, pr, W, bias, Y, M, N, flags, st, partial, epi, rnorm, eps, nb)
+                      : launch_fwd_x6<256, 2>(X, pr, W, bias, Y, M, N, flags, st, partial, epi, rnorm, eps, nb);
+}
 
 extern "C" int mmg_linear_fwd(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias, float* Y,
-                              int64_t M, int N, int K, int flags, void* stream) {
-  return mmg_linear_fwd_stats(X, pro, W, bias, Y, M, N, K, flags, nullptr, nullptr, 0, stream);
-}
-
-static int linear_fwd_stats_impl(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias,
-                                 float* Y, int64_t M, int N, int K, int flags, double* col_sums, void* ws,
-                                 size_t ws_bytes, void* stream, const mmg_bn_fin_t* fin) {
-  const int accumulate = flags;           // the launchers forward the whole flag word
-  if (col_sums) {
-    MMG_CHECK_ARG(ws && ws_bytes >= mmg_linear_fwd_stats_ws_bytes(M, N), "linear_fwd_stats: workspace too small");
-    MMG_CHECK_ARG(M > 0, "linear_fwd_stats: M must be positive");
-  }
-  double* partial = col_sums ? (double*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) : nullptr;
-  bool stats_done = false;
-  MMG_CHECK_ARG(M >= 0, "linear_fwd: M < 0");
-  MMG_CHECK_ARG((flags & ~(MMG_LIN_ACCUMULATE | MMG_LIN_W_KN)) == 0, "linear_fwd: unknown flag bits");
-  MMG_CHECK_ARG(K == 64 || K == 128 || K == 256, "linear_fwd: K=%d unsupported (64|128|256)", K);
-  MMG_CHECK_ARG(N > 0 && N % 64 == 0 && N <= 4096, "linear_fwd: N=%d must be a multiple of 64", N);
-  if (M == 0) return MMG_OK;
-  MMG_CHECK_ARG(X && W && Y, "linear_fwd: null buffer");
-  MMG_CHECK_ARG(!pro || !pro->scale || pro->shift, "linear_fwd: prologue scale without shift");
-  MMG_CHECK_ARG(!pro || pro->relu == MMG_ACT_NONE || pro->relu == MMG_ACT_RELU, "linear_fwd: the prologue takes relu only");
-  hipStream_t st = (hipStream_t)stream;
-  const ProDev pr = mmg_pro_dev(pro);
-  if (M <= 512) {          // vocab-side tables
-    if (K == 64) launch_small<64>(X, pr, W, bias, Y, M, N, accumulate, st);
-    else if (K == 128) launch_small<128>(X, pr, W, bias, Y, M, N, accumulate, st);
-    else launch_small<256>(X, pr, W, bias, Y, M, N, accumulate, st);
-  } else if (K <= 128 || N % 128 == 0) {
-    // exact-product 6-term bf16 split on the bf16 matrix cores
-    int rc = 0;
-    if (K == 64) {
-      if (N % 128 == 0) rc = launch_fwd_x6<64, 4>(X, pr, W, bias, Y, M, N, accumulate, st, partial);
-      else rc = launch_fwd_x6<64, 2>(X, pr, W, bias, Y, M, N, accumulate, st, partial);
-    } else if (K == 128) {
-      if (N % 128 == 0) rc = launch_fwd_x6<128, 4>(X, pr, W, bias, Y, M, N, accumulate, st, partial);
-      else rc = launch_fwd_x6<128, 2>(X, pr, W, bias, Y, M, N, accumulate, st, partial);
-    } else if (N % 256 == 0) {
-      rc = launch_fwd_h3_k256(X, pr, W, bias, Y, M, N, accumulate, st, partial);     // one workgroup spans 256 columns
-    } else {
-      rc = launch_fwd_x6<256, 4>(X, pr, W, bias, Y, M, N, accumulate, st, partial);
-    }
-    if (rc) return rc;
-    if (col_sums) {     // partial[gy][2][N] -> col_sums[2][N]
-      const int rows = (K == 256 && N % 256 == 0) ? (int)fwd_k256_rows(M, N)
-                                                  : (int)fwd_x6_rows(M, N, N % 128 == 0 ? 128 : 64, K);
-      int rc2 = mmg_partial_sum_bn(partial, col_sums, N, rows, fin, stream);     // (+ the BatchNorm fold when asked for)
-      if (rc2) return rc2;
-      stats_done = true;
-    }
-  } else {
-    // K = 256 with a 64-wide output (the heads' first layer at 256-d)
-    int rc = launch_fwd_x6<256, 2>(X, pr, W, bias, Y, M, N, accumulate, st, partial);
-    if (rc) return rc;
-    if (col_sums) {
-      int rc2 = mmg_partial_sum_bn(partial, col_sums, N, (int)fwd_x6_rows(M, N, 64, K), fin, stream);
-      if (rc2) return rc2;
-      stats_done = true;
-    }
-  }
-  MMG_CHECK_LAUNCH("linear_fwd");
-  if (col_sums && !stats_done) {          // small-M / fp32 kernels: a separate pass over Y
-    int rc3 = mmg_col_reduce2(Y, nullptr, col_sums, M, N, ws, ws_bytes, stream);
-    if (rc3 || !fin) return rc3;
-    return mmg_bn_finalize(col_sums, fin->count, fin->gamma, fin->beta, fin->running_mean, fin->running_var, 1, fin->n_updates,
-                           fin->momentum, fin->eps, fin->scale, fin->shift, fin->mean, fin->rstd, N, stream);
-  }
-  return MMG_OK;
-}
-
-extern "C" int mmg_linear_fwd_stats(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias,
-                                    float* Y, int64_t M, int N, int K, int flags, double* col_sums, void* ws,
-                                    size_t ws_bytes, void* stream) {
-  return linear_fwd_stats_impl(X, pro, W, bias, Y, M, N, K, flags, col_sums, ws, ws_bytes, stream, nullptr);
-}
-
-extern "C" int mmg_linear_fwd_stats_bn(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias,
-                                       float* Y, int64_t M, int N, int K, int flags, double* col_sums, void* ws,
-                                       size_t ws_bytes, const mmg_bn_fin_t* fin, void* stream) {
-  MMG_CHECK_ARG(col_sums && fin && fin->count > 0 && fin->scale && fin->shift, "linear_fwd_stats_bn: col_sums and a fold descriptor are required");
-  return linear_fwd_stats_impl(X, pro, W, bias, Y, M, N, K, flags, col_sums, ws, ws_bytes, stream, fin);
-}
-
-extern "C" int mmg_linear_fwd_next_bn(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias, float* Y,
-                                      int64_t M, int N, int K, int flags, const mmg_next_bn_t* next, void* stream) {
-  if (!next) return mmg_linear_fwd(X, pro, W, bias, Y, M, N, K, flags, stream);
-  const ProDev pr = mmg_pro_dev(pro);
-  const bool fused = M > 512 && N % 128 == 0 && N <= 4096 && (K == 64 || K == 128) && (flags & ~MMG_LIN_W_KN) == 0 &&
-                     !(pr.scale || pr.relu || pr.p > 0.f) && next_bn_fusable(next);
-  if (!fused) {
-    int rc0 = mmg_linear_fwd(X, pro, W, bias, Y, M, N, K, flags, stream);
-    return rc0 ? rc0 : mmg_next_bn_fallback(Y, M, N, next, "linear_fwd_next_bn", stream);
-  }
-  MMG_CHECK_ARG(X && W && Y, "linear_fwd_next_bn: null buffer");
-  NextBnDev nb;
+                              int64_t M, int N, int K, int flags, const mmg_fwd_epi_t* epi, void* stream) {
+  const char* what = "linear_fwd";
+  const int mode = epi ? epi->mode : MMG_EPI_NONE;
   double* partial;
-  int rc = mmg_next_bn_dev(next, M, N, "linear_fwd_next_bn", &nb, &partial);
+  NextBnDev nb;
+  int rc = mmg_epi_prepare(epi, M, N, what, &partial, &nb);
   if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (K == 64) rc = launch_fwd_x6_v<64, 4, false, false, false, true>(X, pr, W, bias, Y, M, N, flags, st, partial, nullptr, 0.f, nb);
-  else rc = launch_fwd_x6_v<128, 4, false, false, false, true>(X, pr, W, bias, Y, M, N, flags, st, partial, nullptr, 0.f, nb);
-  if (rc) return rc;
-  MMG_CHECK_LAUNCH("linear_fwd_next_bn");
-  return mmg_next_bn_finish(next, partial, N, (int)fwd_x6_rows(M, N, 128, K), stream);
-}
-
-extern "C" int mmg_linear_fwd_l2norm_supported(int64_t M, int N, int K) {
-  return (M > 512 && ((N == 128 && (K == 64 || K == 128)) || (N == 64 && (K == 64 || K == 128)))) ? 1 : 0;
-}
-
-extern "C" int mmg_linear_fwd_l2norm(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias, float* Y,
-                                     float* rnorm, int64_t M, int N, int K, float eps, void* stream) {
-  MMG_CHECK_ARG(mmg_linear_fwd_l2norm_supported(M, N, K), "linear_fwd_l2norm: M=%lld N=%d K=%d unsupported (M > 512, N and K in {64,128})",
-                (long long)M, N, K);
-  MMG_CHECK_ARG(X && W && Y && rnorm, "linear_fwd_l2norm: null buffer");
-  MMG_CHECK_ARG(!pro || !pro->scale || pro->shift, "linear_fwd_l2norm: prologue scale without shift");
-  MMG_CHECK_ARG(!pro || pro->relu == MMG_ACT_NONE || pro->relu == MMG_ACT_RELU, "linear_fwd_l2norm: the prologue takes relu only");
+  MMG_CHECK_ARG(mmg_linear_fwd_supported(mode, M, N, K), "%s: M=%lld N=%d K=%d unsupported (%s)", what, (long long)M, N, K,
+                mode == MMG_EPI_L2 ? "L2 epilogue: M > 512, N and K in {64,128}"
+                                   : "K in {64,128,256}, N a multiple of 64 up to 4096");
+  MMG_CHECK_ARG((flags & ~(MMG_LIN_ACCUMULATE | MMG_LIN_W_KN)) == 0, "%s: unknown flag bits", what);
+  MMG_CHECK_ARG(mode != MMG_EPI_L2 || flags == 0, "%s: the L2 epilogue takes no flags", what);
+  if (M == 0) return mmg_epi_finish(epi, Y, 0, N, false, nullptr, 0, what, stream);
+  MMG_CHECK_ARG(X && W && Y, "%s: null buffer", what);
+  MMG_CHECK_ARG(!pro || !pro->scale || pro->shift, "%s: prologue scale without shift", what);
+  MMG_CHECK_ARG(!pro || pro->relu == MMG_ACT_NONE || pro->relu == MMG_ACT_RELU, "%s: the prologue takes relu only", what);
   const ProDev pr = mmg_pro_dev(pro);
-  const bool has_pro = pr.scale || pr.relu || pr.p > 0.f;
+  // STATS and L2 come with every bf16-split launch; NEXT_BN only with the instances of a plain K <= 128 linear
+  bool fused = mode != MMG_EPI_NONE && M > 512;
+  if (mode == MMG_EPI_NEXT_BN)
+    fused = fused && N % 128 == 0 && K <= 128 && !(flags & MMG_LIN_ACCUMULATE) && !(pr.scale || pr.relu || pr.p > 0.f) &&
+            mmg_next_bn_fusable(epi->next);
   hipStream_t st = (hipStream_t)stream;
-  int rc;
-  if (N == 128) {
-    if (K == 128) rc = has_pro ? launch_fwd_x6_v<128, 4, true, false, true>(X, pr, W, bias, Y, M, N, 0, st, nullptr, rnorm, eps)
-                               : launch_fwd_x6_v<128, 4, false, false, true>(X, pr, W, bias, Y, M, N, 0, st, nullptr, rnorm, eps);
-    else rc = has_pro ? launch_fwd_x6_v<64, 4, true, false, true>(X, pr, W, bias, Y, M, N, 0, st, nullptr, rnorm, eps)
-                      : launch_fwd_x6_v<64, 4, false, false, true>(X, pr, W, bias, Y, M, N, 0, st, nullptr, rnorm, eps);
-  } else {
-    if (K == 128) rc = has_pro ? launch_fwd_x6_v<128, 2, true, false, true>(X, pr, W, bias, Y, M, N, 0, st, nullptr, rnorm, eps)
-                               : launch_fwd_x6_v<128, 2, false, false, true>(X, pr, W, bias, Y, M, N, 0, st, nullptr, rnorm, eps);
-    else rc = has_pro ? launch_fwd_x6_v<64, 2, true, false, true>(X, pr, W, bias, Y, M, N, 0, st, nullptr, rnorm, eps)
-                      : launch_fwd_x6_v<64, 2, false, false, true>(X, pr, W, bias, Y, M, N, 0, st, nullptr, rnorm, eps);
-  }
+  rc = linear_fwd_launch(X, pr, W, bias, Y, M, N, K, flags, fused ? mode : MMG_EPI_NONE, fused ? partial : nullptr,
+                         mode == MMG_EPI_L2 ? epi->rnorm : nullptr, mode == MMG_EPI_L2 ? epi->eps : 0.f, nb, st);
   if (rc) return rc;
-  MMG_CHECK_LAUNCH("linear_fwd_l2norm");
-  return MMG_OK;
+  MMG_CHECK_LAUNCH(what);
+  const int rows = (int)(K == 256 && N % 256 == 0 ? fwd_k256_rows(M, N) : fwd_x6_rows(M, N, N % 128 == 0 ? 128 : 64, K));
+  return mmg_epi_finish(epi, Y, M, N, fused, partial, rows, what, stream);
 }
 
 extern "C" int mmg_linear_bnbwd_supported(int mode, int64_t M, int N, int K, int with_wgrad) {
@@ -1970,7 +1917,7 @@ static int bnbwd_run(const float* G, const BnBwdDev& bb, const ProDev& pr, const
   if (wg) return bnbwd_wgrad_run<MODE>(G, bb, pr, pr2, W, dX, M, next, wg, what, st);
   int rc;
   if constexpr (MODE != MMG_BNBWD_BN2) {          // no NBN instance (the entry point refuses next)
-    if (next && K == 128 && N == 128 && next_bn_fusable(next)) {
+    if (next && K == 128 && N == 128 && mmg_next_bn_fusable(next)) {
       NextBnDev nb;
       double* partial;
       rc = mmg_next_bn_dev(next, M, N, what, &nb, &partial);

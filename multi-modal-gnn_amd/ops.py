@@ -13,7 +13,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import _lib
-from ._lib import (BnFinT, HeadGradT, HeadT, NextBnT, PairSavedT, PrologueT, RelT, SmallBnBwdT, SmallBnT, SmallFwdT, SmallWgradT, SumJobT, WgradReduceT, BnBwdT, BnBwdWgradT,
+from ._lib import (BnFinT, FwdEpiT, HeadGradT, HeadT, NextBnT, PairSavedT, PrologueT, RelT, SmallBnBwdT, SmallBnT, SmallFwdT, SmallWgradT, SumJobT, WgradReduceT, BnBwdT, BnBwdWgradT,
                    check)
 
 BN_MOMENTUM = 0.1
@@ -272,11 +272,39 @@ def _bn_fin(count: int, N: int, device, bn):
     return fin, BNFold(st[0], st[1], st[2], st[3], int(count), True)
 
 
+EPI_NONE, EPI_STATS, EPI_NEXT_BN, EPI_L2 = range(4)      # mmg_fwd_epi_t.mode
+
+
+def _fwd_epi(what: str, M: int, N: int, device, with_stats=False, bn=None, next_bn: Optional["NextBN"] = None, l2=False):
+    """The epilogue of one linear_fwd / gather_rows / linear_l2norm_fwd call (mmg_fwd_epi_t; it keeps what it points to
+    alive) -> (descriptor or None, what the call returns after its output: (), (sums,), (sums, BNFold) or (rn,))."""
+    if next_bn is not None:
+        if bn is not None or with_stats:
+            raise ValueError(f"{what}: next_bn excludes the forward statistics")
+        nbt, sums = _next_bn(next_bn, M, N)
+        e = FwdEpiT(EPI_NEXT_BN, next=C.pointer(nbt))
+        e._keep = nbt
+        return e, (sums,)
+    if l2:
+        rn = torch.empty(M, device=device)
+        return FwdEpiT(EPI_L2, rnorm=_p(rn).value, eps=L2_EPS), (rn,)
+    if bn is None and not with_stats:
+        return None, ()
+    sums = torch.empty(2, N, dtype=torch.float64, device=device)
+    ws = workspace(_lib.load().mmg_epi_ws_bytes(M, N), device)
+    fin, fold = _bn_fin(M, N, device, bn) if bn is not None else (None, None)
+    e = FwdEpiT(EPI_STATS, col_sums=_p(sums, torch.float64).value, fin=C.pointer(fin) if fin is not None else None,
+                ws=_p(ws, torch.uint8).value, ws_bytes=ws.numel())
+    e._keep = (fin, ws)
+    return e, (sums,) if fold is None else (sums, fold)
+
+
 def gather_rows(rels: Sequence[Rel], n_rows: int, D: int, out: torch.Tensor, accumulate: bool, with_stats: bool = False,
                 bn=None, next_bn: Optional["NextBN"] = None):
     """with_stats: also return fp64 [2,D] = (column sums, column sums of squares) of the final `out`.
     bn = (gamma, beta, running_mean, running_var, n_updates): also fold the training-mode BatchNorm of `out` in the launch
-    that sums the statistics (mmg_gather_rows_stats_bn) -> (out, sums, BNFold)."""
+    that sums the statistics -> (out, sums, BNFold).
+    next_bn: -> (out, the statistics of the BatchNorm backward that consumes out), see NextBN."""
     lib = _lib.load()
     if tuple(out.shape) != (n_rows, D):
         raise ValueError("gather_rows: out shape")
@@ -285,32 +313,11 @@ def gather_rows(rels: Sequence[Rel], n_rows: int, D: int, out: torch.Tensor, acc
             raise ValueError("gather_rows: rowptr length")
     arr = _rels(rels, D, need_table=True)
     _tok = _pb("gather_rows")
-    fold = None
-    if next_bn is not None:       # -> (out, the statistics of the BatchNorm backward that consumes out), see NextBN
-        if bn is not None or with_stats:
-            raise ValueError("gather_rows: next_bn excludes the forward statistics")
-        nbt, sums = _next_bn(next_bn, n_rows, D)
-        check(lib.mmg_gather_rows_next_bn(arr, len(rels), n_rows, D, _p(out), int(accumulate), C.byref(nbt), _stream()),
-              "mmg_gather_rows_next_bn")
-        _pe(_tok, "gather_rows", _agg_bytes(rels, n_rows, D, accumulate) + 4 * D * n_rows, 0)
-        return out, sums
-    if bn is not None:
-        sums = torch.empty(2, D, dtype=torch.float64, device=out.device)
-        ws = workspace(lib.mmg_gather_rows_stats_ws_bytes(n_rows, D), out.device)
-        fin, fold = _bn_fin(n_rows, D, out.device, bn)
-        check(lib.mmg_gather_rows_stats_bn(arr, len(rels), n_rows, D, _p(out), int(accumulate), _p(sums, torch.float64),
-                                           _p(ws, torch.uint8), ws.numel(), C.byref(fin), _stream()), "mmg_gather_rows_stats_bn")
-    elif with_stats:
-        sums = torch.empty(2, D, dtype=torch.float64, device=out.device)
-        ws = workspace(lib.mmg_gather_rows_stats_ws_bytes(n_rows, D), out.device)
-        check(lib.mmg_gather_rows_stats(arr, len(rels), n_rows, D, _p(out), int(accumulate), _p(sums, torch.float64),
-                                        _p(ws, torch.uint8), ws.numel(), _stream()), "mmg_gather_rows_stats")
-    else:
-        check(lib.mmg_gather_rows(arr, len(rels), n_rows, D, _p(out), int(accumulate), _stream()), "mmg_gather_rows")
-    _pe(_tok, "gather_rows", _agg_bytes(rels, n_rows, D, accumulate), 0)
-    if bn is not None:
-        return out, sums, fold
-    return (out, sums) if with_stats else out
+    epi, extra = _fwd_epi("gather_rows", n_rows, D, out.device, with_stats, bn, next_bn)
+    check(lib.mmg_gather_rows(arr, len(rels), n_rows, D, _p(out), int(accumulate), C.byref(epi) if epi is not None else None,
+                              _stream()), "mmg_gather_rows")
+    _pe(_tok, "gather_rows", _agg_bytes(rels, n_rows, D, accumulate) + (4 * D * n_rows if next_bn is not None else 0), 0)
+    return (out,) + extra if extra else out
 
 
 def scatter_rows(rels: Sequence[Rel], n_rows: int, D: int, x: torch.Tensor):
@@ -338,7 +345,12 @@ def linear_fwd(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = 
     next_bn: -> (out, the statistics of the BatchNorm backward that consumes out), see NextBN.
     with_stats: also return fp64 [2,N] = (column sums, column sums of squares) of out, from the GEMM epilogue.
     bn = (gamma, beta, running_mean, running_var, n_updates): also fold the training-mode BatchNorm of `out` in the launch
-    that sums the statistics (mmg_linear_fwd_stats_bn) -> (out, sums, BNFold)."""
+    that sums the statistics -> (out, sums, BNFold)."""
+    return _linear_fwd(x, W, bias, pro, out, accumulate, w_kn, with_stats=with_stats, bn=bn, next_bn=next_bn)
+
+
+def _linear_fwd(x, W, bias, pro, out, accumulate, w_kn, **epi):
+    """The one call behind linear_fwd and linear_l2norm_fwd (mmg_linear_fwd; epi: the options of _fwd_epi)."""
     lib = _lib.load()
     M, K = x.shape
     N = W.shape[1] if w_kn else W.shape[0]
@@ -351,36 +363,13 @@ def linear_fwd(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = 
     elif tuple(out.shape) != (M, N):
         raise ValueError("linear_fwd: out shape")
     _tok = _pb("linear_fwd")
-    flags = int(accumulate) | (2 if w_kn else 0)
-    fold = None
-    if next_bn is not None:
-        if bn is not None or with_stats:
-            raise ValueError("linear_fwd: next_bn excludes the forward statistics")
-        nbt, sums = _next_bn(next_bn, M, N)
-        check(lib.mmg_linear_fwd_next_bn(_p(x, name="x"), _pro(pro), _p(W, name="W"), _p(bias, name="bias"),
-                                         _p(out, name="out"), M, N, K, flags, C.byref(nbt), _stream()), "mmg_linear_fwd_next_bn")
-        _pe(_tok, "linear_fwd", 4 * (M * K + N * K + M * N * (3 if accumulate else 2)), 2 * M * N * K)
-        return out, sums
-    if bn is not None:
-        sums = torch.empty(2, N, dtype=torch.float64, device=x.device)
-        ws = workspace(lib.mmg_linear_fwd_stats_ws_bytes(M, N), x.device)
-        fin, fold = _bn_fin(M, N, x.device, bn)
-        check(lib.mmg_linear_fwd_stats_bn(_p(x, name="x"), _pro(pro), _p(W, name="W"), _p(bias, name="bias"),
-                                          _p(out, name="out"), M, N, K, flags, _p(sums, torch.float64), _p(ws, torch.uint8),
-                                          ws.numel(), C.byref(fin), _stream()), "mmg_linear_fwd_stats_bn")
-    elif with_stats:
-        sums = torch.empty(2, N, dtype=torch.float64, device=x.device)
-        ws = workspace(lib.mmg_linear_fwd_stats_ws_bytes(M, N), x.device)
-        check(lib.mmg_linear_fwd_stats(_p(x, name="x"), _pro(pro), _p(W, name="W"), _p(bias, name="bias"),
-                                       _p(out, name="out"), M, N, K, flags, _p(sums, torch.float64), _p(ws, torch.uint8),
-                                       ws.numel(), _stream()), "mmg_linear_fwd_stats")
-    else:
-        check(lib.mmg_linear_fwd(_p(x, name="x"), _pro(pro), _p(W, name="W"), _p(bias, name="bias"), _p(out, name="out"),
-                                 M, N, K, flags, _stream()), "mmg_linear_fwd")
-    _pe(_tok, "linear_fwd", 4 * (M * K + N * K + M * N * (2 if accumulate else 1)), 2 * M * N * K)
-    if bn is not None:
-        return out, sums, fold
-    return (out, sums) if with_stats else out
+    desc, extra = _fwd_epi("linear_fwd", M, N, x.device, **epi)
+    check(lib.mmg_linear_fwd(_p(x, name="x"), _pro(pro), _p(W, name="W"), _p(bias, name="bias"), _p(out, name="out"), M, N,
+                             K, int(accumulate) | (2 if w_kn else 0), C.byref(desc) if desc is not None else None,
+                             _stream()), "mmg_linear_fwd")
+    nbn = epi.get("next_bn") is not None          # + the next BatchNorm's y
+    _pe(_tok, "linear_fwd", 4 * (M * K + N * K + M * N * (1 + int(accumulate) + int(nbn))), 2 * M * N * K)
+    return (out,) + extra if extra else out
 
 
 def linear_wgrad(dy: torch.Tensor, x: torch.Tensor, pro: Optional[Pro] = None, out: Optional[torch.Tensor] = None,
@@ -485,7 +474,7 @@ def _next_bn(nb: NextBN, M: int, N: int):
     sums = nb.sums if acc else torch.empty(2, N, dtype=torch.float64, device=nb.y.device)
     if tuple(sums.shape) != (2, N) or sums.dtype != torch.float64:
         raise ValueError("next_bn: sums must be fp64 [2,N]")
-    ws = workspace(lib.mmg_next_bn_ws_bytes(M, N), nb.y.device)
+    ws = workspace(lib.mmg_epi_ws_bytes(M, N), nb.y.device)
     pc = nb.pro.c()
     t = NextBnT(_p(nb.y).value, C.pointer(pc), _p(nb.fold.mean).value, _p(nb.fold.rstd).value,
                 _p(sums, torch.float64).value, int(acc), _p(ws, torch.uint8).value, ws.numel())
@@ -607,19 +596,12 @@ def bn_bwd_apply(g: Optional[torch.Tensor], y: torch.Tensor, pro: Pro, fold: Opt
 
 def linear_l2norm_fwd(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None, pro: Optional[Pro] = None):
     """l2norm_fwd(linear_fwd(x, W, bias, pro)) -> (normalised rows, rn): ONE kernel where the GEMM's workgroup holds whole
-    rows (mmg_linear_fwd_l2norm: the norm is taken in the epilogue), the two launches elsewhere."""
-    lib = _lib.load()
+    rows (the norm is taken in the epilogue, mmg_linear_fwd_supported(MMG_EPI_L2, ...)), the two launches elsewhere."""
     M, K = x.shape
     N = W.shape[0]
-    if not lib.mmg_linear_fwd_l2norm_supported(M, N, K):
+    if not _lib.load().mmg_linear_fwd_supported(EPI_L2, M, N, K):
         return l2norm_fwd(linear_fwd(x, W, bias, pro=pro))
-    out = torch.empty(M, N, device=x.device)
-    rn = torch.empty(M, device=x.device)
-    _tok = _pb("linear_fwd")
-    check(lib.mmg_linear_fwd_l2norm(_p(x), _pro(pro), _p(W), _p(bias), _p(out), _p(rn), M, N, K, L2_EPS, _stream()),
-          "mmg_linear_fwd_l2norm")
-    _pe(_tok, "linear_fwd", 4 * (M * K + N * K + M * N), 2 * M * N * K)
-    return out, rn
+    return _linear_fwd(x, W, bias, pro, None, False, False, l2=True)
 
 
 BNBWD_BN, BNBWD_L2, BNBWD_BN2, BNBWD_ROWS = range(4)        # mmg_bnbwd_t.mode: linear_bnbwd / _l2bwd / _bnbwd2 / _bnbwd_rows

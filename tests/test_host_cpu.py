@@ -79,6 +79,89 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert rc == -1 and b"bad row list" in msg
 
 
+def test_forward_epilogue_rejections_without_a_gpu():
+    """mmg_linear_fwd / mmg_gather_rows refuse a bad mmg_fwd_epi_t on the host side (the fake buffers are never touched)."""
+    import mmgnn  # noqa: F401
+    from mmgnn import _lib
+    lib = _lib.load()
+    NONE, STATS, NEXT_BN, L2 = 0, 1, 2, 3
+    sup = lib.mmg_linear_fwd_supported
+    for mode in (NONE, STATS, NEXT_BN):
+        assert sup(mode, 0, 64, 64) and sup(mode, 8, 4096, 256) and sup(mode, 600, 192, 128)
+        assert not sup(mode, -1, 64, 64) and not sup(mode, 8, 48, 64) and not sup(mode, 8, 4160, 64) and not sup(mode, 8, 64, 96)
+    assert sup(L2, 513, 64, 64) and sup(L2, 600, 128, 128) and sup(L2, 600, 64, 128)
+    assert not sup(L2, 512, 128, 128) and not sup(L2, 600, 256, 128) and not sup(L2, 600, 128, 256)
+    assert not sup(-1, 600, 128, 128) and not sup(4, 600, 128, 128)
+    fake = ctypes.c_void_p(256)
+    M, N = 1000, 128
+    need = lib.mmg_epi_ws_bytes(M, N)
+    assert need >= lib.mmg_col_reduce2_ws_bytes(M, N) and need >= 768 * 2 * N * 8
+    pro = _lib.PrologueT()
+    nxt = _lib.NextBnT(fake, ctypes.pointer(pro), fake, fake, fake, 0, fake, need)
+    rels = (_lib.RelT * 1)(_lib.RelT(fake, fake, None, None, fake, None, 50, 1, None, fake))
+
+    def epi(mode, **fields):
+        e = _lib.FwdEpiT(mode, fake, None, fake, need, None, fake, 1e-12)
+        if mode == NEXT_BN:
+            e.col_sums, e.next = None, ctypes.pointer(nxt)
+        for k, v in fields.items():
+            setattr(e, k, v)
+        return e
+
+    def linear(e, M=M, N=N, K=128, flags=0, X=fake):
+        rc = lib.mmg_linear_fwd(X, None, fake, None, fake, M, N, K, flags, ctypes.byref(e) if e is not None else None, None)
+        return rc, lib.mmg_last_error()
+
+    def gather(e, n_rows=M, D=N):
+        rc = lib.mmg_gather_rows(rels, 1, n_rows, D, fake, 0, ctypes.byref(e), None)
+        return rc, lib.mmg_last_error()
+
+    # NULL is the producer alone: the call gets as far as its own buffers
+    rc, msg = linear(None, X=None)
+    assert rc == -1 and b"null buffer" in msg
+    for call in (linear, gather):
+        for mode in (-1, 4):
+            rc, msg = call(epi(mode))
+            assert rc == -1 and b"unknown epilogue mode" in msg, call
+        for mode, field in ((STATS, "col_sums"), (NEXT_BN, "next"), (L2, "rnorm")):
+            if call is gather and mode == L2:
+                continue
+            rc, msg = call(epi(mode, **{field: None}))
+            assert rc == -1 and b"null field" in msg, (call, mode)
+        rc, msg = call(epi(STATS, ws_bytes=need - 1))
+        assert rc == -1 and b"workspace" in msg
+        rc, msg = call(epi(STATS, ws=None))
+        assert rc == -1 and b"workspace" in msg
+        short = _lib.NextBnT(fake, ctypes.pointer(pro), fake, fake, fake, 0, fake, need - 1)
+        rc, msg = call(epi(NEXT_BN, next=ctypes.pointer(short)))
+        assert rc == -1 and b"workspace" in msg
+        rc, msg = call(epi(STATS, next=ctypes.pointer(nxt)))
+        assert rc == -1 and b"exclusive" in msg
+        for bad in (dict(count=0), dict(scale=None), dict(shift=None)):
+            f = _lib.BnFinT(M, None, None, None, None, 1, 0.1, 1e-5, fake, fake, None, None)
+            for k, v in bad.items():
+                setattr(f, k, v)
+            rc, msg = call(epi(STATS, fin=ctypes.pointer(f)))
+            assert rc == -1 and b"BatchNorm fold" in msg, bad
+    rc, msg = linear(epi(STATS), M=0)
+    assert rc == -1 and b"empty" in msg
+    rc, msg = gather(epi(STATS), n_rows=0)
+    assert rc == -1 and b"empty" in msg
+    # L2: the linear's only, at its shapes, without flags
+    for M_, N_, K_ in ((512, 128, 128), (1000, 256, 128), (1000, 128, 256)):
+        rc, msg = linear(epi(L2), M=M_, N=N_, K=K_)
+        assert rc == -1 and b"unsupported" in msg
+    rc, msg = linear(epi(L2), flags=1)
+    assert rc == -1 and b"no flags" in msg
+    rc, msg = gather(epi(L2))
+    assert rc == -1 and b"L2" in msg
+    # the plain shape rules keep their wording
+    rc, msg = linear(epi(STATS), K=96)
+    assert rc == -1 and b"K=96 unsupported" in msg
+    rc, msg = linear(None, N=48)
+    assert rc == -1 and b"multiple of 64" in msg
+
+
 def test_cpu_model_fails_loudly():
     import mmgnn  # noqa: F401
     from mmgnn.model import build_model

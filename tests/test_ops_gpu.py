@@ -603,7 +603,7 @@ def test_bn_relu_dropout_backward(ops, dev, p):
                                    (2000, 256, 256)])
 @pytest.mark.parametrize("with_pro", [False, True])
 def test_l2_norm_inside_the_dense_forward(ops, dev, M, K, N, with_pro):
-    """mmg_linear_fwd_l2norm (row norm in the GEMM epilogue) == mmg_linear_fwd followed by mmg_l2norm_fwd up to the order
+    """mmg_linear_fwd, MMG_EPI_L2 (row norm in the GEMM epilogue) == the plain mmg_linear_fwd + mmg_l2norm_fwd up to the order
     of the 128 squares of a row, and == F.normalize of an fp64 product; unsupported shapes take the two launches."""
     gen = torch.Generator().manual_seed(5 + M)
     x = torch.randn(M, K, generator=gen).to(dev)
@@ -1073,8 +1073,9 @@ def test_c_abi_error_behaviour(ops, dev):
     rc = lib.mmg_linear_wgrad(C.c_void_p(dy.data_ptr()), C.c_void_p(xx.data_ptr()), None, C.c_void_p(dW.data_ptr()), None,
                               4096, 128, 128, 0, C.c_void_p(ws.data_ptr()), ws.numel(), None)
     assert rc != 0 and b"workspace" in lib.mmg_last_error()
-    # null buffers
-    rc = lib.mmg_linear_fwd(None, None, C.c_void_p(dW.data_ptr()), None, C.c_void_p(dy.data_ptr()), 16, 128, 128, 0, None)
+    # null buffers (flags 0, no epilogue, the null stream)
+    rc = lib.mmg_linear_fwd(None, None, C.c_void_p(dW.data_ptr()), None, C.c_void_p(dy.data_ptr()), 16, 128, 128, 0, None,
+                            None)
     assert rc != 0 and b"null" in lib.mmg_last_error()
     # empty problems are fine
     assert ops.linear_fwd(torch.zeros(0, 64, device=dev), torch.zeros(64, 64, device=dev)).shape == (0, 64)
@@ -1231,25 +1232,42 @@ def test_deferred_weight_gradient_sums(ops, dev):
     assert torch.equal(g1, ref1) and torch.equal(gb1, refb1) and torch.equal(g2, ref2)
 
 
+def _fold_matches_finalize(ops, dev, gen, M, N, produce):
+    """produce(bn=...) == produce(with_stats=True) + bn_finalize, bit for bit (output, sums, fold, running statistics)."""
+    gamma, beta = (torch.rand(N, generator=gen) + 0.5).to(dev), torch.randn(N, generator=gen).to(dev)
+    rm0, rv0 = torch.randn(N, generator=gen).to(dev), (torch.rand(N, generator=gen) + 0.5).to(dev)
+    rm1, rv1 = rm0.clone(), rv0.clone()
+    y0, s0 = produce(with_stats=True)
+    f0 = ops.bn_finalize(s0, M, gamma, beta, rm0, rv0, True, 2)
+    y1, s1, f1 = produce(bn=(gamma, beta, rm1, rv1, 2))
+    assert torch.equal(y0, y1) and torch.equal(s0, s1)
+    for a, c in ((f0.scale, f1.scale), (f0.shift, f1.shift), (f0.mean, f1.mean), (f0.rstd, f1.rstd), (rm0, rm1), (rv0, rv1)):
+        assert torch.equal(a, c)
+    assert f1.count == M and f1.training
+
+
 @pytest.mark.parametrize("M", [5003, 300])
 def test_batchnorm_fold_in_the_statistics_launch(ops, dev, M):
     """linear_fwd(bn=...) == linear_fwd(with_stats) + bn_finalize, bit for bit (fold, running statistics, sums), on the
-    epilogue-statistics path (M > 512) and on the separate-reduction path (small M)."""
+    epilogue-statistics path (M > 512) and on the separate-reduction path (small M).  The same for gather_rows, which
+    shares the fold: the bit-plane layout sums the statistics in its epilogue, the multigraph layout (LDS-resident tables)
+    takes the separate reduction."""
     gen = torch.Generator().manual_seed(31 + M)
     K = N = 128
     x = torch.randn(M, K, generator=gen).to(dev)
     W = (torch.randn(N, K, generator=gen) / K ** 0.5).to(dev)
     b = torch.randn(N, generator=gen).to(dev)
-    gamma, beta = (torch.rand(N, generator=gen) + 0.5).to(dev), torch.randn(N, generator=gen).to(dev)
-    rm0, rv0 = torch.randn(N, generator=gen).to(dev), (torch.rand(N, generator=gen) + 0.5).to(dev)
-    rm1, rv1 = rm0.clone(), rv0.clone()
-    y0, s0 = ops.linear_fwd(x, W, b, with_stats=True)
-    f0 = ops.bn_finalize(s0, M, gamma, beta, rm0, rv0, True, 2)
-    y1, s1, f1 = ops.linear_fwd(x, W, b, bn=(gamma, beta, rm1, rv1, 2))
-    assert torch.equal(y0, y1) and torch.equal(s0, s1)
-    for a, c in ((f0.scale, f1.scale), (f0.shift, f1.shift), (f0.mean, f1.mean), (f0.rstd, f1.rstd), (rm0, rm1), (rv0, rv1)):
-        assert torch.equal(a, c)
-    assert f1.count == M and f1.training
+    _fold_matches_finalize(ops, dev, gen, M, N, lambda **kw: ops.linear_fwd(x, W, b, **kw))
+    base = torch.randn(M, N, generator=gen).to(dev)
+    for simple in (True, False):
+        rels = []
+        for nc, md in zip([50, 114, 100], [50, 9, 25]):
+            rp, col = _csr(ops, dev, simple_edges(gen, M, nc, md), M)
+            _, inv = ops.row_degree(rp)
+            mask_r = ops.rel_mask_build(rp, col, nc)[1] if simple else None
+            rels.append(ops.Rel(rp, col, nc, rowscale=inv, table=torch.randn(nc, N, generator=gen).to(dev), simple=simple,
+                                mask_r=mask_r))
+        _fold_matches_finalize(ops, dev, gen, M, N, lambda **kw: ops.gather_rows(rels, M, N, base.clone(), True, **kw))
 
 
 # ------------------------------------------------------------------------------------------ next-BatchNorm statistics
@@ -1270,7 +1288,7 @@ def _stats_close(ops, got, out, y, pro, fold, bar=1e-6):
 @pytest.mark.parametrize("M,N,K,relu", [(5003, 128, 64, 1), (5003, 128, 128, 1), (700, 256, 64, 1), (2049, 128, 64, 0),
                                          (3000, 64, 64, 1), (300, 128, 64, 1), (3000, 128, 64, 2)])
 def test_next_bn_statistics_from_the_linear_epilogue(ops, dev, M, N, K, relu, p):
-    """mmg_linear_fwd_next_bn: the data-gradient GEMM also returns mmg_bn_bwd_stats of its own output (tail tile, two column
+    """mmg_linear_fwd with MMG_EPI_NEXT_BN: the data-gradient GEMM also returns mmg_bn_bwd_stats of its own output (tail tile, two column
     slices, no activation; N = 64, M <= 512 and leaky_relu take the separate pass inside the call)."""
     gen = torch.Generator().manual_seed(M + N + K)
     dy = torch.randn(M, K, generator=gen).to(dev)
@@ -1330,7 +1348,7 @@ def test_next_bn_statistics_from_the_l2_and_bn_backward_gemms(ops, dev, M, K, N,
 @pytest.mark.parametrize("p", [0.0, 0.3])
 @pytest.mark.parametrize("D,n_rows", [(128, 5000), (256, 1834), (64, 1834)])
 def test_next_bn_statistics_from_the_gather_epilogue(ops, dev, D, n_rows, p):
-    """mmg_gather_rows_next_bn: one relation (the last layer's backward) and three, accumulate or not; D = 64 takes the
+    """mmg_gather_rows with MMG_EPI_NEXT_BN: one relation (the last layer's backward) and three, accumulate or not; D = 64 takes the
     separate pass inside the call."""
     gen = torch.Generator().manual_seed(3 * D + n_rows)
     grels = []
