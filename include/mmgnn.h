@@ -377,6 +377,7 @@ int mmg_linear_bnbwd(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX,
 #define MMG_PROBE_BN_BWD_APPLY 10
 #define MMG_PROBE_ELEMENTWISE 11
 #define MMG_PROBE_PAIR_DENSE_FWD 12
+#define MMG_PROBE_KNN_IMPUTE 13
 int mmg_probe_arm(int n_launches);
 #define MMG_PROBE_NAME_LEN 128
 /* names (nullable): cap * MMG_PROBE_NAME_LEN bytes; entry i receives the instantiated kernel symbol of launch i, e.g.
@@ -652,6 +653,28 @@ int mmg_seg_moments(const float* pred, const float* target, const int64_t* seg, 
 int mmg_seg_metrics(const float* pred, const float* target, const int64_t* seg, int64_t n, int n_seg,
                     const double* moments, float n_sigma, float* pred_out, double* sums, void* ws, size_t ws_bytes,
                     void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Nearest-neighbour lab imputation: sklearn.impute.KNNImputer(n_neighbors, weights).fit_transform(X) on the device
+ * (the reference config's evaluation.baselines "nearest_neighbor"; mmgnn/knn.py).  X is a dense [n_rows, ld_x] fp32
+ * patient x lab matrix, NaN = missing; every row is both a donor and a receiver.  For i < n_out and l < n_cols:
+ *   out[i * ld_out + l] = X[r, l] when it is observed (r = rows[i]); otherwise, over the donors D_l = {d : X[d, l]
+ *   observed} (never r itself) at nan-Euclidean distance dist(r, d) = sqrt(n_cols * S / c) -- c = labs both observe,
+ *   S = sum of (X[r, j] - X[d, j])^2 over them, NaN when c = 0 -- the weighted mean of X[d, l] over the min(k, |D_l|)
+ *   donors of smallest (dist, d), NaN last: weights 0 (uniform) 1 per finite distance, 1 (distance) 1 / dist, or
+ *   [dist == 0] when a chosen distance is 0; NaN distances weigh 0.  Every donor at a NaN distance: the fp64 mean of
+ *   the observed X[:, l] rounded to fp32; D_l empty: NaN (sklearn drops such a column).
+ * Distances are direct masked fp32 sums in lab order (no |x|^2 + |y|^2 - 2xy expansion) from the original X, and the
+ * selection is a total order on (S / c, d), so every output cell is bitwise reproducible and does not depend on which
+ * other rows are requested.  A rows[i] outside [0, n_rows) skips output row i; columns n_cols .. ld_out-1 and skipped
+ * rows are left untouched.  Limits: 1 <= n_cols <= 512, 1 <= n_neighbors <= 32, 0 <= n_rows < 2^31, 0 <= n_out < 2^31,
+ * ld_x >= n_cols, ld_out >= n_cols (MMG_E_ARG); ws: mmg_knn_impute_ws_bytes (the column means; MMG_E_WS).  Every
+ * argument is checked on the host before anything is enqueued.  Cost O(n_out * n_rows * observed labs).
+ * ------------------------------------------------------------------------------------- */
+size_t mmg_knn_impute_ws_bytes(int64_t n_rows, int n_cols, int64_t n_out, int n_neighbors);
+int mmg_knn_impute(const float* X, int64_t n_rows, int n_cols, int64_t ld_x, const int32_t* rows, int64_t n_out,
+                   int n_neighbors, int weights /* 0 uniform, 1 distance */, float* out, int64_t ld_out, void* ws,
+                   size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

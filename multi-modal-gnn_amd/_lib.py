@@ -186,6 +186,8 @@ SIGNATURES = {
     "mmg_seg_metrics": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _f32, _vp, _vp, _vp, _sz, _vp]),
     "mmg_pair_select_ws_bytes": (_sz, [_i64]),
     "mmg_pair_select": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mmg_knn_impute_ws_bytes": (_sz, [_i64, _i32, _i64, _i32]),
+    "mmg_knn_impute": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -5,6 +5,7 @@ and files written as the reference:
   compute_regression_metrics  :36-86     MAE / RMSE / R^2 / MAPE(non-zero targets) in float64
   compute_per_lab_metrics     :89-141    one row per lab with >= 2 samples, sorted by MAE
   GlobalMeanBaseline / PerLabMeanBaseline / evaluate_baselines  :152-230
+  evaluate_nearest_neighbor_baseline  the config's "nearest_neighbor" baseline the reference never wrote (mmgnn.knn)
   stratify_by_patient_degree  :237-287   1-5 / 6-15 / 16+ observed labs
   stratify_by_lab_frequency   :290-342   quartiles of the non-zero lab counts
   evaluate_model              :349-570   predict -> per-lab +-3 sigma winsorisation -> metrics -> json / csv
@@ -137,6 +138,23 @@ def evaluate_baselines(train_data, test_data) -> Dict[str, Dict[str, float]]:
     pl.fit(train_values, train_lab_indices)
     results["per_lab_mean"] = compute_regression_metrics(pl.predict(test_lab_indices), test_values)
     return results
+
+
+def evaluate_nearest_neighbor_baseline(graph, masker, split: str = "test", n_neighbors: int = 5,
+                                       weights: str = "uniform") -> Dict[str, Dict[str, float]]:
+    """The config's third baseline (``evaluation.baselines: nearest_neighbor``, which the reference lists but never
+    implemented): KNNImputer(n_neighbors, weights) fitted on the masker's train edges (mmgnn.knn, one HIP kernel) and
+    read at the ``split`` pairs.  A lab without any train value falls back to the global train mean, as
+    PerLabMeanBaseline does.  Unwinsorised, like the two other baselines; the result merges with evaluate_baselines'."""
+    from .knn import KNNLabImputer
+    tr_ei, tr_v, _, _ = masker.get_masked_data("train", want_mask=False)
+    ev_ei, ev_v, _, _ = masker.get_masked_data(split, want_mask=False)
+    dev = tr_ei.device if tr_ei.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    imp = KNNLabImputer(n_neighbors=n_neighbors, weights=weights).fit(
+        tr_ei[0].to(dev), tr_ei[1].to(dev), tr_v.to(dev), graph["patient"].num_nodes, graph["lab"].num_nodes)
+    pred = imp.predict(ev_ei[0].to(dev), ev_ei[1].to(dev)).cpu().numpy()
+    pred = np.where(np.isnan(pred), np.mean(tr_v.cpu().numpy()), pred)
+    return {"nearest_neighbor": compute_regression_metrics(pred, ev_v.cpu().numpy())}
 
 
 def _groups(groups, predictions, targets):

@@ -89,7 +89,7 @@ def _pe(tok, name, nbytes=0, flops=0):
 
 PROBE_TAGS = {1: "linear_fwd", 2: "linear_wgrad", 3: "linear_wgrad_reduce", 4: "gather_rows", 5: "scatter_rows",
               6: "scatter_reduce", 7: "pair_head_fwd", 8: "pair_head_bwd", 9: "bn_bwd_stats", 10: "bn_bwd_apply",
-              11: "elementwise", 12: "pair_head_dense_fwd"}
+              11: "elementwise", 12: "pair_head_dense_fwd", 13: "knn_impute"}
 
 
 def probe_arm(n: int):
@@ -1257,3 +1257,35 @@ def small_bn_bwd_group(items):
             res.append((dy, dbg[0] if dbg is not None else None, dbg[1] if dbg is not None else None))
         check(lib.mmg_small_bn_bwd_group(arr, len(chunk), N, _stream()), "mmg_small_bn_bwd_group")
     return res
+
+
+KNN_WEIGHTS = {"uniform": 0, "distance": 1}
+
+
+def knn_impute(X, rows, n_neighbors: int, weights: str = "uniform", out=None):
+    """sklearn KNNImputer(n_neighbors, weights).fit_transform(X)[rows] over a dense [N, L] fp32 matrix with NaN = missing
+    (mmg_knn_impute): observed cells pass through, a missing cell is the (weighted) mean of its lab over the n_neighbors
+    nearest rows that observe it (nan-Euclidean distance; ties to the lower row index), a lab nobody has stays NaN.
+    rows: int32 [n] receiver rows of X; out: fp32 [n, W >= L] (columns L .. W-1 and the rows of out-of-range receivers are
+    left as they are; a new out is NaN there).  Returns out."""
+    lib = _lib.load()
+    if weights not in KNN_WEIGHTS:
+        raise ValueError(f"knn_impute: weights must be 'uniform' or 'distance', got {weights!r}")
+    if X.dim() != 2:
+        raise ValueError(f"knn_impute: X must be [rows, labs], got {list(X.shape)}")
+    if rows.dim() != 1:
+        raise ValueError(f"knn_impute: rows must be 1-D, got {list(rows.shape)}")
+    N, L = (int(v) for v in X.shape)
+    n = rows.numel()
+    px, pr = _p(X, name="X"), _p(rows, torch.int32, "rows")
+    if out is None:
+        out = torch.full((n, L), float("nan"), dtype=torch.float32, device=X.device)
+    elif out.dim() != 2 or out.shape[0] != n or out.shape[1] < L:
+        raise ValueError(f"knn_impute: out must be [{n}, >= {L}], got {list(out.shape)}")
+    po = _p(out, name="out")
+    if not (X.device == rows.device == out.device):
+        raise ValueError(f"knn_impute: X, rows and out on different devices ({X.device}, {rows.device}, {out.device})")
+    ws = workspace(lib.mmg_knn_impute_ws_bytes(N, L, n, int(n_neighbors)), X.device)
+    check(lib.mmg_knn_impute(px, N, L, L, pr, n, int(n_neighbors), KNN_WEIGHTS[weights], po, int(out.shape[1]),
+                             _p(ws, torch.uint8), ws.numel(), _stream()), "mmg_knn_impute")
+    return out
