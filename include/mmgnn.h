@@ -676,6 +676,55 @@ int mmg_knn_impute(const float* X, int64_t n_rows, int n_cols, int64_t ld_x, con
                    int n_neighbors, int weights /* 0 uniform, 1 distance */, float* out, int64_t ld_out, void* ws,
                    size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Leakage-audit reducers (src/audit_leakage.py; mmgnn/audit.py).  Every argument is checked on the host before anything
+ * is enqueued (MMG_E_ARG; a short workspace MMG_E_WS); no call synchronises with the host, so each one can be captured.
+ *
+ * mmg_order_stats: out[r] = the value of 0-based rank ranks[r] (a HOST array, 0 <= rank < n) of the n keys in ascending
+ *   order, NaN last (numpy's sort order; -0 and +0 are ordered by sign, which np.partition does not promise).  The keys
+ *   are a[i] (b NULL) or |a[i] - b[i]| formed in fp32 (numpy's abs(y_pred - y_true)).  nan_count (device, nullable):
+ *   the number of NaN keys.  Exact: an 11 / 11 / 10-bit radix select with integer histograms, three histogram launches
+ *   and three one-workgroup selection steps.  1 <= n < 2^31, 1 <= n_ranks <= MMG_OS_MAX_RANKS.
+ * ------------------------------------------------------------------------------------- */
+#define MMG_OS_MAX_RANKS 8
+size_t mmg_order_stats_ws_bytes(int64_t n);
+int mmg_order_stats(const float* a, const float* b, int64_t n, const int64_t* ranks, int n_ranks, float* out,
+                    int64_t* nan_count, void* ws, size_t ws_bytes, void* stream);
+
+/* mmg_robust_sums: one pass over (pred, target), r = pred - target in fp32, for compute_robust_metrics.  The winsorising
+ * bounds are numpy's "linear" percentiles of |r|, formed on the device from the order statistics xs[0 .. n_xs) of
+ * mmg_order_stats (mode |a - b|) and its nan_count (any NaN: the percentile is NaN):
+ *   x_i = xs[p.lo], x_j = xs[p.hi], d = x_j - x_i, value = p.g >= 0.5 ? x_j - d * (1 - p.g) : x_i + d * p.g
+ * every operation rounded in fp32 on its own (no fused multiply-add); the host derives (lo, hi, g) from n and the
+ * percentile as numpy does.  out (device, fp64 [MMG_RS_FIELDS]):
+ *   n, sum |r|, sum r^2, sum t, sum t^2, sum |r| / (|t| + |p| + 1e-8f) (the fp32 SMAPE term), sum |t|,
+ *   sum clip(|r|, lower, upper), sum clip(r, -upper, upper)^2, count(|r| < lower or |r| > upper), count(NaN |r|),
+ *   max |r| (NaN if any is NaN), lower, upper, p95.
+ * fp64 sums over the fp32 terms in a fixed order (per-workgroup rows added in row order): bitwise reproducible. */
+typedef struct {
+  int32_t lo, hi; /* indices into xs of the two order statistics */
+  float g;        /* interpolation weight (fp32, numpy's gamma) */
+} mmg_percentile_t;
+#define MMG_RS_FIELDS 15
+#define MMG_RS_LOWER 12
+#define MMG_RS_UPPER 13
+#define MMG_RS_P95 14
+size_t mmg_robust_sums_ws_bytes(int64_t n);
+int mmg_robust_sums(const float* pred, const float* target, int64_t n, const float* xs, int n_xs,
+                    const int64_t* nan_count, mmg_percentile_t lower, mmg_percentile_t upper, mmg_percentile_t p95,
+                    double* out, void* ws, size_t ws_bytes, void* stream);
+
+/* mmg_split_membership: patient[e] (int64) of every has_lab edge and the three bool (one byte) split masks.  Every
+ * patient in [0, n_patients) gets the word OR of 1 << split over its edges; counts (device, int64 [MMG_SM_FIELDS]):
+ *   counts[m], m = 1..7: patients whose word is m (counts[0] = 0: patients without a masked edge are not counted),
+ *   counts[8]: edges in more than one split, counts[9]: edges in train and in val or test.
+ * Patient ids outside [0, n_patients) are not counted.  Integer counts: exact. */
+#define MMG_SM_FIELDS 10
+size_t mmg_split_membership_ws_bytes(int64_t n_patients);
+int mmg_split_membership(const int64_t* patient, const uint8_t* train_mask, const uint8_t* val_mask,
+                         const uint8_t* test_mask, int64_t n_edges, int64_t n_patients, int64_t* counts, void* ws,
+                         size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

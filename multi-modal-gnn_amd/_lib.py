@@ -102,6 +102,10 @@ class BnBwdWgradT(C.Structure):
                 ("job", C.POINTER(WgradReduceT))]
 
 
+class PercentileT(C.Structure):
+    _fields_ = [("lo", C.c_int32), ("hi", C.c_int32), ("g", C.c_float)]
+
+
 class SumJobT(C.Structure):
     _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p * 4), ("n_src", C.c_int), ("len", C.c_int),
                 ("cols", C.c_int), ("ld_dst", C.c_int), ("ld_src", C.c_int * 4)]
@@ -188,6 +192,13 @@ SIGNATURES = {
     "mmg_pair_select": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mmg_knn_impute_ws_bytes": (_sz, [_i64, _i32, _i64, _i32]),
     "mmg_knn_impute": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _sz, _vp]),
+    "mmg_order_stats_ws_bytes": (_sz, [_i64]),
+    "mmg_order_stats": (C.c_int, [_vp, _vp, _i64, _P(C.c_int64), _i32, _vp, _vp, _vp, _sz, _vp]),
+    "mmg_robust_sums_ws_bytes": (_sz, [_i64]),
+    "mmg_robust_sums": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _vp, PercentileT, PercentileT, PercentileT, _vp, _vp, _sz,
+                                  _vp]),
+    "mmg_split_membership_ws_bytes": (_sz, [_i64]),
+    "mmg_split_membership": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

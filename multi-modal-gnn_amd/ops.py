@@ -1289,3 +1289,82 @@ def knn_impute(X, rows, n_neighbors: int, weights: str = "uniform", out=None):
     check(lib.mmg_knn_impute(px, N, L, L, pr, n, int(n_neighbors), KNN_WEIGHTS[weights], po, int(out.shape[1]),
                              _p(ws, torch.uint8), ws.numel(), _stream()), "mmg_knn_impute")
     return out
+
+
+# ------------------------------------------------------------------------------------------ leakage audit
+MAX_ORDER_RANKS = 8          # MMG_OS_MAX_RANKS
+ROBUST_FIELDS = 15           # MMG_RS_FIELDS
+SPLIT_FIELDS = 10            # MMG_SM_FIELDS
+
+
+def order_stats(a: torch.Tensor, ranks: Sequence[int], b: Optional[torch.Tensor] = None, out=None, nan_count=None):
+    """Exact order statistics (mmg_order_stats): the values of the 0-based ranks (host ints, at most 8) of a -- or of
+    |a - b| formed in fp32 -- in ascending order, NaN last.  -> (fp32 [len(ranks)], int64 [1] NaN count), both on the
+    device; nothing synchronises with the host."""
+    lib = _lib.load()
+    n = a.numel()
+    ranks = [int(r) for r in ranks]
+    if not 1 <= len(ranks) <= MAX_ORDER_RANKS:
+        raise ValueError(f"order_stats: 1..{MAX_ORDER_RANKS} ranks, got {len(ranks)}")
+    if n < 1 or any(r < 0 or r >= n for r in ranks):
+        raise ValueError(f"order_stats: ranks {ranks} outside [0, {n})")
+    pa = _p(a, name="a")
+    pb = None
+    if b is not None:
+        pb = _p(b, name="b")
+        if b.numel() != n or b.device != a.device:
+            raise ValueError("order_stats: a and b must have the same length and device")
+    if out is None:
+        out = torch.empty(len(ranks), dtype=torch.float32, device=a.device)
+    if nan_count is None:
+        nan_count = torch.empty(1, dtype=torch.int64, device=a.device)
+    rk = (C.c_int64 * len(ranks))(*ranks)
+    ws = workspace(lib.mmg_order_stats_ws_bytes(n), a.device)
+    check(lib.mmg_order_stats(pa, pb, n, rk, len(ranks), _p(out, name="out"), _p(nan_count, torch.int64, "nan_count"),
+                              _p(ws, torch.uint8), ws.numel(), _stream()), "mmg_order_stats")
+    return out, nan_count
+
+
+def robust_sums(pred: torch.Tensor, target: torch.Tensor, xs: torch.Tensor, nan_count: torch.Tensor, lower, upper, p95,
+                out=None):
+    """Every sum compute_robust_metrics needs, in one pass (mmg_robust_sums).  xs / nan_count: order_stats of |pred -
+    target|; lower / upper / p95: (index into xs of x_i, index of x_j, fp32 gamma) of numpy's "linear" percentile.
+    -> fp64 [15] on the device: n, sum|r|, sum r^2, sum t, sum t^2, sum smape term, sum|t|, sum winsorised |r|, sum
+    clipped r^2, outside count, NaN count, max|r|, lower, upper, p95 (include/mmgnn.h)."""
+    lib = _lib.load()
+    n = pred.numel()
+    if n < 1 or target.numel() != n:
+        raise ValueError(f"robust_sums: pred and target need the same length >= 1, got {n} and {target.numel()}")
+    if not (pred.device == target.device == xs.device == nan_count.device):
+        raise ValueError("robust_sums: tensors on different devices")
+    pp, pt, px = _p(pred, name="pred"), _p(target, name="target"), _p(xs, name="xs")
+    if out is None:
+        out = torch.empty(ROBUST_FIELDS, dtype=torch.float64, device=pred.device)
+    spec = [_lib.PercentileT(int(lo), int(hi), float(g)) for lo, hi, g in (lower, upper, p95)]
+    ws = workspace(lib.mmg_robust_sums_ws_bytes(n), pred.device)
+    check(lib.mmg_robust_sums(pp, pt, n, px, xs.numel(), _p(nan_count, torch.int64, "nan_count"), *spec,
+                              _p(out, torch.float64, "out"), _p(ws, torch.uint8), ws.numel(), _stream()),
+          "mmg_robust_sums")
+    return out
+
+
+def split_membership(patient: torch.Tensor, train_mask: torch.Tensor, val_mask: torch.Tensor, test_mask: torch.Tensor,
+                     n_patients: int, out=None):
+    """Patients per split-membership class (mmg_split_membership).  patient: int64 [E]; masks: bool [E].
+    -> int64 [10] on the device: [m] for m = 1..7 the patients whose edges fall in exactly the splits of bit mask m
+    (1 train, 2 val, 4 test), [8] edges in more than one split, [9] edges in train and in val or test."""
+    lib = _lib.load()
+    E = patient.numel()
+    masks = (train_mask, val_mask, test_mask)
+    if any(m.numel() != E for m in masks):
+        raise ValueError("split_membership: every mask needs one entry per edge")
+    if any(m.device != patient.device for m in masks):
+        raise ValueError("split_membership: tensors on different devices")
+    pp = _p(patient, torch.int64, "patient")
+    pm = [_p(m, torch.bool, "mask") for m in masks]
+    if out is None:
+        out = torch.empty(SPLIT_FIELDS, dtype=torch.int64, device=patient.device)
+    ws = workspace(lib.mmg_split_membership_ws_bytes(int(n_patients)), patient.device)
+    check(lib.mmg_split_membership(pp, *pm, E, int(n_patients), _p(out, torch.int64, "out"), _p(ws, torch.uint8),
+                                   ws.numel(), _stream()), "mmg_split_membership")
+    return out
