@@ -725,6 +725,91 @@ int mmg_split_membership(const int64_t* patient, const uint8_t* train_mask, cons
                          const uint8_t* test_mask, int64_t n_edges, int64_t n_patients, int64_t* counts, void* ws,
                          size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Lab-event preprocessing (src/preprocess.py:28-164, src/utils.py:309-481; mmgnn/preprocess.py).  Events are device
+ * arrays over n rows: lab and patient as int64 codes (code order = key order; a code outside [0, n_labs) /
+ * [0, n_patients) means "not selected" / "not in the cohort": the row is ignored and never used as an address), value
+ * fp64, time int64 with INT64_MAX for a missing time.  All value arithmetic is fp64, every operation rounded on its own
+ * (no fused multiply-add), no floating-point atomics: results are bitwise reproducible.  0 <= n < 2^31,
+ * 1 <= n_patients < 2^31, 1 <= n_labs <= MMG_PREP_MAX_LABS; n = 0 is valid.  Every argument is checked on the host
+ * before anything is enqueued (MMG_E_ARG; a short workspace MMG_E_WS).  ONLY mmg_lab_aggregate synchronises with the
+ * host (its pair count sizes the caller's outputs); the other calls can be captured.
+ *
+ * Per-lab table: stats [n_labs][MMG_LS_FIELDS] fp64, fields MMG_LS_*.  N counts the non-NaN values, ROWS all rows; a lab
+ * without a valid value has N = 0 and NaN elsewhere ("stats[lab] = None" of the reference: its values pass through).
+ * ------------------------------------------------------------------------------------- */
+#define MMG_PREP_MAX_LABS 2048
+#define MMG_LS_FIELDS 9
+#define MMG_LS_N 0
+#define MMG_LS_MEAN 1
+#define MMG_LS_STD 2 /* ddof = 1; NaN for N <= 1 */
+#define MMG_LS_MIN 3
+#define MMG_LS_MAX 4
+#define MMG_LS_Q25 5
+#define MMG_LS_MEDIAN 6
+#define MMG_LS_Q75 7
+#define MMG_LS_ROWS 8
+#define MMG_PS_TIME 0  /* secondary key: int64 time, ascending, INT64_MAX (missing) last */
+#define MMG_PS_VALUE 1 /* secondary key: fp64 value, ascending, every NaN last */
+#define MMG_AGG_LAST 0
+#define MMG_AGG_MEAN 1
+#define MMG_AGG_MEDIAN 2
+#define MMG_AGG_MIN 3
+#define MMG_AGG_MAX 4
+#define MMG_OUT_NONE 0
+#define MMG_OUT_STD 1 /* remove v < mean - t * std or v > mean + t * std */
+#define MMG_OUT_IQR 2 /* remove v < q25 - t * iqr or v > q75 + t * iqr */
+#define MMG_NORM_ZSCORE 0
+#define MMG_NORM_MINMAX 1
+#define MMG_NORM_ROBUST 2
+#define MMG_LT_OUTLIER 0
+#define MMG_LT_NORMALIZE 1
+#define MMG_LT_INVERSE 2
+
+/* mmg_prep_sort: perm [n] = the row ids in ascending (group, secondary key) order, group = lab * n_patients + patient
+ * (patient NULL: group = lab), ties in input order (a stable LSD radix sort; secondary NULL: the group alone).  Ignored
+ * rows come last under the group n_labs * n_patients.  group_sorted [n] = the group at every sorted position;
+ * value_sorted [n] (nullable, with value_src) = value_src[perm[i]].  The digit passes of the secondary key in which
+ * every key agrees move the data unchanged (decided on the device from the OR / AND of the keys). */
+size_t mmg_prep_sort_ws_bytes(int64_t n);
+int mmg_prep_sort(const int64_t* lab, const int64_t* patient, const void* secondary, int kind, int64_t n,
+                  int64_t n_patients, int n_labs, const double* value_src, int32_t* perm, int64_t* group_sorted,
+                  double* value_sorted, void* ws, size_t ws_bytes, void* stream);
+
+/* mmg_lab_stats: N, MEAN, STD, MIN, MAX, ROWS of every lab over a lab-sorted array (group_sorted / n_patients = the
+ * lab; n_patients = 1 for an array of lab codes), NaN-skipping, pandas' two-pass variance; the quantile fields are set to
+ * NaN.  mmg_lab_quantiles: Q25, MEDIAN, Q75 from a (lab, value)-sorted array (mmg_prep_sort with MMG_PS_VALUE): numpy's
+ * "linear" interpolation x_i + (x_j - x_i) * g, or x_j - (x_j - x_i) * (1 - g) for g >= 0.5; the median of an even
+ * count is (a + b) / 2. */
+size_t mmg_lab_stats_ws_bytes(int n_labs);
+int mmg_lab_stats(const int64_t* group_sorted, const double* value_sorted, int64_t n, int64_t n_patients, int n_labs,
+                  double* stats, void* ws, size_t ws_bytes, void* stream);
+size_t mmg_lab_quantiles_ws_bytes(int n_labs);
+int mmg_lab_quantiles(const int64_t* group_sorted, const double* value_sorted, int64_t n, int64_t n_patients, int n_labs,
+                      double* stats, void* ws, size_t ws_bytes, void* stream);
+
+/* mmg_lab_aggregate: one value per (patient, lab) segment of the sorted events, in (lab, patient) order.  With an
+ * outlier method the values outside the lab's bounds (from stats) and the NaN values leave first, and a segment with no
+ * row left gives no pair; without one every row stays and a NaN can be the result.  MMG_AGG_LAST takes the last
+ * remaining row of the segment (sort with MMG_PS_TIME: the greatest time, among equal times the last in input order, a
+ * missing time wins); MEDIAN needs the MMG_PS_VALUE order; MEAN / MIN / MAX / MEDIAN skip NaN (none left: NaN).
+ * Outputs hold up to n entries; *n_pairs (HOST) receives the count -- this call waits for the stream. */
+size_t mmg_lab_aggregate_ws_bytes(int64_t n);
+int mmg_lab_aggregate(const int64_t* group_sorted, const double* value_sorted, int64_t n, int64_t n_patients, int n_labs,
+                      int method, int outlier_method, double threshold, const double* stats, int64_t* out_patient,
+                      int64_t* out_lab, double* out_value, int64_t* n_pairs, void* ws, size_t ws_bytes, void* stream);
+
+/* mmg_lab_transform: out[i] from value[i] and the table row of lab[i] (lab NULL: row 0 for every element).
+ *   MMG_LT_OUTLIER (method MMG_OUT_STD / MMG_OUT_IQR): NaN where the value lies outside the bounds, else the value;
+ *   MMG_LT_NORMALIZE (method MMG_NORM_*): zscore (std 0 or NaN: v - mean), minmax (range 0 or NaN: v * 0), robust (iqr 0
+ *   or NaN: v - median); MMG_LT_INVERSE: v * spread + location, with no special case for a zero spread.
+ * mmg_lab_inverse_matrix: the inverse of a dense fp32 [n_rows, n_labs] matrix (column c = lab c), formed in fp64 and
+ * rounded once. */
+int mmg_lab_transform(int mode, int method, double threshold, const int64_t* lab, const double* value, int64_t n,
+                      int n_labs, const double* stats, double* out, void* stream);
+int mmg_lab_inverse_matrix(int method, const float* pred, int64_t n_rows, int n_labs, int64_t ld, const double* stats,
+                           float* out, int64_t ld_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,4 +16,8 @@ def __getattr__(name):
     if name in ("HeteroGraph",):
         from . import data
         return getattr(data, name)
+    if name in ("preprocess_lab_events", "aggregate_lab_values", "normalize_lab_values", "remove_outliers",
+                "LabNormalizer"):
+        from . import preprocess
+        return getattr(preprocess, name)
     raise AttributeError(name)

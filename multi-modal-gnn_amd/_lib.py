@@ -199,6 +199,17 @@ SIGNATURES = {
                                   _vp]),
     "mmg_split_membership_ws_bytes": (_sz, [_i64]),
     "mmg_split_membership": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "mmg_prep_sort_ws_bytes": (_sz, [_i64]),
+    "mmg_prep_sort": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mmg_lab_stats_ws_bytes": (_sz, [_i32]),
+    "mmg_lab_stats": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "mmg_lab_quantiles_ws_bytes": (_sz, [_i32]),
+    "mmg_lab_quantiles": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "mmg_lab_aggregate_ws_bytes": (_sz, [_i64]),
+    "mmg_lab_aggregate": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp,
+                                    _P(C.c_int64), _vp, _sz, _vp]),
+    "mmg_lab_transform": (C.c_int, [_i32, _i32, C.c_double, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "mmg_lab_inverse_matrix": (C.c_int, [_i32, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

@@ -1368,3 +1368,154 @@ def split_membership(patient: torch.Tensor, train_mask: torch.Tensor, val_mask: 
     check(lib.mmg_split_membership(pp, *pm, E, int(n_patients), _p(out, torch.int64, "out"), _p(ws, torch.uint8),
                                    ws.numel(), _stream()), "mmg_split_membership")
     return out
+
+
+# ------------------------------------------------------------------------------------------ lab preprocessing
+PREP_MAX_LABS = 2048         # MMG_PREP_MAX_LABS
+LAB_STAT_FIELDS = 9          # MMG_LS_FIELDS: n, mean, std, min, max, q25, median, q75, rows
+LS_N, LS_MEAN, LS_STD, LS_MIN, LS_MAX, LS_Q25, LS_MEDIAN, LS_Q75, LS_ROWS = range(9)
+SORT_BY_TIME, SORT_BY_VALUE = 0, 1
+AGG_CODES = {"last": 0, "mean": 1, "median": 2, "min": 3, "max": 4}
+OUTLIER_CODES = {None: 0, "std": 1, "iqr": 2}
+NORM_CODES = {"zscore": 0, "minmax": 1, "robust": 2}
+_LT_OUTLIER, _LT_NORMALIZE, _LT_INVERSE = 0, 1, 2
+
+
+def _prep_sizes(n, n_patients, n_labs):
+    if not (0 <= n < 2 ** 31 - 1 and 1 <= n_patients < 2 ** 31 - 1 and 1 <= n_labs <= PREP_MAX_LABS):
+        raise ValueError(f"lab preprocessing: n {n}, n_patients {n_patients}, n_labs {n_labs} outside [0, 2^31) / "
+                         f"[1, 2^31) / [1, {PREP_MAX_LABS}]")
+
+
+def prep_sort(lab: torch.Tensor, patient: Optional[torch.Tensor], secondary: Optional[torch.Tensor], n_patients: int,
+              n_labs: int, value: Optional[torch.Tensor] = None):
+    """Stable sort of the rows by (lab * n_patients + patient, secondary) (mmg_prep_sort).  secondary: int64 times
+    (INT64_MAX = missing, last), fp64 values (NaN last) or None.  -> (perm int32 [n], group int64 [n] at the sorted
+    positions, value[perm] or None); rows with a code out of range come last under the group n_labs * n_patients."""
+    lib = _lib.load()
+    n = lab.numel()
+    n_patients = int(n_patients) if patient is not None else 1
+    _prep_sizes(n, n_patients, n_labs)
+    _p(lab, torch.int64, "lab")                               # host tensors are refused before anything is allocated
+    kind = SORT_BY_TIME
+    ps = None
+    if secondary is not None:
+        if secondary.dtype == torch.float64:
+            kind = SORT_BY_VALUE
+        ps = _p(secondary, secondary.dtype if kind == SORT_BY_VALUE else torch.int64, "secondary")
+        if secondary.numel() != n:
+            raise ValueError("prep_sort: secondary needs one entry per row")
+    if (patient is not None and patient.numel() != n) or (value is not None and value.numel() != n):
+        raise ValueError("prep_sort: every column needs one entry per row")
+    perm = torch.empty(n, dtype=torch.int32, device=lab.device)
+    group = torch.empty(n, dtype=torch.int64, device=lab.device)
+    vs = torch.empty(n, dtype=torch.float64, device=lab.device) if value is not None else None
+    ws = workspace(lib.mmg_prep_sort_ws_bytes(n), lab.device)
+    check(lib.mmg_prep_sort(_p(lab, torch.int64, "lab"), _p(patient, torch.int64, "patient"), ps, kind, n, n_patients,
+                            int(n_labs), _p(value, torch.float64, "value"), _p(perm, torch.int32), _p(group, torch.int64),
+                            _p(vs, torch.float64), _p(ws, torch.uint8), ws.numel(), _stream()), "mmg_prep_sort")
+    return perm, group, vs
+
+
+def lab_stats(group_sorted: torch.Tensor, value_sorted: torch.Tensor, n_patients: int, n_labs: int, out=None):
+    """Per-lab n / mean / std (ddof 1) / min / max / rows over a lab-sorted array (mmg_lab_stats) -> fp64
+    [n_labs, 9] on the device, the quantile fields NaN."""
+    lib = _lib.load()
+    n = value_sorted.numel()
+    _prep_sizes(n, n_patients, n_labs)
+    if group_sorted.numel() != n:
+        raise ValueError("lab_stats: group and value need the same length")
+    _p(value_sorted, torch.float64, "value")
+    if out is None:
+        out = torch.empty(n_labs, LAB_STAT_FIELDS, dtype=torch.float64, device=value_sorted.device)
+    ws = workspace(lib.mmg_lab_stats_ws_bytes(n_labs), value_sorted.device)
+    check(lib.mmg_lab_stats(_p(group_sorted, torch.int64, "group"), _p(value_sorted, torch.float64, "value"), n,
+                            int(n_patients), int(n_labs), _p(out, torch.float64, "stats"), _p(ws, torch.uint8), ws.numel(),
+                            _stream()), "mmg_lab_stats")
+    return out
+
+
+def lab_quantiles(group_sorted: torch.Tensor, value_sorted: torch.Tensor, n_patients: int, n_labs: int,
+                  stats: torch.Tensor):
+    """q25 / median / q75 of every lab from a (lab, value)-sorted array into stats (mmg_lab_quantiles)."""
+    lib = _lib.load()
+    n = value_sorted.numel()
+    _prep_sizes(n, n_patients, n_labs)
+    if group_sorted.numel() != n or tuple(stats.shape) != (n_labs, LAB_STAT_FIELDS):
+        raise ValueError("lab_quantiles: group / value lengths or the stats shape do not match")
+    ws = workspace(lib.mmg_lab_quantiles_ws_bytes(n_labs), value_sorted.device)
+    check(lib.mmg_lab_quantiles(_p(group_sorted, torch.int64, "group"), _p(value_sorted, torch.float64, "value"), n,
+                                int(n_patients), int(n_labs), _p(stats, torch.float64, "stats"), _p(ws, torch.uint8),
+                                ws.numel(), _stream()), "mmg_lab_quantiles")
+    return stats
+
+
+def lab_aggregate(group_sorted: torch.Tensor, value_sorted: torch.Tensor, n_patients: int, n_labs: int, method: str,
+                  outlier_method: Optional[str] = None, threshold: float = 5.0, stats: Optional[torch.Tensor] = None):
+    """One value per (patient, lab) segment of the sorted events (mmg_lab_aggregate) -> (patient, lab, value) in (lab,
+    patient) order.  Waits for the stream: the pair count comes back to size the results."""
+    lib = _lib.load()
+    n = value_sorted.numel()
+    _prep_sizes(n, n_patients, n_labs)
+    if group_sorted.numel() != n:
+        raise ValueError("lab_aggregate: group and value need the same length")
+    _p(value_sorted, torch.float64, "value")
+    dev = value_sorted.device
+    op = torch.empty(n, dtype=torch.int64, device=dev)
+    ol = torch.empty(n, dtype=torch.int64, device=dev)
+    ov = torch.empty(n, dtype=torch.float64, device=dev)
+    cnt = C.c_int64(0)
+    ws = workspace(lib.mmg_lab_aggregate_ws_bytes(n), dev)
+    check(lib.mmg_lab_aggregate(_p(group_sorted, torch.int64, "group"), _p(value_sorted, torch.float64, "value"), n,
+                                int(n_patients), int(n_labs), AGG_CODES[method], OUTLIER_CODES[outlier_method],
+                                float(threshold), _p(stats, torch.float64, "stats"), _p(op, torch.int64),
+                                _p(ol, torch.int64), _p(ov, torch.float64), C.byref(cnt), _p(ws, torch.uint8), ws.numel(),
+                                _stream()), "mmg_lab_aggregate")
+    k = int(cnt.value)
+    return op[:k], ol[:k], ov[:k]
+
+
+def lab_transform(mode: int, method: int, value: torch.Tensor, lab: Optional[torch.Tensor], stats: torch.Tensor,
+                  threshold: float = 0.0, out=None):
+    """Element-wise outlier masking / normalise / inverse over the per-lab table (mmg_lab_transform), fp64."""
+    lib = _lib.load()
+    n = value.numel()
+    n_labs = stats.shape[0]
+    if stats.dim() != 2 or stats.shape[1] != LAB_STAT_FIELDS or (lab is not None and lab.numel() != n):
+        raise ValueError("lab_transform: stats must be [n_labs, 9] and lab as long as value")
+    if out is None:
+        out = torch.empty_like(value)
+    check(lib.mmg_lab_transform(mode, method, float(threshold), _p(lab, torch.int64, "lab"),
+                                _p(value, torch.float64, "value"), n, int(n_labs), _p(stats, torch.float64, "stats"),
+                                _p(out, torch.float64, "out"), _stream()), "mmg_lab_transform")
+    return out
+
+
+def lab_outlier_mask(value, lab, stats, method: str, threshold: float):
+    return lab_transform(_LT_OUTLIER, OUTLIER_CODES[method], value, lab, stats, threshold)
+
+
+def lab_normalize(value, lab, stats, method: str):
+    return lab_transform(_LT_NORMALIZE, NORM_CODES[method], value, lab, stats)
+
+
+def lab_inverse(value, lab, stats, method: str):
+    return lab_transform(_LT_INVERSE, NORM_CODES[method], value, lab, stats)
+
+
+def lab_inverse_matrix(pred: torch.Tensor, stats: torch.Tensor, method: str, out=None):
+    """The inverse normalisation of a dense fp32 [n_rows, n_labs] matrix (rows may be strided) (mmg_lab_inverse_matrix)."""
+    lib = _lib.load()
+    if pred.dim() != 2 or pred.stride(1) != 1 or pred.shape[1] != stats.shape[0] or stats.shape[1] != LAB_STAT_FIELDS:
+        raise ValueError("lab_inverse_matrix: pred must be [n_rows, n_labs] with unit column stride, stats [n_labs, 9]")
+    if not pred.is_cuda:
+        raise _lib.MmgError(f"pred: expected a HIP device tensor, got {pred.device} (no CPU fallback)")
+    if pred.dtype != torch.float32:
+        raise TypeError(f"pred: expected torch.float32, got {pred.dtype}")
+    if out is None:
+        out = torch.empty(pred.shape, dtype=torch.float32, device=pred.device)
+    check(lib.mmg_lab_inverse_matrix(NORM_CODES[method], C.c_void_p(pred.data_ptr()), pred.shape[0], pred.shape[1],
+                                     pred.stride(0) if pred.shape[0] > 1 else max(pred.stride(0), pred.shape[1]),
+                                     _p(stats, torch.float64, "stats"), _p(out, torch.float32, "out"), out.shape[1],
+                                     _stream()), "mmg_lab_inverse_matrix")
+    return out

@@ -118,3 +118,54 @@ def make_graph(scale: int = 1, seed: int = 0, device="cpu", shape: Dict = EICU,
 
 def directed_edges(g) -> int:
     return sum(int(g[et].edge_index.shape[1]) for et in g.edge_types)
+
+
+def make_lab_events(scale: int = 1, seed: int = 0, device="cpu", events_per_pair: float = 6.0) -> Dict:
+    """The raw lab events behind make_graph(scale, seed)'s has_lab edges, generated on `device`.
+
+    Every edge (patient, lab) gets 1 + Poisson(events_per_pair - 1) events: times in whole hours of a week, in minutes
+    (many ties inside a pair; ~1e-3 of them missing = INT64_MAX), values lab_loc + lab_spread * N(0, 1) in fp64 with the
+    labs' locations spread over two orders of magnitude, ~1e-3 gross outliers (9999) and ~5e-3 NaN.  A few patients
+    outside the cohort (ids >= n_patients) get events too, and the rows are shuffled.
+    -> dict(patient, lab, value, time: tensors over the events; n_patients, n_labs; edge_index: the graph's has_lab
+    edges).  Patient and lab ids are their codes."""
+    device = torch.device(device)
+    g = make_graph(scale, seed, device)
+    ei = g["patient", "has_lab", "lab"].edge_index
+    P, L, E = int(g["patient"].num_nodes), int(g["lab"].num_nodes), int(ei.shape[1])
+    gen = torch.Generator(device=device).manual_seed(seed + 7919)
+    cnt = 1 + torch.poisson(torch.full((E,), float(events_per_pair) - 1.0, device=device), generator=gen).long()
+    pair = torch.repeat_interleave(torch.arange(E, device=device), cnt)
+    n_out_pat = max(3, P // 600)
+    n_out = 20 * n_out_pat
+    patient = torch.cat([ei[0][pair], P + torch.randint(0, n_out_pat, (n_out,), generator=gen, device=device)])
+    lab = torch.cat([ei[1][pair], torch.randint(0, L, (n_out,), generator=gen, device=device)])
+    N = patient.numel()
+    loc = 10.0 ** torch.linspace(0.0, 2.0, L, dtype=torch.float64, device=device)[torch.randperm(L, generator=gen, device=device)]
+    spread = loc * (0.05 + 0.25 * torch.rand(L, generator=gen, device=device, dtype=torch.float64))
+    value = loc[lab] + spread[lab] * torch.randn(N, generator=gen, device=device, dtype=torch.float64)
+    u = torch.rand(N, generator=gen, device=device)
+    value = torch.where(u < 1e-3, torch.full_like(value, 9999.0), value)
+    value = torch.where((u >= 1e-3) & (u < 6e-3), torch.full_like(value, float("nan")), value)
+    time = torch.randint(0, 7 * 24, (N,), generator=gen, device=device) * 60
+    time = torch.where(torch.rand(N, generator=gen, device=device) < 1e-3,
+                       torch.full_like(time, torch.iinfo(torch.int64).max), time)
+    order = torch.randperm(N, generator=gen, device=device)
+    return {"patient": patient[order].contiguous(), "lab": lab[order].contiguous(), "value": value[order].contiguous(),
+            "time": time[order].contiguous(), "n_patients": P, "n_labs": L, "edge_index": ei}
+
+
+def lab_event_frames(ev: Dict, string_itemid: bool = False):
+    """(labs, cohort) frames of make_lab_events' result, as the reference's aggregate_lab_values takes them: SUBJECT_ID,
+    ITEMID (the lab code, or "lab_%03d" names), VALUENUM, CHARTTIME (minutes; NaN = missing)."""
+    import numpy as np
+    import pandas as pd
+    t = ev["time"].cpu().numpy()
+    miss = t == np.iinfo(np.int64).max
+    lab = ev["lab"].cpu().numpy()
+    labs = pd.DataFrame({"SUBJECT_ID": ev["patient"].cpu().numpy(),
+                         "ITEMID": np.array([f"lab_{i:03d}" for i in range(ev["n_labs"])], dtype=object)[lab]
+                         if string_itemid else lab,
+                         "VALUENUM": ev["value"].cpu().numpy(),
+                         "CHARTTIME": np.where(miss, np.nan, t.astype(np.float64))})
+    return labs, pd.DataFrame({"SUBJECT_ID": np.arange(ev["n_patients"], dtype=np.int64)})
