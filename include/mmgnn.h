@@ -810,6 +810,43 @@ int mmg_lab_transform(int mode, int method, double threshold, const int64_t* lab
 int mmg_lab_inverse_matrix(int method, const float* pred, int64_t n_rows, int n_labs, int64_t ld, const double* stats,
                            float* out, int64_t ld_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Prediction-analysis reducers (src/advanced_visualizations.py: per-lab calibration, error against patient lab-degree,
+ * parity by lab-frequency decile; mmgnn/analysis.py).  A pair is (pred[i], target[i], patient[i], lab[i]); the indices
+ * are int64 (index_bytes 8) or int32 (4) and are narrowed in the kernel's load.  An index outside [0, n_labs) /
+ * [0, n_patients) takes the pair out of the lab sums / the bin sums and is never used as an address.  The degree bins are
+ * half open: bin j takes deg[patient] in [bin_edges[j], bin_edges[j + 1]) (a HOST array of n_bins + 1 ascending values,
+ * +-inf allowed); a pair outside every bin is counted in none.  n_labs = 0 (lab NULL) leaves the lab part out, n_bins = 0
+ * (patient, deg NULL) the bin part.
+ *
+ * mmg_pair_analysis: ONE read of the pairs.  lab_sums (device, fp64 [n_labs][MMG_AN_LAB_FIELDS]):
+ *   n, sum t, sum p, sum t^2, sum t p, sum |p - t|, sum (p - t)^2, min t, max t   (min / max of a lab without a pair:
+ *   +inf / -inf); bin_sums (device, fp64 [n_bins][MMG_AN_BIN_FIELDS]): n, sum |p - t|.  p - t, |p - t| and (p - t)^2
+ *   are formed in fp32, as numpy forms them on fp32 arrays; t^2 and t p are exact in fp64.
+ * mmg_pair_calibrated_abs: the second read.  lab_abs (fp64 [n_labs]) = sum |(a[lab] t + b[lab]) - t| with a, b fp32
+ *   (device, [n_labs]) and every operation rounded in fp32 on its own (numpy's a * targets + b on fp32 operands);
+ *   bin_sq (fp64 [n_bins]) = sum (|p - t| - bin_mean[bin])^2 in fp64 (bin_mean: device, fp64 [n_bins]).  With
+ *   n_bins = 0 pred and patient are not read; with n_labs = 0 lab is not read.
+ * fp64 accumulation without floating-point atomics in an order fixed by n, the table sizes and the order of the pairs:
+ * bitwise reproducible from run to run (csrc/analysis.hip).  Limits: 0 <= n < 2^31, n_labs <= 2048,
+ * n_bins <= MMG_AN_MAX_BINS and 64 n_labs + 768 n_bins <= 163840 (the LDS of one wave; otherwise MMG_E_ARG -- the
+ * caller falls back to host arithmetic).  Every argument is checked on the host before anything is enqueued
+ * (MMG_E_ARG; a short workspace MMG_E_WS); no call synchronises with the host, allocates or uses a memset node, so
+ * each one can be captured.
+ * ------------------------------------------------------------------------------------- */
+#define MMG_AN_MAX_BINS 64
+#define MMG_AN_LAB_FIELDS 9
+#define MMG_AN_BIN_FIELDS 2
+size_t mmg_pair_analysis_ws_bytes(int64_t n, int n_labs, int n_bins);
+int mmg_pair_analysis(const float* pred, const float* target, const void* patient, const void* lab, int index_bytes,
+                      int64_t n, int n_labs, const int32_t* deg, int64_t n_patients, const double* bin_edges, int n_bins,
+                      double* lab_sums, double* bin_sums, void* ws, size_t ws_bytes, void* stream);
+size_t mmg_pair_calibrated_abs_ws_bytes(int64_t n, int n_labs, int n_bins);
+int mmg_pair_calibrated_abs(const float* pred, const float* target, const void* patient, const void* lab, int index_bytes,
+                            int64_t n, int n_labs, const float* a, const float* b, const int32_t* deg,
+                            int64_t n_patients, const double* bin_edges, int n_bins, const double* bin_mean,
+                            double* lab_abs, double* bin_sq, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,4 +20,8 @@ def __getattr__(name):
                 "LabNormalizer"):
         from . import preprocess
         return getattr(preprocess, name)
+    if name in ("run_analysis", "create_per_lab_calibration_table", "create_error_vs_degree_table",
+                "parity_by_frequency_decile"):
+        from . import analysis
+        return getattr(analysis, name)
     raise AttributeError(name)

@@ -210,6 +210,12 @@ SIGNATURES = {
                                     _P(C.c_int64), _vp, _sz, _vp]),
     "mmg_lab_transform": (C.c_int, [_i32, _i32, C.c_double, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "mmg_lab_inverse_matrix": (C.c_int, [_i32, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp]),
+    "mmg_pair_analysis_ws_bytes": (_sz, [_i64, _i32, _i32]),
+    "mmg_pair_analysis": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i64, _P(C.c_double), _i32, _vp, _vp, _vp,
+                                    _sz, _vp]),
+    "mmg_pair_calibrated_abs_ws_bytes": (_sz, [_i64, _i32, _i32]),
+    "mmg_pair_calibrated_abs": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _i64, _P(C.c_double), _i32,
+                                          _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

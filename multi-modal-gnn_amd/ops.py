@@ -1519,3 +1519,84 @@ def lab_inverse_matrix(pred: torch.Tensor, stats: torch.Tensor, method: str, out
                                      _p(stats, torch.float64, "stats"), _p(out, torch.float32, "out"), out.shape[1],
                                      _stream()), "mmg_lab_inverse_matrix")
     return out
+
+
+# ------------------------------------------------------------------------------------------ prediction analysis
+AN_MAX_LABS = 2048           # the lab limit of csrc/analysis.hip (and of csrc/evalred.hip)
+AN_MAX_BINS = 64             # MMG_AN_MAX_BINS
+AN_LAB_FIELDS = 9            # MMG_AN_LAB_FIELDS: n, sum t, sum p, sum t^2, sum t p, sum |p - t|, sum (p - t)^2, min t, max t
+AN_BIN_FIELDS = 2            # MMG_AN_BIN_FIELDS: n, sum |p - t|
+
+
+def _an_index(t: Optional[torch.Tensor], n: int, name: str, dev):
+    if t is None:
+        return None, 8
+    if t.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"{name}: expected int64 or int32 indices, got {t.dtype}")
+    if t.numel() != n:
+        raise ValueError(f"{name}: {t.numel()} indices for {n} pairs")
+    if t.device != dev:
+        raise ValueError(f"{name}: tensors on different devices")
+    return _p(t, t.dtype, name), t.element_size()
+
+
+def _an_args(what, pred, target, patient, lab, n_labs, deg, bin_edges):
+    n = target.numel()
+    dev = target.device
+    if pred is not None and (pred.numel() != n or pred.device != dev):
+        raise ValueError(f"{what}: pred and target need the same length and device")
+    pl, ib_l = _an_index(lab, n, "lab", dev)
+    pp, ib_p = _an_index(patient, n, "patient", dev)
+    if lab is not None and patient is not None and ib_l != ib_p:
+        raise TypeError(f"{what}: patient and lab indices must have the same dtype")
+    n_labs = int(n_labs) if lab is not None else 0
+    edges = [float(e) for e in bin_edges] if (bin_edges is not None and patient is not None) else []
+    n_bins = max(len(edges) - 1, 0)
+    if n_bins and deg is None:
+        raise ValueError(f"{what}: degree bins need deg")
+    ed = (C.c_double * (n_bins + 1))(*edges) if n_bins else None
+    ib = ib_l if lab is not None else ib_p
+    return n, dev, pl, pp, ib, n_labs, n_bins, ed
+
+
+def pair_analysis(pred: torch.Tensor, target: torch.Tensor, lab: Optional[torch.Tensor] = None, n_labs: int = 0,
+                  patient: Optional[torch.Tensor] = None, deg: Optional[torch.Tensor] = None, bin_edges=None):
+    """One read of the pairs (mmg_pair_analysis) -> (lab_sums fp64 [n_labs, 9] or None, bin_sums fp64 [n_bins, 2] or
+    None), on the device.  lab / patient: int64 or int32 [n]; deg: int32 [n_patients]; bin_edges: ascending host floats,
+    bin j = [edges[j], edges[j + 1]).  Fixed-order fp64 sums: bitwise reproducible; nothing synchronises with the host."""
+    lib = _lib.load()
+    n, dev, pl, pp, ib, n_labs, n_bins, ed = _an_args("pair_analysis", pred, target, patient, lab, n_labs, deg, bin_edges)
+    lab_sums = torch.empty(n_labs, AN_LAB_FIELDS, dtype=torch.float64, device=dev) if n_labs else None
+    bin_sums = torch.empty(n_bins, AN_BIN_FIELDS, dtype=torch.float64, device=dev) if n_bins else None
+    ws = workspace(lib.mmg_pair_analysis_ws_bytes(n, n_labs, n_bins), dev)
+    check(lib.mmg_pair_analysis(_p(pred, name="pred"), _p(target, name="target"), pp if n_bins else None, pl, ib, n, n_labs,
+                                _p(deg, torch.int32, "deg") if n_bins else None, deg.numel() if n_bins else 0, ed, n_bins,
+                                _p(lab_sums, torch.float64), _p(bin_sums, torch.float64), _p(ws, torch.uint8), ws.numel(),
+                                _stream()), "mmg_pair_analysis")
+    return lab_sums, bin_sums
+
+
+def pair_calibrated_abs(pred: Optional[torch.Tensor], target: torch.Tensor, lab: Optional[torch.Tensor] = None,
+                        a: Optional[torch.Tensor] = None, b: Optional[torch.Tensor] = None,
+                        patient: Optional[torch.Tensor] = None, deg: Optional[torch.Tensor] = None, bin_edges=None,
+                        bin_mean: Optional[torch.Tensor] = None):
+    """The second read (mmg_pair_calibrated_abs) -> (lab_abs fp64 [n_labs] = sum |(a t + b) - t| with fp32 a, b [n_labs],
+    or None; bin_sq fp64 [n_bins] = sum (|p - t| - bin_mean)^2, or None), on the device."""
+    lib = _lib.load()
+    n, dev, pl, pp, ib, n_labs, n_bins, ed = _an_args("pair_calibrated_abs", pred, target, patient, lab,
+                                                      a.numel() if a is not None else 0, deg, bin_edges)
+    if n_labs and (b is None or b.numel() != n_labs):
+        raise ValueError("pair_calibrated_abs: a and b need one entry per lab")
+    if n_bins and (bin_mean is None or bin_mean.numel() != n_bins or pred is None):
+        raise ValueError("pair_calibrated_abs: degree bins need pred and one mean per bin")
+    lab_abs = torch.empty(n_labs, dtype=torch.float64, device=dev) if n_labs else None
+    bin_sq = torch.empty(n_bins, dtype=torch.float64, device=dev) if n_bins else None
+    ws = workspace(lib.mmg_pair_calibrated_abs_ws_bytes(n, n_labs, n_bins), dev)
+    check(lib.mmg_pair_calibrated_abs(_p(pred, name="pred") if n_bins else None, _p(target, name="target"),
+                                      pp if n_bins else None, pl, ib, n, n_labs, _p(a, name="a") if n_labs else None,
+                                      _p(b, name="b") if n_labs else None, _p(deg, torch.int32, "deg") if n_bins else None,
+                                      deg.numel() if n_bins else 0, ed, n_bins,
+                                      _p(bin_mean, torch.float64, "bin_mean") if n_bins else None,
+                                      _p(lab_abs, torch.float64), _p(bin_sq, torch.float64), _p(ws, torch.uint8), ws.numel(),
+                                      _stream()), "mmg_pair_calibrated_abs")
+    return lab_abs, bin_sq
