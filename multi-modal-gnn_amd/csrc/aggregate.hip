@@ -453,8 +453,7 @@ constexpr int H2_E_DROP = 10;
 // m = a lane's finite magnitude maximum of the block.  Returns 1: multiply this block exactly (bf16 pieces), scale unchanged;
 // 0: split it as f16 pieces at the (possibly lowered) scale after multiplying the accumulators by 2^d.
 __device__ __forceinline__ int h2_decide(float m, H2Scale& hs, int& d) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  m = wave_max_f(m);
   // (scalar from here on: every decision below is a uniform branch and the wave's scale stays in scalar registers -- with
   //  the maximum left in a vector register the compiler treats the whole state as divergent and masks the main loop)
   m = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, m)));
@@ -1719,11 +1718,8 @@ extern "C" int mmg_scatter_rows(const mmg_rel_t* rels, int n_rel, int64_t n_rows
   }
   MMG_CHECK_ARG(x && ws, "scatter_rows: null buffer");
   const size_t need = mmg_scatter_rows_ws_bytes(rels, n_rel, n_rows, D);
-  if (ws_bytes < need) {
-    mmg_set_error("scatter_rows: workspace %zu < %zu", ws_bytes, need);
-    return MMG_E_WS;
-  }
-  float* slab = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  MMG_CHECK_WS("scatter_rows", need);
+  float* slab = MmgCarver(ws).take<float>((need - 256) / sizeof(float));
   // 1. bit-plane strip kernel: simple relations, <= 10 tiles, no rowscale
   const StripPlan sp = plan_strip(rels, n_rel, n_rows, D);
   if (sp.ok) {

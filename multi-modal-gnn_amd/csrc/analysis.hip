@@ -65,21 +65,6 @@ bool an_geom(bool pass2, int64_t n, int L, int B, AnGeom* g) {
   return true;
 }
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_min_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 __device__ __forceinline__ void an_wave_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -413,12 +398,9 @@ extern "C" int mmg_pair_analysis(const float* pred, const float* target, const v
   MMG_CHECK_ARG(an_geom(false, n, n_labs, n_bins, &g),
                 "pair_analysis: %d labs and %d bins need more than %d bytes of LDS (64 per lab, 768 per bin)", n_labs,
                 n_bins, AN_LDS_BYTES);
-  if (!ws || ws_bytes < an_ws_need(g)) {
-    mmg_set_error("pair_analysis: workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, an_ws_need(g));
-    return MMG_E_WS;
-  }
+  MMG_CHECK_WS("pair_analysis", an_ws_need(g));
   hipStream_t st = (hipStream_t)stream;
-  double* partial = (double*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  double* partial = MmgCarver(ws).take<double>((size_t)g.grid * g.row_len);
   const dim3 grid(g.grid), block(g.waves * WAVE);
   if (index_bytes == 8) {
     MMG_CHECK_HIP((MmgMaxLds<&k_pair_analysis<int64_t, false>, AN_LDS_BYTES>::set()), "pair_analysis(attr)");
@@ -460,12 +442,9 @@ extern "C" int mmg_pair_calibrated_abs(const float* pred, const float* target, c
   AnGeom g;
   MMG_CHECK_ARG(an_geom(true, n, n_labs, n_bins, &g),
                 "pair_calibrated_abs: %d labs and %d bins need more than %d bytes of LDS", n_labs, n_bins, AN_LDS_BYTES);
-  if (!ws || ws_bytes < an_ws_need(g)) {
-    mmg_set_error("pair_calibrated_abs: workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, an_ws_need(g));
-    return MMG_E_WS;
-  }
+  MMG_CHECK_WS("pair_calibrated_abs", an_ws_need(g));
   hipStream_t st = (hipStream_t)stream;
-  double* partial = (double*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  double* partial = MmgCarver(ws).take<double>((size_t)g.grid * g.row_len);
   const dim3 grid(g.grid), block(g.waves * WAVE);
   if (index_bytes == 8) {
     MMG_CHECK_HIP((MmgMaxLds<&k_pair_analysis<int64_t, true>, AN_LDS_BYTES>::set()), "pair_calibrated_abs(attr)");

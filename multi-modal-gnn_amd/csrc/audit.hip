@@ -168,7 +168,7 @@ __global__ __launch_bounds__(MMG_OS_MAX_RANKS * WAVE) void k_os_pick(OsState* st
 }
 
 size_t os_hist_bytes() { return (size_t)3 * MMG_OS_MAX_RANKS * OS_BINS * sizeof(uint32_t); }
-size_t os_ws_need() { return os_hist_bytes() + ((sizeof(OsState) + 255) & ~(size_t)255); }
+size_t os_ws_need() { return os_hist_bytes() + mmg_align256(sizeof(OsState)); }
 
 int os_grid(int64_t n) {
   int64_t g = (n + OS_THREADS * 16 - 1) / (OS_THREADS * 16);
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_sm_count(const uint32_t* __restr
   if (threadIdx.x > 0 && threadIdx.x < 8 && s_c[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_c[threadIdx.x]);
 }
 
-size_t sm_ws_need(int64_t n_pat) { return ((size_t)(n_pat > 0 ? n_pat : 1) * sizeof(uint32_t) + 255) & ~(size_t)255; }
+size_t sm_ws_need(int64_t n_pat) { return mmg_align256((size_t)(n_pat > 0 ? n_pat : 1) * sizeof(uint32_t)); }
 
 int sm_grid(int64_t n) {
   int64_t g = (n + SM_THREADS * 8 - 1) / (SM_THREADS * 8);
@@ -336,10 +336,7 @@ extern "C" int mmg_order_stats(const float* a, const float* b, int64_t n, const 
                   (long long)n);
     rk.r[r] = ranks[r];
   }
-  if (!ws || ws_bytes < os_ws_need()) {
-    mmg_set_error("order_stats: workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, os_ws_need());
-    return MMG_E_WS;
-  }
+  MMG_CHECK_WS("order_stats", os_ws_need());
   hipStream_t st = (hipStream_t)stream;
   uint32_t* hist = static_cast<uint32_t*>(ws);
   OsState* state = reinterpret_cast<OsState*>(static_cast<unsigned char*>(ws) + os_hist_bytes());
@@ -376,10 +373,7 @@ extern "C" int mmg_robust_sums(const float* pred, const float* target, int64_t n
     MMG_CHECK_ARG(p->lo >= 0 && p->lo < n_xs && p->hi >= 0 && p->hi < n_xs,
                   "robust_sums: percentile reads order statistics %d / %d of %d", p->lo, p->hi, n_xs);
   MMG_CHECK_ARG(pred && target && xs && nan_count && out, "robust_sums: null buffer");
-  if (!ws || ws_bytes < rs_ws_need(n)) {
-    mmg_set_error("robust_sums: workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, rs_ws_need(n));
-    return MMG_E_WS;
-  }
+  MMG_CHECK_WS("robust_sums", rs_ws_need(n));
   hipStream_t st = (hipStream_t)stream;
   const int g = rs_grid(n);
   double* rows = static_cast<double*>(ws);
@@ -398,11 +392,7 @@ extern "C" int mmg_split_membership(const int64_t* patient, const uint8_t* train
   MMG_CHECK_ARG(n_edges >= 0 && n_patients >= 0, "split_membership: negative size");
   MMG_CHECK_ARG(counts, "split_membership: null counts");
   MMG_CHECK_ARG(n_edges == 0 || (patient && train_mask && val_mask && test_mask), "split_membership: null buffer");
-  if (!ws || ws_bytes < sm_ws_need(n_patients)) {
-    mmg_set_error("split_membership: workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0,
-                  sm_ws_need(n_patients));
-    return MMG_E_WS;
-  }
+  MMG_CHECK_WS("split_membership", sm_ws_need(n_patients));
   hipStream_t st = (hipStream_t)stream;
   uint32_t* word = static_cast<uint32_t*>(ws);
   auto* c = reinterpret_cast<unsigned long long*>(counts);

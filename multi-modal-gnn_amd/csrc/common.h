@@ -74,8 +74,36 @@ bool mmg_probe_take(int tag, int64_t M, int N, int K, int flags, const char* ker
 
 static inline int mmg_valid_D(int D) { return D == 64 || D == 128 || D == 256; }
 
+// ---- caller-provided workspaces.  A buffer inside one starts on a 256-byte boundary and takes a multiple of 256 bytes.
+static inline size_t mmg_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Bump carver: rounds the base up to 256 once, take<T>(count) hands out the next buffer.  Over a null base it only adds
+// up, so ONE list of take() calls gives a *_ws_bytes function its size (need()) and the entry point its pointers.
+struct MmgCarver {
+  uintptr_t p;
+  size_t used = 0;
+  explicit MmgCarver(void* ws) : p(mmg_align256((uintptr_t)ws)) {}
+  template <class T>
+  T* take(size_t count) {
+    T* r = reinterpret_cast<T*>(p + used);
+    used += mmg_align256(count * sizeof(T));
+    return r;
+  }
+  size_t need() const { return used + 256; }      // + the slack of the base round-up
+};
+
+// the one refusal of a short (or missing) workspace; expects the entry point's `ws` and `ws_bytes` in scope
+#define MMG_CHECK_WS(name, need)                                                                           \
+  do {                                                                                                     \
+    const size_t have__ = ws ? (size_t)ws_bytes : (size_t)0, need__ = (size_t)(need);                      \
+    if (have__ < need__ || !ws) {                                                                          \
+      mmg_set_error("%s: workspace of %zu bytes, %zu needed", name, have__, need__);                       \
+      return MMG_E_WS;                                                                                     \
+    }                                                                                                      \
+  } while (0)
+
 // Zero-fill on a stream, as a KERNEL -- never hipMemsetAsync.  Recorded into a hipGraph by stream capture, the memset node
-// of this ROCm (the HIP runtime PyTorch 2.10 + rocm7.0 ships) replays, in about every second graph of a process, with a
+// of this ROCm (the HIP runtime PyTorch 2.10 + rocm7.0 ships) replays, in every graph from its second replay on, with a
 // fill pattern that is not the recorded zero: 16-byte groups {n_dwords, 1, 0, 0} -- or whatever else lies where the pattern
 // is fetched from -- land in the buffer (profiles/probes/hipgraph_memset_node.py).  As denormal floats they are invisible in
 // a sum; as a large value in a buffer the step assumes zeroed (predictions outside the supervised pair lists, gradient
@@ -316,6 +344,21 @@ __device__ static inline float wave_sum(float v) {
 __device__ static inline double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_min_f(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ float wave_max_f(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
 

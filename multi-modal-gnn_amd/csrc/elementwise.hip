@@ -509,8 +509,8 @@ int run_col_reduce(const float* A, const float* B, const ProDev& pr, const float
   ColGeom g;
   MMG_CHECK_ARG(col_geom(M, N, &g), "%s: N=%d unsupported", what, N);
   const size_t need = (size_t)g.nblk * 2 * N * 8 + 256;
-  if (ws_bytes < need) { mmg_set_error("%s: workspace %zu < %zu", what, ws_bytes, need); return MMG_E_WS; }
-  double* partial = (double*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  MMG_CHECK_WS(what, need);
+  double* partial = MmgCarver(ws).take<double>((size_t)g.nblk * 2 * N);
   if (g.nblk == 1) {      // small tables (vocab side): the single workgroup's result IS the answer
     hipLaunchKernelGGL((k_col_reduce<MODE, 256>), dim3(1), dim3(256), 0, st, A, B, pr, mean, rstd, out, M, N, g.rows_per_blk, A2,
                        pr2);
@@ -643,7 +643,7 @@ extern "C" int mmg_bn_bwd_stats_rows(const float* G_rows, const float* Y, const 
   if (n_sel == 0) { MMG_CHECK_HIP(mmg_zero_async(sums, (size_t)2 * N * 8, st), "bn_bwd_stats_rows(memset)"); return MMG_OK; }
   MMG_CHECK_ARG(G_rows && Y && rows && ws, "bn_bwd_stats_rows: null buffer");
   MMG_CHECK_ARG(ws_bytes >= mmg_bn_bwd_stats_rows_ws_bytes(N), "bn_bwd_stats_rows: workspace too small");
-  double* partial = (double*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  double* partial = MmgCarver(ws).take<double>((size_t)BSR_MAX_BLOCKS * 2 * N);
   const int rl = 256 / (N / 4);
   int64_t nblk = (n_sel + rl - 1) / rl;
   if (nblk > BSR_MAX_BLOCKS) nblk = BSR_MAX_BLOCKS;
@@ -737,9 +737,9 @@ extern "C" int mmg_sup_mask_draw(const uint64_t* seed_ptr, uint64_t seed, const 
                                  float* sup, double* count, double* inv_den, void* ws, size_t ws_bytes, void* stream) {
   MMG_CHECK_ARG(n >= 0 && ws && (sup || count || inv_den), "sup_mask_draw: bad args");
   MMG_CHECK_ARG(fraction >= 0.f && fraction <= 1.f, "sup_mask_draw: fraction outside [0, 1]");
-  if (ws_bytes < mmg_sup_mask_ws_bytes(n)) { mmg_set_error("sup_mask_draw: workspace too small"); return MMG_E_WS; }
+  MMG_CHECK_WS("sup_mask_draw", mmg_sup_mask_ws_bytes(n));
   hipStream_t st = (hipStream_t)stream;
-  double* partial = (double*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  double* partial = MmgCarver(ws).take<double>(PL_BLOCKS);
   int64_t nb = (n + 255) / 256;
   if (nb > PL_BLOCKS) nb = PL_BLOCKS;
   if (nb < 1) nb = 1;
@@ -758,9 +758,9 @@ extern "C" int mmg_pair_loss(const float* pred, const float* y, const float* w, 
   MMG_CHECK_ARG(n >= 0 && loss && ws, "pair_loss: bad args");
   MMG_CHECK_ARG(loss_type >= 0 && loss_type <= 2, "pair_loss: loss_type must be 0 (mae), 1 (mse) or 2 (huber)");
   MMG_CHECK_ARG(n == 0 || (pred && y), "pair_loss: null buffer");
-  if (ws_bytes < mmg_pair_loss_ws_bytes(n)) { mmg_set_error("pair_loss: workspace too small"); return MMG_E_WS; }
+  MMG_CHECK_WS("pair_loss", mmg_pair_loss_ws_bytes(n));
   hipStream_t st = (hipStream_t)stream;
-  double* partial = (double*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  double* partial = MmgCarver(ws).take<double>(PL_BLOCKS);
   int64_t nb = (n + 255) / 256;
   if (nb > PL_BLOCKS) nb = PL_BLOCKS;
   if (nb < 1) nb = 1;

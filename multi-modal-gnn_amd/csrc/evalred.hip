@@ -100,7 +100,7 @@ extern "C" int mmg_seg_moments(const float* pred, const float* target, const int
   MMG_CHECK_ARG(moments && ws && ws_bytes >= mmg_seg_reduce_ws_bytes(n, n_seg), "seg_moments: bad buffer / workspace");
   MMG_CHECK_ARG(n == 0 || (pred && target && seg), "seg_moments: null buffer");
   hipStream_t st = (hipStream_t)stream;
-  double* partial = (double*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  double* partial = MmgCarver(ws).take<double>((size_t)EV_BLOCKS * n_seg * 8);
   const int nb = ev_blocks(n);
   constexpr int lds_max = EV_MAXSEG * 8 * 8;
   MMG_CHECK_HIP((MmgMaxLds<&k_seg_moments, lds_max>::set()), "seg_moments(attr)");
@@ -117,7 +117,7 @@ extern "C" int mmg_seg_metrics(const float* pred, const float* target, const int
   MMG_CHECK_ARG(n == 0 || (pred && target && seg), "seg_metrics: null buffer");
   MMG_CHECK_ARG(!(n_sigma > 0.f) || moments, "seg_metrics: clipping needs the moments of pass 1");
   hipStream_t st = (hipStream_t)stream;
-  double* partial = (double*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  double* partial = MmgCarver(ws).take<double>((size_t)EV_BLOCKS * n_seg * 8);
   const int nb = ev_blocks(n);
   constexpr int lds_max = EV_MAXSEG * 8 * 8;
   MMG_CHECK_HIP((MmgMaxLds<&k_seg_metrics, lds_max>::set()), "seg_metrics(attr)");

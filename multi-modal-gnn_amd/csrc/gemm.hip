@@ -1733,7 +1733,7 @@ extern "C" int mmg_next_bn_dev(const mmg_next_bn_t* next, int64_t M, int N, cons
   MMG_CHECK_ARG(next->ws && next->ws_bytes >= mmg_epi_ws_bytes(M, N), "%s: next BatchNorm: workspace too small", what);
   d->Y = next->y; d->mean = next->mean; d->rstd = next->rstd;
   d->pr = mmg_pro_dev(next->pro);
-  *partial = (double*)(((uintptr_t)next->ws + 255) & ~(uintptr_t)255);
+  *partial = MmgCarver(next->ws).take<double>((size_t)768 * 2 * N);
   return MMG_OK;
 }
 extern "C" int mmg_next_bn_finish(const mmg_next_bn_t* next, const double* partial, int N, int rows, void* stream) {
@@ -1778,7 +1778,7 @@ int mmg_epi_prepare(const mmg_fwd_epi_t* e, int64_t M, int N, const char* what, 
   MMG_CHECK_ARG(!e->fin || (e->fin->count > 0 && e->fin->scale && e->fin->shift),
                 "%s: BatchNorm fold without count, scale or shift", what);
   MMG_CHECK_ARG(e->ws && e->ws_bytes >= mmg_epi_ws_bytes(M, N), "%s: statistics workspace too small", what);
-  *partial = (double*)(((uintptr_t)e->ws + 255) & ~(uintptr_t)255);
+  *partial = MmgCarver(e->ws).take<double>((size_t)768 * 2 * N);
   return MMG_OK;
 }
 
@@ -1878,12 +1878,10 @@ static int bnbwd_wgrad_run(const float* G, const BnBwdDev& bb, const ProDev& pr,
   MMG_CHECK_ARG(wg->X && wg->dW && wg->ws, "%s: null weight-gradient buffer", what);
   MMG_CHECK_ARG(!wg->pro || wg->pro->relu == MMG_ACT_NONE || wg->pro->relu == MMG_ACT_RELU, "%s: the X prologue takes relu only", what);
   MMG_CHECK_ARG(!wg->pro || !wg->pro->scale || wg->pro->shift, "%s: X prologue: scale without shift", what);
-  const size_t need = mmg_linear_bnbwd_wgrad_ws_bytes(M, N, K);
-  if (wg->ws_bytes < need) {
-    mmg_set_error("%s: weight-gradient workspace %zu < %zu", what, wg->ws_bytes, need);
-    return MMG_E_WS;
-  }
-  float* slab = (float*)(((uintptr_t)wg->ws + 255) & ~(uintptr_t)255);
+  void* const ws = wg->ws;
+  const size_t ws_bytes = wg->ws_bytes, need = mmg_linear_bnbwd_wgrad_ws_bytes(M, N, K);
+  MMG_CHECK_WS(what, need);
+  float* slab = MmgCarver(ws).take<float>((need - 256) / sizeof(float));
   const int64_t stride = (int64_t)K * N + (wg->dbias ? K : 0);
   const int n_split = (int)bnbwd_fw_rows(M);
   const ProDev xpr = mmg_pro_dev(wg->pro);
@@ -2007,12 +2005,9 @@ static int linear_wgrad_impl(const float* dY, const float* X, const mmg_prologue
   MMG_CHECK_ARG(dY && X && ws, "linear_wgrad: null buffer");
   MMG_CHECK_ARG(!pro || pro->relu == MMG_ACT_NONE || pro->relu == MMG_ACT_RELU, "linear_wgrad: the prologue takes relu only");
   const size_t need = mmg_linear_wgrad_ws_bytes(M, N, K);
-  if (ws_bytes < need) {
-    mmg_set_error("linear_wgrad: workspace %zu < %zu", ws_bytes, need);
-    return MMG_E_WS;
-  }
+  MMG_CHECK_WS("linear_wgrad", need);
   WgradPlan p = plan_wgrad(M, N, K);
-  float* slab = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  float* slab = MmgCarver(ws).take<float>((need - 256) / sizeof(float));
   const ProDev pr = mmg_pro_dev(pro);
   dim3 grid((unsigned)p.n_tiles, (unsigned)p.n_split);
   const int direct = p.n_split == 1 ? (accumulate ? 2 : 1) : 0;     // small M: no slab, no reduce launch

@@ -258,9 +258,7 @@ static int knn_launch(const KnnShape& sh, unsigned grid, hipStream_t st, const f
   return MMG_OK;
 }
 
-static size_t knn_ws_need(int n_cols) {
-  return ((size_t)n_cols * sizeof(float) + 255) & ~(size_t)255;
-}
+static size_t knn_ws_need(int n_cols) { return mmg_align256((size_t)n_cols * sizeof(float)); }
 
 }  // namespace
 
@@ -283,10 +281,7 @@ extern "C" int mmg_knn_impute(const float* X, int64_t n_rows, int n_cols, int64_
   MMG_CHECK_ARG(n_out >= 0 && n_out < (1ll << 31), "knn_impute: n_out %lld outside [0, 2^31)", (long long)n_out);
   if (n_out == 0 || n_rows == 0) return MMG_OK;          // nothing requested / every requested row out of range
   MMG_CHECK_ARG(X && rows && out, "knn_impute: null buffer");
-  if (!ws || ws_bytes < knn_ws_need(n_cols)) {
-    mmg_set_error("knn_impute: workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, knn_ws_need(n_cols));
-    return MMG_E_WS;
-  }
+  MMG_CHECK_WS("knn_impute", knn_ws_need(n_cols));
   const KnnShape sh = knn_shape(n_cols);
   const int64_t grid = (n_out + sh.RT - 1) / sh.RT;
   float* col_mean = static_cast<float*>(ws);

@@ -1849,7 +1849,7 @@ extern "C" int mmg_pair_head_bwd_saved(const mmg_head_t* head, const mmg_head_gr
     if (g > 256) g = 256;                // ONE workgroup is resident per CU; fewer workgroups = fewer partial slabs
     if (g < 1) g = 1;
     MMG_CHECK_ARG(ws && ws_bytes >= mmg_pair_head_bwd_ws_bytes(n_pairs, n_labs), "pair_head_bwd: workspace too small");
-    float* slab = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    float* slab = MmgCarver(ws).take<float>((size_t)256 * pair_slab_floats(n_labs <= 64 ? 2 : 4));
     // a front and a back wave per 32-pair tile (k_pair_bwd_duo), two or four lab tiles of dB accumulators
 #define MMG_LAUNCH_PBWD(KERNEL_, NT_, ...)                                                                            \
   MMG_LAUNCH(MMG_PROBE_PAIR_BWD, n_pairs, 0, 0, want_low ? 2 : 0, KERNEL_, dim3((unsigned)g),                          \

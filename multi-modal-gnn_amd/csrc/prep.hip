@@ -6,30 +6,24 @@
 //   mmg_lab_transform  outlier masking / normalise / inverse-normalise, element-wise over a [n_labs, MMG_LS_FIELDS] table
 //   mmg_lab_inverse_matrix  the inverse over a dense fp32 [n_rows, n_labs] matrix
 //
-// Sort.  Two chained stable sorts of (uint64 key, int32 row id) pairs, 8-bit digits, csr.hip's pass structure (tile
-// histogram -> exclusive scan -> stable scatter, no atomics on the data path): first by the secondary key (the time with
-// the sign bit flipped, or the order-preserving image of the fp64 value with every NaN at the top), then by the group,
-// whose bit width the host knows.  The secondary keys' OR and AND are reduced with integer atomics while the keys are
-// formed; a digit in which they agree is the same in every key, and its pass degenerates to a tile copy (the decision is
-// taken on the device: nothing comes back to the host).
+// Sort.  Two chained stable sorts of (uint64 key, int32 row id) pairs by radix_sort.h: first by the secondary key (the
+// time with the sign bit flipped, or the order-preserving image of the fp64 value with every NaN at the top), then by
+// the group, whose bit width the host knows.  The secondary keys' OR and AND are reduced with integer atomics while the keys are
+// formed: the sort's skip words, which turn the pass over a digit that every key shares into a tile copy.
 //
 // Sums.  A lab's slice of the sorted array is cut into LS_SPLIT contiguous chunks; one workgroup sums a chunk (a fixed
 // stride per thread, a fixed LDS tree), one thread per lab adds the chunk rows in index order: no floating-point atomic
 // anywhere, bitwise reproducible.  The variance is pandas' nanvar: the mean first, then the centred squares.
 #include "common.h"
-#include "scan.h"
+#include "radix_sort.h"
 
 namespace {
 
-constexpr int PS_TILE = 1024;      // items per workgroup tile (256 threads x 4)
 constexpr int PS_NTHR = 256;
-constexpr int PS_GROUPS = PS_TILE / WAVE;
 constexpr int LS_SPLIT = 32;       // chunks per lab
 constexpr int LS_NTHR = 256;
 constexpr int LS_PART = 6;         // n, sum, min, max, rows, centred squares
 constexpr int F = MMG_LS_FIELDS;
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ uint64_t value_key(double v) {
   if (v != v) return ~0ull;                                  // every NaN last, as pandas' and numpy's sorts put them
@@ -87,96 +81,6 @@ __global__ __launch_bounds__(PS_NTHR) void k_ps_group(const int64_t* __restrict_
   keys[i] = ok ? (uint64_t)(l * n_patients + p) : (uint64_t)(n_labs * n_patients);
 }
 
-__device__ __forceinline__ bool ps_skip(const unsigned long long* bits, int shift) {
-  return bits && (((bits[0] ^ bits[1]) >> shift) & 255ull) == 0ull;
-}
-
-__global__ __launch_bounds__(PS_NTHR) void k_ps_hist(const uint64_t* __restrict__ keys, uint32_t* tile_hist, int64_t n,
-                                                     int shift, int64_t n_tiles, const unsigned long long* bits) {
-  __shared__ uint32_t h[256];
-  if (ps_skip(bits, shift)) return;
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * PS_TILE;
-#pragma unroll
-  for (int i = 0; i < PS_TILE / PS_NTHR; ++i) {
-    const int64_t e = base + i * PS_NTHR + threadIdx.x;
-    if (e < n) atomicAdd(&h[(uint32_t)(keys[e] >> shift) & 255u], 1u);
-  }
-  __syncthreads();
-  tile_hist[(int64_t)threadIdx.x * n_tiles + blockIdx.x] = h[threadIdx.x];
-}
-
-__global__ __launch_bounds__(PS_NTHR) void k_ps_scatter(const uint64_t* __restrict__ keys_in,
-                                                        const int32_t* __restrict__ vals_in,
-                                                        uint64_t* __restrict__ keys_out, int32_t* __restrict__ vals_out,
-                                                        const uint32_t* __restrict__ tile_off, int64_t n, int shift,
-                                                        int64_t n_tiles, const unsigned long long* bits) {
-  __shared__ uint32_t gcnt[PS_GROUPS][256];   // per 64-item group: count of each digit -> exclusive offset
-  const int64_t base = (int64_t)blockIdx.x * PS_TILE;
-  if (ps_skip(bits, shift)) {                 // one digit for every key: the pass is the identity
-#pragma unroll
-    for (int i = 0; i < PS_TILE / PS_NTHR; ++i) {
-      const int64_t e = base + i * PS_NTHR + threadIdx.x;
-      if (e < n) {
-        keys_out[e] = keys_in[e];
-        vals_out[e] = vals_in[e];
-      }
-    }
-    return;
-  }
-  for (int i = threadIdx.x; i < PS_GROUPS * 256; i += PS_NTHR) (&gcnt[0][0])[i] = 0;
-  __syncthreads();
-
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  uint64_t key[PS_TILE / PS_NTHR];
-  int32_t val[PS_TILE / PS_NTHR];
-  uint32_t rank[PS_TILE / PS_NTHR];
-  // wave w owns groups 4w .. 4w+3 (consecutive 64-item runs) => item order is preserved
-#pragma unroll
-  for (int i = 0; i < PS_TILE / PS_NTHR; ++i) {
-    const int g = wid * (PS_TILE / PS_NTHR) + i;
-    const int64_t e = base + (int64_t)g * 64 + lane;
-    const bool valid = e < n;
-    key[i] = valid ? keys_in[e] : 0ull;
-    val[i] = valid ? vals_in[e] : 0;
-    const uint32_t d = (uint32_t)(key[i] >> shift) & 255u;
-    unsigned long long m = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const unsigned long long bal = __ballot(bit);
-      m &= bit ? bal : ~bal;
-    }
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    rank[i] = (uint32_t)__popcll(m & lt);
-    if (valid && rank[i] == 0) gcnt[g][d] = (uint32_t)__popcll(m);
-  }
-  __syncthreads();
-  {  // thread d: exclusive scan of digit d over the 16 groups, plus the tile's global offset
-    const int d = threadIdx.x;
-    uint32_t run = tile_off[(int64_t)d * n_tiles + blockIdx.x];
-#pragma unroll
-    for (int g = 0; g < PS_GROUPS; ++g) {
-      const uint32_t c = gcnt[g][d];
-      gcnt[g][d] = run;
-      run += c;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < PS_TILE / PS_NTHR; ++i) {
-    const int g = wid * (PS_TILE / PS_NTHR) + i;
-    const int64_t e = base + (int64_t)g * 64 + lane;
-    if (e < n) {
-      const uint32_t d = (uint32_t)(key[i] >> shift) & 255u;
-      const uint32_t pos = gcnt[g][d] + rank[i];      // < n: the offsets are a scan of counts that sum to n
-      keys_out[pos] = key[i];
-      vals_out[pos] = val[i];
-    }
-  }
-}
-
 __global__ __launch_bounds__(PS_NTHR) void k_ps_finish(const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals,
                                                        const double* __restrict__ value_src, int32_t* __restrict__ perm,
                                                        int64_t* __restrict__ group_sorted,
@@ -195,14 +99,16 @@ inline int bits_of(int64_t n_keys) {       // digits needed for keys in [0, n_ke
   return bits;
 }
 
-size_t ps_ws_need(int64_t n) {
-  const int64_t n_tiles = n > 0 ? (n + PS_TILE - 1) / PS_TILE : 1;
-  size_t b = 256;                                            // OR / AND words
-  b += 2 * align256((size_t)n * 8);                          // keys A, B
-  b += 2 * align256((size_t)n * 4);                          // row ids A, B
-  b += align256((size_t)(256 * n_tiles) * 4);                // tile histograms
-  b += align256(scan_scratch_elems(256 * n_tiles) * 4);
-  return b + 256;
+// the sort's workspace, listed once: over a null base the carver only adds the sizes up
+struct PsWs { unsigned long long* bits; RadixPairs<uint64_t> kv; uint32_t *thist, *scr; };      // bits: OR / AND words
+size_t ps_carve(void* ws, int64_t n, PsWs* w) {
+  const RadixSizes rs = radix_sizes(n);
+  const size_t m = (size_t)n;
+  MmgCarver c(ws);                   // (a braced list is evaluated left to right)
+  *w = PsWs{c.take<unsigned long long>(2),
+            {c.take<uint64_t>(m), c.take<uint64_t>(m), c.take<int32_t>(m), c.take<int32_t>(m)},
+            c.take<uint32_t>(rs.hist_elems), c.take<uint32_t>(rs.scratch_elems)};
+  return c.need();
 }
 
 // ------------------------------------------------------------------------------------------ per-lab slices
@@ -300,7 +206,8 @@ __global__ __launch_bounds__(64) void k_ls_comb(const double* __restrict__ part,
 }
 
 size_t ls_ws_need(int n_labs) {
-  return align256((size_t)(n_labs + 1) * sizeof(int64_t)) + align256((size_t)n_labs * LS_SPLIT * LS_PART * sizeof(double));
+  return mmg_align256((size_t)(n_labs + 1) * sizeof(int64_t)) +
+         mmg_align256((size_t)n_labs * LS_SPLIT * LS_PART * sizeof(double));
 }
 
 // numpy's "linear" quantile of m ascending values (lib/function_base _lerp, both branches), fp64, every operation
@@ -499,7 +406,8 @@ __global__ __launch_bounds__(256) void k_ag_compact(const int64_t* __restrict__ 
 
 size_t ag_ws_need(int64_t n) {
   const int64_t m = n > 0 ? n : 1;
-  return 256 + 2 * align256((size_t)m * 4) + align256((size_t)m * 8) + align256(scan_scratch_elems(m) * 4) + 256;
+  return 256 + 2 * mmg_align256((size_t)m * 4) + mmg_align256((size_t)m * 8) + mmg_align256(scan_scratch_elems(m) * 4) +
+         256;
 }
 
 bool sizes_ok(int64_t n, int64_t n_patients, int n_labs) {
@@ -508,15 +416,10 @@ bool sizes_ok(int64_t n, int64_t n_patients, int n_labs) {
 
 }  // namespace
 
-#define PREP_CHECK_WS(name, need)                                                                          \
-  do {                                                                                                     \
-    if (!ws || ws_bytes < (need)) {                                                                        \
-      mmg_set_error(name ": workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, (size_t)(need)); \
-      return MMG_E_WS;                                                                                     \
-    }                                                                                                      \
-  } while (0)
-
-extern "C" size_t mmg_prep_sort_ws_bytes(int64_t n) { return ps_ws_need(n < 0 ? 0 : n); }
+extern "C" size_t mmg_prep_sort_ws_bytes(int64_t n) {
+  PsWs w;
+  return ps_carve(nullptr, n < 0 ? 0 : n, &w);
+}
 
 extern "C" int mmg_prep_sort(const int64_t* lab, const int64_t* patient, const void* secondary, int kind, int64_t n,
                              int64_t n_patients, int n_labs, const double* value_src, int32_t* perm,
@@ -528,43 +431,26 @@ extern "C" int mmg_prep_sort(const int64_t* lab, const int64_t* patient, const v
   MMG_CHECK_ARG(n == 0 || (lab && perm && group_sorted), "prep_sort: null buffer");
   MMG_CHECK_ARG((value_sorted == nullptr) == (value_src == nullptr) || n == 0,
                 "prep_sort: value_src and value_sorted go together");
-  PREP_CHECK_WS("prep_sort", ps_ws_need(n));
+  PsWs w;
+  MMG_CHECK_WS("prep_sort", ps_carve(ws, n, &w));
   if (n == 0) return MMG_OK;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t n_tiles = (n + PS_TILE - 1) / PS_TILE;
-  char* p = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  auto* bits = (unsigned long long*)p;  p += 256;
-  uint64_t* keys_cur = (uint64_t*)p;    p += align256((size_t)n * 8);
-  uint64_t* keys_nxt = (uint64_t*)p;    p += align256((size_t)n * 8);
-  int32_t* vals_cur = (int32_t*)p;      p += align256((size_t)n * 4);
-  int32_t* vals_nxt = (int32_t*)p;      p += align256((size_t)n * 4);
-  uint32_t* thist = (uint32_t*)p;       p += align256((size_t)(256 * n_tiles) * 4);
-  uint32_t* scr = (uint32_t*)p;
   const unsigned eb = (unsigned)((n + PS_NTHR - 1) / PS_NTHR);
-
-  auto pass = [&](int shift, const unsigned long long* b) {
-    hipLaunchKernelGGL(k_ps_hist, dim3((unsigned)n_tiles), dim3(PS_NTHR), 0, st, keys_cur, thist, n, shift, n_tiles, b);
-    exclusive_scan_u32(thist, 256 * n_tiles, scr, st);
-    hipLaunchKernelGGL(k_ps_scatter, dim3((unsigned)n_tiles), dim3(PS_NTHR), 0, st, keys_cur, vals_cur, keys_nxt,
-                       vals_nxt, thist, n, shift, n_tiles, b);
-    uint64_t* tk = keys_cur; keys_cur = keys_nxt; keys_nxt = tk;
-    int32_t* tv = vals_cur; vals_cur = vals_nxt; vals_nxt = tv;
-  };
   if (secondary) {
-    MMG_CHECK_HIP(mmg_zero_async(thist, (size_t)(256 * n_tiles) * 4, st), "prep_sort(zero)");   // a skipped first pass
-    hipLaunchKernelGGL(k_ps_bits_init, dim3(1), dim3(1), 0, st, bits);
-    hipLaunchKernelGGL(k_ps_init, dim3(eb), dim3(PS_NTHR), 0, st, secondary, kind, keys_cur, vals_cur, n, bits);
+    MMG_CHECK_HIP(mmg_zero_async(w.thist, radix_sizes(n).hist_elems * 4, st), "prep_sort(zero)");   // a skipped first pass
+    hipLaunchKernelGGL(k_ps_bits_init, dim3(1), dim3(1), 0, st, w.bits);
+    hipLaunchKernelGGL(k_ps_init, dim3(eb), dim3(PS_NTHR), 0, st, secondary, kind, w.kv.keys, w.kv.vals, n, w.bits);
     MMG_CHECK_LAUNCH("prep_sort(init)");
-    for (int ps = 0; ps < 8; ++ps) pass(8 * ps, bits);
+    for (int ps = 0; ps < 8; ++ps) radix_pass<true>(w.kv, n, 8 * ps, w.bits, w.thist, w.scr, st);
     MMG_CHECK_LAUNCH("prep_sort(secondary)");
   } else {
-    hipLaunchKernelGGL(k_ps_iota, dim3(eb), dim3(PS_NTHR), 0, st, vals_cur, n);
+    hipLaunchKernelGGL(k_ps_iota, dim3(eb), dim3(PS_NTHR), 0, st, w.kv.vals, n);
   }
-  hipLaunchKernelGGL(k_ps_group, dim3(eb), dim3(PS_NTHR), 0, st, lab, patient, vals_cur, keys_cur, n,
+  hipLaunchKernelGGL(k_ps_group, dim3(eb), dim3(PS_NTHR), 0, st, lab, patient, w.kv.vals, w.kv.keys, n,
                      patient ? n_patients : (int64_t)1, (int64_t)n_labs);
   const int gp = (bits_of((patient ? n_patients : (int64_t)1) * n_labs + 1) + 7) / 8;   // + the sentinel group
-  for (int ps = 0; ps < gp; ++ps) pass(8 * ps, nullptr);
-  hipLaunchKernelGGL(k_ps_finish, dim3(eb), dim3(PS_NTHR), 0, st, keys_cur, vals_cur, value_src, perm, group_sorted,
+  for (int ps = 0; ps < gp; ++ps) radix_pass<true>(w.kv, n, 8 * ps, nullptr, w.thist, w.scr, st);
+  hipLaunchKernelGGL(k_ps_finish, dim3(eb), dim3(PS_NTHR), 0, st, w.kv.keys, w.kv.vals, value_src, perm, group_sorted,
                      value_sorted, n);
   MMG_CHECK_LAUNCH("prep_sort");
   return MMG_OK;
@@ -577,11 +463,11 @@ extern "C" int mmg_lab_stats(const int64_t* group_sorted, const double* value_so
   MMG_CHECK_ARG(sizes_ok(n, n_patients, n_labs), "lab_stats: n %lld, n_patients %lld, n_labs %d out of range",
                 (long long)n, (long long)n_patients, n_labs);
   MMG_CHECK_ARG(stats && (n == 0 || (group_sorted && value_sorted)), "lab_stats: null buffer");
-  PREP_CHECK_WS("lab_stats", ls_ws_need(n_labs) + 256);
+  MMG_CHECK_WS("lab_stats", ls_ws_need(n_labs) + 256);
   hipStream_t st = (hipStream_t)stream;
-  char* p = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  int64_t* ptr = (int64_t*)p;  p += align256((size_t)(n_labs + 1) * sizeof(int64_t));
-  double* part = (double*)p;
+  MmgCarver c(ws);
+  int64_t* ptr = c.take<int64_t>((size_t)n_labs + 1);
+  double* part = c.take<double>((size_t)n_labs * LS_SPLIT * LS_PART);
   hipLaunchKernelGGL(k_lab_ptr, dim3((n_labs + 256) / 256), dim3(256), 0, st, group_sorted, n, n_patients, n_labs, ptr);
   const dim3 grid(n_labs, LS_SPLIT), cg((n_labs + 63) / 64);
   hipLaunchKernelGGL(k_ls_part<0>, grid, dim3(LS_NTHR), 0, st, value_sorted, ptr, stats, part);
@@ -593,7 +479,7 @@ extern "C" int mmg_lab_stats(const int64_t* group_sorted, const double* value_so
 }
 
 extern "C" size_t mmg_lab_quantiles_ws_bytes(int n_labs) {
-  return align256((size_t)((n_labs < 1 ? 1 : n_labs) + 1) * sizeof(int64_t)) + 256;
+  return mmg_align256((size_t)((n_labs < 1 ? 1 : n_labs) + 1) * sizeof(int64_t)) + 256;
 }
 
 extern "C" int mmg_lab_quantiles(const int64_t* group_sorted, const double* value_sorted, int64_t n, int64_t n_patients,
@@ -601,9 +487,9 @@ extern "C" int mmg_lab_quantiles(const int64_t* group_sorted, const double* valu
   MMG_CHECK_ARG(sizes_ok(n, n_patients, n_labs), "lab_quantiles: n %lld, n_patients %lld, n_labs %d out of range",
                 (long long)n, (long long)n_patients, n_labs);
   MMG_CHECK_ARG(stats && (n == 0 || (group_sorted && value_sorted)), "lab_quantiles: null buffer");
-  PREP_CHECK_WS("lab_quantiles", mmg_lab_quantiles_ws_bytes(n_labs));
+  MMG_CHECK_WS("lab_quantiles", mmg_lab_quantiles_ws_bytes(n_labs));
   hipStream_t st = (hipStream_t)stream;
-  int64_t* ptr = (int64_t*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  int64_t* ptr = MmgCarver(ws).take<int64_t>((size_t)n_labs + 1);
   hipLaunchKernelGGL(k_lab_ptr, dim3((n_labs + 256) / 256), dim3(256), 0, st, group_sorted, n, n_patients, n_labs, ptr);
   hipLaunchKernelGGL(k_lq, dim3((n_labs + 63) / 64), dim3(64), 0, st, value_sorted, ptr, n_labs, stats);
   MMG_CHECK_LAUNCH("lab_quantiles");
@@ -625,16 +511,16 @@ extern "C" int mmg_lab_aggregate(const int64_t* group_sorted, const double* valu
   MMG_CHECK_ARG(n_pairs, "lab_aggregate: n_pairs is null");
   MMG_CHECK_ARG(n == 0 || (group_sorted && value_sorted && out_patient && out_lab && out_value),
                 "lab_aggregate: null buffer");
-  PREP_CHECK_WS("lab_aggregate", ag_ws_need(n));
+  MMG_CHECK_WS("lab_aggregate", ag_ws_need(n));
   *n_pairs = 0;
   if (n == 0) return MMG_OK;
   hipStream_t st = (hipStream_t)stream;
-  char* p = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  int64_t* count = (int64_t*)p;   p += 256;
-  uint32_t* keep = (uint32_t*)p;  p += align256((size_t)n * 4);
-  uint32_t* pos = (uint32_t*)p;   p += align256((size_t)n * 4);
-  double* segval = (double*)p;    p += align256((size_t)n * 8);
-  uint32_t* scr = (uint32_t*)p;
+  MmgCarver c(ws);
+  int64_t* count = c.take<int64_t>(1);
+  uint32_t* keep = c.take<uint32_t>((size_t)n);
+  uint32_t* pos = c.take<uint32_t>((size_t)n);
+  double* segval = c.take<double>((size_t)n);
+  uint32_t* scr = c.take<uint32_t>(scan_scratch_elems(n));
   const unsigned eb = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(k_ag_heads, dim3(eb), dim3(256), 0, st, group_sorted, value_sorted, n,
                      (int64_t)n_labs * n_patients, n_patients, method, outlier_method != MMG_OUT_NONE ? 1 : 0,

@@ -97,7 +97,7 @@ def kernel_stats(scale, limit):
         for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
             for row in csv.DictReader(open(f)):
                 name = row["Name"].split("(anonymous namespace)::")[-1].split("(")[0]
-                if name.startswith(("k_ps_", "k_ls_", "k_lq", "k_lt", "k_ag_", "k_lab_ptr", "k_scan", "mmg_k_zero")):
+                if name.startswith(("k_ps_", "k_radix_", "k_ls_", "k_lq", "k_lt", "k_ag_", "k_lab_ptr", "k_scan", "mmg_k_zero")):
                     e = rows.setdefault(name, {"calls": 0, "total_us": 0.0})
                     e["calls"] += int(row["Calls"])
                     e["total_us"] += int(row["TotalDurationNs"]) / 1e3

@@ -162,6 +162,81 @@ def test_forward_epilogue_rejections_without_a_gpu():
     assert rc == -1 and b"multiple of 64" in msg
 
 
+def test_short_workspace_is_refused_the_same_way_everywhere():
+    """Every entry point that answers MMG_E_WS, with otherwise valid arguments: one byte short of its *_ws_bytes is -3, and
+    the message names the entry point and the workspace.  The ones whose workspace check also covers a null `ws` refuse
+    that the same way.  The fake buffers are never touched: the refusal comes before any HIP call."""
+    import mmgnn  # noqa: F401
+    from mmgnn import _lib
+    lib = _lib.load()
+    p = ctypes.c_void_p(256)
+    pro = _lib.PrologueT()
+    pct = _lib.PercentileT(0, 1, 0.5)
+    ranks = (ctypes.c_int64 * 1)(3)
+    edges = (ctypes.c_double * 3)(0.0, 1.0, 2.0)
+    cnt = ctypes.c_int64(0)
+    rels = (_lib.RelT * 1)(_lib.RelT(p, p, None, None, p, p, 50, 1, None, p))
+    bn = _lib.BnBwdT(0, p, None, None, 0, p, ctypes.pointer(pro), None, p, p, None, 1.0, None, None, None, 1e-12)
+    assert lib.mmg_linear_bnbwd_supported(0, 1000, 128, 128, 1)
+
+    def bnbwd(ws, nb):
+        wg = _lib.BnBwdWgradT(p, None, p, None, 0, ws, nb, None)
+        return lib.mmg_linear_bnbwd(ctypes.byref(bn), p, None, p, 1000, 128, 128, None, ctypes.byref(wg), None)
+
+    # (name in the message, bytes needed, call(ws, ws_bytes), null ws is a workspace refusal too)
+    table = [
+        ("csr_build", lib.mmg_csr_build_ws_bytes(5000, 100),
+         lambda ws, nb: lib.mmg_csr_build(p, 5000, 100, 0, p, p, p, ws, nb, None), False),
+        ("scatter_rows", lib.mmg_scatter_rows_ws_bytes(rels, 1, 1000, 128),
+         lambda ws, nb: lib.mmg_scatter_rows(rels, 1, 1000, 128, p, ws, nb, None), False),
+        ("linear_wgrad", lib.mmg_linear_wgrad_ws_bytes(1000, 128, 128),
+         lambda ws, nb: lib.mmg_linear_wgrad(p, p, None, p, None, 1000, 128, 128, 0, ws, nb, None), False),
+        ("linear_wgrad", lib.mmg_linear_wgrad_ws_bytes(1000, 128, 128),
+         lambda ws, nb: lib.mmg_linear_wgrad_deferred(p, p, None, p, None, 1000, 128, 128, 0, ws, nb, None,
+                                                      ctypes.byref(_lib.WgradReduceT())), False),
+        ("linear_bnbwd", lib.mmg_linear_bnbwd_wgrad_ws_bytes(1000, 128, 128), bnbwd, False),
+        ("col_reduce2", lib.mmg_col_reduce2_ws_bytes(1000, 128),
+         lambda ws, nb: lib.mmg_col_reduce2(p, p, p, 1000, 128, ws, nb, None), False),
+        ("bn_bwd_stats", lib.mmg_col_reduce2_ws_bytes(1000, 128),
+         lambda ws, nb: lib.mmg_bn_bwd_stats(p, p, ctypes.byref(pro), p, p, p, 1000, 128, ws, nb, None), False),
+        ("bn_bwd_stats2", lib.mmg_col_reduce2_ws_bytes(1000, 128),
+         lambda ws, nb: lib.mmg_bn_bwd_stats2(p, p, p, ctypes.byref(pro), ctypes.byref(pro), p, p, p, 1000, 128, ws, nb,
+                                              None), False),
+        ("sup_mask_draw", lib.mmg_sup_mask_ws_bytes(1000),
+         lambda ws, nb: lib.mmg_sup_mask_draw(None, 1, p, 1000, 0.2, p, p, p, ws, nb, None), False),
+        ("pair_loss", lib.mmg_pair_loss_ws_bytes(1000),
+         lambda ws, nb: lib.mmg_pair_loss(p, p, None, None, 1000, 1.0, None, 0, p, p, ws, nb, None), False),
+        ("knn_impute", lib.mmg_knn_impute_ws_bytes(100, 50, 10, 5),
+         lambda ws, nb: lib.mmg_knn_impute(p, 100, 50, 50, p, 10, 5, 0, p, 50, ws, nb, None), True),
+        ("order_stats", lib.mmg_order_stats_ws_bytes(10),
+         lambda ws, nb: lib.mmg_order_stats(p, None, 10, ranks, 1, p, p, ws, nb, None), True),
+        ("robust_sums", lib.mmg_robust_sums_ws_bytes(10),
+         lambda ws, nb: lib.mmg_robust_sums(p, p, 10, p, 2, p, pct, pct, pct, p, ws, nb, None), True),
+        ("split_membership", lib.mmg_split_membership_ws_bytes(100),
+         lambda ws, nb: lib.mmg_split_membership(p, p, p, p, 10, 100, p, ws, nb, None), True),
+        ("prep_sort", lib.mmg_prep_sort_ws_bytes(10),
+         lambda ws, nb: lib.mmg_prep_sort(p, p, p, 0, 10, 4, 2, None, p, p, None, ws, nb, None), True),
+        ("lab_stats", lib.mmg_lab_stats_ws_bytes(2),
+         lambda ws, nb: lib.mmg_lab_stats(p, p, 10, 4, 2, p, ws, nb, None), True),
+        ("lab_quantiles", lib.mmg_lab_quantiles_ws_bytes(2),
+         lambda ws, nb: lib.mmg_lab_quantiles(p, p, 10, 4, 2, p, ws, nb, None), True),
+        ("lab_aggregate", lib.mmg_lab_aggregate_ws_bytes(10),
+         lambda ws, nb: lib.mmg_lab_aggregate(p, p, 10, 4, 2, 0, 0, 5.0, None, p, p, p, ctypes.byref(cnt), ws, nb, None),
+         True),
+        ("pair_analysis", lib.mmg_pair_analysis_ws_bytes(8, 10, 2),
+         lambda ws, nb: lib.mmg_pair_analysis(p, p, p, p, 4, 8, 10, p, 4, edges, 2, p, p, ws, nb, None), True),
+        ("pair_calibrated_abs", lib.mmg_pair_calibrated_abs_ws_bytes(8, 10, 2),
+         lambda ws, nb: lib.mmg_pair_calibrated_abs(p, p, p, p, 4, 8, 10, p, p, p, 4, edges, 2, p, p, p, ws, nb, None),
+         True),
+    ]
+    for name, need, call, null_too in table:
+        assert need > 0, name
+        for ws, nb in [(p, need - 1)] + ([(None, need)] if null_too else []):
+            rc = call(ws, nb)
+            msg = lib.mmg_last_error()
+            assert rc == -3 and name.encode() in msg and b"workspace" in msg, (name, ws, rc, msg)
+
+
 def test_cpu_model_fails_loudly():
     import mmgnn  # noqa: F401
     from mmgnn.model import build_model
