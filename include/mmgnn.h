@@ -847,6 +847,36 @@ int mmg_pair_calibrated_abs(const float* pred, const float* target, const void* 
                             int64_t n_patients, const double* bin_edges, int n_bins, const double* bin_mean,
                             double* lab_abs, double* bin_sq, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Feature-space selection (src/io_mimic.py filter_labs_for_cohort, src/preprocess.py process_diagnoses /
+ * process_medications; mmgnn/preprocess.py, csrc/select.hip): which codes become nodes and which event rows stay.
+ * Events are device arrays over n rows: code and patient as int64 (code order = key order; a code outside
+ * [0, n_codes) means the row is ignored, a patient outside [0, n_patients) means "not in the cohort" and the row is
+ * ignored; neither is ever used as an address), valid uint8 (nullable; 0 = the row is ignored -- for labs
+ * VALUENUM.notna()).  The remaining rows are the COUNTED rows.
+ *   n_patients_per_code [n_codes] int64: distinct patients among the counted rows (NUM_PATIENTS; value_counts of the
+ *     de-duplicated pairs);  n_rows_per_code [n_codes] int64: counted rows (NUM_MEASUREMENTS);
+ *   rank [n_codes] int32: the position of the code among the ELIGIBLE codes (at least one row and at least
+ *     min_patient_count patients) in (patients descending, code ascending) order, -1 for a code that is not eligible;
+ *   selected [n_codes] uint8: rank >= 0 && (top_k < 0 || rank < top_k) -- a negative top_k means no cut, a tie at the
+ *     cut goes to the smaller code;
+ *   out_rows [<= n] int32: the kept rows in ASCENDING order -- MMG_SEL_ROWS_ALL: every counted row of a selected code;
+ *     MMG_SEL_ROWS_FIRST: of each (patient, code) pair of a selected code the row with the smallest index;
+ *   *n_out (HOST): their number -- this call waits for the stream (as mmg_lab_aggregate does: the count sizes the
+ *     caller's view of out_rows), so it cannot be captured.
+ * Limits: 0 <= n < 2^31 (n = 0 is valid), 1 <= n_patients < 2^31, 1 <= n_codes < 2^31 -- NOT capped at
+ * MMG_PREP_MAX_LABS: a raw vocabulary is cut down to that by this call -- and n_codes * n_patients + 1 < 2^63.  Every
+ * argument is checked on the host before anything is enqueued (MMG_E_ARG; a short workspace MMG_E_WS).  Integer work,
+ * no atomics on the data path, no memset node: every output is exact and bitwise reproducible.
+ * ------------------------------------------------------------------------------------- */
+#define MMG_SEL_ROWS_ALL 0
+#define MMG_SEL_ROWS_FIRST 1
+size_t mmg_code_select_ws_bytes(int64_t n, int64_t n_codes);
+int mmg_code_select(const int64_t* code, const int64_t* patient, const uint8_t* valid, int64_t n, int64_t n_patients,
+                    int64_t n_codes, int64_t min_patient_count, int64_t top_k, int rows_mode,
+                    int64_t* n_patients_per_code, int64_t* n_rows_per_code, int32_t* rank, uint8_t* selected,
+                    int32_t* out_rows, int64_t* n_out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

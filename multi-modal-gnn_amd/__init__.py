@@ -17,7 +17,8 @@ def __getattr__(name):
         from . import data
         return getattr(data, name)
     if name in ("preprocess_lab_events", "aggregate_lab_values", "normalize_lab_values", "remove_outliers",
-                "LabNormalizer"):
+                "LabNormalizer", "select_codes", "filter_labs_for_cohort", "process_diagnoses", "process_medications",
+                "normalize_drug_name", "preprocess_frames"):
         from . import preprocess
         return getattr(preprocess, name)
     if name in ("run_analysis", "create_per_lab_calibration_table", "create_error_vs_degree_table",

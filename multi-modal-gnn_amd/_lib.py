@@ -216,6 +216,9 @@ SIGNATURES = {
     "mmg_pair_calibrated_abs_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "mmg_pair_calibrated_abs": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _i64, _P(C.c_double), _i32,
                                           _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mmg_code_select_ws_bytes": (_sz, [_i64, _i64]),
+    "mmg_code_select": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
+                                  _P(C.c_int64), _vp, _sz, _vp]),
 }
 
 _lib = None

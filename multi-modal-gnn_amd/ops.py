@@ -1521,8 +1521,47 @@ def lab_inverse_matrix(pred: torch.Tensor, stats: torch.Tensor, method: str, out
     return out
 
 
+# ------------------------------------------------------------------------------------------ feature-space selection
+SEL_ROWS = {"all": 0, "first": 1}          # MMG_SEL_ROWS_ALL / MMG_SEL_ROWS_FIRST
+
+
+def code_select(code: torch.Tensor, patient: torch.Tensor, n_patients: int, n_codes: int, min_patient_count: int,
+                top_k: Optional[int] = None, rows: str = "all", valid: Optional[torch.Tensor] = None):
+    """Per-code patient and row counts, the rank of the eligible codes, the selected codes and the kept rows
+    (mmg_code_select).  code, patient: int64 device tensors over the rows (out of range = the row is ignored); valid:
+    uint8 / bool or None.  -> (n_patients_per_code int64 [n_codes], n_rows_per_code int64 [n_codes], rank int32
+    [n_codes], selected uint8 [n_codes], out_rows int32, ascending).  Waits for the stream: the row count comes back."""
+    lib = _lib.load()
+    n = code.numel()
+    if rows not in SEL_ROWS:
+        raise ValueError(f'code_select: rows must be "all" or "first", got {rows!r}')
+    if not (0 <= n < 2 ** 31 - 1 and 1 <= n_patients < 2 ** 31 - 1 and 1 <= n_codes < 2 ** 31 - 1):
+        raise ValueError(f"code_select: n {n}, n_patients {n_patients}, n_codes {n_codes} outside [0, 2^31) / [1, 2^31) / "
+                         f"[1, 2^31)")
+    if patient.numel() != n or (valid is not None and valid.numel() != n):
+        raise ValueError("code_select: every column needs one entry per row")
+    _p(code, torch.int64, "code")                             # host tensors are refused before anything is allocated
+    if valid is not None and valid.dtype == torch.bool:
+        valid = valid.view(torch.uint8)
+    dev = code.device
+    n_pat = torch.empty(n_codes, dtype=torch.int64, device=dev)
+    n_rows = torch.empty(n_codes, dtype=torch.int64, device=dev)
+    rank = torch.empty(n_codes, dtype=torch.int32, device=dev)
+    selected = torch.empty(n_codes, dtype=torch.uint8, device=dev)
+    out_rows = torch.empty(n, dtype=torch.int32, device=dev)
+    cnt = C.c_int64(0)
+    ws = workspace(lib.mmg_code_select_ws_bytes(n, int(n_codes)), dev)
+    check(lib.mmg_code_select(_p(code, torch.int64, "code"), _p(patient, torch.int64, "patient"),
+                              _p(valid, torch.uint8, "valid"), n, int(n_patients), int(n_codes), int(min_patient_count),
+                              -1 if top_k is None else int(top_k), SEL_ROWS[rows], _p(n_pat, torch.int64),
+                              _p(n_rows, torch.int64), _p(rank, torch.int32), _p(selected, torch.uint8),
+                              _p(out_rows, torch.int32), C.byref(cnt), _p(ws, torch.uint8), ws.numel(), _stream()),
+          "mmg_code_select")
+    return n_pat, n_rows, rank, selected, out_rows[:int(cnt.value)]
+
+
 # ------------------------------------------------------------------------------------------ prediction analysis
-AN_MAX_LABS = 2048           # the lab limit of csrc/analysis.hip (and of csrc/evalred.hip)
+AN_MAX_LABS = 2048          # the lab limit of csrc/analysis.hip (and of csrc/evalred.hip)
 AN_MAX_BINS = 64             # MMG_AN_MAX_BINS
 AN_LAB_FIELDS = 9            # MMG_AN_LAB_FIELDS: n, sum t, sum p, sum t^2, sum t p, sum |p - t|, sum (p - t)^2, min t, max t
 AN_BIN_FIELDS = 2            # MMG_AN_BIN_FIELDS: n, sum |p - t|

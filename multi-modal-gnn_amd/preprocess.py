@@ -11,10 +11,26 @@ cases.  The arithmetic runs in the kernels of ``csrc/prep.hip`` (fp64 throughout
 * ``remove_outliers`` and ``LabNormalizer``  on a pandas Series, a numpy array or a device tensor (the same kind comes
   back).  Beyond the reference the normaliser offers ``to_lab_stats()`` (the ``ITEMID, mean, std`` frame
   ``inference.lab_report`` reads) and ``inverse_transform_matrix`` (a whole ``impute_lab_matrix`` result).
+
+Feature-space selection -- which labs, diagnoses and drugs become nodes (``src/io_mimic.py`` filter_labs_for_cohort,
+``src/preprocess.py`` process_diagnoses / process_medications / the frame part of preprocess_pipeline).  The counting,
+ranking and row selection run in ``csrc/select.hip``:
+
+* ``select_codes``  the tensor-level entry over device tensors of event codes.
+* ``filter_labs_for_cohort`` / ``process_diagnoses`` / ``process_medications`` / ``normalize_drug_name``  the
+  reference's frame functions.  String work (strip, 3-character collapse, the drug-name rules) runs on the host over
+  the UNIQUE values only; the row-sized arrays that go to the device are integer codes.
+* ``preprocess_frames``  raw frames -> the frames ``graph_build.build_heterogeneous_graph`` consumes.
+
+Ties.  The reference ranks labs with ``nlargest(keep="first")`` over a sorted index: among equal patient counts the
+smaller ITEMID wins, and so it does here.  It ranks diagnoses and drugs with ``value_counts().head(top_k)``, whose order
+among equal counts is whatever pandas' unstable sort yields; this module's rule is its own: among equal counts the
+smaller code (in sorted key order) wins.  The results differ from the reference's only for a tie exactly at the cut.
 """
 from __future__ import annotations
 
 import logging
+import re
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -323,3 +339,192 @@ def normalize_lab_values(labs_agg: pd.DataFrame, method: str = "zscore") -> Tupl
         pass                                                   # string ids (eICU lab names) stay
     logging.info(f"Normalized {len(out)} lab values")
     return out, normalizer
+
+
+# ============================================================================ feature-space selection
+def select_codes(patient: torch.Tensor, code: torch.Tensor, n_patients: int, n_codes: int, *,
+                 valid: Optional[torch.Tensor] = None, min_patient_count: int, top_k: Optional[int] = None,
+                 rows: str = "all"):
+    """Which codes become nodes and which event rows stay, all on the device.
+
+    patient, code: int64 codes over the event rows (code order = key order; a value outside [0, n_patients) /
+    [0, n_codes) drops the row); valid: uint8 / bool, 0 drops the row.  A code is eligible with at least one row and at
+    least min_patient_count distinct patients; the eligible codes are ranked by (patients descending, code ascending)
+    and the first top_k (None: all) are selected.  rows="all" keeps every counted row of a selected code, "first" the
+    first row of each (patient, code) pair.  n_codes is not limited to ops.PREP_MAX_LABS.
+    -> (n_patients_per_code int64, n_rows_per_code int64, rank int32 (-1: not eligible), selected uint8, out_rows int32
+    ascending)."""
+    return _ops().code_select(code, patient, n_patients, n_codes, min_patient_count, top_k, rows, valid)
+
+
+def _member_codes(col: pd.Series, members) -> Tuple[np.ndarray, np.ndarray]:
+    """(position of every value among the sorted unique members, -1 outside; the sorted unique members)."""
+    keys = np.unique(np.asarray(pd.Series(members).dropna()))
+    v = col.to_numpy()
+    if len(keys) == 0 or len(v) == 0:
+        return np.full(len(v), -1, np.int64), keys
+    try:
+        pos = np.searchsorted(keys, v)
+        pos_c = np.minimum(pos, len(keys) - 1)
+        return np.where(keys[pos_c] == v, pos_c, -1).astype(np.int64), keys
+    except TypeError:                                         # ids that do not order against the members: a lookup
+        return pd.Index(keys).get_indexer(v).astype(np.int64), keys
+
+
+def _string_codes(col: pd.Series, rule) -> Tuple[np.ndarray, np.ndarray]:
+    """Row codes of rule(str(value).strip()) with sorted unique keys; '' (before or after the rule) gives -1.  The
+    strings are formed over the unique values only; a missing value becomes the text pandas' astype(str) gives it
+    ('nan', 'None'), as in the reference."""
+    c0, u0 = pd.factorize(col)                                # missing -> -1
+    texts = pd.Series(u0).astype(str).tolist() if len(u0) else []
+    miss = c0 < 0
+    if miss.any():
+        cm, um = pd.factorize(col[miss].astype(str))
+        c0 = c0.copy()
+        c0[miss] = len(texts) + cm
+        texts += list(um)
+    mapped = []
+    for t in texts:
+        t = t.strip()
+        mapped.append(rule(t) if t != "" else "")
+    keys = np.array(sorted(set(mapped) - {""}), dtype=object)            # code order = sorted key order
+    at = {k: i for i, k in enumerate(keys)}
+    of_unique = np.array([at.get(t, -1) for t in mapped], dtype=np.int64)
+    return (of_unique[c0] if len(c0) else np.empty(0, np.int64)), keys
+
+
+def _run_selection(pcode, ccode, valid, n_patients, n_codes, min_patient_count, top_k, rows):
+    if top_k is not None and top_k < 0:                       # head(-k) / nlargest(-k) are not a selection rule
+        raise ValueError(f"top_k must be None or >= 0, got {top_k}")
+    dev = _device()
+    out = select_codes(torch.from_numpy(np.ascontiguousarray(pcode)).to(dev),
+                       torch.from_numpy(np.ascontiguousarray(ccode)).to(dev), max(int(n_patients), 1),
+                       max(int(n_codes), 1),
+                       valid=None if valid is None else torch.from_numpy(np.ascontiguousarray(valid, dtype=np.uint8)).to(dev),
+                       min_patient_count=int(min_patient_count), top_k=top_k, rows=rows)
+    return [t.cpu().numpy() for t in out]
+
+
+def filter_labs_for_cohort(labevents: pd.DataFrame, cohort: pd.DataFrame, d_labitems: pd.DataFrame,
+                           top_k: Optional[int] = None, min_patient_count: int = 10) -> Tuple[pd.DataFrame, pd.DataFrame]:
+    """io_mimic.py:442-516: the events of the cohort's patients with a numeric VALUENUM, restricted to the labs that at
+    least min_patient_count patients have and, of those, the top_k by NUM_PATIENTS (a tie at the cut goes to the
+    smaller ITEMID, integer or string).  -> (labs: the surviving rows in input order with their index,
+    selected_labitems: d_labitems' rows of the selected ids with NUM_PATIENTS and NUM_MEASUREMENTS merged on)."""
+    logging.info("Filtering lab events for cohort...")
+    pcode, cohort_ids = _member_codes(labevents["SUBJECT_ID"], cohort["SUBJECT_ID"])
+    lcode, lab_keys = _factorize_sorted(labevents["ITEMID"])
+    valid = labevents["VALUENUM"].notna().to_numpy()
+    n_pat, n_rows, rank, selected, rows = _run_selection(pcode, lcode, valid, len(cohort_ids), len(lab_keys),
+                                                        min_patient_count, top_k, "all")
+    sel = np.flatnonzero(selected[:len(lab_keys)])
+    if top_k is not None:
+        sel = sel[np.argsort(rank[sel], kind="stable")]       # nlargest's order; without a cut the groupby's key order
+    lab_counts = pd.DataFrame({"NUM_PATIENTS": n_pat[sel], "NUM_MEASUREMENTS": n_rows[sel]},
+                              index=pd.Index(lab_keys[sel], name="ITEMID"))
+    logging.info(f"Selected {len(lab_counts)} lab tests")
+    labs = labevents.iloc[rows]
+    logging.info(f"Final lab events: {len(labs)}")
+    selected_labitems = d_labitems[d_labitems["ITEMID"].isin(set(lab_counts.index))].copy()
+    selected_labitems = selected_labitems.merge(lab_counts, left_on="ITEMID", right_index=True)
+    return labs, selected_labitems
+
+
+def _select_pairs(frame: pd.DataFrame, cohort: pd.DataFrame, source_col: str, rule, min_patient_count, top_k):
+    """The shared part of process_diagnoses / process_medications -> (kept row positions, their code strings, the
+    selected keys by rank with their patient counts)."""
+    pcode, cohort_ids = _member_codes(frame["SUBJECT_ID"], cohort["SUBJECT_ID"])
+    in_adm = frame["HADM_ID"].isin(set(cohort["HADM_ID"])).to_numpy()
+    ccode, keys = _string_codes(frame[source_col], rule)
+    n_pat, _, rank, selected, rows = _run_selection(pcode, ccode, in_adm, len(cohort_ids), len(keys),
+                                                    min_patient_count, top_k, "first")
+    sel = np.flatnonzero(selected[:len(keys)])
+    sel = sel[np.argsort(rank[sel], kind="stable")]
+    counts = pd.Series(n_pat[sel], index=pd.Index(keys[sel], dtype=object), name="count")
+    return rows, (keys[ccode[rows]] if len(rows) else np.empty(0, object)), counts
+
+
+def process_diagnoses(diagnoses: pd.DataFrame, cohort: pd.DataFrame, collapse_to_3digit: bool = True,
+                      top_k: Optional[int] = None, min_patient_count: int = 5) -> pd.DataFrame:
+    """preprocess.py:171-266.  A row counts if its HADM_ID is one of the cohort's AND its SUBJECT_ID is; the code is
+    str(ICD9_CODE).strip() ('' dropped; a missing code is the code 'nan' / 'None', as in the reference), cut to its first
+    three characters with collapse_to_3digit.  Kept: the diagnoses of at least min_patient_count patients, the top_k
+    most frequent of them -- among equal counts the smaller code (sorted key order) wins, this project's own rule where
+    the reference's value_counts() leaves the order of ties to an unstable sort.
+    -> the first row of each (patient, code) pair of a kept code, in input order with the original index: SUBJECT_ID,
+    ICD3_CODE (collapsed) or ICD9_CODE (not collapsed; then there is no ICD3_CODE column), and DIAGNOSIS_CATEGORY /
+    DIAGNOSIS_SUBCATEGORY / DIAGNOSIS_PRIORITY of that first row when present."""
+    logging.info("Processing diagnosis codes...")
+    col = "ICD3_CODE" if collapse_to_3digit else "ICD9_CODE"
+    rule = (lambda t: t[:3]) if collapse_to_3digit else (lambda t: t)
+    rows, codes, counts = _select_pairs(diagnoses, cohort, "ICD9_CODE", rule, min_patient_count, top_k)
+    logging.info(f"Selected {len(counts)} diagnoses")
+    kept = diagnoses.iloc[rows]
+    out = pd.DataFrame({"SUBJECT_ID": kept["SUBJECT_ID"], col: pd.Series(codes, index=kept.index, dtype=object)})
+    for extra in ("DIAGNOSIS_CATEGORY", "DIAGNOSIS_SUBCATEGORY", "DIAGNOSIS_PRIORITY"):
+        if extra in diagnoses.columns:
+            out[extra] = kept[extra]
+    logging.info(f"Final: {len(out)} patient-diagnosis pairs")
+    return out
+
+
+_DOSAGE = re.compile(r"\d+\.?\d*\s*(mg|mcg|ml|g|%|units?)")
+_FORM_WORDS = re.compile(r"\b(tablet|capsule|injection|solution|suspension|syrup|cream|ointment)\b")
+_ROUTE_WORDS = re.compile(r"\b(oral|topical|iv|intravenous|subcutaneous)\b")
+_PUNCTUATION = re.compile(r"[^\w\s]")
+
+
+def normalize_drug_name(drug) -> str:
+    """preprocess.py:273-312: lower case, dosage patterns ("50mg", "10 ml", "5 %", "3 units"), form words and route
+    words removed, punctuation to spaces, the first remaining word ("" for a missing name; a name with no word left
+    comes back as what is left, the empty string)."""
+    if pd.isna(drug):
+        return ""
+    text = str(drug).lower()
+    for pattern in (_DOSAGE, _FORM_WORDS, _ROUTE_WORDS):
+        text = pattern.sub("", text)
+    words = _PUNCTUATION.sub(" ", text).split()
+    return words[0] if words else ""
+
+
+def process_medications(prescriptions: pd.DataFrame, cohort: pd.DataFrame, normalize_names: bool = True,
+                        top_k: Optional[int] = None, min_patient_count: int = 5) -> pd.DataFrame:
+    """preprocess.py:315-412.  The cohort rule of process_diagnoses; the name is str(DRUG).strip() ('' dropped), with
+    normalize_names passed through normalize_drug_name (empty results dropped).  Kept: the drugs of at least
+    min_patient_count patients, the top_k most frequent of them, among equal counts the smaller name (sorted key order)
+    -- this project's own rule, see process_diagnoses.
+    -> the first row of each (patient, drug) pair of a kept drug, in input order with the original index: SUBJECT_ID,
+    DRUG, and ROUTE / FREQUENCY / PRN / IV_ADMIXTURE of that first row when present."""
+    logging.info("Processing medications...")
+    rule = normalize_drug_name if normalize_names else (lambda t: t)
+    rows, names, counts = _select_pairs(prescriptions, cohort, "DRUG", rule, min_patient_count, top_k)
+    logging.info(f"Selected {len(counts)} medications")
+    kept = prescriptions.iloc[rows]
+    out = pd.DataFrame({"SUBJECT_ID": kept["SUBJECT_ID"], "DRUG": pd.Series(names, index=kept.index, dtype=object)})
+    for extra in ("ROUTE", "FREQUENCY", "PRN", "IV_ADMIXTURE"):
+        if extra in prescriptions.columns:
+            out[extra] = kept[extra]
+    logging.info(f"Final: {len(out)} patient-medication pairs")
+    return out
+
+
+def preprocess_frames(labevents: pd.DataFrame, d_labitems: pd.DataFrame, diagnoses: pd.DataFrame,
+                      prescriptions: pd.DataFrame, cohort: pd.DataFrame, config: Dict) -> Dict:
+    """The frame part of preprocess_pipeline (preprocess.py:553-673), from raw frames to what
+    graph_build.build_heterogeneous_graph consumes; the arguments come from config["feature_space"] as the reference
+    reads them.  -> {"labitems", "labs" (normalised), "lab_normalizer", "diagnoses", "medications"}.  The loaders, the
+    parquet files, the demographic features and the APACHE scores are not part of it."""
+    fs = config["feature_space"]
+    labs_filtered, selected_labitems = filter_labs_for_cohort(
+        labevents, cohort, d_labitems, top_k=fs["labs"]["top_k"], min_patient_count=fs["labs"].get("min_patient_count", 10))
+    labs_agg = aggregate_lab_values(labs_filtered, cohort, method=fs["labs"]["aggregate"],
+                                    remove_outliers_flag=fs["labs"].get("outlier_std_threshold") is not None,
+                                    outlier_threshold=fs["labs"].get("outlier_std_threshold", 5.0))
+    labs_normalized, normalizer = normalize_lab_values(labs_agg, method=fs["labs"]["normalize"])
+    dx = process_diagnoses(diagnoses, cohort, collapse_to_3digit=fs["diagnoses"]["collapse_to_3digit"],
+                           top_k=fs["diagnoses"]["top_k"], min_patient_count=fs["diagnoses"].get("min_patient_count", 5))
+    meds = process_medications(prescriptions, cohort, normalize_names=fs["medications"]["normalize_names"],
+                               top_k=fs["medications"]["top_k"],
+                               min_patient_count=fs["medications"].get("min_patient_count", 5))
+    return {"labitems": selected_labitems, "labs": labs_normalized, "lab_normalizer": normalizer, "diagnoses": dx,
+            "medications": meds}

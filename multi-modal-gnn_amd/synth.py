@@ -169,3 +169,58 @@ def lab_event_frames(ev: Dict, string_itemid: bool = False):
                          "VALUENUM": ev["value"].cpu().numpy(),
                          "CHARTTIME": np.where(miss, np.nan, t.astype(np.float64))})
     return labs, pd.DataFrame({"SUBJECT_ID": np.arange(ev["n_patients"], dtype=np.int64)})
+
+
+CODE_KINDS = {"diagnosis": ("has_diagnosis", "diagnosis"), "medication": ("has_medication", "medication")}
+
+
+def make_code_events(scale: int = 1, seed: int = 0, device="cpu", kind: str = "diagnosis", tail_codes: int = 2048,
+                     events_per_pair: float = 2.5) -> Dict:
+    """The raw diagnosis / prescription rows behind make_graph(scale, seed)'s has_diagnosis / has_medication edges.
+
+    Every edge (patient, code) gets 1 + Poisson(events_per_pair - 1) rows.  Beyond the graph's vocabulary lie
+    tail_codes rare codes (codes n_vocab .. n_codes - 1) with 1..3 patients each -- the long tail a raw ICD-9 or drug
+    vocabulary has, which a min_patient_count of 5 removes again.  A few patients outside the cohort (ids >=
+    n_patients) get rows too, and the rows are shuffled.
+    -> dict(patient, code: int64 tensors over the rows; n_patients, n_vocab, n_codes; edge_index: the graph's edges).
+    Patient and code ids are their codes."""
+    if kind not in CODE_KINDS:
+        raise ValueError(f'kind must be "diagnosis" or "medication", got {kind!r}')
+    device = torch.device(device)
+    g = make_graph(scale, seed, device)
+    rel, node = CODE_KINDS[kind]
+    ei = g["patient", rel, node].edge_index
+    P, V, E = int(g["patient"].num_nodes), int(g[node].num_nodes), int(ei.shape[1])
+    gen = torch.Generator(device=device).manual_seed(seed + (104729 if kind == "diagnosis" else 130003))
+    cnt = 1 + torch.poisson(torch.full((E,), float(events_per_pair) - 1.0, device=device), generator=gen).long()
+    pair = torch.repeat_interleave(torch.arange(E, device=device), cnt)
+    n_tail_pat = torch.randint(1, 4, (tail_codes,), generator=gen, device=device)
+    tail_code = V + torch.repeat_interleave(torch.arange(tail_codes, device=device), n_tail_pat)
+    tail_patient = torch.randint(0, P, (tail_code.numel(),), generator=gen, device=device)
+    n_out_pat = max(3, P // 600)
+    n_out = 20 * n_out_pat
+    patient = torch.cat([ei[0][pair], tail_patient, P + torch.randint(0, n_out_pat, (n_out,), generator=gen, device=device)])
+    code = torch.cat([ei[1][pair], tail_code, torch.randint(0, V, (n_out,), generator=gen, device=device)])
+    order = torch.randperm(patient.numel(), generator=gen, device=device)
+    return {"patient": patient[order].contiguous(), "code": code[order].contiguous(), "n_patients": P, "n_vocab": V,
+            "n_codes": V + tail_codes, "edge_index": ei}
+
+
+def code_event_frames(ev: Dict, kind: str = "diagnosis"):
+    """(rows, cohort) frames of make_code_events' result, as the reference's process_diagnoses / process_medications
+    take them: SUBJECT_ID, HADM_ID (SUBJECT_ID + 100000: one admission per patient) and ICD9_CODE ("%03d" of the code
+    modulo 1000 followed by the thousands, so that a tail code collapses onto a 3-character code of the vocabulary) or
+    DRUG ("drug%04d 10 mg tablet").  The cohort lists every patient below n_patients."""
+    import numpy as np
+    import pandas as pd
+    if kind not in CODE_KINDS:
+        raise ValueError(f'kind must be "diagnosis" or "medication", got {kind!r}')
+    code = ev["code"].cpu().numpy()
+    sid = ev["patient"].cpu().numpy()
+    if kind == "diagnosis":
+        names = np.array([f"{c % 1000:03d}{c // 1000}" for c in range(ev["n_codes"])], dtype=object)
+    else:
+        names = np.array([f"Drug{c:04d} 10 mg Tablet" for c in range(ev["n_codes"])], dtype=object)
+    rows = pd.DataFrame({"SUBJECT_ID": sid, "HADM_ID": sid + 100000, "ICD9_CODE" if kind == "diagnosis" else "DRUG": names[code]})
+    ids = np.arange(ev["n_patients"], dtype=np.int64)
+    return rows, pd.DataFrame({"SUBJECT_ID": ids, "HADM_ID": ids + 100000})
