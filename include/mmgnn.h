@@ -877,6 +877,39 @@ int mmg_code_select(const int64_t* code, const int64_t* patient, const uint8_t* 
                     int64_t* n_patients_per_code, int64_t* n_rows_per_code, int32_t* rank, uint8_t* selected,
                     int32_t* out_rows, int64_t* n_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Embedding maps (src/advanced_visualizations.py create_embedding_visualizations, src/visualize.py plot_embeddings_umap
+ * with visualization.dim_reduction = "pca"; mmgnn/embed.py, csrc/pca.hip): the arithmetic over all rows of a PCA of
+ * fp32 node embeddings and of the density grid of the projected patients.  X is fp32 [n, D] with row stride
+ * ld_x >= D (elements); D is a multiple of 4 in [4, 256].
+ *   mmg_centered_gram: mean_out (device, fp64 [D]) = the column means (fp64 sums, divided by n once); gram_out (device,
+ *     fp64 [D * D]) = S = sum_i (x_i - mean)(x_i - mean)^T, centred in fp64 from the fp32 input (two passes over X, never
+ *     X^T X - n mean mean^T), products and sums in fp64 (v_mfma_f64_16x16x4_f64).  One triangle is computed and
+ *     mirrored: S is exactly symmetric.  2 <= n < 2^31.  Workgroups leave partial slabs in ws, summed in a fixed order.
+ *   mmg_project_rows: out[i * ld_out + c] = scale[c] * sum_d (x_id - mean[d]) * comps[c * D + d] for c < k, the sum in
+ *     fp64, rounded once to fp32; scale NULL = 1.  mean, comps, scale are DEVICE arrays (fp64 [D], [k * D], [k]).
+ *     1 <= k <= 8, ld_out >= k, 1 <= n < 2^31.  One read of X.
+ *   mmg_grid2d: numpy.histogram2d of the points (Y[i * ld_y], Y[i * ld_y + 1]) over explicit edges ex (DEVICE, fp64
+ *     [gx + 1]) and ey ([gy + 1]), ascending: bins are half open, the last edge is inclusive, a point outside the edges
+ *     or with a NaN coordinate is counted nowhere; the fp32 coordinate is widened exactly and compared with the edges.
+ *     count[bx * gy + by] (device, int64 [gx * gy]) = the points of the cell, wsum = the sum of w[i] (int32, nullable;
+ *     wsum may then be null) over them.  Both are zeroed by a kernel first.  1 <= gx, gy <= 256, 0 <= n < 2^31.
+ *     Integer atomics only: the result does not depend on their order.
+ * Every argument is checked on the host before anything is enqueued (MMG_E_ARG; mmg_centered_gram's workspace
+ * MMG_E_WS); mmg_project_rows and mmg_grid2d need no workspace today (their *_ws_bytes is 0 and ws may be NULL).  No call
+ * synchronises with the host, allocates, uses a memset node or a floating-point atomic; the order of every fp64 sum is
+ * fixed by n and D: bitwise reproducible from run to run and eager against a replayed hipGraph.
+ * ------------------------------------------------------------------------------------- */
+size_t mmg_centered_gram_ws_bytes(int64_t n, int D);          /* 0 for an unsupported shape */
+int mmg_centered_gram(const float* X, int64_t n, int D, int64_t ld_x, double* mean_out, double* gram_out, void* ws,
+                      size_t ws_bytes, void* stream);
+size_t mmg_project_rows_ws_bytes(int64_t n, int D, int k);
+int mmg_project_rows(const float* X, int64_t n, int D, int64_t ld_x, const double* mean, const double* comps,
+                     const double* scale, int k, float* out, int64_t ld_out, void* ws, size_t ws_bytes, void* stream);
+size_t mmg_grid2d_ws_bytes(int64_t n, int gx, int gy);
+int mmg_grid2d(const float* Y, int64_t ld_y, const int32_t* w, int64_t n, const double* ex, const double* ey, int gx,
+               int gy, int64_t* count, int64_t* wsum, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,4 +25,7 @@ def __getattr__(name):
                 "parity_by_frequency_decile"):
         from . import analysis
         return getattr(analysis, name)
+    if name in ("embedding_maps", "lab_panels", "PCAResult"):
+        from . import embed
+        return getattr(embed, name)
     raise AttributeError(name)

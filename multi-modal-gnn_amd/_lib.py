@@ -219,6 +219,12 @@ SIGNATURES = {
     "mmg_code_select_ws_bytes": (_sz, [_i64, _i64]),
     "mmg_code_select": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
                                   _P(C.c_int64), _vp, _sz, _vp]),
+    "mmg_centered_gram_ws_bytes": (_sz, [_i64, _i32]),
+    "mmg_centered_gram": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "mmg_project_rows_ws_bytes": (_sz, [_i64, _i32, _i32]),
+    "mmg_project_rows": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _sz, _vp]),
+    "mmg_grid2d_ws_bytes": (_sz, [_i64, _i32, _i32]),
+    "mmg_grid2d": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1639,3 +1639,75 @@ def pair_calibrated_abs(pred: Optional[torch.Tensor], target: torch.Tensor, lab:
                                       _p(lab_abs, torch.float64), _p(bin_sq, torch.float64), _p(ws, torch.uint8), ws.numel(),
                                       _stream()), "mmg_pair_calibrated_abs")
     return lab_abs, bin_sq
+
+
+# ------------------------------------------------------------------------------------------ embedding maps
+PCA_MAX_D = 256              # the widest X of csrc/pca.hip; D is a multiple of 4 in [4, PCA_MAX_D]
+PCA_MAX_K = 8                # components per mmg_project_rows call
+GRID_MAX = 256               # cells per axis of mmg_grid2d
+
+
+def _rows_matrix(x: torch.Tensor, name: str):
+    """fp32 device [n, D] with unit column stride -> (pointer, n, D, row stride in elements)."""
+    if x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise ValueError(f"{name}: expected a 2-D tensor with unit column stride")
+    if not x.is_cuda:
+        raise _lib.MmgError(f"{name}: expected a HIP device tensor, got {x.device} (no CPU fallback)")
+    if x.dtype != torch.float32:
+        raise TypeError(f"{name}: expected torch.float32, got {x.dtype}")
+    n, D = int(x.shape[0]), int(x.shape[1])
+    ld = int(x.stride(0)) if n > 1 else max(int(x.stride(0)), D)
+    return C.c_void_p(x.data_ptr()), n, D, ld
+
+
+def centered_gram(x: torch.Tensor):
+    """Column means and the centred Gram matrix of fp32 [n, D] rows (mmg_centered_gram) -> (mean fp64 [D], S fp64
+    [D, D] = sum_i (x_i - mean)(x_i - mean)^T, exactly symmetric), on the device.  Fixed-order fp64 sums: bitwise
+    reproducible; nothing synchronises with the host."""
+    lib = _lib.load()
+    px, n, D, ld = _rows_matrix(x, "x")
+    mean = torch.empty(D, dtype=torch.float64, device=x.device)
+    gram = torch.empty(D, D, dtype=torch.float64, device=x.device)
+    ws = workspace(lib.mmg_centered_gram_ws_bytes(n, D), x.device)
+    check(lib.mmg_centered_gram(px, n, D, ld, _p(mean, torch.float64), _p(gram, torch.float64), _p(ws, torch.uint8),
+                                ws.numel(), _stream()), "mmg_centered_gram")
+    return mean, gram
+
+
+def project_rows(x: torch.Tensor, mean: torch.Tensor, comps: torch.Tensor, scale: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None):
+    """out[i, c] = scale[c] * sum_d (x[i, d] - mean[d]) * comps[c, d] (mmg_project_rows): fp64 sums rounded once to
+    fp32 [n, k].  mean fp64 [D], comps fp64 [k, D], scale fp64 [k] or None, all on the device."""
+    lib = _lib.load()
+    px, n, D, ld = _rows_matrix(x, "x")
+    if comps.dim() != 2 or comps.shape[1] != D or mean.numel() != D:
+        raise ValueError(f"project_rows: comps must be [k, {D}] and mean [{D}]")
+    k = int(comps.shape[0])
+    if scale is not None and scale.numel() != k:
+        raise ValueError(f"project_rows: scale needs one entry per component ({k})")
+    if out is None:
+        out = torch.empty(n, k, dtype=torch.float32, device=x.device)
+    elif out.shape != (n, k):
+        raise ValueError(f"project_rows: out must be [{n}, {k}]")
+    check(lib.mmg_project_rows(px, n, D, ld, _p(mean, torch.float64, "mean"), _p(comps, torch.float64, "comps"),
+                               _p(scale, torch.float64, "scale"), k, _p(out, torch.float32, "out"), k, None, 0,
+                               _stream()), "mmg_project_rows")
+    return out
+
+
+def grid2d(y: torch.Tensor, ex: torch.Tensor, ey: torch.Tensor, w: Optional[torch.Tensor] = None):
+    """numpy.histogram2d of the fp32 points y [n, 2] over explicit fp64 device edges ex [gx + 1], ey [gy + 1]
+    (mmg_grid2d) -> (count int64 [gx, gy], wsum int64 [gx, gy] = the sum of the int32 weights w per cell, or None)."""
+    lib = _lib.load()
+    if y.dim() != 2 or y.shape[1] < 2:
+        raise ValueError("grid2d: y must be [n, >= 2]")
+    py, n, _, ld = _rows_matrix(y, "y")
+    gx, gy = int(ex.numel()) - 1, int(ey.numel()) - 1
+    if w is not None and w.numel() != n:
+        raise ValueError(f"grid2d: {w.numel()} weights for {n} points")
+    count = torch.empty(max(gx, 0), max(gy, 0), dtype=torch.int64, device=y.device)
+    wsum = torch.empty_like(count) if w is not None else None
+    check(lib.mmg_grid2d(py, max(ld, 2), _p(w, torch.int32, "w"), n, _p(ex, torch.float64, "ex"),
+                         _p(ey, torch.float64, "ey"), gx, gy, _p(count, torch.int64), _p(wsum, torch.int64), None, 0,
+                         _stream()), "mmg_grid2d")
+    return count, wsum
