@@ -7,9 +7,13 @@ BOUNDS (how each was obtained):
   ``sum_i |x_ia - mu_a| |x_ib - mu_b|`` (means: ``sum_i |x_ia| / n``), the largest entry taken.  Allowed: 8 x the distance
   of numpy-float64's own evaluation (``x64.mean(0)``, ``xc.T @ xc``) from that 80-bit evaluation on the same case -- the
   rule the lab-preprocessing sums use.  ``numpy_distances`` computes it on the CPU; ``GRAM_CASES`` records the values it
-  gave (numpy 2.x, OpenBLAS).  The column sums of these cases (fewer than 2^13 fp32 values of magnitude about 1 .. 16)
-  are exact in float64 in any order, so numpy's distance for the means is the one rounding of the division by n; the
-  (2, 4) case is exact throughout (distance 0: the code under test has to be exact there too).
+  gave (numpy 2.x, OpenBLAS).  The column sums of the cases of fewer than 2^13 rows (fp32 values of magnitude about
+  1 .. 16) are exact in float64 in any order, so numpy's distance for the means is the one rounding of the division by
+  n; the (2, 4) case is exact throughout (distance 0: the code under test has to be exact there too).  The bounds of a
+  case also hold with columns removed (the non-finite test): an element's sums do not involve the other columns.
+* Row projection through the C entry point (``project_ratio``) -- per element
+  ``|out - ref| <= 2^-24 |ref| + (D + 8) 2^-53 A`` against the 80-bit ``ref = scale_c sum_d (x_d - mean_d) comps_cd``
+  and ``A``, the same sum over absolute values: derived from the arithmetic, no eigenvector in it.
 * Projection -- per element ``|out - ref| <= 2^-23 max|ref column|``: one fp32 rounding of an fp64 sum (2^-24 of the
   element) plus as much again for the eigenvector perturbation.  Only valid when the leading eigenvalues are well
   separated: ``assert_gaps`` is asserted first by every test that uses it.
@@ -111,6 +115,17 @@ GRAM_CASES = {
     (1025, 128, 128): (BOUND_FACTOR * 7.487201743682543e-17, BOUND_FACTOR * 1.2464372745184453e-15),
     (4097, 256, 256): (BOUND_FACTOR * 7.360046588900792e-17, BOUND_FACTOR * 7.490078925395655e-16),
     (3000, 12, 20): (BOUND_FACTOR * 6.589083381949995e-17, BOUND_FACTOR * 7.869222631723643e-16),
+    # slabs above their minimum (pca_plan: gram_rows 96, 96, 192; mean_rows 274 in the third), ragged last slabs
+    (5000, 256, 256): (BOUND_FACTOR * 7.341794970981506e-17, BOUND_FACTOR * 7.44606677196515e-16),
+    (20000, 128, 136): (BOUND_FACTOR * 7.4058397435317e-17, BOUND_FACTOR * 7.212011390733962e-16),
+    (140001, 4, 4): (BOUND_FACTOR * 2.531308431770682e-16, BOUND_FACTOR * 8.036104990936348e-16),
+    # a ragged last 64-block next to full ones: 4, 16, 4 and 8 columns wide
+    (300, 68, 72): (BOUND_FACTOR * 7.360323444126413e-17, BOUND_FACTOR * 1.5311624184694199e-15),
+    (33, 80, 80): (BOUND_FACTOR * 8.066394607901991e-17, BOUND_FACTOR * 6.017432923919112e-16),
+    (65, 132, 132): (BOUND_FACTOR * 7.430496921308859e-17, BOUND_FACTOR * 7.238503995159488e-16),
+    (97, 200, 200): (BOUND_FACTOR * 7.566403741120352e-17, BOUND_FACTOR * 1.0750020027589124e-15),
+    # fewer rows than one MFMA step
+    (3, 64, 64): (BOUND_FACTOR * 5.856232510070688e-17, BOUND_FACTOR * 1.586770545167059e-16),
 }
 
 
@@ -122,10 +137,10 @@ def gram_case_x(n, D, ld):
     return buf[:, :D]
 
 
-@functools.lru_cache(maxsize=None)
-def gram80(n, D, ld):
-    """80-bit means and centred Gram of the case, and the two denominators -> dict (computed once per case)."""
-    x = np.asarray(gram_case_x(n, D, ld), np.longdouble)
+def gram80_of(x):
+    """80-bit means and centred Gram of the rows x, and the two denominators -> dict."""
+    x = np.asarray(x, np.longdouble)
+    n = x.shape[0]
     mean = x.sum(axis=0) / np.longdouble(n)
     xc = x - mean
     gram = xc.T @ xc
@@ -133,12 +148,21 @@ def gram80(n, D, ld):
     return {"mean": mean, "gram": gram, "mean_den": np.abs(x).sum(axis=0).astype(np.float64) / n, "gram_den": a.T @ a}
 
 
-def distances(mean, gram, n, D, ld):
+@functools.lru_cache(maxsize=None)
+def gram80(n, D, ld):
+    """gram80_of the case (computed once per case)."""
+    return gram80_of(gram_case_x(n, D, ld))
+
+
+def distances_from(mean, gram, ref):
     """(mean distance, Gram distance) of a float64 evaluation from the 80-bit one, in units of the denominators."""
-    ref = gram80(n, D, ld)
     dm = np.abs(np.asarray(mean, np.longdouble) - ref["mean"]).astype(np.float64) / ref["mean_den"]
     dg = np.abs(np.asarray(gram, np.longdouble) - ref["gram"]).astype(np.float64) / ref["gram_den"]
     return float(dm.max()), float(dg.max())
+
+
+def distances(mean, gram, n, D, ld):
+    return distances_from(mean, gram, gram80(n, D, ld))
 
 
 def numpy_distances(n, D, ld):
@@ -151,6 +175,47 @@ def numpy_distances(n, D, ld):
 
 def gram_bounds(n, D, ld):
     return GRAM_CASES[(n, D, ld)]
+
+
+# ---------------------------------------------------------------------------------------------- projection of the rows
+# (n, D, k) of the mmg_project_rows cases: n = 1, n not a multiple of 16, two passes of the grid loop with a ragged
+# second one (n > 65,536 = 4,096 workgroups x 16 rows), every k parity, the narrowest and the widest D
+PROJECT_CASES = [(1, 4, 1), (17, 12, 3), (50, 20, 5), (1000, 128, 7), (1000, 256, 8), (1000, 256, 1), (65537, 16, 8),
+                 (70001, 128, 2), (70001, 128, 3), (50, 4, 4)]
+
+
+@functools.lru_cache(maxsize=None)
+def project_case(n, D, k):
+    """One case of the row projection -> dict: fp32 rows x (magnitude about 1 .. 16), an fp64 mean near the data's, k
+    Gaussian (NOT orthonormal) components, a scale in [0.25, 4] with no power of two in it, and the 80-bit values
+    ``sum`` = sum_d (x_d - mean_d) comps_cd and ``abs`` = the same over absolute values, both [n, k] (computed once)."""
+    rng = np.random.default_rng(1000 * k + D + n)
+    x = make_case(n, D, seed=n + D + k)
+    mean = x.astype(np.float64).mean(axis=0) + 0.01 * rng.standard_normal(D)
+    comps = rng.standard_normal((k, D))
+    scale = rng.uniform(0.25, 4.0, k)
+    assert not np.any(np.frexp(scale)[0] == 0.5)
+    c80 = comps.astype(np.longdouble).T
+    s80 = np.empty((n, k), np.longdouble)
+    a80 = np.empty((n, k), np.longdouble)
+    for r in range(0, n, 8192):                                      # row chunks: the 80-bit copies stay small
+        xc = x[r:r + 8192].astype(np.longdouble) - mean.astype(np.longdouble)
+        s80[r:r + 8192] = xc @ c80
+        a80[r:r + 8192] = np.abs(xc) @ np.abs(c80)
+    for a in (x, mean, comps, scale, s80, a80):
+        a.setflags(write=False)
+    return {"x": x, "mean": mean, "comps": comps, "scale": scale, "sum": s80, "abs": a80}
+
+
+def project_ratio(out, case, D, scaled):
+    """The largest |out - ref| / (2^-24 |ref| + (D + 8) 2^-53 A) over the elements: ref = scale_c x sum, A = scale_c x
+    abs in 80 bits.  The first term is the one fp32 rounding of the result; the second covers the fp64 subtraction,
+    the D / 16 fmas of a lane, the four butterfly additions and the scale multiply (each at most 2^-53 of the partial
+    sum of absolute values, fewer than D + 8 of them in all)."""
+    sc = case["scale"].astype(np.longdouble) if scaled else np.longdouble(1.0)
+    ref, A = case["sum"] * sc, case["abs"] * sc
+    bound = np.longdouble(2.0 ** -24) * np.abs(ref) + np.longdouble((D + 8) * 2.0 ** -53) * A
+    return float((np.abs(np.asarray(out, np.longdouble) - ref) / bound).max())
 
 
 # ---------------------------------------------------------------------------------------------- grid, panels

@@ -63,12 +63,29 @@ def test_restatement_against_sklearn(n, k, sv, whiten):
 
 def test_gram_bounds_hold_for_the_host_arithmetic():
     """The recorded bounds are 8 x numpy's own distance from the 80-bit sums: numpy's evaluation on this machine has to
-    lie inside them (the small cases; the GPU tests use every case)."""
-    for n, D, ld in [(2, 4, 4), (50, 128, 128), (63, 64, 64), (3000, 12, 20)]:
+    lie inside them, on every case the GPU tests use (the 80-bit sums of the two largest take a few seconds each, once:
+    embed_ref.gram80 keeps them)."""
+    assert len(er.GRAM_CASES) == 14
+    for n, D, ld in er.GRAM_CASES:
         dm, dg = er.numpy_distances(n, D, ld)
         bm, bg = er.gram_bounds(n, D, ld)
         print((n, D, ld), dm, dg, bm, bg)
         assert dm <= bm and dg <= bg
+
+
+@pytest.mark.parametrize("n, D, k", [c for c in er.PROJECT_CASES if c[0] <= 1000])
+def test_projection_bound_holds_for_the_host_arithmetic(n, D, k):
+    """A float64 numpy evaluation rounded once to fp32 lies inside the derived bound of the row projection (its sums run
+    over D terms, the device's over D / 16 + 4): the bound asks nothing a correct evaluation cannot give."""
+    case = er.project_case(n, D, k)
+    xc = case["x"].astype(np.float64) - case["mean"]
+    for scaled in (False, True):
+        out = (xc @ case["comps"].T) * (case["scale"] if scaled else 1.0)
+        ratio = er.project_ratio(out.astype(np.float32), case, D, scaled)
+        print((n, D, k), scaled, ratio)
+        assert ratio <= 1.0
+    wrong = (xc @ case["comps"].T).astype(np.float32).astype(np.float64) * (1.0 + 2.0 ** -22)
+    assert er.project_ratio(wrong, case, D, False) > 1.0           # and it notices two fp32 ulps
 
 
 def test_lab_panels_on_the_reference_lab_names():

@@ -1,6 +1,9 @@
 """Embedding maps on the MI355X (csrc/pca.hip, mmgnn/embed.py): the centred Gram matrix and the means against an 80-bit
-evaluation, pca against the float64 restatement under embed_ref's BOUNDS, the 2-D histogram against numpy.histogram2d,
-bitwise reproducibility (eager and replayed hipGraph), the end-to-end maps and the C-level refusals."""
+evaluation (slabs at and above their minimum length, ragged last 64-blocks, non-finite input), the row projection
+through the C ABI against an 80-bit evaluation under a derived bound, pca against the float64 restatement under
+embed_ref's BOUNDS, the 2-D histogram against numpy.histogram2d (two passes of the grid loop, signed and 64-bit weight
+sums, row stride 8, non-uniform and repeated edges, +-inf and -0.0), bitwise reproducibility (eager and replayed
+hipGraph), the end-to-end maps and the C-level refusals."""
 import ctypes
 import os
 
@@ -35,6 +38,57 @@ def test_centered_gram_and_means_against_80_bit(n, D, ld):
     print(f"({n}, {D}, ld {ld}): means {dm:.3e} (bound {bm:.3e}), Gram {dg:.3e} (bound {bg:.3e})")
     assert dm <= bm
     assert dg <= bg
+
+
+def test_non_finite_input_stays_in_its_own_row_and_column():
+    """A NaN in column 5 and an inf in column 66 of the (300, 68, 72) case (the second 64-block is 4 columns wide): the
+    two columns' means, and rows and columns 5 and 66 of S, are non-finite; every other entry is what the case gives
+    with the two columns removed, under the clean case's bounds.  A wrong C/D lane map spreads the NaN over other
+    rows, so this catches one without any tolerance."""
+    n, D, ld = 300, 68, 72
+    x = er.gram_case_x(n, D, ld)
+    x[17, 5] = np.nan
+    x[40, 66] = np.inf
+    mean, gram = ops.centered_gram(_dev_rows(x))
+    assert np.array_equal(gram.cpu().numpy().view(np.int64), gram.T.contiguous().cpu().numpy().view(np.int64)), \
+        "S is not bit-exactly symmetric"
+    mean, gram = mean.cpu().numpy(), gram.cpu().numpy()
+    assert np.isnan(mean[5]) and np.all(np.isnan(gram[5, :])) and np.all(np.isnan(gram[:, 5]))
+    assert mean[66] == np.inf and not np.any(np.isfinite(gram[66, :])) and not np.any(np.isfinite(gram[:, 66]))
+    keep = np.array([c for c in range(D) if c not in (5, 66)])
+    assert np.all(np.isfinite(mean[keep])) and np.all(np.isfinite(gram[np.ix_(keep, keep)]))
+    dm, dg = er.distances_from(mean[keep], gram[np.ix_(keep, keep)], er.gram80_of(x[:, keep]))
+    bm, bg = er.gram_bounds(n, D, ld)
+    print(f"({n}, {D}, ld {ld}) without columns 5 and 66: means {dm:.3e} (bound {bm:.3e}), Gram {dg:.3e} (bound {bg:.3e})")
+    assert dm <= bm
+    assert dg <= bg
+
+
+@pytest.mark.parametrize("n, D, k", er.PROJECT_CASES)
+def test_project_rows_against_80_bit(n, D, k):
+    """mmg_project_rows through the C entry point: out is an [n, 16] buffer of a sentinel (ld_out = 16 > k), the rows
+    dense and with a padded stride (the padding holds 1e6), with and without a scale, general components; the bound is
+    embed_ref.project_ratio's."""
+    from mmgnn import _lib
+    lib = _lib.load()
+    case = er.project_case(n, D, k)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())                      # noqa: E731
+    mean, comps, scale = (torch.from_numpy(case[a].copy()).to(DEV) for a in ("mean", "comps", "scale"))
+    sentinel = -12345.0
+    for ld in (D, D + 8):
+        buf = np.full((n, ld), 1e6, np.float32)
+        buf[:, :D] = case["x"]
+        xd = torch.from_numpy(buf).to(DEV)
+        for scaled in (False, True):
+            out = torch.full((n, 16), sentinel, device=DEV)
+            rc = lib.mmg_project_rows(p(xd), n, D, ld, p(mean), p(comps), p(scale) if scaled else None, k, p(out), 16,
+                                      None, 0, ops._stream())
+            assert rc == 0, lib.mmg_last_error()
+            o = out.cpu().numpy()
+            assert np.all(o[:, k:] == np.float32(sentinel)), "columns k .. 15 of out were written"
+            ratio = er.project_ratio(o[:, :k], case, D, scaled)
+            print(f"({n}, {D}, k {k}) ld_x {ld} scale {scaled}: {ratio:.3f} of the bound")
+            assert ratio <= 1.0
 
 
 @pytest.mark.parametrize("whiten", [False, True])
@@ -80,6 +134,84 @@ def test_grid2d_equals_numpy_histogram2d(gx, gy):
     assert np.array_equal(wsum.cpu().numpy(), er.hist2d_ref(y, ex, ey, w))
     count2, none = ops.grid2d(yd, exd, eyd)
     assert none is None and np.array_equal(count2.cpu().numpy(), want)
+
+
+def test_grid2d_second_grid_pass_signed_weights_and_row_stride_8():
+    """524,288 + 257 points: the 2,048-workgroup cap makes the grid loop take a second, ragged pass.  The points are the
+    first two of eight columns (ld_y = 8: the grid over the first two of eight components; the other six hold values
+    that would land in other cells), the weights are signed."""
+    n = 524288 + 257
+    y, ex, ey, _ = _points(7, 5, seed=3, n=n)
+    rng = np.random.default_rng(4)
+    w = rng.integers(-1000, 1001, n).astype(np.int32)
+    y8 = rng.normal(0.0, 1.2, (n, 8)).astype(np.float32)
+    y8[:, :2] = y
+    yd = torch.from_numpy(y8).to(DEV)[:, :2]
+    assert yd.stride(0) == 8
+    count, wsum = ops.grid2d(yd, torch.from_numpy(ex).to(DEV), torch.from_numpy(ey).to(DEV), torch.from_numpy(w).to(DEV))
+    want, want_w = er.hist2d_ref(y, ex, ey), er.hist2d_ref(y, ex, ey, w)
+    assert 0 < want.sum() < n and want_w.min() < 0 < want_w.max()
+    assert np.array_equal(count.cpu().numpy(), want)
+    assert np.array_equal(wsum.cpu().numpy(), want_w)
+
+
+@pytest.mark.parametrize("weight", [2 ** 31 - 1, -2 ** 31])
+def test_grid2d_weight_sums_past_32_bits(weight):
+    y = torch.zeros(3000, 2, device=DEV)
+    e = torch.tensor([-1.0, 1.0], dtype=torch.float64, device=DEV)
+    w = torch.full((3000,), weight, dtype=torch.int32, device=DEV)
+    count, wsum = ops.grid2d(y, e, e, w)
+    assert abs(3000 * weight) > 2 ** 32
+    assert count.shape == (1, 1) and int(count[0, 0]) == 3000
+    assert int(wsum[0, 0]) == 3000 * weight
+
+
+# non-uniform edges with a repeated one (an empty cell) and the edge 0.0; every value is an fp32 number
+EDGES5 = np.array([-2.0, -1.5, -1.5, 0.0, 0.125, 3.0])
+
+
+def _edges256(seed):
+    e = np.sort(np.random.default_rng(seed).uniform(-2.0, 3.0, 257).astype(np.float32).astype(np.float64))
+    e[100] = e[101]
+    e[np.searchsorted(e, 0.0)] = 0.0
+    assert np.all(np.diff(e) >= 0.0) and e[0] < 0.0 < e[-1]
+    return e
+
+
+def _edge_points(ex, ey):
+    """-0.0, +0.0, +-inf, NaN, every edge (the repeated one and both ends included) and its two fp32 neighbours, in
+    both coordinates -> (y fp32 [n, 2], signed int32 weights)."""
+    rng = np.random.default_rng(7)
+    special = np.array([-0.0, 0.0, np.inf, -np.inf, np.nan], np.float32)
+    vals = []
+    for e in (ex, ey):
+        e32 = e.astype(np.float32)
+        assert np.array_equal(e32.astype(np.float64), e)
+        vals.append(np.concatenate([special, e32, np.nextafter(e32, np.float32(-10)), np.nextafter(e32, np.float32(10)),
+                                    rng.uniform(e[0] - 0.5, e[-1] + 0.5, 64).astype(np.float32)]))
+    m = max(v.size for v in vals)
+    # every value of one axis against values inside the other axis' range, then the two lists against each other
+    inside = [np.float32(0.5 * (e[0] + e[-1])) for e in (ex, ey)]
+    y = np.concatenate([
+        np.stack([vals[0], np.full(vals[0].size, inside[1], np.float32)], axis=1),
+        np.stack([np.full(vals[1].size, inside[0], np.float32), vals[1]], axis=1),
+        np.stack([np.resize(vals[0], m), np.resize(vals[1], m)[::-1]], axis=1)]).astype(np.float32)
+    return y, rng.integers(-50, 50, y.shape[0]).astype(np.int32)
+
+
+@pytest.mark.parametrize("ex, ey", [(EDGES5, EDGES5[::-1] * -1.0), (np.array([-2.0, 3.0]), _edges256(0)),
+                                    (_edges256(1), np.array([-1.0, 0.0]))], ids=["5x5", "1x256", "256x1"])
+def test_grid2d_edge_values_equal_numpy(ex, ey):
+    """Whatever numpy.histogram2d does with _edge_points over non-uniform edges (a repeated edge is an empty cell) is
+    the specification."""
+    y, w = _edge_points(ex, ey)
+    with np.errstate(invalid="ignore"):
+        want, want_w = er.hist2d_ref(y, ex, ey), er.hist2d_ref(y, ex, ey, w)
+    assert 0 < want.sum() < y.shape[0]
+    count, wsum = ops.grid2d(torch.from_numpy(y).to(DEV), torch.from_numpy(ex.copy()).to(DEV),
+                             torch.from_numpy(ey.copy()).to(DEV), torch.from_numpy(w).to(DEV))
+    assert np.array_equal(count.cpu().numpy(), want)
+    assert np.array_equal(wsum.cpu().numpy(), want_w)
 
 
 def test_bitwise_reproducible_eager_and_replayed():
@@ -165,6 +297,18 @@ def test_embedding_maps_end_to_end(tmp_path):
     c = dens["count"].to_numpy()
     assert np.allclose(dens["mean_degree"].to_numpy()[c > 0], ws[c > 0] / c[c > 0], rtol=1e-15, atol=0)
     assert np.all(np.isnan(dens["mean_degree"].to_numpy()[c == 0]))
+    # eight components: the grid is over the first two columns of an [n, 8] projection (row stride 8)
+    er.assert_gaps(ref["eigenvalues"], 8)                            # seed 0 has the gaps up to k = 8
+    out8 = embed.embedding_maps(model, g, n_components=8, grid=8)
+    p8 = out8["patient"].cpu().numpy()
+    assert out8["patient"].is_cuda and p8.shape == (1834, 8) and out8["patient"].stride(0) == 8
+    d8 = float((np.abs(p8[:, :2] - ref["projection"]) / np.abs(ref["projection"]).max(axis=0)).max())
+    print(f"first two of eight components {d8:.3e} (of {er.PROJ_REL:.3e}); eigenvalues {ref['eigenvalues'][:9]}")
+    assert d8 <= er.PROJ_REL                                         # they do not depend on k
+    ex8, ey8 = out8["edges"]
+    count8 = out8["density"]["count"].to_numpy().reshape(8, 8)
+    assert count8.sum() == 1834 and np.array_equal(count8, er.hist2d_ref(p8[:, :2], ex8, ey8))
+    assert len(out8["variance"]) == 32 and list(out8["lab"].columns)[-1] == "pc8"
     # the final space runs too
     fin = embed.embedding_maps(model, g, space="final", grid=8)
     assert fin["patient"].shape == (1834, 2) and int(fin["density"]["count"].sum()) == 1834
