@@ -7,225 +7,120 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmmgnn.so")
-
-MMG_MAX_REL = 4
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mmgnn.h")    # as csrc/Makefile finds it
 
 
 class MmgError(RuntimeError):
     pass
 
 
-class RelT(C.Structure):
-    _fields_ = [("rowptr", C.c_void_p), ("col", C.c_void_p), ("rowscale", C.c_void_p),
-                ("colscale", C.c_void_p), ("table", C.c_void_p), ("out", C.c_void_p),
-                ("n_cols", C.c_int32), ("flags", C.c_uint32), ("mask_t", C.c_void_p),
-                ("mask_r", C.c_void_p)]
+# The one C-type table of the binding: every scalar include/mmgnn.h uses.  `int` is ctypes.c_int itself.
+_SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "int32_t": C.c_int32,
+            "int64_t": C.c_int64, "uint8_t": C.c_uint8, "uint16_t": C.c_uint16, "uint32_t": C.c_uint32,
+            "uint64_t": C.c_uint64}
+_POINTEES = set(_SCALARS) | {"void", "char"}        # T* of these is an untyped address
+_PY_NAMES = {"mmg_bnbwd_t": "BnBwdT", "mmg_bnbwd_wgrad_t": "BnBwdWgradT"}     # where CamelCase of the C name is not it
+_DECLARATOR = re.compile(r"((?:\*\s*(?:const\b\s*)?)*)(\w+)\s*(?:\[\s*(\d+)\s*\])?\s*$")
 
 
-class PrologueT(C.Structure):
-    _fields_ = [("scale", C.c_void_p), ("shift", C.c_void_p), ("relu", C.c_int), ("drop_p", C.c_float),
-                ("seed", C.c_uint64), ("site", C.c_uint32), ("row_offset", C.c_int64), ("seed_ptr", C.c_void_p)]
+def _ctype(base, stars, structs, what, const=False, is_return=False):
+    """C type `base` behind `stars` pointer levels -> ctypes type (structs: the structs declared so far)."""
+    if base not in _POINTEES and base not in structs:
+        raise MmgError(f"mmgnn.h: unknown type {base!r} in {what!r}")
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 0 and base in structs:
+        return structs[base]
+    if stars == 1 and base in structs:
+        return C.POINTER(structs[base])
+    if stars == 1:
+        return C.c_char_p if (is_return and const and base == "char") else C.c_void_p
+    if stars == 2 and base in _POINTEES:
+        return C.POINTER(C.c_void_p)
+    raise MmgError(f"mmgnn.h: unsupported type in {what!r}")
 
 
-class HeadT(C.Structure):
-    _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p),
-                ("W3", C.c_void_p), ("b3", C.c_void_p)]
+def _declaration(text, structs, is_param=False):
+    """`const T* a`, `T lo, hi`, `T* const* p`, `const void* src[4]` -> [(name, ctypes type)]."""
+    m = re.match(r"\s*(const\s+)?(\w+)\b\s*(?:const\b\s*)?(.*)$", text, re.S)
+    names = m.group(3).split(",") if m else []
+    if not names or (is_param and len(names) != 1):
+        raise MmgError(f"mmgnn.h: cannot split the declaration {text.strip()!r}")
+    out = []
+    for decl in names:
+        d = _DECLARATOR.match(decl.strip())
+        if not d or (is_param and d.group(3)):
+            raise MmgError(f"mmgnn.h: cannot split the declaration {text.strip()!r}")
+        t = _ctype(m.group(2), d.group(1).count("*"), structs, text.strip(), bool(m.group(1)))
+        out.append((d.group(2), t * int(d.group(3)) if d.group(3) else t))
+    return out
 
 
-class HeadGradT(C.Structure):
-    _fields_ = [("dA", C.c_void_p), ("dB", C.c_void_p), ("dW2", C.c_void_p), ("db2", C.c_void_p),
-                ("dW3", C.c_void_p), ("db3", C.c_void_p)]
+def parse_header(text):
+    """The C subset of include/mmgnn.h -> (defines {name: int}, structs {C name: ctypes.Structure subclass},
+    signatures {name: (restype, [argtypes])}).  Whatever it does not recognise raises MmgError with the offending text."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    defines, structs, signatures = {}, {}, {}
+
+    def directive(m):
+        line = m.group(0).strip()
+        d = re.match(r"#\s*define\s+(MMG_\w+)\s+\(?\s*(-?\d+)[uU]?\s*\)?$", line)
+        if d:
+            defines[d.group(1)] = int(d.group(2))
+        elif not re.match(r"#\s*(ifndef\s+\w+|ifdef\s+\w+|endif|include\s*<[\w./]+>|define\s+\w+_H)$", line):
+            raise MmgError(f"mmgnn.h: cannot parse the directive {line!r}")
+        return ""
+
+    rest = re.sub(r"^[ \t]*#[^\n]*$", directive, text, flags=re.M).strip()
+    depth = 0
+    while rest:
+        m = re.match(r'extern\s+"C"\s*\{', rest)
+        if m or (depth and rest[0] == "}"):
+            depth += 1 if m else -1
+            rest = rest[m.end() if m else 1:].lstrip()
+            continue
+        m = re.match(r"typedef\s+struct\s*\{([^{}]*)\}\s*(\w+)\s*;", rest)
+        if m:
+            body = m.group(1).split(";")
+            if body.pop().strip() or m.group(2) in structs:
+                raise MmgError(f"mmgnn.h: cannot parse the struct {m.group(0)!r}")
+            fields = [f for decl in body for f in _declaration(decl, structs)]
+            py = _PY_NAMES.get(m.group(2)) or "".join(w.capitalize() for w in m.group(2).split("_")[1:])
+            structs[m.group(2)] = type(py, (C.Structure,), {"_fields_": fields})
+        else:
+            m = re.match(r"(const\s+)?(\w+)\s*(\**)\s*(\w+)\s*\(([^;{}()]*)\)\s*;", rest)
+            if not m or m.group(4) in signatures:
+                raise MmgError(f"mmgnn.h: cannot parse the declaration {rest[:120]!r}")
+            what = m.group(0)
+            res = _ctype(m.group(2), len(m.group(3)), structs, what, bool(m.group(1)), is_return=True)
+            params = [] if m.group(5).strip() == "void" else m.group(5).split(",")
+            signatures[m.group(4)] = (res, [_declaration(p, structs, is_param=True)[0][1] for p in params])
+        rest = rest[m.end():].lstrip()
+    if depth:
+        raise MmgError('mmgnn.h: unbalanced extern "C" block')
+    return defines, structs, signatures
 
 
-class SmallFwdT(C.Structure):
-    _fields_ = [("X", C.c_void_p), ("W", C.c_void_p), ("X2", C.c_void_p), ("W2", C.c_void_p), ("bias", C.c_void_p),
-                ("Y", C.c_void_p), ("M", C.c_int64), ("flags", C.c_int)]
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return f.read()
+    except OSError as e:
+        raise MmgError(f"{HEADER_PATH} not found: the binding is derived from the header the library is built from "
+                       f"({e})") from None
 
 
-class SmallWgradT(C.Structure):
-    _fields_ = [("dY", C.c_void_p), ("X", C.c_void_p), ("dW", C.c_void_p), ("dbias", C.c_void_p), ("M", C.c_int64),
-                ("accumulate", C.c_int)]
-
-
-class SmallBnT(C.Structure):
-    _fields_ = [("Y", C.c_void_p), ("out", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
-                ("running_mean", C.c_void_p), ("running_var", C.c_void_p), ("stats_out", C.c_void_p), ("M", C.c_int64),
-                ("training", C.c_int), ("act", C.c_int), ("drop_p", C.c_float), ("seed", C.c_uint64), ("site", C.c_uint32),
-                ("row_offset", C.c_int64), ("seed_ptr", C.c_void_p)]
-
-
-class SmallBnBwdT(C.Structure):
-    _fields_ = [("G", C.c_void_p), ("Y", C.c_void_p), ("dY", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p),
-                ("mean", C.c_void_p), ("rstd", C.c_void_p), ("dbeta", C.c_void_p), ("dgamma", C.c_void_p), ("M", C.c_int64),
-                ("training", C.c_int), ("act", C.c_int), ("drop_p", C.c_float), ("seed", C.c_uint64), ("site", C.c_uint32),
-                ("row_offset", C.c_int64), ("seed_ptr", C.c_void_p)]
-
-
-class BnFinT(C.Structure):
-    _fields_ = [("count", C.c_int64), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("running_mean", C.c_void_p),
-                ("running_var", C.c_void_p), ("n_updates", C.c_int), ("momentum", C.c_float), ("eps", C.c_float),
-                ("scale", C.c_void_p), ("shift", C.c_void_p), ("mean", C.c_void_p), ("rstd", C.c_void_p)]
-
-
-class NextBnT(C.Structure):
-    _fields_ = [("y", C.c_void_p), ("pro", C.POINTER(PrologueT)), ("mean", C.c_void_p), ("rstd", C.c_void_p),
-                ("sums", C.c_void_p), ("accumulate", C.c_int), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
-
-
-class FwdEpiT(C.Structure):
-    _fields_ = [("mode", C.c_int), ("col_sums", C.c_void_p), ("fin", C.POINTER(BnFinT)), ("ws", C.c_void_p),
-                ("ws_bytes", C.c_size_t), ("next", C.POINTER(NextBnT)), ("rnorm", C.c_void_p), ("eps", C.c_float)]
-
-
-class PairSavedT(C.Structure):
-    _fields_ = [("h1_bits", C.c_void_p), ("h2", C.c_void_p), ("by_position", C.c_int), ("n_entries", C.c_int64)]
-
-
-class WgradReduceT(C.Structure):
-    _fields_ = [("slab", C.c_void_p), ("n4", C.c_int64), ("n_split", C.c_int), ("dW", C.c_void_p), ("dbias", C.c_void_p),
-                ("nk4", C.c_int64), ("accumulate", C.c_int)]
-
-
-class BnBwdT(C.Structure):
-    _fields_ = [("mode", C.c_int), ("G", C.c_void_p), ("G2", C.c_void_p), ("row_pos", C.c_void_p), ("n_sel", C.c_int64),
-                ("y", C.c_void_p), ("pro", C.POINTER(PrologueT)), ("pro2", C.POINTER(PrologueT)), ("mean", C.c_void_p),
-                ("rstd", C.c_void_p), ("sums", C.c_void_p), ("inv_count", C.c_double), ("dbeta", C.c_void_p),
-                ("dgamma", C.c_void_p), ("rnorm", C.c_void_p), ("eps", C.c_float)]
-
-
-class BnBwdWgradT(C.Structure):
-    _fields_ = [("X", C.c_void_p), ("pro", C.POINTER(PrologueT)), ("dW", C.c_void_p), ("dbias", C.c_void_p),
-                ("accumulate", C.c_int), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
-                ("job", C.POINTER(WgradReduceT))]
-
-
-class PercentileT(C.Structure):
-    _fields_ = [("lo", C.c_int32), ("hi", C.c_int32), ("g", C.c_float)]
-
-
-class SumJobT(C.Structure):
-    _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p * 4), ("n_src", C.c_int), ("len", C.c_int),
-                ("cols", C.c_int), ("ld_dst", C.c_int), ("ld_src", C.c_int * 4)]
-
-
-_vp, _i64, _i32, _f32, _sz, _u64, _u32 = (C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t,
-                                          C.c_uint64, C.c_uint32)
-_P = C.POINTER
-
-# name -> (restype, argtypes): every symbol include/mmgnn.h declares
-SIGNATURES = {
-    "mmg_version": (C.c_int, []),
-    "mmg_last_error": (C.c_char_p, []),
-    "mmg_stream_create": (C.c_int, [_P(_vp)]),
-    "mmg_stream_destroy": (C.c_int, [_vp]),
-    "mmg_csr_build_ws_bytes": (_sz, [_i64, _i64]),
-    "mmg_csr_build": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mmg_row_degree": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
-    "mmg_col_degree": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
-    "mmg_rel_mask_words": (_sz, [_i64, C.c_int32]),
-    "mmg_rel_mask_build": (C.c_int, [_vp, _vp, _i64, C.c_int32, _vp, _vp, _vp]),
-    "mmg_gather_rows": (C.c_int, [_P(RelT), _i32, _i64, _i32, _vp, _i32, _P(FwdEpiT), _vp]),
-    "mmg_scatter_rows_ws_bytes": (_sz, [_P(RelT), _i32, _i64, _i32]),
-    "mmg_scatter_rows": (C.c_int, [_P(RelT), _i32, _i64, _i32, _vp, _vp, _sz, _vp]),
-    "mmg_epi_ws_bytes": (_sz, [_i64, _i32]),
-    "mmg_linear_fwd_supported": (C.c_int, [_i32, _i64, _i32, _i32]),
-    "mmg_linear_fwd": (C.c_int, [_vp, _P(PrologueT), _vp, _vp, _vp, _i64, _i32, _i32, _i32, _P(FwdEpiT), _vp]),
-    "mmg_linear_wgrad_ws_bytes": (_sz, [_i64, _i32, _i32]),
-    "mmg_linear_wgrad": (C.c_int, [_vp, _vp, _P(PrologueT), _vp, _vp, _i64, _i32, _i32, _i32, _vp, _sz, _vp]),
-    "mmg_linear_wgrad_deferred": (C.c_int, [_vp, _vp, _P(PrologueT), _vp, _vp, _i64, _i32, _i32, _i32, _vp, _sz, _vp,
-                                            _P(WgradReduceT)]),
-    "mmg_wgrad_reduce_group": (C.c_int, [_P(WgradReduceT), _i32, _vp]),
-    "mmg_linear_wgrad_is_direct": (C.c_int, [_i64, _i32, _i32]),
-    "mmg_col_reduce2_ws_bytes": (_sz, [_i64, _i32]),
-    "mmg_col_reduce2": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
-    "mmg_bn_finalize": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp,
-                                  _i32, _vp]),
-    "mmg_affine_act_drop": (C.c_int, [_vp, _P(PrologueT), _vp, _i64, _i32, _vp]),
-    "mmg_affine_act_drop_rows": (C.c_int, [_vp, _P(PrologueT), _vp, _i64, _vp, _i32, _vp]),
-    "mmg_probe_arm": (C.c_int, [_i32]),
-    "mmg_probe_read": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
-    "mmg_bn_bwd_stats2": (C.c_int, [_vp, _vp, _vp, _P(PrologueT), _P(PrologueT), _vp, _vp, _vp, _i64, _i32, _vp, C.c_size_t, _vp]),
-    "mmg_bn_bwd_apply2": (C.c_int, [_vp, _vp, _vp, _P(PrologueT), _P(PrologueT), _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _i64,
-                                    _i32, _vp]),
-    "mmg_bn_bwd_stats_rows_ws_bytes": (C.c_size_t, [_i32]),
-    "mmg_bn_bwd_stats_rows": (C.c_int, [_vp, _vp, _vp, _i64, _P(PrologueT), _vp, _vp, _vp, _i32, _vp, C.c_size_t, _vp]),
-    "mmg_bn_bwd_apply_rows": (C.c_int, [_vp, _vp, _vp, _i64, _P(PrologueT), _vp, _i32, _vp]),
-    "mmg_bn_bwd_stats": (C.c_int, [_vp, _vp, _P(PrologueT), _vp, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
-    "mmg_bn_bwd_apply": (C.c_int, [_vp, _vp, _P(PrologueT), _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
-    "mmg_linear_bnbwd_supported": (C.c_int, [_i32, _i64, _i32, _i32, _i32]),
-    "mmg_linear_bnbwd_wgrad_ws_bytes": (_sz, [_i64, _i32, _i32]),
-    "mmg_linear_bnbwd": (C.c_int, [_P(BnBwdT), _vp, _vp, _vp, _i64, _i32, _i32, _P(NextBnT), _P(BnBwdWgradT), _vp]),
-    "mmg_l2norm_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _vp]),
-    "mmg_l2norm_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp]),
-    "mmg_pair_loss_ws_bytes": (_sz, [_i64]),
-    "mmg_pair_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i64, C.c_double, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
-    "mmg_sup_mask_ws_bytes": (_sz, [_i64]),
-    "mmg_sup_mask_draw": (C.c_int, [_vp, _u64, _vp, _i64, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mmg_dropout_mask": (C.c_int, [_u64, _vp, _u32, _i64, _i64, _f32, _vp, _vp]),
-    "mmg_pair_head_fwd": (C.c_int, [_P(HeadT), _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i32, _f32, _u64, _vp, _vp,
-                                    _vp, _vp, _vp, _vp, _vp]),
-    "mmg_pair_head_fwd_save": (C.c_int, [_P(HeadT), _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i32, _f32, _u64, _vp, _vp,
-                                         _vp, _vp, _vp, _vp, _P(PairSavedT), _vp]),
-    "mmg_pair_head_dense_fwd": (C.c_int, [_P(HeadT), _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp]),
-    "mmg_pair_head_bwd_saved": (C.c_int, [_P(HeadT), _P(HeadGradT), _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i32, _f32,
-                                          _u64, _vp, _vp, _vp, _vp, _vp, _vp, _P(PairSavedT), _vp, _sz, _vp]),
-    "mmg_pair_head_bwd_ws_bytes": (_sz, [_i64, _i32]),
-    "mmg_pair_head_bwd": (C.c_int, [_P(HeadT), _P(HeadGradT), _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i32, _f32,
-                                    _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mmg_small_fwd_group": (C.c_int, [_P(SmallFwdT), _i32, _i32, _i32, _vp]),
-    "mmg_small_wgrad_group": (C.c_int, [_P(SmallWgradT), _i32, _i32, _i32, _vp]),
-    "mmg_small_bn_act_group": (C.c_int, [_P(SmallBnT), _i32, _i32, _f32, _f32, _vp]),
-    "mmg_small_bn_bwd_group": (C.c_int, [_P(SmallBnBwdT), _i32, _i32, _vp]),
-    "mmg_adam_step": (C.c_int, [_vp, _vp, _vp, _P(C.c_void_p), _P(C.c_int32), _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
-    "mmg_adam_step_dev": (C.c_int, [_vp, _vp, _vp, _P(C.c_void_p), _P(C.c_int32), _i32, _vp, _vp, _vp, _vp]),
-    "mmg_vec_sums": (C.c_int, [_P(SumJobT), _i32, _vp]),
-    "mmg_counters_add": (C.c_int, [_P(C.c_void_p), _P(C.c_int64), _i32, _vp]),
-    "mmg_seed_advance": (C.c_int, [_vp, _vp]),
-    "mmg_fill_zero": (C.c_int, [_vp, _sz, _vp]),
-    "mmg_seg_reduce_ws_bytes": (_sz, [_i64, _i32]),
-    "mmg_seg_moments": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _sz, _vp]),
-    "mmg_seg_metrics": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _f32, _vp, _vp, _vp, _sz, _vp]),
-    "mmg_pair_select_ws_bytes": (_sz, [_i64]),
-    "mmg_pair_select": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mmg_knn_impute_ws_bytes": (_sz, [_i64, _i32, _i64, _i32]),
-    "mmg_knn_impute": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _sz, _vp]),
-    "mmg_order_stats_ws_bytes": (_sz, [_i64]),
-    "mmg_order_stats": (C.c_int, [_vp, _vp, _i64, _P(C.c_int64), _i32, _vp, _vp, _vp, _sz, _vp]),
-    "mmg_robust_sums_ws_bytes": (_sz, [_i64]),
-    "mmg_robust_sums": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _vp, PercentileT, PercentileT, PercentileT, _vp, _vp, _sz,
-                                  _vp]),
-    "mmg_split_membership_ws_bytes": (_sz, [_i64]),
-    "mmg_split_membership": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _sz, _vp]),
-    "mmg_prep_sort_ws_bytes": (_sz, [_i64]),
-    "mmg_prep_sort": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mmg_lab_stats_ws_bytes": (_sz, [_i32]),
-    "mmg_lab_stats": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _sz, _vp]),
-    "mmg_lab_quantiles_ws_bytes": (_sz, [_i32]),
-    "mmg_lab_quantiles": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _sz, _vp]),
-    "mmg_lab_aggregate_ws_bytes": (_sz, [_i64]),
-    "mmg_lab_aggregate": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp,
-                                    _P(C.c_int64), _vp, _sz, _vp]),
-    "mmg_lab_transform": (C.c_int, [_i32, _i32, C.c_double, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
-    "mmg_lab_inverse_matrix": (C.c_int, [_i32, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp]),
-    "mmg_pair_analysis_ws_bytes": (_sz, [_i64, _i32, _i32]),
-    "mmg_pair_analysis": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i64, _P(C.c_double), _i32, _vp, _vp, _vp,
-                                    _sz, _vp]),
-    "mmg_pair_calibrated_abs_ws_bytes": (_sz, [_i64, _i32, _i32]),
-    "mmg_pair_calibrated_abs": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _i64, _P(C.c_double), _i32,
-                                          _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mmg_code_select_ws_bytes": (_sz, [_i64, _i64]),
-    "mmg_code_select": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
-                                  _P(C.c_int64), _vp, _sz, _vp]),
-    "mmg_centered_gram_ws_bytes": (_sz, [_i64, _i32]),
-    "mmg_centered_gram": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _sz, _vp]),
-    "mmg_project_rows_ws_bytes": (_sz, [_i64, _i32, _i32]),
-    "mmg_project_rows": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _sz, _vp]),
-    "mmg_grid2d_ws_bytes": (_sz, [_i64, _i32, _i32]),
-    "mmg_grid2d": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
-}
+# Every MMG_* define (an int), every struct (under its Python name, e.g. mmg_bn_fin_t -> BnFinT) and
+# SIGNATURES, name -> (restype, argtypes) of every symbol, all read from include/mmgnn.h: the header is the only
+# description of the ABI's layout.
+DEFINES, STRUCTS, SIGNATURES = parse_header(_read_header())
+globals().update(DEFINES)
+globals().update({s.__name__: s for s in STRUCTS.values()})
 
 _lib = None
 

@@ -25,6 +25,7 @@ import numpy as np
 import pandas as pd
 import torch
 
+from . import _lib
 from .train import LAB_EDGE
 
 DEFAULT_BINS = (0, 1, 6, 16, 50)
@@ -34,7 +35,7 @@ CALIBRATION_COLUMNS = ["lab_idx", "lab_name", "n_samples", "a", "b", "mae_before
 DEGREE_COLUMNS = ["degree_bin", "mean", "std", "count"]
 DECILE_COLUMNS = ["decile", "n_labs", "count_min", "count_max", "n_pairs", "mae", "r2"]
 # columns of the first read's lab table (MMG_AN_LAB_FIELDS)
-N, ST, SP, STT, STP, SAE, SSE, TMIN, TMAX = range(9)
+N, ST, SP, STT, STP, SAE, SSE, TMIN, TMAX = range(_lib.MMG_AN_LAB_FIELDS)
 
 
 # ============================================================================ inputs
@@ -130,7 +131,6 @@ def patient_degrees(graph_data, dev=None):
 
 # ============================================================================ the two reads
 def _device_fits(n_labs: int, n_bins: int) -> bool:
-    from . import _lib
     return n_labs + n_bins > 0 and _lib.load().mmg_pair_analysis_ws_bytes(1, int(n_labs), int(n_bins)) > 0
 
 

@@ -21,6 +21,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from . import _lib
 from .train import LAB_EDGE, EdgeMasker
 
 
@@ -257,7 +258,7 @@ def robust_metrics_from_sums(s, winsorize_pct: float) -> Dict:
         "num_outliers_capped": int(s[9]),
         "outlier_percentage": float(100 * s[9] / n),
         "max_residual": float(s[11]),
-        "p95_residual": float(s[14]),
+        "p95_residual": float(s[_lib.MMG_RS_P95]),
     }
 
 

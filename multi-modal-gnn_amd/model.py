@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import _lib, ops
 from .data import GraphPlan, LAB_EDGE, ROW_TYPE, RelCSR, build_plan
 from .ops import Pro
 
@@ -184,7 +184,7 @@ class HeteroRGCN(nn.Module):
             raise ValueError(f"Unknown activation: {activation}")
         # activation code of the HIP epilogues (MMG_ACT_*): conv layers only -- patient_transform and the heads are
         # nn.ReLU by construction (model.py:93-103, 373-386)
-        self._act_code = {"relu": 1, "leaky_relu": 2, "elu": 3}[activation]
+        self._act_code = {"relu": _lib.MMG_ACT_RELU, "leaky_relu": _lib.MMG_ACT_LEAKY_RELU, "elu": _lib.MMG_ACT_ELU}[activation]
 
         self.edge_predictor = EdgeRegressionHead(2 * D, [64, 32], 1, dropout)           # model.py:159-164
         self.tabular_mlp = EdgeRegressionHead(2 * D, [64, 32], 1, dropout)              # model.py:172-177
@@ -463,8 +463,8 @@ class _Run:
             self.grads[name] = cur
         self.pending = {}
         for jobs in levels:
-            for j0 in range(0, len(jobs), 8):
-                ops.vec_sums(jobs[j0:j0 + 8])
+            for j0 in range(0, len(jobs), _lib.MMG_SUM_MAX_JOBS):
+                ops.vec_sums(jobs[j0:j0 + _lib.MMG_SUM_MAX_JOBS])
 
     def allreduce(self, t):
         if self.comm is not None:
@@ -1009,7 +1009,7 @@ class _Run:
                                 sums=rec.get("ysums") if t == ROW_TYPE else None) if self.m.use_batch_norm else None
             pro = Pro(fold.scale if fold else None, fold.shift if fold else None, self.m._act_code, p, self.seed,
                       SITE_CONV + 8 * l + ti, plan.row_offset if sharded else 0, self.seed_dev)
-            if last and t == ROW_TYPE and self.lazy_final and self.m._act_code == 1:
+            if last and t == ROW_TYPE and self.lazy_final and self.m._act_code == _lib.MMG_ACT_RELU:
                 out[t] = _LazyAct(y[t], pro, fold)               # consumed through the heads' GEMM prologues
             else:
                 out[t] = ops.affine_act_drop(y[t], pro)

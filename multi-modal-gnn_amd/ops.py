@@ -25,14 +25,17 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _p(t: Optional[torch.Tensor], dtype=torch.float32, name="tensor"):
+def _p(t: Optional[torch.Tensor], dtype=torch.float32, name="tensor", contiguous=True):
+    """Device pointer of a tensor for an argument or a descriptor field (None: NULL).  contiguous=False: the tensor may
+    be a strided view (the caller passes its strides on)."""
     if t is None:
         return None
+    where = f"{name}: " if name else ""
     if not t.is_cuda:
-        raise _lib.MmgError(f"{name}: expected a HIP device tensor, got {t.device} (no CPU fallback)")
+        raise _lib.MmgError(f"{where}expected a HIP device tensor, got {t.device} (no CPU fallback)")
     if t.dtype != dtype:
-        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
-    if not t.is_contiguous():
+        raise TypeError(f"{where}expected {dtype}, got {t.dtype}")
+    if contiguous and not t.is_contiguous():
         raise ValueError(f"{name}: must be contiguous")
     return C.c_void_p(t.data_ptr())
 
@@ -87,9 +90,13 @@ def _pe(tok, name, nbytes=0, flops=0):
     _PROF.rows.append((name, tok, e, int(nbytes), int(flops)))
 
 
-PROBE_TAGS = {1: "linear_fwd", 2: "linear_wgrad", 3: "linear_wgrad_reduce", 4: "gather_rows", 5: "scatter_rows",
-              6: "scatter_reduce", 7: "pair_head_fwd", 8: "pair_head_bwd", 9: "bn_bwd_stats", 10: "bn_bwd_apply",
-              11: "elementwise", 12: "pair_head_dense_fwd", 13: "knn_impute"}
+PROBE_TAGS = {_lib.MMG_PROBE_LINEAR_FWD: "linear_fwd", _lib.MMG_PROBE_LINEAR_WGRAD: "linear_wgrad",
+              _lib.MMG_PROBE_LINEAR_WGRAD_REDUCE: "linear_wgrad_reduce", _lib.MMG_PROBE_GATHER: "gather_rows",
+              _lib.MMG_PROBE_SCATTER: "scatter_rows", _lib.MMG_PROBE_SCATTER_REDUCE: "scatter_reduce",
+              _lib.MMG_PROBE_PAIR_FWD: "pair_head_fwd", _lib.MMG_PROBE_PAIR_BWD: "pair_head_bwd",
+              _lib.MMG_PROBE_BN_BWD_STATS: "bn_bwd_stats", _lib.MMG_PROBE_BN_BWD_APPLY: "bn_bwd_apply",
+              _lib.MMG_PROBE_ELEMENTWISE: "elementwise", _lib.MMG_PROBE_PAIR_DENSE_FWD: "pair_head_dense_fwd",
+              _lib.MMG_PROBE_KNN_IMPUTE: "knn_impute"}
 
 
 def probe_arm(n: int):
@@ -97,7 +104,7 @@ def probe_arm(n: int):
     check(_lib.load().mmg_probe_arm(int(n)), "mmg_probe_arm")
 
 
-PROBE_NAME_LEN = 128
+PROBE_NAME_LEN = _lib.MMG_PROBE_NAME_LEN
 
 
 def probe_read(cap: int = 1 << 16):
@@ -147,7 +154,7 @@ def workspace(nbytes: int, device) -> torch.Tensor:
 @dataclass
 class Pro:
     """Prologue dropout(act(x*scale+shift)) applied on load (mmg_prologue_t).  relu: False / True, or an MMG_ACT_* code
-    (2 = leaky_relu, 3 = elu: the materialising and backward kernels only)."""
+    (MMG_ACT_LEAKY_RELU, MMG_ACT_ELU: the materialising and backward kernels only)."""
     scale: Optional[torch.Tensor] = None
     shift: Optional[torch.Tensor] = None
     relu: int = 0
@@ -242,7 +249,7 @@ def _rels(rels: Sequence[Rel], D: int, need_table=False, need_out=False):
         if need_out and (r.out is None or tuple(r.out.shape) != (r.n_cols, D)):
             raise ValueError(f"relation {i}: out must be [{r.n_cols},{D}]")
         arr[i] = RelT(_p(r.rowptr, torch.int32), _p(r.col, torch.int32), _p(r.rowscale), _p(r.colscale),
-                      _p(r.table), _p(r.out), r.n_cols, 1 if r.simple else 0,
+                      _p(r.table), _p(r.out), r.n_cols, _lib.MMG_REL_SIMPLE if r.simple else 0,
                       _p(r.mask_t, torch.int64) if r.simple else None,
                       _p(r.mask_r, torch.int64) if r.simple else None)
     return arr
@@ -266,13 +273,13 @@ def _bn_fin(count: int, N: int, device, bn):
     """bn = (gamma, beta, running_mean, running_var, n_updates) -> (mmg_bn_fin_t, the BNFold its launch fills)."""
     gamma, beta, rm, rv, n_updates = bn
     st = torch.empty(4, N, dtype=torch.float32, device=device)
-    fin = BnFinT(int(count), _p(gamma).value, _p(beta).value, _p(rm).value if rm is not None else None,
-                 _p(rv).value if rv is not None else None, int(n_updates), BN_MOMENTUM, BN_EPS,
-                 _p(st[0]).value, _p(st[1]).value, _p(st[2]).value, _p(st[3]).value)
+    fin = BnFinT(int(count), _p(gamma), _p(beta), _p(rm), _p(rv), int(n_updates), BN_MOMENTUM, BN_EPS,
+                 _p(st[0]), _p(st[1]), _p(st[2]), _p(st[3]))
     return fin, BNFold(st[0], st[1], st[2], st[3], int(count), True)
 
 
-EPI_NONE, EPI_STATS, EPI_NEXT_BN, EPI_L2 = range(4)      # mmg_fwd_epi_t.mode
+EPI_NONE, EPI_STATS, EPI_NEXT_BN, EPI_L2 = (_lib.MMG_EPI_NONE, _lib.MMG_EPI_STATS, _lib.MMG_EPI_NEXT_BN,
+                                            _lib.MMG_EPI_L2)      # mmg_fwd_epi_t.mode
 
 
 def _fwd_epi(what: str, M: int, N: int, device, with_stats=False, bn=None, next_bn: Optional["NextBN"] = None, l2=False):
@@ -287,14 +294,14 @@ def _fwd_epi(what: str, M: int, N: int, device, with_stats=False, bn=None, next_
         return e, (sums,)
     if l2:
         rn = torch.empty(M, device=device)
-        return FwdEpiT(EPI_L2, rnorm=_p(rn).value, eps=L2_EPS), (rn,)
+        return FwdEpiT(EPI_L2, rnorm=_p(rn), eps=L2_EPS), (rn,)
     if bn is None and not with_stats:
         return None, ()
     sums = torch.empty(2, N, dtype=torch.float64, device=device)
     ws = workspace(_lib.load().mmg_epi_ws_bytes(M, N), device)
     fin, fold = _bn_fin(M, N, device, bn) if bn is not None else (None, None)
-    e = FwdEpiT(EPI_STATS, col_sums=_p(sums, torch.float64).value, fin=C.pointer(fin) if fin is not None else None,
-                ws=_p(ws, torch.uint8).value, ws_bytes=ws.numel())
+    e = FwdEpiT(EPI_STATS, col_sums=_p(sums, torch.float64), fin=C.pointer(fin) if fin is not None else None,
+                ws=_p(ws, torch.uint8), ws_bytes=ws.numel())
     e._keep = (fin, ws)
     return e, (sums,) if fold is None else (sums, fold)
 
@@ -349,6 +356,10 @@ def linear_fwd(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = 
     return _linear_fwd(x, W, bias, pro, out, accumulate, w_kn, with_stats=with_stats, bn=bn, next_bn=next_bn)
 
 
+def _lin_flags(accumulate, w_kn) -> int:
+    return (_lib.MMG_LIN_ACCUMULATE if accumulate else 0) | (_lib.MMG_LIN_W_KN if w_kn else 0)
+
+
 def _linear_fwd(x, W, bias, pro, out, accumulate, w_kn, **epi):
     """The one call behind linear_fwd and linear_l2norm_fwd (mmg_linear_fwd; epi: the options of _fwd_epi)."""
     lib = _lib.load()
@@ -365,7 +376,7 @@ def _linear_fwd(x, W, bias, pro, out, accumulate, w_kn, **epi):
     _tok = _pb("linear_fwd")
     desc, extra = _fwd_epi("linear_fwd", M, N, x.device, **epi)
     check(lib.mmg_linear_fwd(_p(x, name="x"), _pro(pro), _p(W, name="W"), _p(bias, name="bias"), _p(out, name="out"), M, N,
-                             K, int(accumulate) | (2 if w_kn else 0), C.byref(desc) if desc is not None else None,
+                             K, _lin_flags(accumulate, w_kn), C.byref(desc) if desc is not None else None,
                              _stream()), "mmg_linear_fwd")
     nbn = epi.get("next_bn") is not None          # + the next BatchNorm's y
     _pe(_tok, "linear_fwd", 4 * (M * K + N * K + M * N * (1 + int(accumulate) + int(nbn))), 2 * M * N * K)
@@ -411,15 +422,16 @@ def linear_wgrad(dy: torch.Tensor, x: torch.Tensor, pro: Optional[Pro] = None, o
 
 
 def wgrad_reduce_flush(jobs: list):
-    """Sum the slabs of every deferred weight gradient (linear_wgrad(defer=...)): one launch per <= 16 jobs; a job that
-    accumulates into a gradient an earlier job of the list writes goes into a later launch.  Empties the list."""
+    """Sum the slabs of every deferred weight gradient (linear_wgrad(defer=...)): one launch per <= MMG_WGRAD_REDUCE_MAX
+    jobs; a job that accumulates into a gradient an earlier job of the list writes goes into a later launch.  Empties the
+    list."""
     lib = _lib.load()
     todo = [j for j in jobs if j[0].slab]
     jobs.clear()
     while todo:
         group, later, seen = [], [], set()
         for j in todo:
-            if j[0].dW in seen or len(group) == 16:
+            if j[0].dW in seen or len(group) == _lib.MMG_WGRAD_REDUCE_MAX:
                 later.append(j)
             else:
                 group.append(j)
@@ -476,8 +488,8 @@ def _next_bn(nb: NextBN, M: int, N: int):
         raise ValueError("next_bn: sums must be fp64 [2,N]")
     ws = workspace(lib.mmg_epi_ws_bytes(M, N), nb.y.device)
     pc = nb.pro.c()
-    t = NextBnT(_p(nb.y).value, C.pointer(pc), _p(nb.fold.mean).value, _p(nb.fold.rstd).value,
-                _p(sums, torch.float64).value, int(acc), _p(ws, torch.uint8).value, ws.numel())
+    t = NextBnT(_p(nb.y), C.pointer(pc), _p(nb.fold.mean), _p(nb.fold.rstd), _p(sums, torch.float64), int(acc),
+                _p(ws, torch.uint8), ws.numel())
     t._keep = (pc, ws)
     return t, sums
 
@@ -604,7 +616,9 @@ def linear_l2norm_fwd(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Ten
     return _linear_fwd(x, W, bias, pro, None, False, False, l2=True)
 
 
-BNBWD_BN, BNBWD_L2, BNBWD_BN2, BNBWD_ROWS = range(4)        # mmg_bnbwd_t.mode: linear_bnbwd / _l2bwd / _bnbwd2 / _bnbwd_rows
+# mmg_bnbwd_t.mode: linear_bnbwd / _l2bwd / _bnbwd2 / _bnbwd_rows
+BNBWD_BN, BNBWD_L2, BNBWD_BN2, BNBWD_ROWS = (_lib.MMG_BNBWD_BN, _lib.MMG_BNBWD_L2, _lib.MMG_BNBWD_BN2,
+                                             _lib.MMG_BNBWD_ROWS)
 
 
 def linear_bnbwd_supported(M: int, N: int, K: int, mode: int = BNBWD_BN, wgrad: bool = False) -> bool:
@@ -648,9 +662,8 @@ def _fused_wgrad(fw: FusedWgrad, M: int, N: int, K: int):
     ws = torch.empty(nb, dtype=torch.uint8, device=dev)      # its own slabs (the shared workspace may hold a NextBN's partials)
     job = WgradReduceT()
     pc = fw.pro.c() if fw.pro is not None else None
-    t = BnBwdWgradT(_p(fw.x).value, C.pointer(pc) if pc is not None else None, _p(fw.dW).value,
-                    _p(fw.db).value if fw.db is not None else None, int(acc), _p(ws, torch.uint8).value, ws.numel(),
-                    C.pointer(job) if fw.defer is not None else None)
+    t = BnBwdWgradT(_p(fw.x), C.pointer(pc) if pc is not None else None, _p(fw.dW), _p(fw.db), int(acc),
+                    _p(ws, torch.uint8), ws.numel(), C.pointer(job) if fw.defer is not None else None)
     t._keep = (pc, ws, job)
     return t
 
@@ -668,10 +681,6 @@ def _fused_wgrad_bytes(M: int, N: int, K: int) -> int:      # x read once, one s
 # g and out
 _BNBWD_PROF = {BNBWD_BN: ("linear_bnbwd", 2), BNBWD_BN2: ("linear_bnbwd", 3), BNBWD_ROWS: ("linear_bnbwd", 1),
                BNBWD_L2: ("linear_l2bwd", 2)}
-
-
-def _addr(t: Optional[torch.Tensor], dtype=torch.float32):
-    return t.data_ptr() if _p(t, dtype) is not None else None
 
 
 def _linear_bnbwd(mode: int, y: torch.Tensor, W: torch.Tensor, next_bn: Optional["NextBN"], wgrad: Optional[FusedWgrad],
@@ -697,10 +706,10 @@ def _linear_bnbwd(mode: int, y: torch.Tensor, W: torch.Tensor, next_bn: Optional
     nbt, nsums = _next_bn(next_bn, M, N) if next_bn is not None else (None, None)
     wt = _fused_wgrad(wgrad, M, N, K) if wgrad is not None else None
     pcs = [q.c() if q is not None else None for q in (pro, pro2)]          # alive until the call returns
-    desc = BnBwdT(mode, _addr(g), _addr(g2), _addr(row_pos, torch.int32), n_sel, _addr(y),
+    desc = BnBwdT(mode, _p(g), _p(g2), _p(row_pos, torch.int32), n_sel, _p(y),
                   *[C.pointer(pc) if pc is not None else None for pc in pcs],
-                  _addr(fold.mean) if fold else None, _addr(fold.rstd) if fold else None, _addr(sums, torch.float64),
-                  1.0 / float(count), _addr(dbeta), _addr(dgamma), _addr(rn), L2_EPS)
+                  _p(fold.mean) if fold else None, _p(fold.rstd) if fold else None, _p(sums, torch.float64),
+                  1.0 / float(count), _p(dbeta), _p(dgamma), _p(rn), L2_EPS)
     check(lib.mmg_linear_bnbwd(C.byref(desc), _p(W), _p(dz), _p(dx), M, N, K, C.byref(nbt) if nbt is not None else None,
                                C.byref(wt) if wt is not None else None, _stream()), "mmg_linear_bnbwd")
     if wgrad is not None:
@@ -863,7 +872,7 @@ def _pair_saved(saved, n_total: int, n_launch: int):
     if bits.shape[0] < need:
         raise ValueError(f"pair head: saved buffers hold {bits.shape[0]} entries, the launch reaches {need}"
                          + (" list positions" if by_pos else " pairs"))
-    return PairSavedT(_p(bits, torch.int32).value, _p(h2).value, int(by_pos), int(bits.shape[0]))
+    return PairSavedT(_p(bits, torch.int32), _p(h2), int(by_pos), int(bits.shape[0]))
 
 
 def pair_head_fwd(head: Head, pi, li, deg, thr: int, want_low: bool, p: float, seed: int, pair_id, pred, seed_dev=None,
@@ -1030,15 +1039,6 @@ def seg_sums(pred: torch.Tensor, target: torch.Tensor, seg: torch.Tensor, n_seg:
     return sums, adj
 
 
-def _p_any(t: torch.Tensor):
-    """device pointer of an fp32 tensor that may be a strided view (the caller passes its strides on)."""
-    if not t.is_cuda:
-        raise _lib.MmgError(f"expected a HIP device tensor, got {t.device} (no CPU fallback)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"expected torch.float32, got {t.dtype}")
-    return C.c_void_p(t.data_ptr())
-
-
 def _rows_view(t: torch.Tensor):
     """(cols, row stride) of a tensor that is a flat vector or a 2-D matrix with unit column stride."""
     if t.is_contiguous():
@@ -1069,9 +1069,9 @@ def vec_sums(jobs):
         for q, t in enumerate(srcs):
             if t.numel() != dst.numel():
                 raise ValueError("vec_sums: size mismatch")
-            sp[q] = _p_any(t).value
+            sp[q] = _p(t, name="", contiguous=False)
             ld[q] = (views[q + 1][1] or cols) if strided else 0
-        arr[j] = SumJobT(_p_any(dst).value, sp, len(srcs), dst.numel(), cols,
+        arr[j] = SumJobT(_p(dst, name="", contiguous=False), sp, len(srcs), dst.numel(), cols,
                          (views[0][1] or cols) if strided else 0, ld)
     check(lib.mmg_vec_sums(arr, len(jobs), _stream()), "mmg_vec_sums")
 
@@ -1079,9 +1079,10 @@ def vec_sums(jobs):
 def counters_add(counters, incs):
     """*counters[i] += incs[i] (int64 device scalars) in one launch (mmg_counters_add)."""
     lib = _lib.load()
-    for i0 in range(0, len(counters), 32):
-        cs, ins = counters[i0:i0 + 32], incs[i0:i0 + 32]
-        ptrs = (C.c_void_p * len(cs))(*[_p(c, torch.int64).value for c in cs])
+    step = _lib.MMG_COUNTERS_MAX
+    for i0 in range(0, len(counters), step):
+        cs, ins = counters[i0:i0 + step], incs[i0:i0 + step]
+        ptrs = (C.c_void_p * len(cs))(*[_p(c, torch.int64) for c in cs])
         inc = (C.c_int64 * len(cs))(*[int(v) for v in ins])
         check(lib.mmg_counters_add(ptrs, inc, len(cs), _stream()), "mmg_counters_add")
 
@@ -1117,7 +1118,8 @@ class SmallFwd:
 
 
 def small_fwd_group(probs: Sequence[SmallFwd]):
-    """Runs the problems (same N and K) in ceil(len / 8) launches; allocates missing outputs; returns the outputs."""
+    """Runs the problems (same N and K) in ceil(len / MMG_SMALL_MAX) launches; allocates missing outputs; returns the
+    outputs."""
     lib = _lib.load()
     if not probs:
         return []
@@ -1139,15 +1141,12 @@ def small_fwd_group(probs: Sequence[SmallFwd]):
             raise ValueError("small_fwd_group: second term shape")
         outs.append(p.out)
     live = [p for p in probs if p.x.shape[0] > 0]              # (an empty table has an empty output)
-    for i0 in range(0, len(live), 8):
-        chunk = live[i0:i0 + 8]
+    for i0 in range(0, len(live), _lib.MMG_SMALL_MAX):
+        chunk = live[i0:i0 + _lib.MMG_SMALL_MAX]
         arr = (SmallFwdT * len(chunk))()
         for i, p in enumerate(chunk):
-            arr[i] = SmallFwdT(_p(p.x, name="x").value, _p(p.W, name="W").value,
-                               _p(p.x2).value if p.x2 is not None else None,
-                               _p(p.W2).value if p.W2 is not None else None,
-                               _p(p.bias).value if p.bias is not None else None,
-                               _p(p.out).value, p.x.shape[0], int(p.accumulate) | (2 if p.w_kn else 0))
+            arr[i] = SmallFwdT(_p(p.x, name="x"), _p(p.W, name="W"), _p(p.x2), _p(p.W2), _p(p.bias), _p(p.out),
+                               p.x.shape[0], _lin_flags(p.accumulate, p.w_kn))
         check(lib.mmg_small_fwd_group(arr, len(chunk), N, K, _stream()), "mmg_small_fwd_group")
     return outs
 
@@ -1164,7 +1163,8 @@ class SmallWgrad:
 
 
 def small_wgrad_group(probs: Sequence[SmallWgrad]):
-    """Runs the problems (same N and K) in ceil(len / 8) launches; allocates missing outputs; returns [(dW, dbias)]."""
+    """Runs the problems (same N and K) in ceil(len / MMG_SMALL_MAX) launches; allocates missing outputs; returns
+    [(dW, dbias)]."""
     lib = _lib.load()
     if not probs:
         return []
@@ -1182,13 +1182,12 @@ def small_wgrad_group(probs: Sequence[SmallWgrad]):
                 raise ValueError("accumulating the bias gradient needs dbias")
             p.dbias = torch.empty(N, dtype=torch.float32, device=p.x.device)
         res.append((p.dW, p.dbias))
-    for i0 in range(0, len(probs), 8):
-        chunk = probs[i0:i0 + 8]
+    for i0 in range(0, len(probs), _lib.MMG_SMALL_MAX):
+        chunk = probs[i0:i0 + _lib.MMG_SMALL_MAX]
         arr = (SmallWgradT * len(chunk))()
         for i, p in enumerate(chunk):
-            arr[i] = SmallWgradT(_p(p.dy).value if p.dy.numel() else None, _p(p.x).value if p.x.numel() else None,
-                                 _p(p.dW).value, _p(p.dbias).value if p.dbias is not None else None, p.dy.shape[0],
-                                 int(p.accumulate))
+            arr[i] = SmallWgradT(_p(p.dy) if p.dy.numel() else None, _p(p.x) if p.x.numel() else None, _p(p.dW),
+                                 _p(p.dbias), p.dy.shape[0], int(p.accumulate))
         check(lib.mmg_small_wgrad_group(arr, len(chunk), N, K, _stream()), "mmg_small_wgrad_group")
     return res
 
@@ -1202,8 +1201,8 @@ def small_bn_act_group(items, training: bool):
     if not items:
         return res
     N = items[0][0].shape[1]
-    for i0 in range(0, len(items), 8):
-        chunk = items[i0:i0 + 8]
+    for i0 in range(0, len(items), _lib.MMG_SMALL_MAX):
+        chunk = items[i0:i0 + _lib.MMG_SMALL_MAX]
         arr = (SmallBnT * len(chunk))()
         keep = []
         for i, (y, mod, pro) in enumerate(chunk):
@@ -1212,14 +1211,14 @@ def small_bn_act_group(items, training: bool):
                 raise ValueError("small_bn_act_group: same width, M <= 4096")
             out = torch.empty_like(y)
             st = torch.empty(4, N, dtype=torch.float32, device=y.device) if mod is not None else None
-            arr[i] = SmallBnT(_p(y).value if M else None, _p(out).value if M else None,
-                              _p(mod.weight.detach()).value if mod is not None else None,
-                              _p(mod.bias.detach()).value if mod is not None else None,
-                              _p(mod.running_mean).value if mod is not None else None,
-                              _p(mod.running_var).value if mod is not None else None,
-                              _p(st).value if st is not None else None, M, int(training), int(pro.relu), float(pro.p),
+            arr[i] = SmallBnT(_p(y) if M else None, _p(out) if M else None,
+                              _p(mod.weight.detach()) if mod is not None else None,
+                              _p(mod.bias.detach()) if mod is not None else None,
+                              _p(mod.running_mean) if mod is not None else None,
+                              _p(mod.running_var) if mod is not None else None,
+                              _p(st), M, int(training), int(pro.relu), float(pro.p),
                               int(pro.seed) & 0xFFFFFFFFFFFFFFFF, int(pro.site), int(pro.row_offset),
-                              _p(pro.seed_dev, torch.int64).value if pro.seed_dev is not None else None)
+                              _p(pro.seed_dev, torch.int64))
             keep.append((out, st))
             fold = None
             if mod is not None:
@@ -1238,22 +1237,19 @@ def small_bn_bwd_group(items):
     if not items:
         return res
     N = items[0][1].shape[1]
-    for i0 in range(0, len(items), 8):
-        chunk = items[i0:i0 + 8]
+    for i0 in range(0, len(items), _lib.MMG_SMALL_MAX):
+        chunk = items[i0:i0 + _lib.MMG_SMALL_MAX]
         arr = (SmallBnBwdT * len(chunk))()
         for i, (g, y, pro, fold) in enumerate(chunk):
             M = y.shape[0]
             dy = torch.empty_like(y)
             dbg = torch.empty(2, N, dtype=torch.float32, device=y.device) if fold is not None else None
-            arr[i] = SmallBnBwdT(_p(g).value if M else None, _p(y).value if M else None, _p(dy).value if M else None,
-                                 _p(fold.scale).value if fold is not None else None,
-                                 _p(fold.shift).value if fold is not None else None,
-                                 _p(fold.mean).value if fold is not None else None,
-                                 _p(fold.rstd).value if fold is not None else None,
-                                 _p(dbg[0]).value if dbg is not None else None, _p(dbg[1]).value if dbg is not None else None,
-                                 M, int(fold.training) if fold is not None else 0, int(pro.relu), float(pro.p),
+            stats = (fold.scale, fold.shift, fold.mean, fold.rstd, dbg[0], dbg[1]) if fold is not None else (None,) * 6
+            arr[i] = SmallBnBwdT(_p(g) if M else None, _p(y) if M else None, _p(dy) if M else None,
+                                 *[_p(t) for t in stats], M, int(fold.training) if fold is not None else 0,
+                                 int(pro.relu), float(pro.p),
                                  int(pro.seed) & 0xFFFFFFFFFFFFFFFF, int(pro.site), int(pro.row_offset),
-                                 _p(pro.seed_dev, torch.int64).value if pro.seed_dev is not None else None)
+                                 _p(pro.seed_dev, torch.int64))
             res.append((dy, dbg[0] if dbg is not None else None, dbg[1] if dbg is not None else None))
         check(lib.mmg_small_bn_bwd_group(arr, len(chunk), N, _stream()), "mmg_small_bn_bwd_group")
     return res
@@ -1292,13 +1288,13 @@ def knn_impute(X, rows, n_neighbors: int, weights: str = "uniform", out=None):
 
 
 # ------------------------------------------------------------------------------------------ leakage audit
-MAX_ORDER_RANKS = 8          # MMG_OS_MAX_RANKS
-ROBUST_FIELDS = 15           # MMG_RS_FIELDS
-SPLIT_FIELDS = 10            # MMG_SM_FIELDS
+MAX_ORDER_RANKS = _lib.MMG_OS_MAX_RANKS
+ROBUST_FIELDS = _lib.MMG_RS_FIELDS
+SPLIT_FIELDS = _lib.MMG_SM_FIELDS
 
 
 def order_stats(a: torch.Tensor, ranks: Sequence[int], b: Optional[torch.Tensor] = None, out=None, nan_count=None):
-    """Exact order statistics (mmg_order_stats): the values of the 0-based ranks (host ints, at most 8) of a -- or of
+    """Exact order statistics (mmg_order_stats): the values of the 0-based ranks (host ints, at most MAX_ORDER_RANKS) of a -- or of
     |a - b| formed in fp32 -- in ascending order, NaN last.  -> (fp32 [len(ranks)], int64 [1] NaN count), both on the
     device; nothing synchronises with the host."""
     lib = _lib.load()
@@ -1371,14 +1367,17 @@ def split_membership(patient: torch.Tensor, train_mask: torch.Tensor, val_mask: 
 
 
 # ------------------------------------------------------------------------------------------ lab preprocessing
-PREP_MAX_LABS = 2048         # MMG_PREP_MAX_LABS
-LAB_STAT_FIELDS = 9          # MMG_LS_FIELDS: n, mean, std, min, max, q25, median, q75, rows
-LS_N, LS_MEAN, LS_STD, LS_MIN, LS_MAX, LS_Q25, LS_MEDIAN, LS_Q75, LS_ROWS = range(9)
-SORT_BY_TIME, SORT_BY_VALUE = 0, 1
-AGG_CODES = {"last": 0, "mean": 1, "median": 2, "min": 3, "max": 4}
-OUTLIER_CODES = {None: 0, "std": 1, "iqr": 2}
-NORM_CODES = {"zscore": 0, "minmax": 1, "robust": 2}
-_LT_OUTLIER, _LT_NORMALIZE, _LT_INVERSE = 0, 1, 2
+PREP_MAX_LABS = _lib.MMG_PREP_MAX_LABS
+LAB_STAT_FIELDS = _lib.MMG_LS_FIELDS          # n, mean, std, min, max, q25, median, q75, rows
+LS_N, LS_MEAN, LS_STD, LS_MIN, LS_MAX, LS_Q25, LS_MEDIAN, LS_Q75, LS_ROWS = (
+    _lib.MMG_LS_N, _lib.MMG_LS_MEAN, _lib.MMG_LS_STD, _lib.MMG_LS_MIN, _lib.MMG_LS_MAX, _lib.MMG_LS_Q25, _lib.MMG_LS_MEDIAN,
+    _lib.MMG_LS_Q75, _lib.MMG_LS_ROWS)
+SORT_BY_TIME, SORT_BY_VALUE = _lib.MMG_PS_TIME, _lib.MMG_PS_VALUE
+AGG_CODES = {"last": _lib.MMG_AGG_LAST, "mean": _lib.MMG_AGG_MEAN, "median": _lib.MMG_AGG_MEDIAN, "min": _lib.MMG_AGG_MIN,
+             "max": _lib.MMG_AGG_MAX}
+OUTLIER_CODES = {None: _lib.MMG_OUT_NONE, "std": _lib.MMG_OUT_STD, "iqr": _lib.MMG_OUT_IQR}
+NORM_CODES = {"zscore": _lib.MMG_NORM_ZSCORE, "minmax": _lib.MMG_NORM_MINMAX, "robust": _lib.MMG_NORM_ROBUST}
+_LT_OUTLIER, _LT_NORMALIZE, _LT_INVERSE = _lib.MMG_LT_OUTLIER, _lib.MMG_LT_NORMALIZE, _lib.MMG_LT_INVERSE
 
 
 def _prep_sizes(n, n_patients, n_labs):
@@ -1508,13 +1507,10 @@ def lab_inverse_matrix(pred: torch.Tensor, stats: torch.Tensor, method: str, out
     lib = _lib.load()
     if pred.dim() != 2 or pred.stride(1) != 1 or pred.shape[1] != stats.shape[0] or stats.shape[1] != LAB_STAT_FIELDS:
         raise ValueError("lab_inverse_matrix: pred must be [n_rows, n_labs] with unit column stride, stats [n_labs, 9]")
-    if not pred.is_cuda:
-        raise _lib.MmgError(f"pred: expected a HIP device tensor, got {pred.device} (no CPU fallback)")
-    if pred.dtype != torch.float32:
-        raise TypeError(f"pred: expected torch.float32, got {pred.dtype}")
+    pp = _p(pred, torch.float32, "pred", contiguous=False)
     if out is None:
         out = torch.empty(pred.shape, dtype=torch.float32, device=pred.device)
-    check(lib.mmg_lab_inverse_matrix(NORM_CODES[method], C.c_void_p(pred.data_ptr()), pred.shape[0], pred.shape[1],
+    check(lib.mmg_lab_inverse_matrix(NORM_CODES[method], pp, pred.shape[0], pred.shape[1],
                                      pred.stride(0) if pred.shape[0] > 1 else max(pred.stride(0), pred.shape[1]),
                                      _p(stats, torch.float64, "stats"), _p(out, torch.float32, "out"), out.shape[1],
                                      _stream()), "mmg_lab_inverse_matrix")
@@ -1522,7 +1518,7 @@ def lab_inverse_matrix(pred: torch.Tensor, stats: torch.Tensor, method: str, out
 
 
 # ------------------------------------------------------------------------------------------ feature-space selection
-SEL_ROWS = {"all": 0, "first": 1}          # MMG_SEL_ROWS_ALL / MMG_SEL_ROWS_FIRST
+SEL_ROWS = {"all": _lib.MMG_SEL_ROWS_ALL, "first": _lib.MMG_SEL_ROWS_FIRST}
 
 
 def code_select(code: torch.Tensor, patient: torch.Tensor, n_patients: int, n_codes: int, min_patient_count: int,
@@ -1562,9 +1558,9 @@ def code_select(code: torch.Tensor, patient: torch.Tensor, n_patients: int, n_co
 
 # ------------------------------------------------------------------------------------------ prediction analysis
 AN_MAX_LABS = 2048          # the lab limit of csrc/analysis.hip (and of csrc/evalred.hip)
-AN_MAX_BINS = 64             # MMG_AN_MAX_BINS
-AN_LAB_FIELDS = 9            # MMG_AN_LAB_FIELDS: n, sum t, sum p, sum t^2, sum t p, sum |p - t|, sum (p - t)^2, min t, max t
-AN_BIN_FIELDS = 2            # MMG_AN_BIN_FIELDS: n, sum |p - t|
+AN_MAX_BINS = _lib.MMG_AN_MAX_BINS
+AN_LAB_FIELDS = _lib.MMG_AN_LAB_FIELDS      # n, sum t, sum p, sum t^2, sum t p, sum |p - t|, sum (p - t)^2, min t, max t
+AN_BIN_FIELDS = _lib.MMG_AN_BIN_FIELDS      # n, sum |p - t|
 
 
 def _an_index(t: Optional[torch.Tensor], n: int, name: str, dev):
@@ -1651,13 +1647,10 @@ def _rows_matrix(x: torch.Tensor, name: str):
     """fp32 device [n, D] with unit column stride -> (pointer, n, D, row stride in elements)."""
     if x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
         raise ValueError(f"{name}: expected a 2-D tensor with unit column stride")
-    if not x.is_cuda:
-        raise _lib.MmgError(f"{name}: expected a HIP device tensor, got {x.device} (no CPU fallback)")
-    if x.dtype != torch.float32:
-        raise TypeError(f"{name}: expected torch.float32, got {x.dtype}")
+    px = _p(x, torch.float32, name, contiguous=False)
     n, D = int(x.shape[0]), int(x.shape[1])
     ld = int(x.stride(0)) if n > 1 else max(int(x.stride(0)), D)
-    return C.c_void_p(x.data_ptr()), n, D, ld
+    return px, n, D, ld
 
 
 def centered_gram(x: torch.Tensor):
