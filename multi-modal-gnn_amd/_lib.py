@@ -23,6 +23,11 @@ _SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": 
             "int64_t": C.c_int64, "uint8_t": C.c_uint8, "uint16_t": C.c_uint16, "uint32_t": C.c_uint32,
             "uint64_t": C.c_uint64}
 _POINTEES = set(_SCALARS) | {"void", "char"}        # T* of these is an untyped address
+# C scalar behind a pointer parameter -> names of the torch dtypes a tensor handed to it may have (the first is the one
+# a refusal names).  Seeds and bit-plane words are int64 storage; a bool mask is one byte per element.  uint16_t has no
+# entry: the one such parameter (mask_r) points into int64 storage and is converted by hand.
+TORCH_DTYPES = {"float": ("float32",), "double": ("float64",), "int": ("int32",), "int32_t": ("int32",),
+                "uint32_t": ("int32",), "int64_t": ("int64",), "uint64_t": ("int64",), "uint8_t": ("uint8", "bool")}
 _PY_NAMES = {"mmg_bnbwd_t": "BnBwdT", "mmg_bnbwd_wgrad_t": "BnBwdWgradT"}     # where CamelCase of the C name is not it
 _DECLARATOR = re.compile(r"((?:\*\s*(?:const\b\s*)?)*)(\w+)\s*(?:\[\s*(\d+)\s*\])?\s*$")
 
@@ -45,7 +50,8 @@ def _ctype(base, stars, structs, what, const=False, is_return=False):
 
 
 def _declaration(text, structs, is_param=False):
-    """`const T* a`, `T lo, hi`, `T* const* p`, `const void* src[4]` -> [(name, ctypes type)]."""
+    """`const T* a`, `T lo, hi`, `T* const* p`, `const void* src[4]` -> [(name, ctypes type, C base type, pointer
+    depth)]."""
     m = re.match(r"\s*(const\s+)?(\w+)\b\s*(?:const\b\s*)?(.*)$", text, re.S)
     names = m.group(3).split(",") if m else []
     if not names or (is_param and len(names) != 1):
@@ -55,14 +61,18 @@ def _declaration(text, structs, is_param=False):
         d = _DECLARATOR.match(decl.strip())
         if not d or (is_param and d.group(3)):
             raise MmgError(f"mmgnn.h: cannot split the declaration {text.strip()!r}")
-        t = _ctype(m.group(2), d.group(1).count("*"), structs, text.strip(), bool(m.group(1)))
-        out.append((d.group(2), t * int(d.group(3)) if d.group(3) else t))
+        stars = d.group(1).count("*")
+        t = _ctype(m.group(2), stars, structs, text.strip(), bool(m.group(1)))
+        out.append((d.group(2), t * int(d.group(3)) if d.group(3) else t, m.group(2), stars))
     return out
 
 
-def parse_header(text):
+def parse_header(text, params=None):
     """The C subset of include/mmgnn.h -> (defines {name: int}, structs {C name: ctypes.Structure subclass},
-    signatures {name: (restype, [argtypes])}).  Whatever it does not recognise raises MmgError with the offending text."""
+    signatures {name: (restype, [argtypes])}).  Whatever it does not recognise raises MmgError with the offending text.
+    params (a dict): also filled with name -> [(parameter name, C base type, pointer depth)] of every function.
+    A workspace is always the three parameters ws, ws_bytes (directly behind it) and stream: the call layer fills them
+    by name, so a prototype with `ws` that breaks this is refused like unknown C."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"//[^\n]*", " ", text)
     defines, structs, signatures = {}, {}, {}
@@ -89,7 +99,7 @@ def parse_header(text):
             body = m.group(1).split(";")
             if body.pop().strip() or m.group(2) in structs:
                 raise MmgError(f"mmgnn.h: cannot parse the struct {m.group(0)!r}")
-            fields = [f for decl in body for f in _declaration(decl, structs)]
+            fields = [f[:2] for decl in body for f in _declaration(decl, structs)]
             py = _PY_NAMES.get(m.group(2)) or "".join(w.capitalize() for w in m.group(2).split("_")[1:])
             structs[m.group(2)] = type(py, (C.Structure,), {"_fields_": fields})
         else:
@@ -98,8 +108,14 @@ def parse_header(text):
                 raise MmgError(f"mmgnn.h: cannot parse the declaration {rest[:120]!r}")
             what = m.group(0)
             res = _ctype(m.group(2), len(m.group(3)), structs, what, bool(m.group(1)), is_return=True)
-            params = [] if m.group(5).strip() == "void" else m.group(5).split(",")
-            signatures[m.group(4)] = (res, [_declaration(p, structs, is_param=True)[0][1] for p in params])
+            decls = [] if m.group(5).strip() == "void" else m.group(5).split(",")
+            decls = [_declaration(p, structs, is_param=True)[0] for p in decls]
+            names = [d[0] for d in decls]
+            if "ws" in names and (names[names.index("ws") + 1:][:1] != ["ws_bytes"] or "stream" not in names):
+                raise MmgError(f"mmgnn.h: {m.group(4)} takes `ws` without `ws_bytes` directly behind it or without `stream`")
+            signatures[m.group(4)] = (res, [d[1] for d in decls])
+            if params is not None:
+                params[m.group(4)] = [(d[0], d[2], d[3]) for d in decls]
         rest = rest[m.end():].lstrip()
     if depth:
         raise MmgError('mmgnn.h: unbalanced extern "C" block')
@@ -116,9 +132,10 @@ def _read_header():
 
 
 # Every MMG_* define (an int), every struct (under its Python name, e.g. mmg_bn_fin_t -> BnFinT) and
-# SIGNATURES, name -> (restype, argtypes) of every symbol, all read from include/mmgnn.h: the header is the only
-# description of the ABI's layout.
-DEFINES, STRUCTS, SIGNATURES = parse_header(_read_header())
+# SIGNATURES, name -> (restype, argtypes) of every symbol, with PARAMS, name -> [(parameter name, C base type, pointer
+# depth)], all read from include/mmgnn.h: the header is the only description of the ABI's layout.
+PARAMS = {}
+DEFINES, STRUCTS, SIGNATURES = parse_header(_read_header(), PARAMS)
 globals().update(DEFINES)
 globals().update({s.__name__: s for s in STRUCTS.values()})
 

@@ -43,11 +43,10 @@ def eager_collective_stream(device_index: int):
     st = _EAGER_STREAMS.get(device_index)
     if st is None:
         import ctypes
-        from . import _lib
-        lib = _lib.load()
+        from .ops import _call
         out = ctypes.c_void_p()
         with torch.cuda.device(device_index):
-            _lib.check(lib.mmg_stream_create(ctypes.byref(out)), "mmg_stream_create")
+            _call("mmg_stream_create", ctypes.byref(out))
         st = torch.cuda.ExternalStream(out.value, device=torch.device("cuda", device_index))
         _EAGER_STREAMS[device_index] = st
     return st

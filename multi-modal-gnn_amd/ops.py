@@ -26,18 +26,73 @@ def _stream():
 
 
 def _p(t: Optional[torch.Tensor], dtype=torch.float32, name="tensor", contiguous=True):
-    """Device pointer of a tensor for an argument or a descriptor field (None: NULL).  contiguous=False: the tensor may
-    be a strided view (the caller passes its strides on)."""
+    """Device pointer of a tensor for a descriptor field, or for an argument whose dtype or layout the prototype cannot
+    give (None: NULL).  dtype: one, or a tuple of accepted ones.  contiguous=False: the tensor may be a strided view (the
+    caller passes its strides on)."""
     if t is None:
         return None
     where = f"{name}: " if name else ""
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
     if not t.is_cuda:
         raise _lib.MmgError(f"{where}expected a HIP device tensor, got {t.device} (no CPU fallback)")
-    if t.dtype != dtype:
-        raise TypeError(f"{where}expected {dtype}, got {t.dtype}")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{where}expected {dtypes[0]}, got {t.dtype}")
     if contiguous and not t.is_contiguous():
         raise ValueError(f"{name}: must be contiguous")
     return C.c_void_p(t.data_ptr())
+
+
+def _plan(params):
+    """What becomes of each parameter of a prototype: "stream", "ws" or "ws_bytes" (filled by _call), (header's name,
+    accepted torch dtypes) for a pointer to a scalar the dtype table knows, None for the rest (passed as given)
+    -> (plan, number of arguments the caller gives)."""
+    has_ws = any(p[0] == "ws" for p in params)
+    plan = []
+    for pname, base, depth in params:
+        if pname == "stream" or (has_ws and pname in ("ws", "ws_bytes")):
+            plan.append(pname)
+        elif depth == 1 and base in _lib.TORCH_DTYPES:
+            plan.append((pname, tuple(getattr(torch, d) for d in _lib.TORCH_DTYPES[base])))
+        else:
+            plan.append(None)
+    return plan, sum(1 for how in plan if not isinstance(how, str))
+
+
+_PLANS = {sym: _plan(params) for sym, params in _lib.PARAMS.items()}      # decided once, from the header alone
+
+
+def _call(name, *args, ws=None, names=None):
+    """The one path into the library: `args` are the parameters of the prototype of `name` (include/mmgnn.h) without
+    stream, ws and ws_bytes.  A torch.Tensor handed to a scalar pointer parameter is converted under the header's dtype
+    and parameter name (names: {header's name: the name a refusal uses instead}); tensors on different devices are
+    refused; everything else -- None, numbers, ctypes values, a pointer made by _p -- passes through.  ws: a byte count
+    (the shared workspace() on the device of the first tensor argument) or the call's own uint8 tensor.  The stream is the
+    current one; the return code goes through check()."""
+    plan, n_given = _PLANS[name]
+    if len(args) != n_given:
+        raise TypeError(f"{name}: takes {n_given} arguments besides ws and stream, got {len(args)}")
+    if ws is not None and "ws" not in plan:
+        raise TypeError(f"{name}: takes no workspace")
+    out, dev, given = [], None, iter(args)
+    for how in plan:
+        a = (0 if how == "ws_bytes" else None) if isinstance(how, str) else next(given)       # ws=None: NULL, 0
+        if how is not None and isinstance(a, torch.Tensor):
+            t, a = a, _p(a, how[1], names.get(how[0], how[0]) if names else how[0])
+            if dev is None:
+                dev = t.device
+            elif t.device != dev:
+                raise ValueError(f"{name}: {how[0]} is on {t.device}, the tensors before it on {dev}")
+        out.append(a)
+    for i, how in enumerate(plan):              # after the conversions: a refused tensor costs no workspace
+        if how == "stream":
+            out[i] = _stream()
+        elif how == "ws" and ws is not None:
+            if not isinstance(ws, torch.Tensor):
+                if dev is None:
+                    raise _lib.MmgError(f"{name}: no tensor argument names the device of the workspace")
+                ws = workspace(ws, dev)
+            out[i], out[i + 1] = _p(ws, torch.uint8, "ws"), ws.numel()
+    check(getattr(_lib.load(), name)(*out), name)
 
 
 # ------------------------------------------------------------------------------------------
@@ -101,7 +156,7 @@ PROBE_TAGS = {_lib.MMG_PROBE_LINEAR_FWD: "linear_fwd", _lib.MMG_PROBE_LINEAR_WGR
 
 def probe_arm(n: int):
     """Measurement hook: the next n big-kernel launches (any host thread) carry their own HIP start / stop event pair."""
-    check(_lib.load().mmg_probe_arm(int(n)), "mmg_probe_arm")
+    _call("mmg_probe_arm", int(n))
 
 
 PROBE_NAME_LEN = _lib.MMG_PROBE_NAME_LEN
@@ -177,7 +232,6 @@ def _pro(pro: Optional[Pro]):
 # ------------------------------------------------------------------------------------------ CSR
 def csr_build(edge_index: torch.Tensor, n_rows: int, sort_row: int):
     """-> (rowptr int32 [n_rows+1], col int32 [E], perm int32 [E]); see mmg_csr_build."""
-    lib = _lib.load()
     if edge_index.dim() != 2 or edge_index.shape[0] != 2:
         raise ValueError(f"edge_index must be [2,E], got {tuple(edge_index.shape)}")
     E = int(edge_index.shape[1])
@@ -185,29 +239,23 @@ def csr_build(edge_index: torch.Tensor, n_rows: int, sort_row: int):
     rowptr = torch.empty(n_rows + 1, dtype=torch.int32, device=dev)
     col = torch.empty(E, dtype=torch.int32, device=dev)
     perm = torch.empty(E, dtype=torch.int32, device=dev)
-    nb = lib.mmg_csr_build_ws_bytes(E, n_rows)
-    ws = workspace(nb, dev)
-    check(lib.mmg_csr_build(_p(edge_index, torch.int64, "edge_index"), E, n_rows, sort_row, _p(rowptr, torch.int32),
-                            _p(col, torch.int32), _p(perm, torch.int32), _p(ws, torch.uint8), ws.numel(), _stream()),
-          "mmg_csr_build")
+    _call("mmg_csr_build", edge_index, E, n_rows, sort_row, rowptr, col, perm,
+          ws=_lib.load().mmg_csr_build_ws_bytes(E, n_rows))
     return rowptr, col, perm
 
 
 def row_degree(rowptr: torch.Tensor):
-    lib = _lib.load()
     n = rowptr.numel() - 1
     deg = torch.empty(n, dtype=torch.int32, device=rowptr.device)
     inv = torch.empty(n, dtype=torch.float32, device=rowptr.device)
-    check(lib.mmg_row_degree(_p(rowptr, torch.int32), n, _p(deg, torch.int32), _p(inv), _stream()), "mmg_row_degree")
+    _call("mmg_row_degree", rowptr, n, deg, inv)
     return deg, inv
 
 
 def col_degree(col: torch.Tensor, n_cols: int):
-    lib = _lib.load()
     cnt = torch.empty(n_cols, dtype=torch.int32, device=col.device)
     inv = torch.empty(n_cols, dtype=torch.float32, device=col.device)
-    check(lib.mmg_col_degree(_p(col, torch.int32), col.numel(), n_cols, _p(cnt, torch.int32), _p(inv), _stream()),
-          "mmg_col_degree")
+    _call("mmg_col_degree", col, col.numel(), n_cols, cnt, inv)
     return cnt, inv
 
 
@@ -264,8 +312,8 @@ def rel_mask_build(rowptr: torch.Tensor, col: torch.Tensor, n_cols: int):
     words = lib.mmg_rel_mask_words(n_rows, n_cols)
     mask_t = torch.empty(max(words, 1), dtype=torch.int64, device=rowptr.device)
     mask_r = torch.empty(max(words, 1), dtype=torch.int64, device=rowptr.device)
-    check(lib.mmg_rel_mask_build(_p(rowptr, torch.int32), _p(col, torch.int32), n_rows, n_cols, _p(mask_t, torch.int64),
-                                 _p(mask_r, torch.int64), _stream()), "mmg_rel_mask_build")
+    _call("mmg_rel_mask_build", rowptr, col, n_rows, n_cols, mask_t,
+          _p(mask_r, torch.int64, "mask_r"))          # uint16_t fields in int64 storage: no dtype to derive
     return mask_t, mask_r
 
 
@@ -312,7 +360,6 @@ def gather_rows(rels: Sequence[Rel], n_rows: int, D: int, out: torch.Tensor, acc
     bn = (gamma, beta, running_mean, running_var, n_updates): also fold the training-mode BatchNorm of `out` in the launch
     that sums the statistics -> (out, sums, BNFold).
     next_bn: -> (out, the statistics of the BatchNorm backward that consumes out), see NextBN."""
-    lib = _lib.load()
     if tuple(out.shape) != (n_rows, D):
         raise ValueError("gather_rows: out shape")
     for r in rels:
@@ -321,26 +368,22 @@ def gather_rows(rels: Sequence[Rel], n_rows: int, D: int, out: torch.Tensor, acc
     arr = _rels(rels, D, need_table=True)
     _tok = _pb("gather_rows")
     epi, extra = _fwd_epi("gather_rows", n_rows, D, out.device, with_stats, bn, next_bn)
-    check(lib.mmg_gather_rows(arr, len(rels), n_rows, D, _p(out), int(accumulate), C.byref(epi) if epi is not None else None,
-                              _stream()), "mmg_gather_rows")
+    _call("mmg_gather_rows", arr, len(rels), n_rows, D, out, int(accumulate), C.byref(epi) if epi is not None else None)
     _pe(_tok, "gather_rows", _agg_bytes(rels, n_rows, D, accumulate) + (4 * D * n_rows if next_bn is not None else 0), 0)
     return (out,) + extra if extra else out
 
 
 def scatter_rows(rels: Sequence[Rel], n_rows: int, D: int, x: torch.Tensor):
     """Writes every rel.out ([n_cols, D])."""
-    lib = _lib.load()
     if tuple(x.shape) != (n_rows, D):
         raise ValueError("scatter_rows: x shape")
     for r in rels:
         if r.rowptr.numel() != n_rows + 1:
             raise ValueError("scatter_rows: rowptr length")
     arr = _rels(rels, D, need_out=True)
-    nb = lib.mmg_scatter_rows_ws_bytes(arr, len(rels), n_rows, D)
-    ws = workspace(nb, x.device)
+    nb = _lib.load().mmg_scatter_rows_ws_bytes(arr, len(rels), n_rows, D)
     _tok = _pb("scatter_rows")
-    check(lib.mmg_scatter_rows(arr, len(rels), n_rows, D, _p(x), _p(ws, torch.uint8), ws.numel(), _stream()),
-          "mmg_scatter_rows")
+    _call("mmg_scatter_rows", arr, len(rels), n_rows, D, x, ws=nb)
     _pe(_tok, "scatter_rows", _agg_bytes(rels, n_rows, D, False), 0)
 
 
@@ -362,7 +405,6 @@ def _lin_flags(accumulate, w_kn) -> int:
 
 def _linear_fwd(x, W, bias, pro, out, accumulate, w_kn, **epi):
     """The one call behind linear_fwd and linear_l2norm_fwd (mmg_linear_fwd; epi: the options of _fwd_epi)."""
-    lib = _lib.load()
     M, K = x.shape
     N = W.shape[1] if w_kn else W.shape[0]
     if (W.shape[0] if w_kn else W.shape[1]) != K:
@@ -375,9 +417,8 @@ def _linear_fwd(x, W, bias, pro, out, accumulate, w_kn, **epi):
         raise ValueError("linear_fwd: out shape")
     _tok = _pb("linear_fwd")
     desc, extra = _fwd_epi("linear_fwd", M, N, x.device, **epi)
-    check(lib.mmg_linear_fwd(_p(x, name="x"), _pro(pro), _p(W, name="W"), _p(bias, name="bias"), _p(out, name="out"), M, N,
-                             K, _lin_flags(accumulate, w_kn), C.byref(desc) if desc is not None else None,
-                             _stream()), "mmg_linear_fwd")
+    _call("mmg_linear_fwd", x, _pro(pro), W, bias, out, M, N, K, _lin_flags(accumulate, w_kn),
+          C.byref(desc) if desc is not None else None, names={"X": "x", "Y": "out"})
     nbn = epi.get("next_bn") is not None          # + the next BatchNorm's y
     _pe(_tok, "linear_fwd", 4 * (M * K + N * K + M * N * (1 + int(accumulate) + int(nbn))), 2 * M * N * K)
     return (out,) + extra if extra else out
@@ -405,17 +446,13 @@ def linear_wgrad(dy: torch.Tensor, x: torch.Tensor, pro: Optional[Pro] = None, o
     nb = lib.mmg_linear_wgrad_ws_bytes(M, N, K)
     _tok = _pb("linear_wgrad")
     if defer is None:
-        ws = workspace(nb, x.device)
-        check(lib.mmg_linear_wgrad(_p(dy), _p(x), _pro(pro), _p(out), _p(dbias), M, N, K, int(accumulate),
-                                   _p(ws, torch.uint8), ws.numel(), _stream()), "mmg_linear_wgrad")
+        _call("mmg_linear_wgrad", dy, x, _pro(pro), out, dbias, M, N, K, int(accumulate), ws=nb)
     else:
         if accumulate and lib.mmg_linear_wgrad_is_direct(M, N, K) and any(j[2] is out for j in defer):
             wgrad_reduce_flush(defer)        # a small launch adds into `out` in place: its earlier slabs must be summed first
         ws = torch.empty(max(int(nb), 256), dtype=torch.uint8, device=x.device)      # its own slabs: they live until the flush
         job = WgradReduceT()
-        check(lib.mmg_linear_wgrad_deferred(_p(dy), _p(x), _pro(pro), _p(out), _p(dbias), M, N, K, int(accumulate),
-                                            _p(ws, torch.uint8), ws.numel(), _stream(), C.byref(job)),
-              "mmg_linear_wgrad_deferred")
+        _call("mmg_linear_wgrad_deferred", dy, x, _pro(pro), out, dbias, M, N, K, int(accumulate), C.byref(job), ws=ws)
         defer.append((job, ws, out, dbias))
     _pe(_tok, "linear_wgrad", 4 * (M * N + M * K + N * K), 2 * M * N * K)
     return (out, dbias) if with_bias else out
@@ -425,7 +462,6 @@ def wgrad_reduce_flush(jobs: list):
     """Sum the slabs of every deferred weight gradient (linear_wgrad(defer=...)): one launch per <= MMG_WGRAD_REDUCE_MAX
     jobs; a job that accumulates into a gradient an earlier job of the list writes goes into a later launch.  Empties the
     list."""
-    lib = _lib.load()
     todo = [j for j in jobs if j[0].slab]
     jobs.clear()
     while todo:
@@ -437,20 +473,16 @@ def wgrad_reduce_flush(jobs: list):
                 group.append(j)
             seen.add(j[0].dW)            # (also blocks every LATER job of that gradient: the order of its sums is kept)
         arr = (WgradReduceT * len(group))(*[j[0] for j in group])
-        check(lib.mmg_wgrad_reduce_group(arr, len(group), _stream()), "mmg_wgrad_reduce_group")
+        _call("mmg_wgrad_reduce_group", arr, len(group))
         todo = later
 
 
 def col_reduce2(a: torch.Tensor, b: Optional[torch.Tensor] = None):
     """-> fp64 [2,N]: (sum_m a, sum_m a*b) with b = a when omitted."""
-    lib = _lib.load()
     M, N = a.shape
     out = torch.empty(2, N, dtype=torch.float64, device=a.device)
-    nb = lib.mmg_col_reduce2_ws_bytes(M, N)
-    ws = workspace(nb, a.device)
     _tok = _pb("col_reduce2")
-    check(lib.mmg_col_reduce2(_p(a), _p(b), _p(out, torch.float64), M, N, _p(ws, torch.uint8), ws.numel(), _stream()),
-          "mmg_col_reduce2")
+    _call("mmg_col_reduce2", a, b, out, M, N, ws=_lib.load().mmg_col_reduce2_ws_bytes(M, N))
     _pe(_tok, "col_reduce2", 4 * M * N * (2 if b is not None else 1), 0)
     return out
 
@@ -496,22 +528,19 @@ def _next_bn(nb: NextBN, M: int, N: int):
 
 def bn_finalize(sums: Optional[torch.Tensor], count: int, gamma, beta, running_mean, running_var, training: bool,
                 n_updates: int = 1) -> BNFold:
-    lib = _lib.load()
     N = gamma.numel()
     dev = gamma.device
     st = torch.empty(4, N, dtype=torch.float32, device=dev)
-    check(lib.mmg_bn_finalize(_p(sums, torch.float64), count, _p(gamma), _p(beta), _p(running_mean), _p(running_var),
-                              int(training), n_updates, BN_MOMENTUM, BN_EPS, _p(st[0]), _p(st[1]), _p(st[2]), _p(st[3]),
-                              N, _stream()), "mmg_bn_finalize")
+    _call("mmg_bn_finalize", sums, count, gamma, beta, running_mean, running_var, int(training), n_updates, BN_MOMENTUM,
+          BN_EPS, st[0], st[1], st[2], st[3], N)
     return BNFold(st[0], st[1], st[2], st[3], count, training)
 
 
 def affine_act_drop(y: torch.Tensor, pro: Pro, out: Optional[torch.Tensor] = None):
-    lib = _lib.load()
     M, N = y.shape
     out = torch.empty_like(y) if out is None else out
     _tok = _pb("affine_act_drop")
-    check(lib.mmg_affine_act_drop(_p(y), _pro(pro), _p(out), M, N, _stream()), "mmg_affine_act_drop")
+    _call("mmg_affine_act_drop", y, _pro(pro), out, M, N)
     _pe(_tok, "affine_act_drop", 8 * M * N, 0)
     return out
 
@@ -519,72 +548,57 @@ def affine_act_drop(y: torch.Tensor, pro: Pro, out: Optional[torch.Tensor] = Non
 def affine_act_drop_rows(y: torch.Tensor, pro: Pro, rows: torch.Tensor):
     """dropout(relu(y[rows]*scale+shift)) for the selected rows (int64 ids); the dropout mask is the one the full tensor
     would get at those rows."""
-    lib = _lib.load()
     N = y.shape[1]
     n = rows.numel()
     out = torch.empty(n, N, dtype=torch.float32, device=y.device)
-    check(lib.mmg_affine_act_drop_rows(_p(y), _pro(pro), _p(rows, torch.int64), n, _p(out), N, _stream()),
-          "mmg_affine_act_drop_rows")
+    _call("mmg_affine_act_drop_rows", y, _pro(pro), rows, n, out, N)
     return out
 
 
 def bn_bwd_stats(g: torch.Tensor, y: torch.Tensor, pro: Pro, fold: BNFold):
-    lib = _lib.load()
     M, N = y.shape
     out = torch.empty(2, N, dtype=torch.float64, device=y.device)
-    nb = lib.mmg_col_reduce2_ws_bytes(M, N)
-    ws = workspace(nb, y.device)
     _tok = _pb("bn_bwd_stats")
-    check(lib.mmg_bn_bwd_stats(_p(g), _p(y), _pro(pro), _p(fold.mean), _p(fold.rstd), _p(out, torch.float64), M, N,
-                               _p(ws, torch.uint8), ws.numel(), _stream()), "mmg_bn_bwd_stats")
+    _call("mmg_bn_bwd_stats", g, y, _pro(pro), fold.mean, fold.rstd, out, M, N,
+          ws=_lib.load().mmg_col_reduce2_ws_bytes(M, N))
     _pe(_tok, "bn_bwd_stats", 8 * M * N, 0)
     return out
 
 
 def bn_bwd_stats2(g: torch.Tensor, g2: torch.Tensor, y: torch.Tensor, pro: Pro, pro2: Pro, fold: BNFold):
     """bn_bwd_stats of two upstream gradients through the same BatchNorm + ReLU with their own dropout masks."""
-    lib = _lib.load()
     M, N = y.shape
     out = torch.empty(2, N, dtype=torch.float64, device=y.device)
-    nb = lib.mmg_col_reduce2_ws_bytes(M, N)
-    ws = workspace(nb, y.device)
     _tok = _pb("bn_bwd_stats")
-    check(lib.mmg_bn_bwd_stats2(_p(g), _p(g2), _p(y), _pro(pro), _pro(pro2), _p(fold.mean), _p(fold.rstd),
-                                _p(out, torch.float64), M, N, _p(ws, torch.uint8), ws.numel(), _stream()), "mmg_bn_bwd_stats2")
+    _call("mmg_bn_bwd_stats2", g, g2, y, _pro(pro), _pro(pro2), fold.mean, fold.rstd, out, M, N,
+          ws=_lib.load().mmg_col_reduce2_ws_bytes(M, N))
     _pe(_tok, "bn_bwd_stats", 12 * M * N, 0)
     return out
 
 
 def bn_bwd_apply2(g: torch.Tensor, g2: torch.Tensor, y: torch.Tensor, pro: Pro, pro2: Pro, fold: BNFold, sums, count,
                   dbeta=None, dgamma=None):
-    lib = _lib.load()
     M, N = y.shape
     out = torch.empty_like(y)
     _tok = _pb("bn_bwd_apply")
-    check(lib.mmg_bn_bwd_apply2(_p(g), _p(g2), _p(y), _pro(pro), _pro(pro2), _p(fold.mean), _p(fold.rstd),
-                                _p(sums, torch.float64), 1.0 / float(count), _p(dbeta), _p(dgamma), _p(out), M, N, _stream()),
-          "mmg_bn_bwd_apply2")
+    _call("mmg_bn_bwd_apply2", g, g2, y, _pro(pro), _pro(pro2), fold.mean, fold.rstd, sums, 1.0 / float(count), dbeta,
+          dgamma, out, M, N)
     _pe(_tok, "bn_bwd_apply", 16 * M * N, 0)
     return out
 
 
 def bn_bwd_stats_rows(g_rows: torch.Tensor, y: torch.Tensor, rows: torch.Tensor, pro: Pro, fold: BNFold):
     """bn_bwd_stats for an upstream gradient that is zero outside `rows` (g_rows = its rows, in list order)."""
-    lib = _lib.load()
     N = y.shape[1]
     out = torch.empty(2, N, dtype=torch.float64, device=y.device)
-    ws = workspace(lib.mmg_bn_bwd_stats_rows_ws_bytes(N), y.device)
-    check(lib.mmg_bn_bwd_stats_rows(_p(g_rows), _p(y), _p(rows, torch.int64), rows.numel(), _pro(pro), _p(fold.mean),
-                                    _p(fold.rstd), _p(out, torch.float64), N, _p(ws, torch.uint8), ws.numel(), _stream()),
-          "mmg_bn_bwd_stats_rows")
+    _call("mmg_bn_bwd_stats_rows", g_rows, y, rows, rows.numel(), _pro(pro), fold.mean, fold.rstd, out, N,
+          ws=_lib.load().mmg_bn_bwd_stats_rows_ws_bytes(N))
     return out
 
 
 def bn_bwd_apply_rows(g_rows: torch.Tensor, y: torch.Tensor, rows: torch.Tensor, pro: Pro, dy: torch.Tensor):
     """dy[rows] += scale * g'  -- completes a bn_bwd_apply(None, ...) for the listed (distinct) rows."""
-    lib = _lib.load()
-    check(lib.mmg_bn_bwd_apply_rows(_p(g_rows), _p(y), _p(rows, torch.int64), rows.numel(), _pro(pro), _p(dy),
-                                    y.shape[1], _stream()), "mmg_bn_bwd_apply_rows")
+    _call("mmg_bn_bwd_apply_rows", g_rows, y, rows, rows.numel(), _pro(pro), dy, y.shape[1])
     return dy
 
 
@@ -592,16 +606,13 @@ def bn_bwd_apply(g: Optional[torch.Tensor], y: torch.Tensor, pro: Pro, fold: Opt
                  dbeta=None, dgamma=None, out: Optional[torch.Tensor] = None, accumulate: bool = False):
     """sums: the fp64 [2,N] output of bn_bwd_stats (None in eval mode); dbeta / dgamma ([N] float) receive its rows.
     accumulate: out += (needs out).  g = None: an all-zero upstream gradient (see bn_bwd_apply_rows)."""
-    lib = _lib.load()
     M, N = y.shape
     if accumulate and out is None:
         raise ValueError("accumulate needs out")
     out = torch.empty_like(y) if out is None else out
     _tok = _pb("bn_bwd_apply")
-    check(lib.mmg_bn_bwd_apply(_p(g), _p(y), _pro(pro), _p(fold.mean) if fold else None,
-                               _p(fold.rstd) if fold else None, _p(sums, torch.float64), 1.0 / float(count),
-                               _p(dbeta), _p(dgamma), _p(out), M, N, int(accumulate), _stream()),
-          "mmg_bn_bwd_apply")
+    _call("mmg_bn_bwd_apply", g, y, _pro(pro), fold.mean if fold else None, fold.rstd if fold else None, sums,
+          1.0 / float(count), dbeta, dgamma, out, M, N, int(accumulate))
     _pe(_tok, "bn_bwd_apply", (16 if accumulate else 12) * M * N, 0)
     return out
 
@@ -688,7 +699,6 @@ def _linear_bnbwd(mode: int, y: torch.Tensor, W: torch.Tensor, next_bn: Optional
                   fold: Optional[BNFold] = None, sums=None, count: float = 1.0, dbeta=None, dgamma=None, rn=None):
     """The one call behind linear_bnbwd / linear_bnbwd2 / linear_bnbwd_rows / linear_l2bwd (mmg_linear_bnbwd; the
     descriptor fields as mmg_bnbwd_t names them).  -> (dz, dx), + the next BatchNorm's sums with next_bn."""
-    lib = _lib.load()
     M, K = y.shape
     if W.shape[0] != K:
         raise ValueError(f"{_BNBWD_PROF[mode][0]}: W has {W.shape[0]} rows, y has {K} columns")
@@ -710,8 +720,8 @@ def _linear_bnbwd(mode: int, y: torch.Tensor, W: torch.Tensor, next_bn: Optional
                   *[C.pointer(pc) if pc is not None else None for pc in pcs],
                   _p(fold.mean) if fold else None, _p(fold.rstd) if fold else None, _p(sums, torch.float64),
                   1.0 / float(count), _p(dbeta), _p(dgamma), _p(rn), L2_EPS)
-    check(lib.mmg_linear_bnbwd(C.byref(desc), _p(W), _p(dz), _p(dx), M, N, K, C.byref(nbt) if nbt is not None else None,
-                               C.byref(wt) if wt is not None else None, _stream()), "mmg_linear_bnbwd")
+    _call("mmg_linear_bnbwd", C.byref(desc), W, dz, dx, M, N, K, C.byref(nbt) if nbt is not None else None,
+          C.byref(wt) if wt is not None else None)
     if wgrad is not None:
         _fused_wgrad_done(wgrad, wt)
     _pe(_tok, name, nbytes, (4 if wgrad is not None else 2) * M * N * K)
@@ -771,22 +781,20 @@ def linear_l2bwd(g: torch.Tensor, out: torch.Tensor, rn: torch.Tensor, W: torch.
 
 
 def l2norm_fwd(z: torch.Tensor):
-    lib = _lib.load()
     M, N = z.shape
     out = torch.empty_like(z)
     rn = torch.empty(M, dtype=torch.float32, device=z.device)
     _tok = _pb("l2norm_fwd")
-    check(lib.mmg_l2norm_fwd(_p(z), _p(out), _p(rn), M, N, L2_EPS, _stream()), "mmg_l2norm_fwd")
+    _call("mmg_l2norm_fwd", z, out, rn, M, N, L2_EPS)
     _pe(_tok, "l2norm_fwd", 8 * M * N, 0)
     return out, rn
 
 
 def l2norm_bwd(g: torch.Tensor, out: torch.Tensor, rn: torch.Tensor):
-    lib = _lib.load()
     M, N = out.shape
     dz = torch.empty_like(out)
     _tok = _pb("l2norm_bwd")
-    check(lib.mmg_l2norm_bwd(_p(g), _p(out), _p(rn), _p(dz), M, N, L2_EPS, _stream()), "mmg_l2norm_bwd")
+    _call("mmg_l2norm_bwd", g, out, rn, dz, M, N, L2_EPS)
     _pe(_tok, "l2norm_bwd", 12 * M * N, 0)
     return dz
 
@@ -794,10 +802,8 @@ def l2norm_bwd(g: torch.Tensor, out: torch.Tensor, rn: torch.Tensor):
 def dropout_mask(seed: int, site: int, n_rows: int, width: int, p: float, device, row_offset: int = 0, seed_dev=None):
     """The keep-mask ([n_rows, width] uint8) the kernels draw for (seed, site) -- used to inject the
     same masks into the CPU oracle in parity tests."""
-    lib = _lib.load()
     m = torch.empty(n_rows, width, dtype=torch.uint8, device=device)
-    check(lib.mmg_dropout_mask(seed & 0xFFFFFFFFFFFFFFFF, _p(seed_dev, torch.int64), site, row_offset * width,
-                               n_rows * width, float(p), _p(m, torch.uint8), _stream()), "mmg_dropout_mask")
+    _call("mmg_dropout_mask", seed & 0xFFFFFFFFFFFFFFFF, seed_dev, site, row_offset * width, n_rows * width, float(p), m)
     return m
 
 
@@ -820,7 +826,6 @@ def pair_select(pi, deg, thr: int, dpred=None, io_perm=None, dpred_sorted=None, 
     With `dpred`, positions whose upstream gradient is exactly 0 are dropped (dpred is read through io_perm; if
     `dpred_sorted` ([n] float) is given it receives dpred in pair order).  out: the three tensors of an earlier call, to
     be overwritten in place (a captured step holds their addresses)."""
-    lib = _lib.load()
     n = pi.numel()
     if out is not None:
         sel_low, sel_high, counts = out
@@ -828,12 +833,9 @@ def pair_select(pi, deg, thr: int, dpred=None, io_perm=None, dpred_sorted=None, 
         sel_low = torch.empty(max(n, 1), dtype=torch.int32, device=pi.device)
         sel_high = torch.empty(max(n, 1), dtype=torch.int32, device=pi.device)
         counts = torch.empty(2, dtype=torch.int32, device=pi.device)
-    ws = workspace(lib.mmg_pair_select_ws_bytes(n), pi.device)
     _tok = _pb("pair_select")
-    check(lib.mmg_pair_select(_p(pi, torch.int32), _p(deg, torch.int32), thr, _p(dpred), _p(io_perm, torch.int64),
-                              _p(dpred_sorted), n, _p(sel_low, torch.int32),
-                              _p(sel_high, torch.int32), _p(counts, torch.int32), _p(ws, torch.uint8), ws.numel(),
-                              _stream()), "mmg_pair_select")
+    _call("mmg_pair_select", pi, deg, thr, dpred, io_perm, dpred_sorted, n, sel_low, sel_high, counts,
+          ws=_lib.load().mmg_pair_select_ws_bytes(n))
     _pe(_tok, "pair_select", n * 24)
     return sel_low, sel_high, counts
 
@@ -880,7 +882,6 @@ def pair_head_fwd(head: Head, pi, li, deg, thr: int, want_low: bool, p: float, s
     """sel / n_sel: compacted positions (pair_select) and their device-resident count; n_bound >= that count.
     io_perm: pred is written to pred[io_perm[k]] (the caller's pair order).
     save = pair_saved_alloc(...): also leave what the backward needs per visited pair (mmg_pair_saved_t)."""
-    lib = _lib.load()
     n = pi.numel() if sel is None else int(n_bound)
     if n == 0:
         return
@@ -888,13 +889,9 @@ def pair_head_fwd(head: Head, pi, li, deg, thr: int, want_low: bool, p: float, s
     _pair_sizes(head, pi, li, deg, pair_id, io_perm, pred)
     sv = _pair_saved(save, pi.numel(), n)
     _tok = _pb("pair_head_fwd")
-    check(lib.mmg_pair_head_fwd_save(C.byref(h), _p(pi, torch.int32), _p(li, torch.int32), _p(deg, torch.int32), thr,
-                                     int(want_low), n, pi.numel(), min(int(head.A.shape[0]), deg.numel()),
-                                     int(head.B.shape[0]), float(p), seed & 0xFFFFFFFFFFFFFFFF,
-                                     _p(seed_dev, torch.int64),
-                                     _p(pair_id, torch.int64), _p(pred), _p(sel, torch.int32), _p(n_sel, torch.int32),
-                                     _p(io_perm, torch.int64), C.byref(sv) if sv is not None else None, _stream()),
-          "mmg_pair_head_fwd_save")
+    _call("mmg_pair_head_fwd_save", C.byref(h), pi, li, deg, thr, int(want_low), n, pi.numel(),
+          min(int(head.A.shape[0]), deg.numel()), int(head.B.shape[0]), float(p), seed & 0xFFFFFFFFFFFFFFFF, seed_dev,
+          pair_id, pred, sel, n_sel, io_perm, C.byref(sv) if sv is not None else None)
     _pe(_tok, "pair_head_fwd", n * (12 + (136 if sv is not None else 0)) + 256 * (head.A.shape[0] + head.B.shape[0]),
         n * 2 * (64 * 32 + 32 + 64))
 
@@ -904,7 +901,6 @@ def pair_head_dense_fwd(head: Head, rows, out_rows, out):
     out[out_rows[r], l] = the prediction for (A row rows[r], lab l), l < B.shape[0] -- bitwise what pair_head_fwd returns
     for that pair with p = 0.  rows / out_rows: int32 [n]; out: fp32 [n_out, W] with W >= the number of labs (columns
     beyond it and unlisted rows are left as they are).  Returns out."""
-    lib = _lib.load()
     n = rows.numel()
     if out_rows.numel() != n:
         raise ValueError(f"pair_head_dense_fwd: out_rows has {out_rows.numel()} entries, rows has {n}")
@@ -917,9 +913,8 @@ def pair_head_dense_fwd(head: Head, rows, out_rows, out):
         return out
     h = head.c()
     _tok = _pb("pair_head_dense_fwd")
-    check(lib.mmg_pair_head_dense_fwd(C.byref(h), _p(rows, torch.int32), _p(out_rows, torch.int32), n,
-                                      int(head.A.shape[0]), n_labs, _p(out), int(out.shape[0]), int(out.shape[1]),
-                                      _stream()), "mmg_pair_head_dense_fwd")
+    _call("mmg_pair_head_dense_fwd", C.byref(h), rows, out_rows, n, int(head.A.shape[0]), n_labs, out, int(out.shape[0]),
+          int(out.shape[1]))
     _pe(_tok, "pair_head_dense_fwd", n * (8 + 256 + 4 * n_labs) + 256 * n_labs, n * n_labs * 2 * (64 * 32 + 32 + 64))
     return out
 
@@ -930,25 +925,20 @@ def pair_head_bwd(head: Head, grads: Head, pi, li, deg, thr: int, want_low: bool
     """`grads` mirrors `head` (dA,dB,dW2,db2,dW3,db3), accumulated in place.
     saved: what pair_head_fwd(..., save=...) of the SAME head, gate, seed and pair arrays left (it must have visited every
     pair this call visits); None = recompute."""
-    lib = _lib.load()
     n = pi.numel() if sel is None else int(n_bound)
     if n == 0:
         return
     h = head.c()
     g = HeadGradT(_p(grads.A), _p(grads.B), _p(grads.W2), _p(grads.b2), _p(grads.W3), _p(grads.b3))
-    ws = workspace(lib.mmg_pair_head_bwd_ws_bytes(n, n_labs), head.A.device)
     _pair_sizes(head, pi, li, deg, pair_id, io_perm, dpred)
     if tuple(grads.A.shape) != tuple(head.A.shape) or tuple(grads.B.shape) != tuple(head.B.shape):
         raise ValueError("pair_head_bwd: gradient tables must have the shapes of A and B")
     sv = _pair_saved(saved, pi.numel(), n)
     _tok = _pb("pair_head_bwd")
-    check(lib.mmg_pair_head_bwd_saved(C.byref(h), C.byref(g), _p(pi, torch.int32), _p(li, torch.int32),
-                                      _p(deg, torch.int32), thr, int(want_low), n, pi.numel(),
-                                      min(int(head.A.shape[0]), deg.numel()), n_labs, float(p), seed & 0xFFFFFFFFFFFFFFFF,
-                                      _p(seed_dev, torch.int64), _p(pair_id, torch.int64), _p(dpred), _p(sel, torch.int32),
-                                      _p(n_sel, torch.int32), _p(io_perm, torch.int64),
-                                      C.byref(sv) if sv is not None else None, _p(ws, torch.uint8), ws.numel(), _stream()),
-          "mmg_pair_head_bwd_saved")
+    _call("mmg_pair_head_bwd_saved", C.byref(h), C.byref(g), pi, li, deg, thr, int(want_low), n, pi.numel(),
+          min(int(head.A.shape[0]), deg.numel()), n_labs, float(p), seed & 0xFFFFFFFFFFFFFFFF, seed_dev, pair_id, dpred,
+          sel, n_sel, io_perm, C.byref(sv) if sv is not None else None,
+          ws=_lib.load().mmg_pair_head_bwd_ws_bytes(n, n_labs))
     _pe(_tok, "pair_head_bwd", n * 12 + 2 * 256 * (head.A.shape[0] + head.B.shape[0]), n * 2 * (4 * 64 * 32))
 
 
@@ -961,17 +951,14 @@ def sup_mask_draw(n: int, fraction: float, device, seed: int = 0, seed_dev=None,
     """The per-epoch supervision subset drawn on the device (mmg_sup_mask_draw; train.py:150-176 of the reference)
     -> (sup float [n], count fp64 [1], inv_den fp64 [1] = 1 / max(count, 1)); the three may be passed in (a captured step
     overwrites them in place).  seed_dev: int64 device tensor whose first element is the seed at run time."""
-    lib = _lib.load()
     if count_only:                       # the size of the subset of ids 0 .. n-1, nothing written per pair
         sup = None
     else:
         sup = torch.empty(max(n, 1), dtype=torch.float32, device=device)[:n] if sup is None else sup
     count = torch.empty(1, dtype=torch.float64, device=device) if count is None else count
     inv_den = torch.empty(1, dtype=torch.float64, device=device) if inv_den is None else inv_den
-    ws = workspace(lib.mmg_sup_mask_ws_bytes(n), device)
-    check(lib.mmg_sup_mask_draw(_p(seed_dev, torch.int64), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(ids, torch.int64), n,
-                                float(fraction), _p(sup) if (n and sup is not None) else None, _p(count, torch.float64),
-                                _p(inv_den, torch.float64), _p(ws, torch.uint8), ws.numel(), _stream()), "mmg_sup_mask_draw")
+    _call("mmg_sup_mask_draw", seed_dev, int(seed) & 0xFFFFFFFFFFFFFFFF, ids, n, float(fraction), sup if n else None,
+          count, inv_den, ws=_lib.load().mmg_sup_mask_ws_bytes(n))
     return sup, count, inv_den
 
 
@@ -980,20 +967,17 @@ def pair_loss(pred, y, w=None, sup=None, inv_den: float = 1.0, loss_type: str = 
     """-> (loss fp64 scalar tensor, dpred [n]) in one pass (mmg_pair_loss).  inv_den_dev: fp64 [1] device tensor that
     overrides inv_den at run time (a captured step whose supervision subset changes size between replays).
     loss_out: fp64 device scalar to write the loss to (a slot of the caller's buffer); want_dpred = False: loss only."""
-    lib = _lib.load()
     n = pred.numel()
     dpred = torch.empty_like(pred) if want_dpred else None
     loss = torch.empty((), dtype=torch.float64, device=pred.device) if loss_out is None else loss_out
     if loss.numel() != 1:
         raise ValueError("pair_loss: loss_out must hold one fp64 value")
-    ws = workspace(lib.mmg_pair_loss_ws_bytes(n), pred.device)
     if loss_type not in LOSS_TYPES:
         raise ValueError(f"Unknown loss type: {loss_type}")            # (model.py:610 of the reference)
     lt = LOSS_TYPES[loss_type]
     _tok = _pb("pair_loss")
-    check(lib.mmg_pair_loss(_p(pred), _p(y), _p(w), _p(sup), n, float(inv_den), _p(inv_den_dev, torch.float64), lt,
-                            _p(dpred), _p(loss, torch.float64),
-                            _p(ws, torch.uint8), ws.numel(), _stream()), "mmg_pair_loss")
+    _call("mmg_pair_loss", pred, y, w, sup, n, float(inv_den), inv_den_dev, lt, dpred, loss,
+          ws=_lib.load().mmg_pair_loss_ws_bytes(n))
     _pe(_tok, "pair_loss", 20 * n)
     return loss, dpred
 
@@ -1022,20 +1006,16 @@ def seg_sums(pred: torch.Tensor, target: torch.Tensor, seg: torch.Tensor, n_seg:
     """Segment sums of the evaluation metrics (mmg_seg_moments + mmg_seg_metrics) -> (sums fp64 [n_seg, 8], adjusted
     predictions or None).  sums[s] = (n, sum|e|, sum e^2, sum t, sum t^2, sum|e/t| over t != 0, count(t != 0), clipped).
     n_sigma > 0: residuals are clipped to mean +- n_sigma * std of their segment first (evaluate.py:417-440)."""
-    lib = _lib.load()
     n = pred.numel()
     dev = pred.device
-    ws = workspace(lib.mmg_seg_reduce_ws_bytes(n, n_seg), dev)
+    nb = _lib.load().mmg_seg_reduce_ws_bytes(n, n_seg)
     moments = None
     if n_sigma > 0:
         moments = torch.empty(n_seg, 3, dtype=torch.float64, device=dev)
-        check(lib.mmg_seg_moments(_p(pred), _p(target), _p(seg, torch.int64), n, n_seg, _p(moments, torch.float64),
-                                  _p(ws, torch.uint8), ws.numel(), _stream()), "mmg_seg_moments")
+        _call("mmg_seg_moments", pred, target, seg, n, n_seg, moments, ws=nb)
     sums = torch.empty(n_seg, 8, dtype=torch.float64, device=dev)
     adj = torch.empty_like(pred) if want_adjusted else None
-    check(lib.mmg_seg_metrics(_p(pred), _p(target), _p(seg, torch.int64), n, n_seg, _p(moments, torch.float64),
-                              float(n_sigma), _p(adj), _p(sums, torch.float64), _p(ws, torch.uint8), ws.numel(), _stream()),
-          "mmg_seg_metrics")
+    _call("mmg_seg_metrics", pred, target, seg, n, n_seg, moments, float(n_sigma), adj, sums, ws=nb)
     return sums, adj
 
 
@@ -1052,7 +1032,6 @@ def vec_sums(jobs):
     """jobs: list of (dst, [src tensors, 1..4]) -- dst = sum of the sources in list order, ONE launch (mmg_vec_sums).
     2-D tensors may be column slices of wider matrices (row stride > columns): the launch that sums gradient
     contributions also splits / joins the halves of an edge head's first-layer weight."""
-    lib = _lib.load()
     arr = (SumJobT * len(jobs))()
     for j, (dst, srcs) in enumerate(jobs):
         if not 1 <= len(srcs) <= 4:
@@ -1073,30 +1052,29 @@ def vec_sums(jobs):
             ld[q] = (views[q + 1][1] or cols) if strided else 0
         arr[j] = SumJobT(_p(dst, name="", contiguous=False), sp, len(srcs), dst.numel(), cols,
                          (views[0][1] or cols) if strided else 0, ld)
-    check(lib.mmg_vec_sums(arr, len(jobs), _stream()), "mmg_vec_sums")
+    _call("mmg_vec_sums", arr, len(jobs))
 
 
 def counters_add(counters, incs):
     """*counters[i] += incs[i] (int64 device scalars) in one launch (mmg_counters_add)."""
-    lib = _lib.load()
     step = _lib.MMG_COUNTERS_MAX
     for i0 in range(0, len(counters), step):
         cs, ins = counters[i0:i0 + step], incs[i0:i0 + step]
         ptrs = (C.c_void_p * len(cs))(*[_p(c, torch.int64) for c in cs])
         inc = (C.c_int64 * len(cs))(*[int(v) for v in ins])
-        check(lib.mmg_counters_add(ptrs, inc, len(cs), _stream()), "mmg_counters_add")
+        _call("mmg_counters_add", ptrs, inc, len(cs))
 
 
 def seed_advance(state: torch.Tensor):
     """state: int64 [2] on the device = (dropout seed the kernels read, stream position); one SplitMix64 step."""
-    check(_lib.load().mmg_seed_advance(_p(state, torch.int64), _stream()), "mmg_seed_advance")
+    _call("mmg_seed_advance", state)
 
 
 def zeros(*shape, device, dtype=torch.float32):
     """torch.zeros through mmg_fill_zero: a zero-fill KERNEL on the current stream (not hipMemsetAsync -- its hipGraph node
     does not reliably replay the recorded pattern on this ROCm: csrc/common.h, profiles/probes/hipgraph_memset_node.py)."""
     t = torch.empty(*shape, device=device, dtype=dtype)
-    check(_lib.load().mmg_fill_zero(_p(t, dtype), t.numel() * t.element_size(), _stream()), "mmg_fill_zero")
+    _call("mmg_fill_zero", _p(t, dtype), t.numel() * t.element_size())          # void*: any dtype
     return t
 
 
@@ -1120,7 +1098,6 @@ class SmallFwd:
 def small_fwd_group(probs: Sequence[SmallFwd]):
     """Runs the problems (same N and K) in ceil(len / MMG_SMALL_MAX) launches; allocates missing outputs; returns the
     outputs."""
-    lib = _lib.load()
     if not probs:
         return []
     K = probs[0].x.shape[1]
@@ -1147,7 +1124,7 @@ def small_fwd_group(probs: Sequence[SmallFwd]):
         for i, p in enumerate(chunk):
             arr[i] = SmallFwdT(_p(p.x, name="x"), _p(p.W, name="W"), _p(p.x2), _p(p.W2), _p(p.bias), _p(p.out),
                                p.x.shape[0], _lin_flags(p.accumulate, p.w_kn))
-        check(lib.mmg_small_fwd_group(arr, len(chunk), N, K, _stream()), "mmg_small_fwd_group")
+        _call("mmg_small_fwd_group", arr, len(chunk), N, K)
     return outs
 
 
@@ -1165,7 +1142,6 @@ class SmallWgrad:
 def small_wgrad_group(probs: Sequence[SmallWgrad]):
     """Runs the problems (same N and K) in ceil(len / MMG_SMALL_MAX) launches; allocates missing outputs; returns
     [(dW, dbias)]."""
-    lib = _lib.load()
     if not probs:
         return []
     N, K = probs[0].dy.shape[1], probs[0].x.shape[1]
@@ -1188,7 +1164,7 @@ def small_wgrad_group(probs: Sequence[SmallWgrad]):
         for i, p in enumerate(chunk):
             arr[i] = SmallWgradT(_p(p.dy) if p.dy.numel() else None, _p(p.x) if p.x.numel() else None, _p(p.dW),
                                  _p(p.dbias), p.dy.shape[0], int(p.accumulate))
-        check(lib.mmg_small_wgrad_group(arr, len(chunk), N, K, _stream()), "mmg_small_wgrad_group")
+        _call("mmg_small_wgrad_group", arr, len(chunk), N, K)
     return res
 
 
@@ -1196,7 +1172,6 @@ def small_bn_act_group(items, training: bool):
     """items: list of (y [M,N], bn module or None, Pro with the activation / dropout fields) -- the per-type epilogue of
     a HeteroConv layer for every small node type in ONE launch (mmg_small_bn_act_group).
     -> list of (out, BNFold or None); the Pro objects get their scale / shift filled in."""
-    lib = _lib.load()
     res = []
     if not items:
         return res
@@ -1225,14 +1200,13 @@ def small_bn_act_group(items, training: bool):
                 fold = BNFold(st[0], st[1], st[2], st[3], M, training)
                 pro.scale, pro.shift = st[0], st[1]
             res.append((out, fold))
-        check(lib.mmg_small_bn_act_group(arr, len(chunk), N, BN_MOMENTUM, BN_EPS, _stream()), "mmg_small_bn_act_group")
+        _call("mmg_small_bn_act_group", arr, len(chunk), N, BN_MOMENTUM, BN_EPS)
     return res
 
 
 def small_bn_bwd_group(items):
     """items: list of (g [M,N], y [M,N], Pro, BNFold or None) -> list of (dy, dbeta or None, dgamma or None)
     (mmg_small_bn_bwd_group: the backward of small_bn_act_group, one launch)."""
-    lib = _lib.load()
     res = []
     if not items:
         return res
@@ -1251,7 +1225,7 @@ def small_bn_bwd_group(items):
                                  int(pro.seed) & 0xFFFFFFFFFFFFFFFF, int(pro.site), int(pro.row_offset),
                                  _p(pro.seed_dev, torch.int64))
             res.append((dy, dbg[0] if dbg is not None else None, dbg[1] if dbg is not None else None))
-        check(lib.mmg_small_bn_bwd_group(arr, len(chunk), N, _stream()), "mmg_small_bn_bwd_group")
+        _call("mmg_small_bn_bwd_group", arr, len(chunk), N)
     return res
 
 
@@ -1264,7 +1238,6 @@ def knn_impute(X, rows, n_neighbors: int, weights: str = "uniform", out=None):
     nearest rows that observe it (nan-Euclidean distance; ties to the lower row index), a lab nobody has stays NaN.
     rows: int32 [n] receiver rows of X; out: fp32 [n, W >= L] (columns L .. W-1 and the rows of out-of-range receivers are
     left as they are; a new out is NaN there).  Returns out."""
-    lib = _lib.load()
     if weights not in KNN_WEIGHTS:
         raise ValueError(f"knn_impute: weights must be 'uniform' or 'distance', got {weights!r}")
     if X.dim() != 2:
@@ -1273,17 +1246,14 @@ def knn_impute(X, rows, n_neighbors: int, weights: str = "uniform", out=None):
         raise ValueError(f"knn_impute: rows must be 1-D, got {list(rows.shape)}")
     N, L = (int(v) for v in X.shape)
     n = rows.numel()
-    px, pr = _p(X, name="X"), _p(rows, torch.int32, "rows")
     if out is None:
         out = torch.full((n, L), float("nan"), dtype=torch.float32, device=X.device)
     elif out.dim() != 2 or out.shape[0] != n or out.shape[1] < L:
         raise ValueError(f"knn_impute: out must be [{n}, >= {L}], got {list(out.shape)}")
-    po = _p(out, name="out")
-    if not (X.device == rows.device == out.device):
+    if len({t.device for t in (X, rows, out) if t.is_cuda}) > 1:         # (a host tensor is refused as one, by the call)
         raise ValueError(f"knn_impute: X, rows and out on different devices ({X.device}, {rows.device}, {out.device})")
-    ws = workspace(lib.mmg_knn_impute_ws_bytes(N, L, n, int(n_neighbors)), X.device)
-    check(lib.mmg_knn_impute(px, N, L, L, pr, n, int(n_neighbors), KNN_WEIGHTS[weights], po, int(out.shape[1]),
-                             _p(ws, torch.uint8), ws.numel(), _stream()), "mmg_knn_impute")
+    _call("mmg_knn_impute", X, N, L, L, rows, n, int(n_neighbors), KNN_WEIGHTS[weights], out, int(out.shape[1]),
+          ws=_lib.load().mmg_knn_impute_ws_bytes(N, L, n, int(n_neighbors)))
     return out
 
 
@@ -1297,27 +1267,20 @@ def order_stats(a: torch.Tensor, ranks: Sequence[int], b: Optional[torch.Tensor]
     """Exact order statistics (mmg_order_stats): the values of the 0-based ranks (host ints, at most MAX_ORDER_RANKS) of a -- or of
     |a - b| formed in fp32 -- in ascending order, NaN last.  -> (fp32 [len(ranks)], int64 [1] NaN count), both on the
     device; nothing synchronises with the host."""
-    lib = _lib.load()
     n = a.numel()
     ranks = [int(r) for r in ranks]
     if not 1 <= len(ranks) <= MAX_ORDER_RANKS:
         raise ValueError(f"order_stats: 1..{MAX_ORDER_RANKS} ranks, got {len(ranks)}")
     if n < 1 or any(r < 0 or r >= n for r in ranks):
         raise ValueError(f"order_stats: ranks {ranks} outside [0, {n})")
-    pa = _p(a, name="a")
-    pb = None
-    if b is not None:
-        pb = _p(b, name="b")
-        if b.numel() != n or b.device != a.device:
-            raise ValueError("order_stats: a and b must have the same length and device")
+    if b is not None and (b.numel() != n or b.device != a.device):
+        raise ValueError("order_stats: a and b must have the same length and device")
     if out is None:
         out = torch.empty(len(ranks), dtype=torch.float32, device=a.device)
     if nan_count is None:
         nan_count = torch.empty(1, dtype=torch.int64, device=a.device)
     rk = (C.c_int64 * len(ranks))(*ranks)
-    ws = workspace(lib.mmg_order_stats_ws_bytes(n), a.device)
-    check(lib.mmg_order_stats(pa, pb, n, rk, len(ranks), _p(out, name="out"), _p(nan_count, torch.int64, "nan_count"),
-                              _p(ws, torch.uint8), ws.numel(), _stream()), "mmg_order_stats")
+    _call("mmg_order_stats", a, b, n, rk, len(ranks), out, nan_count, ws=_lib.load().mmg_order_stats_ws_bytes(n))
     return out, nan_count
 
 
@@ -1327,20 +1290,16 @@ def robust_sums(pred: torch.Tensor, target: torch.Tensor, xs: torch.Tensor, nan_
     target|; lower / upper / p95: (index into xs of x_i, index of x_j, fp32 gamma) of numpy's "linear" percentile.
     -> fp64 [15] on the device: n, sum|r|, sum r^2, sum t, sum t^2, sum smape term, sum|t|, sum winsorised |r|, sum
     clipped r^2, outside count, NaN count, max|r|, lower, upper, p95 (include/mmgnn.h)."""
-    lib = _lib.load()
     n = pred.numel()
     if n < 1 or target.numel() != n:
         raise ValueError(f"robust_sums: pred and target need the same length >= 1, got {n} and {target.numel()}")
     if not (pred.device == target.device == xs.device == nan_count.device):
         raise ValueError("robust_sums: tensors on different devices")
-    pp, pt, px = _p(pred, name="pred"), _p(target, name="target"), _p(xs, name="xs")
     if out is None:
         out = torch.empty(ROBUST_FIELDS, dtype=torch.float64, device=pred.device)
     spec = [_lib.PercentileT(int(lo), int(hi), float(g)) for lo, hi, g in (lower, upper, p95)]
-    ws = workspace(lib.mmg_robust_sums_ws_bytes(n), pred.device)
-    check(lib.mmg_robust_sums(pp, pt, n, px, xs.numel(), _p(nan_count, torch.int64, "nan_count"), *spec,
-                              _p(out, torch.float64, "out"), _p(ws, torch.uint8), ws.numel(), _stream()),
-          "mmg_robust_sums")
+    _call("mmg_robust_sums", pred, target, n, xs, xs.numel(), nan_count, *spec, out,
+          ws=_lib.load().mmg_robust_sums_ws_bytes(n))
     return out
 
 
@@ -1349,20 +1308,17 @@ def split_membership(patient: torch.Tensor, train_mask: torch.Tensor, val_mask: 
     """Patients per split-membership class (mmg_split_membership).  patient: int64 [E]; masks: bool [E].
     -> int64 [10] on the device: [m] for m = 1..7 the patients whose edges fall in exactly the splits of bit mask m
     (1 train, 2 val, 4 test), [8] edges in more than one split, [9] edges in train and in val or test."""
-    lib = _lib.load()
     E = patient.numel()
     masks = (train_mask, val_mask, test_mask)
     if any(m.numel() != E for m in masks):
         raise ValueError("split_membership: every mask needs one entry per edge")
     if any(m.device != patient.device for m in masks):
         raise ValueError("split_membership: tensors on different devices")
-    pp = _p(patient, torch.int64, "patient")
-    pm = [_p(m, torch.bool, "mask") for m in masks]
     if out is None:
         out = torch.empty(SPLIT_FIELDS, dtype=torch.int64, device=patient.device)
-    ws = workspace(lib.mmg_split_membership_ws_bytes(int(n_patients)), patient.device)
-    check(lib.mmg_split_membership(pp, *pm, E, int(n_patients), _p(out, torch.int64, "out"), _p(ws, torch.uint8),
-                                   ws.numel(), _stream()), "mmg_split_membership")
+    _call("mmg_split_membership", patient, *masks, E, int(n_patients), out,
+          names={"train_mask": "mask", "val_mask": "mask", "test_mask": "mask", "counts": "out"},
+          ws=_lib.load().mmg_split_membership_ws_bytes(int(n_patients)))
     return out
 
 
@@ -1391,61 +1347,50 @@ def prep_sort(lab: torch.Tensor, patient: Optional[torch.Tensor], secondary: Opt
     """Stable sort of the rows by (lab * n_patients + patient, secondary) (mmg_prep_sort).  secondary: int64 times
     (INT64_MAX = missing, last), fp64 values (NaN last) or None.  -> (perm int32 [n], group int64 [n] at the sorted
     positions, value[perm] or None); rows with a code out of range come last under the group n_labs * n_patients."""
-    lib = _lib.load()
     n = lab.numel()
     n_patients = int(n_patients) if patient is not None else 1
     _prep_sizes(n, n_patients, n_labs)
-    _p(lab, torch.int64, "lab")                               # host tensors are refused before anything is allocated
-    kind = SORT_BY_TIME
-    ps = None
-    if secondary is not None:
-        if secondary.dtype == torch.float64:
-            kind = SORT_BY_VALUE
-        ps = _p(secondary, secondary.dtype if kind == SORT_BY_VALUE else torch.int64, "secondary")
-        if secondary.numel() != n:
-            raise ValueError("prep_sort: secondary needs one entry per row")
+    kind = SORT_BY_VALUE if secondary is not None and secondary.dtype == torch.float64 else SORT_BY_TIME
+    if secondary is not None and secondary.numel() != n:
+        raise ValueError("prep_sort: secondary needs one entry per row")
     if (patient is not None and patient.numel() != n) or (value is not None and value.numel() != n):
         raise ValueError("prep_sort: every column needs one entry per row")
     perm = torch.empty(n, dtype=torch.int32, device=lab.device)
     group = torch.empty(n, dtype=torch.int64, device=lab.device)
     vs = torch.empty(n, dtype=torch.float64, device=lab.device) if value is not None else None
-    ws = workspace(lib.mmg_prep_sort_ws_bytes(n), lab.device)
-    check(lib.mmg_prep_sort(_p(lab, torch.int64, "lab"), _p(patient, torch.int64, "patient"), ps, kind, n, n_patients,
-                            int(n_labs), _p(value, torch.float64, "value"), _p(perm, torch.int32), _p(group, torch.int64),
-                            _p(vs, torch.float64), _p(ws, torch.uint8), ws.numel(), _stream()), "mmg_prep_sort")
+    # secondary is void*: int64 times or fp64 values, as `kind` says
+    _call("mmg_prep_sort", lab, patient, _p(secondary, torch.float64 if kind == SORT_BY_VALUE else torch.int64, "secondary"),
+          kind, n, n_patients, int(n_labs), value, perm, group, vs, names={"value_src": "value"},
+          ws=_lib.load().mmg_prep_sort_ws_bytes(n))
     return perm, group, vs
+
+
+_SORTED_NAMES = {"group_sorted": "group", "value_sorted": "value"}       # what the refusals of these wrappers call them
 
 
 def lab_stats(group_sorted: torch.Tensor, value_sorted: torch.Tensor, n_patients: int, n_labs: int, out=None):
     """Per-lab n / mean / std (ddof 1) / min / max / rows over a lab-sorted array (mmg_lab_stats) -> fp64
     [n_labs, 9] on the device, the quantile fields NaN."""
-    lib = _lib.load()
     n = value_sorted.numel()
     _prep_sizes(n, n_patients, n_labs)
     if group_sorted.numel() != n:
         raise ValueError("lab_stats: group and value need the same length")
-    _p(value_sorted, torch.float64, "value")
     if out is None:
         out = torch.empty(n_labs, LAB_STAT_FIELDS, dtype=torch.float64, device=value_sorted.device)
-    ws = workspace(lib.mmg_lab_stats_ws_bytes(n_labs), value_sorted.device)
-    check(lib.mmg_lab_stats(_p(group_sorted, torch.int64, "group"), _p(value_sorted, torch.float64, "value"), n,
-                            int(n_patients), int(n_labs), _p(out, torch.float64, "stats"), _p(ws, torch.uint8), ws.numel(),
-                            _stream()), "mmg_lab_stats")
+    _call("mmg_lab_stats", group_sorted, value_sorted, n, int(n_patients), int(n_labs), out, names=_SORTED_NAMES,
+          ws=_lib.load().mmg_lab_stats_ws_bytes(n_labs))
     return out
 
 
 def lab_quantiles(group_sorted: torch.Tensor, value_sorted: torch.Tensor, n_patients: int, n_labs: int,
                   stats: torch.Tensor):
     """q25 / median / q75 of every lab from a (lab, value)-sorted array into stats (mmg_lab_quantiles)."""
-    lib = _lib.load()
     n = value_sorted.numel()
     _prep_sizes(n, n_patients, n_labs)
     if group_sorted.numel() != n or tuple(stats.shape) != (n_labs, LAB_STAT_FIELDS):
         raise ValueError("lab_quantiles: group / value lengths or the stats shape do not match")
-    ws = workspace(lib.mmg_lab_quantiles_ws_bytes(n_labs), value_sorted.device)
-    check(lib.mmg_lab_quantiles(_p(group_sorted, torch.int64, "group"), _p(value_sorted, torch.float64, "value"), n,
-                                int(n_patients), int(n_labs), _p(stats, torch.float64, "stats"), _p(ws, torch.uint8),
-                                ws.numel(), _stream()), "mmg_lab_quantiles")
+    _call("mmg_lab_quantiles", group_sorted, value_sorted, n, int(n_patients), int(n_labs), stats, names=_SORTED_NAMES,
+          ws=_lib.load().mmg_lab_quantiles_ws_bytes(n_labs))
     return stats
 
 
@@ -1453,23 +1398,18 @@ def lab_aggregate(group_sorted: torch.Tensor, value_sorted: torch.Tensor, n_pati
                   outlier_method: Optional[str] = None, threshold: float = 5.0, stats: Optional[torch.Tensor] = None):
     """One value per (patient, lab) segment of the sorted events (mmg_lab_aggregate) -> (patient, lab, value) in (lab,
     patient) order.  Waits for the stream: the pair count comes back to size the results."""
-    lib = _lib.load()
     n = value_sorted.numel()
     _prep_sizes(n, n_patients, n_labs)
     if group_sorted.numel() != n:
         raise ValueError("lab_aggregate: group and value need the same length")
-    _p(value_sorted, torch.float64, "value")
     dev = value_sorted.device
     op = torch.empty(n, dtype=torch.int64, device=dev)
     ol = torch.empty(n, dtype=torch.int64, device=dev)
     ov = torch.empty(n, dtype=torch.float64, device=dev)
     cnt = C.c_int64(0)
-    ws = workspace(lib.mmg_lab_aggregate_ws_bytes(n), dev)
-    check(lib.mmg_lab_aggregate(_p(group_sorted, torch.int64, "group"), _p(value_sorted, torch.float64, "value"), n,
-                                int(n_patients), int(n_labs), AGG_CODES[method], OUTLIER_CODES[outlier_method],
-                                float(threshold), _p(stats, torch.float64, "stats"), _p(op, torch.int64),
-                                _p(ol, torch.int64), _p(ov, torch.float64), C.byref(cnt), _p(ws, torch.uint8), ws.numel(),
-                                _stream()), "mmg_lab_aggregate")
+    _call("mmg_lab_aggregate", group_sorted, value_sorted, n, int(n_patients), int(n_labs), AGG_CODES[method],
+          OUTLIER_CODES[outlier_method], float(threshold), stats, op, ol, ov, C.byref(cnt), names=_SORTED_NAMES,
+          ws=_lib.load().mmg_lab_aggregate_ws_bytes(n))
     k = int(cnt.value)
     return op[:k], ol[:k], ov[:k]
 
@@ -1477,16 +1417,13 @@ def lab_aggregate(group_sorted: torch.Tensor, value_sorted: torch.Tensor, n_pati
 def lab_transform(mode: int, method: int, value: torch.Tensor, lab: Optional[torch.Tensor], stats: torch.Tensor,
                   threshold: float = 0.0, out=None):
     """Element-wise outlier masking / normalise / inverse over the per-lab table (mmg_lab_transform), fp64."""
-    lib = _lib.load()
     n = value.numel()
     n_labs = stats.shape[0]
     if stats.dim() != 2 or stats.shape[1] != LAB_STAT_FIELDS or (lab is not None and lab.numel() != n):
         raise ValueError("lab_transform: stats must be [n_labs, 9] and lab as long as value")
     if out is None:
         out = torch.empty_like(value)
-    check(lib.mmg_lab_transform(mode, method, float(threshold), _p(lab, torch.int64, "lab"),
-                                _p(value, torch.float64, "value"), n, int(n_labs), _p(stats, torch.float64, "stats"),
-                                _p(out, torch.float64, "out"), _stream()), "mmg_lab_transform")
+    _call("mmg_lab_transform", mode, method, float(threshold), lab, value, n, int(n_labs), stats, out)
     return out
 
 
@@ -1504,16 +1441,13 @@ def lab_inverse(value, lab, stats, method: str):
 
 def lab_inverse_matrix(pred: torch.Tensor, stats: torch.Tensor, method: str, out=None):
     """The inverse normalisation of a dense fp32 [n_rows, n_labs] matrix (rows may be strided) (mmg_lab_inverse_matrix)."""
-    lib = _lib.load()
     if pred.dim() != 2 or pred.stride(1) != 1 or pred.shape[1] != stats.shape[0] or stats.shape[1] != LAB_STAT_FIELDS:
         raise ValueError("lab_inverse_matrix: pred must be [n_rows, n_labs] with unit column stride, stats [n_labs, 9]")
     pp = _p(pred, torch.float32, "pred", contiguous=False)
     if out is None:
         out = torch.empty(pred.shape, dtype=torch.float32, device=pred.device)
-    check(lib.mmg_lab_inverse_matrix(NORM_CODES[method], pp, pred.shape[0], pred.shape[1],
-                                     pred.stride(0) if pred.shape[0] > 1 else max(pred.stride(0), pred.shape[1]),
-                                     _p(stats, torch.float64, "stats"), _p(out, torch.float32, "out"), out.shape[1],
-                                     _stream()), "mmg_lab_inverse_matrix")
+    _call("mmg_lab_inverse_matrix", NORM_CODES[method], pp, pred.shape[0], pred.shape[1],
+          pred.stride(0) if pred.shape[0] > 1 else max(pred.stride(0), pred.shape[1]), stats, out, out.shape[1])
     return out
 
 
@@ -1527,7 +1461,6 @@ def code_select(code: torch.Tensor, patient: torch.Tensor, n_patients: int, n_co
     (mmg_code_select).  code, patient: int64 device tensors over the rows (out of range = the row is ignored); valid:
     uint8 / bool or None.  -> (n_patients_per_code int64 [n_codes], n_rows_per_code int64 [n_codes], rank int32
     [n_codes], selected uint8 [n_codes], out_rows int32, ascending).  Waits for the stream: the row count comes back."""
-    lib = _lib.load()
     n = code.numel()
     if rows not in SEL_ROWS:
         raise ValueError(f'code_select: rows must be "all" or "first", got {rows!r}')
@@ -1536,9 +1469,6 @@ def code_select(code: torch.Tensor, patient: torch.Tensor, n_patients: int, n_co
                          f"[1, 2^31)")
     if patient.numel() != n or (valid is not None and valid.numel() != n):
         raise ValueError("code_select: every column needs one entry per row")
-    _p(code, torch.int64, "code")                             # host tensors are refused before anything is allocated
-    if valid is not None and valid.dtype == torch.bool:
-        valid = valid.view(torch.uint8)
     dev = code.device
     n_pat = torch.empty(n_codes, dtype=torch.int64, device=dev)
     n_rows = torch.empty(n_codes, dtype=torch.int64, device=dev)
@@ -1546,13 +1476,9 @@ def code_select(code: torch.Tensor, patient: torch.Tensor, n_patients: int, n_co
     selected = torch.empty(n_codes, dtype=torch.uint8, device=dev)
     out_rows = torch.empty(n, dtype=torch.int32, device=dev)
     cnt = C.c_int64(0)
-    ws = workspace(lib.mmg_code_select_ws_bytes(n, int(n_codes)), dev)
-    check(lib.mmg_code_select(_p(code, torch.int64, "code"), _p(patient, torch.int64, "patient"),
-                              _p(valid, torch.uint8, "valid"), n, int(n_patients), int(n_codes), int(min_patient_count),
-                              -1 if top_k is None else int(top_k), SEL_ROWS[rows], _p(n_pat, torch.int64),
-                              _p(n_rows, torch.int64), _p(rank, torch.int32), _p(selected, torch.uint8),
-                              _p(out_rows, torch.int32), C.byref(cnt), _p(ws, torch.uint8), ws.numel(), _stream()),
-          "mmg_code_select")
+    _call("mmg_code_select", code, patient, valid, n, int(n_patients), int(n_codes), int(min_patient_count),
+          -1 if top_k is None else int(top_k), SEL_ROWS[rows], n_pat, n_rows, rank, selected, out_rows, C.byref(cnt),
+          ws=_lib.load().mmg_code_select_ws_bytes(n, int(n_codes)))
     return n_pat, n_rows, rank, selected, out_rows[:int(cnt.value)]
 
 
@@ -1599,15 +1525,12 @@ def pair_analysis(pred: torch.Tensor, target: torch.Tensor, lab: Optional[torch.
     """One read of the pairs (mmg_pair_analysis) -> (lab_sums fp64 [n_labs, 9] or None, bin_sums fp64 [n_bins, 2] or
     None), on the device.  lab / patient: int64 or int32 [n]; deg: int32 [n_patients]; bin_edges: ascending host floats,
     bin j = [edges[j], edges[j + 1]).  Fixed-order fp64 sums: bitwise reproducible; nothing synchronises with the host."""
-    lib = _lib.load()
     n, dev, pl, pp, ib, n_labs, n_bins, ed = _an_args("pair_analysis", pred, target, patient, lab, n_labs, deg, bin_edges)
     lab_sums = torch.empty(n_labs, AN_LAB_FIELDS, dtype=torch.float64, device=dev) if n_labs else None
     bin_sums = torch.empty(n_bins, AN_BIN_FIELDS, dtype=torch.float64, device=dev) if n_bins else None
-    ws = workspace(lib.mmg_pair_analysis_ws_bytes(n, n_labs, n_bins), dev)
-    check(lib.mmg_pair_analysis(_p(pred, name="pred"), _p(target, name="target"), pp if n_bins else None, pl, ib, n, n_labs,
-                                _p(deg, torch.int32, "deg") if n_bins else None, deg.numel() if n_bins else 0, ed, n_bins,
-                                _p(lab_sums, torch.float64), _p(bin_sums, torch.float64), _p(ws, torch.uint8), ws.numel(),
-                                _stream()), "mmg_pair_analysis")
+    _call("mmg_pair_analysis", pred, target, pp if n_bins else None, pl, ib, n, n_labs, deg if n_bins else None,
+          deg.numel() if n_bins else 0, ed, n_bins, lab_sums, bin_sums,
+          ws=_lib.load().mmg_pair_analysis_ws_bytes(n, n_labs, n_bins))
     return lab_sums, bin_sums
 
 
@@ -1617,7 +1540,6 @@ def pair_calibrated_abs(pred: Optional[torch.Tensor], target: torch.Tensor, lab:
                         bin_mean: Optional[torch.Tensor] = None):
     """The second read (mmg_pair_calibrated_abs) -> (lab_abs fp64 [n_labs] = sum |(a t + b) - t| with fp32 a, b [n_labs],
     or None; bin_sq fp64 [n_bins] = sum (|p - t| - bin_mean)^2, or None), on the device."""
-    lib = _lib.load()
     n, dev, pl, pp, ib, n_labs, n_bins, ed = _an_args("pair_calibrated_abs", pred, target, patient, lab,
                                                       a.numel() if a is not None else 0, deg, bin_edges)
     if n_labs and (b is None or b.numel() != n_labs):
@@ -1626,14 +1548,9 @@ def pair_calibrated_abs(pred: Optional[torch.Tensor], target: torch.Tensor, lab:
         raise ValueError("pair_calibrated_abs: degree bins need pred and one mean per bin")
     lab_abs = torch.empty(n_labs, dtype=torch.float64, device=dev) if n_labs else None
     bin_sq = torch.empty(n_bins, dtype=torch.float64, device=dev) if n_bins else None
-    ws = workspace(lib.mmg_pair_calibrated_abs_ws_bytes(n, n_labs, n_bins), dev)
-    check(lib.mmg_pair_calibrated_abs(_p(pred, name="pred") if n_bins else None, _p(target, name="target"),
-                                      pp if n_bins else None, pl, ib, n, n_labs, _p(a, name="a") if n_labs else None,
-                                      _p(b, name="b") if n_labs else None, _p(deg, torch.int32, "deg") if n_bins else None,
-                                      deg.numel() if n_bins else 0, ed, n_bins,
-                                      _p(bin_mean, torch.float64, "bin_mean") if n_bins else None,
-                                      _p(lab_abs, torch.float64), _p(bin_sq, torch.float64), _p(ws, torch.uint8), ws.numel(),
-                                      _stream()), "mmg_pair_calibrated_abs")
+    _call("mmg_pair_calibrated_abs", pred if n_bins else None, target, pp if n_bins else None, pl, ib, n, n_labs,
+          a if n_labs else None, b if n_labs else None, deg if n_bins else None, deg.numel() if n_bins else 0, ed, n_bins,
+          bin_mean if n_bins else None, lab_abs, bin_sq, ws=_lib.load().mmg_pair_calibrated_abs_ws_bytes(n, n_labs, n_bins))
     return lab_abs, bin_sq
 
 
@@ -1657,13 +1574,10 @@ def centered_gram(x: torch.Tensor):
     """Column means and the centred Gram matrix of fp32 [n, D] rows (mmg_centered_gram) -> (mean fp64 [D], S fp64
     [D, D] = sum_i (x_i - mean)(x_i - mean)^T, exactly symmetric), on the device.  Fixed-order fp64 sums: bitwise
     reproducible; nothing synchronises with the host."""
-    lib = _lib.load()
     px, n, D, ld = _rows_matrix(x, "x")
     mean = torch.empty(D, dtype=torch.float64, device=x.device)
     gram = torch.empty(D, D, dtype=torch.float64, device=x.device)
-    ws = workspace(lib.mmg_centered_gram_ws_bytes(n, D), x.device)
-    check(lib.mmg_centered_gram(px, n, D, ld, _p(mean, torch.float64), _p(gram, torch.float64), _p(ws, torch.uint8),
-                                ws.numel(), _stream()), "mmg_centered_gram")
+    _call("mmg_centered_gram", px, n, D, ld, mean, gram, ws=_lib.load().mmg_centered_gram_ws_bytes(n, D))
     return mean, gram
 
 
@@ -1671,7 +1585,6 @@ def project_rows(x: torch.Tensor, mean: torch.Tensor, comps: torch.Tensor, scale
                  out: Optional[torch.Tensor] = None):
     """out[i, c] = scale[c] * sum_d (x[i, d] - mean[d]) * comps[c, d] (mmg_project_rows): fp64 sums rounded once to
     fp32 [n, k].  mean fp64 [D], comps fp64 [k, D], scale fp64 [k] or None, all on the device."""
-    lib = _lib.load()
     px, n, D, ld = _rows_matrix(x, "x")
     if comps.dim() != 2 or comps.shape[1] != D or mean.numel() != D:
         raise ValueError(f"project_rows: comps must be [k, {D}] and mean [{D}]")
@@ -1682,16 +1595,13 @@ def project_rows(x: torch.Tensor, mean: torch.Tensor, comps: torch.Tensor, scale
         out = torch.empty(n, k, dtype=torch.float32, device=x.device)
     elif out.shape != (n, k):
         raise ValueError(f"project_rows: out must be [{n}, {k}]")
-    check(lib.mmg_project_rows(px, n, D, ld, _p(mean, torch.float64, "mean"), _p(comps, torch.float64, "comps"),
-                               _p(scale, torch.float64, "scale"), k, _p(out, torch.float32, "out"), k, None, 0,
-                               _stream()), "mmg_project_rows")
+    _call("mmg_project_rows", px, n, D, ld, mean, comps, scale, k, out, k)          # takes no workspace: ws = NULL
     return out
 
 
 def grid2d(y: torch.Tensor, ex: torch.Tensor, ey: torch.Tensor, w: Optional[torch.Tensor] = None):
     """numpy.histogram2d of the fp32 points y [n, 2] over explicit fp64 device edges ex [gx + 1], ey [gy + 1]
     (mmg_grid2d) -> (count int64 [gx, gy], wsum int64 [gx, gy] = the sum of the int32 weights w per cell, or None)."""
-    lib = _lib.load()
     if y.dim() != 2 or y.shape[1] < 2:
         raise ValueError("grid2d: y must be [n, >= 2]")
     py, n, _, ld = _rows_matrix(y, "y")
@@ -1700,7 +1610,5 @@ def grid2d(y: torch.Tensor, ex: torch.Tensor, ey: torch.Tensor, w: Optional[torc
         raise ValueError(f"grid2d: {w.numel()} weights for {n} points")
     count = torch.empty(max(gx, 0), max(gy, 0), dtype=torch.int64, device=y.device)
     wsum = torch.empty_like(count) if w is not None else None
-    check(lib.mmg_grid2d(py, max(ld, 2), _p(w, torch.int32, "w"), n, _p(ex, torch.float64, "ex"),
-                         _p(ey, torch.float64, "ey"), gx, gy, _p(count, torch.int64), _p(wsum, torch.int64), None, 0,
-                         _stream()), "mmg_grid2d")
+    _call("mmg_grid2d", py, max(ld, 2), w, n, ex, ey, gx, gy, count, wsum)          # takes no workspace: ws = NULL
     return count, wsum

@@ -17,7 +17,7 @@ from typing import List
 import torch
 
 from . import _lib
-from .ops import _stream
+from .ops import _call
 
 
 class Adam(torch.optim.Adam):
@@ -91,7 +91,6 @@ class Adam(torch.optim.Adam):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = _lib.load()
         if len(self._flat) != len(self.param_groups):
             raise _lib.MmgError("mmgnn.optim.Adam: param_groups were edited behind add_param_group")
         for group, fl in zip(self.param_groups, self._flat):
@@ -108,10 +107,8 @@ class Adam(torch.optim.Adam):
                     raise _lib.MmgError("mmgnn.optim.Adam: gradients must be contiguous fp32 device tensors")
                 gp[i] = g.data_ptr()
             self._upload_hyper(group, fl)
-            _lib.check(lib.mmg_adam_step_dev(C.c_void_p(fl["p"].data_ptr()), C.c_void_p(fl["m"].data_ptr()),
-                                             C.c_void_p(fl["v"].data_ptr()), gp, fl["offs"], len(ps),
-                                             C.c_void_p(fl["hyper"].data_ptr()), C.c_void_p(fl["step"].data_ptr()),
-                                             C.c_void_p(fl["ticket"].data_ptr()), _stream()), "mmg_adam_step_dev")
+            _call("mmg_adam_step_dev", fl["p"], fl["m"], fl["v"], gp, fl["offs"], len(ps), fl["hyper"], fl["step"],
+                  fl["ticket"])
         return loss
 
     def load_state_dict(self, state_dict):
