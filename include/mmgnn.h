@@ -133,7 +133,9 @@ typedef struct {
   float drop_p;            /* 0 = no dropout */
   uint64_t seed;           /* dropout RNG: keep(seed, site, global_row*K + k) */
   uint32_t site;
-  int64_t row_offset;      /* global index of row 0 (patient sharding) */
+  int64_t row_offset;      /* global index of row 0 (patient sharding), >= 0.  The element index (row_offset + row) * K + k
+                              is honoured as a full 64-bit number by every kernel that draws a mask; it must stay
+                              below 2^63, i.e. (row_offset + M) * K < 2^63 (tested up to 2^51) */
   const uint64_t* seed_ptr;/* optional DEVICE pointer: when non-NULL the seed is read from it at run time
                               (lets a captured hipGraph draw fresh masks on every replay) */
 } mmg_prologue_t;
@@ -411,7 +413,8 @@ int mmg_pair_loss(const float* pred, const float* y, const float* w, const float
  * advances).  count / inv_den (nullable, DEVICE doubles) receive the subset size and 1 / max(size, 1) -- the normaliser
  * mmg_pair_loss reads through inv_den_ptr.  sup == NULL: count only -- a patient-sharded rank draws the mask of ITS pairs
  * (ids = their global ids) and counts the subset of ALL n_global pairs (ids NULL) itself: the draw is a pure function of
- * (seed, id), so every rank gets the global size without a collective. */
+ * (seed, id), so every rank gets the global size without a collective.  ids are non-negative and honoured as full
+ * 64-bit element indices (any value below 2^63; tested up to 2^40). */
 size_t mmg_sup_mask_ws_bytes(int64_t n);
 int mmg_sup_mask_draw(const uint64_t* seed_ptr, uint64_t seed, const int64_t* ids, int64_t n, float fraction, float* sup,
                       double* count, double* inv_den, void* ws, size_t ws_bytes, void* stream);
@@ -450,7 +453,9 @@ typedef struct {
  * (want_low = 1: deg[pi] < degree_threshold -> tabular_mlp; 0: the GNN edge_predictor);
  * other pairs are left untouched in pred / contribute nothing to the gradients.
  * pair_id (nullable) = original position of each pair, used only to key the dropout RNG so that
- * a permuted (patient-sorted) pair list draws the same masks.  seed_ptr (nullable, device): overrides
+ * a permuted (patient-sorted) pair list draws the same masks: the first layer draws elements pair_id * 64 + unit, the
+ * second pair_id * 32 + unit, as full 64-bit indices -- any non-negative pair_id with pair_id * 64 < 2^63 (below 2^57;
+ * tested up to 2^40).  seed_ptr (nullable, device): overrides
  * `seed` at run time (hipGraph replays).
  * io_perm (nullable, device): the kernels work on a patient-SORTED pair list; io_perm[k] is the position of sorted
  * pair k in the caller's order -- pred is written to pred[io_perm[k]] and dpred read from dpred[io_perm[k]], so no

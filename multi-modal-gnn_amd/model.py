@@ -28,6 +28,22 @@ from .ops import Pro
 
 EdgeType = Tuple[str, str, str]
 SITE_CONV = 16
+SITE_H1 = 64                 # csrc/pairs.hip: the pair heads draw sites 64 and 65
+SITE_TYPES_PER_LAYER = 8     # conv layer l, node type ti draws site SITE_CONV + SITE_TYPES_PER_LAYER * l + ti
+
+
+def check_dropout_sites(num_layers: int, n_node_types: int):
+    """Every dropout site of a step must be its own stream of the counter RNG.  The encoder draws sites 0..3, conv layer l
+    and node type ti site SITE_CONV + 8 * l + ti, the pair heads 64 and 65: more than 8 node types would run a layer's
+    sites into the next layer's, more than 6 layers the conv sites into the heads' (two layers sharing a mask silently
+    train another model)."""
+    if n_node_types > SITE_TYPES_PER_LAYER:
+        raise ValueError(f"{n_node_types} node types: the dropout sites of a conv layer hold {SITE_TYPES_PER_LAYER}")
+    if SITE_CONV + SITE_TYPES_PER_LAYER * num_layers > SITE_H1:
+        raise ValueError(f"num_layers={num_layers}: the dropout sites of the conv layers would run into the pair heads' "
+                         f"(site {SITE_H1}); at most {(SITE_H1 - SITE_CONV) // SITE_TYPES_PER_LAYER} layers")
+
+
 # Vocab-side work of a layer on a side stream beside the patient-side kernels: "auto" = from 16 k patient rows up (below
 # that every kernel is launch-sized and the fork / join events cost more than they hide), "off" = one stream, "on" = always.
 OVERLAP_MODE = "auto"
@@ -156,6 +172,7 @@ class HeteroRGCN(nn.Module):
         node_types, edge_types = metadata
         self._node_types = list(node_types)
         self._edge_types = [tuple(e) for e in edge_types]
+        check_dropout_sites(num_layers, len(self._node_types))
 
         self.embeddings = nn.ModuleDict()          # filled by _init_embeddings (lazy, model.py:180-204)
         self.embedding_dims = {}
@@ -423,6 +440,7 @@ class _Run:
             if getattr(model, "_side_stream", None) is None:
                 model._side_stream = torch.cuda.Stream(device=self.dev)
             self.side = model._side_stream
+        check_dropout_sites(model.num_layers, len(self.plan.node_types))     # (ti is the index in the PLAN's type list)
         for t in self.plan.node_types:
             if t not in model.embeddings:
                 raise KeyError(f"no embedding table for node type '{t}': call model._init_embeddings(data) first")
