@@ -12,10 +12,9 @@
 //  patient row), k_gather (L2-served), k_scatter_mfma (fp32 matrix cores on an integer count tile),
 //  k_scatter_atomic (> 512 padded vocab rows).
 #include "common.h"
+#include "mma.h"
 
 namespace {
-
-typedef float f32x4s __attribute__((ext_vector_type(4)));
 
 struct RelDev {
   const int32_t* rowptr; const int32_t* col; const float* rowscale; const float* colscale;
@@ -104,9 +103,9 @@ __global__ __launch_bounds__(GL_THREADS) void k_gather_lds(RelPack rp, int64_t n
     const int n4 = R.n_cols * (DC / 4);
     for (int i = tid; i < n4; i += GL_THREADS) {
       const int c = i / (DC / 4), q = i - c * (DC / 4);
-      f32x4s v = *reinterpret_cast<const f32x4s*>(R.table + (size_t)c * D + d0 + q * 4);
+      f32x4 v = *reinterpret_cast<const f32x4*>(R.table + (size_t)c * D + d0 + q * 4);
       if (R.colscale) v *= R.colscale[c];
-      *reinterpret_cast<f32x4s*>(tab + (size_t)(R.acc_off + c) * DC + q * 4) = v;
+      *reinterpret_cast<f32x4*>(tab + (size_t)(R.acc_off + c) * DC + q * 4) = v;
     }
   }
   __syncthreads();
@@ -196,8 +195,6 @@ __global__ __launch_bounds__(GL_THREADS) void k_gather_lds(RelPack rp, int64_t n
   }
 }
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 // ------------------------------------------------------------------------------ scatter
 // out[v, :] = sum_rows Ind[row, v] * x[row, :]  is a tall-skinny product  Ind^T [V x P] . x [P x D].
 // LDS float atomics (ds_add_f32) were measured at ~0.3 adds/clk/CU on gfx950 -- 40x off the HBM
@@ -208,7 +205,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // relations ride along in the same pass so that x is read from HBM once.
 // Each workgroup owns a contiguous row chunk and ALL vocab tiles (accumulators stay in registers for
 // the whole chunk), writes one partial slab; k_scatter_reduce sums the slabs in fixed order.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int SC_ROWS = 32;     // patient rows per LDS stage (= MFMA K extent per stage)
 
 struct ScatterPlan {
@@ -273,13 +269,13 @@ __global__ __launch_bounds__(256) void k_scatter_mfma(RelPack rp, int64_t n_rows
 
   for (int64_t r0 = r_beg; r0 < r_end; r0 += SC_ROWS) {
     __syncthreads();                       // previous stage's MFMA reads are done
-    const f32x4s z = {0.f, 0.f, 0.f, 0.f};
-    for (int i = tid; i < SC_ROWS * NTOT / 4; i += 256) reinterpret_cast<f32x4s*>(&Cs[0][0])[i] = z;
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    for (int i = tid; i < SC_ROWS * NTOT / 4; i += 256) reinterpret_cast<f32x4*>(&Cs[0][0])[i] = z;
     for (int i = tid; i < SC_ROWS * DC / 4; i += 256) {
       const int r = i / (DC / 4), c4 = i - r * (DC / 4);
-      f32x4s v = z;
-      if (r0 + r < r_end) v = *reinterpret_cast<const f32x4s*>(x + (size_t)(r0 + r) * D + d0 + c4 * 4);
-      *reinterpret_cast<f32x4s*>(&Xs[r][c4 * 4]) = v;
+      f32x4 v = z;
+      if (r0 + r < r_end) v = *reinterpret_cast<const f32x4*>(x + (size_t)(r0 + r) * D + d0 + c4 * 4);
+      *reinterpret_cast<f32x4*>(&Xs[r][c4 * 4]) = v;
     }
     if (HAS_RS) {
       for (int i = tid; i < NT * SC_ROWS; i += 256) {
@@ -334,7 +330,6 @@ __global__ __launch_bounds__(256) void k_scatter_mfma(RelPack rp, int64_t n_rows
     }
 }
 
-
 // ------------------------------------------------------------------------------ scatter on the bf16 matrix cores
 // Simple relations (MMG_REL_SIMPLE: no repeated (patient, item) pair -- the reference's frames are de-duplicated)
 // have a 0/1 indicator, exact in bf16, and an fp32 feature splits exactly into three bf16 pieces (8 significant
@@ -353,71 +348,17 @@ __global__ __launch_bounds__(256) void k_scatter_mfma(RelPack rp, int64_t n_rows
 // 42 us -- the kernel runs at the pace of its 1.38 M matrix instructions, not of HBM (94 MB, 2.0 TB/s); by the issue-rate
 // probe (profiles/probes/mfma_rate.hip: 32 clocks per MFMA per wave) their pure issue time is ~21 us.
 constexpr int SB_SR = 64;                    // patient rows per stage = bits per mask word (4 k-steps of 16)
-
-__device__ inline void split8(const float* v, bf16x8& p0, bf16x8& p1, bf16x8& p2) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 a = (__bf16)v[j];
-    const float r1 = v[j] - (float)a;
-    const __bf16 b = (__bf16)r1;
-    p0[j] = a; p1[j] = b; p2[j] = (__bf16)(r1 - (float)b);
-  }
-}
-
-typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2s __attribute__((ext_vector_type(2)));
-// the three bf16 pieces of 8 values by TRUNCATION (upper 16 bits of a, of a - hi, of a - hi - mid: each exactly a bf16,
-// their sum is a): v_perm / v_and / v_sub only.  Element j of a piece sits in half j & 1 of dword j / 2 = the MFMA
-// operand order.
-__device__ __forceinline__ void split8_tr(const float* v, u32x4s& p0, u32x4s& p1, u32x4s& p2) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const unsigned a0 = __builtin_bit_cast(unsigned, v[2 * j]), a1 = __builtin_bit_cast(unsigned, v[2 * j + 1]);
-    p0[j] = __builtin_amdgcn_perm(a1, a0, 0x07060302u);
-    const float r0 = v[2 * j] - __builtin_bit_cast(float, a0 & 0xFFFF0000u);
-    const float r1 = v[2 * j + 1] - __builtin_bit_cast(float, a1 & 0xFFFF0000u);
-    const unsigned b0 = __builtin_bit_cast(unsigned, r0), b1 = __builtin_bit_cast(unsigned, r1);
-    p1[j] = __builtin_amdgcn_perm(b1, b0, 0x07060302u);
-    const float s0 = r0 - __builtin_bit_cast(float, b0 & 0xFFFF0000u);
-    const float s1 = r1 - __builtin_bit_cast(float, b1 & 0xFFFF0000u);
-    p2[j] = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, s1), __builtin_bit_cast(unsigned, s0), 0x07060302u);
-  }
-}
-
-// (the scatter kernels' split since round 3: 44 plain vector instructions per 8 values instead of 56 with conversions;
-//  same-box A/B 44.9 -> 44.4 us without, 55.7 -> 54.4 us with a rowscale)
-__device__ inline void split8x(const float* v, bf16x8& p0, bf16x8& p1, bf16x8& p2) {
-  u32x4s q0, q1, q2;
-  split8_tr(v, q0, q1, q2);
-  p0 = __builtin_bit_cast(bf16x8, q0); p1 = __builtin_bit_cast(bf16x8, q1); p2 = __builtin_bit_cast(bf16x8, q2);
-}
+// (the splits -- mmg_split8, split8_tr / split8x by truncation, split8_h2 -- and the three-product sequence MMG_X3: mma.h)
 
 // ---- two f16 pieces of x * 2^e (round 4): 18 instead of 27 matrix instructions per 16 patients x 9 item tiles.
-// hi = f16(X), lo = f16(X - hi) with X = x * 2^e: 22 significant bits, relative error <= 2^-22 of X while 2^-3 <= |X| < 65504;
-// below that the residual is an f16 denormal (absolute error 2^-25 in units of X).  The scale is a power of two chosen BY THE
+// The pieces and their error bound: split8_h2 (mma.h).  The scale is a power of two chosen BY THE
 // WAVE from the data it streams (block floating point over the wave's row range): e starts at whatever brings the first
 // 16 x 32 block's largest magnitude to [2^12, 2^13); a later block with an element beyond 2^15 / 2^e lowers e, the
 // accumulators are multiplied by 2^(e_new - e_old) and that block is split again -- so every piece is finite for finite x,
 // whatever its range, and an element's error is <= 2^-22 of itself or 2^-37 of the largest magnitude seen so far in the
 // strip, whichever is larger: the error of an fp32 running sum, not of a format with fewer bits.  A NaN or an infinity in x
 // gives NaN in the sums it enters (fp32 index_add_: NaN, or +-inf for an infinity alone).
-typedef _Float16 f16x8s __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2s __attribute__((ext_vector_type(2)));
-typedef float f32x2s __attribute__((ext_vector_type(2)));
 constexpr int H2_E_INIT = 120, H2_E_MIN = -110;
-
-__device__ __forceinline__ void split8_h2(const float* v, float scale, f16x8s& p0, f16x8s& p1) {
-  u32x4s q0, q1;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const f32x2s a = {v[2 * j] * scale, v[2 * j + 1] * scale};
-    const f16x2s hh = __builtin_convertvector(a, f16x2s);
-    const f32x2s r = {a[0] - (float)hh[0], a[1] - (float)hh[1]};
-    const f16x2s ll = __builtin_convertvector(r, f16x2s);
-    q0[j] = __builtin_bit_cast(unsigned, hh); q1[j] = __builtin_bit_cast(unsigned, ll);
-  }
-  p0 = __builtin_bit_cast(f16x8s, q0); p1 = __builtin_bit_cast(f16x8s, q1);
-}
 
 __device__ __forceinline__ float absmax8(const float* v) {      // (fmaxf drops a NaN operand: a NaN never moves the scale)
   float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fabsf(v[2]));
@@ -444,9 +385,8 @@ __device__ __forceinline__ float absmax8_finite(const float* v) {
 struct H2Scale {
   int e, e_floor, seen;
   float sc, lim;                                       // 2^e, 2^(15 - e): wave-uniform
-  __device__ __forceinline__ void set(int en) { e = en; sc = h2_pow2_(en); lim = h2_pow2_(15 - en); }
+  __device__ __forceinline__ void set(int en) { e = en; sc = mmg_pow2(en); lim = mmg_pow2(15 - en); }
   __device__ __forceinline__ void init() { seen = 0; e_floor = H2_E_MIN; set(H2_E_INIT); }
-  static __device__ __forceinline__ float h2_pow2_(int k) { return __builtin_bit_cast(float, (unsigned)(k + 127) << 23); }
 };
 constexpr int H2_E_DROP = 10;
 
@@ -469,9 +409,6 @@ __device__ __forceinline__ int h2_decide(float m, H2Scale& hs, int& d) {
     d = en - hs.e; hs.e_floor = en - H2_E_DROP; hs.set(en); return 0;
   }
   return 1;
-}
-__device__ __forceinline__ float h2_pow2(int e) {          // 2^e for |e| <= 126 (wave-uniform)
-  return __builtin_bit_cast(float, (unsigned)(e + 127) << 23);
 }
 
 // The strip layout (round 2): a workgroup owns a 32-column STRIP of x for a range of rows; four row quarters stream it and
@@ -506,8 +443,7 @@ __device__ __forceinline__ void strip_main_h(const RelPack& rp, int64_t n_rows, 
   const int64_t r_beg = (int64_t)s_beg * SB_SR;
   const int64_t rows_here = ns <= 0 ? 0 : ((n_rows - r_beg) < (int64_t)ns * SB_SR ? (n_rows - r_beg) : (int64_t)ns * SB_SR);
   const float* xw = x + (size_t)r_beg * D + d0;
-  const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(xw), 0, rows_here > 0 ? (int)((rows_here * D - d0) * 4) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t xsrc = mmg_rsrc(xw, rows_here > 0 ? (int)((rows_here * D - d0) * 4) : 0);
   const unsigned row_bytes = (unsigned)D * 4u;
   const unsigned voff0 = (unsigned)(8 * h) * row_bytes + (unsigned)l31 * 4u;
   float xq[RING][8];
@@ -555,20 +491,20 @@ __device__ __forceinline__ void strip_main_h(const RelPack& rp, int64_t n_rows, 
     const unsigned w = (kq & 2) ? (unsigned)(mw[t] >> 32) : (unsigned)mw[t];
     return (kq & 1) ? ((w >> 16) & lm[t]) : (w & lm[t]);
   };
-  auto make_af = [&](const uint64_t* mw, int kq, f16x8s* af) {
+  auto make_af = [&](const uint64_t* mw, int kq, f16x8* af) {
 #pragma unroll
     for (int t = 0; t < NT; ++t)
-      af[t] = *reinterpret_cast<const f16x8s*>(reinterpret_cast<const unsigned char*>(&lut[0][0]) + frag_off(mw, kq, t));
+      af[t] = *reinterpret_cast<const f16x8*>(reinterpret_cast<const unsigned char*>(&lut[0][0]) + frag_off(mw, kq, t));
   };
   uint64_t mc[NT], mn[NT];
   loadm(0, mc);
   __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0): the loop is entered with no load in flight
-  f16x8s afc[NT], bc[2];
+  f16x8 afc[NT], bc[2];
   make_af(mc, 0, afc);
   H2Scale hs;
   hs.init();
   unsigned long long over = ~0ull;                     // block 0 goes through the decision like any block that does not fit
-  bc[0] = bc[1] = f16x8s{0, 0, 0, 0, 0, 0, 0, 0};
+  bc[0] = bc[1] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
   for (int u = 0; u < ns; ++u) {
 #pragma unroll
     for (int kq = 0; kq < 4; ++kq) {
@@ -586,14 +522,12 @@ __device__ __forceinline__ void strip_main_h(const RelPack& rp, int64_t n_rows, 
 #pragma unroll
           for (int t = 0; t < NT; ++t) {
             const bf16x8 ab = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(&lutb[0][0]) + frag_off(mc, kq, t));
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ab, p0, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ab, p1, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ab, p2, acc[t], 0, 0, 0);
+            MMG_X3(acc[t], ab, p0, p1, p2);
           }
-          bc[0] = bc[1] = f16x8s{0, 0, 0, 0, 0, 0, 0, 0};      // (the f16 products of this k-step add nothing)
+          bc[0] = bc[1] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};      // (the f16 products of this k-step add nothing)
         } else {
           if (d != 0) {
-            const float f = h2_pow2(d < -126 ? -126 : d);
+            const float f = mmg_pow2(d < -126 ? -126 : d);
 #pragma unroll
             for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -605,7 +539,7 @@ __device__ __forceinline__ void strip_main_h(const RelPack& rp, int64_t n_rows, 
       if (kq == 0) loadm(u + 1, mn);
       loadx(u * 4 + kq + AHEAD, xq[(kq + AHEAD) & (RING - 1)]);
       __builtin_amdgcn_sched_barrier(0);
-      f16x8s afn[NT], bn[2];
+      f16x8 afn[NT], bn[2];
       make_af(kq == 3 ? mn : mc, (kq + 1) & 3, afn);
       const float* xn = xq[(kq + 1) & (RING - 1)];
       split8_h2(xn, hs.sc, bn[0], bn[1]);
@@ -673,7 +607,7 @@ __global__ __launch_bounds__(512) void k_scatter_strip2(RelPack rp, int64_t n_ro
   if (wid < 4) {
     f32x16 acc[NA];
     strip_main_h<NA>(rp, n_rows, n_stage_total, D, x, lut, lutb, 0, q_id, n_q, acc, e);
-    const float un = h2_pow2(-e);                      // the accumulators are in units of 2^-e
+    const float un = mmg_pow2(-e);                      // the accumulators are in units of 2^-e
 #pragma unroll
     for (int t = 0; t < NA; ++t)
 #pragma unroll
@@ -686,7 +620,7 @@ __global__ __launch_bounds__(512) void k_scatter_strip2(RelPack rp, int64_t n_ro
   } else {
     f32x16 acc[NB];
     strip_main_h<NB>(rp, n_rows, n_stage_total, D, x, lut, lutb, NA, q_id, n_q, acc, e);
-    const float un = h2_pow2(-e);
+    const float un = mmg_pow2(-e);
     __syncthreads();
     sum_store(0, NA);
     __syncthreads();
@@ -709,7 +643,6 @@ int launch_scatter_strip2(const RelPack& rp, int64_t n_rows, int D, int n_ranges
              dim3((unsigned)n_ranges, (unsigned)(D / 32)), dim3(512), lds, st, rp, n_rows, nst, D, total_pad, x, slab);
   return MMG_OK;
 }
-
 
 // strip plan: instance (padded tile count) and number of row ranges; ok = false -> k_scatter_units / fp32 kernels
 struct StripPlan { bool ok; int nt; int n_ranges; int total_pad; };
@@ -801,8 +734,7 @@ __device__ __forceinline__ void scatter_unit_body(const ScUnits& su, const RelPa
   // x through a buffer descriptor over exactly this wave's rows: rows past the end (and the run-ahead past the last
   // k-step) read 0, no clamps and no exec-masked regions in the loop
   const float* xw = x + (size_t)r_beg * D + d0;
-  const __amdgpu_buffer_rsrc_t xsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xw), 0, (int)((rows_here * D - d0) * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t xsrc = mmg_rsrc(xw, (int)((rows_here * D - d0) * 4));
   const unsigned row_bytes = (unsigned)D * 4u;
   const unsigned voff0 = (unsigned)(8 * h) * row_bytes + (unsigned)l31 * 4u;
   const float* rsp = RS ? rp.r[su.rel[u]].rowscale : nullptr;
@@ -838,8 +770,8 @@ __device__ __forceinline__ void scatter_unit_body(const ScUnits& su, const RelPa
       loadx(s * 4 + kq + SU_AH, xq[(kq + SU_AH) & 3]);
       bf16x8 b0, b1, b2;
       if (RS) {
-        const f32x4s s0 = *reinterpret_cast<const f32x4s*>(rs_cur + kq * 16 + 8 * h);
-        const f32x4s s1 = *reinterpret_cast<const f32x4s*>(rs_cur + kq * 16 + 8 * h + 4);
+        const f32x4 s0 = *reinterpret_cast<const f32x4*>(rs_cur + kq * 16 + 8 * h);
+        const f32x4 s1 = *reinterpret_cast<const f32x4*>(rs_cur + kq * 16 + 8 * h + 4);
         float v[8];
 #pragma unroll
         for (int j = 0; j < 4; ++j) { v[j] = xq[kq][j] * s0[j]; v[4 + j] = xq[kq][4 + j] * s1[j]; }
@@ -852,9 +784,7 @@ __device__ __forceinline__ void scatter_unit_body(const ScUnits& su, const RelPa
         const unsigned w = (kq & 2) ? (unsigned)(mc[t] >> 32) : (unsigned)mc[t];
         const unsigned off = __builtin_amdgcn_ubfe(w, 16u * (kq & 1), 12u);
         const bf16x8 af = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(&lut[0][0]) + off);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, b0, acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, b1, acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, b2, acc[t], 0, 0, 0);
+        MMG_X3(acc[t], af, b0, b1, b2);
       }
     }
 #pragma unroll
@@ -1060,7 +990,7 @@ __device__ __forceinline__ void gather_bits_body(const RelPack& rp, int64_t n_ro
         const float t = R.colscale ? tv[q][j] * cv[q][j] : tv[q][j];
         v[j] = item < R.n_cols ? t : 0.f;
       }
-      split8(v, tb[q][0], tb[q][1], tb[q][2]);
+      mmg_split8(v, tb[q][0], tb[q][1], tb[q][2]);
     }
   }
   constexpr int NF0 = K1, NF1 = K2 - K1, NF2 = NK - K2;             // 16-bit fields per (row, half)
@@ -1072,7 +1002,7 @@ __device__ __forceinline__ void gather_bits_body(const RelPack& rp, int64_t n_ro
   // whole tensor (the launcher checks that it is below 4 GB).
   const int t_beg = blockIdx.x, t_step = gridDim.x, t_end = n_tile_total;
   const int64_t last_row = n_rows - 1;
-  const __amdgpu_buffer_rsrc_t osrc = __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)(unsigned)(n_rows * D * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t osrc = mmg_rsrc(out, (int)(unsigned)(n_rows * D * 4));
   const unsigned row_bytes = (unsigned)D * 4u;
   unsigned mcur[NK / 4], mnxt[NK / 4];                              // fields KB..KE-1 as dwords
   float rsn[3], prev[16];
@@ -1098,19 +1028,18 @@ __device__ __forceinline__ void gather_bits_body(const RelPack& rp, int64_t n_ro
     const unsigned vo = ((unsigned)(tile * 32 + 4 * h) * (unsigned)D + (unsigned)dcol) * 4u;
 #pragma unroll
     for (int i = 0; i < 16; ++i)
-      dst[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(osrc, vo, ((i & 3) + 8 * (i >> 2)) * row_bytes, 0));
+      dst[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(osrc, vo, mmg_c_row(i) * row_bytes, 0));
   };
   // next-BatchNorm statistics: the pre-BatchNorm activation of the layer below, same shape and addressing as `out`; one
   // tile ahead where registers allow (few table pieces), else in flight under this tile's products
   constexpr bool NB_ON = NBN && KH == 0, NB_AHEAD = NB_ON && NK <= 8;
-  const __amdgpu_buffer_rsrc_t ysrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(NB_ON ? nb.Y : out), 0,
-                                                                        (int)(unsigned)(n_rows * D * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t ysrc = mmg_rsrc(NB_ON ? nb.Y : out, (int)(unsigned)(n_rows * D * 4));
   float ynx[NB_ON ? 16 : 1];
   auto loady = [&](int tile, float* dst) {
     const unsigned vo = ((unsigned)(tile * 32 + 4 * h) * (unsigned)D + (unsigned)dcol) * 4u;
 #pragma unroll
     for (int i = 0; i < 16; ++i)
-      dst[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ysrc, vo, ((i & 3) + 8 * (i >> 2)) * row_bytes, 0));
+      dst[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ysrc, vo, mmg_c_row(i) * row_bytes, 0));
   };
   if (t_beg < t_end) {
     loadm(t_beg, mcur); loadrs(t_beg, rsn);
@@ -1154,18 +1083,16 @@ __device__ __forceinline__ void gather_bits_body(const RelPack& rp, int64_t n_ro
       const int r = ks < K1 ? 0 : (ks < K2 ? 1 : 2);
       const unsigned off = __builtin_amdgcn_ubfe(mcur[q >> 1], 16u * (q & 1), 12u);
       const bf16x8 af = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(&lut[0][0]) + off);
-      acc[r] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, tb[q][0], acc[r], 0, 0, 0);
-      acc[r] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, tb[q][1], acc[r], 0, 0, 0);
-      acc[r] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, tb[q][2], acc[r], 0, 0, 0);
+      MMG_X3(acc[r], af, tb[q][0], tb[q][1], tb[q][2]);
     }
     // scaled partial in the C layout: register i <-> patient row (i & 3) + 8 (i >> 2) + 4 h, lane <-> feature column
     float v[16];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      f32x4s s0, s1, s2;
-      if (USE0) s0 = *reinterpret_cast<const f32x4s*>(&rss[wid][0][8 * q + 4 * h]);
-      if (USE1) s1 = *reinterpret_cast<const f32x4s*>(&rss[wid][1][8 * q + 4 * h]);
-      if (USE2) s2 = *reinterpret_cast<const f32x4s*>(&rss[wid][2][8 * q + 4 * h]);
+      f32x4 s0, s1, s2;
+      if (USE0) s0 = *reinterpret_cast<const f32x4*>(&rss[wid][0][8 * q + 4 * h]);
+      if (USE1) s1 = *reinterpret_cast<const f32x4*>(&rss[wid][1][8 * q + 4 * h]);
+      if (USE2) s2 = *reinterpret_cast<const f32x4*>(&rss[wid][2][8 * q + 4 * h]);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int i = 4 * q + e;
@@ -1190,7 +1117,7 @@ __device__ __forceinline__ void gather_bits_body(const RelPack& rp, int64_t n_ro
         for (int i = 0; i < 16; ++i) {
           float t = v[i] + xb[i][lane];
           if (ACCUM) t += pc[i];
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, t), osrc, vo, ((i & 3) + 8 * (i >> 2)) * row_bytes, 0);
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, t), osrc, vo, mmg_c_row(i) * row_bytes, 0);
           tv[i] = t;
         }
         const int64_t left = n_rows - (int64_t)tile * 32;
@@ -1201,7 +1128,7 @@ __device__ __forceinline__ void gather_bits_body(const RelPack& rp, int64_t n_ro
         for (int i = 0; i < 16; ++i) {
           float t = v[i] + xb[i][lane];
           if (ACCUM) t += pc[i];
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, t), osrc, vo, ((i & 3) + 8 * (i >> 2)) * row_bytes, 0);
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, t), osrc, vo, mmg_c_row(i) * row_bytes, 0);
           if ((int64_t)tile * 32 + (i & 3) + 8 * (i >> 2) + 4 * h < n_rows) { t1 += t; t2 = fmaf(t, t, t2); }
         }
         if (stat_partial) { cs1 += (double)t1; cs2 += (double)t2; }
@@ -1314,12 +1241,12 @@ __global__ __launch_bounds__(512) void k_gather_units(GaUnits gu, RelPack rp, in
         const float t = R.colscale ? tv[qq][j] * cv[qq][j] : tv[qq][j];
         v[j] = (q < nks && item < R.n_cols) ? t : 0.f;
       }
-      split8(v, tb[q][0], tb[q][1], tb[q][2]);
+      mmg_split8(v, tb[q][0], tb[q][1], tb[q][2]);
     }
   }
   const int t_step = gridDim.x;
   const int64_t last_row = n_rows - 1;
-  const __amdgpu_buffer_rsrc_t osrc = __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)(unsigned)(n_rows * D * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t osrc = mmg_rsrc(out, (int)(unsigned)(n_rows * D * 4));
   const unsigned row_bytes = (unsigned)D * 4u;
   const unsigned* mrow = reinterpret_cast<const unsigned*>(R.mask_r);
   // Inputs run GU_DEPTH tiles ahead in as many register sets (iteration i uses set i % GU_DEPTH): a tile takes less time
@@ -1344,7 +1271,7 @@ __global__ __launch_bounds__(512) void k_gather_units(GaUnits gu, RelPack rp, in
     const unsigned vo = ((unsigned)(tile * 32 + 4 * h) * (unsigned)D + (unsigned)dcol) * 4u;
 #pragma unroll
     for (int i = 0; i < 16; ++i)
-      dst[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(osrc, vo, ((i & 3) + 8 * (i >> 2)) * row_bytes, 0));
+      dst[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(osrc, vo, mmg_c_row(i) * row_bytes, 0));
   };
   float* rss = rss_all + wid * 32;
   double cs1 = 0.0, cs2 = 0.0;
@@ -1369,16 +1296,14 @@ __global__ __launch_bounds__(512) void k_gather_units(GaUnits gu, RelPack rp, in
       if (q < nks) {                                                 // wave-uniform
         const unsigned off = __builtin_amdgcn_ubfe(mS[q >> 1], 16u * (q & 1), 12u);
         const bf16x8 af = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(&lut[0][0]) + off);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, tb[q][0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, tb[q][1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, tb[q][2], acc, 0, 0, 0);
+        MMG_X3(acc, af, tb[q][0], tb[q][1], tb[q][2]);
       }
     loadm(tn, mS);
     // scaled partial in the C layout: register i <-> patient row (i & 3) + 8 (i >> 2) + 4 h, lane <-> feature column
     float v[16];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const f32x4s sc = *reinterpret_cast<const f32x4s*>(&rss[8 * q + 4 * h]);
+      const f32x4 sc = *reinterpret_cast<const f32x4*>(&rss[8 * q + 4 * h]);
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[4 * q + e] = sc[e] * acc[4 * q + e];
     }
@@ -1405,8 +1330,8 @@ __global__ __launch_bounds__(512) void k_gather_units(GaUnits gu, RelPack rp, in
       for (int i = 0; i < 16; ++i) {
         float t = tt[i];
         if (ACCUM) t += pS[i];
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, t), osrc, vo, ((i & 3) + 8 * (i >> 2)) * row_bytes, 0);
-        if ((i & 3) + 8 * (i >> 2) + 4 * h < rows_left) { t1 += t; t2 = fmaf(t, t, t2); }
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, t), osrc, vo, mmg_c_row(i) * row_bytes, 0);
+        if (mmg_c_row(i) + 4 * h < rows_left) { t1 += t; t2 = fmaf(t, t, t2); }
       }
       if (stat_partial) { cs1 += (double)t1; cs2 += (double)t2; }
       if (ACCUM) loadprev(tn, pS);
@@ -1484,7 +1409,7 @@ __global__ __launch_bounds__(256) void k_mask_build_rows(const int32_t* __restri
 // epilogue of the slab sum: padded accumulator row -> (relation, vocab row), times colscale
 struct EpiScatter {
   RelPack rp; int D;
-  __device__ void operator()(int64_t i4, mmg_f4 v) const {
+  __device__ void operator()(int64_t i4, f32x4 v) const {
     const int64_t i = i4 * 4;
     const int c = (int)(i / D), d = (int)(i - (int64_t)c * D);
     for (int r = 0; r < rp.n; ++r) {
@@ -1492,7 +1417,7 @@ struct EpiScatter {
       if (c >= R.acc_off && c < R.acc_off + R.n_cols) {
         const int j = c - R.acc_off;
         const float cs = R.colscale ? R.colscale[j] : 1.f;
-        *reinterpret_cast<mmg_f4*>(R.out + (size_t)j * D + d) = v * cs;
+        *reinterpret_cast<f32x4*>(R.out + (size_t)j * D + d) = v * cs;
         return;
       }
     }
@@ -1777,7 +1702,6 @@ extern "C" int mmg_scatter_rows(const mmg_rel_t* rels, int n_rel, int64_t n_rows
   MMG_CHECK_LAUNCH("scatter_rows");
   return MMG_OK;
 }
-
 
 extern "C" size_t mmg_rel_mask_words(int64_t n_rows, int32_t n_cols) {
   if (n_rows <= 0 || n_cols <= 0) return 0;

@@ -7,6 +7,7 @@
 #include <stdarg.h>
 #include <atomic>
 #include "../../include/mmgnn.h"
+#include "mma.h"
 
 #define WAVE 64
 
@@ -178,14 +179,14 @@ __host__ __device__ static inline bool mmg_keep(uint64_t seed, uint32_t site, ui
 }
 
 // Dropout keep-fields of a 32 x 32 tile held in the MFMA C layout (lane = column col0 + (lane & 31), register r = tile row
-// (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) of a row-major [*, ncols] tensor: element (row, col) belongs to the RNG group
+// mmg_c_row(r) + 4 * (lane >> 5)) of a row-major [*, ncols] tensor: element (row, col) belongs to the RNG group
 // (row * ncols + col) >> 2, shared by the four lanes of a quad.  For the four registers 4g .. 4g+3 quad lane j hashes the
 // row of register 4g + j (ONE hash per lane instead of four) and the words travel inside the quad by DPP:
 //   mmg_c_layout_hash(key, first row of the tile, ncols, col, lane, g, &w0, &w1);
 //   field of register 4g + j  =  mmg_rng_field(mmg_quad_bcast(w0, j), mmg_quad_bcast(w1, j), col & 3)
 __device__ __forceinline__ void mmg_c_layout_hash(uint32_t key, uint64_t row_first, uint32_t ncols, int col, int lane, int g,
                                                   uint32_t* w0, uint32_t* w1) {
-  const uint64_t row = row_first + (uint64_t)((lane & 3) + 8 * g + 4 * (lane >> 5));
+  const uint64_t row = row_first + (uint64_t)(mmg_c_row(4 * g + (lane & 3)) + 4 * (lane >> 5));
   mmg_rng_group(key, (row * (uint64_t)ncols + (uint64_t)col) >> 2, w0, w1);
 }
 __device__ __forceinline__ uint32_t mmg_quad_bcast(uint32_t v, int j) {     // j must fold to a constant (unrolled loops)
@@ -195,6 +196,12 @@ __device__ __forceinline__ uint32_t mmg_quad_bcast(uint32_t v, int j) {     // j
     case 2: return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xAA, 0xF, 0xF, true);
     default: return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xFF, 0xF, 0xF, true);
   }
+}
+
+// buffer descriptor over `bytes` bytes at p (raw buffer, 32-bit out-of-range check: a load past the end reads 0, a store is
+// dropped; bytes = 0: nothing is accessible)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mmg_rsrc(const void* p, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
 }
 
 // activation codes of mmg_prologue_t::relu (include/mmgnn.h): the reference's HeteroRGCN accepts relu, elu and leaky_relu
@@ -297,7 +304,7 @@ __device__ __forceinline__ void next_bn_tile(const NextBnDev& nb, const NextBnCo
     if (cc.drop) mmg_c_layout_hash(nb.pr.key, (uint64_t)(nb.pr.row_offset + row0), (uint32_t)N, col, lane, g4, &w0, &w1);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int i = 4 * g4 + j, r = j + 8 * g4 + h4;
+      const int i = 4 * g4 + j, r = mmg_c_row(i) + h4;
       const float y = yv[i];
       float g = v[i];
       const float act = fmaf(y, cc.sc, cc.sh);
@@ -362,24 +369,37 @@ __device__ __forceinline__ float wave_max_f(float v) {
   return v;
 }
 
+__device__ __forceinline__ float wave_max_dpp(float x) {      // -> the maximum over the 64 lanes, in a scalar register
+#define MMG_DPP_MAX(ctrl, rmask)                                                                                             \
+  x = fmaxf(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, x), __builtin_bit_cast(int, x),   \
+                                                                     ctrl, rmask, 0xF, false)))
+  MMG_DPP_MAX(0xB1, 0xF);        // quad_perm [1,0,3,2]
+  MMG_DPP_MAX(0x4E, 0xF);        // quad_perm [2,3,0,1]
+  MMG_DPP_MAX(0x141, 0xF);       // row_half_mirror
+  MMG_DPP_MAX(0x140, 0xF);       // row_mirror
+  MMG_DPP_MAX(0x142, 0xA);       // row_bcast:15 -> rows 1, 3
+  MMG_DPP_MAX(0x143, 0xC);       // row_bcast:31 -> rows 2, 3
+#undef MMG_DPP_MAX
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
+}
+
 // ------------------------------------------------------------------------------------
 // Deterministic sum over partial slabs: out[i] = epi(sum_s slab[s][i]).  256 threads =
 // 16 float4 elements x 16 split groups; every thread keeps 8 independent 16-B loads in flight,
 // the 16 group partials are combined through LDS in fixed order.  Grid = ceil(n4 / 16).
 // ------------------------------------------------------------------------------------
-typedef float mmg_f4 __attribute__((ext_vector_type(4)));
 template <class Epi>
 __global__ __launch_bounds__(256) void mmg_k_reduce_slabs(const float* __restrict__ slab, int64_t n4, int n_split,
                                                           Epi epi) {
-  __shared__ mmg_f4 part[16][16];
+  __shared__ f32x4 part[16][16];
   const int e = threadIdx.x & 15, g = threadIdx.x >> 4;
   const int64_t i4 = (int64_t)blockIdx.x * 16 + e;
-  mmg_f4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   if (i4 < n4) {
-    const mmg_f4* base = reinterpret_cast<const mmg_f4*>(slab) + i4;
+    const f32x4* base = reinterpret_cast<const f32x4*>(slab) + i4;
     int s = g;
     for (; s + 7 * 16 < n_split; s += 8 * 16) {
-      mmg_f4 v[8];
+      f32x4 v[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) v[u] = base[(size_t)(s + u * 16) * n4];
 #pragma unroll
@@ -390,7 +410,7 @@ __global__ __launch_bounds__(256) void mmg_k_reduce_slabs(const float* __restric
   part[g][e] = acc;
   __syncthreads();
   if (g == 0 && i4 < n4) {
-    mmg_f4 t = part[0][e];
+    f32x4 t = part[0][e];
 #pragma unroll
     for (int q = 1; q < 16; ++q) t += part[q][e];
     epi(i4, t);

@@ -3,10 +3,10 @@
 // All loads/stores are 16 B per lane; column reductions accumulate in fp64 and are summed in a
 // fixed order (deterministic).
 #include "common.h"
+#include "mma.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 // Big inputs: one 1024-thread workgroup per CU (16 waves keep 128 KB of loads in flight per CU) so that only 256
 // partial rows are left for the second pass; small inputs: 256-thread workgroups of 64 rows.
 constexpr int CR_BIG_ROWS = 32768, CR_BIG_BLOCKS = 256, CR_MAX_BLOCKS = 2048;

@@ -13,24 +13,16 @@
 //              stages into a [TN,TK] register tile, writes one partial slab, a second kernel sums the slabs in
 //              fixed order (bitwise reproducible).  The bias gradient (column sums of dY) rides in the same pass.
 #include "common.h"
+#include "mma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // ---------------------------------------------------------------------------------- fp32 GEMM on the bf16 matrix cores
-// An fp32 value is EXACTLY hi + mid + lo with three bf16 pieces (8 significant bits each), so
-//     x . w = x1 w1 + (x1 w2 + x2 w1) + (x2 w2 + x1 w3 + x3 w1) + O(2^-24 |x||w|)
-// Six v_mfma_f32_32x32x16_bf16 products (each exact, accumulated in fp32) reproduce the fp32 product to within
-// its own rounding error at 6/16 of the fp32 matrix time: the dropped terms x2 w3 + x3 w2 + x3 w3 are below
-// 3 * 2^-25 |x||w| -- less than the rounding of the fp32 FMA chain they replace.
+// The split (MMG_SPLIT3), its error bound and the six-product sequence (MMG_X6_ALO in every kernel here): mma.h.
 // Layout: the three W pieces stay in registers for the whole kernel (lane (n = l&31, h = l>>5) holds
 // W[n][16 ks + 8 h + 0..7]); every 64-row X tile is prologue'd AND split once while it is staged to LDS (three
 // bf16 planes, double-buffered: tile t+1 is staged while tile t is multiplied, one barrier per tile), and an A
 // fragment is one conflict-free ds_read_b128 per piece.
-typedef __bf16 xbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 xbf16x4 __attribute__((ext_vector_type(4)));
 
 // XCD-aware block -> (tile, row-set) map for 2-D grids whose x index selects an output tile (a column slice of the
 // forward, an [TN, TK] tile of the weight gradient) and whose y index selects the rows.  Every tile of one row-set reads
@@ -49,14 +41,12 @@ __device__ __forceinline__ void xcd_tile_map(int* bx, int* by) {
   }
 }
 
-
 // Memory pipeline: every global access goes through a per-tile buffer descriptor (rows past M and tiles past the end
 // read 0 / are dropped by the range check), so the tile loop is straight-line code without a branch around a load or a
 // store and the compiler's vmcnt waits are exact: X runs two tiles ahead in registers, the epilogue's stores are never
 // waited for (gfx9 counts stores in vmcnt, in order: a conservative wait exposes the full store-acknowledge latency
 // once per tile, which is what the first version of this kernel did), and in accumulate mode the old output tile is
 // loaded INTO the accumulator before the next tile is staged, so its latency hides under the split.
-typedef unsigned xu32x4 __attribute__((ext_vector_type(4)));
 // cache policy of the streamed operands (aux = 2: the `nt` bit -- X is read once, Y written once: -1.3 % on the step)
 #ifndef MMG_NT_LD
 #define MMG_NT_LD 2
@@ -73,10 +63,10 @@ typedef unsigned xu32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void next_bn_load(const NextBnDev& nb, int64_t tile, int rows, int N, int c0, int vo, float* yv) {
   const size_t off = (size_t)(rows ? tile : 0) * 32 * N + c0;
   const int bytes = rows ? (rows * N - c0) * 4 : 0;
-  const __amdgpu_buffer_rsrc_t ysrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(nb.Y) + off, 0, bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ysrc = mmg_rsrc(nb.Y + off, bytes);
 #pragma unroll
   for (int i = 0; i < 16; ++i)
-    yv[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ysrc, vo, ((i & 3) + 8 * (i >> 2)) * N * 4, MMG_NT_LD));
+    yv[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ysrc, vo, mmg_c_row(i) * N * 4, MMG_NT_LD));
 }
 // L2: the row L2 normalisation that follows the layer (F.normalize, src/model.py:232) in the epilogue -- the workgroup
 // holds whole rows (N == 32 * WN), so Y receives  y / max(|y|, eps)  and rn_out[row] = 1 / max(|y|, eps); the separate
@@ -100,7 +90,7 @@ __global__ __launch_bounds__(64 * WN, (WN == 4 && K <= 128) ? 2 : 1) void k_line
   xcd_tile_map(&bx, &by);                 // (column slice, row-set): the slices of one row-set share an XCD's L2
   const int col = bx * BN + wn * 32 + l31;
 
-  xbf16x8 wb[NK][3];
+  bf16x8 wb[NK][3];
   {
     const bool wkn = (flags & MMG_LIN_W_KN) != 0;
     const float* wp = wkn ? W + (size_t)(8 * h) * N + col : W + (size_t)col * K + 8 * h;
@@ -116,10 +106,7 @@ __global__ __launch_bounds__(64 * WN, (WN == 4 && K <= 128) ? 2 : 1) void k_line
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float v = j < 4 ? w0[j] : w1[j - 4];
-        const __bf16 a = (__bf16)v;
-        const float r1 = v - (float)a;
-        const __bf16 b = (__bf16)r1;
-        wb[ks][0][j] = a; wb[ks][1][j] = b; wb[ks][2][j] = (__bf16)(r1 - (float)b);
+        MMG_SPLIT3(v, wb[ks][0][j], wb[ks][1][j], wb[ks][2][j]);
       }
     }
   }
@@ -156,8 +143,7 @@ __global__ __launch_bounds__(64 * WN, (WN == 4 && K <= 128) ? 2 : 1) void k_line
   const int xvo = (prow * K + kc4 * 4) * 4;
   auto fetch = [&](int64_t tile, f32x4* nx) {
     const int rows = rows_of(tile);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(X) + (size_t)(rows ? tile : 0) * BM * K, 0, rows * K * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = mmg_rsrc(X + (size_t)(rows ? tile : 0) * BM * K, rows * K * 4);
 #pragma unroll
     for (int p = 0; p < NP; ++p)
       nx[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, xvo, p * ROWS_PER_PASS * K * 4, MMG_NT_LD));
@@ -174,17 +160,12 @@ __global__ __launch_bounds__(64 * WN, (WN == 4 && K <= 128) ? 2 : 1) void k_line
         if (drop)
           mmg_drop4(v, pr.key, (uint64_t)(pr.row_offset + row0 + r) * (uint64_t)K + (uint64_t)(kc4 * 4), pr.thr, pr.inv_keep);
       }
-      xbf16x4 q0, q1, q2;
+      bf16x4 q0, q1, q2;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const __bf16 a = (__bf16)v[j];
-        const float r1 = v[j] - (float)a;
-        const __bf16 b = (__bf16)r1;
-        q0[j] = a; q1[j] = b; q2[j] = (__bf16)(r1 - (float)b);
-      }
-      *reinterpret_cast<xbf16x4*>(pb + (0 * BM + r) * LDP + kc4 * 4) = q0;
-      *reinterpret_cast<xbf16x4*>(pb + (1 * BM + r) * LDP + kc4 * 4) = q1;
-      *reinterpret_cast<xbf16x4*>(pb + (2 * BM + r) * LDP + kc4 * 4) = q2;
+      for (int j = 0; j < 4; ++j) MMG_SPLIT3(v[j], q0[j], q1[j], q2[j]);
+      *reinterpret_cast<bf16x4*>(pb + (0 * BM + r) * LDP + kc4 * 4) = q0;
+      *reinterpret_cast<bf16x4*>(pb + (1 * BM + r) * LDP + kc4 * 4) = q1;
+      *reinterpret_cast<bf16x4*>(pb + (2 * BM + r) * LDP + kc4 * 4) = q2;
     }
   };
   auto stage = [&](int64_t tile, int buf, const f32x4* nx) __attribute__((always_inline)) {  // prologue + split + three plane writes
@@ -206,12 +187,11 @@ __global__ __launch_bounds__(64 * WN, (WN == 4 && K <= 128) ? 2 : 1) void k_line
   auto tile_body = [&](int64_t tt, int buf, f32x4* nx) {
     // nx holds tile tt+G (fetched two tiles ago); after staging it, the registers take tile tt+3G
     const int rows = rows_of(tt);
-    const __amdgpu_buffer_rsrc_t ys = __builtin_amdgcn_make_buffer_rsrc(
-        Y + (size_t)(rows ? tt : 0) * BM * N + c0, 0, rows ? (rows * N - c0) * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ys = mmg_rsrc(Y + (size_t)(rows ? tt : 0) * BM * N + c0, rows ? (rows * N - c0) * 4 : 0);
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i)
-      acc[i] = ACC ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ys, yvo, ((i & 3) + 8 * (i >> 2)) * N * 4, 0))
+      acc[i] = ACC ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ys, yvo, mmg_c_row(i) * N * 4, 0))
                    : 0.f;
     float nby[NBN ? 16 : 1];
     if constexpr (NBN) next_bn_load(nb, tt, rows, N, c0, yvo, nby);   // in flight under the products
@@ -224,15 +204,10 @@ __global__ __launch_bounds__(64 * WN, (WN == 4 && K <= 128) ? 2 : 1) void k_line
     if constexpr (!WEAVE) {
 #pragma unroll
       for (int ks = 0; ks < NK; ++ks) {
-        const xbf16x8 a1 = *reinterpret_cast<const xbf16x8*>(ap + ks * 16);
-        const xbf16x8 a2 = *reinterpret_cast<const xbf16x8*>(ap + BM * LDP + ks * 16);
-        const xbf16x8 a3 = *reinterpret_cast<const xbf16x8*>(ap + 2 * BM * LDP + ks * 16);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, wb[ks][0], acc, 0, 0, 0);   // small terms first
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, wb[ks][2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, wb[ks][1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, wb[ks][0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, wb[ks][1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, wb[ks][0], acc, 0, 0, 0);
+        const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(ap + ks * 16);
+        const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(ap + BM * LDP + ks * 16);
+        const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(ap + 2 * BM * LDP + ks * 16);
+        MMG_X6_ALO(acc, a1, a2, a3, wb[ks][0], wb[ks][1], wb[ks][2]);
       }
     } else {
       // A wave that is alone on its SIMD hides nothing by itself: the fragments of k-step ks+1 are fetched before the
@@ -240,11 +215,11 @@ __global__ __launch_bounds__(64 * WN, (WN == 4 && K <= 128) ? 2 : 1) void k_line
       // NEXT tile is dealt out between the products of every KS_PER_PASS-th k-step (sched_group_barrier: a dependent
       // MFMA chain issues one instruction per 32 clocks, the vector / LDS work of the pass issues in between).
       constexpr int KS_PER_PASS = NK / NP;
-      xbf16x8 fr[2][3];
-      auto ldfrag = [&](int ks, xbf16x8* f) __attribute__((always_inline)) {
-        f[0] = *reinterpret_cast<const xbf16x8*>(ap + ks * 16);
-        f[1] = *reinterpret_cast<const xbf16x8*>(ap + BM * LDP + ks * 16);
-        f[2] = *reinterpret_cast<const xbf16x8*>(ap + 2 * BM * LDP + ks * 16);
+      bf16x8 fr[2][3];
+      auto ldfrag = [&](int ks, bf16x8* f) __attribute__((always_inline)) {
+        f[0] = *reinterpret_cast<const bf16x8*>(ap + ks * 16);
+        f[1] = *reinterpret_cast<const bf16x8*>(ap + BM * LDP + ks * 16);
+        f[2] = *reinterpret_cast<const bf16x8*>(ap + 2 * BM * LDP + ks * 16);
       };
       ldfrag(0, fr[0]);
 #pragma unroll
@@ -253,13 +228,8 @@ __global__ __launch_bounds__(64 * WN, (WN == 4 && K <= 128) ? 2 : 1) void k_line
         for (int kk = 0; kk < KS_PER_PASS; ++kk) {
           const int ks = pg * KS_PER_PASS + kk;
           if (ks + 1 < NK) ldfrag(ks + 1, fr[(ks + 1) & 1]);
-          const xbf16x8* f = fr[ks & 1];
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[2], wb[ks][0], acc, 0, 0, 0);   // small terms first
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[0], wb[ks][2], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[1], wb[ks][1], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[1], wb[ks][0], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[0], wb[ks][1], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[0], wb[ks][0], acc, 0, 0, 0);
+          const bf16x8* f = fr[ks & 1];
+          MMG_X6_ALO(acc, f[0], f[1], f[2], wb[ks][0], wb[ks][1], wb[ks][2]);
         }
         stage_pass(tt + G, buf ^ 1, nx, pg);
         // a lone wave hides 2-3 vector instructions behind a matrix instruction (profiles/probes/mfma_shadow): the pass
@@ -311,7 +281,7 @@ __global__ __launch_bounds__(64 * WN, (WN == 4 && K <= 128) ? 2 : 1) void k_line
       __syncthreads();
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int r = (i & 3) + 8 * (i >> 2);
+        const int r = mmg_c_row(i);
         const float v = vv[i] * l2_rn[r + 4 * h];
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ys, yvo, r * N * 4, MMG_NT_ST);
       }
@@ -322,14 +292,14 @@ __global__ __launch_bounds__(64 * WN, (WN == 4 && K <= 128) ? 2 : 1) void k_line
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         vv[i] = acc[i] + bv;
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[i]), ys, yvo, ((i & 3) + 8 * (i >> 2)) * N * 4, MMG_NT_ST);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[i]), ys, yvo, mmg_c_row(i) * N * 4, MMG_NT_ST);
       }
       next_bn_tile(nb, nbc, vv, nby, rows, tt * BM, N, col, lane, cs1, cs2);
     } else {
       float t1 = 0.f, t2 = 0.f;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int r = (i & 3) + 8 * (i >> 2);
+        const int r = mmg_c_row(i);
         const float v = acc[i] + bv;
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ys, yvo, r * N * 4, MMG_NT_ST);
         const float vs = r + 4 * h < rows ? v : 0.f;
@@ -381,24 +351,7 @@ __global__ __launch_bounds__(64 * WN, (WN == 4 && K <= 128) ? 2 : 1) void k_line
 // waves, two column tiles and 384 registers of W pieces per wave) measured 147 us per [183400, 256] x [256, 256] call, this
 // one 102-112 (179 -> 122 with BatchNorm fold + ReLU + dropout in the prologue); its parts add up -- staging and epilogue
 // alone 48 us, + matrix instructions 32, + memory 29 -- the two waves of a SIMD run the same phase between the per-tile barriers.
-typedef _Float16 xf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 xf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 xf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ float wave_max_dpp(float x) {      // -> the maximum over the 64 lanes, in a scalar register
-#define MMG_DPP_MAX(ctrl, rmask)                                                                                             \
-  x = fmaxf(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, x), __builtin_bit_cast(int, x),   \
-                                                                     ctrl, rmask, 0xF, false)))
-  MMG_DPP_MAX(0xB1, 0xF);        // quad_perm [1,0,3,2]
-  MMG_DPP_MAX(0x4E, 0xF);        // quad_perm [2,3,0,1]
-  MMG_DPP_MAX(0x141, 0xF);       // row_half_mirror
-  MMG_DPP_MAX(0x140, 0xF);       // row_mirror
-  MMG_DPP_MAX(0x142, 0xA);       // row_bcast:15 -> rows 1, 3
-  MMG_DPP_MAX(0x143, 0xC);       // row_bcast:31 -> rows 2, 3
-#undef MMG_DPP_MAX
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
-}
 // exponent e with  m * 2^e in [2^13, 2^14)  for a normal m (0 for zero / denormal / inf / NaN), from the exponent field of m:
 // integer arithmetic only, so that a wave-uniform m (wave_max_dpp) keeps all of it on the scalar unit
 __device__ __forceinline__ int h3_exponent(float m) {
@@ -406,7 +359,6 @@ __device__ __forceinline__ int h3_exponent(float m) {
   const int e = 140 - E;
   return (E == 0 || E == 255) ? 0 : (e > 126 ? 126 : e);
 }
-__device__ __forceinline__ float h3_pow2(int e) { return __builtin_bit_cast(float, (unsigned)(e + 127) << 23); }
 
 template <int PRO, bool ACC, bool STATS, int WN>      // WN = 4: two column tiles per wave; 8: one (two waves per SIMD)
 __global__ __launch_bounds__(64 * WN, 1) void k_linear_fwd_h3_k256(
@@ -422,7 +374,7 @@ __global__ __launch_bounds__(64 * WN, 1) void k_linear_fwd_h3_k256(
   const int h = lane >> 5, l31 = lane & 31;
   const int bx = blockIdx.x, by = blockIdx.y;
   const int c0 = bx * BN;
-  xf16x8 wh[CT][NK], wl[CT][NK];
+  f16x8 wh[CT][NK], wl[CT][NK];
   float bv[CT], cf[CT];                      // bias and 2^-ew of this lane's two columns
   {
     const bool wkn = (flags & MMG_LIN_W_KN) != 0;
@@ -451,8 +403,8 @@ __global__ __launch_bounds__(64 * WN, 1) void k_linear_fwd_h3_k256(
       }
       m = fmaxf(m, __shfl_xor(m, 32, 64));             // the other half of the column's K (lane ^ 32)
       const int ew = h3_exponent(m);
-      const float sw = h3_pow2(ew > 126 ? 126 : ew);
-      cf[ct] = h3_pow2(-(ew > 126 ? 126 : ew));
+      const float sw = mmg_pow2(ew > 126 ? 126 : ew);
+      cf[ct] = mmg_pow2(-(ew > 126 ? 126 : ew));
 #pragma unroll
       for (int ks = 0; ks < NK; ++ks)
 #pragma unroll
@@ -484,8 +436,7 @@ __global__ __launch_bounds__(64 * WN, 1) void k_linear_fwd_h3_k256(
   };
   auto x_rsrc = [&](int64_t tile) __attribute__((always_inline)) {
     const int rows = rows_of(tile);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X) + (size_t)(rows ? tile : 0) * BM * K, 0, rows * K * 4,
-                                             0x00020000);
+    return mmg_rsrc(X + (size_t)(rows ? tile : 0) * BM * K, rows * K * 4);
   };
   const int xvo = (prow * K + kc4 * 4) * 4;
   // TWO tiles of X in registers (the six-term kernel had room for one): a workgroup per CU with one 32 KB tile in flight
@@ -514,19 +465,19 @@ __global__ __launch_bounds__(64 * WN, 1) void k_linear_fwd_h3_k256(
     float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
     m = wave_max_dpp(m);
     const int ex = h3_exponent(m);
-    const float sx = h3_pow2(ex);
-    xf16x4 qh, ql;
+    const float sx = mmg_pow2(ex);
+    f16x4 qh, ql;
 #pragma unroll
     for (int j = 0; j < 4; j += 2) {
       const f32x2 a = {v[j] * sx, v[j + 1] * sx};
-      const xf16x2 hh = __builtin_convertvector(a, xf16x2);
+      const f16x2 hh = __builtin_convertvector(a, f16x2);
       const f32x2 rr = {(a[0] - (float)hh[0]) * 2048.f, (a[1] - (float)hh[1]) * 2048.f};
-      const xf16x2 ll = __builtin_convertvector(rr, xf16x2);
+      const f16x2 ll = __builtin_convertvector(rr, f16x2);
       qh[j] = hh[0]; qh[j + 1] = hh[1]; ql[j] = ll[0]; ql[j + 1] = ll[1];
     }
-    *reinterpret_cast<xf16x4*>(pb + (0 * BM + r) * LDP + kc4 * 4) = qh;
-    *reinterpret_cast<xf16x4*>(pb + (1 * BM + r) * LDP + kc4 * 4) = ql;
-    if (lane == 0) rowf[buf * BM + r] = h3_pow2(-ex);
+    *reinterpret_cast<f16x4*>(pb + (0 * BM + r) * LDP + kc4 * 4) = qh;
+    *reinterpret_cast<f16x4*>(pb + (1 * BM + r) * LDP + kc4 * 4) = ql;
+    if (lane == 0) rowf[buf * BM + r] = mmg_pow2(-ex);
   };
   {
     const __amdgpu_buffer_rsrc_t r0 = x_rsrc(t0), r1 = x_rsrc(t0 + G), r2 = x_rsrc(t0 + 2 * G);
@@ -548,8 +499,7 @@ __global__ __launch_bounds__(64 * WN, 1) void k_linear_fwd_h3_k256(
     const int64_t tt = t0 + (int64_t)i * G;
     const int buf = par;
     const int rows = rows_of(tt);
-    const __amdgpu_buffer_rsrc_t ys = __builtin_amdgcn_make_buffer_rsrc(
-        Y + (size_t)(rows ? tt : 0) * BM * N + c0, 0, rows ? (rows * N - c0) * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ys = mmg_rsrc(Y + (size_t)(rows ? tt : 0) * BM * N + c0, rows ? (rows * N - c0) * 4 : 0);
     const __amdgpu_buffer_rsrc_t xs3 = x_rsrc(tt + 3 * G);     // refills: three tiles ahead (slot of tile t + 1)
     f32x16 ah[CT], al[CT];
     float yold[ACC ? CT : 1][16];
@@ -559,21 +509,21 @@ __global__ __launch_bounds__(64 * WN, 1) void k_linear_fwd_h3_k256(
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         ah[ct][r] = 0.f; al[ct][r] = 0.f;
-        if (ACC) yold[ct][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ys, yvo, ((r & 3) + 8 * (r >> 2)) * N * 4, 0));
+        if (ACC) yold[ct][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ys, yvo, mmg_c_row(r) * N * 4, 0));
       }
     }
     const _Float16* ap = hplanes + (size_t)buf * 2 * PLANE + l31 * LDP + 8 * h;
-    xf16x8 fr[2][2];
-    auto ldfrag = [&](int ks, xf16x8* f) __attribute__((always_inline)) {
-      f[0] = *reinterpret_cast<const xf16x8*>(ap + ks * 16);
-      f[1] = *reinterpret_cast<const xf16x8*>(ap + PLANE + ks * 16);
+    f16x8 fr[2][2];
+    auto ldfrag = [&](int ks, f16x8* f) __attribute__((always_inline)) {
+      f[0] = *reinterpret_cast<const f16x8*>(ap + ks * 16);
+      f[1] = *reinterpret_cast<const f16x8*>(ap + PLANE + ks * 16);
     };
     ldfrag(0, fr[0]);
 #pragma unroll
     for (int ks = 0; ks < NK; ++ks) {
       const bool pass = (ks % KPP) == KPP - 1;
       if (ks + 1 < NK) ldfrag(ks + 1, fr[(ks + 1) & 1]);
-      const xf16x8* f = fr[ks & 1];
+      const f16x8* f = fr[ks & 1];
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct) {
         al[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f[1], wh[ct][ks], al[ct], 0, 0, 0);   // Xl Wh
@@ -603,7 +553,7 @@ __global__ __launch_bounds__(64 * WN, 1) void k_linear_fwd_h3_k256(
       float t1 = 0.f, t2 = 0.f;
 #pragma unroll
       for (int r16 = 0; r16 < 16; ++r16) {
-        const int r = (r16 & 3) + 8 * (r16 >> 2);
+        const int r = mmg_c_row(r16);
         float v = fmaf(al[ct][r16], 1.f / 2048.f, ah[ct][r16]) * (rf4[r16 >> 2][r16 & 3] * cf[ct]) + bv[ct];
         if (ACC) v += yold[ct][r16];
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ys, yvo, r * N * 4, MMG_NT_ST);
@@ -721,16 +671,8 @@ int launch_fwd_x6(const float* X, const ProDev& pr, const float* W, const float*
              : launch_fwd_x6_v<K, WN, false, false>(X, pr, W, bias, Y, M, N, flags, st, stat_partial);
 }
 
-// the gfx950 transposing LDS read of an MFMA operand that is contracted over its ROW index (see the wgrad section)
-typedef short xs16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ xbf16x8 tr_frag(const __bf16* p, int row_stride) {   // rows +0..3 and +4..7 of this lane's column
-  const xs16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) xs16x4*)p);
-  const xs16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) xs16x4*)(p + 4 * row_stride));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(xbf16x8, v);
-}
+// rows +0..3 and +4..7 of this lane's column through the transposing LDS read (see the wgrad section)
+__device__ __forceinline__ bf16x8 tr_frag(const __bf16* p, int row_stride) { return mmg_tr_pair(p, p + 4 * row_stride); }
 
 // ---------------------------------------------------------------------------- BatchNorm backward inside the data-gradient GEMM
 // dX = dZ . W  with  dZ = the backward of  dropout(relu(BN(y)))  at the upstream gradient G  (mmg_bn_bwd_apply's
@@ -788,7 +730,7 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
   const int h = lane >> 5, l31 = lane & 31;
   const int col = wn * 32 + l31;
   const bool xrole = FW && tid >= NTHR;    // (wave-uniform) the X stagers / dW multipliers
-  xbf16x8 wb[NK][3];                       // W stored [K, N] (the forward weight, read in place)
+  bf16x8 wb[NK][3];                       // W stored [K, N] (the forward weight, read in place)
   if (!xrole) {
     const float* wp = W + (size_t)(8 * h) * N + col;
 #pragma unroll
@@ -796,10 +738,7 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float v = wp[(size_t)(ks * 16 + j) * N];
-        const __bf16 a = (__bf16)v;
-        const float r1 = v - (float)a;
-        const __bf16 b = (__bf16)r1;
-        wb[ks][0][j] = a; wb[ks][1][j] = b; wb[ks][2][j] = (__bf16)(r1 - (float)b);
+        MMG_SPLIT3(v, wb[ks][0][j], wb[ks][1][j], wb[ks][2][j]);
       }
   }
   NextBnCol nbc = {};
@@ -849,19 +788,18 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
   int ridx[MODE == 3 ? NP : 1];             // MODE 3: list positions of the rows of the tile the NEXT fetch serves
   auto fetch_idx = [&](int64_t tile) __attribute__((always_inline)) {
     const int rows = rows_of(tile);
-    const __amdgpu_buffer_rsrc_t ps = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<int32_t*>(bb.row_pos) + (size_t)(rows ? tile : 0) * BM, 0, rows * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ps = mmg_rsrc(bb.row_pos + (size_t)(rows ? tile : 0) * BM, rows * 4);
 #pragma unroll
     for (int p = 0; p < NP; ++p) ridx[p] = rows ? (int)__builtin_amdgcn_raw_buffer_load_b32(ps, (p * ROWS_PER_PASS + prow) * 4, 0, 0) : -1;
   };
   auto fetch = [&](int64_t tile) __attribute__((always_inline)) {
     const int rows = rows_of(tile);
     const size_t off = (size_t)(rows ? tile : 0) * BM * K;
-    const __amdgpu_buffer_rsrc_t ysrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bb.Y) + off, 0, rows * K * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ysrc = mmg_rsrc(bb.Y + off, rows * K * 4);
     if constexpr (MODE == 3) {
       // the listed rows through one descriptor over the whole list: a row that is not listed (or past the end) gets an
       // offset behind the list and reads 0
-      const __amdgpu_buffer_rsrc_t gs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(G), 0, (int)(bb.n_sel * K * 4), 0x00020000);
+      const __amdgpu_buffer_rsrc_t gs = mmg_rsrc(G, (int)(bb.n_sel * K * 4));
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
         const unsigned vo = ridx[p] >= 0 && p * ROWS_PER_PASS + prow < rows ? (unsigned)ridx[p] * (unsigned)(K * 4) + (unsigned)(kc4 * 16) : 0xFFFFFF00u;
@@ -871,14 +809,14 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
       fetch_idx(tile + GY);
       return;
     }
-    const __amdgpu_buffer_rsrc_t gs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(G) + off, 0, rows * K * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t gs = mmg_rsrc(G + off, rows * K * 4);
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
       ng[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(gs, xvo, p * ROWS_PER_PASS * K * 4, MMG_NT_LD));
       ny[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ysrc, xvo, p * ROWS_PER_PASS * K * 4, MMG_NT_LD));
     }
     if constexpr (MODE == 2) {
-      const __amdgpu_buffer_rsrc_t g2s = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bb.G2) + off, 0, rows * K * 4, 0x00020000);
+      const __amdgpu_buffer_rsrc_t g2s = mmg_rsrc(bb.G2 + off, rows * K * 4);
 #pragma unroll
       for (int p = 0; p < NP; ++p)
         ng2[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(g2s, xvo, p * ROWS_PER_PASS * K * 4, MMG_NT_LD));
@@ -887,8 +825,7 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
   auto stage = [&](int64_t tile, int buf) __attribute__((always_inline)) {   // BatchNorm backward of the tile in ng / ny, dZ out, split, three plane writes
     const int64_t row0 = tile * BM;
     const int rows = rows_of(tile);
-    const __amdgpu_buffer_rsrc_t zs = __builtin_amdgcn_make_buffer_rsrc(
-        bb.dZ + (size_t)(rows && bb.dZ ? tile : 0) * BM * K, 0, bb.dZ ? rows * K * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t zs = mmg_rsrc(bb.dZ + (size_t)(rows && bb.dZ ? tile : 0) * BM * K, bb.dZ ? rows * K * 4 : 0);
     __bf16* pb = planes + (size_t)buf * 3 * BM * LDP;
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
@@ -934,18 +871,13 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
       }
       if constexpr (FW)
         if (r >= rows) v = zero;           // rows past the end: nothing to the weight gradient (their stores are dropped)
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(xu32x4, v), zs, xvo, p * ROWS_PER_PASS * K * 4, 0);
-      xbf16x4 q0, q1, q2;
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), zs, xvo, p * ROWS_PER_PASS * K * 4, 0);
+      bf16x4 q0, q1, q2;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const __bf16 a = (__bf16)v[j];
-        const float r1 = v[j] - (float)a;
-        const __bf16 b = (__bf16)r1;
-        q0[j] = a; q1[j] = b; q2[j] = (__bf16)(r1 - (float)b);
-      }
-      *reinterpret_cast<xbf16x4*>(pb + (0 * BM + r) * LDP + kc4 * 4) = q0;
-      *reinterpret_cast<xbf16x4*>(pb + (1 * BM + r) * LDP + kc4 * 4) = q1;
-      *reinterpret_cast<xbf16x4*>(pb + (2 * BM + r) * LDP + kc4 * 4) = q2;
+      for (int j = 0; j < 4; ++j) MMG_SPLIT3(v[j], q0[j], q1[j], q2[j]);
+      *reinterpret_cast<bf16x4*>(pb + (0 * BM + r) * LDP + kc4 * 4) = q0;
+      *reinterpret_cast<bf16x4*>(pb + (1 * BM + r) * LDP + kc4 * 4) = q1;
+      *reinterpret_cast<bf16x4*>(pb + (2 * BM + r) * LDP + kc4 * 4) = q2;
     }
   };
   if (xrole) {
@@ -957,8 +889,7 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
     f32x4 nx[XU];                                   // the NEXT tile of X
     auto xfetch = [&](int64_t tile) __attribute__((always_inline)) {
       const int rows = rows_of(tile);
-      const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<float*>(wg.X) + (size_t)(rows ? tile : 0) * BM * N, 0, rows * N * 4, 0x00020000);
+      const __amdgpu_buffer_rsrc_t xsrc = mmg_rsrc(wg.X + (size_t)(rows ? tile : 0) * BM * N, rows * N * 4);
 #pragma unroll
       for (int u = 0; u < XU; ++u)
         nx[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xvo2, u * (NTHR / 32) * N * 4, MMG_NT_LD));
@@ -986,17 +917,12 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
           mmg_drop4(v, wg.xpr.key, (uint64_t)(wg.xpr.row_offset + tile * BM + r) * (uint64_t)N + (uint64_t)(xc4 * 4),
                     wg.xpr.thr, wg.xpr.inv_keep);
         // rows past the end need no zeroing: their dZ rows are zero
-        xbf16x4 q0, q1, q2;
+        bf16x4 q0, q1, q2;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const __bf16 a = (__bf16)v[j];
-          const float r1 = v[j] - (float)a;
-          const __bf16 b = (__bf16)r1;
-          q0[j] = a; q1[j] = b; q2[j] = (__bf16)(r1 - (float)b);
-        }
-        *reinterpret_cast<xbf16x4*>(xb + (0 * BM + r) * SX + xc4 * 4) = q0;
-        *reinterpret_cast<xbf16x4*>(xb + (1 * BM + r) * SX + xc4 * 4) = q1;
-        *reinterpret_cast<xbf16x4*>(xb + (2 * BM + r) * SX + xc4 * 4) = q2;
+        for (int j = 0; j < 4; ++j) MMG_SPLIT3(v[j], q0[j], q1[j], q2[j]);
+        *reinterpret_cast<bf16x4*>(xb + (0 * BM + r) * SX + xc4 * 4) = q0;
+        *reinterpret_cast<bf16x4*>(xb + (1 * BM + r) * SX + xc4 * 4) = q1;
+        *reinterpret_cast<bf16x4*>(xb + (2 * BM + r) * SX + xc4 * 4) = q2;
       }
     };
     // wave w owns the quadrant (w >> 1, w & 1) of dW [K, N]; transposing-read lane roles as in k_linear_wgrad_x6
@@ -1029,7 +955,7 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
       const __bf16* xb = xplanes + (size_t)buf * 3 * BM * SX + tr_row * SX + qk * 64 + tr_col;
 #pragma unroll
       for (int ks = 0; ks < BM / 16; ++ks) {
-        xbf16x8 fa[2][3], fb[2][3];
+        bf16x8 fa[2][3], fb[2][3];
 #pragma unroll
         for (int x = 0; x < 2; ++x)
 #pragma unroll
@@ -1050,13 +976,13 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
       if (has_bias) {
         const __bf16* zp = planes + (size_t)buf * 3 * BM * LDP + bc0;
         if (wg.bias_order == 0) {              // k_linear_wgrad_ws: group g, rows 8 g .. 8 g + 7 in order
-          typedef __bf16 xbf16x2 __attribute__((ext_vector_type(2)));
+          typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
             const int r = 8 * bg + j;
-            const xbf16x2 a = *reinterpret_cast<const xbf16x2*>(zp + r * LDP);
-            const xbf16x2 b = *reinterpret_cast<const xbf16x2*>(zp + (BM + r) * LDP);
-            const xbf16x2 c = *reinterpret_cast<const xbf16x2*>(zp + (2 * BM + r) * LDP);
+            const bf16x2 a = *reinterpret_cast<const bf16x2*>(zp + r * LDP);
+            const bf16x2 b = *reinterpret_cast<const bf16x2*>(zp + (BM + r) * LDP);
+            const bf16x2 c = *reinterpret_cast<const bf16x2*>(zp + (2 * BM + r) * LDP);
 #pragma unroll
             for (int e = 0; e < 2; ++e) bacc[e] += ((float)a[e] + (float)b[e]) + (float)c[e];
           }
@@ -1064,9 +990,9 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
             const int r = bg + 16 * u;
-            const xbf16x8 a = *reinterpret_cast<const xbf16x8*>(zp + r * LDP);
-            const xbf16x8 b = *reinterpret_cast<const xbf16x8*>(zp + (BM + r) * LDP);
-            const xbf16x8 c = *reinterpret_cast<const xbf16x8*>(zp + (2 * BM + r) * LDP);
+            const bf16x8 a = *reinterpret_cast<const bf16x8*>(zp + r * LDP);
+            const bf16x8 b = *reinterpret_cast<const bf16x8*>(zp + (BM + r) * LDP);
+            const bf16x8 c = *reinterpret_cast<const bf16x8*>(zp + (2 * BM + r) * LDP);
 #pragma unroll
             for (int e = 0; e < 8; ++e) bacc[e] += ((float)a[e] + (float)b[e]) + (float)c[e];
           }
@@ -1109,8 +1035,7 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
     const int yvo = ((4 * h) * N + wn * 32 + l31) * 4;     // C/D map: col = lane&31, row = (i&3) + 8*(i>>2) + 4*(lane>>5)
     auto tile_body = [&](int64_t tt, int buf) __attribute__((always_inline)) {
       const int rows = rows_of(tt);
-      const __amdgpu_buffer_rsrc_t xs = __builtin_amdgcn_make_buffer_rsrc(
-          DX + (size_t)(rows ? tt : 0) * BM * N, 0, rows * N * 4, 0x00020000);
+      const __amdgpu_buffer_rsrc_t xs = mmg_rsrc(DX + (size_t)(rows ? tt : 0) * BM * N, rows * N * 4);
       f32x16 acc;
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[i] = 0.f;
@@ -1122,21 +1047,16 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
       const __bf16* ap = planes + (size_t)buf * 3 * BM * LDP + l31 * LDP + 8 * h;
 #pragma unroll
       for (int ks = 0; ks < NK; ++ks) {
-        const xbf16x8 a1f = *reinterpret_cast<const xbf16x8*>(ap + ks * 16);
-        const xbf16x8 a2f = *reinterpret_cast<const xbf16x8*>(ap + BM * LDP + ks * 16);
-        const xbf16x8 a3f = *reinterpret_cast<const xbf16x8*>(ap + 2 * BM * LDP + ks * 16);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3f, wb[ks][0], acc, 0, 0, 0);   // small terms first
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1f, wb[ks][2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2f, wb[ks][1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2f, wb[ks][0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1f, wb[ks][1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1f, wb[ks][0], acc, 0, 0, 0);
+        const bf16x8 a1f = *reinterpret_cast<const bf16x8*>(ap + ks * 16);
+        const bf16x8 a2f = *reinterpret_cast<const bf16x8*>(ap + BM * LDP + ks * 16);
+        const bf16x8 a3f = *reinterpret_cast<const bf16x8*>(ap + 2 * BM * LDP + ks * 16);
+        MMG_X6_ALO(acc, a1f, a2f, a3f, wb[ks][0], wb[ks][1], wb[ks][2]);
       }
       float vv[16];
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         vv[i] = acc[i];                        // (a bit_cast straight from the vector element stored element 0 sixteen times)
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[i]), xs, yvo, ((i & 3) + 8 * (i >> 2)) * N * 4,
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[i]), xs, yvo, mmg_c_row(i) * N * 4,
                                               MMG_NT_ST);
       }
       if constexpr (NBN) next_bn_tile(nb, nbc, vv, nby, rows, tt * BM, N, col, lane, cs1, cs2);
@@ -1325,10 +1245,8 @@ __global__ __launch_bounds__(64 * WNN * WNK) void k_linear_wgrad_x6(const float*
     const int64_t left = M - r0;
     const int rows = st < n_st ? (left < WG_ROWS ? (int)left : WG_ROWS) : 0;
     const int64_t rb = rows ? r0 : 0;
-    const __amdgpu_buffer_rsrc_t ys = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(dY) + (size_t)rb * N + tn0, 0, rows ? (rows * N - tn0) * 4 : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(X) + (size_t)rb * K + tk0, 0, rows ? (rows * K - tk0) * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ys = mmg_rsrc(dY + (size_t)rb * N + tn0, rows ? (rows * N - tn0) * 4 : 0);
+    const __amdgpu_buffer_rsrc_t xs = mmg_rsrc(X + (size_t)rb * K + tk0, rows ? (rows * K - tk0) * 4 : 0);
 #pragma unroll
     for (int u = 0; u < NY; ++u)
       fy[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ys, yvo, u * RY * N * 4, MMG_NT_WG));
@@ -1337,17 +1255,12 @@ __global__ __launch_bounds__(64 * WNN * WNK) void k_linear_wgrad_x6(const float*
       fx[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xs, xvo, u * RX * K * 4, MMG_NT_WG));
   };
   auto split_store = [&](f32x4 v, __bf16* plane0, int plane_elems, int off) {
-    xbf16x4 q0, q1, q2;
+    bf16x4 q0, q1, q2;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const __bf16 a = (__bf16)v[j];
-      const float r1 = v[j] - (float)a;
-      const __bf16 b = (__bf16)r1;
-      q0[j] = a; q1[j] = b; q2[j] = (__bf16)(r1 - (float)b);
-    }
-    *reinterpret_cast<xbf16x4*>(plane0 + off) = q0;
-    *reinterpret_cast<xbf16x4*>(plane0 + plane_elems + off) = q1;
-    *reinterpret_cast<xbf16x4*>(plane0 + 2 * plane_elems + off) = q2;
+    for (int j = 0; j < 4; ++j) MMG_SPLIT3(v[j], q0[j], q1[j], q2[j]);
+    *reinterpret_cast<bf16x4*>(plane0 + off) = q0;
+    *reinterpret_cast<bf16x4*>(plane0 + plane_elems + off) = q1;
+    *reinterpret_cast<bf16x4*>(plane0 + 2 * plane_elems + off) = q2;
   };
   // prologue constants of this thread's column quad (identity when a part is absent: x*1+0, max(x,-inf))
   f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
@@ -1408,7 +1321,7 @@ __global__ __launch_bounds__(64 * WNN * WNK) void k_linear_wgrad_x6(const float*
     const __bf16* xb = wplanes + (size_t)buf * (PY + PX) + PY + tr_row * SX + wk * (TK / WNK) + tr_col;
 #pragma unroll
     for (int ks = 0; ks < WG_ROWS / 16; ++ks) {
-      xbf16x8 a[MT][3], b[KT][3];
+      bf16x8 a[MT][3], b[KT][3];
 #pragma unroll
       for (int x = 0; x < MT; ++x)
 #pragma unroll
@@ -1420,14 +1333,7 @@ __global__ __launch_bounds__(64 * WNN * WNK) void k_linear_wgrad_x6(const float*
 #pragma unroll
       for (int x = 0; x < MT; ++x)
 #pragma unroll
-        for (int y = 0; y < KT; ++y) {
-          acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[x][2], b[y][0], acc[x][y], 0, 0, 0);   // small terms first
-          acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[x][0], b[y][2], acc[x][y], 0, 0, 0);
-          acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[x][1], b[y][1], acc[x][y], 0, 0, 0);
-          acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[x][1], b[y][0], acc[x][y], 0, 0, 0);
-          acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[x][0], b[y][1], acc[x][y], 0, 0, 0);
-          acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[x][0], b[y][0], acc[x][y], 0, 0, 0);
-        }
+        for (int y = 0; y < KT; ++y) MMG_X6_ALO(acc[x][y], a[x][0], a[x][1], a[x][2], b[y][0], b[y][1], b[y][2]);
     }
     __syncthreads();
   };
@@ -1510,26 +1416,20 @@ __global__ __launch_bounds__(512) void k_linear_wgrad_ws(const float* __restrict
       const int64_t r0 = ((int64_t)by + (int64_t)st * G) * WG_ROWS;
       const int64_t left = M - r0;
       const int rows = st < n_st ? (left < WG_ROWS ? (int)left : WG_ROWS) : 0;
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<float*>(src) + (size_t)(rows ? r0 : 0) * ld + c0, 0, rows ? (rows * ld - c0) * 4 : 0, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs = mmg_rsrc(src + (size_t)(rows ? r0 : 0) * ld + c0, rows ? (rows * ld - c0) * 4 : 0);
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         f[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, j * ld * 4, MMG_NT_WG));
     };
     f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
     auto stage = [&](int st, int buf, const f32x4* f) {
-      xbf16x8 q[3][4];                             // [piece][column of the quad] = 8 rows
+      bf16x8 q[3][4];                             // [piece][column of the quad] = 8 rows
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const f32x4 v = f[j];                      // rows past the end arrive as zeros
         bsum += v;                                 // column sums of dY (the bias gradient); ignored by the X waves
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const __bf16 a = (__bf16)v[e];
-          const float r1 = v[e] - (float)a;
-          const __bf16 b = (__bf16)r1;
-          q[0][e][j] = a; q[1][e][j] = b; q[2][e][j] = (__bf16)(r1 - (float)b);
-        }
+        for (int e = 0; e < 4; ++e) MMG_SPLIT3(v[e], q[0][e][j], q[1][e][j], q[2][e][j]);
       }
       // column c of a group sits at entry (c & ~15) | ((c / 4 + 4 (c % 4)) & 15): 16 consecutive lanes then touch 16
       // distinct 16-B bank groups both here (lane = column quad, fixed e) and in the fragment reads (lane = column)
@@ -1538,7 +1438,7 @@ __global__ __launch_bounds__(512) void k_linear_wgrad_ws(const float* __restrict
       for (int pc = 0; pc < 3; ++pc)
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          *reinterpret_cast<xbf16x8*>(base + pc * 4 * GRP + ((c4 + 4 * e) & 15) * 8) = q[pc][e];
+          *reinterpret_cast<bf16x8*>(base + pc * 4 * GRP + ((c4 + 4 * e) & 15) * 8) = q[pc][e];
     };
 #pragma unroll
     for (int j = 0; j < RING; ++j) fetch(j, ring[j]);
@@ -1595,13 +1495,13 @@ __global__ __launch_bounds__(512) void k_linear_wgrad_ws(const float* __restrict
           const __bf16* pb = wplanes + (size_t)j * BUF;
 #pragma unroll
           for (int ks = 0; ks < WG_ROWS / 16; ++ks) {
-            xbf16x8 a[2][3], b[2][3];
+            bf16x8 a[2][3], b[2][3];
 #pragma unroll
             for (int x = 0; x < 2; ++x)
 #pragma unroll
               for (int pc = 0; pc < 3; ++pc) {
-                a[x][pc] = *reinterpret_cast<const xbf16x8*>(pb + ya[x] + (pc * 4 + 2 * ks) * GRP);
-                b[x][pc] = *reinterpret_cast<const xbf16x8*>(pb + xa[x] + (pc * 4 + 2 * ks) * GRP);
+                a[x][pc] = *reinterpret_cast<const bf16x8*>(pb + ya[x] + (pc * 4 + 2 * ks) * GRP);
+                b[x][pc] = *reinterpret_cast<const bf16x8*>(pb + xa[x] + (pc * 4 + 2 * ks) * GRP);
               }
             // small terms first; consecutive MFMAs go to different accumulators
             constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
@@ -1664,8 +1564,8 @@ int launch_wgrad_x6(dim3 grid, hipStream_t st, const float* dY, const float* X, 
 struct EpiStore {
   float* out; int accumulate;
   float* out2; int64_t n4_first;          // elements past n4_first float4s go to out2 (the bias sums behind a dW slab)
-  __device__ void operator()(int64_t i4, mmg_f4 v) const {
-    mmg_f4* o = i4 < n4_first ? reinterpret_cast<mmg_f4*>(out) + i4 : reinterpret_cast<mmg_f4*>(out2) + (i4 - n4_first);
+  __device__ void operator()(int64_t i4, f32x4 v) const {
+    f32x4* o = i4 < n4_first ? reinterpret_cast<f32x4*>(out) + i4 : reinterpret_cast<f32x4*>(out2) + (i4 - n4_first);
     *o = accumulate ? (*o + v) : v;
   }
 };
@@ -2061,17 +1961,17 @@ namespace {
 struct WgradReduceTable { mmg_wgrad_reduce_t j[MMG_WGRAD_REDUCE_MAX]; };
 // the slab sums of several weight gradients in ONE launch: blockIdx.y = job, the body of mmg_k_reduce_slabs<EpiStore>
 __global__ __launch_bounds__(256) void k_wgrad_reduce_group(WgradReduceTable tb) {
-  __shared__ mmg_f4 part[16][16];
+  __shared__ f32x4 part[16][16];
   const mmg_wgrad_reduce_t jb = tb.j[blockIdx.y];
   const int e = threadIdx.x & 15, g = threadIdx.x >> 4;
   const int64_t i4 = (int64_t)blockIdx.x * 16 + e;
   if ((int64_t)blockIdx.x * 16 >= jb.n4) return;               // (uniform per block)
-  mmg_f4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   if (i4 < jb.n4) {
-    const mmg_f4* base = reinterpret_cast<const mmg_f4*>(jb.slab) + i4;
+    const f32x4* base = reinterpret_cast<const f32x4*>(jb.slab) + i4;
     int sidx = g;
     for (; sidx + 7 * 16 < jb.n_split; sidx += 8 * 16) {
-      mmg_f4 v[8];
+      f32x4 v[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) v[u] = base[(size_t)(sidx + u * 16) * jb.n4];
 #pragma unroll
@@ -2082,7 +1982,7 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce_group(WgradReduceTable tb)
   part[g][e] = acc;
   __syncthreads();
   if (g == 0 && i4 < jb.n4) {
-    mmg_f4 t = part[0][e];
+    f32x4 t = part[0][e];
 #pragma unroll
     for (int q = 1; q < 16; ++q) t += part[q][e];
     EpiStore{jb.dW, jb.accumulate, jb.dbias, jb.nk4}(i4, t);

@@ -9,10 +9,10 @@
 // and indices through a software pipeline of unconditional buffer loads.
 // k_pair_bwd (thread-per-pair on the vector ALUs, LDS accumulators for dB) remains for lab vocabularies > 128 rows.
 #include "common.h"
+#include "mma.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int PT = 256;          // pairs per workgroup tile == threads
 constexpr uint32_t SITE_H1 = 64, SITE_H2 = 65;
 
@@ -208,10 +208,6 @@ __global__ __launch_bounds__(PT) void k_pair_bwd(HeadDev H, HeadGradDev Gd, cons
 //   (4) dB[lab,k]      += [li[pair]==lab] * dH1[pair,k]    12*LT bf16 MFMA (exact: one-hot x 3-way bf16 split of dH1)
 // dA[pi] is flushed with run-length pre-reduction (pairs arrive sorted by patient).  Rounds 1-2 ran all of it in ONE wave
 // per tile (k_pair_bwd_mfma: ~500 registers, one wave per SIMD); k_pair_bwd_duo below splits it between two.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 pbf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned pu32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned pu32x4 __attribute__((ext_vector_type(4)));
 constexpr int TP = 32;                 // pairs per wave tile
 
 // Every INDEXED access of the two matrix-core pair kernels goes through a buffer descriptor whose base and byte length
@@ -231,9 +227,6 @@ struct PairBufs {
   uint32_t b_bytes;                         // n_labs * 256: rows of B
   int32_t n_pat;
 };
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t pair_rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
 __device__ __forceinline__ int pair_ld_i32(__amdgpu_buffer_rsrc_t d, unsigned byte_off) {
   return (int)__builtin_amdgcn_raw_buffer_load_b32(d, (int)byte_off, 0, 0);
 }
@@ -243,7 +236,7 @@ __device__ __forceinline__ f32x4 pair_ld_f4(__amdgpu_buffer_rsrc_t d, unsigned b
 constexpr int LDH = 68;                // H1 / dH1 tile row stride (floats)
 constexpr int LDD = 36;                // D2 tile row stride
 
-__device__ inline int crow(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+__device__ inline int crow(int reg, int h) { return mmg_c_row(reg) + 4 * h; }
 
 // Layer-2 dropout keeps in the MFMA C layout (lane = unit u, register r = pair row crow(r, h)): the element
 // (pair id, u) belongs to the RNG group (pair id * 8 + u / 4), shared by the four lanes of a quad.  Instead of every
@@ -320,13 +313,13 @@ __device__ __forceinline__ void pair_bwd_front(const HeadDev& H, const int32_t* 
   // A / B row halves.  A stage only ISSUES loads; they are finalised one iteration later.  Every load is unconditional and
   // BOUNDED by a host-sized descriptor (a branch around a load makes the compiler's vmcnt waits conservative).
   struct Meta { int k; int p_i; int l_i; int o; uint64_t pid; };
-  const __amdgpu_buffer_rsrc_t sel_d = pair_rsrc(sel ? sel : pi, sel ? (uint32_t)(n * 4) : 0u);
-  const __amdgpu_buffer_rsrc_t io_d = pair_rsrc(pb.io, pb.io_bytes), pid_d = pair_rsrc(pb.pid, pb.pid_bytes);
-  const __amdgpu_buffer_rsrc_t pi_d = pair_rsrc(pi, pb.pair_bytes), li_d = pair_rsrc(li, pb.pair_bytes);
-  const __amdgpu_buffer_rsrc_t dp_d = pair_rsrc(dpred, pb.pair_bytes), deg_d = pair_rsrc(deg, pb.pat_bytes);
-  const __amdgpu_buffer_rsrc_t A_d = pair_rsrc(H.A, pb.a_bytes), B_d = pair_rsrc(H.B, pb.b_bytes);
+  const __amdgpu_buffer_rsrc_t sel_d = mmg_rsrc(sel ? sel : pi, sel ? (uint32_t)(n * 4) : 0u);
+  const __amdgpu_buffer_rsrc_t io_d = mmg_rsrc(pb.io, pb.io_bytes), pid_d = mmg_rsrc(pb.pid, pb.pid_bytes);
+  const __amdgpu_buffer_rsrc_t pi_d = mmg_rsrc(pi, pb.pair_bytes), li_d = mmg_rsrc(li, pb.pair_bytes);
+  const __amdgpu_buffer_rsrc_t dp_d = mmg_rsrc(dpred, pb.pair_bytes), deg_d = mmg_rsrc(deg, pb.pat_bytes);
+  const __amdgpu_buffer_rsrc_t A_d = mmg_rsrc(H.A, pb.a_bytes), B_d = mmg_rsrc(H.B, pb.b_bytes);
   const bool has_sel = sel != nullptr, has_io = pb.io_bytes != 0u, has_pid = pb.pid_bytes != 0u;
-  struct RawMeta { int k, p, l; pu32x2 o2, d2; };
+  struct RawMeta { int k, p, l; u32x2 o2, d2; };
   auto issue_k = [&](int64_t t) {
     const int64_t idx = t * TP + l31;
     return pair_ld_i32(sel_d, (unsigned)(idx < n ? idx : 0) * 4u);
@@ -533,23 +526,20 @@ __device__ __forceinline__ void pair_bwd_back(float* __restrict__ dA, float drop
         //      products are exact and the fp32 accumulation matches the fp32 path up to order -- at 1/5 of its matrix time.
 #pragma unroll
         for (int t2 = 0; t2 < 2; ++t2) {
-          pbf16x8 bp[2][3];
+          bf16x8 bp[2][3];
 #pragma unroll
           for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
               const float v = dh[8 * t2 + j][ct];
-              const __bf16 a = (__bf16)v;
-              const float r1 = v - (float)a;
-              const __bf16 b = (__bf16)r1;
-              bp[ct][0][j] = a; bp[ct][1][j] = b; bp[ct][2][j] = (__bf16)(r1 - (float)b);
+              MMG_SPLIT3(v, bp[ct][0][j], bp[ct][1][j], bp[ct][2][j]);
             }
           int labs[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) labs[j] = XL[par][w][crow(8 * t2 + j, h)];
 #pragma unroll
           for (int lt = 0; lt < LT; ++lt) {
-            pbf16x8 oh;
+            bf16x8 oh;
 #pragma unroll
             for (int j = 0; j < 8; ++j) oh[j] = (labs[j] == lt * 32 + l31) ? (__bf16)1.0f : (__bf16)0.0f;
 #pragma unroll
@@ -669,7 +659,7 @@ __global__ __launch_bounds__(512) void k_pair_bwd_duo(HeadDev H, HeadGradDev Gd,
 // the SIMD issues vector work, so the 96 of them per tile in k_pair_bwd_duo (6,144 cycles) simply ADD to the vector time
 // of both waves -- measured: front alone 151 us, back alone 116 us, both 193 us; raising the matrix wave's priority
 // (s_setprio) changes nothing.  The bf16 matrix pipe runs BESIDE the vector ALU.  Here (1), (2) and (3) use the exact
-// six-term bf16 split of gemm.hip (fp32-grade: the three pieces of an fp32 value are exact, six of the nine cross terms
+// six-term bf16 split of mma.h (fp32-grade: the three pieces of an fp32 value are exact, six of the nine cross terms
 // are kept, fp32 accumulation), 24 matrix instructions of 32 cycles each instead of 32 of 64, and what the split costs in
 // vector instructions issues in their shadow or in the other wave's:
 //   front wave: load pipeline, h1 -> its three bf16 pieces (registers: A of (1); row-major LDS planes: B of (2) through
@@ -687,34 +677,8 @@ constexpr int F6_LDS = 3 * TP * 4 + 3 * TP * P1S * 2 + TP * LDD * 4;   // bytes 
 constexpr int B6_LDS = 2 * TP * 4;                   // bytes private to a back wave: run id per pair | patient per run
 constexpr int H6_LDS = TP * LDD * 4 + TP * 2 * 4;    // bytes per hand-off buffer: D2 tile | sign bits
 
-__device__ __forceinline__ void psplit8(const float* v, pbf16x8& p0, pbf16x8& p1, pbf16x8& p2) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 a = (__bf16)v[j];
-    const float r1 = v[j] - (float)a;
-    const __bf16 b = (__bf16)r1;
-    p0[j] = a; p1[j] = b; p2[j] = (__bf16)(r1 - (float)b);
-  }
-}
-// six exact products, small terms first (the order of k_pair_fwd_mfma and gemm.hip)
-#define MMG_X6(acc, a, b)                                                     \
-  do {                                                                        \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc, 0, 0, 0);  \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc, 0, 0, 0);  \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc, 0, 0, 0);  \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc, 0, 0, 0);  \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc, 0, 0, 0);  \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);  \
-  } while (0)
-
-typedef short ps16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ pbf16x8 tr_pair(const __bf16* p_lo, const __bf16* p_hi) {   // 4 + 4 rows of this lane's column
-  const ps16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ps16x4*)p_lo);
-  const ps16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ps16x4*)p_hi);
-  typedef short ps16x8 __attribute__((ext_vector_type(8)));
-  const ps16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(pbf16x8, v);
-}
+// The six exact products of this backward are MMG_X6_BLO (mma.h): in (1), whose operands are the forward's swapped, that is
+// the forward's own term order.
 
 // SAVED: the forward left the sign bits of h1 and the layer-2 activations of every pair it visited (mmg_pair_saved_t):
 // no RNG, no (1) and no layer-2 epilogue arithmetic -- h1 = bit ? (A + B) / (1 - p) : 0, the layer-2 mask is the sign
@@ -740,14 +704,14 @@ __device__ __forceinline__ void pair_bwd6_front(const HeadDev& H, const int32_t*
   const uint32_t key1 = mmg_rng_key(seed, SITE_H1);
   const float b2v = H.b2[l31], w3v = H.W3[l31];
   // B of (1): W2[unit = l31][k = 16 ks + 8 h + j] as three exact bf16 pieces
-  pbf16x8 w2p[SAVED ? 1 : 4][3];
+  bf16x8 w2p[SAVED ? 1 : 4][3];
   if constexpr (!SAVED) {
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       float v[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = H.W2[l31 * 64 + 16 * ks + 8 * h + j];
-      psplit8(v, w2p[ks][0], w2p[ks][1], w2p[ks][2]);
+      mmg_split8(v, w2p[ks][0], w2p[ks][1], w2p[ks][2]);
     }
   }
   float w3acc = 0.f, b2acc = 0.f, b3acc = 0.f;
@@ -757,16 +721,16 @@ __device__ __forceinline__ void pair_bwd6_front(const HeadDev& H, const int32_t*
   const int64_t wave_id = (int64_t)blockIdx.x * 4 + w, n_waves = (int64_t)gridDim.x * 4;
   // the three-deep load pipeline of k_pair_bwd_duo; the row halves in the FORWARD's order: register q of a lane holds
   // k = 16 (q >> 1) + 8 h + 4 (q & 1) + 0..3, so that a k-step's eight values are lane-local
-  pu32x2 sbw = {0u, 0u};                            // SAVED: the pair's 64 sign bits / this lane's 16 saved activations
+  u32x2 sbw = {0u, 0u};                            // SAVED: the pair's 64 sign bits / this lane's 16 saved activations
   f32x4 sh2[SAVED ? 4 : 1];
   struct Meta { int k; int p_i; int l_i; int o; uint64_t pid; };
-  const __amdgpu_buffer_rsrc_t sel_d = pair_rsrc(sel ? sel : pi, sel ? (uint32_t)(n * 4) : 0u);
-  const __amdgpu_buffer_rsrc_t io_d = pair_rsrc(pb.io, pb.io_bytes), pid_d = pair_rsrc(pb.pid, pb.pid_bytes);
-  const __amdgpu_buffer_rsrc_t pi_d = pair_rsrc(pi, pb.pair_bytes), li_d = pair_rsrc(li, pb.pair_bytes);
-  const __amdgpu_buffer_rsrc_t dp_d = pair_rsrc(dpred, pb.pair_bytes), deg_d = pair_rsrc(deg, pb.pat_bytes);
-  const __amdgpu_buffer_rsrc_t A_d = pair_rsrc(H.A, pb.a_bytes), B_d = pair_rsrc(H.B, pb.b_bytes);
+  const __amdgpu_buffer_rsrc_t sel_d = mmg_rsrc(sel ? sel : pi, sel ? (uint32_t)(n * 4) : 0u);
+  const __amdgpu_buffer_rsrc_t io_d = mmg_rsrc(pb.io, pb.io_bytes), pid_d = mmg_rsrc(pb.pid, pb.pid_bytes);
+  const __amdgpu_buffer_rsrc_t pi_d = mmg_rsrc(pi, pb.pair_bytes), li_d = mmg_rsrc(li, pb.pair_bytes);
+  const __amdgpu_buffer_rsrc_t dp_d = mmg_rsrc(dpred, pb.pair_bytes), deg_d = mmg_rsrc(deg, pb.pat_bytes);
+  const __amdgpu_buffer_rsrc_t A_d = mmg_rsrc(H.A, pb.a_bytes), B_d = mmg_rsrc(H.B, pb.b_bytes);
   const bool has_sel = sel != nullptr, has_io = pb.io_bytes != 0u, has_pid = pb.pid_bytes != 0u;
-  struct RawMeta { int k, p, l; pu32x2 o2, d2; };
+  struct RawMeta { int k, p, l; u32x2 o2, d2; };
   auto issue_k = [&](int64_t t) {
     const int64_t idx = t * TP + l31;
     return pair_ld_i32(sel_d, (unsigned)(idx < n ? idx : 0) * 4u);
@@ -809,7 +773,7 @@ __device__ __forceinline__ void pair_bwd6_front(const HeadDev& H, const int32_t*
     }
     if constexpr (SAVED) {          // (a pair that is not one -- p_i < 0 -- reads entry 0: always inside the buffers)
       const size_t kc = m.p_i >= 0 ? (size_t)(sv_by_pos ? tile * TP + l31 : (int64_t)m.k) : 0;
-      sbw = *reinterpret_cast<const pu32x2*>(sv_bits + kc * 2);
+      sbw = *reinterpret_cast<const u32x2*>(sv_bits + kc * 2);
 #pragma unroll
       for (int q = 0; q < 4; ++q) sh2[q] = *reinterpret_cast<const f32x4*>(sv_h2 + kc * 32 + 16 * h + 4 * q);
     }
@@ -853,11 +817,11 @@ __device__ __forceinline__ void pair_bwd6_front(const HeadDev& H, const int32_t*
         }
         if constexpr (SAVED) {
           // a pair of the tile that is not this head's was never written by the forward: its entry is arbitrary memory
-          const pu32x2 bwv = active ? sbw : pu32x2{0u, 0u};
+          const u32x2 bwv = active ? sbw : u32x2{0u, 0u};
           const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int q = 0; q < 4; ++q) *reinterpret_cast<f32x4*>(T2 + l31 * LDD + 16 * h + 4 * q) = active ? sh2[q] : z4;
-          if (h == 0) *reinterpret_cast<pu32x2*>(XB + 2 * l31) = bwv;
+          if (h == 0) *reinterpret_cast<u32x2*>(XB + 2 * l31) = bwv;
 #pragma unroll
           for (int ks = 0; ks < 4; ++ks) {
             const uint32_t wbits = (bwv[ks >> 1] >> (16 * (ks & 1) + 8 * h)) & 0xFFu;
@@ -865,11 +829,11 @@ __device__ __forceinline__ void pair_bwd6_front(const HeadDev& H, const int32_t*
 #pragma unroll
             for (int j = 0; j < 8; ++j)
               x8[j] = (wbits >> j) & 1u ? (ra[2 * ks + (j >> 2)][j & 3] + rb[2 * ks + (j >> 2)][j & 3]) * inv_keep : 0.f;
-            pbf16x8 xp[3];
-            psplit8(x8, xp[0], xp[1], xp[2]);
+            bf16x8 xp[3];
+            mmg_split8(x8, xp[0], xp[1], xp[2]);
 #pragma unroll
             for (int pc = 0; pc < 3; ++pc)
-              *reinterpret_cast<pbf16x8*>(P1 + (pc * TP + l31) * P1S + 16 * ks + 8 * h) = xp[pc];
+              *reinterpret_cast<bf16x8*>(P1 + (pc * TP + l31) * P1S + 16 * ks + 8 * h) = xp[pc];
           }
         } else {
           // ---- h1 (gather-add, relu, dropout), k-step by k-step: pieces -> (1) and the planes, sign bits
@@ -888,22 +852,17 @@ __device__ __forceinline__ void pair_bwd6_front(const HeadDev& H, const int32_t*
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) bw[ks >> 1] |= x8[j] > 0.f ? (1u << (16 * (ks & 1) + j)) << (8 * h) : 0u;
-            pbf16x8 xp[3];
-            psplit8(x8, xp[0], xp[1], xp[2]);
+            bf16x8 xp[3];
+            mmg_split8(x8, xp[0], xp[1], xp[2]);
 #pragma unroll
             for (int pc = 0; pc < 3; ++pc)
-              *reinterpret_cast<pbf16x8*>(P1 + (pc * TP + l31) * P1S + 16 * ks + 8 * h) = xp[pc];
+              *reinterpret_cast<bf16x8*>(P1 + (pc * TP + l31) * P1S + 16 * ks + 8 * h) = xp[pc];
             // (1) C[pair rows, unit] = H1 . W2^T: the forward's six products in the forward's order (operands swapped)
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xp[0], w2p[ks][2], acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xp[2], w2p[ks][0], acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xp[1], w2p[ks][1], acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xp[0], w2p[ks][1], acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xp[1], w2p[ks][0], acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xp[0], w2p[ks][0], acc1, 0, 0, 0);
+            MMG_X6_BLO(acc1, xp[0], xp[1], xp[2], w2p[ks][0], w2p[ks][1], w2p[ks][2]);
           }
           bw[0] |= (uint32_t)__shfl_xor((int)bw[0], 32, 64);
           bw[1] |= (uint32_t)__shfl_xor((int)bw[1], 32, 64);
-          if (h == 0) *reinterpret_cast<pu32x2*>(XB + 2 * l31) = pu32x2{bw[0], bw[1]};
+          if (h == 0) *reinterpret_cast<u32x2*>(XB + 2 * l31) = u32x2{bw[0], bw[1]};
         }
       }
       // the row registers are consumed: the next tile's rows are requested now and have the rest of this tile to arrive
@@ -955,17 +914,17 @@ __device__ __forceinline__ void pair_bwd6_front(const HeadDev& H, const int32_t*
         // ---- (2) dW2[u,k] += D2[pair,u] * H1[pair,k]: A = d2c pieces (lane = u), B = h1 pieces of column ct * 32 + l31
 #pragma unroll
         for (int t2 = 0; t2 < 2; ++t2) {
-          pbf16x8 ap[3];
-          psplit8(d2c + 8 * t2, ap[0], ap[1], ap[2]);
+          bf16x8 ap[3];
+          mmg_split8(d2c + 8 * t2, ap[0], ap[1], ap[2]);
 #pragma unroll
           for (int ct = 0; ct < 2; ++ct) {
-            pbf16x8 bp[3];
+            bf16x8 bp[3];
 #pragma unroll
             for (int pc = 0; pc < 3; ++pc) {
               const __bf16* base = P1 + (pc * TP + 16 * t2 + 4 * h + trq) * P1S + ct * 32 + trc;
-              bp[pc] = tr_pair(base, base + 8 * P1S);
+              bp[pc] = mmg_tr_pair(base, base + 8 * P1S);
             }
-            MMG_X6(accW2[ct], ap, bp);
+            MMG_X6_BLO(accW2[ct], ap[0], ap[1], ap[2], bp[0], bp[1], bp[2]);
           }
         }
       }
@@ -1001,7 +960,7 @@ __device__ __forceinline__ void pair_bwd6_back(const HeadDev& H, float* __restri
   int* RI = reinterpret_cast<int*>(bl);             // [32] run id of a pair (-1: not a pair of this head)
   int* RP = RI + TP;                                // [32] patient of a run
   // B of (3): W2[u = 16 kq + 8 h + j][k = ct * 32 + l31] as three exact bf16 pieces
-  pbf16x8 w2t[2][2][3];
+  bf16x8 w2t[2][2][3];
 #pragma unroll
   for (int kq = 0; kq < 2; ++kq)
 #pragma unroll
@@ -1009,7 +968,7 @@ __device__ __forceinline__ void pair_bwd6_back(const HeadDev& H, float* __restri
       float v[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = H.W2[(16 * kq + 8 * h + j) * 64 + ct * 32 + l31];
-      psplit8(v, w2t[kq][ct][0], w2t[kq][ct][1], w2t[kq][ct][2]);
+      mmg_split8(v, w2t[kq][ct][0], w2t[kq][ct][1], w2t[kq][ct][2]);
     }
   f32x16 accB[LT][2];
 #pragma unroll
@@ -1045,36 +1004,37 @@ __device__ __forceinline__ void pair_bwd6_back(const HeadDev& H, float* __restri
           const f32x4 v0 = *reinterpret_cast<const f32x4*>(D2s + l31 * LDD + 16 * kq + 8 * h);
           const f32x4 v1 = *reinterpret_cast<const f32x4*>(D2s + l31 * LDD + 16 * kq + 8 * h + 4);
           const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-          pbf16x8 ap[3];
-          psplit8(v, ap[0], ap[1], ap[2]);
+          bf16x8 ap[3];
+          mmg_split8(v, ap[0], ap[1], ap[2]);
 #pragma unroll
-          for (int ct = 0; ct < 2; ++ct) MMG_X6(accH[ct], ap, w2t[kq][ct]);
+          for (int ct = 0; ct < 2; ++ct)
+            MMG_X6_BLO(accH[ct], ap[0], ap[1], ap[2], w2t[kq][ct][0], w2t[kq][ct][1], w2t[kq][ct][2]);
         }
         // through dropout + relu of layer 1: the sign bit of h1[pair crow(r,h)][ct * 32 + l31]
         float dh[16][2];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const pu32x2 bwv = *reinterpret_cast<const pu32x2*>(XB + 2 * crow(r, h));
+          const u32x2 bwv = *reinterpret_cast<const u32x2*>(XB + 2 * crow(r, h));
           dh[r][0] = (bwv[0] >> l31) & 1u ? accH[0][r] * inv_keep : 0.f;
           dh[r][1] = (bwv[1] >> l31) & 1u ? accH[1][r] * inv_keep : 0.f;
         }
         // ---- (4) dB[lab,k] += onehot(li[pair])[lab] * dH1[pair,k] (exact: one-hot x three bf16 pieces of dH1)
 #pragma unroll
         for (int t2 = 0; t2 < 2; ++t2) {
-          pbf16x8 bp[2][3];
+          bf16x8 bp[2][3];
 #pragma unroll
           for (int ct = 0; ct < 2; ++ct) {
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = dh[8 * t2 + j][ct];
-            psplit8(v, bp[ct][0], bp[ct][1], bp[ct][2]);
+            mmg_split8(v, bp[ct][0], bp[ct][1], bp[ct][2]);
           }
           int labs[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) labs[j] = XL[par][w][crow(8 * t2 + j, h)];
 #pragma unroll
           for (int lt = 0; lt < LT; ++lt) {
-            pbf16x8 oh;
+            bf16x8 oh;
 #pragma unroll
             for (int j = 0; j < 8; ++j) oh[j] = (labs[j] == lt * 32 + l31) ? (__bf16)1.0f : (__bf16)0.0f;
 #pragma unroll
@@ -1084,7 +1044,7 @@ __device__ __forceinline__ void pair_bwd6_back(const HeadDev& H, float* __restri
                 accB[lt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(oh, bp[ct][p], accB[lt][ct], 0, 0, 0);
           }
           // ---- dA[pi] += dH1, run by run, the same way: [run == row]^T . dH1 (one-hot x the same three pieces)
-          pbf16x8 ohr;
+          bf16x8 ohr;
 #pragma unroll
           for (int j = 0; j < 8; ++j) ohr[j] = (RI[crow(8 * t2 + j, h)] == l31) ? (__bf16)1.0f : (__bf16)0.0f;
 #pragma unroll
@@ -1181,15 +1141,15 @@ __global__ __launch_bounds__(512) void k_pair_bwd_duo6(HeadDev H, HeadGradDev Gd
 struct EpiPairFlush {
   float *dW2, *dB, *db2, *dW3, *db3;
   int n_labs, LT;
-  __device__ void operator()(int64_t i4, mmg_f4 v) const {
+  __device__ void operator()(int64_t i4, f32x4 v) const {
     const int i = (int)i4 * 4;
     if (i < 2048) {
-      mmg_f4* o = reinterpret_cast<mmg_f4*>(dW2 + i);
+      f32x4* o = reinterpret_cast<f32x4*>(dW2 + i);
       *o = *o + v;
     } else if (i < 2048 + LT * 2048) {
       const int j = i - 2048;
       if (j / 64 < n_labs) {
-        mmg_f4* o = reinterpret_cast<mmg_f4*>(dB + j);
+        f32x4* o = reinterpret_cast<f32x4*>(dB + j);
         *o = *o + v;
       }
     } else {
@@ -1237,19 +1197,16 @@ __global__ __launch_bounds__(256, 2) void k_pair_fwd_mfma(HeadDev H, const int32
   const float inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
   const uint32_t thr_keep = mmg_keep_threshold(drop_p);
   const uint32_t key1 = mmg_rng_key(seed, SITE_H1), key2 = mmg_rng_key(seed, SITE_H2);
-  // A operand: W2[unit = l31][k = 16 ks + 8 h + j] as three exact bf16 pieces (the 6-term split of gemm.hip: the
+  // A operand: W2[unit = l31][k = 16 ks + 8 h + j] as three exact bf16 pieces (the six-term split of mma.h: the
   // fp32 matrix instruction shares the vector ALU's multipliers -- its 2048 cycles per tile ADD to the VALU time of
   // this VALU-heavy kernel -- while the bf16 matrix pipe runs beside it)
-  pbf16x8 w2p[4][3];
+  bf16x8 w2p[4][3];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float v = H.W2[l31 * 64 + 16 * ks + 8 * h + j];
-      const __bf16 a = (__bf16)v;
-      const float r1 = v - (float)a;
-      const __bf16 b = (__bf16)r1;
-      w2p[ks][0][j] = a; w2p[ks][1][j] = b; w2p[ks][2][j] = (__bf16)(r1 - (float)b);
+      MMG_SPLIT3(v, w2p[ks][0][j], w2p[ks][1][j], w2p[ks][2][j]);
     }
   float b2r[16], w3r[16];            // this lane's 16 units: crow(r, h)
 #pragma unroll
@@ -1267,15 +1224,15 @@ __global__ __launch_bounds__(256, 2) void k_pair_fwd_mfma(HeadDev H, const int32
   // select substitutes the default).  A branch around a load makes the compiler's vmcnt waits conservative (minimum
   // over both paths) and the first version of this loop drained the whole pipeline twice per tile.
   struct Meta { int k; int p_i; int l_i; int o; uint64_t pid; };
-  const __amdgpu_buffer_rsrc_t sel_d = pair_rsrc(sel ? sel : pi, sel ? (uint32_t)(n * 4) : 0u);
-  const __amdgpu_buffer_rsrc_t io_d = pair_rsrc(pb.io, pb.io_bytes), pid_d = pair_rsrc(pb.pid, pb.pid_bytes);
-  const __amdgpu_buffer_rsrc_t pi_d = pair_rsrc(pi, pb.pair_bytes), li_d = pair_rsrc(li, pb.pair_bytes);
-  const __amdgpu_buffer_rsrc_t pred_d = pair_rsrc(pred, pb.pair_bytes), deg_d = pair_rsrc(deg, pb.pat_bytes);
-  const __amdgpu_buffer_rsrc_t A_d = pair_rsrc(H.A, pb.a_bytes), B_d = pair_rsrc(H.B, pb.b_bytes);
+  const __amdgpu_buffer_rsrc_t sel_d = mmg_rsrc(sel ? sel : pi, sel ? (uint32_t)(n * 4) : 0u);
+  const __amdgpu_buffer_rsrc_t io_d = mmg_rsrc(pb.io, pb.io_bytes), pid_d = mmg_rsrc(pb.pid, pb.pid_bytes);
+  const __amdgpu_buffer_rsrc_t pi_d = mmg_rsrc(pi, pb.pair_bytes), li_d = mmg_rsrc(li, pb.pair_bytes);
+  const __amdgpu_buffer_rsrc_t pred_d = mmg_rsrc(pred, pb.pair_bytes), deg_d = mmg_rsrc(deg, pb.pat_bytes);
+  const __amdgpu_buffer_rsrc_t A_d = mmg_rsrc(H.A, pb.a_bytes), B_d = mmg_rsrc(H.B, pb.b_bytes);
   const bool has_sel = sel != nullptr, has_io = pb.io_bytes != 0u, has_pid = pb.pid_bytes != 0u;
   // A stage only ISSUES loads; what it loaded is finalised (selects, clamps) one iteration later by the next stage, so
   // nothing is waited for in the iteration that issued it.
-  struct RawMeta { int k, p, l; pu32x2 o2, d2; };
+  struct RawMeta { int k, p, l; u32x2 o2, d2; };
   auto issue_k = [&](int64_t t) {                    // raw list entry of tile t (0 past the end / without a list)
     const int64_t idx = t * TP + l31;
     return pair_ld_i32(sel_d, (unsigned)(idx < n ? idx : 0) * 4u);
@@ -1363,21 +1320,11 @@ __global__ __launch_bounds__(256, 2) void k_pair_fwd_mfma(HeadDev H, const int32
 #pragma unroll
         for (int j = 0; j < 8; ++j) bw[ks >> 1] |= x8[j] > 0.f ? (1u << (16 * (ks & 1) + j)) << (8 * h) : 0u;
       }
-      pbf16x8 x1, x2, x3;
+      bf16x8 x1, x2, x3;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const __bf16 a = (__bf16)x8[j];
-        const float r1 = x8[j] - (float)a;
-        const __bf16 b = (__bf16)r1;
-        x1[j] = a; x2[j] = b; x3[j] = (__bf16)(r1 - (float)b);
-      }
+      for (int j = 0; j < 8; ++j) MMG_SPLIT3(x8[j], x1[j], x2[j], x3[j]);
       // C^T: lane = pair, reg = unit.  W2 . h1^T, six exact products, small terms first
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][2], x1, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][0], x3, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][1], x2, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][1], x1, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][0], x2, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][0], x1, acc, 0, 0, 0);
+      MMG_X6_ALO(acc, w2p[ks][0], w2p[ks][1], w2p[ks][2], x1, x2, x3);
     }
     // lane = pair l31, register r = unit crow(r, h) = (r & 3) + 8 (r >> 2) + 4 h
     float part = 0.f;
@@ -1397,7 +1344,7 @@ __global__ __launch_bounds__(256, 2) void k_pair_fwd_mfma(HeadDev H, const int32
       bw[0] |= (uint32_t)__shfl_xor((int)bw[0], 32, 64);
       bw[1] |= (uint32_t)__shfl_xor((int)bw[1], 32, 64);
       if (h == 0 && active)
-        *reinterpret_cast<pu32x2*>(sv_bits + (size_t)(sv_by_pos ? t * TP + l31 : (int64_t)mc.k) * 2) = pu32x2{bw[0], bw[1]};
+        *reinterpret_cast<u32x2*>(sv_bits + (size_t)(sv_by_pos ? t * TP + l31 : (int64_t)mc.k) * 2) = u32x2{bw[0], bw[1]};
     }
     part += __shfl_xor(part, 32, 64);
     if (h == 0 && active)          // (a slot past the end of pred is dropped by the descriptor's range check)
@@ -1432,16 +1379,13 @@ __global__ __launch_bounds__(256, 2) void k_pair_dense_fwd(HeadDev H, const int3
   }
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int h = lane >> 5, l31 = lane & 31;
-  pbf16x8 w2p[4][3];                 // W2 as three exact bf16 pieces, the A operand of k_pair_fwd_mfma
+  bf16x8 w2p[4][3];                 // W2 as three exact bf16 pieces, the A operand of k_pair_fwd_mfma
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float v = H.W2[l31 * 64 + 16 * ks + 8 * h + j];
-      const __bf16 a = (__bf16)v;
-      const float r1 = v - (float)a;
-      const __bf16 b = (__bf16)r1;
-      w2p[ks][0][j] = a; w2p[ks][1][j] = b; w2p[ks][2][j] = (__bf16)(r1 - (float)b);
+      MMG_SPLIT3(v, w2p[ks][0][j], w2p[ks][1][j], w2p[ks][2][j]);
     }
   float b2r[16], w3r[16];            // this lane's 16 units: crow(r, h)
 #pragma unroll
@@ -1451,8 +1395,8 @@ __global__ __launch_bounds__(256, 2) void k_pair_dense_fwd(HeadDev H, const int3
   const uint32_t n_cells = n_rows * n_labs;
   const int64_t n_tiles = (n_cells + TP - 1) / TP;
   const int64_t wave_id = (int64_t)blockIdx.x * 4 + wid, n_waves = (int64_t)gridDim.x * 4;
-  const __amdgpu_buffer_rsrc_t rows_d = pair_rsrc(rows, n_rows * 4u), orow_d = pair_rsrc(out_rows, n_rows * 4u);
-  const __amdgpu_buffer_rsrc_t A_d = pair_rsrc(H.A, (uint32_t)n_pat * 256u), B_d = pair_rsrc(H.B, n_labs * 256u);
+  const __amdgpu_buffer_rsrc_t rows_d = mmg_rsrc(rows, n_rows * 4u), orow_d = mmg_rsrc(out_rows, n_rows * 4u);
+  const __amdgpu_buffer_rsrc_t A_d = mmg_rsrc(H.A, (uint32_t)n_pat * 256u), B_d = mmg_rsrc(H.B, n_labs * 256u);
   // Two-deep pipeline, one dependent load per stage:  tile t+2: cell -> (row, lab); patient row id, output row
   //                                                   tile t+1: patient -> A row (lab -> B row without LDS)
   // (loads are unconditional, as in k_pair_fwd_mfma: a stage only issues them, the next one finalises what came back)
@@ -1512,21 +1456,11 @@ __global__ __launch_bounds__(256, 2) void k_pair_dense_fwd(HeadDev H, const int3
       for (int c = 0; c < 2; ++c)
 #pragma unroll
         for (int j = 0; j < 4; ++j) x8[4 * c + j] = fmaxf(ca[2 * ks + c][j] + cb[2 * ks + c][j], 0.f);
-      pbf16x8 x1, x2, x3;
+      bf16x8 x1, x2, x3;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const __bf16 a = (__bf16)x8[j];
-        const float r1 = x8[j] - (float)a;
-        const __bf16 b = (__bf16)r1;
-        x1[j] = a; x2[j] = b; x3[j] = (__bf16)(r1 - (float)b);
-      }
+      for (int j = 0; j < 8; ++j) MMG_SPLIT3(x8[j], x1[j], x2[j], x3[j]);
       // C^T: lane = cell, reg = unit.  The order of k_pair_fwd_mfma
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][2], x1, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][0], x3, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][1], x2, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][1], x1, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][0], x2, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2p[ks][0], x1, acc, 0, 0, 0);
+      MMG_X6_ALO(acc, w2p[ks][0], w2p[ks][1], w2p[ks][2], x1, x2, x3);
     }
     float part = 0.f;
 #pragma unroll

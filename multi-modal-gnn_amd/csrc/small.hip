@@ -11,11 +11,9 @@
 //                          (statistics, folded scale / shift, running-statistics update and the apply pass fused:
 //                          nine, respectively six, launches per layer before)
 #include "common.h"
+#include "mma.h"
 
 namespace {
-
-typedef float sf32x16 __attribute__((ext_vector_type(16)));
-typedef float sf32x4 __attribute__((ext_vector_type(4)));
 
 struct FwdGroup { mmg_small_fwd_t p[MMG_SMALL_MAX]; int n; };
 struct WgradGroup { mmg_small_wgrad_t p[MMG_SMALL_MAX]; int n; };
@@ -37,10 +35,10 @@ __global__ __launch_bounds__(256) void k_small_fwd_group(FwdGroup g, int N) {
   const int n0 = blockIdx.x * 32;
   const int64_t ar = row0 + l31;
   const int n_terms = P.X2 ? 2 : 1;
-  sf32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-  sf32x4 a[2][KW / 4], w[2][KW / 4];
+  f32x4 a[2][KW / 4], w[2][KW / 4];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     if (t < n_terms) {
@@ -50,12 +48,12 @@ __global__ __launch_bounds__(256) void k_small_fwd_group(FwdGroup g, int N) {
       const float* wp = wkn ? W + (size_t)kb * N + n0 + l31 : W + (size_t)(n0 + l31) * K + kb;
 #pragma unroll
       for (int q = 0; q < KW / 4; ++q) {
-        a[t][q] = *reinterpret_cast<const sf32x4*>(xp + q * 4);
+        a[t][q] = *reinterpret_cast<const f32x4*>(xp + q * 4);
         if (wkn) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) w[t][q][j] = wp[(size_t)(q * 4 + j) * N];
         } else {
-          w[t][q] = *reinterpret_cast<const sf32x4*>(wp + q * 4);
+          w[t][q] = *reinterpret_cast<const f32x4*>(wp + q * 4);
         }
       }
     }
@@ -65,7 +63,7 @@ __global__ __launch_bounds__(256) void k_small_fwd_group(FwdGroup g, int N) {
     if (t < n_terms) {
 #pragma unroll
       for (int q = 0; q < KW / 4; ++q) {
-        if (ar >= M) a[t][q] = sf32x4{0.f, 0.f, 0.f, 0.f};
+        if (ar >= M) a[t][q] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t][q][j], w[t][q][j], acc, 0, 0, 0);
       }
@@ -100,7 +98,7 @@ __global__ __launch_bounds__(256) void k_small_wgrad_group(WgradGroup g, int N, 
   __shared__ float bpart[4][64];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, h = lane >> 5, l31 = lane & 31;
   const int k0 = blockIdx.x * 32, n0 = blockIdx.y * 32;
-  sf32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc[i] = 0.f;
   float bsum = 0.f;
@@ -170,7 +168,7 @@ __global__ __launch_bounds__(256) void k_small_bn_act_group(BnGroup g, int N, fl
   if (has_bn && P.training) {
     double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
     for (int r = rl; r < M; r += 32) {
-      const sf32x4 v = *reinterpret_cast<const sf32x4*>(P.Y + (size_t)r * N + c);
+      const f32x4 v = *reinterpret_cast<const f32x4*>(P.Y + (size_t)r * N + c);
 #pragma unroll
       for (int j = 0; j < 4; ++j) { s0[j] += (double)v[j]; s1[j] += (double)v[j] * (double)v[j]; }
     }
@@ -212,11 +210,11 @@ __global__ __launch_bounds__(256) void k_small_bn_act_group(BnGroup g, int N, fl
   }
   __syncthreads();
   const ProDev pr = small_pro(P, has_bn ? scs : nullptr, shs);
-  const sf32x4 sc4 = *reinterpret_cast<const sf32x4*>(&scs[c4 * 4]), sh4 = *reinterpret_cast<const sf32x4*>(&shs[c4 * 4]);
+  const f32x4 sc4 = *reinterpret_cast<const f32x4*>(&scs[c4 * 4]), sh4 = *reinterpret_cast<const f32x4*>(&shs[c4 * 4]);
   for (int r = rl; r < M; r += 32) {
-    sf32x4 v = *reinterpret_cast<const sf32x4*>(P.Y + (size_t)r * N + c);
+    f32x4 v = *reinterpret_cast<const f32x4*>(P.Y + (size_t)r * N + c);
     mmg_pro_apply4(pr, v, sc4, sh4, r, c, N);
-    *reinterpret_cast<sf32x4*>(P.out + (size_t)r * N + c) = v;
+    *reinterpret_cast<f32x4*>(P.out + (size_t)r * N + c) = v;
   }
 }
 
@@ -233,19 +231,19 @@ __global__ __launch_bounds__(256) void k_small_bn_bwd_group(BnBwdGroup g, int N)
   const int tid = threadIdx.x, c4 = tid & 7, rl = tid >> 3;
   const int c0 = blockIdx.x * 32, c = c0 + c4 * 4;
   const bool has_bn = P.scale != nullptr;
-  const sf32x4 one = {1.f, 1.f, 1.f, 1.f}, zero = {0.f, 0.f, 0.f, 0.f};
-  sf32x4 sc = one, sh = zero, mu = zero, rs = one;
+  const f32x4 one = {1.f, 1.f, 1.f, 1.f}, zero = {0.f, 0.f, 0.f, 0.f};
+  f32x4 sc = one, sh = zero, mu = zero, rs = one;
   if (has_bn) {
-    sc = *reinterpret_cast<const sf32x4*>(P.scale + c); sh = *reinterpret_cast<const sf32x4*>(P.shift + c);
-    mu = *reinterpret_cast<const sf32x4*>(P.mean + c); rs = *reinterpret_cast<const sf32x4*>(P.rstd + c);
+    sc = *reinterpret_cast<const f32x4*>(P.scale + c); sh = *reinterpret_cast<const f32x4*>(P.shift + c);
+    mu = *reinterpret_cast<const f32x4*>(P.mean + c); rs = *reinterpret_cast<const f32x4*>(P.rstd + c);
   }
   mmg_small_bn_t fwd{};                       // (reuses the forward's prologue builder for the dropout fields)
   fwd.act = P.act; fwd.drop_p = P.drop_p; fwd.seed = P.seed; fwd.site = P.site; fwd.row_offset = P.row_offset;
   fwd.seed_ptr = P.seed_ptr;
   const ProDev pr = small_pro(fwd, nullptr, nullptr);
   auto gprime = [&](int r) {
-    sf32x4 gv = *reinterpret_cast<const sf32x4*>(P.G + (size_t)r * N + c);
-    const sf32x4 y = *reinterpret_cast<const sf32x4*>(P.Y + (size_t)r * N + c);
+    f32x4 gv = *reinterpret_cast<const f32x4*>(P.G + (size_t)r * N + c);
+    const f32x4 y = *reinterpret_cast<const f32x4*>(P.Y + (size_t)r * N + c);
     if (P.act) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) gv[j] *= mmg_act_grad(P.act, has_bn ? fmaf(y[j], sc[j], sh[j]) : y[j]);
@@ -257,8 +255,8 @@ __global__ __launch_bounds__(256) void k_small_bn_bwd_group(BnBwdGroup g, int N)
   if (stats) {
     double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
     for (int r = rl; r < M; r += 32) {
-      const sf32x4 gv = gprime(r);
-      const sf32x4 y = *reinterpret_cast<const sf32x4*>(P.Y + (size_t)r * N + c);
+      const f32x4 gv = gprime(r);
+      const f32x4 y = *reinterpret_cast<const f32x4*>(P.Y + (size_t)r * N + c);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         s0[j] += (double)gv[j];
@@ -280,8 +278,8 @@ __global__ __launch_bounds__(256) void k_small_bn_bwd_group(BnBwdGroup g, int N)
     // eval mode: d beta / d gamma are still the column sums (no mean subtraction in dY)
     double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
     for (int r = rl; r < M; r += 32) {
-      const sf32x4 gv = gprime(r);
-      const sf32x4 y = *reinterpret_cast<const sf32x4*>(P.Y + (size_t)r * N + c);
+      const f32x4 gv = gprime(r);
+      const f32x4 y = *reinterpret_cast<const f32x4*>(P.Y + (size_t)r * N + c);
 #pragma unroll
       for (int j = 0; j < 4; ++j) { s0[j] += (double)gv[j]; s1[j] += (double)gv[j] * (double)((y[j] - mu[j]) * rs[j]); }
     }
@@ -297,17 +295,17 @@ __global__ __launch_bounds__(256) void k_small_bn_bwd_group(BnBwdGroup g, int N)
     }
     __syncthreads();
   }
-  sf32x4 a0 = zero, a1 = zero;
-  if (stats) { a0 = *reinterpret_cast<const sf32x4*>(&a0s[c4 * 4]); a1 = *reinterpret_cast<const sf32x4*>(&a1s[c4 * 4]); }
+  f32x4 a0 = zero, a1 = zero;
+  if (stats) { a0 = *reinterpret_cast<const f32x4*>(&a0s[c4 * 4]); a1 = *reinterpret_cast<const f32x4*>(&a1s[c4 * 4]); }
   for (int r = rl; r < M; r += 32) {
-    const sf32x4 gv = gprime(r);
-    sf32x4 o = gv;
+    const f32x4 gv = gprime(r);
+    f32x4 o = gv;
     if (has_bn) {
-      const sf32x4 y = *reinterpret_cast<const sf32x4*>(P.Y + (size_t)r * N + c);
+      const f32x4 y = *reinterpret_cast<const f32x4*>(P.Y + (size_t)r * N + c);
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[j] = sc[j] * (gv[j] - a0[j] - ((y[j] - mu[j]) * rs[j]) * a1[j]);
     }
-    *reinterpret_cast<sf32x4*>(P.dY + (size_t)r * N + c) = o;
+    *reinterpret_cast<f32x4*>(P.dY + (size_t)r * N + c) = o;
   }
 }
 
