@@ -385,6 +385,10 @@ int mmg_probe_arm(int n_launches);
 /* names (nullable): cap * MMG_PROBE_NAME_LEN bytes; entry i receives the instantiated kernel symbol of launch i, e.g.
  * "k_linear_bnbwd_x6<128, 4, 0>" -- the name rocprofv3 lists the same launch under. */
 int mmg_probe_read(float* ms, int* tag, int64_t* M, int* N, int* K, int* flags, char* names, int cap);
+/* The launch extents of the entries the LAST mmg_probe_read returned, in its order: grid_xyz (nullable) [cap][3] = gridDim
+ * x, y, z; block_x (nullable) [cap] = blockDim.x.  Returns how many it wrote (<= cap).  The persistent kernels walk tiles
+ * t0, t0 + G, ...: with this a test reads G -- and so how many tiles a workgroup took -- from the launch that happened. */
+int mmg_probe_grids(uint32_t* grid_xyz, uint32_t* block_x, int cap);
 
 /* Row L2 normalisation, F.normalize(p=2, dim=1, eps): out = z / max(||z||, eps); rnorm = 1/max(..) */
 int mmg_l2norm_fwd(const float* Z, float* out, float* rnorm, int64_t M, int N, float eps, void* stream);

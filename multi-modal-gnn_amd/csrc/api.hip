@@ -40,9 +40,11 @@ extern "C" int mmg_stream_destroy(void* stream) {
 // per-thread hook would miss half of the step); it is mutex-guarded, never armed by the product path, and costs the
 // unarmed launch path one relaxed atomic load.
 namespace {
-struct ProbeEntry { hipEvent_t e0, e1; int tag; int64_t M; int N, K, flags; const char* text; const char* launcher; };
+struct ProbeEntry { hipEvent_t e0, e1; int tag; int64_t M; int N, K, flags; const char* text; const char* launcher; dim3 grid, block; };
+struct ProbeGrid { uint32_t gx, gy, gz, bx; };
 std::mutex g_probe_mu;
 std::vector<ProbeEntry> g_probe;
+std::vector<ProbeGrid> g_probe_grids;       // launch extents of the entries the last mmg_probe_read returned
 std::atomic<int> g_probe_left{0};
 void probe_clear() {
   for (auto& e : g_probe) { (void)hipEventDestroy(e.e0); (void)hipEventDestroy(e.e1); }
@@ -51,11 +53,11 @@ void probe_clear() {
 }  // namespace
 
 bool mmg_probe_take(int tag, int64_t M, int N, int K, int flags, const char* kernel_text, const char* launcher,
-                    hipEvent_t* e0, hipEvent_t* e1) {
+                    dim3 grid, dim3 block, hipEvent_t* e0, hipEvent_t* e1) {
   if (g_probe_left.load(std::memory_order_relaxed) <= 0) return false;
   std::lock_guard<std::mutex> lk(g_probe_mu);
   if (g_probe_left.load(std::memory_order_relaxed) <= 0) return false;
-  ProbeEntry e{nullptr, nullptr, tag, M, N, K, flags, kernel_text, launcher};
+  ProbeEntry e{nullptr, nullptr, tag, M, N, K, flags, kernel_text, launcher, grid, block};
   if (hipEventCreate(&e.e0) != hipSuccess) return false;
   if (hipEventCreate(&e.e1) != hipSuccess) { (void)hipEventDestroy(e.e0); return false; }
   g_probe.push_back(e);
@@ -125,15 +127,29 @@ static void probe_symbol(const char* text, const char* launcher, char* out, int 
 extern "C" int mmg_probe_read(float* ms, int* tag, int64_t* M, int* N, int* K, int* flags, char* names, int cap) {
   std::lock_guard<std::mutex> lk(g_probe_mu);
   g_probe_left.store(0, std::memory_order_relaxed);
+  g_probe_grids.clear();
   int n = 0;
   for (auto& e : g_probe) {
     float t = 0.f;
     if (n < cap && hipEventSynchronize(e.e1) == hipSuccess && hipEventElapsedTime(&t, e.e0, e.e1) == hipSuccess) {
       ms[n] = t; tag[n] = e.tag; M[n] = e.M; N[n] = e.N; K[n] = e.K; flags[n] = e.flags;
       if (names) probe_symbol(e.text, e.launcher, names + (size_t)n * MMG_PROBE_NAME_LEN, MMG_PROBE_NAME_LEN);
+      g_probe_grids.push_back(ProbeGrid{e.grid.x, e.grid.y, e.grid.z, e.block.x});
       ++n;
     }
   }
   probe_clear();
+  return n;
+}
+
+extern "C" int mmg_probe_grids(uint32_t* grid_xyz, uint32_t* block_x, int cap) {
+  std::lock_guard<std::mutex> lk(g_probe_mu);
+  int n = 0;
+  for (const auto& g : g_probe_grids) {
+    if (n >= cap) break;
+    if (grid_xyz) { grid_xyz[3 * n] = g.gx; grid_xyz[3 * n + 1] = g.gy; grid_xyz[3 * n + 2] = g.gz; }
+    if (block_x) block_x[n] = g.bx;
+    ++n;
+  }
   return n;
 }

@@ -61,13 +61,16 @@ struct MmgMaxLds {
 // carries a HIP start / stop event pair on the kernel itself (hipExtLaunchKernelGGL: the kernel's own begin / end
 // timestamps on its stream).  Process-wide and mutex-guarded (api.hip); unarmed cost: one relaxed atomic load.
 // (the record also keeps what names the INSTANTIATED kernel: the kernel expression as written at the launch site and the
-// __PRETTY_FUNCTION__ of the launcher, whose "[K = 128, WN = 4, ...]" suffix binds the template parameters it mentions)
+// __PRETTY_FUNCTION__ of the launcher, whose "[K = 128, WN = 4, ...]" suffix binds the template parameters it mentions;
+// and the grid and block the launch was made with -- mmg_probe_grids -- so that a test reads how many tiles a persistent
+// workgroup walked from the launch that happened instead of restating the launcher's grid rule)
 bool mmg_probe_take(int tag, int64_t M, int N, int K, int flags, const char* kernel_text, const char* launcher,
-                    hipEvent_t* e0, hipEvent_t* e1);
+                    dim3 grid, dim3 block, hipEvent_t* e0, hipEvent_t* e1);
 #define MMG_LAUNCH(tag, pM, pN, pK, pflags, kernel, grid, block, lds, st, ...)                         \
   do {                                                                                                \
     hipEvent_t e0__, e1__;                                                                            \
-    if (mmg_probe_take(tag, pM, pN, pK, pflags, #kernel, __PRETTY_FUNCTION__, &e0__, &e1__))          \
+    if (mmg_probe_take(tag, pM, pN, pK, pflags, #kernel, __PRETTY_FUNCTION__, dim3(grid), dim3(block), &e0__, \
+                       &e1__))                                                                        \
       hipExtLaunchKernelGGL(kernel, grid, block, lds, st, e0__, e1__, 0, __VA_ARGS__);                \
     else                                                                                              \
       hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__);                                  \

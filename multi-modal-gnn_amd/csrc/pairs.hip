@@ -1820,9 +1820,9 @@ extern "C" int mmg_pair_head_bwd_saved(const mmg_head_t* head, const mmg_head_gr
     MMG_CHECK_HIP((MmgMaxLds<&k_pair_bwd, (int)BWD_LDS_MAX>::set()), "pair_head_bwd(attr)");
     int64_t g = (n_pairs + PT - 1) / PT;
     if (g > 512) g = 512;
-    hipLaunchKernelGGL(k_pair_bwd, dim3((unsigned)g), dim3(PT), lds, st, H, G, pi, li, deg, degree_threshold,
-                       want_low ? 1 : 0, n_pairs, n_total, (int)n_patients, n_labs, lds_db, drop_p, seed, seed_ptr, pair_id,
-                       dpred, sel, n_sel, io_perm);
+    MMG_LAUNCH(MMG_PROBE_PAIR_BWD, n_pairs, 0, 0, want_low ? 2 : 0, k_pair_bwd, dim3((unsigned)g), dim3(PT), lds, st, H, G,
+               pi, li, deg, degree_threshold, want_low ? 1 : 0, n_pairs, n_total, (int)n_patients, n_labs, lds_db, drop_p,
+               seed, seed_ptr, pair_id, dpred, sel, n_sel, io_perm);
   }
   MMG_CHECK_LAUNCH("pair_head_bwd");
   return MMG_OK;

@@ -175,6 +175,15 @@ def probe_read(cap: int = 1 << 16):
              bytes(nm[i]).split(b"\0", 1)[0].decode("ascii", "replace")) for i in range(n)]
 
 
+def probe_grids(cap: int = 1 << 16):
+    """-> list of ((gridDim.x, y, z), blockDim.x) of the launches the LAST probe_read returned, in its order: the grid of a
+    persistent kernel tells how many tiles each of its workgroups walked."""
+    import numpy as np
+    grid = np.zeros((cap, 3), np.uint32); block = np.zeros(cap, np.uint32)
+    n = _lib.load().mmg_probe_grids(grid.ctypes.data, block.ctypes.data, cap)
+    return [((int(grid[i, 0]), int(grid[i, 1]), int(grid[i, 2])), int(block[i])) for i in range(n)]
+
+
 _WS = {}              # key -> [buffer, handed out during a stream capture?]
 _WS_RETIRED = []      # outgrown workspaces a captured hipGraph may hold the address of: never handed back
 
