@@ -106,6 +106,24 @@ int mmg_rel_mask_build(const int32_t* rowptr, const int32_t* col, int64_t n_rows
 
 /* mmg_gather_rows: below, with the producer epilogues */
 
+/* mmg_scatter_rows: out[col] = sum over the edges (row, col) of rowscale[row] * x[row], times colscale[col].
+ * Precision.  A launch with a rowscale, a multigraph relation, a relation without bit planes or more than 352 padded items
+ * adds the fp32 terms themselves in fp32 (the matrix-core kernels multiply three exact bf16 pieces of each): every output
+ * has the accuracy of an fp32 sum against the sum of |terms| of ITS OWN element (6e-7 of it), whatever the magnitudes in x.
+ * The forward launch -- no rowscale, every relation MMG_REL_SIMPLE with mask_t, n_rows >= 64 -- multiplies two f16 pieces
+ * of x * 2^e, e chosen by each wave for the row range (a few hundred rows) of the 32-column strip that it streams.  With
+ * L = the largest finite magnitude among the strip's 32 columns over the rows of that range streamed so far (a 16-row block
+ * more than ~2^12 above everything before it is multiplied exactly and does not count):
+ *   - a term of at least 2^-15 L is kept to 2^-22 of itself (a block above L: to 2^-22 or exactly); an output whose terms
+ *     are all such is within 6e-7 of the sum of its |terms|, as above;
+ *   - a smaller term carries an ABSOLUTE error of up to 2^-37 L (2^-25 2^-e, with 2^(13 - e) between L / 4 and 2 L): it
+ *     loses a bit per factor of two below 2^-15 L and is lost altogether 2^37 below.  That is the error of an fp32 running
+ *     sum where small and large terms enter the same sum, but an output column (or item) whose terms ALL lie that far below
+ *     the other columns of its strip, or below earlier rows of the same range, is not kept to fp32 accuracy of itself.
+ *     A partial sum more than 2^100 below a later L of the range is unspecified within that absolute error.
+ * A caller whose columns differ by more than 2^15 inside a 32-column strip and who needs each to fp32 accuracy passes a
+ * rowscale of ones (the exact kernels).  A NaN or an infinity in x[row, c] makes column c of the outputs non-finite (of
+ * every item, as in the dense layers) and changes no other column. */
 size_t mmg_scatter_rows_ws_bytes(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D);
 int mmg_scatter_rows(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D,
                      const float* x, void* ws, size_t ws_bytes, void* stream);

@@ -352,13 +352,19 @@ constexpr int SB_SR = 64;                    // patient rows per stage = bits pe
 
 // ---- two f16 pieces of x * 2^e (round 4): 18 instead of 27 matrix instructions per 16 patients x 9 item tiles.
 // The pieces and their error bound: split8_h2 (mma.h).  The scale is a power of two chosen BY THE
-// WAVE from the data it streams (block floating point over the wave's row range): e starts at whatever brings the first
-// 16 x 32 block's largest magnitude to [2^12, 2^13); a later block with an element beyond 2^15 / 2^e lowers e, the
-// accumulators are multiplied by 2^(e_new - e_old) and that block is split again -- so every piece is finite for finite x,
-// whatever its range, and an element's error is <= 2^-22 of itself or 2^-37 of the largest magnitude seen so far in the
-// strip, whichever is larger: the error of an fp32 running sum, not of a format with fewer bits.  A NaN or an infinity in x
-// gives NaN in the sums it enters (fp32 index_add_: NaN, or +-inf for an infinity alone).
-constexpr int H2_E_INIT = 120, H2_E_MIN = -110;
+// WAVE from the data it streams (block floating point over the wave's row range; the rule: H2Scale / h2_decide_uniform,
+// mma.h): e starts at whatever brings the first 16 x 32 block's largest magnitude to [2^12, 2^13); a later block with an
+// element beyond 2^15 / 2^e lowers e (by at most 10 below the first), the accumulators are multiplied by 2^(e_new - e_old) and
+// that block is split again; a block further above is multiplied exactly on its own -- so every piece is finite for finite x,
+// whatever its range.  What a caller may rely on (include/mmgnn.h states it; tests/test_scatter_scale_gpu.py holds the kernel
+// to it inside one wave's range): with M = 2^(13 - e) -- between 1/4 of and twice the largest magnitude the wave has streamed
+// in the strip when the term passes, outlier blocks not counted -- a term within [2^-16 M, 4 M] is kept to 2^-22 of ITSELF, a
+// term above is exact, and a term below carries an ABSOLUTE error of up to 2^-38 M = 2^-25 2^-e.  That is the error of an
+// fp32 running sum only where the small and the large terms enter the SAME sum: all items and all 32 columns of the strip
+// share the wave's scale, so an output whose terms all lie more than 2^16 below the other columns or the earlier rows of the
+// wave's range is NOT kept to fp32 accuracy of itself (it loses a bit per factor of two, everything 2^38 below).  The
+// row-scaled launches (k_scatter_units<true>) are exact.  A NaN or an infinity in x gives NaN in the sums it enters (fp32 index_add_: NaN,
+// or +-inf for an infinity alone) and takes part in no scale decision.
 
 __device__ __forceinline__ float absmax8(const float* v) {      // (fmaxf drops a NaN operand: a NaN never moves the scale)
   float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fabsf(v[2]));
@@ -376,39 +382,14 @@ __device__ __forceinline__ float absmax8_finite(const float* v) {
   return m;
 }
 
-// The wave's scale.  e: the pieces are those of x * 2^e.  The first block with a finite non-zero value sets e so that its
-// largest magnitude lands in [2^12, 2^13) and anchors e_floor = e - 10; from then on a block that does not fit
-// (an element beyond 2^15 / 2^e) either lowers e (not below e_floor: the data grew, the accumulators are multiplied by the
-// power of two, nothing is lost) or -- an outlier more than ~2^12 above anything seen before -- is multiplied exactly on its own.
-// Every term is therefore kept to 2^-22 of itself while it is within [2^-16, 2^2] of the wave's reference magnitude 2^(13 - e)
-// (at least 2^-6 of the first block's maximum), exactly if it is an outlier above, and to an absolute 2^-25 * 2^-e below.
-struct H2Scale {
-  int e, e_floor, seen;
-  float sc, lim;                                       // 2^e, 2^(15 - e): wave-uniform
-  __device__ __forceinline__ void set(int en) { e = en; sc = mmg_pow2(en); lim = mmg_pow2(15 - en); }
-  __device__ __forceinline__ void init() { seen = 0; e_floor = H2_E_MIN; set(H2_E_INIT); }
-};
-constexpr int H2_E_DROP = 10;
-
-// m = a lane's finite magnitude maximum of the block.  Returns 1: multiply this block exactly (bf16 pieces), scale unchanged;
-// 0: split it as f16 pieces at the (possibly lowered) scale after multiplying the accumulators by 2^d.
+// m = a lane's finite magnitude maximum of the block.  The wave's maximum goes through the rule of mma.h (returns 1: multiply
+// this block exactly, scale unchanged; 0: split it as f16 pieces after multiplying the accumulators by 2^d).
 __device__ __forceinline__ int h2_decide(float m, H2Scale& hs, int& d) {
   m = wave_max_f(m);
-  // (scalar from here on: every decision below is a uniform branch and the wave's scale stays in scalar registers -- with
+  // (scalar from here on: every decision of the rule is a uniform branch and the wave's scale stays in scalar registers -- with
   //  the maximum left in a vector register the compiler treats the whole state as divergent and masks the main loop)
   m = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, m)));
-  d = 0;
-  if (!(m > 0.f)) return 0;                            // nothing finite and non-zero: the block cannot move the scale
-  const int fe = __builtin_amdgcn_frexp_expf(m);       // floor(log2 m) + 1
-  int en = 13 - fe;
-  en = en < H2_E_MIN ? H2_E_MIN : en;
-  en = en > hs.e ? hs.e : en;
-  if (!hs.seen) { hs.seen = 1; hs.e_floor = en - H2_E_DROP; hs.set(en); return 0; }   // (the accumulators are still zero)
-  if (en >= hs.e_floor) { d = en - hs.e; hs.set(en); return 0; }
-  if (fe + hs.e >= 100) {                              // x * 2^e would leave the fp32 range: re-anchor
-    d = en - hs.e; hs.e_floor = en - H2_E_DROP; hs.set(en); return 0;
-  }
-  return 1;
+  return h2_decide_uniform(m, hs, d);
 }
 
 // The strip layout (round 2): a workgroup owns a 32-column STRIP of x for a range of rows; four row quarters stream it and

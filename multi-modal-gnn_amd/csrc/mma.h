@@ -73,7 +73,7 @@ __device__ inline void split8x(const float* v, bf16x8& p0, bf16x8& p1, bf16x8& p
 
 // ---- two f16 pieces of X = x * 2^e: hi = f16(X), lo = f16(X - hi): 22 significant bits, relative error <= 2^-22 of X
 // while 2^-3 <= |X| < 65504; below that the residual is an f16 denormal (absolute error 2^-25 in units of X).  Who picks e,
-// and how: aggregate.hip (H2Scale).
+// and how: H2Scale / h2_decide_uniform below (used by strip_main_h, aggregate.hip).
 __host__ __device__ __forceinline__ void split8_h2(const float* v, float scale, f16x8& p0, f16x8& p1) {
   u32x4 q0, q1;
 #pragma unroll
@@ -126,6 +126,56 @@ __host__ __device__ __forceinline__ void split8_h2(const float* v, float scale, 
 
 // 2^e from the exponent field, -126 <= e <= 127: integer arithmetic only, so a wave-uniform e stays on the scalar unit
 __host__ __device__ __forceinline__ float mmg_pow2(int e) { return __builtin_bit_cast(float, (unsigned)(e + 127) << 23); }
+
+// ---- the scale of the two f16 pieces: block floating point over ONE WAVE's row range of a 32-column strip (the forward
+// scatter, strip_main_h in aggregate.hip).  The rule is host + device code so that tests/split_cpu.hip runs THESE statements
+// on the host against the numpy restatement tests/h2_ref.py; the wave maximum and the readfirstlane stay in the kernel.
+// e: the pieces are those of x * 2^e.  The first block (16 rows x 32 columns) with a finite non-zero value sets e so that its
+// largest magnitude lands in [2^12, 2^13) and anchors e_floor = e - 10; from then on a block that does not fit
+// (an element beyond 2^15 / 2^e) either lowers e (not below e_floor: the data grew, the accumulators are multiplied by the
+// power of two, nothing is lost) or -- an outlier more than ~2^12 above anything seen before -- is multiplied exactly on its own.
+// Every term is therefore kept to 2^-22 of itself while it is within [2^-16, 2^2] of the wave's reference magnitude 2^(13 - e)
+// (at least 2^-6 of the first block's maximum), exactly if it is an outlier above, and to an absolute 2^-25 * 2^-e below.
+constexpr int H2_E_INIT = 120, H2_E_MIN = -110;
+struct H2Scale {
+  int e, e_floor, seen;
+  float sc, lim;                                       // 2^e, 2^(15 - e): wave-uniform
+  __host__ __device__ __forceinline__ void set(int en) { e = en; sc = mmg_pow2(en); lim = mmg_pow2(15 - en); }
+  __host__ __device__ __forceinline__ void init() { seen = 0; e_floor = H2_E_MIN; set(H2_E_INIT); }
+};
+constexpr int H2_E_DROP = 10;
+
+// floor(log2 m) + 1 of a finite m > 0
+__host__ __device__ __forceinline__ int h2_frexp_exp(float m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_frexp_expf(m);
+#else
+  int fe;
+  (void)frexpf(m, &fe);
+  return fe;
+#endif
+}
+
+// m = the wave's finite magnitude maximum of the block (uniform).  Returns 1: multiply this block exactly (bf16 pieces), scale
+// unchanged; 0: split it as f16 pieces at the (possibly lowered) scale after multiplying the accumulators by 2^d.
+// The kernel asks only for a block with an element beyond hs.lim (an infinity included) and for the first block of the wave.
+__host__ __device__ __forceinline__ int h2_decide_uniform(float m, H2Scale& hs, int& d) {
+  d = 0;
+  if (!(m > 0.f)) return 0;                            // nothing finite and non-zero: the block cannot move the scale
+  const int fe = h2_frexp_exp(m);
+  int en = 13 - fe;
+  en = en < H2_E_MIN ? H2_E_MIN : en;
+  en = en > hs.e ? hs.e : en;
+  if (!hs.seen) { hs.seen = 1; hs.e_floor = en - H2_E_DROP; hs.set(en); return 0; }   // (the accumulators are still zero)
+  if (en >= hs.e_floor) { d = en - hs.e; hs.set(en); return 0; }
+  if (fe + hs.e >= 100) {                              // x * 2^e would leave the fp32 range: re-anchor.  d may reach -230: the
+    // kernel multiplies the accumulators by 2^max(d, -126) and later unscales them by 2^-e, so a sum more than 2^126 below the
+    // new scale comes out as a SMALL WRONG number, not a rounded one.  It is then more than 2^100 below the absolute floor
+    // 2^-25 * 2^-e of the contract: such values are unspecified (within the floor), like anything else below it.
+    d = en - hs.e; hs.e_floor = en - H2_E_DROP; hs.set(en); return 0;
+  }
+  return 1;
+}
 
 // C / D layout of the 32 x 32 MFMAs: lane l holds column l & 31; its accumulator register i holds tile row
 // mmg_c_row(i) + 4 * (l >> 5)
