@@ -937,6 +937,41 @@ size_t mmg_grid2d_ws_bytes(int64_t n, int gx, int gy);
 int mmg_grid2d(const float* Y, int64_t ld_y, const int32_t* w, int64_t n, const double* ex, const double* ey, int gx,
                int gy, int64_t* count, int64_t* wsum, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Device graph build (src/graph_build.py NodeIndexer :34-97, :163-173, create_patient_*_edges :476-586, the flip(0)
+ * reverse relations :222; mmgnn/graph_build.py build_graph_from_events, csrc/graph.hip): node indices in first-seen
+ * order and one edge per event row whose two ids are known, from device arrays of CODES (int64, one code per key: the
+ * caller factorises after the key rule).  A code outside its range means the row is ignored; it is never used as an
+ * address.
+ *   mmg_first_seen_index: the rows with a code in [0, n_codes) and valid[e] != 0 (valid uint8, nullable = every row)
+ *     are the COUNTED rows.  index_of_code [n_codes] int32: the position of code c when the distinct codes are listed in
+ *     the order of their first counted row (NodeIndexer.add order = Series.unique() order), -1 for a code without a
+ *     counted row;  code_of_index int64, the inverse: min(n, n_codes) entries, the first *n_nodes are written;
+ *     *n_nodes (HOST): the number of codes seen.
+ *   mmg_edge_build: row e is KEPT when patient[e] is in [0, n_patient_codes), item[e] in [0, n_item_codes) and both
+ *     patient_index[patient[e]] and item_index[item[e]] are >= 0 (int32 tables as mmg_first_seen_index writes them).
+ *     The kept rows are compacted in ASCENDING row order; for the k-th of them fwd[0 * ld + k] = the patient index,
+ *     fwd[1 * ld + k] = the item index (int64, ld >= n), rev (nullable) the same with the two rows swapped -- flip(0) --
+ *     and attr[k] (fp32, nullable; needs value) = (float)value[e], ONE round-to-nearest-even from fp64 as
+ *     astype(np.float32) does; a NaN value keeps its row.  A repeated (patient, item) pair gives one edge per row.
+ *     fwd and rev hold 2 * ld entries, attr n; only the first *n_edges columns are written.
+ *     *n_edges (HOST): the number of kept rows.
+ * Both calls wait for the stream before they write the host count (as mmg_code_select does for n_out: the count sizes
+ * the caller's views), so they cannot be captured.  Limits: 0 <= n < 2^31 (n = 0 is valid), 1 <= n_codes,
+ * n_patient_codes, n_item_codes < 2^31.  Every argument is checked on the host before anything is enqueued (MMG_E_ARG; a
+ * short workspace MMG_E_WS).  Integer work: flags, an exclusive scan and a scatter that writes every output once; the
+ * first row of a code is an integer atomicMin over a table a kernel filled (no memset node), whose result does not
+ * depend on the order.  Every output is exact and bitwise equal from call to call.
+ * ------------------------------------------------------------------------------------- */
+size_t mmg_first_seen_index_ws_bytes(int64_t n, int64_t n_codes);
+int mmg_first_seen_index(const int64_t* code, const uint8_t* valid, int64_t n, int64_t n_codes, int32_t* index_of_code,
+                         int64_t* code_of_index, int64_t* n_nodes, void* ws, size_t ws_bytes, void* stream);
+size_t mmg_edge_build_ws_bytes(int64_t n);
+int mmg_edge_build(const int64_t* patient, const int64_t* item, const double* value, int64_t n,
+                   const int32_t* patient_index, int64_t n_patient_codes, const int32_t* item_index,
+                   int64_t n_item_codes, int64_t* fwd, int64_t* rev, int64_t ld, float* attr, int64_t* n_edges, void* ws,
+                   size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,10 @@
 The reference walks every row with ``DataFrame.iterrows`` (~35 us/row: an hour at the x1000 scale); here ids are
 factorised once (``pd.factorize`` keeps first-seen order = ``Series.unique()`` order) and only the UNIQUE ids go
 through the Python key rule.  Golden parity: tests/test_graph_build_cpu.py against tests/golden/edges_*.npz.
+
+``build_graph_from_events`` / ``index_first_seen`` build the same graph on the device from tensors of event codes
+(csrc/graph.hip: first-seen indices by an integer minimum, flags and a scan; edges by flags, a scan and a scatter), with
+no CPU fallback; tests/test_graph_device_gpu.py pins them to the same golden edges and to the host builder.
 """
 from __future__ import annotations
 
@@ -170,6 +174,109 @@ def build_heterogeneous_graph(cohort, labs, diagnoses, medications, demographics
         if ec["patient_medication"]["bidirectional"]:
             data["medication", "has_medication_rev", "patient"].edge_index = ei.flip(0)
     data.indexers = {t: {"id_to_index": ix.id_to_index, "index_to_id": ix.index_to_id} for t, ix in indexers.items()}
+    data.config = config
+    validate_graph(data)
+    return data
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The same graph from DEVICE tensors of event codes (csrc/graph.hip): what preprocess.preprocess_lab_events and
+# preprocess.select_codes leave on the device goes to data.build_plan without a trip through DataFrames.  The ids are
+# CODES, one per key: the caller factorises AFTER the key rule (_key), so that 10006.0 and "10006" are one code -- the
+# kernels compare integers and know nothing of the rule.  Code order is free (sorted uniques, say); the node order is
+# first-seen order, as NodeIndexer gives it.
+# ------------------------------------------------------------------------------------------------------------------
+_RELATIONS = (("patient_lab", "has_lab", "lab"), ("patient_diagnosis", "has_diagnosis", "diagnosis"),
+              ("patient_medication", "has_medication", "medication"))
+
+
+def _event_column(t, name: str, dtype, device=None) -> torch.Tensor:
+    if not torch.is_tensor(t) or not t.is_cuda:
+        where = t.device if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"{name}: expected a HIP device tensor, got {where} (no CPU fallback)")
+    if t.dtype != dtype or t.dim() != 1:
+        raise ValueError(f"{name}: expected a 1-D {dtype} tensor, got {t.dtype} {tuple(t.shape)}")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name}: on {t.device}, the cohort on {device}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: must be contiguous")
+    return t
+
+
+def index_first_seen(code: torch.Tensor, n_codes: int, valid: Optional[torch.Tensor] = None):
+    """NodeIndexer.add over a device column of codes: -> (index_of_code int32 [n_codes], -1 for a code that never occurs;
+    code_of_index int64 [number of nodes]).  A code outside [0, n_codes) and a row with valid == 0 are skipped.
+    n_codes == 0 (an empty vocabulary) gives two empty tables."""
+    code = _event_column(code, "code", torch.int64)
+    from . import ops
+    index_of_code, code_of_index = ops.first_seen_index(code, max(int(n_codes), 1), valid)
+    return index_of_code[:max(int(n_codes), 0)], code_of_index
+
+
+def build_graph_from_events(cohort, labs, diagnoses, medications, n_codes: Dict, config: Dict,
+                            keys: Optional[Dict] = None) -> HeteroGraph:
+    """build_heterogeneous_graph on device tensors of codes: same num_nodes, edge order, reverse relations, dtypes and
+    empty shapes as the host builder gives for the same ids, on the events' device.
+
+    cohort: int64 [rows] patient codes in cohort order; labs: (patient, lab, value_normalized fp64); diagnoses,
+    medications: (patient, code); n_codes: {"patient", "lab", "diagnosis", "medication"} -> the size of each code space;
+    config["graph"]["edge_types"]: enabled / bidirectional per relation, as the host builder reads it.  Patients are
+    indexed in first-seen order over `cohort`, the other node types over their own event column -- whether or not the
+    relation is enabled, as in the reference.  An event whose patient is not in the cohort leaves no edge.
+    The codes must be ONE PER KEY: factorise after the key rule (10006.0 and "10006" are one code).
+    keys (optional): {node type: array of the original ids by code}; data.indexers then holds id_to_index / index_to_id
+    (host dicts, in index order, through the key rule) of those node types."""
+    try:
+        ec = config["graph"]["edge_types"]
+        flags = [(bool(ec[name]["enabled"]), bool(ec[name]["bidirectional"])) for name, _, _ in _RELATIONS]
+        sizes = {t: int(n_codes[t]) for t in ("patient", "lab", "diagnosis", "medication")}
+    except (KeyError, TypeError, ValueError) as e:
+        raise ValueError(f"build_graph_from_events: cannot read config['graph']['edge_types'] / n_codes ({e!r})") from None
+    cohort = _event_column(cohort, "cohort", torch.int64)
+    dev = cohort.device
+    if len(labs) != 3 or len(diagnoses) != 2 or len(medications) != 2:
+        raise ValueError("build_graph_from_events: labs is (patient, lab, value), diagnoses and medications (patient, code)")
+    events = []
+    for (name, _, node), cols in zip(_RELATIONS, (labs, diagnoses, medications)):
+        p = _event_column(cols[0], f"{name}: patient", torch.int64, dev)
+        c = _event_column(cols[1], f"{name}: {node}", torch.int64, dev)
+        v = _event_column(cols[2], f"{name}: value", torch.float64, dev) if len(cols) == 3 else None
+        if c.numel() != p.numel() or (v is not None and v.numel() != p.numel()):
+            raise ValueError(f"{name}: every column needs one entry per row")
+        events.append((p, c, v))
+    from . import ops
+
+    data = HeteroGraph()
+    index, inverse = {}, {}
+    for t, col in zip(("patient", "lab", "diagnosis", "medication"), (cohort,) + tuple(e[1] for e in events)):
+        index[t], inverse[t] = index_first_seen(col, sizes[t])
+        data[t].num_nodes = int(inverse[t].numel())
+    for (_, rel, node), (enabled, bidirectional), (p, c, v) in zip(_RELATIONS, flags, events):
+        if not enabled:
+            continue
+        if sizes["patient"] < 1 or sizes[node] < 1:            # an empty vocabulary: no edge (and no table to look into)
+            fwd = torch.empty((2, 0), dtype=torch.int64, device=dev)
+            rev = fwd.clone() if bidirectional else None
+            attr = torch.empty(0, dtype=torch.float32, device=dev) if v is not None else None
+        else:
+            fwd, rev, attr = ops.edge_build(p, c, index["patient"], index[node], v, reverse=bidirectional)
+        data["patient", rel, node].edge_index = fwd
+        if attr is not None:
+            data["patient", rel, node].edge_attr = attr.unsqueeze(1)
+        if bidirectional:
+            data[node, rel + "_rev", "patient"].edge_index = rev
+            if attr is not None:
+                data[node, rel + "_rev", "patient"].edge_attr = data["patient", rel, node].edge_attr
+    if keys is not None:
+        indexers = {}
+        for t, ids in keys.items():
+            if t not in inverse:
+                raise ValueError(f"keys: unknown node type {t!r}")
+            if len(ids) != sizes[t]:
+                raise ValueError(f"keys[{t!r}]: {len(ids)} ids for {sizes[t]} codes")
+            order = [_key(ids[c]) for c in inverse[t].cpu().tolist()]
+            indexers[t] = {"id_to_index": {k: i for i, k in enumerate(order)}, "index_to_id": dict(enumerate(order))}
+        data.indexers = indexers
     data.config = config
     validate_graph(data)
     return data

@@ -1491,6 +1491,52 @@ def code_select(code: torch.Tensor, patient: torch.Tensor, n_patients: int, n_co
     return n_pat, n_rows, rank, selected, out_rows[:int(cnt.value)]
 
 
+# ------------------------------------------------------------------------------------------ device graph build
+def first_seen_index(code: torch.Tensor, n_codes: int, valid: Optional[torch.Tensor] = None):
+    """Node indices in first-seen order (mmg_first_seen_index).  code: int64 device tensor over the rows (out of range =
+    the row is ignored); valid: uint8 / bool or None.  -> (index_of_code int32 [n_codes], -1 = never seen;
+    code_of_index int64 [number of codes seen]).  Waits for the stream: the count comes back."""
+    n = code.numel()
+    if not (0 <= n < 2 ** 31 - 1 and 1 <= n_codes < 2 ** 31 - 1):
+        raise ValueError(f"first_seen_index: n {n}, n_codes {n_codes} outside [0, 2^31) / [1, 2^31)")
+    if valid is not None and valid.numel() != n:
+        raise ValueError("first_seen_index: every column needs one entry per row")
+    dev = code.device
+    index_of_code = torch.empty(n_codes, dtype=torch.int32, device=dev)
+    code_of_index = torch.empty(min(n, int(n_codes)), dtype=torch.int64, device=dev)
+    cnt = C.c_int64(0)
+    _call("mmg_first_seen_index", code, valid, n, int(n_codes), index_of_code, code_of_index, C.byref(cnt),
+          ws=_lib.load().mmg_first_seen_index_ws_bytes(n, int(n_codes)))
+    return index_of_code, code_of_index[:int(cnt.value)]
+
+
+def edge_build(patient: torch.Tensor, item: torch.Tensor, patient_index: torch.Tensor, item_index: torch.Tensor,
+               value: Optional[torch.Tensor] = None, reverse: bool = True):
+    """One edge per row whose two codes have an index, row order kept (mmg_edge_build).  patient, item: int64 device
+    tensors over the rows; patient_index, item_index: the int32 tables of first_seen_index; value: fp64 or None.
+    -> (fwd int64 [2, E] contiguous, rev = fwd.flip(0) or None, attr fp32 [E] or None).  Waits for the stream: E comes
+    back.  The kernels write into [2, n] buffers; when rows were dropped (E < n) the [2, E] result is their narrowing
+    copy."""
+    n = patient.numel()
+    if not 0 <= n < 2 ** 31 - 1:
+        raise ValueError(f"edge_build: n {n} outside [0, 2^31)")
+    if item.numel() != n or (value is not None and value.numel() != n):
+        raise ValueError("edge_build: every column needs one entry per row")
+    dev = patient.device
+    fwd = torch.empty((2, n), dtype=torch.int64, device=dev)
+    rev = torch.empty((2, n), dtype=torch.int64, device=dev) if reverse else None
+    attr = torch.empty(n, dtype=torch.float32, device=dev) if value is not None else None
+    cnt = C.c_int64(0)
+    _call("mmg_edge_build", patient, item, value, n, patient_index, patient_index.numel(), item_index,
+          item_index.numel(), fwd, rev, n, attr, C.byref(cnt), ws=_lib.load().mmg_edge_build_ws_bytes(n))
+    E = int(cnt.value)
+    if E < n:
+        fwd = fwd[:, :E].contiguous()
+        rev = rev[:, :E].contiguous() if reverse else None
+        attr = attr[:E] if attr is not None else None
+    return fwd, rev, attr
+
+
 # ------------------------------------------------------------------------------------------ prediction analysis
 AN_MAX_LABS = 2048          # the lab limit of csrc/analysis.hip (and of csrc/evalred.hip)
 AN_MAX_BINS = _lib.MMG_AN_MAX_BINS
