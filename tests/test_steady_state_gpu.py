@@ -28,10 +28,10 @@ Measured worst per-row error of the dense families (MI355X, these shapes and see
 """
 import functools
 
-import numpy as np
 import pytest
 import torch
 
+import pair_ref
 import rng_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -742,39 +742,7 @@ def head_params(L):
     return A, B, W2, b2, W3, b3
 
 
-def head_ref(params, pi, li, ids, p, dpred=None, chunk=65536):
-    """The head in fp64, in chunks of 64k pairs: pred, and with dpred (zero where a pair is not visited) the six gradients.
-    ids: the pair ids the dropout streams are indexed by."""
-    A, B, W2, b2, W3, b3 = [t.double() for t in params]
-    n = pi.numel()
-    pred = torch.empty(n, dtype=torch.float64)
-    grads = [torch.zeros_like(t) for t in (A, B, W2, b2, W3, b3)] if dpred is not None else None
-    ik = float(R.inv_keep(p))
-    kkey1, kkey2, thr = R.key(SEED, R.SITE_H1), R.key(SEED, R.SITE_H2), np.uint32(R.threshold(p))
-    for i in range(0, n, chunk):
-        sl = slice(i, i + chunk)
-        a, l = pi[sl], li[sl]
-        z1 = A[a] + B[l]
-        d1 = d2 = 1.0
-        if p > 0:
-            e = ids[sl].numpy().astype(np.uint64)
-            d1 = torch.from_numpy(R.fields_at(kkey1, e[:, None] * np.uint64(64) + np.arange(64, dtype=np.uint64)) >= thr).double() * ik
-            d2 = torch.from_numpy(R.fields_at(kkey2, e[:, None] * np.uint64(32) + np.arange(32, dtype=np.uint64)) >= thr).double() * ik
-        h1 = z1.clamp(min=0) * d1
-        z2 = h1 @ W2.t() + b2
-        h2 = z2.clamp(min=0) * d2
-        pred[sl] = h2 @ W3 + b3
-        if dpred is not None:
-            gp = dpred[sl].double()
-            grads[4] += h2.t() @ gp
-            grads[5] += gp.sum()
-            dz2 = gp[:, None] * W3[None, :] * d2 * (z2 > 0)
-            grads[2] += dz2.t() @ h1
-            grads[3] += dz2.sum(0)
-            dz1 = (dz2 @ W2) * d1 * (z1 > 0)
-            grads[0].index_add_(0, a, dz1)
-            grads[1].index_add_(0, l, dz1)
-    return pred, grads
+head_ref = functools.partial(pair_ref.head_ref, seed=SEED)      # the head in fp64 (tests/pair_ref.py), on this file's streams
 
 
 def pair_fwd_n(ops, dev):
