@@ -16,7 +16,8 @@ Algebra used (exact up to fp32 re-association, inside the 1e-4 parity bar):
 from __future__ import annotations
 
 import logging
-from typing import Dict, List, Optional, Tuple
+from dataclasses import dataclass, field
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -97,6 +98,36 @@ def set_fused_wgrad(on: bool):
 
 def _mangle(et: EdgeType) -> str:
     return "<" + "___".join(et) + ">"
+
+
+class HeadLists(NamedTuple):
+    """Which head serves which pair of a PairSet (static per pair set): the tabular head the patients with deg < thr."""
+    sel_low: torch.Tensor    # positions (in sorted order) of the pairs tabular_mlp serves
+    sel_high: torch.Tensor   # ... and of those edge_predictor serves
+    counts: torch.Tensor     # int32[2] on the device: the lengths of the two lists
+    n_low: int               # the same lengths on the host (they size the launches)
+    n_high: int
+    low_rows: torch.Tensor   # int64 ids of the low-degree patients: the tabular head works on their compacted rows
+    pi_low: torch.Tensor     # pi in those compacted row numbers (-1: not a low-degree patient)
+    deg_low: torch.Tensor    # the degrees the tabular head's gate reads: all zero, every compacted row is low
+    low_pos: torch.Tensor    # int32[n_rows]: position of a patient in low_rows, or -1
+
+
+class PairSet(NamedTuple):
+    """(patient, lab) pairs sorted by patient."""
+    pi: torch.Tensor         # int32 patient ids, sorted
+    li: torch.Tensor         # int32 lab ids, in the same order
+    perm: torch.Tensor       # int64: sorted position -> position in the caller's order
+    ids: torch.Tensor        # int64 ids that key the per-pair dropout draws (perm, or the caller's pair_ids permuted)
+    lists: Optional[HeadLists]   # None when no degrees were given
+
+
+def _low_tables(deg: torch.Tensor, thr: int, n_rows: int):
+    """-> (low_rows, low_pos) of HeadLists: the patients with deg < thr and every patient's position among them."""
+    low_rows = torch.nonzero(deg < int(thr)).squeeze(1)
+    low_pos = torch.full((n_rows,), -1, dtype=torch.int32, device=deg.device)
+    low_pos[low_rows] = torch.arange(low_rows.numel(), dtype=torch.int32, device=deg.device)
+    return low_rows, low_pos
 
 
 # =============================================================================================
@@ -241,22 +272,19 @@ class HeteroRGCN(nn.Module):
     # ------------------------------------------------------------------------------ public API
     def encode_nodes(self, data):
         """model.py:206-234 -> dict node_type -> [N_t, D]."""
-        run = _Run(self, data)
-        return run.apply("encode")
+        return _Run(self, data).apply("encode")
 
     def forward(self, data):
         """model.py:236-271 -> dict node_type -> final embeddings."""
         if len(self.embeddings) == 0:
             self._init_embeddings(data)
-        run = _Run(self, data)
-        return run.apply("forward")
+        return _Run(self, data).apply("forward")
 
     def predict_lab_values(self, data, patient_indices, lab_indices):
         """model.py:273-335 -> [n] predictions (degree-gated dual heads)."""
         if len(self.embeddings) == 0:
             self._init_embeddings(data)
-        run = _Run(self, data)
-        return run.apply("predict", patient_indices, lab_indices)
+        return _Run(self, data).apply("predict", patient_indices, lab_indices)
 
     def impute_lab_matrix(self, data, patient_indices: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The degree-gated prediction of EVERY lab for the requested patients (all of them when None), in the requested
@@ -272,8 +300,7 @@ class HeteroRGCN(nn.Module):
         if len(self.embeddings) == 0:
             self._init_embeddings(data)
         with torch.no_grad():
-            run = _Run(self, data)
-            return run.apply("impute", patient_indices)
+            return _Run(self, data).apply("impute", patient_indices)
 
     def configure_execution(self, overlap: Optional[str] = None, next_bn=None, save_pair_state: Optional[bool] = None):
         """Per-model execution switches (None = keep / fall back to the module-level default): `overlap` 'auto' | 'off' |
@@ -296,13 +323,11 @@ class HeteroRGCN(nn.Module):
         self._exec = ex
         return self
 
-    # pairs sorted by patient (cached: the split is static across epochs)
     def _pairs(self, pi: torch.Tensor, li: torch.Tensor, n_rows: int, pair_ids: Optional[torch.Tensor] = None,
-               deg: Optional[torch.Tensor] = None, thr: int = 0):
-        """(pi, li) sorted by patient -> (pi32, li32, perm, rng ids, head lists).  Cached per tensor OBJECT (the
-        cache holds the tensors, so their storage cannot be recycled under a stale entry).  head lists = the
-        positions served by tabular_mlp / edge_predictor (deg[pi] < thr or not; static per pair set):
-        (sel_low, sel_high, counts_dev, n_low, n_high)."""
+               deg: Optional[torch.Tensor] = None, thr: int = 0) -> PairSet:
+        """(pi, li) sorted by patient -> PairSet, with its HeadLists (deg[pi] < thr or not) when deg is given.  Cached (the
+        split is static across epochs) per tensor OBJECT: the cache holds the tensors, so their storage cannot be recycled
+        under a stale entry."""
         if pair_ids is not None and pair_ids.numel() != pi.numel():
             pair_ids = None     # ids of ANOTHER pair set (a shard's train-pair ids while its validation pairs are scored)
         key = (id(pi), id(li), pi._version, li._version, n_rows, id(pair_ids), id(deg), int(thr))
@@ -325,14 +350,12 @@ class HeteroRGCN(nn.Module):
             sel_low, sel_high, counts = ops.pair_select(pi_sorted, deg, int(thr))
             n_low, n_high = counts.tolist()             # one-off sync per pair set (sizes the launches)
             # the tabular head only ever sees the low-degree patients (~1.5 %): it works on their compacted rows
-            low_rows = torch.nonzero(deg < int(thr)).squeeze(1)
-            low_pos = torch.full((n_rows,), -1, dtype=torch.int32, device=pi.device)
-            low_pos[low_rows] = torch.arange(low_rows.numel(), dtype=torch.int32, device=pi.device)
+            low_rows, low_pos = _low_tables(deg, thr, n_rows)
             pi_low = low_pos[pi_sorted.to(torch.int64)].contiguous() if n else pi_sorted
             deg_low = torch.zeros(max(int(low_rows.numel()), 1), dtype=torch.int32, device=pi.device)
-            lists = (sel_low[:max(n_low, 1)].clone(), sel_high[:max(n_high, 1)].clone(), counts, n_low, n_high,
-                     low_rows, pi_low, deg_low, low_pos)
-        out = (pi_sorted, li_sorted, perm64, ids, lists)
+            lists = HeadLists(sel_low[:max(n_low, 1)].clone(), sel_high[:max(n_high, 1)].clone(), counts, n_low, n_high,
+                              low_rows, pi_low, deg_low, low_pos)
+        out = PairSet(pi_sorted, li_sorted, perm64, ids, lists)
         if len(self._pair_cache) >= 6:
             self._pair_cache.clear()
         self._pair_cache[key] = (out, pi, li, pair_ids, deg)
@@ -362,10 +385,11 @@ class _NextStats:
     """The statistics pass of a BatchNorm backward, taken from the epilogue(s) of the kernel(s) that produce its upstream
     gradient (ops.NextBN / mmg_next_bn_t): y, fold = that BatchNorm's pre-activation and fold; every producer passes
     `self.next(pro)` (its own dropout mask) and reports the sums it got back.  `sums` is complete once `n` producers --
-    one per gradient that flows into the BatchNorm -- have added their share."""
+    one per gradient that flows into the BatchNorm -- have added their share.  ride False: the producer is to take them
+    with the separate pass over its output instead."""
 
-    def __init__(self, y, fold):
-        self.y, self.fold, self.sums, self.n = y, fold, None, 0
+    def __init__(self, y, fold, ride=True):
+        self.y, self.fold, self.sums, self.n, self.ride = y, fold, None, 0, ride
 
     def next(self, pro):
         return ops.NextBN(self.y, pro, self.fold, self.sums)
@@ -373,6 +397,75 @@ class _NextStats:
     def took(self, sums):
         self.sums = sums
         self.n += 1
+
+
+# ---- the tape: what a forward leaves for its backward
+@dataclass
+class _EncMid:
+    """Second linear of one encoder pass (enc_mid): its prologue (the first BatchNorm's fold + this pass's dropout), its
+    output, that output's statistics as with_bn_stats hands them back, and whether they are summed over the shards yet."""
+    pro1: Pro
+    z2: torch.Tensor
+    stats: object
+    reduced: bool = False
+
+
+@dataclass
+class _EncPass:
+    """One pass of patient_transform (enc_fwd): z1 / z2 = outputs of the first two linears, f1 / f2 = the folds of the
+    BatchNorms behind them, pro1 / pro2 = those folds with this pass's dropout, x0 / rn = the normalised output and the
+    reciprocal row norms.  A compact tail (rows: the third linear and the L2 norm saw these rows only) also keeps
+    act = the third linear's input and row_pos = every row's position in `rows` or -1."""
+    E: torch.Tensor
+    z1: torch.Tensor
+    z2: torch.Tensor
+    x0: torch.Tensor
+    rn: torch.Tensor
+    f1: ops.BNFold
+    f2: ops.BNFold
+    pro1: Pro
+    pro2: Pro
+    rows: Optional[torch.Tensor] = None
+    act: Optional[torch.Tensor] = None
+    row_pos: Optional[torch.Tensor] = None
+
+
+@dataclass
+class _LayerRec:
+    """One HeteroConv layer (layer_fwd): x / y = inputs / pre-BatchNorm outputs, folds / pros = BatchNorm fold and
+    activation prologue of every output, all by node type; rin / rout = the relations into / out of the patient rows,
+    tables / aggs = their transformed vocab rows / scattered patient means; with rin only: Wsum = the summed self-loop
+    weight, ysums = what the gather took of the patient BatchNorm (bn_fold's `sums`)."""
+    l: int
+    x: dict
+    rin: list
+    rout: list
+    y: dict = field(default_factory=dict)
+    folds: dict = field(default_factory=dict)
+    pros: dict = field(default_factory=dict)
+    tables: list = field(default_factory=list)
+    aggs: Optional[list] = None
+    Wsum: Optional[torch.Tensor] = None
+    ysums: object = None
+
+
+@dataclass
+class _PatientGrads:
+    """What layer_bwd.patient_1 leaves for vocab_2: the gradients of the vocab tables, views of the one buffer."""
+    dTs: list
+    buf: torch.Tensor
+
+
+@dataclass
+class _HeadRec:
+    """One pair head (heads_fwd): the node embeddings it read (by node type), its tables and weights, the halves of its
+    first weight, the patient rows it saw and the per-pair state its forward saved (or None)."""
+    src: dict
+    head: ops.Head
+    w1a: torch.Tensor
+    w1b: torch.Tensor
+    xP: object
+    save: Optional[tuple]
 
 
 class _StepFn(torch.autograd.Function):
@@ -453,6 +546,11 @@ class _Run:
         return self.params[name].detach()
 
     def acc(self, name, g, partial=False):
+        """name: a parameter's name, or a tuple of names whose parameters share the gradient g."""
+        if isinstance(name, tuple):
+            for n in name:
+                self.acc(n, g, partial)
+            return
         if name in self.grads:
             if g is not self.grads[name]:            # (a producer that accumulated in place hands the same tensor back)
                 self.pending.setdefault(name, []).append(g)      # summed by flush_grad_sums: one launch for all of them
@@ -489,16 +587,18 @@ class _Run:
             self.comm.all_reduce(t)
         return t
 
+    def set_pairs(self, pi, li, pair_ids=None):
+        """The pair set of a predict run: (pi, li) sorted by patient, with the head lists (HeteroRGCN._pairs)."""
+        self.pairs = self.m._pairs(pi, li, self.plan.n_rows, pair_ids, self.plan.lab_deg, int(self.m.degree_threshold))
+        self.n_pairs = pi.numel()
+
     def apply(self, mode, pi=None, li=None):
         if mode == "predict":
             if pi.numel() != li.numel():
                 raise ValueError("patient_indices and lab_indices differ in length")
             if pi.device != self.dev or li.device != self.dev:
                 raise ops._lib.MmgError("patient_indices / lab_indices must live on the model's device")
-            self.pairs = self.m._pairs(pi, li, self.plan.n_rows,
-                                       getattr(self.comm, "pair_ids", None) if self.comm else None,
-                                       self.plan.lab_deg, int(self.m.degree_threshold))
-            self.n_pairs = pi.numel()
+            self.set_pairs(pi, li, getattr(self.comm, "pair_ids", None) if self.comm else None)
         elif mode == "impute":
             P, L = self.plan.n_rows, self.plan.num_nodes["lab"]
             if pi is None:
@@ -512,8 +612,7 @@ class _Run:
             if int(pi.min()) < 0 or int(pi.max()) >= P:
                 raise IndexError("patient_indices out of range")
             self.impute_rows = pi.to(torch.int64)
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.params.values())
-        self.need_grad = need_grad
+        self.need_grad = need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.params.values())
         self.m._last_run = self if need_grad else None      # (tests drive run_backward by hand through this)
         plist = [self.params[n] for n in self.names]
         if need_grad:
@@ -537,7 +636,6 @@ class _Run:
         return outs
 
     def _run_forward(self, mode):
-        T, plan = self.T, self.plan
         if mode == "encode":
             enc = self.enc_fwd(0, 1)
             x = self.enc_dict(enc)
@@ -562,16 +660,16 @@ class _Run:
             first = self.enc_first(2)            # shared by both passes (no dropout before the first BatchNorm)
             m0, m1 = self.enc_mid(0, first), self.enc_mid(1, first)
             if self.comm is not None and self.T:     # sharded: the statistics of both passes in ONE all-reduce
-                both = torch.stack([m0[2], m1[2]])
+                both = torch.stack([m0.stats, m1.stats])
                 self.allreduce(both)
-                m0[2], m1[2], m0[3], m1[3] = both[0], both[1], True, True
-            enc0 = self.enc_fwd(0, 1, first, rows=self.pairs[4][5], mid=m0)   # feeds the tabular head only: low-degree rows
-            enc0["row_pos"] = self.pairs[4][8]
+                m0.stats, m1.stats, m0.reduced, m1.reduced = both[0], both[1], True, True
+            lists = self.pairs.lists                 # the first pass feeds the tabular head only: low-degree rows
+            enc0 = self.enc_fwd(0, 1, first, rows=lists.low_rows, row_pos=lists.low_pos, mid=m0)
             enc1 = self.enc_fwd(1, 1, first, mid=m1)
         else:
             enc0 = enc1 = self.enc_fwd(0, 2)
         init = self.enc_dict(enc0)
-        self._init_compact = enc0.get("rows") is not None
+        self._init_compact = enc0.rows is not None
         fin, layers = self.layers_fwd(self.enc_dict(enc1))
         pred, hrec = self.heads_fwd(init, fin)
         self.tape["mode"] = ("predict", enc0, enc1, layers, hrec)
@@ -618,7 +716,7 @@ class _Run:
                 self.enc_bwd(enc0, tot)
             else:
                 a1 = self.enc_bwd_a(enc1, g.get(ROW_TYPE))
-                a0 = self.enc_bwd_a(enc0, gi if enc0.get("rows") is not None else dense(gi))
+                a0 = self.enc_bwd_a(enc0, gi if enc0.rows is not None else dense(gi))
                 if self.comm is not None:        # sharded: the BatchNorm statistics of both passes in ONE all-reduce
                     live = [a for a in (a1, a0) if a is not None]
                     if len(live) == 2:
@@ -627,7 +725,7 @@ class _Run:
                         a1, a0 = (a1[0], both[0]), (a0[0], both[1])
                     elif live:
                         self.allreduce(live[0][1])
-                nstats = _NextStats(enc1["z1"], enc1["f1"])      # the shared first BatchNorm: both passes add their share
+                nstats = _NextStats(enc1.z1, enc1.f1)      # the shared first BatchNorm: both passes add their share
                 self.enc_bwd_shared(enc1, self.enc_bwd_b(enc1, a1, nstats), enc0, self.enc_bwd_b(enc0, a0, nstats), nstats)
             for t, gt in g.items():
                 if t not in (ROW_TYPE, BN_SUMS) and gt is not None:
@@ -665,28 +763,39 @@ class _Run:
         ent[1] += int(n_updates)
 
     def bn_fold(self, y, mod: nn.BatchNorm1d, n_updates=1, sharded=False, sums=None, reduced=False) -> ops.BNFold:
-        """Batch statistics (train) or running statistics (eval) folded to scale/shift.  sums: the column sums of
-        y and y^2 when the producing kernel already took them (reduced: already summed over the shards)."""
+        """Batch statistics (train) or running statistics (eval) folded to scale/shift.  sums: what with_bn_stats handed
+        back for y -- the BNFold of a producer that already folded it, or the column sums of y and y^2 (reduced: already
+        summed over the shards), or None."""
         count = y.shape[0]
-        if isinstance(sums, ops.BNFold):         # the producer already folded it (bn_spec)
-            self.count_bn(mod, n_updates)
+        if not self.T:
+            return ops.bn_finalize(None, count, mod.weight.detach(), mod.bias.detach(), mod.running_mean, mod.running_var,
+                                   False, 0)
+        self.count_bn(mod, n_updates)
+        if isinstance(sums, ops.BNFold):
             return sums
-        if self.T:
-            if sums is None:
-                sums = ops.col_reduce2(y)
-            if sharded and self.comm is not None:
-                if not reduced:
-                    self.allreduce(sums)
-                count = self.plan.n_rows_global
-            if count <= 1:
-                raise ValueError(f"Expected more than 1 value per channel when training, got input size {list(y.shape)}")
-            fold = ops.bn_finalize(sums, count, mod.weight.detach(), mod.bias.detach(), mod.running_mean,
-                                   mod.running_var, True, n_updates)
-            ent = self._nbt.setdefault(id(mod), [mod.num_batches_tracked, 0])           # bumped once, together
-            ent[1] += int(n_updates)
-            return fold
-        return ops.bn_finalize(None, count, mod.weight.detach(), mod.bias.detach(), mod.running_mean, mod.running_var,
-                               False, 0)
+        if sums is None:
+            sums = ops.col_reduce2(y)
+        if sharded and self.comm is not None:
+            if not reduced:
+                self.allreduce(sums)
+            count = self.plan.n_rows_global
+        if count <= 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {list(y.shape)}")
+        return ops.bn_finalize(sums, count, mod.weight.detach(), mod.bias.detach(), mod.running_mean, mod.running_var,
+                               True, n_updates)
+
+    def with_bn_stats(self, producer, mod: Optional[nn.BatchNorm1d], n_updates: int, rows: int, stats=True):
+        """Runs producer(**epilogue), a kernel whose [rows, .] output feeds the patient-sharded BatchNorm `mod` (None: no
+        BatchNorm), with the most that kernel can do for that BatchNorm -> (what it returns first, what bn_fold takes as
+        `sums`): the finished BNFold where bn_spec allows, else in training the column sums (stats: the kernel can take
+        them at this shape), else None."""
+        spec = self.bn_spec(mod, n_updates, rows, True) if mod is not None else None
+        if spec is not None:
+            out = producer(bn=spec)
+            return out[0], out[2]
+        if self.T and mod is not None and stats:
+            return producer(with_stats=True)
+        return producer(), None
 
     def enc_first(self, n_updates):
         """First linear + BatchNorm statistics of patient_transform.  No dropout sits in front of them, so the two
@@ -694,54 +803,46 @@ class _Run:
         statistics advanced n_updates times."""
         pt = self.m.patient_transform
         E = self.W(f"embeddings.{ROW_TYPE}.weight")
-        # the batch statistics of z1 / z2 come out of the GEMM epilogue (training mode)
-        spec = self.bn_spec(pt[1], n_updates, E.shape[0], True)
-        if spec is not None:                     # ... and so does the BatchNorm fold (single GPU)
-            z1, _, s1 = ops.linear_fwd(E, pt[0].weight.detach(), pt[0].bias.detach(), bn=spec)
-        else:
-            z1, s1 = ops.linear_fwd(E, pt[0].weight.detach(), pt[0].bias.detach(), with_stats=True) if self.T else \
-                (ops.linear_fwd(E, pt[0].weight.detach(), pt[0].bias.detach()), None)
+        # the batch statistics of z1 / z2 come out of the GEMM epilogue (training mode), on a single GPU already folded
+        z1, s1 = self.with_bn_stats(lambda **epi: ops.linear_fwd(E, pt[0].weight.detach(), pt[0].bias.detach(), **epi),
+                                    pt[1], n_updates, E.shape[0])
         f1 = self.bn_fold(z1, pt[1], n_updates, sharded=True, sums=s1)
         return E, z1, f1
 
-    def enc_mid(self, call, first, n_updates=1):
+    def enc_mid(self, call, first, n_updates=1) -> _EncMid:
         """Second linear of pass `call` with the BatchNorm statistics of its output (not yet summed over the shards; on a
         single GPU already folded: a BNFold instead of the sums)."""
         pt = self.m.patient_transform
         E, z1, f1 = first
         pro1 = Pro(f1.scale, f1.shift, True, self.p, self.seed, 2 * call, self.plan.row_offset, self.seed_dev)
-        spec = self.bn_spec(pt[5], n_updates, z1.shape[0], True)
-        if spec is not None:
-            z2, _, s2 = ops.linear_fwd(z1, pt[4].weight.detach(), pt[4].bias.detach(), pro=pro1, bn=spec)
-        else:
-            z2, s2 = ops.linear_fwd(z1, pt[4].weight.detach(), pt[4].bias.detach(), pro=pro1, with_stats=True) if self.T else \
-                (ops.linear_fwd(z1, pt[4].weight.detach(), pt[4].bias.detach(), pro=pro1), None)
-        return [pro1, z2, s2, False]
+        z2, s2 = self.with_bn_stats(lambda **epi: ops.linear_fwd(z1, pt[4].weight.detach(), pt[4].bias.detach(), pro=pro1,
+                                                                 **epi), pt[5], n_updates, z1.shape[0])
+        return _EncMid(pro1, z2, s2)
 
-    def enc_fwd(self, call, n_updates, first=None, rows=None, mid=None):
-        """rows (int64 ids): everything after the last BatchNorm -- third linear, L2 norm -- is evaluated for these rows
-        only and x0 / rn are compact [len(rows), .] (the first encode_nodes pass of a training step only feeds the
-        tabular head, which only sees the low-degree patients; its BatchNorm statistics still need every row)."""
+    def enc_fwd(self, call, n_updates, first=None, rows=None, row_pos=None, mid: Optional[_EncMid] = None) -> _EncPass:
+        """rows (int64 ids; row_pos = every row's position among them or -1): everything after the last BatchNorm -- third
+        linear, L2 norm -- is evaluated for these rows only and x0 / rn are compact [len(rows), .] (the first encode_nodes
+        pass of a training step only feeds the tabular head, which only sees the low-degree patients; its BatchNorm
+        statistics still need every row)."""
         pt = self.m.patient_transform
-        off = self.plan.row_offset
         if first is None:
             first = self.enc_first(n_updates)
         E, z1, f1 = first
-        pro1, z2, s2, reduced = mid if mid is not None else self.enc_mid(call, first, n_updates)
-        f2 = self.bn_fold(z2, pt[5], n_updates, sharded=True, sums=s2, reduced=reduced)
-        pro2 = Pro(f2.scale, f2.shift, True, self.p, self.seed, 2 * call + 1, off, self.seed_dev)
+        if mid is None:
+            mid = self.enc_mid(call, first, n_updates)
+        z2 = mid.z2
+        f2 = self.bn_fold(z2, pt[5], n_updates, sharded=True, sums=mid.stats, reduced=mid.reduced)
+        pro2 = Pro(f2.scale, f2.shift, True, self.p, self.seed, 2 * call + 1, self.plan.row_offset, self.seed_dev)
+        act = None
         if rows is not None:
             act = ops.affine_act_drop_rows(z2, pro2, rows)       # the dropout masks of the ORIGINAL rows
             x0, rn = ops.linear_l2norm_fwd(act, pt[8].weight.detach(), pt[8].bias.detach())
-            return dict(E=E, z1=z1, z2=z2, x0=x0, rn=rn, f1=f1, f2=f2, pro1=pro1, pro2=pro2, rows=rows, act=act)
-        x0, rn = ops.linear_l2norm_fwd(z2, pt[8].weight.detach(), pt[8].bias.detach(), pro=pro2)    # third linear + L2 norm
-        return dict(E=E, z1=z1, z2=z2, x0=x0, rn=rn, f1=f1, f2=f2, pro1=pro1, pro2=pro2)
+        else:
+            x0, rn = ops.linear_l2norm_fwd(z2, pt[8].weight.detach(), pt[8].bias.detach(), pro=pro2)   # third linear + L2 norm
+        return _EncPass(E, z1, z2, x0, rn, f1, f2, mid.pro1, pro2, rows, act, row_pos)
 
-    def enc_dict(self, enc):
-        x = {}
-        for t in self.plan.node_types:
-            x[t] = enc["x0"] if t == ROW_TYPE else self.W(f"embeddings.{t}.weight")
-        return x
+    def enc_dict(self, enc: _EncPass):
+        return {t: enc.x0 if t == ROW_TYPE else self.W(f"embeddings.{t}.weight") for t in self.plan.node_types}
 
     def bn_bwd_sums(self, g, y, pro: Pro, fold: Optional[ops.BNFold], sharded: bool):
         """first half of bn_bwd: the column statistics (all-reduced over the shards); None without batch norm."""
@@ -752,75 +853,50 @@ class _Run:
             self.allreduce(sums)
         return sums
 
+    def bn_param_grads(self, fold: Optional[ops.BNFold], bn_prefix: Optional[str], sums, N: int):
+        """The (sums, count, dbeta, dgamma) arguments of a BatchNorm-backward kernel, and that BatchNorm's bias / weight
+        gradients recorded: in training the kernel writes them (d beta | d gamma are rows of `sums`, converted), in eval
+        mode they ARE the sums and the kernel gets none; nothing without BatchNorm."""
+        if fold is None:
+            return None, 1.0, None, None
+        dbg = torch.empty(2, N, device=sums.device)      # d beta | d gamma
+        self.acc(bn_prefix + ".bias", dbg[0])
+        self.acc(bn_prefix + ".weight", dbg[1])
+        if fold.training:
+            return sums, fold.count, dbg[0], dbg[1]
+        dbg.copy_(sums)
+        return None, 1.0, None, None
+
     def bn_bwd(self, g, y, pro: Pro, fold: Optional[ops.BNFold], bn_prefix: Optional[str], sharded: bool, sums=None,
                add_into=None):
         """grad wrt the pre-BN tensor y of  x' = dropout(relu(BN(y)));  accumulates d gamma / d beta.
         add_into: add the result to this tensor (inside the kernel) instead of returning a new one."""
-        acc = add_into is not None
-        if fold is None:        # no batch norm: relu/dropout only
-            return ops.bn_bwd_apply(g, y, pro, None, out=add_into, accumulate=acc)
-        if sums is None:
+        if fold is not None and sums is None:
             sums = self.bn_bwd_sums(g, y, pro, fold, sharded)
-        N = y.shape[1]
-        dbg = torch.empty(2, N, device=y.device)       # d beta | d gamma, written by the apply kernel
-        if fold.training:
-            dy = ops.bn_bwd_apply(g, y, pro, fold, sums, fold.count, dbg[0], dbg[1], out=add_into, accumulate=acc)
-        else:
-            dbg.copy_(sums)
-            dy = ops.bn_bwd_apply(g, y, pro, fold, out=add_into, accumulate=acc)
-        self.acc(bn_prefix + ".bias", dbg[0])
-        self.acc(bn_prefix + ".weight", dbg[1])
-        return dy
+        return ops.bn_bwd_apply(g, y, pro, fold, *self.bn_param_grads(fold, bn_prefix, sums, y.shape[1]),
+                                out=add_into, accumulate=add_into is not None)
 
-    def bn_lin_bwd(self, g, y, pro: Pro, fold: Optional[ops.BNFold], bn_prefix: Optional[str], sharded: bool, sums, W,
-                   nxt: Optional[Tuple["_NextStats", Pro]] = None, wgrad: Optional[ops.FusedWgrad] = None):
-        """bn_bwd followed by the data gradient  dz @ W  through the linear in front of that BatchNorm, as ONE kernel
-        (mmg_linear_bnbwd: g and y are read once, dz is written once for the weight gradient).  -> (dz, dx), or None where
-        the fused kernel does not apply (the caller then runs bn_bwd and the GEMM).
-        nxt = (stats holder, prologue) of the BatchNorm below, whose backward consumes dx: its statistics ride along.
-        wgrad: the weight gradient of that linear in the same launch (ops.FusedWgrad; only used where the result is not None)."""
-        if g is None or pro.relu not in (0, 1) or not ops.linear_bnbwd_supported(y.shape[0], W.shape[1], y.shape[1]):
-            return None
-        nb = nxt[0].next(nxt[1]) if nxt is not None else None
-
-        def done(out):
-            if nb is not None:
-                nxt[0].took(out[2])
-            return out[0], out[1]
-
-        if fold is None:
-            return done(ops.linear_bnbwd(g, y, pro, None, W, next_bn=nb, wgrad=wgrad))
-        if sums is None:
-            sums = self.bn_bwd_sums(g, y, pro, fold, sharded)
-        dbg = torch.empty(2, y.shape[1], device=y.device)       # d beta | d gamma, written by the kernel
-        if fold.training:
-            out = ops.linear_bnbwd(g, y, pro, fold, W, sums, fold.count, dbg[0], dbg[1], next_bn=nb, wgrad=wgrad)
-        else:
-            dbg.copy_(sums)
-            out = ops.linear_bnbwd(g, y, pro, fold, W, next_bn=nb, wgrad=wgrad)
-        self.acc(bn_prefix + ".bias", dbg[0])
-        self.acc(bn_prefix + ".weight", dbg[1])
-        return done(out)
+    def wgrad_target(self, wname, bname):
+        """Where the weight (and bias) gradient of a linear goes, as ops.linear_wgrad / ops.FusedWgrad arguments: a second
+        contribution (the encoder runs twice) accumulates inside the kernel -- with a bias, where both have a gradient."""
+        gw = self.grads.get(wname)
+        if bname is None:
+            return dict(out=gw, accumulate=gw is not None)
+        gb = self.grads.get(bname)
+        both = gw is not None and gb is not None
+        return dict(out=gw if both else None, accumulate=both, with_bias=True, bias_out=gb if both else None)
 
     def lin_bwd(self, dy, x, pro, wname, bname, need_dx=True, partial=False, dx_into=None):
         """grads of  y = pro(x) W^T + b.  dx_into: accumulate dX into this tensor (inside the GEMM) instead of a new one."""
-        gw = self.grads.get(wname)       # a second contribution (the encoder runs twice) accumulates inside the kernel
+        res = ops.linear_wgrad(dy, x, pro, defer=self.wgrad_jobs, **self.wgrad_target(wname, bname))
         if bname is not None:            # the bias gradient (column sums of dy) comes out of the same pass over dy
-            gb = self.grads.get(bname)
-            if gw is not None and gb is not None:
-                ops.linear_wgrad(dy, x, pro, out=gw, accumulate=True, with_bias=True, bias_out=gb, defer=self.wgrad_jobs)
-                dW, db = gw, gb
-            else:
-                dW, db = ops.linear_wgrad(dy, x, pro, with_bias=True, defer=self.wgrad_jobs)
-            self.acc(wname, dW, partial)
-            self.acc(bname, db, partial)
+            self.acc(wname, res[0], partial)
+            self.acc(bname, res[1], partial)
         else:
-            self.acc(wname, ops.linear_wgrad(dy, x, pro, out=gw, accumulate=gw is not None, defer=self.wgrad_jobs), partial)
-        if need_dx:
-            if dx_into is not None:
-                return ops.linear_fwd(dy, self.W(wname), w_kn=True, out=dx_into, accumulate=True)
-            return ops.linear_fwd(dy, self.W(wname), w_kn=True)          # dX = dY . W, W read in place
-        return None
+            self.acc(wname, res, partial)
+        if not need_dx:
+            return None
+        return ops.linear_fwd(dy, self.W(wname), w_kn=True, out=dx_into, accumulate=dx_into is not None)   # dX = dY . W
 
     def fused_wgrad_for(self, x, pro, wname, bname, keep_dz, M, N, K, next_bn=False) -> Optional[ops.FusedWgrad]:
         """The weight gradient lin_bwd(dz, x, pro, wname, bname, need_dx=False) would compute, as an ops.FusedWgrad for the
@@ -828,125 +904,117 @@ class _Run:
         next_bn: the GEMM also takes the next BatchNorm's statistics in its epilogue.  The fused kernel has no room for that
         epilogue (the statistics would come from a separate pass over dx), and at the x100 shape that pass costs more than
         the fused weight gradient saves (L2 backward: 96.7 + 56.1 us separate, 112.0 + 45.9 fused + pass): not taken."""
-        if next_bn or not self.fused_wgrad or not ops.linear_bnbwd_wgrad_supported(M, N, K):
+        if next_bn or not self.fused_wgrad or not x.is_contiguous() or not ops.linear_bnbwd_wgrad_supported(M, N, K):
             return None
-        gw = self.grads.get(wname)
-        if bname is not None:
-            gb = self.grads.get(bname)
-            both = gw is not None and gb is not None
-            return ops.FusedWgrad(x, pro, out=gw if both else None, accumulate=both, with_bias=True,
-                                  bias_out=gb if both else None, defer=self.wgrad_jobs, keep_dz=keep_dz)
-        return ops.FusedWgrad(x, pro, out=gw, accumulate=gw is not None, defer=self.wgrad_jobs, keep_dz=keep_dz)
+        return ops.FusedWgrad(x, pro, defer=self.wgrad_jobs, keep_dz=keep_dz, **self.wgrad_target(wname, bname))
 
-    def fused_wgrad_done(self, fw: ops.FusedWgrad, wname, bname, partial=False):
-        self.acc(wname, fw.dW, partial)
-        if bname is not None:
-            self.acc(bname, fw.db, partial)
+    def bn_lin_bwd(self, form, args, bn_prefix: Optional[str], x, pro: Optional[Pro], wname, bname, W,
+                   next_bn: Optional[_NextStats] = None, keep_dz=False):
+        """Backward of  x' = dropout(relu(BN(y))),  y = pro(x) W^T + b  as ONE kernel (mmg_linear_bnbwd): the BatchNorm
+        backward dz, the data gradient dx = dz @ W, the BatchNorm's bias / weight gradients (bn_prefix; None: no BatchNorm)
+        and the linear's weight / bias gradients (wname / bname, per-shard partial sums; a tuple of names: parameters that
+        share the gradient) -- in the same launch where fused_wgrad_for allows (dz is then only written with keep_dz), by
+        lin_bwd elsewhere.  -> (dz, dx), or None, with nothing launched, where the kernel does not apply.  form, args:
+          "plain"  (g, y, ypro, fold, sums, sharded)            sums None: taken here (all-reduced when sharded)
+          "rows"   (g_rows, y, ypro, fold, sums, row_pos)       g is zero outside the listed rows (training folds only)
+          "two"    (g_a, y, ypro_a, fold, sums, g_b, ypro_b)    two upstream gradients with their own dropout masks
+          "l2"     (g, out, rn)                                 an L2 normalisation in the BatchNorm's place (always applies)
+        next_bn: holder of the statistics of the BatchNorm backward that consumes dx (that BatchNorm's prologue is `pro`):
+        taken in the kernel's epilogue, or (holder.ride False) by the separate pass right behind it."""
+        K, N = W.shape
+        if form == "l2":
+            (g, y, rn), fold, sums = args, None, None
+        else:
+            g, y, ypro, fold, sums, *more = args
+            ok = g is not None if form == "plain" else form == "two" or (more[0] is not None and fold.training)
+            mode = {"plain": ops.BNBWD_BN, "rows": ops.BNBWD_ROWS, "two": ops.BNBWD_BN2}[form]
+            if not ok or ypro.relu not in (0, 1) or not ops.linear_bnbwd_supported(y.shape[0], N, K, mode):
+                return None
+        nb = next_bn.next(pro) if next_bn is not None and next_bn.ride else None
+        fw = self.fused_wgrad_for(x, pro, wname, bname, keep_dz, y.shape[0], N, K, next_bn=nb is not None)
+        if form == "plain" and fold is not None and sums is None:
+            sums = self.bn_bwd_sums(g, y, ypro, fold, more[0])
+        bn = self.bn_param_grads(fold, bn_prefix, sums, K)
+        if form == "plain":
+            out = ops.linear_bnbwd(g, y, ypro, fold, W, *bn, next_bn=nb, wgrad=fw)
+        elif form == "rows":
+            out = ops.linear_bnbwd_rows(g, more[0], y, ypro, fold, W, *bn, next_bn=nb, wgrad=fw)
+        elif form == "two":
+            out = ops.linear_bnbwd2(g, more[0], y, ypro, more[1], fold, W, *bn, wgrad=fw)
+        else:
+            out = ops.linear_l2bwd(g, y, rn, W, next_bn=nb, wgrad=fw)
+        if next_bn is not None:
+            next_bn.took(out[2] if nb is not None else ops.bn_bwd_stats(out[1], next_bn.y, pro, next_bn.fold))
+        if fw is not None:
+            self.acc(wname, fw.dW, True)
+            if bname is not None:
+                self.acc(bname, fw.db, True)
+        else:
+            self.lin_bwd(out[0], x, pro, wname, bname, need_dx=False, partial=True)
+        return out[0], out[1]
 
-    def enc_bwd_a(self, enc, g_x0):
+    def enc_bwd_a(self, enc: _EncPass, g_x0):
         """Backward of one encoder pass down to the statistics of its last BatchNorm (local sums, not yet all-reduced):
         -> (upstream gradient of that BatchNorm [dense, or the listed rows], fp64 sums) or None."""
         if g_x0 is None:
             return None
         pt = "patient_transform"
-        if enc.get("rows") is not None:      # compact tail: g_x0 = (row ids, gradient rows)
+        if enc.rows is not None:             # compact tail: g_x0 = (row ids, gradient rows)
             rows, g_rows = g_x0
             # L2-norm backward inside the data-gradient GEMM of the third linear; the weight gradient reads dz3 afterwards
-            dz3, g = ops.linear_l2bwd(g_rows.contiguous(), enc["x0"], enc["rn"], self.W(f"{pt}.8.weight"))
-            self.lin_bwd(dz3, enc["act"], None, f"{pt}.8.weight", f"{pt}.8.bias", need_dx=False, partial=True)
-            sums = ops.bn_bwd_stats_rows(g, enc["z2"], rows, enc["pro2"], enc["f2"])
-        else:
-            # the statistics of the second BatchNorm's backward come out of the epilogue of the GEMM that produces its
-            # upstream gradient (the separate pass read g and z2 once more); the weight gradient of the third linear
-            # rides in the same launch where it can (dz3 is then never written)
-            W8 = self.W(f"{pt}.8.weight")
-            fw = self.fused_wgrad_for(enc["z2"], enc["pro2"], f"{pt}.8.weight", f"{pt}.8.bias", False,
-                                      enc["x0"].shape[0], W8.shape[1], W8.shape[0], next_bn="enc2" in self.next_bn_sites)
-            if "enc2" in self.next_bn_sites:
-                dz3, g, sums = ops.linear_l2bwd(g_x0.contiguous(), enc["x0"], enc["rn"], W8,
-                                                next_bn=ops.NextBN(enc["z2"], enc["pro2"], enc["f2"]), wgrad=fw)
-            else:
-                dz3, g = ops.linear_l2bwd(g_x0.contiguous(), enc["x0"], enc["rn"], W8, wgrad=fw)
-                sums = ops.bn_bwd_stats(g, enc["z2"], enc["pro2"], enc["f2"])
-            if fw is not None:
-                self.fused_wgrad_done(fw, f"{pt}.8.weight", f"{pt}.8.bias", partial=True)
-            else:
-                self.lin_bwd(dz3, enc["z2"], enc["pro2"], f"{pt}.8.weight", f"{pt}.8.bias", need_dx=False, partial=True)
-        return g, sums
+            dz3, g = ops.linear_l2bwd(g_rows.contiguous(), enc.x0, enc.rn, self.W(f"{pt}.8.weight"))
+            self.lin_bwd(dz3, enc.act, None, f"{pt}.8.weight", f"{pt}.8.bias", need_dx=False, partial=True)
+            return g, ops.bn_bwd_stats_rows(g, enc.z2, rows, enc.pro2, enc.f2)
+        # the statistics of the second BatchNorm's backward come out of the epilogue of the GEMM that produces its upstream
+        # gradient where that site is on; the third linear's weight gradient rides in the launch where it can (no dz3 then)
+        nstats = _NextStats(enc.z2, enc.f2, ride="enc2" in self.next_bn_sites)
+        _, g = self.bn_lin_bwd("l2", (g_x0.contiguous(), enc.x0, enc.rn), None, enc.z2, enc.pro2, f"{pt}.8.weight",
+                               f"{pt}.8.bias", self.W(f"{pt}.8.weight"), next_bn=nstats)
+        return g, nstats.sums
 
-    def enc_bwd_b(self, enc, state, nstats: Optional["_NextStats"] = None):
+    def enc_bwd_b(self, enc: _EncPass, state, nstats: Optional["_NextStats"] = None):
         """...and from the (all-reduced) statistics on to the upstream gradient of the first BatchNorm.
         nstats: holder of that BatchNorm's backward statistics; a fused producer adds its share (this pass's mask)."""
         if state is None:
             return None
         pt = "patient_transform"
         g, sums = state
-        y, pro, fold = enc["z2"], enc["pro2"], enc["f2"]
-        nxt = (nstats, enc["pro1"]) if nstats is not None and nstats.fold is not None and "enc1" in self.next_bn_sites else None
-        if enc.get("rows") is not None:
+        y, pro, fold = enc.z2, enc.pro2, enc.f2
+        if nstats is not None and (nstats.fold is None or "enc1" not in self.next_bn_sites):
+            nstats = None
+        # the BatchNorm backward (for a compact tail: the dense pass over an all-zero gradient and the patch of the listed
+        # rows) inside the data-gradient GEMM of the second linear, + its weight gradient
+        form, args = ("rows", (g, y, pro, fold, sums, enc.row_pos)) if enc.rows is not None else \
+            ("plain", (g, y, pro, fold, sums, True))
+        fused = self.bn_lin_bwd(form, args, f"{pt}.5", enc.z1, enc.pro1, f"{pt}.4.weight", f"{pt}.4.bias",
+                                self.W(f"{pt}.4.weight"), next_bn=nstats)
+        if fused is not None:
+            return fused[1]
+        if enc.rows is not None:
             # an upstream gradient that is zero outside the listed rows (training statistics): the dense apply pass never
             # reads a gradient tensor, the listed rows are patched afterwards
-            dbg = torch.empty(2, y.shape[1], device=y.device)   # d beta | d gamma, written by the apply kernel
-            W4 = self.W(f"{pt}.4.weight")
-            if enc.get("row_pos") is not None and pro.relu in (0, 1) and fold.training and \
-                    ops.linear_bnbwd_supported(y.shape[0], W4.shape[1], y.shape[1], ops.BNBWD_ROWS):
-                # dense pass, row patch and the data-gradient GEMM of the second linear in ONE kernel (+ its weight gradient)
-                fw = self.fused_wgrad_for(enc["z1"], enc["pro1"], f"{pt}.4.weight", f"{pt}.4.bias", False,
-                                          y.shape[0], W4.shape[1], W4.shape[0], next_bn=nxt is not None)
-                if nxt is not None:
-                    dz2, dx, nsums = ops.linear_bnbwd_rows(g, enc["row_pos"], y, pro, fold, W4, sums, fold.count, dbg[0], dbg[1],
-                                                           next_bn=nstats.next(enc["pro1"]), wgrad=fw)
-                    nstats.took(nsums)
-                else:
-                    dz2, dx = ops.linear_bnbwd_rows(g, enc["row_pos"], y, pro, fold, W4, sums, fold.count, dbg[0], dbg[1],
-                                                    wgrad=fw)
-                self.acc(f"{pt}.5.bias", dbg[0])
-                self.acc(f"{pt}.5.weight", dbg[1])
-                if fw is not None:
-                    self.fused_wgrad_done(fw, f"{pt}.4.weight", f"{pt}.4.bias", partial=True)
-                else:
-                    self.lin_bwd(dz2, enc["z1"], enc["pro1"], f"{pt}.4.weight", f"{pt}.4.bias", need_dx=False, partial=True)
-                return dx
-            dz2 = ops.bn_bwd_apply(None, y, pro, fold, sums, fold.count, dbg[0], dbg[1])
-            ops.bn_bwd_apply_rows(g, y, enc["rows"], pro, dz2)
-            self.acc(f"{pt}.5.bias", dbg[0])
-            self.acc(f"{pt}.5.weight", dbg[1])
+            dz2 = ops.bn_bwd_apply(None, y, pro, fold, *self.bn_param_grads(fold, f"{pt}.5", sums, y.shape[1]))
+            ops.bn_bwd_apply_rows(g, y, enc.rows, pro, dz2)
         else:
-            W4 = self.W(f"{pt}.4.weight")
-            fw = self.fused_wgrad_for(enc["z1"], enc["pro1"], f"{pt}.4.weight", f"{pt}.4.bias", False,
-                                      y.shape[0], W4.shape[1], W4.shape[0], next_bn=nxt is not None)
-            fused = self.bn_lin_bwd(g, y, pro, fold, f"{pt}.5", True, sums, W4, nxt=nxt, wgrad=fw)
-            if fused is not None:                # BatchNorm backward inside the data-gradient GEMM of the second linear
-                dz2, dx = fused
-                if fw is not None:
-                    self.fused_wgrad_done(fw, f"{pt}.4.weight", f"{pt}.4.bias", partial=True)
-                else:
-                    self.lin_bwd(dz2, enc["z1"], enc["pro1"], f"{pt}.4.weight", f"{pt}.4.bias", need_dx=False, partial=True)
-                return dx
             dz2 = self.bn_bwd(g, y, pro, fold, f"{pt}.5", sharded=True, sums=sums)
-        return self.lin_bwd(dz2, enc["z1"], enc["pro1"], f"{pt}.4.weight", f"{pt}.4.bias", partial=True)
+        return self.lin_bwd(dz2, enc.z1, enc.pro1, f"{pt}.4.weight", f"{pt}.4.bias", partial=True)
 
-    def enc_bwd(self, enc, g_x0, upto_bn1=False):
-        """upto_bn1: stop in front of the first BatchNorm and return its upstream gradient (the two passes of a training
-        step share that BatchNorm and the linear in front of it: enc_bwd_shared differentiates them once for both)."""
+    def enc_bwd(self, enc: _EncPass, g_x0):
+        """Backward of an encoder pass that shares nothing with another one."""
         state = self.enc_bwd_a(enc, g_x0)
         if state is None:
-            return None
+            return
         if self.comm is not None:
             self.allreduce(state[1])
-        nstats = _NextStats(enc["z1"], enc["f1"]) if not upto_bn1 else None
+        nstats = _NextStats(enc.z1, enc.f1)
         g = self.enc_bwd_b(enc, state, nstats)
-        if upto_bn1:
-            return g
-        pt = "patient_transform"
         sums = nstats.sums if nstats.n == 1 else None        # from the epilogue of the kernel that produced g
         if sums is not None and self.comm is not None:
             self.allreduce(sums)
-        dz1 = self.bn_bwd(g, enc["z1"], enc["pro1"], enc["f1"], f"{pt}.1", sharded=True, sums=sums)
+        dz1 = self.bn_bwd(g, enc.z1, enc.pro1, enc.f1, "patient_transform.1", sharded=True, sums=sums)
         self.enc_bwd_first(enc, dz1)
-        return None
 
-    def enc_bwd_shared(self, enc_a, g_a, enc_b, g_b, nstats: Optional["_NextStats"] = None):
+    def enc_bwd_shared(self, enc_a: _EncPass, g_a, enc_b: _EncPass, g_b, nstats: Optional["_NextStats"] = None):
         """First BatchNorm + first linear of two passes that share them (same z1, same statistics, own dropout masks):
         g_out = g_out(g_a; pro1_a) + g_out(g_b; pro1_b) -- one statistics pass, one apply pass, one weight / data gradient.
         nstats: the statistics the producers of g_a / g_b summed in their epilogues (complete when every gradient that is
@@ -960,41 +1028,30 @@ class _Run:
             enc, g = (enc_a, g_a) if g_b is None else (enc_b, g_b)
             if pre is not None and self.comm is not None:
                 self.allreduce(pre)
-            dz1 = self.bn_bwd(g, enc["z1"], enc["pro1"], enc["f1"], f"{pt}.1", sharded=True, sums=pre)
+            dz1 = self.bn_bwd(g, enc.z1, enc.pro1, enc.f1, f"{pt}.1", sharded=True, sums=pre)
         else:
-            y, fold = enc_a["z1"], enc_a["f1"]
-            sums = pre if pre is not None else ops.bn_bwd_stats2(g_a, g_b, y, enc_a["pro1"], enc_b["pro1"], fold)
+            y, fold = enc_a.z1, enc_a.f1
+            sums = pre if pre is not None else ops.bn_bwd_stats2(g_a, g_b, y, enc_a.pro1, enc_b.pro1, fold)
             if self.comm is not None:
                 self.allreduce(sums)
-            dbg = torch.empty(2, y.shape[1], device=y.device)
-            ename, W0 = f"embeddings.{ROW_TYPE}.weight", self.W(f"{pt}.0.weight")
-            if self.params[ename].requires_grad and ename not in self.grads and \
-                    ops.linear_bnbwd2_supported(y.shape[0], W0.shape[1], y.shape[1]):
-                # the joint BatchNorm backward inside the data-gradient GEMM of the first linear (dE, + its weight gradient)
-                fw = self.fused_wgrad_for(enc_a["E"], None, f"{pt}.0.weight", f"{pt}.0.bias", False,
-                                          y.shape[0], W0.shape[1], W0.shape[0])
-                dz1, dE = ops.linear_bnbwd2(g_a, g_b, y, enc_a["pro1"], enc_b["pro1"], fold, W0, sums, fold.count,
-                                            dbg[0], dbg[1], wgrad=fw)
-                self.acc(f"{pt}.1.bias", dbg[0])
-                self.acc(f"{pt}.1.weight", dbg[1])
-                if fw is not None:
-                    self.fused_wgrad_done(fw, f"{pt}.0.weight", f"{pt}.0.bias", partial=True)
-                else:
-                    self.lin_bwd(dz1, enc_a["E"], None, f"{pt}.0.weight", f"{pt}.0.bias", need_dx=False, partial=True)
-                self.acc(ename, dE)
+            ename = f"embeddings.{ROW_TYPE}.weight"
+            # the joint BatchNorm backward inside the data-gradient GEMM of the first linear (dE, + its weight gradient)
+            fused = self.bn_lin_bwd("two", (g_a, y, enc_a.pro1, fold, sums, g_b, enc_b.pro1), f"{pt}.1", enc_a.E, None,
+                                    f"{pt}.0.weight", f"{pt}.0.bias", self.W(f"{pt}.0.weight")) \
+                if self.params[ename].requires_grad and ename not in self.grads else None
+            if fused is not None:
+                self.acc(ename, fused[1])
                 return
-            dz1 = ops.bn_bwd_apply2(g_a, g_b, y, enc_a["pro1"], enc_b["pro1"], fold, sums, fold.count, dbg[0], dbg[1])
-            self.acc(f"{pt}.1.bias", dbg[0])
-            self.acc(f"{pt}.1.weight", dbg[1])
+            dz1 = ops.bn_bwd_apply2(g_a, g_b, y, enc_a.pro1, enc_b.pro1, fold,
+                                    *self.bn_param_grads(fold, f"{pt}.1", sums, y.shape[1]))
         self.enc_bwd_first(enc_a, dz1)
 
     def enc_bwd_first(self, enc, dz1):
         pt = "patient_transform"
         ename = f"embeddings.{ROW_TYPE}.weight"
-        need_dE = self.params[ename].requires_grad
         # the second encoder pass (dropout: encode_nodes runs twice, F7) adds its dE inside the GEMM
-        dE = self.lin_bwd(dz1, enc["E"], None, f"{pt}.0.weight", f"{pt}.0.bias", need_dx=need_dE, partial=True,
-                          dx_into=self.grads.get(ename))
+        dE = self.lin_bwd(dz1, enc.E, None, f"{pt}.0.weight", f"{pt}.0.bias", need_dx=self.params[ename].requires_grad,
+                          partial=True, dx_into=self.grads.get(ename))
         if dE is not None and ename not in self.grads:
             self.acc(ename, dE)
 
@@ -1009,24 +1066,37 @@ class _Run:
     def conv_name(self, l, et):
         return f"convs.{l}.convs.{_mangle(et)}"
 
+    def scatter_patients(self, rels, xP, scale):
+        """The patient rows xP scattered onto the vocab rows of every relation, scaled by the mean's 1 / degree of the
+        columns ("colscale") or of the rows ("rowscale") -> (one [n_cols, D] view per relation, the ONE buffer they share:
+        a sharded run sums it over the ranks with one all-reduce)."""
+        buf = torch.empty(sum(r.n_cols for r in rels), self.D, device=self.dev)
+        parts = list(buf.split([r.n_cols for r in rels]))
+        ops.scatter_rows([ops.Rel(r.rowptr, r.col, r.n_cols, out=o, simple=r.simple, mask_t=r.mask_t,
+                                  **{scale: r.inv_col if scale == "colscale" else r.inv_row}) for r, o in zip(rels, parts)],
+                         self.plan.n_rows, self.D, xP)
+        return parts, buf
+
     def layer_fwd(self, l, x):
         plan, D, P = self.plan, self.D, self.plan.n_rows
         xP = x.get(ROW_TYPE)
         rin = [r for r in plan.rels_into_patient() if r.other in x and xP is not None]
         rout = [r for r in plan.rels_from_patient() if r.other in x and xP is not None]
-        y: Dict[str, torch.Tensor] = {}
-        rec = dict(x=x, rin=rin, rout=rout)
+        rec = _LayerRec(l, x, rin, rout)
+        y, folds, pros, tables = rec.y, rec.folds, rec.pros, rec.tables
         last = l == self.m.num_layers - 1
         p = 0.0 if last else self.p
-        out, folds, pros = {}, {}, {}
+        out = {}
+
+        def act_pro(t, fold=None):       # activation + dropout of type t's output, behind its BatchNorm fold
+            return Pro(fold.scale if fold else None, fold.shift if fold else None, self.m._act_code, p, self.seed,
+                       SITE_CONV + SITE_TYPES_PER_LAYER * l + plan.node_types.index(t),
+                       plan.row_offset if t == ROW_TYPE else 0, self.seed_dev)
 
         def bn_act(t):       # per-type BN -> ReLU -> Dropout (model.py:258-269)
-            ti = plan.node_types.index(t)
-            sharded = t == ROW_TYPE
-            fold = self.bn_fold(y[t], self.m.batch_norms[l][t], 1, sharded,
-                                sums=rec.get("ysums") if t == ROW_TYPE else None) if self.m.use_batch_norm else None
-            pro = Pro(fold.scale if fold else None, fold.shift if fold else None, self.m._act_code, p, self.seed,
-                      SITE_CONV + 8 * l + ti, plan.row_offset if sharded else 0, self.seed_dev)
+            fold = self.bn_fold(y[t], self.m.batch_norms[l][t], 1, t == ROW_TYPE,
+                                sums=rec.ysums if t == ROW_TYPE else None) if self.m.use_batch_norm else None
+            pro = act_pro(t, fold)
             if last and t == ROW_TYPE and self.lazy_final and self.m._act_code == _lib.MMG_ACT_RELU:
                 out[t] = _LazyAct(y[t], pro, fold)               # consumed through the heads' GEMM prologues
             else:
@@ -1034,69 +1104,41 @@ class _Run:
             folds[t], pros[t] = fold, pro
 
         names = [self.conv_name(l, r.edge_type) for r in rin]
-        tables = []
 
         def vocab_tables():  # T_v = x_v W_l^T: the transformed vocab rows the patient-side gather reads (ONE launch)
-            if all(x[r.other].shape[0] <= ops.SMALL_MAX_ROWS for r in rin):
-                tables.extend(ops.small_fwd_group([ops.SmallFwd(x[r.other], self.W(nme + ".lin_l.weight"))
-                                                   for r, nme in zip(rin, names)]))
-                return
-            for r, nme in zip(rin, names):
-                tables.append(ops.linear_fwd(x[r.other], self.W(nme + ".lin_l.weight")))
-
-        scat = {}
+            tables.extend(ops.small_fwd_group([ops.SmallFwd(x[r.other], self.W(nme + ".lin_l.weight"))
+                                               for r, nme in zip(rin, names)]))
 
         def vocab_scatter():
             # ---- dst = vocab type v: y_v = mean_scatter(x_P) W_l^T + b + x_v W_r^T   (summed over relations into v)
             if not rout:
                 return
-            aggs, rels, off = [], [], 0
-            buf = torch.empty(sum(r.n_cols for r in rout), D, device=self.dev)   # one buffer = one all-reduce
-            for r in rout:
-                agg = buf[off:off + r.n_cols]
-                off += r.n_cols
-                rels.append(ops.Rel(r.rowptr, r.col, r.n_cols, colscale=r.inv_col, out=agg, simple=r.simple, mask_t=r.mask_t))
-                aggs.append(agg)
-            ops.scatter_rows(rels, P, D, xP)
+            rec.aggs, buf = self.scatter_patients(rout, xP, "colscale")
             self.allreduce(buf)                          # partial sums over patient shards
-            scat["aggs"] = aggs
 
         def vocab_small():
             if rout:
-                others = [r.other for r in rout]
-                if len(set(others)) == len(others) and all(r.n_cols <= ops.SMALL_MAX_ROWS for r in rout):
-                    # every vocab type has ONE incoming relation: y_v = agg W_l^T + b + x_v W_r^T is a two-term problem,
-                    # all of them in one launch
-                    outs = ops.small_fwd_group([
-                        ops.SmallFwd(agg, self.W(self.conv_name(l, r.edge_type) + ".lin_l.weight"),
-                                     bias=self.W(self.conv_name(l, r.edge_type) + ".lin_l.bias"), x2=x[r.other],
-                                     W2=self.W(self.conv_name(l, r.edge_type) + ".lin_r.weight"))
-                        for r, agg in zip(rout, scat["aggs"])])
-                    for r, o in zip(rout, outs):
-                        y[r.other] = o
-                else:
-                    for r, agg in zip(rout, scat["aggs"]):
-                        nme = self.conv_name(l, r.edge_type)
-                        first = r.other not in y
-                        y[r.other] = ops.linear_fwd(agg, self.W(nme + ".lin_l.weight"), self.W(nme + ".lin_l.bias"),
-                                                    out=None if first else y[r.other], accumulate=not first)
-                        ops.linear_fwd(x[r.other], self.W(nme + ".lin_r.weight"), out=y[r.other], accumulate=True)
-                rec["aggs"] = scat["aggs"]
+                # y_v = agg W_l^T + b + x_v W_r^T, a two-term problem per relation: all of them in one launch where every
+                # vocab type has ONE incoming relation (several into one type add up: one after the other)
+                probs = []
+                for r, agg in zip(rout, rec.aggs):
+                    nme = self.conv_name(l, r.edge_type)
+                    first = r.other not in y
+                    if first:
+                        y[r.other] = torch.empty(r.n_cols, D, device=self.dev)
+                    probs.append(ops.SmallFwd(agg, self.W(nme + ".lin_l.weight"), out=y[r.other],
+                                              bias=self.W(nme + ".lin_l.bias"), x2=x[r.other],
+                                              W2=self.W(nme + ".lin_r.weight"), accumulate=not first))
+                ops.small_fwd_group(probs, grouped=len({r.other for r in rout}) == len(rout))
             vts = [t for t in plan.node_types if t != ROW_TYPE and t in y]
             if vts and all(y[t].shape[0] <= ops.SMALL_MAX_ROWS for t in vts) and \
                     not (self.T and self.m.use_batch_norm and any(y[t].shape[0] <= 1 for t in vts)):
                 # BatchNorm statistics + fold + running update + activation + dropout of every vocab type: ONE launch
-                items = []
-                for t in vts:
-                    ti = plan.node_types.index(t)
-                    mod = self.m.batch_norms[l][t] if self.m.use_batch_norm else None
-                    items.append((y[t], mod, Pro(None, None, self.m._act_code, p, self.seed, SITE_CONV + 8 * l + ti, 0,
-                                                 self.seed_dev)))
+                items = [(y[t], self.m.batch_norms[l][t] if self.m.use_batch_norm else None, act_pro(t)) for t in vts]
                 for t, (o, fold), it in zip(vts, ops.small_bn_act_group(items, self.T), items):
                     out[t], folds[t], pros[t] = o, fold, it[2]
                     if self.T and it[1] is not None:
-                        ent = self._nbt.setdefault(id(it[1]), [it[1].num_batches_tracked, 0])
-                        ent[1] += 1
+                        self.count_bn(it[1], 1)
             else:
                 for t in vts:
                     bn_act(t)
@@ -1122,17 +1164,12 @@ class _Run:
             wait_tables()
             rels = [ops.Rel(r.rowptr, r.col, r.n_cols, rowscale=r.inv_row, table=Tv, simple=r.simple, mask_r=r.mask_r)
                     for r, Tv in zip(rin, tables)]
-            ysums = None
-            spec = self.bn_spec(self.m.batch_norms[l][ROW_TYPE], 1, P, True) if self.m.use_batch_norm else None
-            if spec is not None:                     # BatchNorm statistics AND fold of y_P from the gather's launches
-                _, _, ysums = ops.gather_rows(rels, P, D, yP, accumulate=True, bn=spec)
-            elif self.T and self.m.use_batch_norm and P > 0:       # BatchNorm statistics of y_P from the gather epilogue
-                _, ysums = ops.gather_rows(rels, P, D, yP, accumulate=True, with_stats=True)
-            else:
-                ops.gather_rows(rels, P, D, yP, accumulate=True)
+            # the BatchNorm statistics of y_P (on a single GPU: and its fold) from the gather's launches
+            _, rec.ysums = self.with_bn_stats(lambda **epi: ops.gather_rows(rels, P, D, yP, accumulate=True, **epi),
+                                              self.m.batch_norms[l][ROW_TYPE] if self.m.use_batch_norm else None, 1, P,
+                                              stats=P > 0)
             y[ROW_TYPE] = yP
-            rec["Wsum"] = Wsum
-            rec["ysums"] = ysums
+            rec.Wsum = Wsum
 
         def patient_bn():
             if rin:
@@ -1169,7 +1206,6 @@ class _Run:
             patient_bn()
             vocab_scatter()
             vocab_small()
-        rec.update(y=y, folds=folds, pros=pros, l=l, tables=tables)
         return out, rec
 
     def layers_bwd(self, recs, g):
@@ -1177,20 +1213,19 @@ class _Run:
             g = self.layer_bwd(recs[i], g, below=recs[i - 1] if i > 0 else None)
         return g
 
-    def layer_bwd(self, rec, g_out, below=None):
+    def layer_bwd(self, rec: _LayerRec, g_out, below: Optional[_LayerRec] = None):
         """g_out[BN_SUMS] (optional): the LOCAL statistics of this layer's patient BatchNorm backward, summed by the kernel
         that produced g_out[ROW_TYPE]; below: the record of the layer underneath, whose patient BatchNorm consumes the
         patient gradient this layer hands down (its statistics then ride on the last kernel that writes that gradient)."""
-        plan, D, P, l = self.plan, self.D, self.plan.n_rows, rec["l"]
-        x, y = rec["x"], rec["y"]
-        dy = {}
+        plan, D, P, l = self.plan, self.D, self.plan.n_rows, rec.l
+        x, y, dy = rec.x, rec.y, {}
+        bn_prefix = {t: f"batch_norms.{l}.{t}" if self.m.use_batch_norm else None for t in y}
 
         def bn_bwd_t(t, sums=None):
             gt = g_out.get(t)
             if gt is None or t not in y:
                 return
-            bn_prefix = f"batch_norms.{l}.{t}" if self.m.use_batch_norm else None
-            dy[t] = self.bn_bwd(gt.contiguous(), y[t], rec["pros"][t], rec["folds"][t], bn_prefix,
+            dy[t] = self.bn_bwd(gt.contiguous(), y[t], rec.pros[t], rec.folds[t], bn_prefix[t],
                                 sharded=(t == ROW_TYPE), sums=sums)
 
         def patient_sums():      # statistics of the patient rows' BN backward (sharded: a collective)
@@ -1198,26 +1233,26 @@ class _Run:
             if gt is None or ROW_TYPE not in y:
                 return None
             pre = g_out.get(BN_SUMS)
-            if pre is not None and rec["folds"][ROW_TYPE] is not None:
+            if pre is not None and rec.folds[ROW_TYPE] is not None:
                 if self.comm is not None:
                     self.allreduce(pre)
                 return pre
-            return self.bn_bwd_sums(gt.contiguous(), y[ROW_TYPE], rec["pros"][ROW_TYPE], rec["folds"][ROW_TYPE], True)
+            return self.bn_bwd_sums(gt.contiguous(), y[ROW_TYPE], rec.pros[ROW_TYPE], rec.folds[ROW_TYPE], True)
 
         g_in: Dict[str, Optional[torch.Tensor]] = {t: None for t in x}
 
-        def add_dgrad(t, dy_, W_):
-            """g_in[t] += dy_ . W_  (W_ is the forward weight [N,K], read in place; accumulated by the GEMM itself)."""
-            if g_in[t] is None:
-                g_in[t] = ops.linear_fwd(dy_, W_, w_kn=True)
-            else:
-                ops.linear_fwd(dy_, W_, w_kn=True, out=g_in[t], accumulate=True)
+        def dgrad(t, dy_, W_) -> ops.SmallFwd:
+            """The problem  g_in[t] += dy_ . W_  (W_ is the forward weight [N,K], read in place; accumulated by the GEMM)."""
+            acc_ = g_in[t] is not None
+            if not acc_:
+                g_in[t] = torch.empty(dy_.shape[0], W_.shape[1], device=self.dev)
+            return ops.SmallFwd(dy_, W_, out=g_in[t], accumulate=acc_, w_kn=True)
 
         def vocab_1():
             """BN backward of the vocab types and everything that only depends on it (vocab destinations)."""
             vts = [t for t in y if t != ROW_TYPE and g_out.get(t) is not None]
             if vts and all(y[t].shape[0] <= ops.SMALL_MAX_ROWS for t in vts):
-                items = [(g_out[t].contiguous(), y[t], rec["pros"][t], rec["folds"][t]) for t in vts]
+                items = [(g_out[t].contiguous(), y[t], rec.pros[t], rec.folds[t]) for t in vts]
                 for t, (dyt, dbeta, dgamma) in zip(vts, ops.small_bn_bwd_group(items)):
                     dy[t] = dyt
                     if dbeta is not None:
@@ -1228,117 +1263,71 @@ class _Run:
                     if t != ROW_TYPE:
                         bn_bwd_t(t)
             rels = []
-            live = [(r, agg) for r, agg in zip(rec["rout"], rec.get("aggs", [])) if dy.get(r.other) is not None]
-            if live and all(r.n_cols <= ops.SMALL_MAX_ROWS for r, _ in live) and \
-                    all(g_in[r.other] is None for r, _ in live) and len({r.other for r, _ in live}) == len(live):
-                # grouped: the weight gradients of every relation in one launch, their data gradients in another
-                wg = []
-                for r, agg in live:
-                    dyv = dy[r.other]
-                    wg += [ops.SmallWgrad(dyv, agg, with_bias=True), ops.SmallWgrad(dyv, x[r.other])]
-                res = ops.small_wgrad_group(wg)
-                fw = []
-                for r, agg in live:
-                    nme = self.conv_name(l, r.edge_type)
-                    dyv = dy[r.other]
-                    fw += [ops.SmallFwd(dyv, self.W(nme + ".lin_r.weight"), w_kn=True),      # -> g_in[other]
-                           ops.SmallFwd(dyv, self.W(nme + ".lin_l.weight"), w_kn=True)]      # -> d agg
-                outs = ops.small_fwd_group(fw)
-                for i, (r, agg) in enumerate(live):
-                    nme = self.conv_name(l, r.edge_type)
-                    self.acc(nme + ".lin_l.weight", res[2 * i][0])
-                    self.acc(nme + ".lin_l.bias", res[2 * i][1])
-                    self.acc(nme + ".lin_r.weight", res[2 * i + 1][0])
-                    g_in[r.other] = outs[2 * i]
-                    rels.append(ops.Rel(r.rowptr, r.col, r.n_cols, colscale=r.inv_col, table=outs[2 * i + 1],
-                                        simple=r.simple, mask_r=r.mask_r))
-                return rels
+            live = [(r, agg) for r, agg in zip(rec.rout, rec.aggs or []) if dy.get(r.other) is not None]
+            # the weight gradients of every relation in one launch, their data gradients in another -- where no vocab type
+            # has a gradient yet and each has ONE relation; else each problem on its own, in order
+            grouped = all(g_in[r.other] is None for r, _ in live) and len({r.other for r, _ in live}) == len(live)
+            wg, fw = [], []
             for r, agg in live:
-                dyv = dy[r.other]
+                nme, dyv = self.conv_name(l, r.edge_type), dy[r.other]
+                wg += [ops.SmallWgrad(dyv, agg, with_bias=True), ops.SmallWgrad(dyv, x[r.other])]
+                fw += [dgrad(r.other, dyv, self.W(nme + ".lin_r.weight")),                   # -> g_in[other]
+                       ops.SmallFwd(dyv, self.W(nme + ".lin_l.weight"), w_kn=True)]          # -> d agg
+            res = ops.small_wgrad_group(wg, grouped)
+            outs = ops.small_fwd_group(fw, grouped)
+            for i, (r, agg) in enumerate(live):
                 nme = self.conv_name(l, r.edge_type)
-                dWl, dbl = ops.linear_wgrad(dyv, agg, with_bias=True)     # the bias gradient rides in the same pass
-                self.acc(nme + ".lin_l.weight", dWl)
-                self.acc(nme + ".lin_l.bias", dbl)
-                self.acc(nme + ".lin_r.weight", ops.linear_wgrad(dyv, x[r.other]))
-                add_dgrad(r.other, dyv, self.W(nme + ".lin_r.weight"))
-                dagg = ops.linear_fwd(dyv, self.W(nme + ".lin_l.weight"), w_kn=True)
-                rels.append(ops.Rel(r.rowptr, r.col, r.n_cols, colscale=r.inv_col, table=dagg, simple=r.simple, mask_r=r.mask_r))
+                self.acc(nme + ".lin_l.weight", res[2 * i][0])
+                self.acc(nme + ".lin_l.bias", res[2 * i][1])
+                self.acc(nme + ".lin_r.weight", res[2 * i + 1][0])
+                rels.append(ops.Rel(r.rowptr, r.col, r.n_cols, colscale=r.inv_col, table=outs[2 * i + 1],
+                                    simple=r.simple, mask_r=r.mask_r))
             return rels
 
         def patient_1(sums=None, reduce=True):
             """BN backward of the patient rows, their weight / data gradients, scatter of dy_P onto the vocab rows."""
-            gt, fused, fw = g_out.get(ROW_TYPE), None, None
-            if gt is not None and ROW_TYPE in y and rec["rin"] and g_in[ROW_TYPE] is None:
-                # BatchNorm backward inside the data-gradient GEMM of the self-loop weights (sum of the three lin_r), with
-                # the weight gradient of that sum in the same launch (dy_P is still written: the scatter below reads it)
-                xP, Wsum = x[ROW_TYPE], rec["Wsum"]
-                if self.fused_wgrad and isinstance(xP, torch.Tensor) and xP.is_contiguous() and \
-                        ops.linear_bnbwd_wgrad_supported(xP.shape[0], Wsum.shape[1], Wsum.shape[0]):
-                    fw = ops.FusedWgrad(xP, None, with_bias=True, defer=self.wgrad_jobs, keep_dz=True)
-                fused = self.bn_lin_bwd(gt.contiguous(), y[ROW_TYPE], rec["pros"][ROW_TYPE], rec["folds"][ROW_TYPE],
-                                        f"batch_norms.{l}.{ROW_TYPE}" if self.m.use_batch_norm else None, True, sums,
-                                        Wsum, wgrad=fw)
+            gt, fused = g_out.get(ROW_TYPE), None
+            # the self-loop weights (sum of the lin_r) and the lin_l biases of the relations into the patient rows share x_P
+            wnames = tuple(self.conv_name(l, r.edge_type) + ".lin_r.weight" for r in rec.rin)
+            bnames = tuple(self.conv_name(l, r.edge_type) + ".lin_l.bias" for r in rec.rin)
+            if gt is not None and ROW_TYPE in y and rec.rin and g_in[ROW_TYPE] is None:
+                # BatchNorm backward inside the data-gradient GEMM of the self-loop weights, with the weight gradient of
+                # that sum in the same launch (dy_P is still written: the scatter below reads it)
+                fused = self.bn_lin_bwd("plain", (gt.contiguous(), y[ROW_TYPE], rec.pros[ROW_TYPE], rec.folds[ROW_TYPE],
+                                                  sums, True), bn_prefix[ROW_TYPE], x[ROW_TYPE], None, wnames, bnames,
+                                        rec.Wsum, keep_dz=True)
             if fused is not None:
-                dy[ROW_TYPE], g_in[ROW_TYPE] = fused
+                dyP, g_in[ROW_TYPE] = fused
             else:
                 bn_bwd_t(ROW_TYPE, sums)
-            dyP = dy.get(ROW_TYPE)
-            if dyP is None or not rec["rin"]:
-                return None
-            xP = x[ROW_TYPE]
-            if fused is not None and fw is not None:
-                dWsum, dbsum = fw.dW, fw.db
-            else:
-                dWsum, dbsum = ops.linear_wgrad(dyP, xP, with_bias=True, defer=self.wgrad_jobs)
-            if fused is None:
-                add_dgrad(ROW_TYPE, dyP, rec["Wsum"])
-            rels, dTs, off = [], [], 0
-            buf = torch.empty(sum(r.n_cols for r in rec["rin"]), D, device=self.dev)
-            for r in rec["rin"]:
-                dT = buf[off:off + r.n_cols]
-                off += r.n_cols
-                rels.append(ops.Rel(r.rowptr, r.col, r.n_cols, rowscale=r.inv_row, out=dT, simple=r.simple, mask_t=r.mask_t))
-                dTs.append(dT)
-            ops.scatter_rows(rels, P, D, dyP)
+                dyP = dy.get(ROW_TYPE)
+                if dyP is None or not rec.rin:
+                    return None
+                self.lin_bwd(dyP, x[ROW_TYPE], None, wnames, bnames, need_dx=False, partial=True)
+                ops.small_fwd_group([dgrad(ROW_TYPE, dyP, rec.Wsum)], grouped=False)
+            res = _PatientGrads(*self.scatter_patients(rec.rin, dyP, "rowscale"))
             if reduce:
-                self.allreduce(buf)
-            return dTs, dWsum, dbsum, buf
+                self.allreduce(res.buf)
+            return res
 
         def vocab_2(res):
             """Per-relation work behind the scatter: gradients of the vocab-table transforms T_v = x_v W_l^T."""
             if res is None:
                 return
-            dTs, dWsum, dbsum, _ = res
-            rin_ = rec["rin"]
-            if all(r.n_cols <= ops.SMALL_MAX_ROWS for r in rin_) and len({r.other for r in rin_}) == len(rin_):
-                # grouped: gradients of the vocab-table transforms T_v = x_v W_l^T, one launch each for dW and dX
-                wres = ops.small_wgrad_group([ops.SmallWgrad(dT, x[r.other]) for r, dT in zip(rin_, dTs)])
-                fw = []
-                for r, dT in zip(rin_, dTs):
-                    nme = self.conv_name(l, r.edge_type)
-                    fw.append(ops.SmallFwd(dT, self.W(nme + ".lin_l.weight"), out=g_in[r.other],
-                                           accumulate=g_in[r.other] is not None, w_kn=True))
-                outs = ops.small_fwd_group(fw)
-                for (r, dT), (dW, _), o in zip(zip(rin_, dTs), wres, outs):
-                    nme = self.conv_name(l, r.edge_type)
-                    self.acc(nme + ".lin_r.weight", dWsum, partial=True)
-                    self.acc(nme + ".lin_l.bias", dbsum, partial=True)
-                    self.acc(nme + ".lin_l.weight", dW)
-                    g_in[r.other] = o
-                return
-            for r, dT in zip(rin_, dTs):
-                nme = self.conv_name(l, r.edge_type)
-                self.acc(nme + ".lin_r.weight", dWsum, partial=True)
-                self.acc(nme + ".lin_l.bias", dbsum, partial=True)
-                self.acc(nme + ".lin_l.weight", ops.linear_wgrad(dT, x[r.other]))
-                add_dgrad(r.other, dT, self.W(nme + ".lin_l.weight"))
+            # one launch each for dW and dX where every vocab type has ONE relation into the patient rows
+            grouped = len({r.other for r in rec.rin}) == len(rec.rin)
+            wres = ops.small_wgrad_group([ops.SmallWgrad(dT, x[r.other]) for r, dT in zip(rec.rin, res.dTs)], grouped)
+            ops.small_fwd_group([dgrad(r.other, dT, self.W(self.conv_name(l, r.edge_type) + ".lin_l.weight"))
+                                 for r, dT in zip(rec.rin, res.dTs)], grouped)
+            for r, (dW, _) in zip(rec.rin, wres):
+                self.acc(self.conv_name(l, r.edge_type) + ".lin_l.weight", dW)
 
         def patient_2(rels):
             if rels:
                 nb = None
-                if below is not None and ROW_TYPE in below["y"] and below["folds"].get(ROW_TYPE) is not None and \
+                if below is not None and ROW_TYPE in below.y and below.folds.get(ROW_TYPE) is not None and \
                         "conv" in self.next_bn_sites:
-                    nb = ops.NextBN(below["y"][ROW_TYPE], below["pros"][ROW_TYPE], below["folds"][ROW_TYPE])
+                    nb = ops.NextBN(below.y[ROW_TYPE], below.pros[ROW_TYPE], below.folds[ROW_TYPE])
                 acc_ = g_in[ROW_TYPE] is not None
                 if not acc_:
                     g_in[ROW_TYPE] = torch.empty(P, D, device=self.dev)
@@ -1373,7 +1362,7 @@ class _Run:
             res = patient_1(sums, reduce=False)
             main.wait_stream(side)
             if res is not None:
-                self.allreduce(res[3])                   # collective
+                self.allreduce(res.buf)                  # collective
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 vocab_2(res)
@@ -1414,7 +1403,8 @@ class _Run:
         plan = self.plan
         if LAB_EDGE not in plan.rels:
             raise KeyError(f"graph has no {LAB_EDGE} relation (model.py:297)")
-        pi, li, perm, ids, (sel_low, sel_high, counts, n_low, n_high, low_rows, pi_low, deg_low, _) = self.pairs
+        ps, ls = self.pairs, self.pairs.lists
+        pi, sel_low, sel_high, counts = ps.pi, ls.sel_low, ls.sel_high, ls.counts
         thr = int(self.m.degree_threshold)
         if self.lists_ready is not None:             # drawn / selected on the side stream beside the encoder pass
             torch.cuda.current_stream().wait_event(self.lists_ready)
@@ -1423,26 +1413,26 @@ class _Run:
             sel_low, sel_high, counts = self.forward_select      # (subsets of the static lists: n_low / n_high still bound them)
         else:
             pred = torch.empty(pi.numel(), device=self.dev)      # every pair belongs to exactly one head list
-        rec = dict(init=init, fin=fin)
+        rec: Dict[str, _HeadRec] = {}
         halves = self.head_weight_halves()
         for which, src, want_low in (("edge_predictor", fin, False), ("tabular_mlp", init, True)):
             # tabular_mlp: patient rows, ids and gate of the compacted low-degree patients (gate: all of them are low)
             if want_low and self._init_compact:
                 xP = src[ROW_TYPE]                                   # the first pass was evaluated on these rows only
             else:
-                xP = src[ROW_TYPE].index_select(0, low_rows) if want_low else src[ROW_TYPE]
+                xP = src[ROW_TYPE].index_select(0, ls.low_rows) if want_low else src[ROW_TYPE]
             head, w1a, w1b = self.head_tensors(which, xP, src["lab"], *halves[which])
-            sel, n_sel, nb = (sel_low, counts[0:1], n_low) if want_low else (sel_high, counts[1:2], n_high)
+            sel, n_sel, nb = (sel_low, counts[0:1], ls.n_low) if want_low else (sel_high, counts[1:2], ls.n_high)
             # training: the forward leaves the first layer's sign bits and the second layer's activations of the pairs it
             # visits (136 B per pair) -- the backward then recomputes neither the dropout masks nor the 64 x 32 product
             # (indexed by list position -- dense -- when the backward is known to run over the same lists)
             by_pos = self.static_select is self.forward_select
             save = ops.pair_saved_alloc(nb if by_pos else pi.numel(), self.dev) + (by_pos,) \
                 if self.T and self.save_pair_state and self.forward_select is not None else None
-            ops.pair_head_fwd(head, pi_low if want_low else pi, li, deg_low if want_low else plan.lab_deg, thr, want_low,
-                              self.p, self.seed, ids, pred, self.seed_dev,
-                              sel=sel, n_sel=n_sel, n_bound=nb, io_perm=perm, save=save)   # written in the caller's pair order
-            rec[which] = (head, w1a, w1b, xP, save)
+            ops.pair_head_fwd(head, ls.pi_low if want_low else pi, ps.li, ls.deg_low if want_low else plan.lab_deg, thr,
+                              want_low, self.p, self.seed, ps.ids, pred, self.seed_dev,
+                              sel=sel, n_sel=n_sel, n_bound=nb, io_perm=ps.perm, save=save)   # written in the caller's pair order
+            rec[which] = _HeadRec(src, head, w1a, w1b, xP, save)
         return pred, rec
 
     def heads_dense(self, init, fin, rows):
@@ -1452,13 +1442,10 @@ class _Run:
         if LAB_EDGE not in plan.rels:
             raise KeyError(f"graph has no {LAB_EDGE} relation (model.py:297)")
         thr = int(self.m.degree_threshold)
-        low = plan.lab_deg < thr
-        low_rows = torch.nonzero(low).squeeze(1)
-        low_pos = torch.full((plan.n_rows,), -1, dtype=torch.int32, device=self.dev)
-        low_pos[low_rows] = torch.arange(low_rows.numel(), dtype=torch.int32, device=self.dev)
+        low_rows, low_pos = _low_tables(plan.lab_deg, thr, plan.n_rows)
         out = torch.empty(rows.numel(), plan.num_nodes["lab"], device=self.dev)
         pos = torch.arange(rows.numel(), dtype=torch.int32, device=self.dev)
-        row_low = low[rows]
+        row_low = low_pos[rows] >= 0
         halves = self.head_weight_halves()
         for which, src, want_low in (("edge_predictor", fin, False), ("tabular_mlp", init, True)):
             sel = row_low if want_low else ~row_low
@@ -1471,9 +1458,10 @@ class _Run:
             ops.pair_head_dense_fwd(head, r, o, out)
         return out
 
-    def heads_bwd(self, rec, dpred):
+    def heads_bwd(self, rec: Dict[str, _HeadRec], dpred):
         plan, D = self.plan, self.D
-        pi, li, perm, ids, (_, _, _, n_low, n_high, low_rows, pi_low, deg_low, _) = self.pairs
+        ps, ls = self.pairs, self.pairs.lists
+        pi, perm = ps.pi, ps.perm
         thr = int(self.m.degree_threshold)
         dps = dpred.contiguous()                 # caller's pair order: the kernels read it through perm
         n_lab = plan.num_nodes["lab"]
@@ -1489,15 +1477,16 @@ class _Run:
             dsorted = torch.empty_like(dps)      # dpred in sorted pair order: the one random pass, made by the selection
             bsel_low, bsel_high, bcounts = ops.pair_select(pi, plan.lab_deg, thr, dps, io_perm=perm, dpred_sorted=dsorted)
             dsrc, dio = dsorted, None
-        order = (("edge_predictor", rec["fin"], False), ("tabular_mlp", rec["init"], True))
+        order = tuple((w, rec[w].src, want_low) for w, want_low in (("edge_predictor", False), ("tabular_mlp", True)))
+        heads = {w: rec[w].head for w, _, _ in order}
         # one zero-fill for the small gradients of BOTH heads; the two lab-side tables dB sit first and adjacent, so that
         # a sharded run sums them over the ranks with ONE all-reduce
-        smalls = {w: [rec[w][0].B, rec[w][0].W2, rec[w][0].b2, rec[w][0].W3, rec[w][0].b3] for w, _, _ in order}
+        smalls = {w: [heads[w].B, heads[w].W2, heads[w].b2, heads[w].W3, heads[w].b3] for w, _, _ in order}
         n_b = sum(smalls[w][0].numel() for w, _, _ in order)
         n_small = sum(t.numel() for w, _, _ in order for t in smalls[w])
         n_small_pad = (n_small + 63) & ~63               # (the dA tables behind them start on a 256-byte boundary)
         # ...and the per-patient tables dA of both heads behind them: ONE zero-fill for everything the kernels add into
-        flat = ops.zeros(n_small_pad + sum(rec[w][0].A.numel() for w, _, _ in order), device=self.dev)
+        flat = ops.zeros(n_small_pad + sum(heads[w].A.numel() for w, _, _ in order), device=self.dev)
         views, ob, o, oa, dA = {}, 0, n_b, n_small_pad, {}
         for w, _, _ in order:
             tB = smalls[w][0]
@@ -1507,17 +1496,18 @@ class _Run:
                 v.append(flat[o:o + t.numel()].view(t.shape))
                 o += t.numel()
             views[w] = v
-            tA = rec[w][0].A
+            tA = heads[w].A
             dA[w] = flat[oa:oa + tA.numel()].view(tA.shape)
             oa += tA.numel()
         gs, join = {}, []
         for which, src, want_low in order:
-            head, w1a, w1b, xP, save = rec[which]
+            hr = rec[which]
+            xP, w1a = hr.xP, hr.w1a
             g = ops.Head(dA[which], *views[which])
-            sel, n_sel, nb = (bsel_low, bcounts[0:1], n_low) if want_low else (bsel_high, bcounts[1:2], n_high)
-            ops.pair_head_bwd(head, g, pi_low if want_low else pi, li, deg_low if want_low else plan.lab_deg, thr,
-                              want_low, n_lab, self.p, self.seed, ids, dsrc,
-                              self.seed_dev, sel=sel, n_sel=n_sel, n_bound=nb, io_perm=dio, saved=save)
+            sel, n_sel, nb = (bsel_low, bcounts[0:1], ls.n_low) if want_low else (bsel_high, bcounts[1:2], ls.n_high)
+            ops.pair_head_bwd(hr.head, g, ls.pi_low if want_low else pi, ps.li, ls.deg_low if want_low else plan.lab_deg, thr,
+                              want_low, n_lab, self.p, self.seed, ps.ids, dsrc,
+                              self.seed_dev, sel=sel, n_sel=n_sel, n_bound=nb, io_perm=dio, saved=hr.save)
             gs[which] = g
             self.acc(f"{which}.mlp.3.weight", g.W2, partial=True)
             self.acc(f"{which}.mlp.3.bias", g.b2, partial=True)
@@ -1539,8 +1529,8 @@ class _Run:
         ops.vec_sums(join)                       # [dW1a | dW1b] of both heads: one launch
         self.allreduce(flat[:n_b])               # lab-side partials dB of both heads from the sharded pairs
         for which, src, want_low in order:
-            head, w1a, w1b, xP, _ = rec[which]
-            g = gs[which]
+            hr, g = rec[which], gs[which]
+            xP, w1a, w1b, low_rows = hr.xP, hr.w1a, hr.w1b, ls.low_rows
             glab = ops.linear_fwd(g.B, w1b, w_kn=True)
             if want_low:                         # gradient rows of the low-degree patients only: (row ids, rows)
                 if xP.shape[0]:

@@ -1104,11 +1104,17 @@ class SmallFwd:
     w_kn: bool = False
 
 
-def small_fwd_group(probs: Sequence[SmallFwd]):
-    """Runs the problems (same N and K) in ceil(len / MMG_SMALL_MAX) launches; allocates missing outputs; returns the
-    outputs."""
+def small_fwd_group(probs: Sequence[SmallFwd], grouped: bool = True):
+    """Runs the problems (same N and K) in ceil(len / MMG_SMALL_MAX) launches; allocates missing outputs; returns them.
+    grouped False, or a problem with more than SMALL_MAX_ROWS rows: each runs through linear_fwd instead, in list order."""
     if not probs:
         return []
+    if not grouped or any(p.x.shape[0] > SMALL_MAX_ROWS for p in probs):
+        for p in probs:
+            p.out = linear_fwd(p.x, p.W, p.bias, out=p.out, accumulate=p.accumulate, w_kn=p.w_kn)
+            if p.x2 is not None:
+                linear_fwd(p.x2, p.W2, out=p.out, accumulate=True, w_kn=p.w_kn)
+        return [p.out for p in probs]
     K = probs[0].x.shape[1]
     N = probs[0].W.shape[1] if probs[0].w_kn else probs[0].W.shape[0]
     outs = []
@@ -1148,11 +1154,15 @@ class SmallWgrad:
     accumulate: bool = False
 
 
-def small_wgrad_group(probs: Sequence[SmallWgrad]):
-    """Runs the problems (same N and K) in ceil(len / MMG_SMALL_MAX) launches; allocates missing outputs; returns
-    [(dW, dbias)]."""
+def small_wgrad_group(probs: Sequence[SmallWgrad], grouped: bool = True):
+    """Runs the problems (same N and K) in ceil(len / MMG_SMALL_MAX) launches; allocates missing outputs; returns [(dW,
+    dbias)].  grouped False, or a problem with more than SMALL_MAX_ROWS rows: each runs through linear_wgrad instead."""
     if not probs:
         return []
+    if not grouped or any(p.dy.shape[0] > SMALL_MAX_ROWS for p in probs):
+        res = [linear_wgrad(p.dy, p.x, out=p.dW, accumulate=p.accumulate, with_bias=p.with_bias, bias_out=p.dbias)
+               for p in probs]
+        return [r if p.with_bias else (r, None) for p, r in zip(probs, res)]
     N, K = probs[0].dy.shape[1], probs[0].x.shape[1]
     res = []
     for p in probs:

@@ -796,10 +796,7 @@ class PiecewiseGraphedTrainStep:
             if self.mask_fraction is not None:       # this step's supervision subset, its size and its pair lists
                 self._draw_and_select()
             run = self._Run(model, self.plan)
-            run.pairs = model._pairs(self.pi, self.li, self.plan.n_rows,
-                                     getattr(self.comm, "pair_ids", None) if self.comm else None,
-                                     self.plan.lab_deg, int(model.degree_threshold))
-            run.n_pairs = self.pi.numel()
+            run.set_pairs(self.pi, self.li, getattr(self.comm, "pair_ids", None) if self.comm else None)
             run.need_grad = True
             run.static_select = self._sel
             run.lists_ready = self._sel_ready
@@ -847,8 +844,8 @@ class PiecewiseGraphedTrainStep:
         pairs = model._pairs(self.pi, self.li, self.plan.n_rows,
                              getattr(self.comm, "pair_ids", None) if self.comm else None,
                              self.plan.lab_deg, int(model.degree_threshold))
-        self._sel = ops.pair_select(pairs[0], self.plan.lab_deg, int(model.degree_threshold), self.sup, io_perm=pairs[2],
-                                    out=self._sel)
+        self._sel = ops.pair_select(pairs.pi, self.plan.lab_deg, int(model.degree_threshold), self.sup,
+                                    io_perm=pairs.perm, out=self._sel)
 
     def set_mask(self, sup_mask, n_sup_global=None):
         """New supervision subset; 1 / n_sup (summed over the shards) and the backward's pair lists follow it on the device."""
@@ -911,9 +908,7 @@ class GraphedEval:
         ops, model = self._ops, self.model
         with torch.no_grad():
             run = self._Run(model, self.plan)
-            run.pairs = model._pairs(self.pi, self.li, self.plan.n_rows, None, self.plan.lab_deg,
-                                     int(model.degree_threshold))
-            run.n_pairs = self.pi.numel()
+            run.set_pairs(self.pi, self.li)
             run.need_grad = False
             (pred,) = run.run_forward("predict")
             self.loss, _ = ops.pair_loss(pred, self.y, None, None, 1.0 / self._n_global, self.loss_fn,
