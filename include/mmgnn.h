@@ -938,6 +938,52 @@ int mmg_grid2d(const float* Y, int64_t ld_y, const int32_t* w, int64_t n, const 
                int gy, int64_t* count, int64_t* wsum, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Exact t-SNE (src/advanced_visualizations.py create_embedding_visualizations -> sklearn.manifold.TSNE; mmgnn/embed.py
+ * tsne, csrc/tsne.hip): the O(n^2) algorithm of TSNE(method="exact") with 2 map components.  X is fp32 [n, D] with row
+ * stride ld_x >= D, D a multiple of 4 in [4, 256], 4 <= n <= MMG_TSNE_MAX_N.  A is ONE caller-owned fp32 n x n buffer
+ * with row stride ld_a >= n (the padding is never written): the squared distances, then the joint probabilities, in
+ * place.
+ *   mmg_tsne_sqdist: A[i][j] = sum_d (x_id - x_jd)^2, the difference form in fp64 from the widened fp32 inputs (never
+ *     the Gram form), columns in ascending order, rounded once to fp32.  The upper triangle is computed and mirrored: A
+ *     is exactly symmetric and A[i][i] = 0.
+ *   mmg_tsne_joint_p: sklearn's _binary_search_perplexity per row, in fp64 on the widened distances: beta = 1, at most
+ *     100 steps; p_j = exp(-beta d_ij), p_i = 0; s = sum p (1e-8 if 0); H = log s + beta (sum d_ij p_j) / s; stop when
+ *     |H - log(perplexity)| <= 1e-5, else double / halve beta while the far bound is infinite, else bisect.  The
+ *     conditional row p / s, rounded to fp32, overwrites row i.  Then in place P_ij = max((double)(C_ij + C_ji) / S,
+ *     eps) rounded to fp32, the sum C_ij + C_ji in fp32, S = max(sum_ij (C_ij + C_ji), eps) in fp64, eps = 2^-52; the
+ *     diagonal is 0 and P is exactly symmetric.  beta_out (device, fp64 [n]) = the beta of the row that was written,
+ *     steps_out (device, int32 [n]) = the number of evaluations of H (1 .. 100).  0 < perplexity < n.
+ *   mmg_tsne_step: one iteration of sklearn's _gradient_descent on _kl_divergence, all in fp64; Y, U (the update) and
+ *     G (the gains) are device fp64 [n, 2].  num_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i != j} num_ij;
+ *     Q_ij = max(num_ij / Z, eps), Pe_ij = exaggeration * (double)A_ij; grad_i = 4 sum_j (Pe_ij - Q_ij) num_ij
+ *     (y_i - y_j); with want_kl, KL = sum_{i != j} Pe_ij log(max(Pe_ij, eps) / Q_ij).  Then inc = U grad < 0;
+ *     gain = max(inc ? G + 0.2 : 0.8 G, min_gain); g = grad gain; and with update != 0: G = gain,
+ *     U = momentum U - learning_rate g, Y += U -- every product and sum of this update rounded on its own (no fused
+ *     multiply-add): bit-equal to numpy.  stats_out (device, fp64 [3]) = (KL or NaN, sum g^2, Z); grad_out (device,
+ *     fp64 [n, 2], nullable) = the gradient before the gains.  With update = 0 only stats_out and grad_out are written.
+ *     Three kernels: Z (a pass over Y alone), the gradient (one read of A; Y staged through LDS in tiles of
+ *     MMG_TSNE_TILE points), the update.
+ * Every argument is checked on the host before anything is enqueued (MMG_E_ARG; a short workspace MMG_E_WS;
+ * mmg_tsne_sqdist needs none today: its *_ws_bytes is 0 and ws may be NULL).  No call synchronises with the host,
+ * allocates, uses a memset node or a floating-point atomic; the order of every fp64 sum is fixed by n and D (a row's
+ * sums are reduced over MMG_TSNE_SEARCH_WIDTH threads): bitwise reproducible from run to run and eager against a
+ * replayed hipGraph.
+ * ------------------------------------------------------------------------------------- */
+#define MMG_TSNE_MAX_N 16384
+#define MMG_TSNE_TILE 512
+#define MMG_TSNE_SEARCH_WIDTH 256
+size_t mmg_tsne_sqdist_ws_bytes(int64_t n, int D);
+int mmg_tsne_sqdist(const float* X, int64_t n, int D, int64_t ld_x, float* A, int64_t ld_a, void* ws, size_t ws_bytes,
+                    void* stream);
+size_t mmg_tsne_joint_p_ws_bytes(int64_t n);                  /* 0 for an unsupported shape */
+int mmg_tsne_joint_p(float* A, int64_t n, int64_t ld_a, double perplexity, double* beta_out, int32_t* steps_out, void* ws,
+                     size_t ws_bytes, void* stream);
+size_t mmg_tsne_step_ws_bytes(int64_t n);                     /* 0 for an unsupported shape */
+int mmg_tsne_step(const float* A, int64_t n, int64_t ld_a, double exaggeration, double* Y, double* U, double* G,
+                  double momentum, double learning_rate, double min_gain, int want_kl, double* stats_out, double* grad_out,
+                  int update, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Device graph build (src/graph_build.py NodeIndexer :34-97, :163-173, create_patient_*_edges :476-586, the flip(0)
  * reverse relations :222; mmgnn/graph_build.py build_graph_from_events, csrc/graph.hip): node indices in first-seen
  * order and one edge per event row whose two ids are known, from device arrays of CODES (int64, one code per key: the

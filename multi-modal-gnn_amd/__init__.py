@@ -25,7 +25,7 @@ def __getattr__(name):
                 "parity_by_frequency_decile"):
         from . import analysis
         return getattr(analysis, name)
-    if name in ("embedding_maps", "lab_panels", "PCAResult"):
+    if name in ("embedding_maps", "lab_panels", "PCAResult", "embedding_tsne", "tsne", "TSNEResult"):
         from . import embed
         return getattr(embed, name)
     raise AttributeError(name)

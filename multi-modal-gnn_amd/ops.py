@@ -1677,3 +1677,56 @@ def grid2d(y: torch.Tensor, ex: torch.Tensor, ey: torch.Tensor, w: Optional[torc
     wsum = torch.empty_like(count) if w is not None else None
     _call("mmg_grid2d", py, max(ld, 2), w, n, ex, ey, gx, gy, count, wsum)          # takes no workspace: ws = NULL
     return count, wsum
+
+
+# ------------------------------------------------------------------------------------------ exact t-SNE
+TSNE_MAX_N = _lib.MMG_TSNE_MAX_N                   # csrc/tsne.hip: 4 <= n <= TSNE_MAX_N
+TSNE_TILE = _lib.MMG_TSNE_TILE                     # points of Y per LDS tile of the step kernels
+TSNE_SEARCH_WIDTH = _lib.MMG_TSNE_SEARCH_WIDTH     # threads that reduce one row of the perplexity search
+
+
+def _tsne_square(a: torch.Tensor, name: str):
+    """The fp32 device n x n buffer of the t-SNE calls (unit column stride; the rows may be padded) -> (pointer, n, ld)."""
+    pa, n, m, ld = _rows_matrix(a, name)
+    if n != m:
+        raise ValueError(f"{name}: expected a square [n, n] buffer, got [{n}, {m}]")
+    return pa, n, ld
+
+
+def tsne_sqdist(x: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """A[i, j] = sum_d (x[i, d] - x[j, d])^2 of fp32 [n, D] rows (mmg_tsne_sqdist): the difference form in fp64, rounded
+    once to fp32, exactly symmetric with a zero diagonal -> fp32 [n, n] (out: the buffer to fill, rows may be padded)."""
+    px, n, D, ld = _rows_matrix(x, "x")
+    if out is None:
+        out = torch.empty(n, n, dtype=torch.float32, device=x.device)
+    pa, na, ld_a = _tsne_square(out, "out")
+    if na != n:
+        raise ValueError(f"tsne_sqdist: out must be [{n}, {n}]")
+    _call("mmg_tsne_sqdist", px, n, D, ld, pa, ld_a)                                # takes no workspace: ws = NULL
+    return out
+
+
+def tsne_joint_p(a: torch.Tensor, perplexity: float):
+    """The squared distances a [n, n] become the joint probabilities IN PLACE (mmg_tsne_joint_p: sklearn's binary search
+    per row, then the symmetrisation) -> (beta fp64 [n], steps int32 [n])."""
+    pa, n, ld = _tsne_square(a, "a")
+    beta = torch.empty(n, dtype=torch.float64, device=a.device)
+    steps = torch.empty(n, dtype=torch.int32, device=a.device)
+    _call("mmg_tsne_joint_p", pa, n, ld, float(perplexity), beta, steps, ws=_lib.load().mmg_tsne_joint_p_ws_bytes(n))
+    return beta, steps
+
+
+def tsne_step(a: torch.Tensor, y: torch.Tensor, u: torch.Tensor, g: torch.Tensor, stats: torch.Tensor, exaggeration=1.0,
+              momentum=0.8, learning_rate=200.0, min_gain=0.01, want_kl=False, update=True,
+              grad_out: Optional[torch.Tensor] = None):
+    """One iteration of sklearn's _gradient_descent on _kl_divergence (mmg_tsne_step) over the joint probabilities a
+    [n, n]: y, u (the update) and g (the gains) are fp64 [n, 2] and change in place when `update`; stats fp64 [3]
+    receives (KL or NaN, sum of the squared gained gradient, Z); grad_out fp64 [n, 2] the gradient before the gains."""
+    pa, n, ld = _tsne_square(a, "a")
+    for name, t in (("y", y), ("u", u), ("g", g), ("grad_out", grad_out)):
+        if t is not None and tuple(t.shape) != (n, 2):
+            raise ValueError(f"tsne_step: {name} must be [{n}, 2] (the map has 2 components), got {tuple(t.shape)}")
+    if stats.numel() != 3:
+        raise ValueError("tsne_step: stats must hold 3 values")
+    _call("mmg_tsne_step", pa, n, ld, float(exaggeration), y, u, g, float(momentum), float(learning_rate), float(min_gain),
+          int(bool(want_kl)), stats, grad_out, int(bool(update)), ws=_lib.load().mmg_tsne_step_ws_bytes(n))
