@@ -229,6 +229,17 @@ size_t mmg_epi_ws_bytes(int64_t M, int N);
 int mmg_linear_fwd_supported(int mode, int64_t M, int N, int K);
 int mmg_linear_fwd(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias, float* Y, int64_t M, int N,
                    int K, int flags, const mmg_fwd_epi_t* epi, void* stream);
+/* The same layer under two dropout masks in ONE launch: Y0 = pro0(X) . W^T + b, Y1 = pro1(X) . W^T + b, where pro0 and pro1
+ * agree in scale, shift, relu, drop_p (> 0), seed, seed_ptr and row_offset and differ in the site alone (the second linear of
+ * the two encode_nodes passes of a training step, src/model.py:294,301).  X is read, folded and split once.  Both epilogues
+ * are MMG_EPI_STATS with their own col_sums and workspaces; their folds (both, or neither) are taken in one launch, fin of
+ * epi0 before fin of epi1 -- they may advance the same running statistics.  Y0, Y1, the sums and the folds are bit for bit
+ * those of two mmg_linear_fwd calls in that order.  mmg_linear_fwd_dual_supported: M > 512, N = K = 128; anything else, and
+ * prologues that differ in more than the site, are refused with MMG_E_ARG before anything is launched. */
+int mmg_linear_fwd_dual_supported(int64_t M, int N, int K);
+int mmg_linear_fwd_dual(const float* X, const mmg_prologue_t* pro0, const mmg_prologue_t* pro1, const float* W,
+                        const float* bias, float* Y0, float* Y1, int64_t M, int N, int K, const mmg_fwd_epi_t* epi0,
+                        const mmg_fwd_epi_t* epi1, void* stream);
 int mmg_gather_rows(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D, float* out, int accumulate,
                     const mmg_fwd_epi_t* epi, void* stream);
 
@@ -383,7 +394,8 @@ int mmg_linear_bnbwd(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX,
  * waits for them, disarms the hook and returns how many entries it wrote (<= cap):
  *   ms = kernel duration, tag = MMG_PROBE_* family, (M, N, K) = the launch's shape: rows / output width / inner width for
  *   the dense kernels; patient rows / D / total vocab rows of the fused relations for the aggregates; pairs / 0 / 0 for
- *   the heads;  flags: 1 = accumulate, 4 = prologue, 8 = rowscale.
+ *   the heads;  flags: 1 = accumulate, 4 = prologue, 8 = rowscale, 2048 = the dual linear forward (mmg_linear_fwd_dual: N is
+ *   reported as 2 * 128, the two outputs side by side, so that 4 (M K + N K + M N) bytes and 2 M N K FLOP price the launch).
  * The hook is the library's only process-wide mutable state (mutex-guarded); the product path never arms it. */
 #define MMG_PROBE_LINEAR_FWD 1
 #define MMG_PROBE_LINEAR_WGRAD 2

@@ -328,6 +328,9 @@ extern "C" int mmg_partial_sum_add(const double* partial, double* out, int n, in
 // partial [n_rows][2][N] -> col_sums, + the BatchNorm fold of the sums (fin != NULL)
 extern "C" int mmg_partial_sum_bn(const double* partial, double* col_sums, int N, int n_rows, const mmg_bn_fin_t* fin,
                                   void* stream);
+// the same for the two passes of mmg_linear_fwd_dual: fold A, then fold B (one launch when both fold)
+extern "C" int mmg_partial_sum_bn2(const double* pa, const double* pb, double* sums_a, double* sums_b, int N, int n_rows,
+                                   const mmg_bn_fin_t* fa, const mmg_bn_fin_t* fb, void* stream);
 // mmg_next_bn_t: validates the descriptor, fills the device view, *partial = the aligned workspace
 extern "C" int mmg_next_bn_dev(const mmg_next_bn_t* next, int64_t M, int N, const char* what, NextBnDev* d, double** partial);
 // the fused producer's partial rows -> next->sums (or +=)

@@ -176,6 +176,32 @@ __global__ __launch_bounds__(256) void k_bn_finalize(const double* __restrict__ 
               training, n_updates, momentum, eps, scale, shift, mean_out, rstd_out);
 }
 
+// Column sums of NS series of partial rows (series k: p[k][b * stride], b < nblk) in k_partial_sum's order -- a lane adds rows
+// lane, lane + 64, ... one after the other, the wave reduction follows -- with the loads of eight rows of every series issued
+// before the first add (the plain loop waited for each row in turn: a launch of 128 waves is all latency).  A row past
+// the end is read at the last row and enters as +0.0, which leaves a sum that started at +0.0 as it is, bit for bit.
+template <int NS>
+__device__ __forceinline__ void partial_rows_sum(const double* const (&p)[NS], size_t stride, int nblk, int lane, double (&s)[NS]) {
+#pragma unroll
+  for (int k = 0; k < NS; ++k) s[k] = 0;
+  for (int b0 = lane; b0 < nblk; b0 += 512) {
+    double v[NS][8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int b = b0 + 64 * u, bc = b < nblk ? b : nblk - 1;
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        const double x = p[k][(size_t)bc * stride];
+        v[k][u] = b < nblk ? x : 0.0;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+      for (int k = 0; k < NS; ++k) s[k] += v[k][u];
+  }
+}
+
 // the partial statistics rows of a producer kernel ([nblk][2][N] fp64) summed in fixed order -- one wave per column, as
 // k_partial_sum -- and folded at once (training mode)
 __global__ __launch_bounds__(256) void k_partial_sum_bn(const double* __restrict__ partial, double* __restrict__ out, int N,
@@ -183,17 +209,38 @@ __global__ __launch_bounds__(256) void k_partial_sum_bn(const double* __restrict
   const int lane = threadIdx.x & 63;
   const int i = (blockIdx.x * 256 + threadIdx.x) >> 6;
   if (i >= N) return;
-  double s1 = 0, s2 = 0;
-  for (int b = lane; b < nblk; b += 64) {
-    s1 += partial[(size_t)b * 2 * N + i];
-    s2 += partial[(size_t)b * 2 * N + N + i];
-  }
-  s1 = wave_sum_d(s1);
-  s2 = wave_sum_d(s2);
+  const double* const p[2] = {partial + i, partial + N + i};
+  double s[2];
+  partial_rows_sum<2>(p, (size_t)2 * N, nblk, lane, s);
+  const double s1 = wave_sum_d(s[0]), s2 = wave_sum_d(s[1]);
   if (lane == 0) {
     out[i] = s1; out[N + i] = s2;
     bn_fold_col(s1, s2, f.count, i, f.gamma, f.beta, f.running_mean, f.running_var, 1, f.n_updates, f.momentum, f.eps,
                 f.scale, f.shift, f.mean, f.rstd);
+  }
+}
+
+// the same for the two outputs of the dual linear forward (k_linear_fwd_x6_dual) in one launch.  One wave takes a column of
+// BOTH passes: each pass's sums in k_partial_sum_bn's order (the four running sums are independent, their loads overlap),
+// then the fold of pass A, then that of pass B -- the two folds advance the SAME running statistics, a read-modify-write
+// that has to happen in the order of the two launches it replaces, so the passes are not dealt to different workgroups.
+__global__ __launch_bounds__(256) void k_partial_sum_bn2(const double* __restrict__ pa, const double* __restrict__ pb,
+                                                         double* __restrict__ outa, double* __restrict__ outb, int N, int nblk,
+                                                         mmg_bn_fin_t fa, mmg_bn_fin_t fb) {
+  const int lane = threadIdx.x & 63;
+  const int i = (blockIdx.x * 256 + threadIdx.x) >> 6;
+  if (i >= N) return;
+  const double* const p[4] = {pa + i, pa + N + i, pb + i, pb + N + i};
+  double s[4];
+  partial_rows_sum<4>(p, (size_t)2 * N, nblk, lane, s);
+  const double a1 = wave_sum_d(s[0]), a2 = wave_sum_d(s[1]), b1 = wave_sum_d(s[2]), b2 = wave_sum_d(s[3]);
+  if (lane == 0) {
+    outa[i] = a1; outa[N + i] = a2;
+    outb[i] = b1; outb[N + i] = b2;
+    bn_fold_col(a1, a2, fa.count, i, fa.gamma, fa.beta, fa.running_mean, fa.running_var, 1, fa.n_updates, fa.momentum, fa.eps,
+                fa.scale, fa.shift, fa.mean, fa.rstd);
+    bn_fold_col(b1, b2, fb.count, i, fb.gamma, fb.beta, fb.running_mean, fb.running_var, 1, fb.n_updates, fb.momentum, fb.eps,
+                fb.scale, fb.shift, fb.mean, fb.rstd);
   }
 }
 
@@ -548,6 +595,21 @@ extern "C" int mmg_partial_sum_bn(const double* partial, double* col_sums, int N
   if (!fin) return mmg_partial_sum(partial, col_sums, 2 * N, n_rows, stream);
   MMG_CHECK_ARG(fin->count > 0 && fin->scale && fin->shift, "partial_sum_bn: bad BatchNorm fold descriptor");
   hipLaunchKernelGGL(k_partial_sum_bn, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, partial, col_sums, N, n_rows, *fin);
+  MMG_CHECK_LAUNCH("partial_sum_bn");
+  return MMG_OK;
+}
+
+// internal (common.h): two producers' partial rows, folded one after the other (A, then B) -- one launch when both fold
+extern "C" int mmg_partial_sum_bn2(const double* pa, const double* pb, double* sums_a, double* sums_b, int N, int n_rows,
+                                   const mmg_bn_fin_t* fa, const mmg_bn_fin_t* fb, void* stream) {
+  if (!fa || !fb) {
+    const int rc = mmg_partial_sum_bn(pa, sums_a, N, n_rows, fa, stream);
+    return rc ? rc : mmg_partial_sum_bn(pb, sums_b, N, n_rows, fb, stream);
+  }
+  MMG_CHECK_ARG(fa->count > 0 && fa->scale && fa->shift && fb->count > 0 && fb->scale && fb->shift,
+                "partial_sum_bn: bad BatchNorm fold descriptor");
+  hipLaunchKernelGGL(k_partial_sum_bn2, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, pa, pb, sums_a, sums_b, N, n_rows,
+                     *fa, *fb);
   MMG_CHECK_LAUNCH("partial_sum_bn");
   return MMG_OK;
 }

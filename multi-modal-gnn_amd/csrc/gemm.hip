@@ -671,6 +671,207 @@ int launch_fwd_x6(const float* X, const ProDev& pr, const float* W, const float*
              : launch_fwd_x6_v<K, WN, false, false>(X, pr, W, bias, Y, M, N, flags, st, stat_partial);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// k_linear_fwd_x6_dual: the SAME [M, 128] x [128, 128] layer under two dropout masks in one launch -- the encoder's second
+// linear of the two encode_nodes passes of a training step.  The passes share X, the BatchNorm fold, the ReLU and
+// inv_keep; only the RNG site differs, so a staged element is  v * inv_keep  where its pass keeps it and zero where not.
+// Every 16-byte element is loaded once, affine + ReLU + scaling + MMG_SPLIT3 run once, the two passes' keep fields mask
+// the three pieces (split(0) = three +0 pieces: the bits k_linear_fwd_x6 stages for a dropped element), six plane writes.
+// Eight waves: waves 0..3 multiply the planes of pass 0 and waves 4..7 those of pass 1, each with the W pieces of its 32
+// columns in registers and the products of k_linear_fwd_x6<128, 4, true, false> in the same k-step order, so Y and the
+// statistics partials of a pass are that kernel's, bit for bit.  A workgroup walks row sets  blockIdx.x, + gridDim.x, ...
+// of the n_sets = fwd_x6_rows(M, 128, 128) the single launch has (tiles by, by + n_sets, ... in that order) and writes
+// partial[by][2][128] of each pass as the single kernel does.  Loads and stores go through per-tile buffer descriptors
+// (no branch around them), one barrier per tile, the first tile pair peeled -- see k_linear_fwd_x6.
+__global__ __launch_bounds__(512, 1) void k_linear_fwd_x6_dual(
+    const float* __restrict__ X, ProDev pr, ProDev prb, const float* __restrict__ W, const float* __restrict__ bias,
+    float* __restrict__ Y0, float* __restrict__ Y1, int64_t M, int n_sets, double* __restrict__ part0,
+    double* __restrict__ part1) {
+  constexpr int K = 128, N = 128, BN = 128, LDP = K + 8, NK = K / 16, NTHR = 512, BM = 32;
+  constexpr int PLANE = BM * LDP;            // one piece of one pass of one buffer, in bf16 elements
+  pr.resolve();
+  prb.resolve();
+  extern __shared__ __attribute__((aligned(16))) __bf16 planes[];     // [2 buffers][2 passes][3 pieces][BM][LDP]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int pass = wv >> 2, wn = wv & 3;
+  const int h = lane >> 5, l31 = lane & 31;
+  const int col = wn * 32 + l31;
+  float* __restrict__ const Y = pass ? Y1 : Y0;
+  double* __restrict__ const stat_partial = pass ? part1 : part0;
+
+  bf16x8 wb[NK][3];
+  {
+    const float* wp = W + (size_t)col * K + 8 * h;
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) {
+      const f32x4 w0 = *reinterpret_cast<const f32x4*>(wp + ks * 16), w1 = *reinterpret_cast<const f32x4*>(wp + ks * 16 + 4);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float v = j < 4 ? w0[j] : w1[j - 4];
+        MMG_SPLIT3(v, wb[ks][0][j], wb[ks][1][j], wb[ks][2][j]);
+      }
+    }
+  }
+  const float bv = bias ? bias[col] : 0.f;
+
+  constexpr int K4 = K / 4, ROWS_PER_PASS = NTHR / K4, NP = BM / ROWS_PER_PASS;      // 32 quads, 16 rows per pass, 2 passes
+  constexpr int KS_PER_PASS = NK / NP;
+  const int kc4 = tid % K4, prow = tid / K4;
+  f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
+  if (pr.scale) {
+    sc = *reinterpret_cast<const f32x4*>(pr.scale + kc4 * 4);
+    sh = *reinterpret_cast<const f32x4*>(pr.shift + kc4 * 4);
+  }
+  const float floor_v = pr.relu ? 0.f : -__builtin_inff();
+  const uint32_t thr = pr.thr, key0 = pr.key, key1 = prb.key;
+  const float inv_keep = pr.inv_keep;
+  const int64_t n_tiles = (M + BM - 1) / BM;
+  const int64_t G = n_sets;
+  auto rows_of = [&](int64_t tile) -> int {
+    const int64_t r = M - tile * BM;
+    return r <= 0 ? 0 : (r < BM ? (int)r : BM);
+  };
+  const int xvo = (prow * K + kc4 * 4) * 4;
+  auto fetch = [&](int64_t tile, f32x4* nx) {
+    const int rows = rows_of(tile);
+    const __amdgpu_buffer_rsrc_t rs = mmg_rsrc(X + (size_t)(rows ? tile : 0) * BM * K, rows * K * 4);
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+      nx[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, xvo, p * ROWS_PER_PASS * K * 4, MMG_NT_LD));
+  };
+  // 16-bit lanes of a piece pair kept (all ones) or dropped (zero): fields 0, 1 of a hash word against the threshold
+  auto keep_mask = [&](uint32_t w) __attribute__((always_inline)) -> uint32_t {
+    return ((w & 0xFFFFu) >= thr ? 0x0000FFFFu : 0u) | ((w >> 16) >= thr ? 0xFFFF0000u : 0u);
+  };
+  auto stage_pass = [&](int64_t tile, int buf, const f32x4* nx, int p) __attribute__((always_inline)) {
+    const int r = p * ROWS_PER_PASS + prow;
+    __bf16* pb = planes + (size_t)buf * 6 * PLANE + r * LDP + kc4 * 4;
+    f32x4 v = nx[p];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float s = fmaxf(fmaf(v[j], sc[j], sh[j]), floor_v) * inv_keep;
+      // the ROUNDED product is what gets split: in k_linear_fwd_x6 the dropout select stands between this multiply and the
+      // split's subtraction; without it the compiler contracts the two into one fma (an exact product minus the high
+      // piece) and the middle and low pieces come out an ulp off.  An empty asm keeps the multiply a multiply.
+      asm("" : "+v"(s));
+      v[j] = s;
+    }
+    const uint64_t grp = ((uint64_t)(pr.row_offset + tile * BM + r) * (uint64_t)K + (uint64_t)(kc4 * 4)) >> 2;
+    uint32_t a0, a1, b0, b1;
+    mmg_rng_group(key0, grp, &a0, &a1);
+    mmg_rng_group(key1, grp, &b0, &b1);
+    bf16x4 q[3];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) MMG_SPLIT3(v[j], q[0][j], q[1][j], q[2][j]);
+    const u32x2 ma = {keep_mask(a0), keep_mask(a1)}, mb = {keep_mask(b0), keep_mask(b1)};
+#pragma unroll
+    for (int pc = 0; pc < 3; ++pc) {
+      const u32x2 bits = __builtin_bit_cast(u32x2, q[pc]);
+      *reinterpret_cast<u32x2*>(pb + pc * PLANE) = bits & ma;
+      *reinterpret_cast<u32x2*>(pb + (3 + pc) * PLANE) = bits & mb;
+    }
+  };
+  const int yvo = ((4 * h) * N + col) * 4;     // C/D map: col = lane&31, row = (i&3) + 8*(i>>2) + 4*(lane>>5)
+
+  for (int by = blockIdx.x; by < n_sets; by += gridDim.x) {
+    const int64_t t0 = by;
+    const int n_my = (int)((n_tiles - t0 + G - 1) / G);      // tiles t0, t0+G, ... of this row set
+    double cs1 = 0.0, cs2 = 0.0;
+    f32x4 nxa[NP], nxb[NP];                   // two tiles of X in flight: tiles alternate between them
+    fetch(t0, nxa);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) stage_pass(t0, 0, nxa, p);
+    fetch(t0 + G, nxa);
+    fetch(t0 + 2 * G, nxb);
+    __syncthreads();
+    auto tile_body = [&](int64_t tt, int buf, f32x4* nx) {
+      // nx holds tile tt+G (fetched two tiles ago); after staging it, the registers take tile tt+3G
+      const int rows = rows_of(tt);
+      const __amdgpu_buffer_rsrc_t ys = mmg_rsrc(Y + (size_t)(rows ? tt : 0) * BM * N, rows * N * 4);
+      f32x16 acc;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+      const __bf16* ap = planes + (size_t)(buf * 6 + pass * 3) * PLANE + l31 * LDP + 8 * h;
+      bf16x8 fr[2][3];
+      auto ldfrag = [&](int ks, bf16x8* f) __attribute__((always_inline)) {
+        f[0] = *reinterpret_cast<const bf16x8*>(ap + ks * 16);
+        f[1] = *reinterpret_cast<const bf16x8*>(ap + PLANE + ks * 16);
+        f[2] = *reinterpret_cast<const bf16x8*>(ap + 2 * PLANE + ks * 16);
+      };
+      ldfrag(0, fr[0]);
+#pragma unroll
+      for (int pg = 0; pg < NP; ++pg) {          // one scheduling region = the k-steps that carry one staging pass
+#pragma unroll
+        for (int kk = 0; kk < KS_PER_PASS; ++kk) {
+          const int ks = pg * KS_PER_PASS + kk;
+          if (ks + 1 < NK) ldfrag(ks + 1, fr[(ks + 1) & 1]);
+          const bf16x8* f = fr[ks & 1];
+          MMG_X6_ALO(acc, f[0], f[1], f[2], wb[ks][0], wb[ks][1], wb[ks][2]);
+        }
+        stage_pass(tt + G, buf ^ 1, nx, pg);
+        // the pass (~90 vector instructions: prologue, two hashes, split, masks) is dealt out over the 24 products of
+        // its k-steps, its six plane writes behind the last six
+        constexpr int NM = 6 * KS_PER_PASS, VPER = 4;
+#pragma unroll
+        for (int i = 0; i < NM; ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                        // one MFMA
+          if (i % 6 < 3) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);         // one fragment read of the next k-step
+          __builtin_amdgcn_sched_group_barrier(0x002, VPER, 0);                     // a slice of the staging pass
+          if (i >= NM - 6) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);       // its plane writes at the end
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      fetch(tt + 3 * G, nx);                     // (its registers are free only now: two tiles stay in flight all the same)
+      float t1 = 0.f, t2 = 0.f;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int r = mmg_c_row(i);
+        const float v = acc[i] + bv;
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ys, yvo, r * N * 4, MMG_NT_ST);
+        const float vs = r + 4 * h < rows ? v : 0.f;
+        t1 += vs; t2 = fmaf(vs, vs, t2);
+      }
+      cs1 += (double)t1; cs2 += (double)t2;      // 16 rows in fp32, tiles in fp64
+      __syncthreads();                           // buf fully read, buf^1 fully written
+    };
+    tile_body(t0, 0, nxa);
+    tile_body(t0 + G, 1, nxb);
+    for (int i = 2; i < n_my; i += 2) {
+      tile_body(t0 + (int64_t)i * G, 0, nxa);
+      tile_body(t0 + (int64_t)(i + 1) * G, 1, nxb);
+    }
+    // two partials per column (the lane halves) -> one: partial[row-set][2][N] of each pass, fixed order
+    double* red = reinterpret_cast<double*>(planes) + pass * 4 * BN;      // the planes are dead: every wave passed the last barrier
+    red[(h * 2 + 0) * BN + col] = cs1;
+    red[(h * 2 + 1) * BN + col] = cs2;
+    __syncthreads();
+    {
+      const int e = tid & 255, which = e / BN, c = e % BN;      // threads 0..255: pass 0, 256..511: pass 1 (their own waves' sums)
+      stat_partial[((size_t)by * 2 + which) * N + c] = red[which * BN + c] + red[(2 + which) * BN + c];
+    }
+    __syncthreads();                             // the next row set stages over `red`
+  }
+}
+
+// one workgroup per CU (104 KB of planes).  The n_sets row sets are those of the single launch; they are dealt to
+// MMG_DUAL_WGS workgroups, a workgroup keeping its W pieces over its row sets (256: two row sets each at n_sets = 512)
+#ifndef MMG_DUAL_WGS
+#define MMG_DUAL_WGS 256
+#endif
+int launch_fwd_x6_dual(const float* X, const ProDev& pr, const ProDev& prb, const float* W, const float* bias, float* Y0,
+                       float* Y1, int64_t M, hipStream_t st, double* part0, double* part1) {
+  constexpr int lds = 2 * 2 * 3 * 32 * (128 + 8) * 2;
+  const int n_sets = (int)fwd_x6_rows(M, 128, 128, 128);
+  const int wgs = n_sets < MMG_DUAL_WGS ? n_sets : MMG_DUAL_WGS;
+  MMG_CHECK_HIP((MmgMaxLds<&k_linear_fwd_x6_dual, lds>::set()), "linear_fwd_dual(attr)");
+  // N is reported as 256: the launch computes 2 M N K products, reads X and W once and writes two [M, 128] outputs;
+  // flag 2048 = dual
+  MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, 256, 128, 4 | 2048, k_linear_fwd_x6_dual, dim3((unsigned)wgs), dim3(512), lds, st, X,
+             pr, prb, W, bias, Y0, Y1, M, n_sets, part0, part1);
+  return 0;
+}
+
 // rows +0..3 and +4..7 of this lane's column through the transposing LDS read (see the wgrad section)
 __device__ __forceinline__ bf16x8 tr_frag(const __bf16* p, int row_stride) { return mmg_tr_pair(p, p + 4 * row_stride); }
 
@@ -1753,6 +1954,42 @@ extern "C" int mmg_linear_fwd(const float* X, const mmg_prologue_t* pro, const f
   MMG_CHECK_LAUNCH(what);
   const int rows = (int)(K == 256 && N % 256 == 0 ? fwd_k256_rows(M, N) : fwd_x6_rows(M, N, N % 128 == 0 ? 128 : 64, K));
   return mmg_epi_finish(epi, Y, M, N, fused, partial, rows, what, stream);
+}
+
+extern "C" int mmg_linear_fwd_dual_supported(int64_t M, int N, int K) { return (M > 512 && N == 128 && K == 128) ? 1 : 0; }
+
+extern "C" int mmg_linear_fwd_dual(const float* X, const mmg_prologue_t* pro0, const mmg_prologue_t* pro1, const float* W,
+                                   const float* bias, float* Y0, float* Y1, int64_t M, int N, int K,
+                                   const mmg_fwd_epi_t* epi0, const mmg_fwd_epi_t* epi1, void* stream) {
+  const char* what = "linear_fwd_dual";
+  MMG_CHECK_ARG(mmg_linear_fwd_dual_supported(M, N, K), "%s: M=%lld N=%d K=%d unsupported (M > 512, N = K = 128)", what,
+                (long long)M, N, K);
+  MMG_CHECK_ARG(X && W && Y0 && Y1 && Y0 != Y1 && pro0 && pro1, "%s: null buffer or prologue, or one output for both passes", what);
+  MMG_CHECK_ARG(pro0->drop_p > 0.f, "%s: the two passes differ by their dropout masks only: drop_p > 0", what);
+  MMG_CHECK_ARG(pro0->scale == pro1->scale && pro0->shift == pro1->shift && pro0->relu == pro1->relu &&
+                    pro0->drop_p == pro1->drop_p && pro0->seed == pro1->seed && pro0->seed_ptr == pro1->seed_ptr &&
+                    pro0->row_offset == pro1->row_offset,
+                "%s: the two prologues must agree in everything but the site", what);
+  MMG_CHECK_ARG(pro0->site != pro1->site, "%s: the two prologues have the same site", what);
+  MMG_CHECK_ARG(!pro0->scale || pro0->shift, "%s: prologue scale without shift", what);
+  MMG_CHECK_ARG(pro0->relu == MMG_ACT_NONE || pro0->relu == MMG_ACT_RELU, "%s: the prologue takes relu only", what);
+  MMG_CHECK_ARG(epi0 && epi1 && epi0->mode == MMG_EPI_STATS && epi1->mode == MMG_EPI_STATS, "%s: both epilogues are MMG_EPI_STATS", what);
+  double *part0, *part1;
+  NextBnDev nb;
+  int rc = mmg_epi_prepare(epi0, M, N, what, &part0, &nb);
+  if (rc) return rc;
+  rc = mmg_epi_prepare(epi1, M, N, what, &part1, &nb);
+  if (rc) return rc;
+  const size_t part_bytes = (size_t)768 * 2 * N * sizeof(double);
+  const uintptr_t a = (uintptr_t)part0, b = (uintptr_t)part1;
+  MMG_CHECK_ARG((a > b ? a - b : b - a) >= part_bytes && epi0->col_sums != epi1->col_sums,
+                "%s: the two epilogues share a workspace or their sums", what);
+  hipStream_t st = (hipStream_t)stream;
+  rc = launch_fwd_x6_dual(X, mmg_pro_dev(pro0), mmg_pro_dev(pro1), W, bias, Y0, Y1, M, st, part0, part1);
+  if (rc) return rc;
+  MMG_CHECK_LAUNCH(what);
+  return mmg_partial_sum_bn2(part0, part1, epi0->col_sums, epi1->col_sums, N, (int)fwd_x6_rows(M, N, 128, K), epi0->fin,
+                             epi1->fin, stream);
 }
 
 extern "C" int mmg_linear_bnbwd_supported(int mode, int64_t M, int N, int K, int with_wgrad) {

@@ -96,6 +96,17 @@ def set_fused_wgrad(on: bool):
     FUSED_WGRAD = bool(on)
 
 
+# The second linear of the encoder runs once per encode_nodes pass of a training step, on the same input under two dropout
+# masks: one launch serves both (ops.linear_fwd_dual), bit for bit the two launches.  set_dual_enc(False) restores them.
+DUAL_ENC = True
+
+
+def set_dual_enc(on: bool):
+    """True (default) | False -- see DUAL_ENC (the tests switch it)."""
+    global DUAL_ENC
+    DUAL_ENC = bool(on)
+
+
 def _mangle(et: EdgeType) -> str:
     return "<" + "___".join(et) + ">"
 
@@ -658,7 +669,7 @@ class _Run:
         # advanced twice.
         if self.p > 0:
             first = self.enc_first(2)            # shared by both passes (no dropout before the first BatchNorm)
-            m0, m1 = self.enc_mid(0, first), self.enc_mid(1, first)
+            m0, m1 = self.enc_mid_both(first)
             if self.comm is not None and self.T:     # sharded: the statistics of both passes in ONE all-reduce
                 both = torch.stack([m0.stats, m1.stats])
                 self.allreduce(both)
@@ -818,6 +829,20 @@ class _Run:
         z2, s2 = self.with_bn_stats(lambda **epi: ops.linear_fwd(z1, pt[4].weight.detach(), pt[4].bias.detach(), pro=pro1,
                                                                  **epi), pt[5], n_updates, z1.shape[0])
         return _EncMid(pro1, z2, s2)
+
+    def enc_mid_both(self, first):
+        """enc_mid of pass 0 and of pass 1: one launch (ops.linear_fwd_dual, DUAL_ENC) where the library takes the shape --
+        the two calls read the same z1 and differ in their dropout site alone -- else the two calls."""
+        pt = self.m.patient_transform
+        E, z1, f1 = first
+        w = pt[4].weight.detach()
+        if not (DUAL_ENC and self.T and ops.linear_fwd_dual_supported(z1.shape[0], w.shape[0], w.shape[1])):
+            return self.enc_mid(0, first), self.enc_mid(1, first)
+        pros = [Pro(f1.scale, f1.shift, True, self.p, self.seed, 2 * call, self.plan.row_offset, self.seed_dev)
+                for call in (0, 1)]
+        spec = self.bn_spec(pt[5], 1, z1.shape[0], True)      # None (sharded): the sums come back unfolded, as from enc_mid
+        r0, r1 = ops.linear_fwd_dual(z1, w, pt[4].bias.detach(), pros[0], pros[1], bn0=spec, bn1=spec)
+        return _EncMid(pros[0], r0[0], r0[-1]), _EncMid(pros[1], r1[0], r1[-1])
 
     def enc_fwd(self, call, n_updates, first=None, rows=None, row_pos=None, mid: Optional[_EncMid] = None) -> _EncPass:
         """rows (int64 ids; row_pos = every row's position among them or -1): everything after the last BatchNorm -- third

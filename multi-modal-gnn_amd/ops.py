@@ -163,7 +163,7 @@ PROBE_NAME_LEN = _lib.MMG_PROBE_NAME_LEN
 
 
 def probe_read(cap: int = 1 << 16):
-    """-> list of (ms, family name, M, N, K, flags, kernel symbol) of the probed launches (flags: 1 accumulate, 4 prologue, 8 rowscale, 16 BatchNorm backward staged in the GEMM, 32 L2-norm epilogue, 64 L2-norm backward staged, 128 two upstream gradients, 256 row-list upstream gradient)."""
+    """-> list of (ms, family name, M, N, K, flags, kernel symbol) of the probed launches (flags: 1 accumulate, 4 prologue, 8 rowscale, 16 BatchNorm backward staged in the GEMM, 32 L2-norm epilogue, 64 L2-norm backward staged, 128 two upstream gradients, 256 row-list upstream gradient, 2048 the dual linear forward: N = both outputs)."""
     import numpy as np
     ms = np.zeros(cap, np.float32); tag = np.zeros(cap, np.int32); M = np.zeros(cap, np.int64)
     N = np.zeros(cap, np.int32); K = np.zeros(cap, np.int32); fl = np.zeros(cap, np.int32)
@@ -431,6 +431,40 @@ def _linear_fwd(x, W, bias, pro, out, accumulate, w_kn, **epi):
     nbn = epi.get("next_bn") is not None          # + the next BatchNorm's y
     _pe(_tok, "linear_fwd", 4 * (M * K + N * K + M * N * (1 + int(accumulate) + int(nbn))), 2 * M * N * K)
     return (out,) + extra if extra else out
+
+
+def linear_fwd_dual_supported(M: int, N: int, K: int) -> bool:
+    return bool(_lib.load().mmg_linear_fwd_dual_supported(M, N, K))
+
+
+def linear_fwd_dual(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], pro0: Pro, pro1: Pro, bn0=None, bn1=None):
+    """The same layer under two dropout masks in one launch (mmg_linear_fwd_dual): pro0 and pro1 differ in their site
+    alone.  -> ((out0, sums0[, BNFold0]), (out1, sums1[, BNFold1])): what linear_fwd(x, W, bias, pro=pro_c, with_stats=True
+    / bn=bn_c) returns, pass 0's call before pass 1's, bit for bit.  bn0 / bn1 as linear_fwd's bn: both or neither."""
+    M, K = x.shape
+    N = W.shape[0]
+    if W.shape[1] != K:
+        raise ValueError(f"linear_fwd_dual: W {tuple(W.shape)} vs x {tuple(x.shape)}")
+    if (bn0 is None) != (bn1 is None):
+        raise ValueError("linear_fwd_dual: a BatchNorm fold for both passes or for neither")
+    outs = [torch.empty(M, N, dtype=torch.float32, device=x.device) for _ in range(2)]
+    nb = (_lib.load().mmg_epi_ws_bytes(M, N) + 255) // 256 * 256
+    ws = workspace(2 * nb + 256, x.device)             # one half per pass: the two sets of partial rows live side by side
+    descs, extras = [], []
+    for c, bn in enumerate((bn0, bn1)):
+        sums = torch.empty(2, N, dtype=torch.float64, device=x.device)
+        fin, fold = _bn_fin(M, N, x.device, bn) if bn is not None else (None, None)
+        half = ws[c * nb:(c + 1) * nb]
+        e = FwdEpiT(EPI_STATS, col_sums=_p(sums, torch.float64), fin=C.pointer(fin) if fin is not None else None,
+                    ws=_p(half, torch.uint8), ws_bytes=half.numel())
+        e._keep = (fin, ws)
+        descs.append(e)
+        extras.append((sums,) if fold is None else (sums, fold))
+    _tok = _pb("linear_fwd")
+    _call("mmg_linear_fwd_dual", x, _pro(pro0), _pro(pro1), W, bias, outs[0], outs[1], M, N, K, C.byref(descs[0]),
+          C.byref(descs[1]), names={"X": "x", "Y0": "out0", "Y1": "out1"})
+    _pe(_tok, "linear_fwd", 4 * (M * K + N * K + 2 * M * N), 4 * M * N * K)
+    return (outs[0],) + extras[0], (outs[1],) + extras[1]
 
 
 def linear_wgrad(dy: torch.Tensor, x: torch.Tensor, pro: Optional[Pro] = None, out: Optional[torch.Tensor] = None,
