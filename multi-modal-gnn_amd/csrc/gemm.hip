@@ -1811,8 +1811,10 @@ int launch_bnbwd_fw(const float* G, const BnBwdDev& bb, const ProDev& pr, const 
 template <int K>
 int launch_small(const float* X, const ProDev& pr, const float* W, const float* bias, float* Y, int64_t M, int N,
                  int accumulate, hipStream_t st) {
-  hipLaunchKernelGGL((k_linear_small<K>), dim3((unsigned)(N / 32), (unsigned)((M + 31) / 32)), dim3(256), 0, st, X, pr, W,
-                     bias, Y, M, N, accumulate);
+  // (through the probe like the split kernels: a test reads from it on which side of M = 512 a call ran)
+  MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, N, K, (accumulate & MMG_LIN_ACCUMULATE) | ((pr.scale || pr.relu || pr.p > 0.f) ? 4 : 0),
+             (k_linear_small<K>), dim3((unsigned)(N / 32), (unsigned)((M + 31) / 32)), dim3(256), 0, st, X, pr, W, bias, Y, M,
+             N, accumulate);
   return 0;
 }
 

@@ -106,7 +106,7 @@ def _x(ops, dev, M, with_pro, p, seed):
     return x, pro, ops.affine_act_drop(x, pro)
 
 
-@pytest.mark.parametrize("M", [600, 1001, 5003, 183400])
+@pytest.mark.parametrize("M", [513, 600, 1001, 5003, 183400])
 @pytest.mark.parametrize("with_pro", [False, True])
 @pytest.mark.parametrize("mode", [0, 1, 2, 3])
 def test_fused_weight_gradient_matches_the_two_kernels(ops, dev, mode, with_pro, M):

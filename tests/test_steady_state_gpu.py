@@ -33,6 +33,7 @@ import torch
 
 import pair_ref
 import rng_ref as R
+from dense_plan_ref import fwd_symbol, tf
 
 pytestmark = pytest.mark.gpu
 
@@ -58,10 +59,6 @@ def ops():
 def rel(a, b):
     a, b = a.double().cpu(), b.double().cpu()
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
-
-
-def tf(b):
-    return "true" if b else "false"
 
 
 # ------------------------------------------------------------------------------------------ the regime, from the probe
@@ -252,13 +249,6 @@ def bn_below(ops, dev, M, N, p, seed=71, site=23, row_offset=10):
 
 
 # ------------------------------------------------------------------------------------------ mmg_linear_fwd
-def fwd_symbol(K, N, pro=False, acc=False, l2=False, nbn=False, stats=False, p=0.0):
-    if K == 256 and N % 256 == 0:
-        return f"k_linear_fwd_h3_k256<{2 if pro and p > 0 else int(pro)}, {tf(acc)}, {tf(stats)}, 8>"
-    wn = 4 if N % 128 == 0 else 2
-    return f"k_linear_fwd_x6<{K}, {wn}, {tf(pro)}, {tf(acc)}, {tf(l2)}, {tf(nbn)}>"
-
-
 def fwd_family(K, N):
     return "h3" if K == 256 and N % 256 == 0 else ("x6 K = 256" if K == 256 else "x6 K <= 128")
 
