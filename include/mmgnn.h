@@ -387,6 +387,26 @@ int mmg_linear_bnbwd_supported(int mode, int64_t M, int N, int K, int with_wgrad
 size_t mmg_linear_bnbwd_wgrad_ws_bytes(int64_t M, int N, int K);
 int mmg_linear_bnbwd(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
                      const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, void* stream);
+/* The data gradient AND the weight gradient of a plain linear in ONE launch -- the first layer of a pair head, whose
+ * upstream gradient dY [M, K] is the gradient of the head's per-patient table (K = 64) and whose input X [M, N] is the
+ * final patient activation (N = 128):
+ *   dX [M, N] = dY . W            W stored [K, N], the forward weight in place: mmg_linear_fwd(dY, NULL, W, NULL, dX, M, N, K,
+ *                                 MMG_LIN_W_KN, next ? {MMG_EPI_NEXT_BN, next} : NULL)
+ *   wg->dW [K, N] (+)= dY^T . pro(X)    mmg_linear_wgrad(dY, wg->X, wg->pro, wg->dW, NULL, M, K, N, wg->accumulate, ...)
+ * dY is read and split once and serves both products; dX and dW are bit for bit those of the two calls (same products, same
+ * order, same slabs, same slab sum).  wg->dbias must be NULL; wg->pro takes scale / shift and relu, no dropout; the slabs are
+ * left in wg->ws and described in *wg->job for mmg_wgrad_reduce_group, job == NULL sums them before returning.
+ * next (nullable): the statistics of the BatchNorm backward that consumes dX, from the epilogue.  The layer's input IS that
+ * BatchNorm's pre-activation: wg->X must be next->y, and wg->pro and next->pro must agree (scale, shift, relu; no dropout).
+ * The partial statistics rows are one per weight-gradient workgroup, so the fp64 summation order differs from
+ * mmg_linear_fwd's (the sums are bitwise repeatable from call to call).
+ * mmg_linear_dgrad_wgrad_supported: M > 512, N = 128, K = 64, and no dropout in either prologue (drop_p = the larger of
+ * the two); anything else is refused with MMG_E_ARG before anything is launched -- the caller then makes the two calls.
+ * Workspace: mmg_linear_dgrad_wgrad_ws_bytes(M, N, K) = mmg_linear_wgrad_ws_bytes(M, K, N). */
+int mmg_linear_dgrad_wgrad_supported(int64_t M, int N, int K, float drop_p);
+size_t mmg_linear_dgrad_wgrad_ws_bytes(int64_t M, int N, int K);
+int mmg_linear_dgrad_wgrad(const float* dY, const float* W, float* dX, int64_t M, int N, int K, const mmg_next_bn_t* next,
+                           const mmg_bnbwd_wgrad_t* wg, void* stream);
 
 /* Measurement hook (bench.py).  After mmg_probe_arm(n) the next n launches of the big kernels (from any host thread: the
  * backward of a step runs on the autograd engine's thread) carry a HIP start / stop event pair on the kernel itself (hipExtLaunchKernelGGL: the kernel's own begin / end
@@ -395,7 +415,10 @@ int mmg_linear_bnbwd(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX,
  *   ms = kernel duration, tag = MMG_PROBE_* family, (M, N, K) = the launch's shape: rows / output width / inner width for
  *   the dense kernels; patient rows / D / total vocab rows of the fused relations for the aggregates; pairs / 0 / 0 for
  *   the heads;  flags: 1 = accumulate, 4 = prologue, 8 = rowscale, 2048 = the dual linear forward (mmg_linear_fwd_dual: N is
- *   reported as 2 * 128, the two outputs side by side, so that 4 (M K + N K + M N) bytes and 2 M N K FLOP price the launch).
+ *   reported as 2 * 128, the two outputs side by side, so that 4 (M K + N K + M N) bytes and 2 M N K FLOP price the launch),
+ *   4096 = the layer's weight gradient rides along (mmg_linear_dgrad_wgrad: the row is the data gradient's (M, 128, 64), with
+ *   512 where the next-BatchNorm epilogue runs; priced as the data gradient alone, the launch also reads X [M, N] and does
+ *   2 M N K FLOP more).
  * The hook is the library's only process-wide mutable state (mutex-guarded); the product path never arms it. */
 #define MMG_PROBE_LINEAR_FWD 1
 #define MMG_PROBE_LINEAR_WGRAD 2

@@ -1808,6 +1808,268 @@ int launch_bnbwd_fw(const float* G, const BnBwdDev& bb, const ProDev& pr, const 
   return 0;
 }
 
+// ---------------------------------------------------------------------------- data gradient + weight gradient of a pair head's first layer
+// k_linear_dgrad_wgrad_x6: DX [M, 128] = dY . W (W [64, 128], the forward weight in place) AND the slabs of
+// dW [64, 128] = dY^T . pro(X) in one pass over dY [M, 64] and X [M, 128] -- k_linear_fwd_x6<64, 4, false, false, false, NBN>
+// and k_linear_wgrad_x6<64, 128, 2, 4, PRO> each read both tensors (with NBN, X is the next BatchNorm's y) and split dY.
+// The skeleton of k_linear_bnbwd_x6<..., FW = true>: one 512-thread workgroup per CU, tiles dealt round-robin over
+// gridDim.y = plan_wgrad(M, 64, 128).n_split workgroups -- the row set and the 32-row stage order of the separate
+// weight-gradient kernel's slab -- one barrier per tile, per-tile buffer descriptors, the first tile pair peeled.
+//   waves 0..3  the body of k_linear_fwd_x6<64, 4, ...>: stage the 32 x 64 dY tile (MMG_SPLIT3, three bf16 planes, two tiles
+//               in flight in registers), the W pieces of the wave's 32 columns in 48 registers, MMG_X6_ALO over the four
+//               k-steps in order, store, next_bn_tile -> DX and the per-tile statistics are that kernel's bit for bit
+//   waves 4..7  stage the 32 x 128 tile of X (affine + ReLU, one split; two tiles in flight) and each hold the 64 x 32 column
+//               block w of dW as two accumulators; the operands come through the transposing LDS read from the dY planes
+//               and the X planes, the six products per accumulator and 16-row step in k_linear_wgrad_x6's order (both
+//               kernels split dY with MMG_SPLIT3: the pieces are the same), so the slab is that kernel's bit for bit
+// dY planes: 128-byte rows without padding, the 16-byte chunk c of row r stored at chunk  c ^ f(r),
+// f(r) = 4 ((r >> 1) & 1) | ((r >> 2) & 3).  No plain row stride serves both readers: the row reads (ds_read_b128, a
+// 16-lane group = 16 rows, one chunk each) need stride / 16 B odd, the transposing reads (4 rows x 64 B per half wave) need
+// it = 64 or 192 B mod 256.  With the XOR the 8 rows of one parity in a 16-lane group get 8 distinct chunks (all 64 banks),
+// and the rows q, q + 2 of a transposed block land in different 64-byte halves of their 128 bytes (bit 2 of f), q and q + 1
+// in different 128-byte halves of the 256-byte bank line: both reads are conflict-free, and the planes take 24 KB instead of
+// the 27 (row-read stride) or 37 KB (transposing stride).  X planes: row stride + 64 B as in k_linear_wgrad_x6.
+struct DgWgDev { const float* X; ProDev xpr; float* slab; int64_t slab_stride; };
+
+template <bool NBN>
+__global__ __launch_bounds__(512, 1) void k_linear_dgrad_wgrad_x6(
+    const float* __restrict__ dY, const float* __restrict__ W, float* __restrict__ DX, int64_t M, NextBnDev nb,
+    double* __restrict__ stat_partial, DgWgDev wg) {
+  constexpr int K = 64, N = 128, NK = K / 16, NTHR = 256, BM = 32;
+  constexpr int PZ = BM * K;               // one dY plane (bf16 elements)
+  constexpr int SX = N + 32;               // X plane row stride: +64 B puts the 4 rows of a transposing read on disjoint banks
+  extern __shared__ __attribute__((aligned(16))) __bf16 planes[];     // [2 buffers][3 pieces][BM][K] of dY + [2][3][BM][SX] of X
+  const int tid = threadIdx.x, lane = tid & 63, wn = tid >> 6;
+  const int h = lane >> 5, l31 = lane & 31;
+  const bool xrole = tid >= NTHR;          // (wave-uniform) the X stagers / dW multipliers
+  // element offset of (row r, column c) in a dY plane
+  auto zoff = [](int r, int c) __attribute__((always_inline)) -> int {
+    const int f = (((r >> 1) & 1) << 2) | ((r >> 2) & 3);
+    return r * K + ((((c >> 3) ^ f)) << 3) + (c & 7);
+  };
+  // (the row-set index through readfirstlane: see k_linear_bnbwd_x6)
+  const int by_u = __builtin_amdgcn_readfirstlane((int)blockIdx.y);
+  const int64_t n_tiles = (M + BM - 1) / BM;
+  const int64_t GY = gridDim.y, t0 = by_u;
+  const int n_my = t0 < n_tiles ? (int)((n_tiles - t0 + GY - 1) / GY) : 0;     // tiles t0, t0 + GY, ... (0: a slab of zeros)
+  auto rows_of = [&](int64_t tile) __attribute__((always_inline)) -> int {     // valid rows of a tile (0 past the end)
+    const int64_t r = M - tile * BM;
+    return r <= 0 ? 0 : (r < BM ? (int)r : BM);
+  };
+  __bf16* xplanes = planes + 2 * 3 * PZ;
+  if (xrole) {
+    // ---------------------------------------------------------------- X stagers and dW multipliers (waves 4..7)
+    wg.xpr.resolve();
+    const int t = tid - NTHR, w = wn - 4;
+    const int xc4 = t & 31, xr = t >> 5;            // a thread stages the column quad xc4 of rows xr + 8 u
+    constexpr int XU = BM * N / 4 / NTHR;           // 16-B loads per thread per tile
+    const int xvo = (xr * N + xc4 * 4) * 4;
+    f32x4 nxa[XU], nxb[XU];                         // two tiles of X in flight: tiles alternate between them
+    auto xfetch = [&](int64_t tile, f32x4* nx) __attribute__((always_inline)) {
+      const int rows = rows_of(tile);
+      const __amdgpu_buffer_rsrc_t xsrc = mmg_rsrc(wg.X + (size_t)(rows ? tile : 0) * BM * N, rows * N * 4);
+#pragma unroll
+      for (int u = 0; u < XU; ++u)
+        nx[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, xvo, u * (NTHR / 32) * N * 4, MMG_NT_WG));
+    };
+    f32x4 xsc = {1.f, 1.f, 1.f, 1.f}, xsh = {0.f, 0.f, 0.f, 0.f};
+    float xfloor = -__builtin_inff();
+    const bool xaff = wg.xpr.scale != nullptr || wg.xpr.relu;
+    if (wg.xpr.scale) {
+      xsc = *reinterpret_cast<const f32x4*>(wg.xpr.scale + xc4 * 4);
+      xsh = *reinterpret_cast<const f32x4*>(wg.xpr.shift + xc4 * 4);
+    }
+    if (wg.xpr.relu) xfloor = 0.f;
+    auto xstage = [&](int buf, const f32x4* nx) __attribute__((always_inline)) {
+      __bf16* xb = xplanes + (size_t)buf * 3 * BM * SX;
+#pragma unroll
+      for (int u = 0; u < XU; ++u) {
+        const int r = xr + u * (NTHR / 32);
+        f32x4 v = nx[u];
+        if (xaff) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = fmaxf(fmaf(v[j], xsc[j], xsh[j]), xfloor);
+        }
+        // rows past the end need no zeroing: their dY rows are zero
+        bf16x4 q0, q1, q2;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) MMG_SPLIT3(v[j], q0[j], q1[j], q2[j]);
+        *reinterpret_cast<bf16x4*>(xb + (0 * BM + r) * SX + xc4 * 4) = q0;
+        *reinterpret_cast<bf16x4*>(xb + (1 * BM + r) * SX + xc4 * 4) = q1;
+        *reinterpret_cast<bf16x4*>(xb + (2 * BM + r) * SX + xc4 * 4) = q2;
+      }
+    };
+    // transposing-read lane roles as in k_linear_wgrad_x6: group g4 fetches rows 8 (g4 >> 1) + q, columns 16 (g4 & 1) + 4 p4
+    const int g4 = lane >> 4, q = (lane >> 2) & 3, p4 = lane & 3;
+    const int tr_row = 8 * (g4 >> 1) + q, tr_col = 16 * (g4 & 1) + 4 * p4;
+    // dY planes: rows +0..3 and +4..7 of the 32-column block x (f does not change with the 16-row step: 16 ks adds 0 to
+    // (r >> 1) & 1 and to (r >> 2) & 3)
+    int zo[2][2];
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) zo[x][u] = zoff(tr_row + 4 * u, x * 32 + tr_col);
+    f32x16 wacc[2];
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) wacc[x][i] = 0.f;
+    xfetch(t0, nxa);
+    xstage(0, nxa);
+    xfetch(t0 + GY, nxa);
+    xfetch(t0 + 2 * GY, nxb);
+    __syncthreads();
+    auto wbody = [&](int64_t tt, int buf, f32x4* nx) __attribute__((always_inline)) {
+      // nx holds tile tt + GY (fetched two tiles ago); after staging it, the registers take tile tt + 3 GY
+      xstage(buf ^ 1, nx);
+      xfetch(tt + 3 * GY, nx);
+      __builtin_amdgcn_sched_barrier(0);         // keep the fetch ahead of the matrix loop
+      const __bf16* zb = planes + (size_t)buf * 3 * PZ;
+      const __bf16* xb = xplanes + (size_t)buf * 3 * BM * SX + tr_row * SX + w * 32 + tr_col;
+#pragma unroll
+      for (int ks = 0; ks < BM / 16; ++ks) {
+        bf16x8 fa[2][3], fb[3];
+#pragma unroll
+        for (int pc = 0; pc < 3; ++pc) {
+#pragma unroll
+          for (int x = 0; x < 2; ++x)
+            fa[x][pc] = mmg_tr_pair(zb + pc * PZ + ks * 16 * K + zo[x][0], zb + pc * PZ + ks * 16 * K + zo[x][1]);
+          fb[pc] = tr_frag(xb + pc * BM * SX + ks * 16 * SX, SX);
+        }
+        // MMG_X6_ALO's order for each accumulator, the two accumulators' chains interleaved
+        constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+        for (int tm = 0; tm < 6; ++tm)
+#pragma unroll
+          for (int x = 0; x < 2; ++x)
+            wacc[x] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[x][PA[tm]], fb[PB[tm]], wacc[x], 0, 0, 0);
+      }
+      __syncthreads();                           // buf fully read, buf^1 fully written
+    };
+    wbody(t0, 0, nxa);
+    wbody(t0 + GY, 1, nxb);
+    for (int i = 2; i < n_my; i += 2) {
+      wbody(t0 + (int64_t)i * GY, 0, nxa);
+      wbody(t0 + (int64_t)(i + 1) * GY, 1, nxb);
+    }
+    if constexpr (NBN) __syncthreads();          // pairs with the barrier of the statistics epilogue below
+    // slab[row-set][64 x 128], the layout of k_linear_wgrad_x6
+    float* dst = wg.slab + (size_t)by_u * wg.slab_stride;
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) dst[(size_t)(x * 32 + mmg_c_row(i) + 4 * h) * N + w * 32 + l31] = wacc[x][i];
+    return;
+  }
+  // -------------------------------------------------------------------- dY stagers and DX multipliers (waves 0..3)
+  const int col = wn * 32 + l31;
+  bf16x8 wb[NK][3];                         // W stored [K, N] (the forward weight, read in place)
+  {
+    const float* wp = W + (size_t)(8 * h) * N + col;
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float v = wp[(size_t)(ks * 16 + j) * N];
+        MMG_SPLIT3(v, wb[ks][0][j], wb[ks][1][j], wb[ks][2][j]);
+      }
+  }
+  NextBnCol nbc = {};
+  double cs1 = 0.0, cs2 = 0.0;
+  if constexpr (NBN) nbc = next_bn_col(nb, col);
+  constexpr int K4 = K / 4, ROWS_PER_PASS = NTHR / K4, NP = BM / ROWS_PER_PASS;
+  const int kc4 = tid % K4, prow = tid / K4;
+  f32x4 nxa[NP], nxb[NP];                   // two tiles of dY in flight: tiles alternate between them
+  const int xvo = (prow * K + kc4 * 4) * 4;
+  auto fetch = [&](int64_t tile, f32x4* nx) __attribute__((always_inline)) {
+    const int rows = rows_of(tile);
+    const __amdgpu_buffer_rsrc_t rs = mmg_rsrc(dY + (size_t)(rows ? tile : 0) * BM * K, rows * K * 4);
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+      nx[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, xvo, p * ROWS_PER_PASS * K * 4, MMG_NT_LD));
+  };
+  const int zst = zoff(prow, kc4 * 4);      // (f is the same for the rows prow and prow + 16 of the two passes)
+  auto stage = [&](int buf, const f32x4* nx) __attribute__((always_inline)) {      // split + three plane writes (rows past the end: zeros)
+    __bf16* pb = planes + (size_t)buf * 3 * PZ + zst;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      const f32x4 v = nx[p];
+      bf16x4 q0, q1, q2;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) MMG_SPLIT3(v[j], q0[j], q1[j], q2[j]);
+      *reinterpret_cast<bf16x4*>(pb + 0 * PZ + p * ROWS_PER_PASS * K) = q0;
+      *reinterpret_cast<bf16x4*>(pb + 1 * PZ + p * ROWS_PER_PASS * K) = q1;
+      *reinterpret_cast<bf16x4*>(pb + 2 * PZ + p * ROWS_PER_PASS * K) = q2;
+    }
+  };
+  int ao[NK];                               // this lane's A fragment of k-step ks: row l31, columns 16 ks + 8 h + 0..7
+#pragma unroll
+  for (int ks = 0; ks < NK; ++ks) ao[ks] = zoff(l31, ks * 16 + 8 * h);
+  fetch(t0, nxa);
+  stage(0, nxa);
+  fetch(t0 + GY, nxa);
+  fetch(t0 + 2 * GY, nxb);
+  __syncthreads();
+  const int yvo = ((4 * h) * N + col) * 4;     // C/D map: col = lane&31, row = (i&3) + 8*(i>>2) + 4*(lane>>5)
+  auto tile_body = [&](int64_t tt, int buf, f32x4* nx) __attribute__((always_inline)) {
+    // nx holds tile tt + GY (fetched two tiles ago); after staging it, the registers take tile tt + 3 GY
+    const int rows = rows_of(tt);
+    const __amdgpu_buffer_rsrc_t xs = mmg_rsrc(DX + (size_t)(rows ? tt : 0) * BM * N, rows * N * 4);
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    float nby[NBN ? 16 : 1];
+    if constexpr (NBN) next_bn_load(nb, tt, rows, N, 0, yvo, nby);   // in flight under the products
+    stage(buf ^ 1, nx);                        // the other buffer: its readers passed the barrier of the last tile
+    fetch(tt + 3 * GY, nx);
+    __builtin_amdgcn_sched_barrier(0);         // keep the fetch ahead of the matrix loop
+    const __bf16* ap = planes + (size_t)buf * 3 * PZ;
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) {
+      const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(ap + ao[ks]);
+      const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(ap + PZ + ao[ks]);
+      const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(ap + 2 * PZ + ao[ks]);
+      MMG_X6_ALO(acc, a1, a2, a3, wb[ks][0], wb[ks][1], wb[ks][2]);
+    }
+    float vv[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      vv[i] = acc[i] + 0.f;                    // (k_linear_fwd_x6 adds its absent bias as +0: a sum that underflowed to -0 becomes +0)
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[i]), xs, yvo, mmg_c_row(i) * N * 4, MMG_NT_ST);
+    }
+    if constexpr (NBN) next_bn_tile(nb, nbc, vv, nby, rows, tt * BM, N, col, lane, cs1, cs2);
+    __syncthreads();                           // buf fully read, buf^1 fully written
+  };
+  tile_body(t0, 0, nxa);
+  tile_body(t0 + GY, 1, nxb);
+  for (int i = 2; i < n_my; i += 2) {
+    tile_body(t0 + (int64_t)i * GY, 0, nxa);
+    tile_body(t0 + (int64_t)(i + 1) * GY, 1, nxb);
+  }
+  if constexpr (NBN) {
+    // two partials per column (the lane halves) -> one: partial[row-set][2][N], fixed order
+    double* red = reinterpret_cast<double*>(planes);          // the planes are dead: every wave passed the last barrier
+    red[(h * 2 + 0) * N + col] = cs1;
+    red[(h * 2 + 1) * N + col] = cs2;
+    __syncthreads();
+    for (int e = tid; e < 2 * N; e += NTHR) {
+      const int which = e / N, cc = e % N;
+      stat_partial[((size_t)by_u * 2 + which) * N + cc] = red[which * N + cc] + red[(2 + which) * N + cc];
+    }
+  }
+}
+
+template <bool NBN>
+int launch_dgrad_wgrad(const float* dY, const float* W, float* DX, int64_t M, const NextBnDev& nb, double* stat_partial,
+                       const DgWgDev& wg, int n_split, bool has_pro, hipStream_t st) {
+  constexpr int lds = 2 * 3 * 32 * 64 * 2 + 2 * 3 * 32 * (128 + 32) * 2;      // dY planes + X planes: 84 KB
+  MMG_CHECK_HIP((MmgMaxLds<&k_linear_dgrad_wgrad_x6<NBN>, lds>::set()), "linear_dgrad_wgrad(attr)");
+  // flags: 4 = the X prologue, 512 = the next-BatchNorm epilogue, 4096 = the weight gradient rides along
+  MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, 128, 64, (has_pro ? 4 : 0) | (NBN ? 512 : 0) | 4096, (k_linear_dgrad_wgrad_x6<NBN>),
+             dim3(1u, (unsigned)n_split), dim3(512), lds, st, dY, W, DX, M, nb, stat_partial, wg);
+  return 0;
+}
+
 template <int K>
 int launch_small(const float* X, const ProDev& pr, const float* W, const float* bias, float* Y, int64_t M, int N,
                  int accumulate, hipStream_t st) {
@@ -2194,6 +2456,67 @@ extern "C" int mmg_linear_wgrad_deferred(const float* dY, const float* X, const 
                                          mmg_wgrad_reduce_t* job) {
   MMG_CHECK_ARG(job, "linear_wgrad_deferred: job is null");
   return linear_wgrad_impl(dY, X, pro, dW, dbias, M, N, K, accumulate, ws, ws_bytes, stream, job);
+}
+
+extern "C" int mmg_linear_dgrad_wgrad_supported(int64_t M, int N, int K, float drop_p) {
+  return (M > 512 && N == 128 && K == 64 && !(drop_p > 0.f)) ? 1 : 0;
+}
+
+extern "C" size_t mmg_linear_dgrad_wgrad_ws_bytes(int64_t M, int N, int K) {
+  return mmg_linear_wgrad_ws_bytes(M, K, N);            // the slabs of the separate weight gradient of dY [M, K], X [M, N]
+}
+
+extern "C" int mmg_linear_dgrad_wgrad(const float* dY, const float* W, float* dX, int64_t M, int N, int K,
+                                      const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, void* stream) {
+  const char* what = "linear_dgrad_wgrad";
+  MMG_CHECK_ARG(wg, "%s: null weight-gradient descriptor", what);
+  mmg_wgrad_reduce_t* job = wg->job;
+  if (job) { job->slab = nullptr; job->n4 = 0; job->n_split = 0; job->dW = wg->dW; job->dbias = nullptr; job->nk4 = (int64_t)K * N / 4; job->accumulate = wg->accumulate; }
+  float drop_p = wg->pro ? wg->pro->drop_p : 0.f;
+  if (next && next->pro && next->pro->drop_p > drop_p) drop_p = next->pro->drop_p;
+  MMG_CHECK_ARG(mmg_linear_dgrad_wgrad_supported(M, N, K, drop_p), "%s: M=%lld N=%d K=%d drop_p=%g unsupported (M > 512, N = 128, K = 64, no dropout)",
+                what, (long long)M, N, K, (double)drop_p);
+  MMG_CHECK_ARG(dY && W && dX && wg->X && wg->dW && wg->ws, "%s: null buffer", what);
+  MMG_CHECK_ARG(!wg->dbias, "%s: the layer's bias gradient comes from the lab side: dbias must be NULL", what);
+  MMG_CHECK_ARG(!wg->pro || wg->pro->relu == MMG_ACT_NONE || wg->pro->relu == MMG_ACT_RELU, "%s: the X prologue takes relu only", what);
+  MMG_CHECK_ARG(!wg->pro || !wg->pro->scale || wg->pro->shift, "%s: X prologue: scale without shift", what);
+  const ProDev xpr = mmg_pro_dev(wg->pro);
+  NextBnDev nb = next_bn_none();
+  double* partial = nullptr;
+  if (next) {
+    MMG_CHECK_ARG(next->y == wg->X, "%s: the next BatchNorm's y must be the layer input wg->X", what);
+    MMG_CHECK_ARG(next->pro && mmg_next_bn_fusable(next), "%s: the next BatchNorm takes relu only", what);
+    MMG_CHECK_ARG(next->pro->scale == xpr.scale && next->pro->shift == xpr.shift && next->pro->relu == xpr.relu,
+                  "%s: the X prologue and the next BatchNorm's prologue must agree", what);
+    const int rc = mmg_next_bn_dev(next, M, N, what, &nb, &partial);
+    if (rc) return rc;
+  }
+  void* const ws = wg->ws;
+  const size_t ws_bytes = wg->ws_bytes, need = mmg_linear_dgrad_wgrad_ws_bytes(M, N, K);
+  MMG_CHECK_WS(what, need);
+  float* slab = MmgCarver(ws).take<float>((need - 256) / sizeof(float));
+  const int64_t stride = (int64_t)K * N;
+  const int n_split = plan_wgrad(M, K, N).n_split;
+  const DgWgDev wd{wg->X, xpr, slab, stride};
+  const bool has_pro = xpr.scale || xpr.relu;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = next ? launch_dgrad_wgrad<true>(dY, W, dX, M, nb, partial, wd, n_split, has_pro, st)
+                : launch_dgrad_wgrad<false>(dY, W, dX, M, nb, nullptr, wd, n_split, has_pro, st);
+  if (rc) return rc;
+  MMG_CHECK_LAUNCH(what);
+  if (next) {
+    rc = mmg_next_bn_finish(next, partial, N, n_split, st);
+    if (rc) return rc;
+  }
+  if (job) {                        // the caller sums the slabs later, together with those of other layers
+    job->slab = slab; job->n4 = stride / 4; job->n_split = n_split;
+  } else {                          // the launch of mmg_linear_wgrad(dY, X, ., dW, NULL, M, K, N, ...): the same sum, the same probe row
+    MMG_LAUNCH(MMG_PROBE_LINEAR_WGRAD_REDUCE, M, K, N, 0, (mmg_k_reduce_slabs<EpiStore>),
+               dim3((unsigned)((stride / 4 + 15) / 16)), dim3(256), 0, st, slab, stride / 4, n_split,
+               EpiStore{wg->dW, wg->accumulate, nullptr, (int64_t)K * N / 4});
+    MMG_CHECK_LAUNCH(what);
+  }
+  return MMG_OK;
 }
 
 namespace {

@@ -107,6 +107,19 @@ def set_dual_enc(on: bool):
     DUAL_ENC = bool(on)
 
 
+# The first layer of a pair head: its data gradient (gradient of the patient table . W1a) and its weight gradient read the
+# same two tensors; one launch serves both (ops.linear_dgrad_wgrad), bit for bit the two launches (the next BatchNorm's
+# statistics of the "heads" site are then summed per weight-gradient workgroup: last-bit differences in fp64).
+# set_fused_head_wgrad(False) restores the two launches.
+FUSED_HEAD_WGRAD = True
+
+
+def set_fused_head_wgrad(on: bool):
+    """True (default) | False -- see FUSED_HEAD_WGRAD (the tests switch it)."""
+    global FUSED_HEAD_WGRAD
+    FUSED_HEAD_WGRAD = bool(on)
+
+
 def _mangle(et: EdgeType) -> str:
     return "<" + "___".join(et) + ">"
 
@@ -1524,7 +1537,7 @@ class _Run:
             tA = heads[w].A
             dA[w] = flat[oa:oa + tA.numel()].view(tA.shape)
             oa += tA.numel()
-        gs, join = {}, []
+        gs, join, fused_gp = {}, [], {}
         for which, src, want_low in order:
             hr = rec[which]
             xP, w1a = hr.xP, hr.w1a
@@ -1540,7 +1553,16 @@ class _Run:
             self.acc(f"{which}.mlp.6.bias", g.b3, partial=True)
             # first-layer weight / bias gradients from this shard's pairs only (the LOCAL dA and dB): per-shard partial
             # sums like every other parameter gradient, summed by the one bucket at the end of the backward
-            if isinstance(xP, _LazyAct):
+            lazy = isinstance(xP, _LazyAct)
+            if FUSED_HEAD_WGRAD and ops.linear_dgrad_wgrad_supported(xP.shape[0], D, w1a.shape[0], xP.pro.p if lazy else 0.0):
+                # the data gradient of the same layer in the same launch (the second loop below picks it up); the high
+                # head's also sums the statistics of the BatchNorm backward that consumes it, as its own GEMM would
+                fw = ops.FusedWgrad(xP.y, pro=xP.pro) if lazy else ops.FusedWgrad(xP)
+                nbn = (ops.NextBN(xP.y, xP.pro, xP.fold)
+                       if lazy and not want_low and xP.fold is not None and "heads" in self.next_bn_sites else None)
+                fused_gp[which] = ops.linear_dgrad_wgrad(g.A, w1a, fw, next_bn=nbn)
+                dW1a = fw.dW
+            elif lazy:
                 dW1a = ops.linear_wgrad(g.A, xP.y, xP.pro)
             elif xP.shape[0]:
                 dW1a = ops.linear_wgrad(g.A, xP)
@@ -1557,7 +1579,15 @@ class _Run:
             hr, g = rec[which], gs[which]
             xP, w1a, w1b, low_rows = hr.xP, hr.w1a, hr.w1b, ls.low_rows
             glab = ops.linear_fwd(g.B, w1b, w_kn=True)
-            if want_low:                         # gradient rows of the low-degree patients only: (row ids, rows)
+            if which in fused_gp:                # came with the weight gradient above
+                gP = fused_gp[which]
+                if want_low:
+                    gsets[which] = {ROW_TYPE: (low_rows, gP), "lab": glab}
+                elif isinstance(gP, tuple):
+                    gsets[which] = {ROW_TYPE: gP[0], "lab": glab, BN_SUMS: gP[1]}
+                else:
+                    gsets[which] = {ROW_TYPE: gP, "lab": glab}
+            elif want_low:                       # gradient rows of the low-degree patients only: (row ids, rows)
                 if xP.shape[0]:
                     gP = (low_rows, ops.linear_fwd(g.A, w1a, w_kn=True))
                 elif self.comm is not None:

@@ -163,7 +163,7 @@ PROBE_NAME_LEN = _lib.MMG_PROBE_NAME_LEN
 
 
 def probe_read(cap: int = 1 << 16):
-    """-> list of (ms, family name, M, N, K, flags, kernel symbol) of the probed launches (flags: 1 accumulate, 4 prologue, 8 rowscale, 16 BatchNorm backward staged in the GEMM, 32 L2-norm epilogue, 64 L2-norm backward staged, 128 two upstream gradients, 256 row-list upstream gradient, 2048 the dual linear forward: N = both outputs)."""
+    """-> list of (ms, family name, M, N, K, flags, kernel symbol) of the probed launches (flags: 1 accumulate, 4 prologue, 8 rowscale, 16 BatchNorm backward staged in the GEMM, 32 L2-norm epilogue, 64 L2-norm backward staged, 128 two upstream gradients, 256 row-list upstream gradient, 2048 the dual linear forward: N = both outputs, 4096 the weight gradient rides along the data gradient: linear_dgrad_wgrad)."""
     import numpy as np
     ms = np.zeros(cap, np.float32); tag = np.zeros(cap, np.int32); M = np.zeros(cap, np.int64)
     N = np.zeros(cap, np.int32); K = np.zeros(cap, np.int32); fl = np.zeros(cap, np.int32)
@@ -729,6 +729,34 @@ def _fused_wgrad_done(fw: FusedWgrad, t):
 
 def _fused_wgrad_bytes(M: int, N: int, K: int) -> int:      # x read once, one slab per workgroup written
     return 4 * M * N + 4 * int(_lib.load().mmg_linear_bnbwd_wgrad_ws_bytes(M, N, K))
+
+
+def linear_dgrad_wgrad_supported(M: int, N: int, K: int, p: float = 0.0) -> bool:
+    """p: the dropout of the layer input's prologue (the fused launch takes none)."""
+    return bool(_lib.load().mmg_linear_dgrad_wgrad_supported(int(M), int(N), int(K), float(p)))
+
+
+def linear_dgrad_wgrad(dy: torch.Tensor, W: torch.Tensor, wgrad: FusedWgrad, next_bn: Optional["NextBN"] = None):
+    """The data gradient and the weight gradient of a plain linear in one launch (mmg_linear_dgrad_wgrad): dx [M,N] =
+    dy [M,K] @ W [K,N] (the forward weight, read in place) and wgrad.dW [K,N] (+)= dy^T @ pro(x) -- bit for bit
+    linear_fwd(dy, W, w_kn=True) and linear_wgrad(dy, wgrad.x, wgrad.pro, wgrad.out, wgrad.accumulate, defer=wgrad.defer).
+    next_bn: + the statistics of the BatchNorm backward that consumes dx, from the epilogue; next_bn.y is wgrad.x and
+    next_bn.pro agrees with wgrad.pro.  -> dx, or (dx, sums) with next_bn; the call fills wgrad.dW.  No bias gradient."""
+    M, K = dy.shape
+    if W.shape[0] != K:
+        raise ValueError(f"linear_dgrad_wgrad: W has {W.shape[0]} rows, dy has {K} columns")
+    if wgrad.with_bias:
+        raise ValueError("linear_dgrad_wgrad: no bias gradient")
+    N = W.shape[1]
+    dx = torch.empty(M, N, dtype=torch.float32, device=dy.device)
+    _tok = _pb("linear_dgrad_wgrad")
+    nbt, nsums = _next_bn(next_bn, M, N) if next_bn is not None else (None, None)
+    wt = _fused_wgrad(wgrad, M, N, K)
+    _call("mmg_linear_dgrad_wgrad", dy, W, dx, M, N, K, C.byref(nbt) if nbt is not None else None, C.byref(wt),
+          names={"dY": "dy", "dX": "dx"})
+    _fused_wgrad_done(wgrad, wt)
+    _pe(_tok, "linear_dgrad_wgrad", 4 * (M * K + K * N + M * N) + _fused_wgrad_bytes(M, N, K), 4 * M * N * K)
+    return (dx, nsums) if next_bn is not None else dx
 
 
 # mode -> (profiler name, [M,K] tensors the kernel reads): g and y; g, g2 and y; y (the listed rows are not counted);
