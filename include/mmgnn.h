@@ -683,6 +683,10 @@ int mmg_adam_step(float* p, float* m, float* v, const float* const* grads, const
  * the caller refreshes `hyper` between replays instead. */
 int mmg_adam_step_dev(float* p, float* m, float* v, const float* const* grads, const int32_t* offsets, int n_tensors,
                       const float* hyper, float* step, uint32_t* ticket, void* stream);
+/* mmg_adam_step_dev's update launches WITHOUT the one-thread launch that advances `step`: the caller advances it behind
+ * them, with mmg_step_advance. */
+int mmg_adam_update_dev(float* p, float* m, float* v, const float* const* grads, const int32_t* offsets, int n_tensors,
+                        const float* hyper, float* step, void* stream);
 typedef struct {
   float* dst;
   const float* src[4];
@@ -693,9 +697,36 @@ typedef struct {
   int ld_src[4];           /* row stride of every source */
 } mmg_sum_job_t;
 int mmg_vec_sums(const mmg_sum_job_t* jobs, int n_jobs, void* stream);
+/* Everything that finishes the gradients of a step, in ONE launch: the slab sums of mmg_wgrad_reduce_group, the sums of
+ * further contributions of mmg_vec_sums, and the placement of a sum inside a wider matrix -- described with the job
+ * types of those two calls.  One job = one destination; per element, in this order:
+ *   (a) `series`, in list order: an entry is summed as mmg_wgrad_reduce_group sums it (16 slab groups, group g adds its
+ *       slabs g, g + 16, ... in turn, then part[0] + ... + part[15]) and stored, or added to its dW with `accumulate`.  A
+ *       later entry with the same dW (and n4, nk4, dbias; accumulate != 0; up to MMG_GRAD_FINISH_SERIES entries per dW) is
+ *       a further series of that job: its finished sum is added to the value -- what one launch per entry gives.
+ *   (b) `sums`, mmg_vec_sums jobs.  A sum whose src[0] is EXACTLY the dW of a series job (len = 4 * nk4, n_src <= 4, at
+ *       most one such sum per dW) belongs to that job: value = (a) + src[1] + src[2] + src[3], in mmg_vec_sums' order, and
+ *   (c) the store goes to the sum's dst with its cols / ld_dst -- dW itself when dst == dW, else a column slice of a
+ *       wider matrix, and dW is then NOT written (nobody may read it); the dbias tail goes to dbias either way.  With
+ *       slabs, addresses, cols and strides are multiples of four elements.  Every other sum is a job of its own, as in
+ *       mmg_vec_sums (any length, any alignment).
+ * The jobs of a launch run concurrently: a job that reads what another job writes (or a dW left unwritten), and two jobs
+ * whose destinations overlap, are refused with MMG_E_ARG before anything is launched (such a job belongs in a later
+ * launch); column slices of one matrix with the same row stride are told apart.  More than MMG_GRAD_FINISH_MAX jobs (the
+ * table travels by value in the kernarg segment) take several launches, and the rule holds across them.  NULL
+ * destinations, sources or slabs are refused. */
+#define MMG_GRAD_FINISH_MAX 24
+#define MMG_GRAD_FINISH_SERIES 4
+int mmg_grad_finish_group(const mmg_wgrad_reduce_t* series, int n_series, const mmg_sum_job_t* sums, int n_sums,
+                          void* stream);
 #define MMG_COUNTERS_MAX 32
 int mmg_counters_add(int64_t* const* counters, const int64_t* incs, int n, void* stream);
 int mmg_seed_advance(uint64_t* state /* [2]: seed | stream position */, void* stream);
+/* The one-thread updates that end a captured training step, in ONE launch: *adam_step += 1 (what mmg_adam_step* launch
+ * behind their update), mmg_seed_advance(seed_state) and mmg_counters_add(counters, incs, n_counters).  adam_step NULL,
+ * seed_state NULL, n_counters 0: that part is left out. */
+int mmg_step_advance(float* adam_step, uint64_t* seed_state, int64_t* const* counters, const int64_t* incs, int n_counters,
+                     void* stream);
 int mmg_fill_zero(void* ptr, size_t bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------

@@ -107,11 +107,24 @@ __global__ void k_seed_advance(uint64_t* state) {
   state[0] = (z ^ (z >> 31)) >> 2;
 }
 
+// the three one-thread updates of a captured step's state in one launch: k_adam_bump, k_seed_advance, k_counters_add
+__global__ void k_step_advance(float* __restrict__ step, uint64_t* __restrict__ seed, CounterTable tb) {
+  const int i = threadIdx.x;
+  if (i < tb.n) *tb.p[i] += tb.inc[i];
+  if (i == 0 && step) *step += 1.f;
+  if (i == 0 && seed) {
+    uint64_t z = (seed[1] += 0x9E3779B97F4A7C15ull);                  // SplitMix64
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    seed[0] = (z ^ (z >> 31)) >> 2;
+  }
+}
+
 }  // namespace
 
 static int adam_launch(float* p, float* m, float* v, const float* const* grads, const int32_t* offsets, int n_tensors,
                        float lr, float beta1, float beta2, float eps, float weight_decay, const float* hyper, float* step,
-                       uint32_t* ticket, void* stream) {
+                       uint32_t* ticket, void* stream, bool bump = true) {
   MMG_CHECK_ARG(p && m && v && grads && offsets && step && ticket, "adam_step: null buffer");
   MMG_CHECK_ARG(n_tensors >= 1, "adam_step: no tensors");
   hipStream_t st = (hipStream_t)stream;
@@ -129,7 +142,7 @@ static int adam_launch(float* p, float* m, float* v, const float* const* grads, 
     if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(k_adam, dim3(nb), dim3(256), 0, st, tb, p, m, v, lr, beta1, beta2, eps, weight_decay, hyper, step);
   }
-  hipLaunchKernelGGL(k_adam_bump, dim3(1), dim3(1), 0, st, step);       // every launch above read the same t
+  if (bump) hipLaunchKernelGGL(k_adam_bump, dim3(1), dim3(1), 0, st, step);       // every launch above read the same t
   MMG_CHECK_LAUNCH("adam_step");
   return MMG_OK;
 }
@@ -144,6 +157,13 @@ extern "C" int mmg_adam_step_dev(float* p, float* m, float* v, const float* cons
                                  int n_tensors, const float* hyper, float* step, uint32_t* ticket, void* stream) {
   MMG_CHECK_ARG(hyper, "adam_step_dev: null hyper-parameter buffer");
   return adam_launch(p, m, v, grads, offsets, n_tensors, 0.f, 0.f, 0.f, 0.f, 0.f, hyper, step, ticket, stream);
+}
+
+extern "C" int mmg_adam_update_dev(float* p, float* m, float* v, const float* const* grads, const int32_t* offsets,
+                                   int n_tensors, const float* hyper, float* step, void* stream) {
+  MMG_CHECK_ARG(hyper, "adam_update_dev: null hyper-parameter buffer");
+  uint32_t unused = 0;             // (`ticket` is checked for NULL only)
+  return adam_launch(p, m, v, grads, offsets, n_tensors, 0.f, 0.f, 0.f, 0.f, 0.f, hyper, step, &unused, stream, false);
 }
 
 extern "C" int mmg_vec_sums(const mmg_sum_job_t* jobs, int n_jobs, void* stream) {
@@ -196,6 +216,22 @@ extern "C" int mmg_seed_advance(uint64_t* state, void* stream) {
   MMG_CHECK_ARG(state, "seed_advance: null state");
   hipLaunchKernelGGL(k_seed_advance, dim3(1), dim3(1), 0, (hipStream_t)stream, state);
   MMG_CHECK_LAUNCH("seed_advance");
+  return MMG_OK;
+}
+
+extern "C" int mmg_step_advance(float* adam_step, uint64_t* seed_state, int64_t* const* counters, const int64_t* incs,
+                                int n_counters, void* stream) {
+  MMG_CHECK_ARG(n_counters >= 0 && n_counters <= MMG_COUNTERS_MAX, "step_advance: 0..%d counters", MMG_COUNTERS_MAX);
+  MMG_CHECK_ARG(n_counters == 0 || (counters && incs), "step_advance: null table");
+  if (!adam_step && !seed_state && n_counters == 0) return MMG_OK;
+  CounterTable tb;
+  tb.n = n_counters;
+  for (int i = 0; i < n_counters; ++i) {
+    MMG_CHECK_ARG(counters[i], "step_advance: counter %d is null", i);
+    tb.p[i] = counters[i]; tb.inc[i] = incs[i];
+  }
+  hipLaunchKernelGGL(k_step_advance, dim3(1), dim3(64), 0, (hipStream_t)stream, adam_step, seed_state, tb);
+  MMG_CHECK_LAUNCH("step_advance");
   return MMG_OK;
 }
 

@@ -107,6 +107,19 @@ def set_dual_enc(on: bool):
     DUAL_ENC = bool(on)
 
 
+# Everything that only finishes a gradient -- the deferred slab sums of the big weight gradients, the second accumulating
+# contribution to one of them, the sums of a parameter's further contributions, the slab sums of the heads' dW1a and the
+# [dW1a | dW1b] join of both heads -- runs in one launch at the end of the backward (ops.grad_finish), every element in the
+# order of additions the separate launches give it.  set_grad_finish(False) restores those launches.
+GRAD_FINISH = True
+
+
+def set_grad_finish(on: bool):
+    """True (default) | False -- see GRAD_FINISH (the tests switch it)."""
+    global GRAD_FINISH
+    GRAD_FINISH = bool(on)
+
+
 # The first layer of a pair head: its data gradient (gradient of the patient table . W1a) and its weight gradient read the
 # same two tensors; one launch serves both (ops.linear_dgrad_wgrad), bit for bit the two launches (the next BatchNorm's
 # statistics of the "heads" site are then summed per weight-gradient workgroup: last-bit differences in fp64).
@@ -507,6 +520,9 @@ class _StepFn(torch.autograd.Function):
 
 
 class _Run:
+    grad_finish = False              # (a run takes GRAD_FINISH when it is set up; without one the separate launches)
+    defer_counters = None            # a list: run_forward leaves the BatchNorm counters [buffer, increment] there
+
     def __init__(self, model: HeteroRGCN, data):
         self.m = model
         self.dev = next(model.parameters()).device
@@ -531,6 +547,8 @@ class _Run:
         self._nbt = {}               # BatchNorm step counters to advance: {id(module): [buffer, increment]}
         self.pending = {}            # parameter name -> further gradient contributions, summed at the end of the backward
         self.wgrad_jobs = []         # deferred slab sums of the big weight gradients: one launch at the end of the backward
+        self.finish_sums = []        # (dst, [sources]) sums that launch takes along (GRAD_FINISH: the heads' dW1 joins)
+        self.grad_finish = GRAD_FINISH
         # (sel_low, sel_high, counts) of the pairs the backward must visit, when the caller knows them in advance (a
         # captured step with a per-epoch supervision mask: train.PiecewiseGraphedTrainStep); None: selected from dpred != 0
         self.static_select = None
@@ -588,9 +606,28 @@ class _Run:
         contribution recorded by acc(), all parameters in ONE mmg_vec_sums launch per 8.  The sum goes to a NEW tensor:
         grads[name] may be shared (dWsum serves three lin_r names) or belong to the caller (an autograd grad_output in
         encode / forward mode).  More than three further contributions chain: each level reads the previous level's
-        result, so levels are separate launches (jobs of one launch run concurrently)."""
-        ops.wgrad_reduce_flush(self.wgrad_jobs)
+        result, so levels are separate launches (jobs of one launch run concurrently).
+        GRAD_FINISH: the slab sums, the first level of those sums and the joins heads_bwd left in finish_sums share ONE
+        launch (ops.grad_finish); a gradient that is the destination of a slab sum and belongs to one name alone takes its
+        further contributions inside that job, in place."""
         levels: List[list] = []
+        if not self.grad_finish:
+            ops.wgrad_reduce_flush(self.wgrad_jobs)
+        else:
+            first = self.finish_sums
+            self.finish_sums = []
+            outs = {id(e[2]) for e in self.wgrad_jobs if len(e) == 4}
+            for name, more in self.pending.items():
+                cur = self.grads[name]
+                srcs = [cur] + [m.reshape(cur.shape) for m in more[:3]]
+                if id(cur) in outs and sum(1 for g in self.grads.values() if g is cur) == 1:
+                    first.append((cur, srcs))         # ours alone, and complete only after this launch: in place
+                else:
+                    dst = torch.empty_like(cur, memory_format=torch.contiguous_format)
+                    first.append((dst, srcs))
+                    self.grads[name] = dst
+                self.pending[name] = more[3:]
+            ops.grad_finish(self.wgrad_jobs, first)
         for name, more in self.pending.items():
             cur, lvl = self.grads[name], 0
             more = [m.reshape(cur.shape) for m in more]
@@ -650,7 +687,9 @@ class _Run:
     # ======================================================================== forward driver
     def _bump_counters(self):
         ents = [e for e in self._nbt.values() if e[1]]
-        if ents:                                         # every num_batches_tracked buffer in ONE launch
+        if self.defer_counters is not None:              # the caller advances them at the end of its step (nothing
+            self.defer_counters += ents                  # reads them before): train.PiecewiseGraphedTrainStep
+        elif ents:                                       # every num_batches_tracked buffer in ONE launch
             ops.counters_add([b for b, _ in ents], [i for _, i in ents])
         self._nbt = {}
 
@@ -1554,26 +1593,36 @@ class _Run:
             # first-layer weight / bias gradients from this shard's pairs only (the LOCAL dA and dB): per-shard partial
             # sums like every other parameter gradient, summed by the one bucket at the end of the backward
             lazy = isinstance(xP, _LazyAct)
+            # GRAD_FINISH: the slabs of dW1a stay where the GEMM left them; the launch at the end of the backward sums them
+            # straight into dW1[:, :D] (nobody reads dW1 before the optimizer)
+            hold = [] if self.grad_finish else None
             if FUSED_HEAD_WGRAD and ops.linear_dgrad_wgrad_supported(xP.shape[0], D, w1a.shape[0], xP.pro.p if lazy else 0.0):
                 # the data gradient of the same layer in the same launch (the second loop below picks it up); the high
                 # head's also sums the statistics of the BatchNorm backward that consumes it, as its own GEMM would
-                fw = ops.FusedWgrad(xP.y, pro=xP.pro) if lazy else ops.FusedWgrad(xP)
+                fw = ops.FusedWgrad(xP.y, pro=xP.pro, defer=hold) if lazy else ops.FusedWgrad(xP, defer=hold)
                 nbn = (ops.NextBN(xP.y, xP.pro, xP.fold)
                        if lazy and not want_low and xP.fold is not None and "heads" in self.next_bn_sites else None)
                 fused_gp[which] = ops.linear_dgrad_wgrad(g.A, w1a, fw, next_bn=nbn)
                 dW1a = fw.dW
             elif lazy:
-                dW1a = ops.linear_wgrad(g.A, xP.y, xP.pro)
+                dW1a = ops.linear_wgrad(g.A, xP.y, xP.pro, defer=hold)
             elif xP.shape[0]:
-                dW1a = ops.linear_wgrad(g.A, xP)
+                dW1a = ops.linear_wgrad(g.A, xP, defer=hold)
             else:
                 dW1a = ops.zeros(*w1a.shape, device=self.dev)
             dW1b, db1 = ops.linear_wgrad(g.B, src["lab"], with_bias=True)
             dW1 = torch.empty(w1a.shape[0], 2 * D, device=self.dev)
-            join += [(dW1[:, :D], [dW1a]), (dW1[:, D:], [dW1b])]
+            if hold and hold[0][0].slab:         # (no slabs: a small launch wrote dW1a itself)
+                self.wgrad_jobs.append(hold[0] + (dW1[:, :D],))
+                join += [(dW1[:, D:], [dW1b])]
+            else:
+                join += [(dW1[:, :D], [dW1a]), (dW1[:, D:], [dW1b])]
             self.acc(f"{which}.mlp.0.weight", dW1, partial=True)
             self.acc(f"{which}.mlp.0.bias", db1, partial=True)
-        ops.vec_sums(join)                       # [dW1a | dW1b] of both heads: one launch
+        if self.grad_finish:
+            self.finish_sums += join             # [dW1a | dW1b] of both heads: jobs of the launch that ends the backward
+        else:
+            ops.vec_sums(join)                   # [dW1a | dW1b] of both heads: one launch
         self.allreduce(flat[:n_b])               # lab-side partials dB of both heads from the sharded pairs
         for which, src, want_low in order:
             hr, g = rec[which], gs[which]

@@ -505,6 +505,8 @@ def wgrad_reduce_flush(jobs: list):
     """Sum the slabs of every deferred weight gradient (linear_wgrad(defer=...)): one launch per <= MMG_WGRAD_REDUCE_MAX
     jobs; a job that accumulates into a gradient an earlier job of the list writes goes into a later launch.  Empties the
     list."""
+    if any(len(j) > 4 for j in jobs):        # an entry that lands in a view of a wider matrix: grad_finish places it
+        return grad_finish(jobs)
     todo = [j for j in jobs if j[0].slab]
     jobs.clear()
     while todo:
@@ -518,6 +520,113 @@ def wgrad_reduce_flush(jobs: list):
         arr = (WgradReduceT * len(group))(*[j[0] for j in group])
         _call("mmg_wgrad_reduce_group", arr, len(group))
         todo = later
+
+
+def _span(t: torch.Tensor):
+    """[first byte, one past the last byte) of the storage a tensor's elements lie in (the hull of a strided view)."""
+    if t.numel() == 0:
+        return t.data_ptr(), t.data_ptr()
+    last = sum((s - 1) * st for s, st in zip(t.shape, t.stride()))
+    return t.data_ptr(), t.data_ptr() + (last + 1) * t.element_size()
+
+
+def grad_finish(wjobs: list, sums=()):
+    """Everything that finishes the gradients of a step in as few launches as its dependencies allow (mmg_grad_finish_group),
+    bit for bit wgrad_reduce_flush(wjobs) followed by vec_sums(sums).  Empties wjobs.
+    wjobs: the deferred weight gradients (linear_wgrad(defer=...) entries; a fifth element is the 2-D view the sum lands in
+    instead of the entry's `out`, a column slice of a wider matrix).  An accumulating entry on the gradient of an earlier
+    one becomes a further slab series of that job.
+    sums: (dst, [sources, 1..4]) as vec_sums takes them.  dst is sources[0] = the `out` of an entry: the further sources
+    are added by that entry's job, in place.  A sum that reads what a job of the launch writes goes into the next launch."""
+    SER = _lib.MMG_GRAD_FINISH_SERIES
+    fjs = []                                  # [dst ptr, entry, series [(slab, n_split)], level, dense sources, view]
+    last = {}                                 # destination address -> its latest job
+    for ent in wjobs:
+        job = ent[0]
+        if not job.slab:
+            continue
+        view = ent[4] if len(ent) > 4 else None
+        key = view.data_ptr() if view is not None else job.dW
+        prev = last.get(key)
+        if (prev is not None and job.accumulate and len(prev[2]) < SER and prev[5] is None and view is None and not prev[4]
+                and (prev[1][0].n4, prev[1][0].nk4, prev[1][0].dbias) == (job.n4, job.nk4, job.dbias)):
+            prev[2].append((job.slab, job.n_split))
+            continue
+        fj = [key, ent, [(job.slab, job.n_split)], prev[3] + 1 if prev is not None else 0, [], view]
+        fjs.append(fj)
+        last[key] = fj
+    wjobs_keep = list(wjobs)                  # (the slabs live until the launches below are enqueued)
+    wjobs.clear()
+
+    def writes(fj):
+        ent = fj[1]
+        spans = [_span(fj[5] if fj[5] is not None else ent[2])]
+        if ent[3] is not None:
+            spans.append(_span(ent[3]))
+        return spans
+
+    dense = []                                # (dst, sources, level)
+    for dst, srcs in sums:
+        if not 1 <= len(srcs) <= 4:
+            raise ValueError("grad_finish: 1..4 sources per sum")
+        if any(t.numel() != dst.numel() for t in srcs):
+            raise ValueError("grad_finish: size mismatch")
+        host = None
+        if dst is srcs[0]:
+            host = next((f for f in fjs if f[5] is None and f[1][2] is dst and last[f[0]] is f), None)
+        rest = srcs[1:] if host is not None else srcs
+        lvl, read = 0, [_span(t) for t in rest]
+        for f in fjs:
+            if any(a0 < s1 and s0 < a1 for a0, a1 in writes(f) for s0, s1 in read):
+                lvl = max(lvl, f[3] + 1)
+        ok = (host is not None and lvl <= host[3] and dst.is_contiguous() and dst.numel() == 4 * host[1][0].nk4
+              and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in rest))
+        if ok:
+            host[4] = list(rest)
+        else:
+            if host is not None:                       # in place behind the job that writes dst
+                lvl = max(lvl, host[3] + 1)
+            dense.append((dst, list(srcs), lvl))
+    n_lvl = max([f[3] for f in fjs] + [d[2] for d in dense], default=-1) + 1
+    for lvl in range(n_lvl):
+        group = [f for f in fjs if f[3] == lvl]
+        dgroup = [d for d in dense if d[2] == lvl]
+        series, sjobs = [], []
+        for f in group:
+            job, view = f[1][0], f[5]
+            series.append(job)
+            for slab, n_split in f[2][1:]:               # the accumulating entries that joined it
+                series.append(WgradReduceT(slab, job.n4, n_split, job.dW, job.dbias, job.nk4, 1))
+            if view is None and not f[4]:
+                continue
+            # a sum whose first source is the job's dW: the value takes the further sources and lands in the sum's dst
+            sp, ld, cols, ld_dst, dst = (C.c_void_p * 4)(), (C.c_int * 4)(), 0, 0, job.dW
+            if view is not None:
+                if view.dim() != 2 or view.stride(1) != 1 or view.numel() != 4 * job.nk4:
+                    raise ValueError("grad_finish: the destination view must be 2-D with unit column stride and the gradient's size")
+                cols, ld_dst, dst = view.shape[1], view.stride(0), _p(view, name="", contiguous=False)
+            sp[0], ld[0] = job.dW, cols
+            for q, sct in enumerate(f[4], 1):
+                sp[q], ld[q] = _p(sct, name=""), cols
+            sjobs.append(SumJobT(dst, sp, 1 + len(f[4]), 4 * job.nk4, cols, ld_dst, ld))
+        for dst, srcs, _ in dgroup:
+            views = [_rows_view(x) for x in [dst] + srcs]
+            strided = any(c for c, _ in views)
+            cols = 0
+            if strided:
+                if dst.dim() != 2 or any(x.shape != dst.shape for x in srcs):
+                    raise ValueError("grad_finish: strided sums take 2-D tensors of one shape")
+                cols = dst.shape[1]
+            sp, ld = (C.c_void_p * 4)(), (C.c_int * 4)()
+            for q, sct in enumerate(srcs):
+                sp[q] = _p(sct, name="", contiguous=False)
+                ld[q] = (views[q + 1][1] or cols) if strided else 0
+            sjobs.append(SumJobT(_p(dst, name="", contiguous=False), sp, len(srcs), dst.numel(), cols,
+                                 (views[0][1] or cols) if strided else 0, ld))
+        if series or sjobs:
+            _call("mmg_grad_finish_group", (WgradReduceT * max(len(series), 1))(*series), len(series),
+                  (SumJobT * max(len(sjobs), 1))(*sjobs), len(sjobs))
+    del wjobs_keep
 
 
 def col_reduce2(a: torch.Tensor, b: Optional[torch.Tensor] = None):
@@ -1139,6 +1248,19 @@ def counters_add(counters, incs):
 def seed_advance(state: torch.Tensor):
     """state: int64 [2] on the device = (dropout seed the kernels read, stream position); one SplitMix64 step."""
     _call("mmg_seed_advance", state)
+
+
+def step_advance(adam_steps=(), seed_state: Optional[torch.Tensor] = None, counters=(), incs=()):
+    """The one-thread updates that end a captured training step in ONE launch (mmg_step_advance): every optimizer step
+    counter += 1 (float device scalars), seed_advance(seed_state), counters_add(counters, incs).  More than one step
+    counter, or more than MMG_COUNTERS_MAX counters, take further launches."""
+    steps, cmax = list(adam_steps), _lib.MMG_COUNTERS_MAX
+    n_calls = max(len(steps), (len(counters) + cmax - 1) // cmax, 1 if seed_state is not None else 0)
+    for i in range(n_calls):
+        cs, ins = counters[i * cmax:(i + 1) * cmax], incs[i * cmax:(i + 1) * cmax]
+        ptrs = (C.c_void_p * max(len(cs), 1))(*[_p(c, torch.int64) for c in cs])
+        inc = (C.c_int64 * max(len(cs), 1))(*[int(v) for v in ins])
+        _call("mmg_step_advance", steps[i] if i < len(steps) else None, seed_state if i == 0 else None, ptrs, inc, len(cs))
 
 
 def zeros(*shape, device, dtype=torch.float32):

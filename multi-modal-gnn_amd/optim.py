@@ -85,8 +85,14 @@ class Adam(torch.optim.Adam):
             if fl is not None:
                 self._upload_hyper(group, fl)
 
+    def step_counters(self):
+        """The device step counter of every non-empty parameter group (what step(bump=False) leaves to the caller)."""
+        return [fl["step"] for fl in self._flat if fl is not None]
+
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, bump=True):
+        """bump=False: the update launches alone (mmg_adam_update_dev); the caller advances step_counters() behind them
+        (ops.step_advance: one launch together with the dropout seed and the BatchNorm counters of a captured step)."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -107,8 +113,11 @@ class Adam(torch.optim.Adam):
                     raise _lib.MmgError("mmgnn.optim.Adam: gradients must be contiguous fp32 device tensors")
                 gp[i] = g.data_ptr()
             self._upload_hyper(group, fl)
-            _call("mmg_adam_step_dev", fl["p"], fl["m"], fl["v"], gp, fl["offs"], len(ps), fl["hyper"], fl["step"],
-                  fl["ticket"])
+            if bump:
+                _call("mmg_adam_step_dev", fl["p"], fl["m"], fl["v"], gp, fl["offs"], len(ps), fl["hyper"], fl["step"],
+                      fl["ticket"])
+            else:
+                _call("mmg_adam_update_dev", fl["p"], fl["m"], fl["v"], gp, fl["offs"], len(ps), fl["hyper"], fl["step"])
         return loss
 
     def load_state_dict(self, state_dict):

@@ -615,6 +615,19 @@ class _Recording:
         self.comm = None
 
 
+# The hand-driven captured step ends with ONE one-thread launch (ops.step_advance) that advances the optimizer's step
+# counter, the dropout seed and the BatchNorm counters of the forward, instead of one launch each (the counters' sat between
+# the heads' forward and the loss).  The three pieces of state are what the separate launches leave.
+# set_step_advance(False) restores them.
+STEP_ADVANCE = True
+
+
+def set_step_advance(on: bool):
+    """True (default) | False -- see STEP_ADVANCE (the tests switch it)."""
+    global STEP_ADVANCE
+    STEP_ADVANCE = bool(on)
+
+
 class GraphedTrainStep:
     """One whole training step -- zero_grad, predict_lab_values, weighted loss, backward, optimizer.step --
     captured ONCE into a hipGraph and replayed per epoch (the eICU-scale graph is launch-bound: ~250 kernel
@@ -802,6 +815,10 @@ class PiecewiseGraphedTrainStep:
             run.lists_ready = self._sel_ready
             if self.supervised_heads_only:
                 run.forward_select = self._sel
+            # STEP_ADVANCE: the BatchNorm counters wait for the one launch behind the optimizer (nothing in the step reads them)
+            one = STEP_ADVANCE and hasattr(self.opt, "step_counters")
+            if one:
+                run.defer_counters = []
             (pred,) = run.run_forward("predict")
             self.pred = pred
             loss, dpred = ops.pair_loss(pred, self.y, self.wl, self.sup, 1.0, self.loss_fn, self._sv.inv_den,
@@ -812,8 +829,13 @@ class PiecewiseGraphedTrainStep:
             for p, g in zip(self.params, grads):
                 if g is not None:
                     p.grad = g
-            self.opt.step()
-            ops.seed_advance(model._seed_dev)        # fresh dropout masks for the next replay, drawn on the device
+            if one:                                  # step counter, dropout seed and BatchNorm counters: one launch
+                self.opt.step(bump=False)
+                ents = run.defer_counters
+                ops.step_advance(self.opt.step_counters(), model._seed_dev, [b for b, _ in ents], [i for _, i in ents])
+            else:
+                self.opt.step()
+                ops.seed_advance(model._seed_dev)    # fresh dropout masks for the next replay, drawn on the device
             self.loss = loss                         # fp64 scalar in the graph's pool: the same address at every replay
 
     def _draw_and_select(self):
