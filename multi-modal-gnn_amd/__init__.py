@@ -28,4 +28,7 @@ def __getattr__(name):
     if name in ("embedding_maps", "lab_panels", "PCAResult", "embedding_tsne", "tsne", "TSNEResult"):
         from . import embed
         return getattr(embed, name)
+    if name in ("LabConformal", "fit_conformal", "conformal_report", "impute_intervals"):
+        from . import conformal
+        return getattr(conformal, name)
     raise AttributeError(name)

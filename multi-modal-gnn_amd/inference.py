@@ -10,6 +10,9 @@ patient is assembled on the host from its row of that matrix:
   predict_for_patients  the same dicts for many patients from one forward
   lab_report            the host-side assembly of one patient's dict (no device, no model)
 
+With ``intervals=`` (a fitted ``conformal.LabConformal``) every predicted entry also carries its split-conformal
+interval; without it the dicts are the reference's.
+
 Printing, config loading and the command line of the reference script (``print_patient_report``, ``run_inference``)
 are not part of this module.
 """
@@ -50,12 +53,24 @@ def _lab_stats_rows(lab_stats, names):
 
 
 def lab_report(pred_row: np.ndarray, lab_indices: np.ndarray, values: np.ndarray, in_test: np.ndarray,
-               lab_stats, lab_indexer: Dict, stats_rows: Optional[Dict] = None) -> Dict:
+               lab_stats, lab_indexer: Dict, stats_rows: Optional[Dict] = None,
+               bounds: Optional[Tuple[np.ndarray, np.ndarray]] = None) -> Dict:
     """One patient's report, reference inference.py:107-178, from host data only.
     pred_row: [L] normalised predictions of every lab (a row of impute_lab_matrix); lab_indices / values / in_test: the
     patient's has_lab edges in edge order -- lab index, normalised value, edge in the test split.  Values are
     denormalised as value * std + mean with the lab's row of lab_stats (columns ITEMID, mean, std).
+    bounds: (lower_row, upper_row), [L] normalised interval bounds of every lab (conformal.LabConformal.predict_matrix);
+    every entry of masked_labs and truly_missing_labs then also has 'lower', 'upper' (bound * std + mean, as 'predicted'
+    is formed), 'normalized_lower' and 'normalized_upper'.
     -> {'measured_labs', 'masked_labs', 'truly_missing_labs'} with the reference's keys."""
+
+    def interval(lab_idx, lab_stat):
+        if bounds is None:
+            return {}
+        lo, hi = bounds[0][lab_idx], bounds[1][lab_idx]
+        return {'lower': float(lo * lab_stat['std'] + lab_stat['mean']), 'upper': float(hi * lab_stat['std'] + lab_stat['mean']),
+                'normalized_lower': float(lo), 'normalized_upper': float(hi)}
+
     lab_idx_to_name = {v: k for k, v in lab_indexer.items()}
     if stats_rows is None:
         stats_rows = _lab_stats_rows(lab_stats, lab_indexer.keys())
@@ -76,6 +91,7 @@ def lab_report(pred_row: np.ndarray, lab_indices: np.ndarray, values: np.ndarray
                 'normalized_predicted': float(pred),
                 'normalized_actual': float(actual)
             }
+            masked_labs[lab_name].update(interval(lab_idx, lab_stat))
         else:
             measured_labs[lab_name] = {
                 'value': float(actual_original),
@@ -94,6 +110,7 @@ def lab_report(pred_row: np.ndarray, lab_indices: np.ndarray, values: np.ndarray
             'normalized_predicted': float(pred),
             'note': 'Lab was never measured for this patient'
         }
+        truly_missing_labs[lab_name].update(interval(lab_idx, lab_stat))
     return {
         'measured_labs': measured_labs,
         'masked_labs': masked_labs,
@@ -102,12 +119,17 @@ def lab_report(pred_row: np.ndarray, lab_indices: np.ndarray, values: np.ndarray
 
 
 def predict_for_patients(patient_ids: Sequence, data, model, device, labs_df, lab_stats, masker, patient_indexer: Dict,
-                         lab_indexer: Dict) -> List[Dict]:
-    """predict_for_patient for many patients from ONE impute_lab_matrix forward -> one dict per id, in order."""
+                         lab_indexer: Dict, intervals=None) -> List[Dict]:
+    """predict_for_patient for many patients from ONE impute_lab_matrix forward -> one dict per id, in order.
+    intervals: a fitted conformal.LabConformal; the bounds of every cell come from one more streaming launch."""
     idx = [patient_indexer[str(pid)] for pid in patient_ids]
     data_device = data.to(device)
     rows = torch.tensor(idx, dtype=torch.int64, device=device)
-    pred = model.impute_lab_matrix(data_device, rows).cpu().numpy()
+    pred = model.impute_lab_matrix(data_device, rows)
+    lower = upper = None
+    if intervals is not None and idx:
+        _, lower, upper = (t.cpu().numpy() for t in intervals.predict_matrix(pred, rows))
+    pred = pred.cpu().numpy()
     if not idx:
         return []
     # the requested patients' edges, grouped by patient in edge order (torch.where(edge_index[0] == p) of the reference)
@@ -126,14 +148,14 @@ def predict_for_patients(patient_ids: Sequence, data, model, device, labs_df, la
     for i, p in enumerate(idx):
         lo, hi = np.searchsorted(e_pat, p, "left"), np.searchsorted(e_pat, p, "right")
         out.append(lab_report(pred[i], e_lab[lo:hi], e_val[lo:hi], test_mask[pos[lo:hi]], lab_stats, lab_indexer,
-                              stats_rows))
+                              stats_rows, None if lower is None else (lower[i], upper[i])))
     return out
 
 
 def predict_for_patient(patient_id: int, data, model, device, labs_df, lab_stats, masker, patient_indexer: Dict,
-                        lab_indexer: Dict) -> Dict:
+                        lab_indexer: Dict, intervals=None) -> Dict:
     """Reference inference.py:53-178 (same arguments, same result): the patient's measured labs, the labs held out in
     the test split (predicted vs actual) and the labs never measured (predicted), denormalised through lab_stats --
     from one row of impute_lab_matrix instead of two whole-graph forwards."""
     return predict_for_patients([patient_id], data, model, device, labs_df, lab_stats, masker, patient_indexer,
-                                lab_indexer)[0]
+                                lab_indexer, intervals)[0]
