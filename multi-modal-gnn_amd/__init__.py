@@ -31,4 +31,7 @@ def __getattr__(name):
     if name in ("LabConformal", "fit_conformal", "conformal_report", "impute_intervals"):
         from . import conformal
         return getattr(conformal, name)
+    if name in ("BootstrapResult", "bootstrap_metrics", "evaluate_with_intervals", "poisson_weights"):
+        from . import bootstrap
+        return getattr(bootstrap, name)
     raise AttributeError(name)
