@@ -594,6 +594,26 @@ int mmg_pair_select(const int32_t* pi, const int32_t* deg, int degree_threshold,
                     const int64_t* io_perm, float* dpred_sorted, int64_t n_pairs, int32_t* sel_low, int32_t* sel_high,
                     int32_t* counts, void* ws, size_t ws_bytes, void* stream);
 
+/* The supervision subset of a step AND the two pair lists derived from it, in two launches: what mmg_sup_mask_draw
+ * followed by mmg_pair_select(pi, deg, threshold, sup, io_perm) gives, bit for bit, without reading a mask back.
+ *   s = 0 .. n_pairs-1 (patient-sorted position):  c = io_perm ? io_perm[s] : s  (the caller's index of that pair),
+ *   e = ids ? ids[c] : c  (its id),  supervised(s) = mmg_sup_mask_draw's draw for id e with the same seed and fraction,
+ *   low(s) = deg[pi[s]] < degree_threshold
+ * sel_low / sel_high (capacity n_pairs each) receive the supervised positions of each head in increasing order, counts[2]
+ * (device) their lengths; count / inv_den (nullable, DEVICE doubles) the subset size (double)(counts[0] + counts[1]) and
+ * 1 / max(size, 1); sup (nullable, [n_pairs] float, CALLER order) the mask mmg_pair_loss reads: sup[c] = 1.0f or 0.0f.
+ * seed_ptr (nullable, DEVICE) overrides `seed` at run time; ids (nullable) as in mmg_sup_mask_draw.  pi is in sorted
+ * order, io_perm a permutation of 0 .. n_pairs-1 (or NULL: the pairs are sorted as the caller has them).
+ * Launch 1 hashes every position and leaves per-workgroup totals (and writes sup, sequentially); launch 2 scans the totals
+ * and emits the lists.  No workgroup waits for another one: the stream orders the two launches.  max_groups: 0, or the
+ * number of workgroups to use at most (1 .. 1024; a test walks several chunks per workgroup with a small one).
+ * n_pairs == 0: counts = {0, 0}, count = 0, inv_den = 1. */
+size_t mmg_sup_draw_select_ws_bytes(int64_t n_pairs);
+int mmg_sup_draw_select(const uint64_t* seed_ptr, uint64_t seed, float fraction, const int64_t* ids,
+                        const int64_t* io_perm, const int32_t* pi, const int32_t* deg, int degree_threshold,
+                        int64_t n_pairs, int max_groups, float* sup, int32_t* sel_low, int32_t* sel_high, int32_t* counts,
+                        double* count, double* inv_den, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Grouped launches for the vocab side (tables of 50 .. 200 rows: every lin_l / lin_r of a SAGEConv into a vocab type, the
  * transformed tables the patient-side gather reads, their weight / data gradients -- src/model.py:125-131,256 -- is a few

@@ -180,6 +180,8 @@ __host__ __device__ static inline bool mmg_keep(uint64_t seed, uint32_t site, ui
   mmg_rng_group(mmg_rng_key(seed, site), elem >> 2, &w0, &w1);
   return mmg_rng_field(w0, w1, (uint32_t)elem & 3u) >= mmg_keep_threshold(p);
 }
+// RNG site of the supervision subset (mmg_sup_mask_draw, mmg_sup_draw_select): element = the pair's id
+constexpr uint32_t MMG_SUP_SITE = 0x53555031u;
 
 // Dropout keep-fields of a 32 x 32 tile held in the MFMA C layout (lane = column col0 + (lane & 31), register r = tile row
 // mmg_c_row(r) + 4 * (lane >> 5)) of a row-major [*, ncols] tensor: element (row, col) belongs to the RNG group

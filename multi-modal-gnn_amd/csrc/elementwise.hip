@@ -512,7 +512,7 @@ __global__ __launch_bounds__(256) void k_pair_loss(const float* __restrict__ pre
 
 // Supervision subset of one epoch (src/train.py:150-176: torch.rand(n) < mask_fraction, redrawn every epoch): drawn on
 // the device from the counter RNG, keyed on (the seed the captured step reads, a site of its own, the pair's id).
-constexpr uint32_t SUP_SITE = 0x53555031u;
+constexpr uint32_t SUP_SITE = MMG_SUP_SITE;
 __global__ __launch_bounds__(256) void k_sup_mask_draw(const uint64_t* __restrict__ seed_ptr, uint64_t seed,
                                                        const int64_t* __restrict__ ids, int64_t n, float keep_p,
                                                        float* __restrict__ sup, double* __restrict__ partial) {

@@ -1597,6 +1597,185 @@ __global__ __launch_bounds__(256) void k_sel_write(const int32_t* __restrict__ p
   }
 }
 
+// ---------------------------------------------------------------------------- supervision draw + pair lists in two launches
+// mmg_sup_draw_select: the subset is a pure function of (seed, pair id), so the lists are built from the hash itself --
+// no float mask is read.  Every workgroup owns a contiguous range of 2048-position chunks; launch 1 leaves the range
+// totals and one 16-bit flag word per thread and chunk (bits 0..7: supervised, bits 8..15: supervised and low head),
+// launch 2 scans the totals for its bases and emits from the flag words.  No workgroup waits for another one: the stream
+// orders the two launches.
+constexpr int SDS_GROUPS = 512, SDS_GROUPS_MAX = 1024;   // default / largest grid (the totals: 8 KB at most)
+
+__device__ inline void sds_range(int64_t n_chunks, int64_t* c0, int64_t* c1) {
+  const int64_t per = (n_chunks + gridDim.x - 1) / gridDim.x;
+  const int64_t a = (int64_t)blockIdx.x * per, b = a + per;
+  *c0 = a < n_chunks ? a : n_chunks;
+  *c1 = b < n_chunks ? b : n_chunks;
+}
+
+__device__ inline bool sds_keep(uint32_t key, uint32_t thr_keep, uint64_t e) {      // mmg_keep with the key hoisted
+  uint32_t w0, w1;
+  mmg_rng_group(key, e >> 2, &w0, &w1);
+  return mmg_rng_field(w0, w1, (uint32_t)e & 3u) >= thr_keep;
+}
+
+// both sums to every thread; red: [8]
+__device__ inline void sds_block_sum2(unsigned* a, unsigned* b, unsigned* red) {
+  unsigned x = *a, y = *b;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { x += __shfl_xor(x, o, 64); y += __shfl_xor(y, o, 64); }
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = x; red[4 + (threadIdx.x >> 6)] = y; }
+  __syncthreads();
+  *a = red[0] + red[1] + red[2] + red[3];
+  *b = red[4] + red[5] + red[6] + red[7];
+}
+
+struct SdsIn { int64_t c[SEL_PER]; int32_t p[SEL_PER]; };     // caller index and patient of a thread's 8 positions
+
+// vec: io and pi are 16-byte aligned (s0 is a multiple of 8).  Positions past the end read the last pair (never flagged).
+__device__ inline void sds_load(SdsIn& r, const int64_t* __restrict__ io, const int32_t* __restrict__ pi, int64_t n,
+                                int64_t s0, bool vec) {
+  if (vec && s0 + SEL_PER <= n) {
+    const int4 p0 = *reinterpret_cast<const int4*>(pi + s0), p1 = *reinterpret_cast<const int4*>(pi + s0 + 4);
+    r.p[0] = p0.x; r.p[1] = p0.y; r.p[2] = p0.z; r.p[3] = p0.w;
+    r.p[4] = p1.x; r.p[5] = p1.y; r.p[6] = p1.z; r.p[7] = p1.w;
+#pragma unroll
+    for (int j = 0; j < SEL_PER; j += 2) {
+      if (io) {
+        const longlong2 v = *reinterpret_cast<const longlong2*>(io + s0 + j);
+        r.c[j] = v.x; r.c[j + 1] = v.y;
+      } else { r.c[j] = s0 + j; r.c[j + 1] = s0 + j + 1; }
+    }
+    return;
+  }
+  const int64_t kl = n - 1;
+#pragma unroll
+  for (int j = 0; j < SEL_PER; ++j) {
+    const int64_t s = s0 + j < kl ? s0 + j : kl;
+    r.c[j] = io ? io[s] : s;
+    r.p[j] = pi[s];
+  }
+}
+
+__device__ inline unsigned sds_flags(const SdsIn& r, uint32_t key, uint32_t thr_keep, const int64_t* __restrict__ ids,
+                                     const int32_t* __restrict__ deg, int thr, int64_t n, int64_t s0) {
+  int dg[SEL_PER];
+  uint64_t e[SEL_PER];
+#pragma unroll
+  for (int j = 0; j < SEL_PER; ++j) {
+    dg[j] = deg[r.p[j]];
+    e[j] = ids ? (uint64_t)ids[r.c[j]] : (uint64_t)r.c[j];
+  }
+  unsigned bits = 0;
+#pragma unroll
+  for (int j = 0; j < SEL_PER; ++j)
+    if (s0 + j < n && sds_keep(key, thr_keep, e[j])) bits |= (dg[j] < thr ? 0x101u : 0x1u) << j;
+  return bits;
+}
+
+__global__ __launch_bounds__(256) void k_sds_count(const uint64_t* __restrict__ seed_ptr, uint64_t seed, float keep_p,
+                                                   const int64_t* __restrict__ ids, const int64_t* __restrict__ io,
+                                                   const int32_t* __restrict__ pi, const int32_t* __restrict__ deg,
+                                                   int thr, int64_t n, int64_t n_chunks, uint16_t* __restrict__ flags,
+                                                   uint2* __restrict__ totals, float* __restrict__ sup) {
+  __shared__ unsigned red[8];
+  if (seed_ptr) seed = *seed_ptr;
+  const uint32_t key = mmg_rng_key(seed, MMG_SUP_SITE), thr_keep = mmg_keep_threshold(keep_p);
+  const int tid = threadIdx.x;
+  const bool vec = ((((uintptr_t)pi) | ((uintptr_t)io)) & 15u) == 0;
+  int64_t c0, c1;
+  sds_range(n_chunks, &c0, &c1);
+  unsigned n_low = 0, n_any = 0;
+  SdsIn cur, nxt;
+  if (c0 < c1) sds_load(cur, io, pi, n, c0 * SEL_CH + tid * SEL_PER, vec);
+  for (int64_t ch = c0; ch < c1; ++ch) {
+    // the next chunk's sequential loads are in flight while this chunk's gathers (deg, ids) come back
+    if (ch + 1 < c1) sds_load(nxt, io, pi, n, (ch + 1) * SEL_CH + tid * SEL_PER, vec);
+    const unsigned bits = sds_flags(cur, key, thr_keep, ids, deg, thr, n, ch * SEL_CH + tid * SEL_PER);
+    flags[ch * 256 + tid] = (uint16_t)bits;
+    n_any += __popc(bits & 0xFFu);
+    n_low += __popc(bits >> 8);
+    cur = nxt;
+  }
+  unsigned n_high = n_any - n_low;
+  sds_block_sum2(&n_low, &n_high, red);
+  if (tid == 0) totals[blockIdx.x] = make_uint2(n_low, n_high);
+  if (!sup) return;
+  // the float mask the loss reads, in the caller's order: this workgroup's slice of aligned groups of four ids
+  const int64_t n4 = (n + 3) >> 2, per = (n4 + gridDim.x - 1) / gridDim.x;
+  const int64_t q0 = (int64_t)blockIdx.x * per, q1 = q0 + per < n4 ? q0 + per : n4;
+  const bool svec = (((uintptr_t)sup) & 15u) == 0;
+  for (int64_t q = q0 + tid; q < q1; q += 256) {
+    const int64_t k0 = q << 2;
+    float m[4];
+    if (!ids) {                                  // ids k0 .. k0+3 are ONE group of the RNG: one hash
+      uint32_t w0, w1;
+      mmg_rng_group(key, (uint64_t)q, &w0, &w1);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) m[j] = mmg_rng_field(w0, w1, (uint32_t)j) >= thr_keep ? 1.f : 0.f;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t k = k0 + j < n ? k0 + j : n - 1;
+        m[j] = sds_keep(key, thr_keep, (uint64_t)ids[k]) ? 1.f : 0.f;
+      }
+    }
+    if (svec && k0 + 4 <= n) {
+      *reinterpret_cast<float4*>(sup + k0) = make_float4(m[0], m[1], m[2], m[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (k0 + j < n) sup[k0 + j] = m[j];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_sds_write(const uint16_t* __restrict__ flags, const uint2* __restrict__ totals,
+                                                   int64_t n_chunks, int32_t* __restrict__ sel_low,
+                                                   int32_t* __restrict__ sel_high, int32_t* __restrict__ counts,
+                                                   double* __restrict__ count, double* __restrict__ inv_den) {
+  __shared__ unsigned red[8];
+  __shared__ unsigned sm[4];
+  const int tid = threadIdx.x;
+  // bases of this range = the totals of the ranges before it; workgroup 0 (bases 0) sums all of them for the outputs
+  const int lim = blockIdx.x == 0 ? (int)gridDim.x : (int)blockIdx.x;
+  unsigned bl = 0, bh = 0;
+  for (int i = tid; i < lim; i += 256) {
+    const uint2 t = totals[i];
+    bl += t.x; bh += t.y;
+  }
+  sds_block_sum2(&bl, &bh, red);
+  if (blockIdx.x == 0) {
+    if (tid == 0) {
+      counts[0] = (int32_t)bl; counts[1] = (int32_t)bh;
+      const double s = (double)(bl + bh);
+      if (count) *count = s;
+      if (inv_den) *inv_den = 1.0 / (s > 1.0 ? s : 1.0);
+    }
+    bl = 0; bh = 0;
+  }
+  int64_t c0, c1;
+  sds_range(n_chunks, &c0, &c1);
+  unsigned nxt = c0 < c1 ? flags[c0 * 256 + tid] : 0u;
+  for (int64_t ch = c0; ch < c1; ++ch) {
+    const unsigned bits = nxt;
+    if (ch + 1 < c1) nxt = flags[(ch + 1) * 256 + tid];       // in flight under this chunk's scan and stores
+    const unsigned nl = __popc(bits >> 8), na = __popc(bits & 0xFFu);
+    unsigned tot;
+    const unsigned off = block_excl_scan(nl | ((na - nl) << 16), &tot, sm);
+    const int32_t k0 = (int32_t)(ch * SEL_CH + tid * SEL_PER);
+    unsigned ol = bl + (off & 0xFFFFu), oh = bh + (off >> 16);
+#pragma unroll
+    for (int j = 0; j < SEL_PER; ++j) {
+      if (bits & (1u << j)) {
+        if (bits & (1u << (8 + j))) sel_low[ol++] = k0 + j;
+        else sel_high[oh++] = k0 + j;
+      }
+    }
+    bl += tot & 0xFFFFu; bh += tot >> 16;
+    __syncthreads();                             // sm is rewritten by the next chunk's scan
+  }
+}
+
 inline unsigned pair_grid(int64_t n) {
   int64_t t = (n + PT - 1) / PT;
   if (t > 1024) t = 1024;
@@ -1854,5 +2033,51 @@ extern "C" int mmg_pair_select(const int32_t* pi, const int32_t* deg, int degree
   hipLaunchKernelGGL(k_sel_write, dim3(nb), dim3(256), 0, st, pi, deg, degree_threshold, dpred, io_perm, dpred_sorted,
                      n_pairs, base, sel_low, sel_high);
   MMG_CHECK_LAUNCH("pair_select");
+  return MMG_OK;
+}
+
+// workspace of mmg_sup_draw_select: the range totals and one flag word per thread and chunk
+static void sds_carve(MmgCarver& c, int64_t n_pairs, uint2** totals, uint16_t** flags) {
+  const int64_t nb = (n_pairs + SEL_CH - 1) / SEL_CH;
+  *totals = c.take<uint2>(SDS_GROUPS_MAX);
+  *flags = c.take<uint16_t>((size_t)(nb > 0 ? nb : 1) * 256);
+}
+
+extern "C" size_t mmg_sup_draw_select_ws_bytes(int64_t n_pairs) {
+  if (n_pairs < 0) return 0;
+  MmgCarver c(nullptr);
+  uint2* t;
+  uint16_t* f;
+  sds_carve(c, n_pairs, &t, &f);
+  return c.need();
+}
+
+extern "C" int mmg_sup_draw_select(const uint64_t* seed_ptr, uint64_t seed, float fraction, const int64_t* ids,
+                                   const int64_t* io_perm, const int32_t* pi, const int32_t* deg, int degree_threshold,
+                                   int64_t n_pairs, int max_groups, float* sup, int32_t* sel_low, int32_t* sel_high,
+                                   int32_t* counts, double* count, double* inv_den, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  MMG_CHECK_ARG(n_pairs >= 0 && n_pairs < (int64_t)INT32_MAX, "sup_draw_select: n_pairs out of range");
+  MMG_CHECK_ARG(fraction >= 0.f && fraction <= 1.f, "sup_draw_select: fraction outside [0, 1]");
+  MMG_CHECK_ARG(max_groups >= 0 && max_groups <= SDS_GROUPS_MAX, "sup_draw_select: max_groups outside [0, %d]",
+                SDS_GROUPS_MAX);
+  MMG_CHECK_ARG(counts, "sup_draw_select: counts is null");
+  MMG_CHECK_ARG(n_pairs == 0 || (pi && deg && sel_low && sel_high), "sup_draw_select: null buffer");
+  MMG_CHECK_WS("sup_draw_select", mmg_sup_draw_select_ws_bytes(n_pairs));
+  hipStream_t st = (hipStream_t)stream;
+  MmgCarver c(ws);
+  uint2* totals;
+  uint16_t* flags;
+  sds_carve(c, n_pairs, &totals, &flags);
+  const int64_t nb = (n_pairs + SEL_CH - 1) / SEL_CH;
+  int64_t g = max_groups > 0 ? max_groups : SDS_GROUPS;
+  if (g > nb) g = nb;
+  if (g < 1) g = 1;                        // (n_pairs == 0: one workgroup with an empty range writes the zero outputs)
+  // mmg_keep keeps with probability 1 - p: a pair is supervised with probability `fraction` (as mmg_sup_mask_draw)
+  hipLaunchKernelGGL(k_sds_count, dim3((unsigned)g), dim3(256), 0, st, seed_ptr, seed, 1.0f - fraction, ids, io_perm, pi,
+                     deg, degree_threshold, n_pairs, nb, flags, totals, sup);
+  hipLaunchKernelGGL(k_sds_write, dim3((unsigned)g), dim3(256), 0, st, flags, totals, nb, sel_low, sel_high, counts, count,
+                     inv_den);
+  MMG_CHECK_LAUNCH("sup_draw_select");
   return MMG_OK;
 }

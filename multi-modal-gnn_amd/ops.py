@@ -1142,6 +1142,39 @@ def sup_mask_draw(n: int, fraction: float, device, seed: int = 0, seed_dev=None,
     return sup, count, inv_den
 
 
+def sup_draw_select(pi, deg, thr: int, fraction: float, seed: int = 0, seed_dev=None, ids=None, io_perm=None, sup=None,
+                    out=None, count=None, inv_den=None, max_groups: int = 0, want_sup: bool = True):
+    """sup_mask_draw followed by pair_select(pi, deg, thr, sup, io_perm=io_perm) in two launches (mmg_sup_draw_select), bit
+    for bit -> (sup float [n] in the caller's order, (sel_low, sel_high, counts), count fp64 [1], inv_den fp64 [1]).
+    sup, out, count and inv_den may be passed in (a captured step overwrites them in place); want_sup = False: no mask.
+    max_groups > 0: at most that many workgroups."""
+    n = pi.numel()
+    dev = pi.device
+    if not want_sup:
+        sup = None
+    elif sup is None:
+        sup = torch.empty(max(n, 1), dtype=torch.float32, device=dev)[:n]
+    if out is not None:
+        sel_low, sel_high, counts = out
+    else:
+        sel_low = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        sel_high = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.float64, device=dev) if count is None else count
+    inv_den = torch.empty(1, dtype=torch.float64, device=dev) if inv_den is None else inv_den
+    if sup is not None and sup.numel() != n:
+        raise ValueError(f"sup_draw_select: sup has {sup.numel()} entries, pi has {n}")
+    for name, t in (("ids", ids), ("io_perm", io_perm)):
+        if t is not None and t.numel() != n:
+            raise ValueError(f"sup_draw_select: {name} has {t.numel()} entries, pi has {n}")
+    _tok = _pb("sup_draw_select")
+    _call("mmg_sup_draw_select", seed_dev, int(seed) & 0xFFFFFFFFFFFFFFFF, float(fraction), ids, io_perm, pi, deg, int(thr),
+          n, int(max_groups), sup if n else None, sel_low, sel_high, counts, count, inv_den,
+          ws=_lib.load().mmg_sup_draw_select_ws_bytes(n))
+    _pe(_tok, "sup_draw_select", n * 24)
+    return sup, (sel_low, sel_high, counts), count, inv_den
+
+
 def pair_loss(pred, y, w=None, sup=None, inv_den: float = 1.0, loss_type: str = "mae", inv_den_dev=None, loss_out=None,
               want_dpred: bool = True):
     """-> (loss fp64 scalar tensor, dpred [n]) in one pass (mmg_pair_loss).  inv_den_dev: fp64 [1] device tensor that

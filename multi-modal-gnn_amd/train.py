@@ -628,6 +628,19 @@ def set_step_advance(on: bool):
     STEP_ADVANCE = bool(on)
 
 
+# A single-GPU step that draws its supervision subset builds the mask, its size and the two pair lists in two launches
+# (ops.sup_draw_select: the lists come from the draw's hash itself) instead of five (draw, count, and the three of
+# pair_select, which gathered the mask back through the permutation twice).  Mask, size and lists are bit for bit the same.
+# set_fused_select(False) restores the five launches.
+FUSED_SELECT = True
+
+
+def set_fused_select(on: bool):
+    """True (default) | False -- see FUSED_SELECT (the tests switch it; read when a step is recorded)."""
+    global FUSED_SELECT
+    FUSED_SELECT = bool(on)
+
+
 class GraphedTrainStep:
     """One whole training step -- zero_grad, predict_lab_values, weighted loss, backward, optimizer.step --
     captured ONCE into a hipGraph and replayed per epoch (the eICU-scale graph is launch-bound: ~250 kernel
@@ -845,17 +858,33 @@ class PiecewiseGraphedTrainStep:
         model = self.model
         ids = self._draw_ids
         side = getattr(model, "_side_stream", None)
-        if self.comm is not None or side is None:
+        if self.comm is not None:
             self._sv.draw(self.mask_fraction, model._seed_dev, ids, self.n_pairs_global)
             self._select()
+            return
+        if side is None:
+            self._draw_select_local(ids)
             return
         main = torch.cuda.current_stream()
         side.wait_stream(main)
         with torch.cuda.stream(side):
-            self._sv.draw(self.mask_fraction, model._seed_dev, ids)
-            self._select()
+            self._draw_select_local(ids)
             self._sel_ready = torch.cuda.Event()
             self._sel_ready.record(side)      # the heads wait for this (_Run.heads_fwd); the encoder pass does not
+
+    def _draw_select_local(self, ids):
+        """Single GPU: mask, subset size, 1 / size and both pair lists on the current stream, in place (the captured step
+        holds their addresses).  FUSED_SELECT: two launches; otherwise the draw and pair_select, five."""
+        model = self.model
+        if not FUSED_SELECT:
+            self._sv.draw(self.mask_fraction, model._seed_dev, ids)
+            self._select()
+            return
+        thr = int(model.degree_threshold)
+        pairs = model._pairs(self.pi, self.li, self.plan.n_rows, None, self.plan.lab_deg, thr)
+        _, self._sel, _, _ = self._ops.sup_draw_select(
+            pairs.pi, self.plan.lab_deg, thr, self.mask_fraction, seed_dev=model._seed_dev, ids=ids, io_perm=pairs.perm,
+            sup=self._sv.sup, out=self._sel, count=self._sv.count, inv_den=self._sv.inv_den)
 
     # ---- replay
     def _select(self):
