@@ -387,6 +387,23 @@ int mmg_linear_bnbwd_supported(int mode, int64_t M, int N, int K, int with_wgrad
 size_t mmg_linear_bnbwd_wgrad_ws_bytes(int64_t M, int N, int K);
 int mmg_linear_bnbwd(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
                      const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, void* stream);
+/* mmg_linear_bnbwd(a, W, dZ, dX, M, N, K, NULL, wg, stream) with a MASKED dX store: the dropout that the consumer of dX --
+ * the backward of the BatchNorm + activation + dropout in front of this linear, whose prologue is wg->pro -- would apply
+ * first is applied by the producer, and a second producer adds its share:
+ *   accumulate == 0:  dX[r, c]  = kept(r, c) ? dx * inv_keep : 0
+ *   accumulate != 0:  dX[r, c] += kept(r, c) ? dx * inv_keep : 0       (the product rounded, then ONE fp32 add)
+ * kept / inv_keep are those of `mask` (its dropout fields: drop_p, seed / seed_ptr, site, row_offset, over [M, N]).  The
+ * kernel takes the keep bits from the hashes its weight-gradient half makes for wg->pro anyway, so `mask` must BE the
+ * dropout of wg->pro (equal in those fields; both without dropout: a plain / accumulating store); anything else is refused
+ * with MMG_E_ARG before anything is launched.
+ * After a write by one pass and an accumulate by another, dX = dropA(dX_A) + dropB(dX_B) in fp32: the consumer then applies
+ * the activation's select (mmg_bn_bwd_stats / mmg_linear_bnbwd with the prologue's drop_p = 0) but NO dropout -- bit for
+ * bit what mmg_bn_bwd_stats2 / MMG_BNBWD_BN2 form from the two unmasked tensors.  dZ, dW, dbias, dbeta and dgamma are those
+ * of mmg_linear_bnbwd.
+ * mmg_linear_bnbwd_masked_supported: MMG_BNBWD_BN and MMG_BNBWD_ROWS with a weight gradient, K = N = 128, M > 512. */
+int mmg_linear_bnbwd_masked_supported(int mode, int64_t M, int N, int K, int with_wgrad);
+int mmg_linear_bnbwd_masked(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
+                            const mmg_prologue_t* mask, int accumulate, const mmg_bnbwd_wgrad_t* wg, void* stream);
 /* The data gradient AND the weight gradient of a plain linear in ONE launch -- the first layer of a pair head, whose
  * upstream gradient dY [M, K] is the gradient of the head's per-patient table (K = 64) and whose input X [M, N] is the
  * final patient activation (N = 128):
@@ -418,7 +435,8 @@ int mmg_linear_dgrad_wgrad(const float* dY, const float* W, float* dX, int64_t M
  *   reported as 2 * 128, the two outputs side by side, so that 4 (M K + N K + M N) bytes and 2 M N K FLOP price the launch),
  *   4096 = the layer's weight gradient rides along (mmg_linear_dgrad_wgrad: the row is the data gradient's (M, 128, 64), with
  *   512 where the next-BatchNorm epilogue runs; priced as the data gradient alone, the launch also reads X [M, N] and does
- *   2 M N K FLOP more).
+ *   2 M N K FLOP more), 8192 = the masked dX store of mmg_linear_bnbwd_masked (beside the mode's own bits; an accumulating
+ *   launch reads dX once more than its row prices).
  * The hook is the library's only process-wide mutable state (mutex-guarded); the product path never arms it. */
 #define MMG_PROBE_LINEAR_FWD 1
 #define MMG_PROBE_LINEAR_WGRAD 2

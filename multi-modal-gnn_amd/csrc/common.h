@@ -175,6 +175,19 @@ __host__ __device__ static inline void mmg_drop4(V4& v, uint32_t key, uint64_t e
   v[2] = MMG_KEPT(w0, w1, 2, thr) ? v[2] * inv_keep : 0.f;
   v[3] = MMG_KEPT(w0, w1, 3, thr) ? v[3] * inv_keep : 0.f;
 }
+// mmg_drop4 that also returns the four keep bits (bit j = element j kept): the same hash, compares and selects
+template <class V4>
+__host__ __device__ static inline uint32_t mmg_drop4_bits(V4& v, uint32_t key, uint64_t e0, uint32_t thr, float inv_keep) {
+  uint32_t w0, w1;
+  mmg_rng_group(key, e0 >> 2, &w0, &w1);
+  const bool k0 = MMG_KEPT(w0, w1, 0, thr), k1 = MMG_KEPT(w0, w1, 1, thr), k2 = MMG_KEPT(w0, w1, 2, thr),
+             k3 = MMG_KEPT(w0, w1, 3, thr);
+  v[0] = k0 ? v[0] * inv_keep : 0.f;
+  v[1] = k1 ? v[1] * inv_keep : 0.f;
+  v[2] = k2 ? v[2] * inv_keep : 0.f;
+  v[3] = k3 ? v[3] * inv_keep : 0.f;
+  return (k0 ? 1u : 0u) | (k1 ? 2u : 0u) | (k2 ? 4u : 0u) | (k3 ? 8u : 0u);
+}
 __host__ __device__ static inline bool mmg_keep(uint64_t seed, uint32_t site, uint64_t elem, float p) {
   uint32_t w0, w1;
   mmg_rng_group(mmg_rng_key(seed, site), elem >> 2, &w0, &w1);

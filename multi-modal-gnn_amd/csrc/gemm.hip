@@ -911,22 +911,28 @@ struct BnBwdDev {
 // k_linear_wgrad_ws (four 8-row groups, ((g0 + g1) + g2) + g3), 1: k_linear_wgrad_x6<128, 128, 4, 2, true> (16 row
 // residues mod 16 of every 32-row tile, summed in order).
 // dZ is stored only where bb.dZ is set (a zero-sized descriptor drops the stores otherwise).
+// MSK (FW, MODE 0 / 3): the dX store applies the dropout of wg.xpr -- the mask the consumer of dX would apply first, and
+// the one the X stagers hash anyway.  They leave the four keep bits of every group as one byte beside the X planes
+// ([buffer][column quad][row], read by the dX waves in the body that multiplies that buffer); 1: DX = kept ? dx * inv_keep
+// : 0, 2: DX += the same (the two encoder passes of a step hand ONE tensor to the BatchNorm they share).
 struct BnWgDev {
   const float* X; ProDev xpr; float* slab; int64_t slab_stride; int bias_order;
 };
 static inline BnWgDev bn_wg_none() { return BnWgDev{nullptr, mmg_pro_dev(nullptr), nullptr, 0, 0}; }
 
-template <int K, int WN, int MODE = 0, bool NBN = false, bool FW = false>
+template <int K, int WN, int MODE = 0, bool NBN = false, bool FW = false, int MSK = 0>
 __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) void k_linear_bnbwd_x6(
     const float* __restrict__ G, BnBwdDev bb, ProDev pr, const float* __restrict__ W, float* __restrict__ DX, int64_t M,
     ProDev pr2, NextBnDev nb, double* __restrict__ stat_partial, BnWgDev wg) {
   static_assert(!FW || (K == 128 && WN == 4), "the fused weight gradient covers K = N = 128");
+  static_assert(MSK == 0 || (FW && !NBN && (MODE == 0 || MODE == 3)), "the masked dX store rides on the X stagers' hashes");
   if (MODE != 1) pr.resolve();
   if (MODE == 2) pr2.resolve();
   if (FW) wg.xpr.resolve();
   constexpr int LDP = K + 8, N = 32 * WN, NK = K / 16, NTHR = 64 * WN, BM = 32;
   constexpr int SX = N + 32;               // X plane row stride (FW): +64 B puts the 4 rows of a transposing read on disjoint banks
-  extern __shared__ __attribute__((aligned(16))) __bf16 planes[];     // [2 buffers][3 pieces][BM][LDP] (FW: + [2][3][BM][SX] of X)
+  constexpr int KBS = BM + 4;              // keep-bit row stride (MSK): [column quad][tile row] bytes, +4 B spreads the quads over the banks
+  extern __shared__ __attribute__((aligned(16))) __bf16 planes[];     // [2 buffers][3 pieces][BM][LDP] (FW: + [2][3][BM][SX] of X; MSK: + [2][N / 4][KBS] keep bits)
   const int tid = threadIdx.x, lane = tid & 63, wn = tid >> 6;
   const int h = lane >> 5, l31 = lane & 31;
   const int col = wn * 32 + l31;
@@ -1104,6 +1110,7 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
     }
     if (wg.xpr.relu) xfloor = 0.f;
     __bf16* xplanes = planes + 2 * 3 * BM * LDP;
+    unsigned char* keepb = reinterpret_cast<unsigned char*>(xplanes + 2 * 3 * BM * SX);
     auto xstage = [&](int64_t tile, int buf) __attribute__((always_inline)) {
       __bf16* xb = xplanes + (size_t)buf * 3 * BM * SX;
 #pragma unroll
@@ -1114,7 +1121,14 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = fmaxf(fmaf(v[j], xsc[j], xsh[j]), xfloor);
         }
-        if (xdrop)
+        if constexpr (MSK != 0) {
+          // the keep bits of this group of four go to the dX waves, whose masked store applies the SAME mask
+          uint32_t kb = 0xFu;
+          if (xdrop)
+            kb = mmg_drop4_bits(v, wg.xpr.key, (uint64_t)(wg.xpr.row_offset + tile * BM + r) * (uint64_t)N + (uint64_t)(xc4 * 4),
+                                wg.xpr.thr, wg.xpr.inv_keep);
+          keepb[(buf * (N / 4) + xc4) * KBS + r] = (unsigned char)kb;
+        } else if (xdrop)
           mmg_drop4(v, wg.xpr.key, (uint64_t)(wg.xpr.row_offset + tile * BM + r) * (uint64_t)N + (uint64_t)(xc4 * 4),
                     wg.xpr.thr, wg.xpr.inv_keep);
         // rows past the end need no zeroing: their dZ rows are zero
@@ -1244,6 +1258,12 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
       fetch(tt + 2 * GY);
       float nby[NBN ? 16 : 1];
       if constexpr (NBN) next_bn_load(nb, tt, rows, N, 0, yvo, nby);   // in flight under the products
+      float old[MSK == 2 ? 16 : 1];              // MSK 2: the tile the masked store adds to, in flight under the products too
+      if constexpr (MSK == 2) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          old[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xs, yvo, mmg_c_row(i) * N * 4, MMG_NT_LD));
+      }
       __builtin_amdgcn_sched_barrier(0);         // keep the fetch ahead of the matrix loop
       const __bf16* ap = planes + (size_t)buf * 3 * BM * LDP + l31 * LDP + 8 * h;
 #pragma unroll
@@ -1254,11 +1274,35 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
         MMG_X6_ALO(acc, a1f, a2f, a3f, wb[ks][0], wb[ks][1], wb[ks][2]);
       }
       float vv[16];
+      if constexpr (MSK != 0) {
+        // DX (+)= dropout(dX) under the mask of wg.xpr (mmg_drop4's expression; the product is rounded before the add: an
+        // empty asm keeps it a multiply, as in k_linear_fwd_x6_dual).  The X stagers left the keep bits of this buffer's
+        // tile beside the X planes before the barrier that released it: rows 8 g + 4 h + 0..3 of this lane's column quad
+        const unsigned char* kq = reinterpret_cast<const unsigned char*>(planes + 2 * 3 * BM * LDP + 2 * 3 * BM * SX) +
+                                  (buf * (N / 4) + (col >> 2)) * KBS + 4 * h;
+        const int sub = col & 3;
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        vv[i] = acc[i];                        // (a bit_cast straight from the vector element stored element 0 sixteen times)
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[i]), xs, yvo, mmg_c_row(i) * N * 4,
-                                              MMG_NT_ST);
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const uint32_t kw = *reinterpret_cast<const uint32_t*>(kq + 8 * g4) >> sub;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int i = 4 * g4 + j;
+            float s = acc[i] * wg.xpr.inv_keep;
+            asm("" : "+v"(s));
+            s = (kw >> (8 * j)) & 1u ? s : 0.f;
+            vv[i] = MSK == 2 ? old[i] + s : s;
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[i]), xs, yvo, mmg_c_row(i) * N * 4, MMG_NT_ST);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          vv[i] = acc[i];                        // (a bit_cast straight from the vector element stored element 0 sixteen times)
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[i]), xs, yvo, mmg_c_row(i) * N * 4,
+                                                MMG_NT_ST);
+        }
       }
       if constexpr (NBN) next_bn_tile(nb, nbc, vv, nby, rows, tt * BM, N, col, lane, cs1, cs2);
       __syncthreads();                         // buf fully read, buf^1 fully written
@@ -1808,6 +1852,21 @@ int launch_bnbwd_fw(const float* G, const BnBwdDev& bb, const ProDev& pr, const 
   return 0;
 }
 
+// the FW form with the masked dX store (MSK 1: DX = dropout(dX), 2: DX += dropout(dX), under the mask of wg.xpr): + the keep
+// bits of both buffers' tiles behind the X planes; flag 8192 = masked
+template <int MODE, int MSK>
+int launch_bnbwd_fw_masked(const float* G, const BnBwdDev& bb, const ProDev& pr, const float* W, float* DX, int64_t M,
+                           const BnWgDev& wg, hipStream_t st) {
+  constexpr int K = 128, N = 128;
+  const int64_t gy = bnbwd_fw_rows(M);
+  constexpr int lds = 2 * 3 * 32 * (K + 8) * 2 + 2 * 3 * 32 * (N + 32) * 2 + 2 * (N / 4) * (32 + 4);    // + 2.3 KB: 113 KB
+  MMG_CHECK_HIP((MmgMaxLds<&k_linear_bnbwd_x6<K, 4, MODE, false, true, MSK>, lds>::set()), "linear_bnbwd_masked(attr)");
+  MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, N, K, (MODE == 3 ? 16 | 256 : 16) | 1024 | 8192,
+             (k_linear_bnbwd_x6<K, 4, MODE, false, true, MSK>), dim3(1u, (unsigned)gy), dim3(512), lds, st, G, bb, pr, W, DX, M,
+             mmg_pro_dev(nullptr), next_bn_none(), nullptr, wg);
+  return 0;
+}
+
 // ---------------------------------------------------------------------------- data gradient + weight gradient of a pair head's first layer
 // k_linear_dgrad_wgrad_x6: DX [M, 128] = dY . W (W [64, 128], the forward weight in place) AND the slabs of
 // dW [64, 128] = dY^T . pro(X) in one pass over dY [M, 64] and X [M, 128] -- k_linear_fwd_x6<64, 4, false, false, false, NBN>
@@ -2272,7 +2331,7 @@ extern "C" size_t mmg_linear_bnbwd_wgrad_ws_bytes(int64_t M, int N, int K) {
 template <int MODE>
 static int bnbwd_wgrad_run(const float* G, const BnBwdDev& bb, const ProDev& pr, const ProDev& pr2, const float* W, float* dX,
                            int64_t M, const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, const char* what,
-                           hipStream_t st) {
+                           hipStream_t st, int msk = 0) {
   constexpr int N = 128, K = 128;
   mmg_wgrad_reduce_t* job = wg->job;
   if (job) { job->slab = nullptr; job->n4 = 0; job->n_split = 0; job->dW = wg->dW; job->dbias = wg->dbias; job->nk4 = (int64_t)K * N / 4; job->accumulate = wg->accumulate; }
@@ -2291,7 +2350,12 @@ static int bnbwd_wgrad_run(const float* G, const BnBwdDev& bb, const ProDev& pr,
   // the next BatchNorm's statistics always come from the separate pass over dX: the epilogue that sums them does not fit
   // beside the dW waves (k_linear_bnbwd_x6<128, 4, MODE, true, true> spills 124..220 B per lane at the 256-register budget
   // of two waves per SIMD, which the plain NBN instances already exceed by 40..136 B)
-  int rc = launch_bnbwd_fw<MODE>(G, bb, pr, pr2, W, dX, M, wd, st);
+  int rc = MMG_E_ARG;
+  if (!msk) rc = launch_bnbwd_fw<MODE>(G, bb, pr, pr2, W, dX, M, wd, st);
+  if constexpr (MODE == MMG_BNBWD_BN || MODE == MMG_BNBWD_ROWS) {      // msk: the masked dX store (mmg_linear_bnbwd_masked)
+    if (msk == 1) rc = launch_bnbwd_fw_masked<MODE, 1>(G, bb, pr, W, dX, M, wd, st);
+    if (msk == 2) rc = launch_bnbwd_fw_masked<MODE, 2>(G, bb, pr, W, dX, M, wd, st);
+  }
   if (rc) return rc;
   MMG_CHECK_LAUNCH(what);
   rc = next ? mmg_next_bn_fallback(dX, M, N, next, what, st) : MMG_OK;
@@ -2312,8 +2376,8 @@ static int bnbwd_wgrad_run(const float* G, const BnBwdDev& bb, const ProDev& pr,
 template <int MODE>
 static int bnbwd_run(const float* G, const BnBwdDev& bb, const ProDev& pr, const ProDev& pr2, const float* W, float* dX,
                      int64_t M, int N, int K, const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, const char* what,
-                     hipStream_t st) {
-  if (wg) return bnbwd_wgrad_run<MODE>(G, bb, pr, pr2, W, dX, M, next, wg, what, st);
+                     hipStream_t st, int msk) {
+  if (wg) return bnbwd_wgrad_run<MODE>(G, bb, pr, pr2, W, dX, M, next, wg, what, st, msk);
   int rc;
   if constexpr (MODE != MMG_BNBWD_BN2) {          // no NBN instance (the entry point refuses next)
     if (next && K == 128 && N == 128 && mmg_next_bn_fusable(next)) {
@@ -2347,8 +2411,9 @@ static const struct {
     {"linear_bnbwd_rows",    false, false, true,   true,  false, false},    // G NULL iff n_sel == 0 (checked below)
 };
 
-extern "C" int mmg_linear_bnbwd(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
-                                const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, void* stream) {
+// msk: 0, or the masked dX store of mmg_linear_bnbwd_masked (1: write, 2: accumulate; validated there)
+static int linear_bnbwd_impl(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
+                             const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, int msk, void* stream) {
   MMG_CHECK_ARG(a, "linear_bnbwd: null descriptor");
   MMG_CHECK_ARG(a->mode >= MMG_BNBWD_BN && a->mode <= MMG_BNBWD_ROWS, "linear_bnbwd: unknown mode %d", a->mode);
   const auto& m = kBnBwdMode[a->mode];
@@ -2376,11 +2441,37 @@ extern "C" int mmg_linear_bnbwd(const mmg_bnbwd_t* a, const float* W, float* dZ,
   const float* G = rows && !a->G ? a->y : a->G;   // an empty row list: no row of G is read
   hipStream_t st = (hipStream_t)stream;
   switch (a->mode) {
-    case MMG_BNBWD_BN: return bnbwd_run<MMG_BNBWD_BN>(G, bb, pr, pr2, W, dX, M, N, K, next, wg, what, st);
-    case MMG_BNBWD_L2: return bnbwd_run<MMG_BNBWD_L2>(G, bb, pr, pr2, W, dX, M, N, K, next, wg, what, st);
-    case MMG_BNBWD_BN2: return bnbwd_run<MMG_BNBWD_BN2>(G, bb, pr, pr2, W, dX, M, N, K, next, wg, what, st);
-    default: return bnbwd_run<MMG_BNBWD_ROWS>(G, bb, pr, pr2, W, dX, M, N, K, next, wg, what, st);
+    case MMG_BNBWD_BN: return bnbwd_run<MMG_BNBWD_BN>(G, bb, pr, pr2, W, dX, M, N, K, next, wg, what, st, msk);
+    case MMG_BNBWD_L2: return bnbwd_run<MMG_BNBWD_L2>(G, bb, pr, pr2, W, dX, M, N, K, next, wg, what, st, msk);
+    case MMG_BNBWD_BN2: return bnbwd_run<MMG_BNBWD_BN2>(G, bb, pr, pr2, W, dX, M, N, K, next, wg, what, st, msk);
+    default: return bnbwd_run<MMG_BNBWD_ROWS>(G, bb, pr, pr2, W, dX, M, N, K, next, wg, what, st, msk);
   }
+}
+
+extern "C" int mmg_linear_bnbwd(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
+                                const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, void* stream) {
+  return linear_bnbwd_impl(a, W, dZ, dX, M, N, K, next, wg, 0, stream);
+}
+
+extern "C" int mmg_linear_bnbwd_masked_supported(int mode, int64_t M, int N, int K, int with_wgrad) {
+  return (mode == MMG_BNBWD_BN || mode == MMG_BNBWD_ROWS) && with_wgrad && mmg_linear_bnbwd_supported(mode, M, N, K, 1) ? 1 : 0;
+}
+
+extern "C" int mmg_linear_bnbwd_masked(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
+                                       const mmg_prologue_t* mask, int accumulate, const mmg_bnbwd_wgrad_t* wg, void* stream) {
+  const char* what = "linear_bnbwd_masked";
+  MMG_CHECK_ARG(a, "%s: null descriptor", what);
+  MMG_CHECK_ARG(mmg_linear_bnbwd_masked_supported(a->mode, M, N, K, wg != nullptr), "%s: mode %d M=%lld N=%d K=%d%s unsupported",
+                what, a->mode, (long long)M, N, K, wg ? "" : " without a weight gradient");
+  MMG_CHECK_ARG(mask, "%s: null mask", what);
+  // the keep bits are those the X stagers hash for the weight gradient: the mask IS the dropout of wg->pro
+  const mmg_prologue_t* xp = wg->pro;
+  const float xp_p = xp ? xp->drop_p : 0.f;
+  MMG_CHECK_ARG(mask->drop_p == xp_p &&
+                    (!(xp_p > 0.f) || (mask->seed_ptr == xp->seed_ptr && (mask->seed_ptr || mask->seed == xp->seed) &&
+                                       mask->site == xp->site && mask->row_offset == xp->row_offset)),
+                "%s: the mask is not the dropout of the X prologue", what);
+  return linear_bnbwd_impl(a, W, dZ, dX, M, N, K, nullptr, wg, accumulate ? 2 : 1, stream);
 }
 
 extern "C" size_t mmg_linear_wgrad_ws_bytes(int64_t M, int N, int K) {

@@ -16,7 +16,7 @@ Algebra used (exact up to fp32 re-association, inside the 1e-4 parity bar):
 from __future__ import annotations
 
 import logging
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
@@ -131,6 +131,21 @@ def set_fused_head_wgrad(on: bool):
     """True (default) | False -- see FUSED_HEAD_WGRAD (the tests switch it)."""
     global FUSED_HEAD_WGRAD
     FUSED_HEAD_WGRAD = bool(on)
+
+
+# The two encode_nodes passes of a training step hand two gradients to the first BatchNorm they share, each to be masked
+# with its own pass's dropout by BOTH readers (the joint statistics pass and the joint BatchNorm-backward GEMM).  The two
+# producers -- the BatchNorm-backward GEMMs of the second linear, whose weight-gradient halves hash exactly those masks
+# anyway -- store the masked sum instead (ops.MaskedDx: the dense pass writes, the listed-rows pass adds), and the readers
+# take ONE tensor with the activation's select alone: bit for bit the same sums and gradients.
+# set_masked_handdown(False) restores the two tensors.
+MASKED_HANDDOWN = True
+
+
+def set_masked_handdown(on: bool):
+    """True (default) | False -- see MASKED_HANDDOWN (the tests switch it)."""
+    global MASKED_HANDDOWN
+    MASKED_HANDDOWN = bool(on)
 
 
 def _mangle(et: EdgeType) -> str:
@@ -570,6 +585,7 @@ class _Run:
         self.next_bn_sites = ex["next_bn"] if ex.get("next_bn") is not None else NEXT_BN_SITES
         self.save_pair_state = ex["save_pair_state"] if ex.get("save_pair_state") is not None else SAVE_PAIR_STATE
         self.fused_wgrad = FUSED_WGRAD
+        self.masked_handdown = MASKED_HANDDOWN
         self.overlap = mode == "on" or (mode == "auto" and self.plan.n_rows >= 16384)
         if self.overlap:
             if getattr(model, "_side_stream", None) is None:
@@ -788,8 +804,14 @@ class _Run:
                         a1, a0 = (a1[0], both[0]), (a0[0], both[1])
                     elif live:
                         self.allreduce(live[0][1])
-                nstats = _NextStats(enc1.z1, enc1.f1)      # the shared first BatchNorm: both passes add their share
-                self.enc_bwd_shared(enc1, self.enc_bwd_b(enc1, a1, nstats), enc0, self.enc_bwd_b(enc0, a0, nstats), nstats)
+                if self.masked_handdown_applies(enc1, a1, enc0, a0):
+                    # pass B stores its gradient under its own mask, pass A adds its own under its mask: one tensor down
+                    gs = self.enc_bwd_b(enc1, a1, masked=ops.MaskedDx(enc1.pro1))
+                    gs = self.enc_bwd_b(enc0, a0, masked=ops.MaskedDx(enc0.pro1, into=gs))
+                    self.enc_bwd_shared_masked(enc1, gs)
+                else:
+                    nstats = _NextStats(enc1.z1, enc1.f1)      # the shared first BatchNorm: both passes add their share
+                    self.enc_bwd_shared(enc1, self.enc_bwd_b(enc1, a1, nstats), enc0, self.enc_bwd_b(enc0, a0, nstats), nstats)
             for t, gt in g.items():
                 if t not in (ROW_TYPE, BN_SUMS) and gt is not None:
                     self.acc(f"embeddings.{t}.weight", gt)
@@ -986,7 +1008,7 @@ class _Run:
         return ops.FusedWgrad(x, pro, defer=self.wgrad_jobs, keep_dz=keep_dz, **self.wgrad_target(wname, bname))
 
     def bn_lin_bwd(self, form, args, bn_prefix: Optional[str], x, pro: Optional[Pro], wname, bname, W,
-                   next_bn: Optional[_NextStats] = None, keep_dz=False):
+                   next_bn: Optional[_NextStats] = None, keep_dz=False, masked: Optional[ops.MaskedDx] = None):
         """Backward of  x' = dropout(relu(BN(y))),  y = pro(x) W^T + b  as ONE kernel (mmg_linear_bnbwd): the BatchNorm
         backward dz, the data gradient dx = dz @ W, the BatchNorm's bias / weight gradients (bn_prefix; None: no BatchNorm)
         and the linear's weight / bias gradients (wname / bname, per-shard partial sums; a tuple of names: parameters that
@@ -997,7 +1019,9 @@ class _Run:
           "two"    (g_a, y, ypro_a, fold, sums, g_b, ypro_b)    two upstream gradients with their own dropout masks
           "l2"     (g, out, rn)                                 an L2 normalisation in the BatchNorm's place (always applies)
         next_bn: holder of the statistics of the BatchNorm backward that consumes dx (that BatchNorm's prologue is `pro`):
-        taken in the kernel's epilogue, or (holder.ride False) by the separate pass right behind it."""
+        taken in the kernel's epilogue, or (holder.ride False) by the separate pass right behind it.
+        masked ("plain" / "rows", no next_bn): dx is stored under a dropout mask (ops.MaskedDx); the caller has made sure
+        that the fused launch applies (masked_handdown_applies)."""
         K, N = W.shape
         if form == "l2":
             (g, y, rn), fold, sums = args, None, None
@@ -1011,11 +1035,14 @@ class _Run:
         fw = self.fused_wgrad_for(x, pro, wname, bname, keep_dz, y.shape[0], N, K, next_bn=nb is not None)
         if form == "plain" and fold is not None and sums is None:
             sums = self.bn_bwd_sums(g, y, ypro, fold, more[0])
+        if masked is not None and (fw is None or nb is not None or form not in ("plain", "rows")):
+            raise RuntimeError(f"bn_lin_bwd: no masked dx store for form {form!r} here")
+        mk = dict(masked=masked) if masked is not None else {}
         bn = self.bn_param_grads(fold, bn_prefix, sums, K)
         if form == "plain":
-            out = ops.linear_bnbwd(g, y, ypro, fold, W, *bn, next_bn=nb, wgrad=fw)
+            out = ops.linear_bnbwd(g, y, ypro, fold, W, *bn, next_bn=nb, wgrad=fw, **mk)
         elif form == "rows":
-            out = ops.linear_bnbwd_rows(g, more[0], y, ypro, fold, W, *bn, next_bn=nb, wgrad=fw)
+            out = ops.linear_bnbwd_rows(g, more[0], y, ypro, fold, W, *bn, next_bn=nb, wgrad=fw, **mk)
         elif form == "two":
             out = ops.linear_bnbwd2(g, more[0], y, ypro, more[1], fold, W, *bn, wgrad=fw)
         else:
@@ -1049,9 +1076,51 @@ class _Run:
                                f"{pt}.8.bias", self.W(f"{pt}.8.weight"), next_bn=nstats)
         return g, nstats.sums
 
-    def enc_bwd_b(self, enc: _EncPass, state, nstats: Optional["_NextStats"] = None):
+    def masked_handdown_applies(self, enc_b: _EncPass, state_b, enc_a: _EncPass, state_a) -> bool:
+        """Whether the two passes hand ONE masked gradient to their shared first BatchNorm (MASKED_HANDDOWN): both live,
+        pass B dense and pass A on listed rows, both producers the fused BatchNorm-backward + weight-gradient launch with
+        the masked store, and the consumer the fused launch as well.  Everything else keeps the two tensors."""
+        if not self.masked_handdown or state_b is None or state_a is None:
+            return False
+        if enc_b.rows is not None or enc_a.rows is None or enc_a.row_pos is None or "enc1" in self.next_bn_sites:
+            return False
+        if not self.fused_wgrad or enc_b.z1 is not enc_a.z1 or not enc_b.z1.is_contiguous() or not enc_b.E.is_contiguous():
+            return False
+        folds = (enc_b.f1, enc_b.f2, enc_a.f1, enc_a.f2)
+        if any(f is None or not f.training for f in folds):
+            return False
+        if any(q.relu not in (0, 1) for q in (enc_b.pro1, enc_b.pro2, enc_a.pro1, enc_a.pro2)):
+            return False
+        ename = f"embeddings.{ROW_TYPE}.weight"
+        if not self.params[ename].requires_grad or ename in self.grads:
+            return False
+        M = enc_b.z2.shape[0]
+        K, N = self.W("patient_transform.4.weight").shape
+        K1, N1 = self.W("patient_transform.0.weight").shape
+        return ops.linear_bnbwd_masked_supported(M, N, K, ops.BNBWD_BN) and \
+            ops.linear_bnbwd_masked_supported(M, N, K, ops.BNBWD_ROWS) and \
+            ops.linear_bnbwd_supported(M, N, K, ops.BNBWD_BN) and ops.linear_bnbwd_supported(M, N, K, ops.BNBWD_ROWS) and \
+            ops.linear_bnbwd_supported(M, N1, K1, ops.BNBWD_BN) and ops.linear_bnbwd_wgrad_supported(M, N1, K1)
+
+    def enc_bwd_shared_masked(self, enc: _EncPass, gs):
+        """enc_bwd_shared for the ONE gradient gs = drop_b(g_b) + drop_a(g_a) the masked producers left: the statistics and
+        the BatchNorm backward + first linear with the activation's select and no dropout."""
+        pt = "patient_transform"
+        y, fold = enc.z1, enc.f1
+        pro = replace(enc.pro1, p=0.0)
+        sums = ops.bn_bwd_stats(gs, y, pro, fold)
+        if self.comm is not None:
+            self.allreduce(sums)
+        fused = self.bn_lin_bwd("plain", (gs, y, pro, fold, sums, True), f"{pt}.1", enc.E, None, f"{pt}.0.weight",
+                                f"{pt}.0.bias", self.W(f"{pt}.0.weight"))
+        if fused is None:
+            raise RuntimeError("enc_bwd_shared_masked: the fused BatchNorm-backward launch does not apply")
+        self.acc(f"embeddings.{ROW_TYPE}.weight", fused[1])
+
+    def enc_bwd_b(self, enc: _EncPass, state, nstats: Optional["_NextStats"] = None, masked: Optional[ops.MaskedDx] = None):
         """...and from the (all-reduced) statistics on to the upstream gradient of the first BatchNorm.
-        nstats: holder of that BatchNorm's backward statistics; a fused producer adds its share (this pass's mask)."""
+        nstats: holder of that BatchNorm's backward statistics; a fused producer adds its share (this pass's mask).
+        masked: the producer stores that gradient under this pass's dropout mask (masked_handdown_applies)."""
         if state is None:
             return None
         pt = "patient_transform"
@@ -1064,9 +1133,11 @@ class _Run:
         form, args = ("rows", (g, y, pro, fold, sums, enc.row_pos)) if enc.rows is not None else \
             ("plain", (g, y, pro, fold, sums, True))
         fused = self.bn_lin_bwd(form, args, f"{pt}.5", enc.z1, enc.pro1, f"{pt}.4.weight", f"{pt}.4.bias",
-                                self.W(f"{pt}.4.weight"), next_bn=nstats)
+                                self.W(f"{pt}.4.weight"), next_bn=nstats, masked=masked)
         if fused is not None:
             return fused[1]
+        if masked is not None:
+            raise RuntimeError("enc_bwd_b: the fused BatchNorm-backward launch does not apply")
         if enc.rows is not None:
             # an upstream gradient that is zero outside the listed rows (training statistics): the dense apply pass never
             # reads a gradient tensor, the listed rows are patched afterwards

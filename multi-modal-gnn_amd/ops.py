@@ -874,19 +874,41 @@ _BNBWD_PROF = {BNBWD_BN: ("linear_bnbwd", 2), BNBWD_BN2: ("linear_bnbwd", 3), BN
                BNBWD_L2: ("linear_l2bwd", 2)}
 
 
+@dataclass
+class MaskedDx:
+    """The masked dx store of linear_bnbwd / linear_bnbwd_rows (mmg_linear_bnbwd_masked; needs wgrad): dx holds
+    dropout(dx) under the mask of `pro` -- which must be the dropout of wgrad.pro -- or, with `into`, that is ADDED to the
+    tensor `into` [M,N] (which the call returns as dx).  The consumer of dx applies the activation's select but no dropout."""
+    pro: Pro
+    into: Optional[torch.Tensor] = None
+
+
+def linear_bnbwd_masked_supported(M: int, N: int, K: int, mode: int = 0, wgrad: bool = True) -> bool:
+    return bool(_lib.load().mmg_linear_bnbwd_masked_supported(int(mode), int(M), int(N), int(K), int(wgrad)))
+
+
 def _linear_bnbwd(mode: int, y: torch.Tensor, W: torch.Tensor, next_bn: Optional["NextBN"], wgrad: Optional[FusedWgrad],
                   g=None, g2=None, row_pos=None, n_sel=0, pro: Optional[Pro] = None, pro2: Optional[Pro] = None,
-                  fold: Optional[BNFold] = None, sums=None, count: float = 1.0, dbeta=None, dgamma=None, rn=None):
-    """The one call behind linear_bnbwd / linear_bnbwd2 / linear_bnbwd_rows / linear_l2bwd (mmg_linear_bnbwd; the
-    descriptor fields as mmg_bnbwd_t names them).  -> (dz, dx), + the next BatchNorm's sums with next_bn."""
+                  fold: Optional[BNFold] = None, sums=None, count: float = 1.0, dbeta=None, dgamma=None, rn=None,
+                  masked: Optional[MaskedDx] = None):
+    """The one call behind linear_bnbwd / linear_bnbwd2 / linear_bnbwd_rows / linear_l2bwd (mmg_linear_bnbwd, or
+    mmg_linear_bnbwd_masked with `masked`; the descriptor fields as mmg_bnbwd_t names them).  -> (dz, dx), + the next
+    BatchNorm's sums with next_bn."""
     M, K = y.shape
     if W.shape[0] != K:
         raise ValueError(f"{_BNBWD_PROF[mode][0]}: W has {W.shape[0]} rows, y has {K} columns")
     N = W.shape[1]
+    if masked is not None:
+        if wgrad is None or next_bn is not None:
+            raise ValueError(f"{_BNBWD_PROF[mode][0]}: the masked dx store needs wgrad and takes no next_bn")
+        if masked.into is not None and (tuple(masked.into.shape) != (M, N) or masked.into.device != y.device):
+            raise ValueError(f"{_BNBWD_PROF[mode][0]}: masked.into is {tuple(masked.into.shape)} on {masked.into.device}, "
+                             f"expected [{M},{N}] on {y.device}")
     dz = torch.empty_like(y) if wgrad is None or wgrad.keep_dz else None
-    dx = torch.empty(M, N, device=y.device)
+    into = masked.into if masked is not None else None
+    dx = into if into is not None else torch.empty(M, N, device=y.device)
     name, reads = _BNBWD_PROF[mode]
-    nbytes = 4 * (reads * M * K + (M * K if dz is not None else 0) + M * N)
+    nbytes = 4 * (reads * M * K + (M * K if dz is not None else 0) + M * N * (2 if into is not None else 1))
     if wgrad is not None:
         name += "_wgrad"
         nbytes += _fused_wgrad_bytes(M, N, K) + (4 * M if mode == BNBWD_L2 else 0)       # + rn
@@ -900,8 +922,13 @@ def _linear_bnbwd(mode: int, y: torch.Tensor, W: torch.Tensor, next_bn: Optional
                   *[C.pointer(pc) if pc is not None else None for pc in pcs],
                   _p(fold.mean) if fold else None, _p(fold.rstd) if fold else None, _p(sums, torch.float64),
                   1.0 / float(count), _p(dbeta), _p(dgamma), _p(rn), L2_EPS)
-    _call("mmg_linear_bnbwd", C.byref(desc), W, dz, dx, M, N, K, C.byref(nbt) if nbt is not None else None,
-          C.byref(wt) if wt is not None else None)
+    if masked is not None:
+        mpc = masked.pro.c()
+        _call("mmg_linear_bnbwd_masked", C.byref(desc), W, dz, dx, M, N, K, C.byref(mpc), int(masked.into is not None),
+              C.byref(wt))
+    else:
+        _call("mmg_linear_bnbwd", C.byref(desc), W, dz, dx, M, N, K, C.byref(nbt) if nbt is not None else None,
+              C.byref(wt) if wt is not None else None)
     if wgrad is not None:
         _fused_wgrad_done(wgrad, wt)
     _pe(_tok, name, nbytes, (4 if wgrad is not None else 2) * M * N * K)
@@ -910,13 +937,14 @@ def _linear_bnbwd(mode: int, y: torch.Tensor, W: torch.Tensor, next_bn: Optional
 
 def linear_bnbwd(g: torch.Tensor, y: torch.Tensor, pro: Pro, fold: Optional[BNFold], W: torch.Tensor, sums=None,
                  count: float = 1.0, dbeta=None, dgamma=None, next_bn: Optional["NextBN"] = None,
-                 wgrad: Optional[FusedWgrad] = None):
+                 wgrad: Optional[FusedWgrad] = None, masked: Optional[MaskedDx] = None):
     """bn_bwd_apply(g, y, ...) and the data gradient dz @ W of the linear in front of that BatchNorm in ONE pass over g and
     y (mmg_linear_bnbwd): -> (dz [M,K], dx [M,N]).  W [K, N] is the forward weight of the linear, read in place.
     next_bn: + the statistics of the BatchNorm backward that consumes dx (see NextBN).
-    wgrad: the layer's weight gradient in the same launch (see FusedWgrad)."""
+    wgrad: the layer's weight gradient in the same launch (see FusedWgrad).
+    masked: dx is stored under, or added under, a dropout mask (see MaskedDx; linear_bnbwd_masked_supported)."""
     return _linear_bnbwd(BNBWD_BN, y, W, next_bn, wgrad, g=g, pro=pro, fold=fold, sums=sums, count=count, dbeta=dbeta,
-                         dgamma=dgamma)
+                         dgamma=dgamma, masked=masked)
 
 
 def linear_bnbwd2_supported(M: int, N: int, K: int) -> bool:
@@ -933,12 +961,13 @@ def linear_bnbwd2(g: torch.Tensor, g2: torch.Tensor, y: torch.Tensor, pro: Pro, 
 
 def linear_bnbwd_rows(g_rows: torch.Tensor, row_pos: torch.Tensor, y: torch.Tensor, pro: Pro, fold: BNFold, W: torch.Tensor,
                       sums, count, dbeta=None, dgamma=None, next_bn: Optional["NextBN"] = None,
-                      wgrad: Optional[FusedWgrad] = None):
+                      wgrad: Optional[FusedWgrad] = None, masked: Optional[MaskedDx] = None):
     """bn_bwd_apply(None, ...) + bn_bwd_apply_rows(g_rows, ...) + the data gradient dz @ W in one pass -> (dz, dx): the
     upstream gradient is zero outside the listed rows; row_pos [M] int32 = position of a row in the list or -1.
-    next_bn / wgrad: as for linear_bnbwd."""
+    next_bn / wgrad / masked: as for linear_bnbwd."""
     return _linear_bnbwd(BNBWD_ROWS, y, W, next_bn, wgrad, g=g_rows if g_rows.numel() else None, row_pos=row_pos,
-                         n_sel=g_rows.shape[0], pro=pro, fold=fold, sums=sums, count=count, dbeta=dbeta, dgamma=dgamma)
+                         n_sel=g_rows.shape[0], pro=pro, fold=fold, sums=sums, count=count, dbeta=dbeta, dgamma=dgamma,
+                         masked=masked)
 
 
 def linear_l2bwd(g: torch.Tensor, out: torch.Tensor, rn: torch.Tensor, W: torch.Tensor, next_bn: Optional["NextBN"] = None,
