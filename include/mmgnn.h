@@ -404,6 +404,21 @@ int mmg_linear_bnbwd(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX,
 int mmg_linear_bnbwd_masked_supported(int mode, int64_t M, int N, int K, int with_wgrad);
 int mmg_linear_bnbwd_masked(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
                             const mmg_prologue_t* mask, int accumulate, const mmg_bnbwd_wgrad_t* wg, void* stream);
+/* Both passes' masked launches of one layer in ONE launch -- the second linear of the encoder under the two dropout passes
+ * of a training step.  Bit for bit in every output (dX, both passes' slabs with their jobs, dW, dbias, dbeta, dgamma, and
+ * dZ where kept) the two calls
+ *   mmg_linear_bnbwd_masked(b, W, dZ_b, dX, M, N, K, wg_b->pro, 0, wg_b, stream)      b->mode == MMG_BNBWD_BN
+ *   mmg_linear_bnbwd_masked(a, W, dZ_a, dX, M, N, K, wg_a->pro, 1, wg_a, stream)      a->mode == MMG_BNBWD_ROWS
+ * with dX written once and never read back, the shared X [M, N] and W read once, and each 32-row tile walked through pass b
+ * and then pass a.  The passes stage one tile of X: wg_b->X == wg_a->X, and the two X prologues agree in everything but
+ * the dropout site (scale, shift, relu, drop_p, seed / seed_ptr, row_offset).  Each pass keeps its own slab workspace
+ * and job.  Other modes, a missing weight-gradient descriptor and whatever mmg_linear_bnbwd_masked refuses are refused
+ * with MMG_E_ARG before anything is launched.
+ * mmg_linear_bnbwd_dual_supported: K = N = 128, M > 512. */
+int mmg_linear_bnbwd_dual_supported(int64_t M, int N, int K);
+int mmg_linear_bnbwd_dual(const mmg_bnbwd_t* b, const mmg_bnbwd_wgrad_t* wg_b, const mmg_bnbwd_t* a,
+                          const mmg_bnbwd_wgrad_t* wg_a, const float* W, float* dZ_b, float* dZ_a, float* dX, int64_t M,
+                          int N, int K, void* stream);
 /* The data gradient AND the weight gradient of a plain linear in ONE launch -- the first layer of a pair head, whose
  * upstream gradient dY [M, K] is the gradient of the head's per-patient table (K = 64) and whose input X [M, N] is the
  * final patient activation (N = 128):
@@ -436,7 +451,9 @@ int mmg_linear_dgrad_wgrad(const float* dY, const float* W, float* dX, int64_t M
  *   4096 = the layer's weight gradient rides along (mmg_linear_dgrad_wgrad: the row is the data gradient's (M, 128, 64), with
  *   512 where the next-BatchNorm epilogue runs; priced as the data gradient alone, the launch also reads X [M, N] and does
  *   2 M N K FLOP more), 8192 = the masked dX store of mmg_linear_bnbwd_masked (beside the mode's own bits; an accumulating
- *   launch reads dX once more than its row prices).
+ *   launch reads dX once more than its row prices), 16384 = the dual backward of mmg_linear_bnbwd_dual (beside 16 | 128 | 1024 |
+ *   8192: four [M, 128] inputs -- G and y of pass b, y of pass a, X -- and one output price the launch, the listed rows of
+ *   pass a's G and the row list left out).
  * The hook is the library's only process-wide mutable state (mutex-guarded); the product path never arms it. */
 #define MMG_PROBE_LINEAR_FWD 1
 #define MMG_PROBE_LINEAR_WGRAD 2

@@ -919,20 +919,37 @@ struct BnWgDev {
   const float* X; ProDev xpr; float* slab; int64_t slab_stride; int bias_order;
 };
 static inline BnWgDev bn_wg_none() { return BnWgDev{nullptr, mmg_pro_dev(nullptr), nullptr, 0, 0}; }
+// MSK 3, the DUAL form (FW, MODE 0): BOTH passes' launches of one layer -- MSK 1 of MODE 0 (G, bb, pr, wg: "pass B") and then
+// MSK 2 of MODE 3 (the fields below: "pass A") on the same W, X and DX -- in one walk over the tiles.  The two bodies of the
+// peeled tile pair become the two passes of ONE tile: the body on LDS buffer 0 is pass B of tile t, the body on buffer 1
+// pass A of tile t.  Every register set that runs a tile ahead stays single and alternates between the passes; the dX
+// waves hold pass B's masked product in registers where MSK 2 holds the tile it re-read, so DX is written once and never
+// read; the X stagers fetch, fold and scale a tile once and mask its pieces with each pass's keep bits (split(0) = three
+// +0 pieces, as in k_linear_fwd_x6_dual); the dW waves keep one accumulator set and one slab series per pass, each fed
+// the fragments and the order of its own launch.  The per-column BatchNorm constants of both passes live in an LDS table
+// behind the keep bits.  Every output is that of the two launches bit for bit.
+struct BnDualDev {
+  const float* G; BnBwdDev bb; ProDev pr; BnWgDev wg;
+};
+static inline BnDualDev bn_dual_none() { return BnDualDev{nullptr, BnBwdDev{}, mmg_pro_dev(nullptr), bn_wg_none()}; }
+template <int V> struct PassMode { static constexpr int value = V; };      // a pass's MODE as a compile-time lambda argument
 
 template <int K, int WN, int MODE = 0, bool NBN = false, bool FW = false, int MSK = 0>
 __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) void k_linear_bnbwd_x6(
     const float* __restrict__ G, BnBwdDev bb, ProDev pr, const float* __restrict__ W, float* __restrict__ DX, int64_t M,
-    ProDev pr2, NextBnDev nb, double* __restrict__ stat_partial, BnWgDev wg) {
+    ProDev pr2, NextBnDev nb, double* __restrict__ stat_partial, BnWgDev wg, BnDualDev du) {
   static_assert(!FW || (K == 128 && WN == 4), "the fused weight gradient covers K = N = 128");
   static_assert(MSK == 0 || (FW && !NBN && (MODE == 0 || MODE == 3)), "the masked dX store rides on the X stagers' hashes");
+  static_assert(MSK != 3 || MODE == 0, "the dual form: pass B is MODE 0, pass A MODE 3");
+  constexpr bool DUAL = MSK == 3;
   if (MODE != 1) pr.resolve();
   if (MODE == 2) pr2.resolve();
   if (FW) wg.xpr.resolve();
+  if (DUAL) { du.pr.resolve(); du.wg.xpr.resolve(); }
   constexpr int LDP = K + 8, N = 32 * WN, NK = K / 16, NTHR = 64 * WN, BM = 32;
   constexpr int SX = N + 32;               // X plane row stride (FW): +64 B puts the 4 rows of a transposing read on disjoint banks
   constexpr int KBS = BM + 4;              // keep-bit row stride (MSK): [column quad][tile row] bytes, +4 B spreads the quads over the banks
-  extern __shared__ __attribute__((aligned(16))) __bf16 planes[];     // [2 buffers][3 pieces][BM][LDP] (FW: + [2][3][BM][SX] of X; MSK: + [2][N / 4][KBS] keep bits)
+  extern __shared__ __attribute__((aligned(16))) __bf16 planes[];     // [2 buffers][3 pieces][BM][LDP] (FW: + [2][3][BM][SX] of X; MSK: + [2][N / 4][KBS] keep bits; MSK 3: + the constants table)
   const int tid = threadIdx.x, lane = tid & 63, wn = tid >> 6;
   const int h = lane >> 5, l31 = lane & 31;
   const int col = wn * 32 + l31;
@@ -958,29 +975,55 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
   const int prow = tid / K4;
   const f32x4 one = {1.f, 1.f, 1.f, 1.f}, zero = {0.f, 0.f, 0.f, 0.f};
   f32x4 sc = one, sh = zero, mu = zero, rs = one, a0 = zero, a1 = zero;
-  if (MODE != 1 && pr.scale) {
-    sc = *reinterpret_cast<const f32x4*>(pr.scale + c); sh = *reinterpret_cast<const f32x4*>(pr.shift + c);
-    mu = *reinterpret_cast<const f32x4*>(bb.mean + c); rs = *reinterpret_cast<const f32x4*>(bb.rstd + c);
-    if (bb.sums) {
+  auto col_consts = [&](const ProDev& p_, const BnBwdDev& b_) __attribute__((always_inline)) {
+    sc = one; sh = zero; mu = zero; rs = one; a0 = zero; a1 = zero;
+    if (MODE != 1 && p_.scale) {
+      sc = *reinterpret_cast<const f32x4*>(p_.scale + c); sh = *reinterpret_cast<const f32x4*>(p_.shift + c);
+      mu = *reinterpret_cast<const f32x4*>(b_.mean + c); rs = *reinterpret_cast<const f32x4*>(b_.rstd + c);
+      if (b_.sums) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        a0[j] = (float)(bb.sums[c + j] * bb.inv_count);
-        a1[j] = (float)(bb.sums[K + c + j] * bb.inv_count);
+        for (int j = 0; j < 4; ++j) {
+          a0[j] = (float)(b_.sums[c + j] * b_.inv_count);
+          a1[j] = (float)(b_.sums[K + c + j] * b_.inv_count);
+        }
       }
     }
+  };
+  // DUAL: [pass][sc, sh, mu, rs, a0, a1][K] behind the keep bits, read by `stage` (a second register set does not fit)
+  float* const ctab = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(planes) + 2 * 3 * BM * LDP * 2 +
+                                               2 * 3 * BM * SX * 2 + 2 * (N / 4) * KBS);
+  if constexpr (DUAL) {
+    if (tid < K4) {
+#pragma unroll
+      for (int ps = 0; ps < 2; ++ps) {
+        col_consts(ps ? du.pr : pr, ps ? du.bb : bb);
+        const f32x4 six[6] = {sc, sh, mu, rs, a0, a1};
+#pragma unroll
+        for (int e = 0; e < 6; ++e) *reinterpret_cast<f32x4*>(ctab + (ps * 6 + e) * K + c) = six[e];
+      }
+      // + the fold of the X prologue [scale, shift][N] for the X stagers, whose second accumulator set leaves no room for it
+      *reinterpret_cast<f32x4*>(ctab + 12 * K + c) = wg.xpr.scale ? *reinterpret_cast<const f32x4*>(wg.xpr.scale + c) : one;
+      *reinterpret_cast<f32x4*>(ctab + 12 * K + N + c) = wg.xpr.scale ? *reinterpret_cast<const f32x4*>(wg.xpr.shift + c) : zero;
+    }
+    __syncthreads();
+  } else {
+    col_consts(pr, bb);
   }
   // (the row-set index through readfirstlane: behind the lane-dependent branch below the compiler otherwise carries
   //  blockIdx.y -- known to be 0 inside it -- in a VECTOR register, every tile index and buffer descriptor derived from it
   //  becomes "divergent", and each of the ~135 buffer accesses of the kernel is wrapped in a waterfall loop)
   const int by_u = __builtin_amdgcn_readfirstlane((int)blockIdx.y);
-  if (MODE != 1 && bb.sums && by_u == 0 && tid < K4) {          // d beta / d gamma ride along
+  auto ride = [&](const BnBwdDev& b_) __attribute__((always_inline)) {      // d beta / d gamma ride along
+    if (MODE != 1 && b_.sums && by_u == 0 && tid < K4) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (bb.dbeta) bb.dbeta[c + j] = (float)bb.sums[c + j];
-      if (bb.dgamma) bb.dgamma[c + j] = (float)bb.sums[K + c + j];
+      for (int j = 0; j < 4; ++j) {
+        if (b_.dbeta) b_.dbeta[c + j] = (float)b_.sums[c + j];
+        if (b_.dgamma) b_.dgamma[c + j] = (float)b_.sums[K + c + j];
+      }
     }
-  }
-  const bool relu = MODE != 1 && pr.relu == MMG_ACT_RELU, drop = MODE != 1 && pr.p > 0.f, has_bn = MODE != 1 && pr.scale != nullptr;
+  };
+  ride(bb);
+  if constexpr (DUAL) ride(du.bb);
   const bool drop2 = MODE == 2 && pr2.p > 0.f;
   const int64_t n_tiles = (M + BM - 1) / BM;
   const int64_t GY = gridDim.y, t0 = by_u;
@@ -992,21 +1035,27 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
   };
   f32x4 ng[NP], ny[NP], ng2[MODE == 2 ? NP : 1];      // the NEXT tile of G and Y (and G2)
   const int xvo = (prow * K + kc4 * 4) * 4;
-  int ridx[MODE == 3 ? NP : 1];             // MODE 3: list positions of the rows of the tile the NEXT fetch serves
+  const BnBwdDev& bbr = DUAL ? du.bb : bb;     // the pass with the row list
+  int ridx[MODE == 3 || DUAL ? NP : 1];             // MODE 3: list positions of the rows of the tile the NEXT fetch serves
   auto fetch_idx = [&](int64_t tile) __attribute__((always_inline)) {
     const int rows = rows_of(tile);
-    const __amdgpu_buffer_rsrc_t ps = mmg_rsrc(bb.row_pos + (size_t)(rows ? tile : 0) * BM, rows * 4);
+    const __amdgpu_buffer_rsrc_t ps = mmg_rsrc(bbr.row_pos + (size_t)(rows ? tile : 0) * BM, rows * 4);
 #pragma unroll
     for (int p = 0; p < NP; ++p) ridx[p] = rows ? (int)__builtin_amdgcn_raw_buffer_load_b32(ps, (p * ROWS_PER_PASS + prow) * 4, 0, 0) : -1;
   };
-  auto fetch = [&](int64_t tile) __attribute__((always_inline)) {
+  // (pm: the MODE of the pass the call serves -- MODE itself, or in the dual form 0 for pass B and 3 for pass A)
+  auto fetch = [&](int64_t tile, auto pm) __attribute__((always_inline)) {
+    constexpr int PM = decltype(pm)::value;
+    constexpr bool second = DUAL && PM == 3;
+    const BnBwdDev& b_ = second ? du.bb : bb;
+    const float* const G_ = second ? du.G : G;
     const int rows = rows_of(tile);
     const size_t off = (size_t)(rows ? tile : 0) * BM * K;
-    const __amdgpu_buffer_rsrc_t ysrc = mmg_rsrc(bb.Y + off, rows * K * 4);
-    if constexpr (MODE == 3) {
+    const __amdgpu_buffer_rsrc_t ysrc = mmg_rsrc(b_.Y + off, rows * K * 4);
+    if constexpr (PM == 3) {
       // the listed rows through one descriptor over the whole list: a row that is not listed (or past the end) gets an
       // offset behind the list and reads 0
-      const __amdgpu_buffer_rsrc_t gs = mmg_rsrc(G, (int)(bb.n_sel * K * 4));
+      const __amdgpu_buffer_rsrc_t gs = mmg_rsrc(G_, (int)(b_.n_sel * K * 4));
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
         const unsigned vo = ridx[p] >= 0 && p * ROWS_PER_PASS + prow < rows ? (unsigned)ridx[p] * (unsigned)(K * 4) + (unsigned)(kc4 * 16) : 0xFFFFFF00u;
@@ -1016,7 +1065,7 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
       fetch_idx(tile + GY);
       return;
     }
-    const __amdgpu_buffer_rsrc_t gs = mmg_rsrc(G + off, rows * K * 4);
+    const __amdgpu_buffer_rsrc_t gs = mmg_rsrc(G_ + off, rows * K * 4);
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
       ng[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(gs, xvo, p * ROWS_PER_PASS * K * 4, MMG_NT_LD));
@@ -1029,10 +1078,21 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
         ng2[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(g2s, xvo, p * ROWS_PER_PASS * K * 4, MMG_NT_LD));
     }
   };
-  auto stage = [&](int64_t tile, int buf) __attribute__((always_inline)) {   // BatchNorm backward of the tile in ng / ny, dZ out, split, three plane writes
+  auto stage = [&](int64_t tile, int buf, auto pm) __attribute__((always_inline)) {   // BatchNorm backward of the tile in ng / ny, dZ out, split, three plane writes
+    constexpr bool second = DUAL && decltype(pm)::value == 3;
+    const BnBwdDev& b_ = second ? du.bb : bb;
+    const ProDev& pr_ = second ? du.pr : pr;
+    const bool relu = MODE != 1 && pr_.relu == MMG_ACT_RELU, drop = MODE != 1 && pr_.p > 0.f, has_bn = MODE != 1 && pr_.scale != nullptr;
+    f32x4 sc_ = sc, sh_ = sh, mu_ = mu, rs_ = rs, a0_ = a0, a1_ = a1;
+    if constexpr (DUAL) {
+      const float* ct = ctab + (second ? 6 * K : 0) + c;
+      sc_ = *reinterpret_cast<const f32x4*>(ct); sh_ = *reinterpret_cast<const f32x4*>(ct + K);
+      mu_ = *reinterpret_cast<const f32x4*>(ct + 2 * K); rs_ = *reinterpret_cast<const f32x4*>(ct + 3 * K);
+      a0_ = *reinterpret_cast<const f32x4*>(ct + 4 * K); a1_ = *reinterpret_cast<const f32x4*>(ct + 5 * K);
+    }
     const int64_t row0 = tile * BM;
     const int rows = rows_of(tile);
-    const __amdgpu_buffer_rsrc_t zs = mmg_rsrc(bb.dZ + (size_t)(rows && bb.dZ ? tile : 0) * BM * K, bb.dZ ? rows * K * 4 : 0);
+    const __amdgpu_buffer_rsrc_t zs = mmg_rsrc(b_.dZ + (size_t)(rows && b_.dZ ? tile : 0) * BM * K, b_.dZ ? rows * K * 4 : 0);
     __bf16* pb = planes + (size_t)buf * 3 * BM * LDP;
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
@@ -1046,8 +1106,8 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
 #pragma unroll
         for (int o = 1; o < K4; o <<= 1) dot += __shfl_xor(dot, o, 64);      // the K / 4 lanes of a row are adjacent
         const int64_t grow = row0 + r;
-        const float rr = grow < M ? bb.mean[grow] : 0.f;
-        if (!(rr * bb.l2_eps < 1.0f)) dot = 0.f;           // ||z|| <= eps: the denominator was the constant eps
+        const float rr = grow < M ? b_.mean[grow] : 0.f;
+        if (!(rr * b_.l2_eps < 1.0f)) dot = 0.f;           // ||z|| <= eps: the denominator was the constant eps
 #pragma unroll
         for (int j = 0; j < 4; ++j) gm[j] = rr * (gm[j] - y4[j] * dot);
       }
@@ -1056,12 +1116,12 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
       if (relu) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float act = has_bn ? fmaf(y4[j], sc[j], sh[j]) : y4[j];
+          const float act = has_bn ? fmaf(y4[j], sc_[j], sh_[j]) : y4[j];
           if (!(act > 0.f)) { gm[j] = 0.f; gm2[j] = 0.f; }
         }
       }
       if (drop)
-        mmg_drop4(gm, pr.key, (uint64_t)(pr.row_offset + row0 + r) * (uint64_t)K + (uint64_t)c, pr.thr, pr.inv_keep);
+        mmg_drop4(gm, pr_.key, (uint64_t)(pr_.row_offset + row0 + r) * (uint64_t)K + (uint64_t)c, pr_.thr, pr_.inv_keep);
       if constexpr (MODE == 2) {
         if (drop2)
           mmg_drop4(gm2, pr2.key, (uint64_t)(pr2.row_offset + row0 + r) * (uint64_t)K + (uint64_t)c, pr2.thr, pr2.inv_keep);
@@ -1071,8 +1131,8 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
       for (int j = 0; j < 4; ++j) {
         float g = gm[j];
         if (has_bn) {
-          const float xh = (y4[j] - mu[j]) * rs[j];
-          g = sc[j] * (g - a0[j] - xh * a1[j]);
+          const float xh = (y4[j] - mu_[j]) * rs_[j];
+          g = sc_[j] * (g - a0_[j] - xh * a1_[j]);
         }
         v[j] = g;
       }
@@ -1104,7 +1164,7 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
     f32x4 xsc = one, xsh = zero;
     float xfloor = -__builtin_inff();
     const bool xaff = wg.xpr.scale != nullptr || wg.xpr.relu, xdrop = wg.xpr.p > 0.f;
-    if (wg.xpr.scale) {
+    if (!DUAL && wg.xpr.scale) {
       xsc = *reinterpret_cast<const f32x4*>(wg.xpr.scale + xc4 * 4);
       xsh = *reinterpret_cast<const f32x4*>(wg.xpr.shift + xc4 * 4);
     }
@@ -1140,53 +1200,142 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
         *reinterpret_cast<bf16x4*>(xb + (2 * BM + r) * SX + xc4 * 4) = q2;
       }
     };
+    // DUAL: the tile in nx goes through the affine, the ReLU and the scaling ONCE (xscale, in place: the product rounded
+    // before the split -- an empty asm keeps it a multiply, see k_linear_fwd_x6_dual) and stays in nx while each pass
+    // masks its pieces with its own keep bits (xput: the hash of mmg_drop4_bits under the pass's key; a dropped element
+    // is three +0 pieces, split(0)) into the buffer its body multiplies, the keep bytes beside them as xstage leaves them
+    auto xscale = [&]() __attribute__((always_inline)) {
+      const f32x4 xsc = *reinterpret_cast<const f32x4*>(ctab + 12 * K + xc4 * 4);
+      const f32x4 xsh = *reinterpret_cast<const f32x4*>(ctab + 12 * K + N + xc4 * 4);
+#pragma unroll
+      for (int u = 0; u < XU; ++u)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float s = nx[u][j];
+          if (xaff) s = fmaxf(fmaf(s, xsc[j], xsh[j]), xfloor);
+          if (xdrop) {
+            s *= wg.xpr.inv_keep;
+            asm("" : "+v"(s));
+          }
+          nx[u][j] = s;
+        }
+    };
+    auto xput = [&](int64_t tile, int buf, uint32_t key) __attribute__((always_inline)) {
+      __bf16* xb = xplanes + (size_t)buf * 3 * BM * SX;
+#pragma unroll
+      for (int u = 0; u < XU; ++u) {
+        const int r = xr + u * (NTHR / 32);
+        u32x2 km = {0xFFFFFFFFu, 0xFFFFFFFFu};
+        uint32_t kb = 0xFu;
+        if (xdrop) {
+          uint32_t w0, w1;
+          mmg_rng_group(key, ((uint64_t)(wg.xpr.row_offset + tile * BM + r) * (uint64_t)N + (uint64_t)(xc4 * 4)) >> 2, &w0, &w1);
+          const bool k0 = MMG_KEPT(w0, w1, 0, wg.xpr.thr), k1 = MMG_KEPT(w0, w1, 1, wg.xpr.thr),
+                     k2 = MMG_KEPT(w0, w1, 2, wg.xpr.thr), k3 = MMG_KEPT(w0, w1, 3, wg.xpr.thr);
+          km[0] = (k0 ? 0x0000FFFFu : 0u) | (k1 ? 0xFFFF0000u : 0u);
+          km[1] = (k2 ? 0x0000FFFFu : 0u) | (k3 ? 0xFFFF0000u : 0u);
+          kb = (k0 ? 1u : 0u) | (k1 ? 2u : 0u) | (k2 ? 4u : 0u) | (k3 ? 8u : 0u);
+        }
+        keepb[(buf * (N / 4) + xc4) * KBS + r] = (unsigned char)kb;
+        bf16x4 q0, q1, q2;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) MMG_SPLIT3(nx[u][j], q0[j], q1[j], q2[j]);
+        *reinterpret_cast<u32x2*>(xb + (0 * BM + r) * SX + xc4 * 4) = __builtin_bit_cast(u32x2, q0) & km;
+        *reinterpret_cast<u32x2*>(xb + (1 * BM + r) * SX + xc4 * 4) = __builtin_bit_cast(u32x2, q1) & km;
+        *reinterpret_cast<u32x2*>(xb + (2 * BM + r) * SX + xc4 * 4) = __builtin_bit_cast(u32x2, q2) & km;
+      }
+    };
     // wave w owns the quadrant (w >> 1, w & 1) of dW [K, N]; transposing-read lane roles as in k_linear_wgrad_x6
     const int qn = w >> 1, qk = w & 1;
     const int g4 = lane >> 4, q = (lane >> 2) & 3, p4 = lane & 3;
     const int tr_row = 8 * (g4 >> 1) + q, tr_col = 16 * (g4 & 1) + 4 * p4;
-    f32x16 wacc[2][2];
+    constexpr int NPS = DUAL ? 2 : 1;               // passes: an accumulator set, bias partials and a slab series each
+    f32x16 wacc[NPS][2][2];
     // the column sums of dZ (the bias gradient) as the partial sums the separate kernel keeps (see BnWgDev), each row
     // reassembled from the three planes.  bias_order 0: thread t owns group t >> 6 and the columns 2 (t & 63) + 0..1;
     // 1: thread t owns residue t >> 4 and the columns 8 (t & 15) + 0..7 (one ds_read_b128 per plane and row)
-    const bool has_bias = wg.slab_stride > (int64_t)K * N;
     const int bg = wg.bias_order == 0 ? t >> 6 : t >> 4;
     const int bc0 = wg.bias_order == 0 ? 2 * (t & 63) : 8 * (t & 15);
-    float bacc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float bacc[NPS][8];
 #pragma unroll
-    for (int x = 0; x < 2; ++x)
+    for (int ps = 0; ps < NPS; ++ps) {
 #pragma unroll
-      for (int y = 0; y < 2; ++y)
+      for (int e = 0; e < 8; ++e) bacc[ps][e] = 0.f;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) wacc[x][y][i] = 0.f;
+      for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) wacc[ps][x][y][i] = 0.f;
+    }
     xfetch(t0);
-    xstage(t0, 0);
-    xfetch(t0 + GY);
+    if constexpr (DUAL) {
+      xscale();
+      xput(t0, 0, wg.xpr.key);
+    } else {
+      xstage(t0, 0);
+      xfetch(t0 + GY);
+    }
     __syncthreads();
-    auto wbody = [&](int64_t tt, int buf) __attribute__((always_inline)) {
-      xstage(tt + GY, buf ^ 1);
-      xfetch(tt + 2 * GY);
-      __builtin_amdgcn_sched_barrier(0);
+    auto wbody = [&](int64_t tt, int buf, auto pm) __attribute__((always_inline)) {
+      constexpr int ps = DUAL && decltype(pm)::value == 3 ? 1 : 0;
+      const bool has_bias = (ps ? du.wg.slab_stride : wg.slab_stride) > (int64_t)K * N;
+      // the products first and the staging behind them -- the dZ wave that shares the SIMD stages first and multiplies
+      // second, so one wave's vector work runs under the other's matrix work instead of both queueing for the same pipe
+      // (either order is free: a body reads buf and writes buf ^ 1)
+      auto xwork = [&]() __attribute__((always_inline)) {
+        if constexpr (!DUAL) {
+          xstage(tt + GY, buf ^ 1);
+          xfetch(tt + 2 * GY);
+        } else if constexpr (ps == 0) {          // pass B of tile tt: its planes of pass A, then nx is free for the next tile
+          xput(tt, 1, du.wg.xpr.key);
+          xfetch(tt + GY);
+        } else {                                 // pass A of tile tt: the next tile, and its planes of pass B
+          xscale();
+          xput(tt + GY, 0, wg.xpr.key);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      };
       const __bf16* zb = planes + (size_t)buf * 3 * BM * LDP + tr_row * LDP + qn * 64 + tr_col;
       const __bf16* xb = xplanes + (size_t)buf * 3 * BM * SX + tr_row * SX + qk * 64 + tr_col;
 #pragma unroll
       for (int ks = 0; ks < BM / 16; ++ks) {
         bf16x8 fa[2][3], fb[2][3];
-#pragma unroll
-        for (int x = 0; x < 2; ++x)
-#pragma unroll
-          for (int pc = 0; pc < 3; ++pc) {
-            fa[x][pc] = tr_frag(zb + pc * BM * LDP + ks * 16 * LDP + x * 32, LDP);
-            fb[x][pc] = tr_frag(xb + pc * BM * SX + ks * 16 * SX + x * 32, SX);
-          }
         // small terms first, the order of k_linear_wgrad_ws / k_linear_wgrad_x6 for every accumulator
         constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+        if constexpr (DUAL) {
+          // the dZ fragments one x half at a time (12 registers less in flight beside the second accumulator set); every
+          // accumulator still takes its six products in the order above
 #pragma unroll
-        for (int tm = 0; tm < 6; ++tm)
+          for (int y = 0; y < 2; ++y)
+#pragma unroll
+            for (int pc = 0; pc < 3; ++pc) fb[y][pc] = tr_frag(xb + pc * BM * SX + ks * 16 * SX + y * 32, SX);
+#pragma unroll
+          for (int x = 0; x < 2; ++x) {
+#pragma unroll
+            for (int pc = 0; pc < 3; ++pc) fa[0][pc] = tr_frag(zb + pc * BM * LDP + ks * 16 * LDP + x * 32, LDP);
+#pragma unroll
+            for (int tm = 0; tm < 6; ++tm)
+#pragma unroll
+              for (int y = 0; y < 2; ++y)
+                wacc[ps][x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0][PA[tm]], fb[y][PB[tm]], wacc[ps][x][y], 0, 0, 0);
+          }
+        } else {
 #pragma unroll
           for (int x = 0; x < 2; ++x)
 #pragma unroll
-            for (int y = 0; y < 2; ++y)
-              wacc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[x][PA[tm]], fb[y][PB[tm]], wacc[x][y], 0, 0, 0);
+            for (int pc = 0; pc < 3; ++pc) {
+              fa[x][pc] = tr_frag(zb + pc * BM * LDP + ks * 16 * LDP + x * 32, LDP);
+              fb[x][pc] = tr_frag(xb + pc * BM * SX + ks * 16 * SX + x * 32, SX);
+            }
+#pragma unroll
+          for (int tm = 0; tm < 6; ++tm)
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+              for (int y = 0; y < 2; ++y)
+                wacc[ps][x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[x][PA[tm]], fb[y][PB[tm]], wacc[ps][x][y], 0, 0, 0);
+        }
       }
       if (has_bias) {
         const __bf16* zp = planes + (size_t)buf * 3 * BM * LDP + bc0;
@@ -1199,7 +1348,7 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
             const bf16x2 b = *reinterpret_cast<const bf16x2*>(zp + (BM + r) * LDP);
             const bf16x2 c = *reinterpret_cast<const bf16x2*>(zp + (2 * BM + r) * LDP);
 #pragma unroll
-            for (int e = 0; e < 2; ++e) bacc[e] += ((float)a[e] + (float)b[e]) + (float)c[e];
+            for (int e = 0; e < 2; ++e) bacc[ps][e] += ((float)a[e] + (float)b[e]) + (float)c[e];
           }
         } else {                               // k_linear_wgrad_x6: residue q, rows q then q + 16
 #pragma unroll
@@ -1209,53 +1358,77 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
             const bf16x8 b = *reinterpret_cast<const bf16x8*>(zp + (BM + r) * LDP);
             const bf16x8 c = *reinterpret_cast<const bf16x8*>(zp + (2 * BM + r) * LDP);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) bacc[e] += ((float)a[e] + (float)b[e]) + (float)c[e];
+            for (int e = 0; e < 8; ++e) bacc[ps][e] += ((float)a[e] + (float)b[e]) + (float)c[e];
           }
         }
       }
+      __builtin_amdgcn_sched_barrier(0);
+      xwork();
       __syncthreads();                         // buf fully read, buf^1 fully written
     };
-    wbody(t0, 0);
-    wbody(t0 + GY, 1);
-    for (int i = 2; i < n_my; i += 2) {
-      wbody(t0 + (int64_t)i * GY, 0);
-      wbody(t0 + (int64_t)(i + 1) * GY, 1);
+    if constexpr (DUAL) {                      // every tile of the row set: pass B on buffer 0, then pass A on buffer 1
+      for (int i = 0; i < n_my; ++i) {
+        wbody(t0 + (int64_t)i * GY, 0, PassMode<0>{});
+        wbody(t0 + (int64_t)i * GY, 1, PassMode<3>{});
+      }
+    } else {
+      wbody(t0, 0, PassMode<MODE>{});
+      wbody(t0 + GY, 1, PassMode<MODE>{});
+      for (int i = 2; i < n_my; i += 2) {
+        wbody(t0 + (int64_t)i * GY, 0, PassMode<MODE>{});
+        wbody(t0 + (int64_t)(i + 1) * GY, 1, PassMode<MODE>{});
+      }
     }
     if constexpr (NBN) __syncthreads();        // pairs with the barrier of the statistics epilogue below
-    if (has_bias) {                            // the partial sums -> the X planes (dead: every wave passed the last barrier)
-      float* red = reinterpret_cast<float*>(xplanes);          // [group / residue][K]
-      const int np = wg.bias_order == 0 ? 2 : 8;
 #pragma unroll
-      for (int e = 0; e < 8; ++e)
-        if (e < np) red[bg * K + bc0 + e] = bacc[e];
+    for (int ps = 0; ps < NPS; ++ps) {
+      const BnWgDev& w_ = ps ? du.wg : wg;
+      if (w_.slab_stride > (int64_t)K * N) {   // the partial sums -> the X planes (dead: every wave passed the last barrier)
+        float* red = reinterpret_cast<float*>(xplanes) + ps * 16 * K;          // [pass][group / residue][K]
+        const int np = wg.bias_order == 0 ? 2 : 8;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (e < np) red[bg * K + bc0 + e] = bacc[ps][e];
+      }
+      // slab[row-set][K * N (+ K column sums of dZ)]
+      float* dst = w_.slab + (size_t)by_u * w_.slab_stride;
+#pragma unroll
+      for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int n = qn * 64 + x * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+            const int k = qk * 64 + y * 32 + l31;
+            dst[(size_t)n * N + k] = wacc[ps][x][y][i];
+          }
     }
-    // slab[row-set][K * N (+ K column sums of dZ)]
-    float* dst = wg.slab + (size_t)by_u * wg.slab_stride;
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-      for (int y = 0; y < 2; ++y)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int n = qn * 64 + x * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-          const int k = qk * 64 + y * 32 + l31;
-          dst[(size_t)n * N + k] = wacc[x][y][i];
-        }
   } else {
-    if constexpr (MODE == 3) fetch_idx(t0);
-    fetch(t0);
-    stage(t0, 0);
-    fetch(t0 + GY);
+    if constexpr (MODE == 3 || DUAL) fetch_idx(t0);
+    fetch(t0, PassMode<MODE>{});
+    stage(t0, 0, PassMode<MODE>{});
+    if constexpr (DUAL) fetch(t0, PassMode<3>{});
+    else fetch(t0 + GY, PassMode<MODE>{});
     __syncthreads();
     const int yvo = ((4 * h) * N + wn * 32 + l31) * 4;     // C/D map: col = lane&31, row = (i&3) + 8*(i>>2) + 4*(lane>>5)
-    auto tile_body = [&](int64_t tt, int buf) __attribute__((always_inline)) {
+    float held[DUAL ? 16 : 1];                   // DUAL: pass B's masked product of the tile, until pass A adds its own
+    auto tile_body = [&](int64_t tt, int buf, auto pm) __attribute__((always_inline)) {
+      constexpr bool second = DUAL && decltype(pm)::value == 3;
       const int rows = rows_of(tt);
       const __amdgpu_buffer_rsrc_t xs = mmg_rsrc(DX + (size_t)(rows ? tt : 0) * BM * N, rows * N * 4);
       f32x16 acc;
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-      stage(tt + GY, buf ^ 1);                   // the other buffer: its readers passed the barrier of the last tile
-      fetch(tt + 2 * GY);
+      if constexpr (!DUAL) {
+        stage(tt + GY, buf ^ 1, pm);             // the other buffer: its readers passed the barrier of the last tile
+        fetch(tt + 2 * GY, pm);
+      } else if constexpr (!second) {            // pass B of tile tt: pass A's dZ of the same tile, pass B's inputs of the next
+        stage(tt, 1, PassMode<3>{});
+        fetch(tt + GY, PassMode<0>{});
+      } else {                                   // pass A of tile tt: pass B's dZ of the next tile, pass A's inputs of the next
+        stage(tt + GY, 0, PassMode<0>{});
+        fetch(tt + GY, PassMode<3>{});
+      }
       float nby[NBN ? 16 : 1];
       if constexpr (NBN) next_bn_load(nb, tt, rows, N, 0, yvo, nby);   // in flight under the products
       float old[MSK == 2 ? 16 : 1];              // MSK 2: the tile the masked store adds to, in flight under the products too
@@ -1290,12 +1463,15 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
             float s = acc[i] * wg.xpr.inv_keep;
             asm("" : "+v"(s));
             s = (kw >> (8 * j)) & 1u ? s : 0.f;
-            vv[i] = MSK == 2 ? old[i] + s : s;
+            if constexpr (DUAL && !second) held[i] = s;
+            else vv[i] = MSK == 2 ? old[i] + s : (DUAL ? held[i] + s : s);
           }
         }
+        if constexpr (!DUAL || second) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i)
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[i]), xs, yvo, mmg_c_row(i) * N * 4, MMG_NT_ST);
+          for (int i = 0; i < 16; ++i)
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[i]), xs, yvo, mmg_c_row(i) * N * 4, MMG_NT_ST);
+        }
       } else {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -1307,11 +1483,18 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
       if constexpr (NBN) next_bn_tile(nb, nbc, vv, nby, rows, tt * BM, N, col, lane, cs1, cs2);
       __syncthreads();                         // buf fully read, buf^1 fully written
     };
-    tile_body(t0, 0);
-    tile_body(t0 + GY, 1);
-    for (int i = 2; i < n_my; i += 2) {
-      tile_body(t0 + (int64_t)i * GY, 0);
-      tile_body(t0 + (int64_t)(i + 1) * GY, 1);
+    if constexpr (DUAL) {
+      for (int i = 0; i < n_my; ++i) {
+        tile_body(t0 + (int64_t)i * GY, 0, PassMode<0>{});
+        tile_body(t0 + (int64_t)i * GY, 1, PassMode<3>{});
+      }
+    } else {
+      tile_body(t0, 0, PassMode<MODE>{});
+      tile_body(t0 + GY, 1, PassMode<MODE>{});
+      for (int i = 2; i < n_my; i += 2) {
+        tile_body(t0 + (int64_t)i * GY, 0, PassMode<MODE>{});
+        tile_body(t0 + (int64_t)(i + 1) * GY, 1, PassMode<MODE>{});
+      }
     }
     if constexpr (NBN) {
       // two partials per column (the lane halves) -> one: partial[row-set][2][N], fixed order
@@ -1328,17 +1511,21 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
   if constexpr (FW) {
     __syncthreads();                           // the partial column sums of dZ are in LDS
     const int cc = tid - NTHR;
-    if (xrole && cc < K && wg.slab_stride > (int64_t)K * N) {
-      const float* red = reinterpret_cast<const float*>(planes + 2 * 3 * BM * LDP);
-      float v;
-      if (wg.bias_order == 0) {
-        v = ((red[cc] + red[K + cc]) + red[2 * K + cc]) + red[3 * K + cc];
-      } else {
-        v = 0.f;
 #pragma unroll
-        for (int qq = 0; qq < 16; ++qq) v += red[qq * K + cc];
+    for (int ps = 0; ps < (DUAL ? 2 : 1); ++ps) {
+      const BnWgDev& w_ = ps ? du.wg : wg;
+      if (xrole && cc < K && w_.slab_stride > (int64_t)K * N) {
+        const float* red = reinterpret_cast<const float*>(planes + 2 * 3 * BM * LDP) + ps * 16 * K;
+        float v;
+        if (wg.bias_order == 0) {
+          v = ((red[cc] + red[K + cc]) + red[2 * K + cc]) + red[3 * K + cc];
+        } else {
+          v = 0.f;
+#pragma unroll
+          for (int qq = 0; qq < 16; ++qq) v += red[qq * K + cc];
+        }
+        w_.slab[(size_t)by_u * w_.slab_stride + (size_t)K * N + cc] = v;
       }
-      wg.slab[(size_t)by_u * wg.slab_stride + (size_t)K * N + cc] = v;
     }
   }
 }
@@ -1359,7 +1546,7 @@ int launch_bnbwd_x6(const float* G, const BnBwdDev& bb, const ProDev& pr, const 
   MMG_CHECK_HIP((MmgMaxLds<&k_linear_bnbwd_x6<K, WN, MODE, NBN>, lds>::set()), "linear_bnbwd(attr)");
   MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, N, K, (MODE == 1 ? 64 : (MODE == 2 ? 16 | 128 : (MODE == 3 ? 16 | 256 : 16))) | (NBN ? 512 : 0),
              (k_linear_bnbwd_x6<K, WN, MODE, NBN>), dim3(1u, (unsigned)gy),
-             dim3(64 * WN), lds, st, G, bb, pr, W, DX, M, pr2, nb, stat_partial, bn_wg_none());
+             dim3(64 * WN), lds, st, G, bb, pr, W, DX, M, pr2, nb, stat_partial, bn_wg_none(), bn_dual_none());
   return 0;
 }
 
@@ -1848,7 +2035,7 @@ int launch_bnbwd_fw(const float* G, const BnBwdDev& bb, const ProDev& pr, const 
   MMG_CHECK_HIP((MmgMaxLds<&k_linear_bnbwd_x6<K, 4, MODE, false, true>, lds>::set()), "linear_bnbwd_wgrad(attr)");
   MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, N, K, (MODE == 1 ? 64 : (MODE == 2 ? 16 | 128 : (MODE == 3 ? 16 | 256 : 16))) | 1024,
              (k_linear_bnbwd_x6<K, 4, MODE, false, true>), dim3(1u, (unsigned)gy), dim3(512), lds, st, G, bb, pr, W, DX, M,
-             pr2, next_bn_none(), nullptr, wg);
+             pr2, next_bn_none(), nullptr, wg, bn_dual_none());
   return 0;
 }
 
@@ -1863,7 +2050,23 @@ int launch_bnbwd_fw_masked(const float* G, const BnBwdDev& bb, const ProDev& pr,
   MMG_CHECK_HIP((MmgMaxLds<&k_linear_bnbwd_x6<K, 4, MODE, false, true, MSK>, lds>::set()), "linear_bnbwd_masked(attr)");
   MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, N, K, (MODE == 3 ? 16 | 256 : 16) | 1024 | 8192,
              (k_linear_bnbwd_x6<K, 4, MODE, false, true, MSK>), dim3(1u, (unsigned)gy), dim3(512), lds, st, G, bb, pr, W, DX, M,
-             mmg_pro_dev(nullptr), next_bn_none(), nullptr, wg);
+             mmg_pro_dev(nullptr), next_bn_none(), nullptr, wg, bn_dual_none());
+  return 0;
+}
+
+// the dual form (MSK 3): pass B = MODE 0 / MSK 1 and pass A = MODE 3 / MSK 2 of the same layer in one launch; + the two
+// passes' BatchNorm constants and the X fold behind the keep bits (7 KB: 120 KB).  The row prices G_B, y_B, y_A and X in and dX out
+// (flag 128: one more [M, K] input); flag 16384 = dual backward
+int launch_bnbwd_fw_dual(const float* Gb, const BnBwdDev& bbb, const ProDev& prb, const BnWgDev& wgb, const float* Ga,
+                         const BnBwdDev& bba, const ProDev& pra, const BnWgDev& wga, const float* W, float* DX, int64_t M,
+                         hipStream_t st) {
+  constexpr int K = 128, N = 128;
+  const int64_t gy = bnbwd_fw_rows(M);
+  constexpr int lds = 2 * 3 * 32 * (K + 8) * 2 + 2 * 3 * 32 * (N + 32) * 2 + 2 * (N / 4) * (32 + 4) + (2 * 6 * K + 2 * N) * 4;
+  MMG_CHECK_HIP((MmgMaxLds<&k_linear_bnbwd_x6<K, 4, 0, false, true, 3>, lds>::set()), "linear_bnbwd_dual(attr)");
+  MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, N, K, 16 | 128 | 1024 | 8192 | 16384, (k_linear_bnbwd_x6<K, 4, 0, false, true, 3>),
+             dim3(1u, (unsigned)gy), dim3(512), lds, st, Gb, bbb, prb, W, DX, M, mmg_pro_dev(nullptr), next_bn_none(), nullptr,
+             wgb, BnDualDev{Ga, bba, pra, wga});
   return 0;
 }
 
@@ -2328,10 +2531,8 @@ extern "C" size_t mmg_linear_bnbwd_wgrad_ws_bytes(int64_t M, int N, int K) {
 
 // the FW launch of one mode (k_linear_bnbwd_x6<128, 4, MODE, NBN, true>): the weight-gradient descriptor, the next
 // BatchNorm's statistics (fused, or the separate pass over dX), the slab sum (deferred to wg->job, or now)
-template <int MODE>
-static int bnbwd_wgrad_run(const float* G, const BnBwdDev& bb, const ProDev& pr, const ProDev& pr2, const float* W, float* dX,
-                           int64_t M, const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, const char* what,
-                           hipStream_t st, int msk = 0) {
+// the weight-gradient descriptor of an FW launch: the job reset, the checks, the slabs carved from wg->ws
+static int bnbwd_wgrad_prepare(const mmg_bnbwd_wgrad_t* wg, int64_t M, const char* what, BnWgDev* wd) {
   constexpr int N = 128, K = 128;
   mmg_wgrad_reduce_t* job = wg->job;
   if (job) { job->slab = nullptr; job->n4 = 0; job->n_split = 0; job->dW = wg->dW; job->dbias = wg->dbias; job->nk4 = (int64_t)K * N / 4; job->accumulate = wg->accumulate; }
@@ -2343,23 +2544,18 @@ static int bnbwd_wgrad_run(const float* G, const BnBwdDev& bb, const ProDev& pr,
   MMG_CHECK_WS(what, need);
   float* slab = MmgCarver(ws).take<float>((need - 256) / sizeof(float));
   const int64_t stride = (int64_t)K * N + (wg->dbias ? K : 0);
-  const int n_split = (int)bnbwd_fw_rows(M);
   const ProDev xpr = mmg_pro_dev(wg->pro);
   // the column sums of dZ in the order of the kernel linear_wgrad runs for this X (see linear_wgrad_impl)
-  const BnWgDev wd{wg->X, xpr, slab, stride, (xpr.scale || xpr.relu || xpr.p > 0.f) ? 1 : 0};
-  // the next BatchNorm's statistics always come from the separate pass over dX: the epilogue that sums them does not fit
-  // beside the dW waves (k_linear_bnbwd_x6<128, 4, MODE, true, true> spills 124..220 B per lane at the 256-register budget
-  // of two waves per SIMD, which the plain NBN instances already exceed by 40..136 B)
-  int rc = MMG_E_ARG;
-  if (!msk) rc = launch_bnbwd_fw<MODE>(G, bb, pr, pr2, W, dX, M, wd, st);
-  if constexpr (MODE == MMG_BNBWD_BN || MODE == MMG_BNBWD_ROWS) {      // msk: the masked dX store (mmg_linear_bnbwd_masked)
-    if (msk == 1) rc = launch_bnbwd_fw_masked<MODE, 1>(G, bb, pr, W, dX, M, wd, st);
-    if (msk == 2) rc = launch_bnbwd_fw_masked<MODE, 2>(G, bb, pr, W, dX, M, wd, st);
-  }
-  if (rc) return rc;
-  MMG_CHECK_LAUNCH(what);
-  rc = next ? mmg_next_bn_fallback(dX, M, N, next, what, st) : MMG_OK;
-  if (rc) return rc;
+  *wd = BnWgDev{wg->X, xpr, slab, stride, (xpr.scale || xpr.relu || xpr.p > 0.f) ? 1 : 0};
+  return MMG_OK;
+}
+// the slab sum of an FW launch: deferred to wg->job, or now
+static int bnbwd_wgrad_finish(const mmg_bnbwd_wgrad_t* wg, const BnWgDev& wd, int64_t M, const char* what, hipStream_t st) {
+  constexpr int N = 128, K = 128;
+  mmg_wgrad_reduce_t* job = wg->job;
+  float* const slab = wd.slab;
+  const int64_t stride = wd.slab_stride;
+  const int n_split = (int)bnbwd_fw_rows(M);
   if (job) {                        // the caller sums the slabs later, together with those of other layers
     job->slab = slab; job->n4 = stride / 4; job->n_split = n_split;
   } else {
@@ -2369,6 +2565,30 @@ static int bnbwd_wgrad_run(const float* G, const BnBwdDev& bb, const ProDev& pr,
     MMG_CHECK_LAUNCH(what);
   }
   return MMG_OK;
+}
+
+template <int MODE>
+static int bnbwd_wgrad_run(const float* G, const BnBwdDev& bb, const ProDev& pr, const ProDev& pr2, const float* W, float* dX,
+                           int64_t M, const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, const char* what,
+                           hipStream_t st, int msk = 0) {
+  constexpr int N = 128;
+  BnWgDev wd;
+  int rc = bnbwd_wgrad_prepare(wg, M, what, &wd);
+  if (rc) return rc;
+  // the next BatchNorm's statistics always come from the separate pass over dX: the epilogue that sums them does not fit
+  // beside the dW waves (k_linear_bnbwd_x6<128, 4, MODE, true, true> spills 124..220 B per lane at the 256-register budget
+  // of two waves per SIMD, which the plain NBN instances already exceed by 40..136 B)
+  rc = MMG_E_ARG;
+  if (!msk) rc = launch_bnbwd_fw<MODE>(G, bb, pr, pr2, W, dX, M, wd, st);
+  if constexpr (MODE == MMG_BNBWD_BN || MODE == MMG_BNBWD_ROWS) {      // msk: the masked dX store (mmg_linear_bnbwd_masked)
+    if (msk == 1) rc = launch_bnbwd_fw_masked<MODE, 1>(G, bb, pr, W, dX, M, wd, st);
+    if (msk == 2) rc = launch_bnbwd_fw_masked<MODE, 2>(G, bb, pr, W, dX, M, wd, st);
+  }
+  if (rc) return rc;
+  MMG_CHECK_LAUNCH(what);
+  rc = next ? mmg_next_bn_fallback(dX, M, N, next, what, st) : MMG_OK;
+  if (rc) return rc;
+  return bnbwd_wgrad_finish(wg, wd, M, what, st);
 }
 
 // one mode: the FW instance when the weight gradient rides along; else the NBN instance when the next BatchNorm's
@@ -2411,9 +2631,12 @@ static const struct {
     {"linear_bnbwd_rows",    false, false, true,   true,  false, false},    // G NULL iff n_sel == 0 (checked below)
 };
 
-// msk: 0, or the masked dX store of mmg_linear_bnbwd_masked (1: write, 2: accumulate; validated there)
-static int linear_bnbwd_impl(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
-                             const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, int msk, void* stream) {
+// a validated call: the device descriptors of its mode
+struct BnBwdCall {
+  BnBwdDev bb; ProDev pr, pr2; const float* G; const char* what;
+};
+static int bnbwd_marshal(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
+                         const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, BnBwdCall* call) {
   MMG_CHECK_ARG(a, "linear_bnbwd: null descriptor");
   MMG_CHECK_ARG(a->mode >= MMG_BNBWD_BN && a->mode <= MMG_BNBWD_ROWS, "linear_bnbwd: unknown mode %d", a->mode);
   const auto& m = kBnBwdMode[a->mode];
@@ -2434,11 +2657,26 @@ static int linear_bnbwd_impl(const mmg_bnbwd_t* a, const float* W, float* dZ, fl
     MMG_CHECK_ARG(!pro || pro->relu == MMG_ACT_NONE || pro->relu == MMG_ACT_RELU, "%s: relu only", what);
     MMG_CHECK_ARG(!a->sums || (pro && pro->scale), "%s: sums without a BatchNorm fold", what);
   }
-  const BnBwdDev bb = l2 ? BnBwdDev{a->y, a->rnorm, nullptr, nullptr, 0.0, dZ, nullptr, nullptr, a->eps, nullptr, nullptr, 0}
+  call->bb = l2 ? BnBwdDev{a->y, a->rnorm, nullptr, nullptr, 0.0, dZ, nullptr, nullptr, a->eps, nullptr, nullptr, 0}
                          : BnBwdDev{a->y, a->mean, a->rstd, a->sums, a->inv_count, dZ, a->dbeta, a->dgamma, 0.f,
                                     a->mode == MMG_BNBWD_BN2 ? a->G2 : nullptr, rows ? a->row_pos : nullptr, rows ? a->n_sel : 0};
-  const ProDev pr = mmg_pro_dev(l2 ? nullptr : a->pro), pr2 = mmg_pro_dev(a->mode == MMG_BNBWD_BN2 ? a->pro2 : nullptr);
-  const float* G = rows && !a->G ? a->y : a->G;   // an empty row list: no row of G is read
+  call->pr = mmg_pro_dev(l2 ? nullptr : a->pro);
+  call->pr2 = mmg_pro_dev(a->mode == MMG_BNBWD_BN2 ? a->pro2 : nullptr);
+  call->G = rows && !a->G ? a->y : a->G;   // an empty row list: no row of G is read
+  call->what = what;
+  return MMG_OK;
+}
+
+// msk: 0, or the masked dX store of mmg_linear_bnbwd_masked (1: write, 2: accumulate; validated there)
+static int linear_bnbwd_impl(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
+                             const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, int msk, void* stream) {
+  BnBwdCall call;
+  const int rc_ = bnbwd_marshal(a, W, dZ, dX, M, N, K, next, wg, &call);
+  if (rc_) return rc_;
+  const BnBwdDev& bb = call.bb;
+  const ProDev &pr = call.pr, &pr2 = call.pr2;
+  const float* G = call.G;
+  const char* what = call.what;
   hipStream_t st = (hipStream_t)stream;
   switch (a->mode) {
     case MMG_BNBWD_BN: return bnbwd_run<MMG_BNBWD_BN>(G, bb, pr, pr2, W, dX, M, N, K, next, wg, what, st, msk);
@@ -2457,9 +2695,9 @@ extern "C" int mmg_linear_bnbwd_masked_supported(int mode, int64_t M, int N, int
   return (mode == MMG_BNBWD_BN || mode == MMG_BNBWD_ROWS) && with_wgrad && mmg_linear_bnbwd_supported(mode, M, N, K, 1) ? 1 : 0;
 }
 
-extern "C" int mmg_linear_bnbwd_masked(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
-                                       const mmg_prologue_t* mask, int accumulate, const mmg_bnbwd_wgrad_t* wg, void* stream) {
-  const char* what = "linear_bnbwd_masked";
+// what mmg_linear_bnbwd_masked refuses before it marshals the call
+static int bnbwd_masked_check(const mmg_bnbwd_t* a, int64_t M, int N, int K, const mmg_prologue_t* mask,
+                              const mmg_bnbwd_wgrad_t* wg, const char* what) {
   MMG_CHECK_ARG(a, "%s: null descriptor", what);
   MMG_CHECK_ARG(mmg_linear_bnbwd_masked_supported(a->mode, M, N, K, wg != nullptr), "%s: mode %d M=%lld N=%d K=%d%s unsupported",
                 what, a->mode, (long long)M, N, K, wg ? "" : " without a weight gradient");
@@ -2471,7 +2709,52 @@ extern "C" int mmg_linear_bnbwd_masked(const mmg_bnbwd_t* a, const float* W, flo
                     (!(xp_p > 0.f) || (mask->seed_ptr == xp->seed_ptr && (mask->seed_ptr || mask->seed == xp->seed) &&
                                        mask->site == xp->site && mask->row_offset == xp->row_offset)),
                 "%s: the mask is not the dropout of the X prologue", what);
+  return MMG_OK;
+}
+
+extern "C" int mmg_linear_bnbwd_masked(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
+                                       const mmg_prologue_t* mask, int accumulate, const mmg_bnbwd_wgrad_t* wg, void* stream) {
+  const int rc = bnbwd_masked_check(a, M, N, K, mask, wg, "linear_bnbwd_masked");
+  if (rc) return rc;
   return linear_bnbwd_impl(a, W, dZ, dX, M, N, K, nullptr, wg, accumulate ? 2 : 1, stream);
+}
+
+extern "C" int mmg_linear_bnbwd_dual_supported(int64_t M, int N, int K) {
+  return mmg_linear_bnbwd_masked_supported(MMG_BNBWD_BN, M, N, K, 1) && mmg_linear_bnbwd_masked_supported(MMG_BNBWD_ROWS, M, N, K, 1);
+}
+
+extern "C" int mmg_linear_bnbwd_dual(const mmg_bnbwd_t* b, const mmg_bnbwd_wgrad_t* wg_b, const mmg_bnbwd_t* a,
+                                     const mmg_bnbwd_wgrad_t* wg_a, const float* W, float* dZ_b, float* dZ_a, float* dX,
+                                     int64_t M, int N, int K, void* stream) {
+  const char* what = "linear_bnbwd_dual";
+  MMG_CHECK_ARG(b && a && wg_b && wg_a, "%s: null descriptor", what);
+  MMG_CHECK_ARG(b->mode == MMG_BNBWD_BN && a->mode == MMG_BNBWD_ROWS, "%s: modes (%d, %d), not (BN, ROWS)", what, b->mode, a->mode);
+  MMG_CHECK_ARG(mmg_linear_bnbwd_dual_supported(M, N, K), "%s: M=%lld N=%d K=%d unsupported", what, (long long)M, N, K);
+  // each pass masks dX with the dropout of its own X prologue, as in  masked(b, ..., wg_b->pro, 0, wg_b)  and
+  // masked(a, ..., wg_a->pro, 1, wg_a); the passes stage ONE X tile, so their X prologues may differ in the dropout site only
+  static const mmg_prologue_t no_pro = {};
+  const mmg_prologue_t *xb = wg_b->pro ? wg_b->pro : &no_pro, *xa = wg_a->pro ? wg_a->pro : &no_pro;
+  int rc = bnbwd_masked_check(b, M, N, K, xb, wg_b, what);
+  if (!rc) rc = bnbwd_masked_check(a, M, N, K, xa, wg_a, what);
+  if (rc) return rc;
+  MMG_CHECK_ARG(wg_b->X == wg_a->X, "%s: the passes read different X", what);
+  MMG_CHECK_ARG(wg_b->ws != wg_a->ws, "%s: the passes share a slab workspace", what);
+  MMG_CHECK_ARG(xb->scale == xa->scale && xb->shift == xa->shift && xb->relu == xa->relu && xb->drop_p == xa->drop_p &&
+                    xb->seed_ptr == xa->seed_ptr && (xb->seed_ptr || xb->seed == xa->seed) && xb->row_offset == xa->row_offset,
+                "%s: the X prologues differ in more than the dropout site", what);
+  BnBwdCall cb, ca;
+  rc = bnbwd_marshal(b, W, dZ_b, dX, M, N, K, nullptr, wg_b, &cb);
+  if (!rc) rc = bnbwd_marshal(a, W, dZ_a, dX, M, N, K, nullptr, wg_a, &ca);
+  BnWgDev wb, wa;
+  if (!rc) rc = bnbwd_wgrad_prepare(wg_b, M, what, &wb);
+  if (!rc) rc = bnbwd_wgrad_prepare(wg_a, M, what, &wa);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  rc = launch_bnbwd_fw_dual(cb.G, cb.bb, cb.pr, wb, ca.G, ca.bb, ca.pr, wa, W, dX, M, st);
+  if (rc) return rc;
+  MMG_CHECK_LAUNCH(what);
+  rc = bnbwd_wgrad_finish(wg_b, wb, M, what, st);
+  return rc ? rc : bnbwd_wgrad_finish(wg_a, wa, M, what, st);
 }
 
 extern "C" size_t mmg_linear_wgrad_ws_bytes(int64_t M, int N, int K) {

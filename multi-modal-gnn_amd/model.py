@@ -148,6 +148,19 @@ def set_masked_handdown(on: bool):
     MASKED_HANDDOWN = bool(on)
 
 
+# The two masked producers of the hand-down above -- pass B's dense launch and pass A's listed-rows launch of the second
+# linear's BatchNorm-backward GEMM -- as ONE launch (ops.DualBwd, mmg_linear_bnbwd_dual): each tile goes through pass B and
+# then pass A, the sum never leaves the registers in between, X and W are read once.  Every output is bit for bit that of
+# the two launches.  set_dual_enc_bwd(False) restores them.
+DUAL_ENC_BWD = True
+
+
+def set_dual_enc_bwd(on: bool):
+    """True (default) | False -- see DUAL_ENC_BWD (the tests switch it)."""
+    global DUAL_ENC_BWD
+    DUAL_ENC_BWD = bool(on)
+
+
 def _mangle(et: EdgeType) -> str:
     return "<" + "___".join(et) + ">"
 
@@ -586,6 +599,7 @@ class _Run:
         self.save_pair_state = ex["save_pair_state"] if ex.get("save_pair_state") is not None else SAVE_PAIR_STATE
         self.fused_wgrad = FUSED_WGRAD
         self.masked_handdown = MASKED_HANDDOWN
+        self.dual_enc_bwd = DUAL_ENC_BWD
         self.overlap = mode == "on" or (mode == "auto" and self.plan.n_rows >= 16384)
         if self.overlap:
             if getattr(model, "_side_stream", None) is None:
@@ -806,8 +820,12 @@ class _Run:
                         self.allreduce(live[0][1])
                 if self.masked_handdown_applies(enc1, a1, enc0, a0):
                     # pass B stores its gradient under its own mask, pass A adds its own under its mask: one tensor down
-                    gs = self.enc_bwd_b(enc1, a1, masked=ops.MaskedDx(enc1.pro1))
-                    gs = self.enc_bwd_b(enc0, a0, masked=ops.MaskedDx(enc0.pro1, into=gs))
+                    # (one launch for both where dual_enc_bwd_applies: the write parks, the accumulate launches)
+                    pair = ops.DualBwd() if self.dual_enc_bwd_applies(enc1) else None
+                    gs = self.enc_bwd_b(enc1, a1, masked=ops.MaskedDx(enc1.pro1, pair=pair))
+                    gs = self.enc_bwd_b(enc0, a0, masked=ops.MaskedDx(enc0.pro1, into=gs, pair=pair))
+                    if pair is not None:
+                        pair.require_consumed()
                     self.enc_bwd_shared_masked(enc1, gs)
                 else:
                     nstats = _NextStats(enc1.z1, enc1.f1)      # the shared first BatchNorm: both passes add their share
@@ -1101,6 +1119,14 @@ class _Run:
             ops.linear_bnbwd_masked_supported(M, N, K, ops.BNBWD_ROWS) and \
             ops.linear_bnbwd_supported(M, N, K, ops.BNBWD_BN) and ops.linear_bnbwd_supported(M, N, K, ops.BNBWD_ROWS) and \
             ops.linear_bnbwd_supported(M, N1, K1, ops.BNBWD_BN) and ops.linear_bnbwd_wgrad_supported(M, N1, K1)
+
+    def dual_enc_bwd_applies(self, enc_b: _EncPass) -> bool:
+        """Whether the two masked producers of a hand-down that applies (masked_handdown_applies) run as ONE launch
+        (DUAL_ENC_BWD): the switch, and the shape the dual kernel covers."""
+        if not self.dual_enc_bwd:
+            return False
+        K, N = self.W("patient_transform.4.weight").shape
+        return ops.linear_bnbwd_dual_supported(enc_b.z2.shape[0], N, K)
 
     def enc_bwd_shared_masked(self, enc: _EncPass, gs):
         """enc_bwd_shared for the ONE gradient gs = drop_b(g_b) + drop_a(g_a) the masked producers left: the statistics and

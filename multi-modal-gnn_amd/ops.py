@@ -163,7 +163,7 @@ PROBE_NAME_LEN = _lib.MMG_PROBE_NAME_LEN
 
 
 def probe_read(cap: int = 1 << 16):
-    """-> list of (ms, family name, M, N, K, flags, kernel symbol) of the probed launches (flags: 1 accumulate, 4 prologue, 8 rowscale, 16 BatchNorm backward staged in the GEMM, 32 L2-norm epilogue, 64 L2-norm backward staged, 128 two upstream gradients, 256 row-list upstream gradient, 2048 the dual linear forward: N = both outputs, 4096 the weight gradient rides along the data gradient: linear_dgrad_wgrad)."""
+    """-> list of (ms, family name, M, N, K, flags, kernel symbol) of the probed launches (flags: 1 accumulate, 4 prologue, 8 rowscale, 16 BatchNorm backward staged in the GEMM, 32 L2-norm epilogue, 64 L2-norm backward staged, 128 two upstream gradients, 256 row-list upstream gradient, 2048 the dual linear forward: N = both outputs, 4096 the weight gradient rides along the data gradient: linear_dgrad_wgrad, 8192 the masked dx store, 16384 the dual backward: linear_bnbwd_dual)."""
     import numpy as np
     ms = np.zeros(cap, np.float32); tag = np.zeros(cap, np.int32); M = np.zeros(cap, np.int64)
     N = np.zeros(cap, np.int32); K = np.zeros(cap, np.int32); fl = np.zeros(cap, np.int32)
@@ -875,12 +875,32 @@ _BNBWD_PROF = {BNBWD_BN: ("linear_bnbwd", 2), BNBWD_BN2: ("linear_bnbwd", 3), BN
 
 
 @dataclass
+class DualBwd:
+    """Pairs the masked write of one pass (linear_bnbwd) with the masked accumulate of the other (linear_bnbwd_rows) into ONE
+    launch (mmg_linear_bnbwd_dual): hand the same holder to both calls through MaskedDx.pair.  The write validates,
+    allocates its outputs, registers its deferred slab job and parks its descriptor here WITHOUT launching; the accumulate
+    into the tensor the write returned launches both.  Nothing falls back: a second write on a holder that still holds a
+    descriptor, an accumulate on an empty holder or one whose `into` or W is not the parked call's raises."""
+    parked: Optional[tuple] = None
+
+    def require_consumed(self):
+        if self.parked is not None:
+            raise RuntimeError("DualBwd: the parked write was never launched (no accumulate followed it)")
+
+
+@dataclass
 class MaskedDx:
     """The masked dx store of linear_bnbwd / linear_bnbwd_rows (mmg_linear_bnbwd_masked; needs wgrad): dx holds
     dropout(dx) under the mask of `pro` -- which must be the dropout of wgrad.pro -- or, with `into`, that is ADDED to the
-    tensor `into` [M,N] (which the call returns as dx).  The consumer of dx applies the activation's select but no dropout."""
+    tensor `into` [M,N] (which the call returns as dx).  The consumer of dx applies the activation's select but no dropout.
+    pair: the write and the accumulate of the two passes as one launch (see DualBwd; linear_bnbwd_dual_supported)."""
     pro: Pro
     into: Optional[torch.Tensor] = None
+    pair: Optional[DualBwd] = None
+
+
+def linear_bnbwd_dual_supported(M: int, N: int, K: int) -> bool:
+    return bool(_lib.load().mmg_linear_bnbwd_dual_supported(int(M), int(N), int(K)))
 
 
 def linear_bnbwd_masked_supported(M: int, N: int, K: int, mode: int = 0, wgrad: bool = True) -> bool:
@@ -904,6 +924,19 @@ def _linear_bnbwd(mode: int, y: torch.Tensor, W: torch.Tensor, next_bn: Optional
         if masked.into is not None and (tuple(masked.into.shape) != (M, N) or masked.into.device != y.device):
             raise ValueError(f"{_BNBWD_PROF[mode][0]}: masked.into is {tuple(masked.into.shape)} on {masked.into.device}, "
                              f"expected [{M},{N}] on {y.device}")
+    pair = masked.pair if masked is not None else None
+    if pair is not None:
+        what = f"{_BNBWD_PROF[mode][0]}: the dual launch"
+        if mode != (BNBWD_BN if masked.into is None else BNBWD_ROWS):
+            raise ValueError(f"{what} pairs a linear_bnbwd write with a linear_bnbwd_rows accumulate")
+        if not linear_bnbwd_dual_supported(M, N, K):
+            raise ValueError(f"{what} does not cover M={M} N={N} K={K}")
+        if masked.into is None:
+            pair.require_consumed()
+        elif pair.parked is None:
+            raise RuntimeError(f"{what}: no parked write to accumulate onto")
+        elif pair.parked[0] is not masked.into or pair.parked[1].data_ptr() != W.data_ptr() or pair.parked[1].shape != W.shape:
+            raise ValueError(f"{what}: `into` or W is not that of the parked write")
     dz = torch.empty_like(y) if wgrad is None or wgrad.keep_dz else None
     into = masked.into if masked is not None else None
     dx = into if into is not None else torch.empty(M, N, device=y.device)
@@ -922,6 +955,21 @@ def _linear_bnbwd(mode: int, y: torch.Tensor, W: torch.Tensor, next_bn: Optional
                   *[C.pointer(pc) if pc is not None else None for pc in pcs],
                   _p(fold.mean) if fold else None, _p(fold.rstd) if fold else None, _p(sums, torch.float64),
                   1.0 / float(count), _p(dbeta), _p(dgamma), _p(rn), L2_EPS)
+    if pair is not None and into is None:
+        # parked: the descriptor, what it points into, and the tensors it names stay alive in the holder until the launch
+        _fused_wgrad_done(wgrad, wt)               # B's slab series before A's in the finish list
+        pair.parked = (dx, W, desc, wt, dz, pcs, (g, y, row_pos, fold, sums, dbeta, dgamma))
+        return dz, dx
+    if pair is not None:
+        _, _, desc_b, wt_b, dz_b, *_keep = pair.parked
+        _tok = _pb("linear_bnbwd_dual")
+        _call("mmg_linear_bnbwd_dual", C.byref(desc_b), C.byref(wt_b), C.byref(desc), C.byref(wt), W, dz_b, dz, dx, M, N, K)
+        pair.parked = None
+        _fused_wgrad_done(wgrad, wt)
+        nd = (dz is not None) + (dz_b is not None)
+        # g and y of the write, y of the accumulate, dx once, x once, two slab series
+        _pe(_tok, "linear_bnbwd_dual", 4 * ((3 + nd) * M * K + M * N) + 2 * _fused_wgrad_bytes(M, N, K) - 4 * M * N, 8 * M * N * K)
+        return dz, dx
     if masked is not None:
         mpc = masked.pro.c()
         _call("mmg_linear_bnbwd_masked", C.byref(desc), W, dz, dx, M, N, K, C.byref(mpc), int(masked.into is not None),
