@@ -413,10 +413,10 @@ def evaluate_with_intervals(model, graph, masker, config: Dict, output_dir, spli
     difference ``model - baseline`` over patients.  Writes ``evaluation_intervals.json``, ``per_lab_metrics_ci.csv`` and
     ``baseline_comparison.csv`` (one row per baseline x metric x scope) into ``output_dir``; ``evaluate_model`` and its
     files are untouched."""
-    known = ("global_mean", "per_lab_mean", "nearest_neighbor")
+    from .evaluate import BASELINES, baseline_pairs, fit_baselines
     for b in baselines:
-        if b not in known:
-            raise ValueError(f"unknown baseline {b!r}: one of {known}")
+        if b not in BASELINES:
+            raise ValueError(f"unknown baseline {b!r}: one of {BASELINES}")
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     model.eval()
@@ -434,21 +434,9 @@ def evaluate_with_intervals(model, graph, masker, config: Dict, output_dir, spli
     lab_names = {idx: m["label"] for idx, m in meta.items()} if meta else None
     stratify = tuple((config.get("evaluation") or {}).get("stratify_by") or ())
 
-    g_mean = tr_v.double().mean().float() if tr_v.numel() else torch.zeros((), device=dev)
-    fitted = {}
-    for b in baselines:
-        if b == "global_mean":
-            fitted[b] = g_mean.expand(pred.numel()).contiguous()
-        elif b == "per_lab_mean":
-            cnt = torch.bincount(tr_ei[1], minlength=n_labs).double()
-            tot = torch.zeros(n_labs, dtype=torch.float64, device=dev).index_add_(0, tr_ei[1], tr_v.double())
-            means = torch.where(cnt > 0, tot / cnt.clamp(min=1), g_mean.double()).float()
-            fitted[b] = means[li].contiguous()
-        else:
-            from .knn import KNNLabImputer
-            nn = (config.get("evaluation") or {}).get("n_neighbors", 5)
-            p = KNNLabImputer(n_neighbors=nn).fit(tr_ei[0], tr_ei[1], tr_v, n_pat, n_labs).predict(pi, li)
-            fitted[b] = torch.where(torch.isnan(p), g_mean, p).contiguous()
+    nn = (config.get("evaluation") or {}).get("n_neighbors", 5)
+    models = fit_baselines(tuple(baselines), tr_ei, tr_v, n_labs, n_pat, nn)
+    fitted = {b: baseline_pairs(m, pi, li) for b, m in models.items()}
 
     kw = dict(replicates=replicates, confidence=confidence, seed=seed, cluster="patient", lab_names=lab_names)
     res = bootstrap_metrics(pred, ev_v, pi, li, graph, stratify=stratify, **kw)

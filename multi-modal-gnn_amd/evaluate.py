@@ -23,7 +23,7 @@ from __future__ import annotations
 import json
 import logging
 from pathlib import Path
-from typing import Dict, Tuple
+from typing import Dict, Sequence, Tuple
 
 import numpy as np
 import pandas as pd
@@ -138,6 +138,59 @@ def evaluate_baselines(train_data, test_data) -> Dict[str, Dict[str, float]]:
     pl.fit(train_values, train_lab_indices)
     results["per_lab_mean"] = compute_regression_metrics(pl.predict(test_lab_indices), test_values)
     return results
+
+
+BASELINES = ("global_mean", "per_lab_mean", "nearest_neighbor")
+
+
+def fit_baselines(baselines: Sequence[str], tr_ei, tr_v, n_labs: int, n_pat: int, n_neighbors: int = 5) -> dict:
+    """The named baselines ("global_mean", "per_lab_mean", "nearest_neighbor": mmgnn.knn.KNNLabImputer) fitted on the
+    train edges tr_ei [2, m] with values tr_v fp32 [m], all on one device -> {name: model}.  A model is
+    ``(kind, payload)``; ``baseline_pairs`` and ``baseline_matrix`` evaluate it.  ``bootstrap.evaluate_with_intervals`` and
+    the drivers of ``stacking`` share this one fit."""
+    for b in baselines:
+        if b not in BASELINES:
+            raise ValueError(f"unknown baseline {b!r}: one of {BASELINES}")
+    dev = tr_v.device
+    g_mean = tr_v.double().mean().float() if tr_v.numel() else torch.zeros((), device=dev)
+    fitted = {}
+    for b in baselines:
+        if b == "global_mean":
+            fitted[b] = ("global_mean", g_mean)
+        elif b == "per_lab_mean":
+            cnt = torch.bincount(tr_ei[1], minlength=n_labs).double()
+            tot = torch.zeros(n_labs, dtype=torch.float64, device=dev).index_add_(0, tr_ei[1], tr_v.double())
+            fitted[b] = ("per_lab_mean", torch.where(cnt > 0, tot / cnt.clamp(min=1), g_mean.double()).float())
+        else:
+            from .knn import KNNLabImputer
+            fitted[b] = ("nearest_neighbor", (KNNLabImputer(n_neighbors=n_neighbors).fit(tr_ei[0], tr_ei[1], tr_v, n_pat,
+                                                                                         n_labs), g_mean))
+    return fitted
+
+
+def baseline_pairs(model, pi, li) -> torch.Tensor:
+    """A fitted baseline's prediction fp32 [n] for the pairs (pi, li)."""
+    kind, payload = model
+    if kind == "global_mean":
+        return payload.expand(li.numel()).contiguous()
+    if kind == "per_lab_mean":
+        return payload[li].contiguous()
+    imputer, g_mean = payload
+    p = imputer.predict(pi, li)
+    return torch.where(torch.isnan(p), g_mean, p).contiguous()
+
+
+def baseline_matrix(model, rows, n_labs: int) -> torch.Tensor:
+    """A fitted baseline's dense prediction: a vector [n_labs] to broadcast, or (nearest neighbour) [n_rows, n_labs] --
+    KNNLabImputer.impute_matrix, which passes a patient's own train-edge values through and imputes the rest."""
+    kind, payload = model
+    if kind == "global_mean":
+        return payload.expand(n_labs).contiguous()
+    if kind == "per_lab_mean":
+        return payload.contiguous()
+    imputer, g_mean = payload
+    p = imputer.impute_matrix(rows)
+    return torch.where(torch.isnan(p), g_mean, p).contiguous()
 
 
 def evaluate_nearest_neighbor_baseline(graph, masker, split: str = "test", n_neighbors: int = 5,

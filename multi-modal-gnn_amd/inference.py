@@ -11,7 +11,8 @@ patient is assembled on the host from its row of that matrix:
   lab_report            the host-side assembly of one patient's dict (no device, no model)
 
 With ``intervals=`` (a fitted ``conformal.LabConformal``) every predicted entry also carries its split-conformal
-interval; without it the dicts are the reference's.
+interval; without it the dicts are the reference's.  With ``stacker=`` (a fitted ``stacking.LabStacker``) every
+predicted entry carries the stacked value and keeps the model's own under ``raw_prediction``.
 
 Printing, config loading and the command line of the reference script (``print_patient_report``, ``run_inference``)
 are not part of this module.
@@ -54,7 +55,7 @@ def _lab_stats_rows(lab_stats, names):
 
 def lab_report(pred_row: np.ndarray, lab_indices: np.ndarray, values: np.ndarray, in_test: np.ndarray,
                lab_stats, lab_indexer: Dict, stats_rows: Optional[Dict] = None,
-               bounds: Optional[Tuple[np.ndarray, np.ndarray]] = None) -> Dict:
+               bounds: Optional[Tuple[np.ndarray, np.ndarray]] = None, raw_row: Optional[np.ndarray] = None) -> Dict:
     """One patient's report, reference inference.py:107-178, from host data only.
     pred_row: [L] normalised predictions of every lab (a row of impute_lab_matrix); lab_indices / values / in_test: the
     patient's has_lab edges in edge order -- lab index, normalised value, edge in the test split.  Values are
@@ -62,6 +63,9 @@ def lab_report(pred_row: np.ndarray, lab_indices: np.ndarray, values: np.ndarray
     bounds: (lower_row, upper_row), [L] normalised interval bounds of every lab (conformal.LabConformal.predict_matrix);
     every entry of masked_labs and truly_missing_labs then also has 'lower', 'upper' (bound * std + mean, as 'predicted'
     is formed), 'normalized_lower' and 'normalized_upper'.
+    raw_row: [L] the model's own normalised predictions when pred_row holds stacked ones (stacking.LabStacker); every
+    entry of masked_labs and truly_missing_labs then also has 'raw_prediction' (raw * std + mean) and
+    'normalized_raw_prediction'.
     -> {'measured_labs', 'masked_labs', 'truly_missing_labs'} with the reference's keys."""
 
     def interval(lab_idx, lab_stat):
@@ -70,6 +74,12 @@ def lab_report(pred_row: np.ndarray, lab_indices: np.ndarray, values: np.ndarray
         lo, hi = bounds[0][lab_idx], bounds[1][lab_idx]
         return {'lower': float(lo * lab_stat['std'] + lab_stat['mean']), 'upper': float(hi * lab_stat['std'] + lab_stat['mean']),
                 'normalized_lower': float(lo), 'normalized_upper': float(hi)}
+
+    def raw(lab_idx, lab_stat):
+        if raw_row is None:
+            return {}
+        r = raw_row[lab_idx]
+        return {'raw_prediction': float(r * lab_stat['std'] + lab_stat['mean']), 'normalized_raw_prediction': float(r)}
 
     lab_idx_to_name = {v: k for k, v in lab_indexer.items()}
     if stats_rows is None:
@@ -92,6 +102,7 @@ def lab_report(pred_row: np.ndarray, lab_indices: np.ndarray, values: np.ndarray
                 'normalized_actual': float(actual)
             }
             masked_labs[lab_name].update(interval(lab_idx, lab_stat))
+            masked_labs[lab_name].update(raw(lab_idx, lab_stat))
         else:
             measured_labs[lab_name] = {
                 'value': float(actual_original),
@@ -111,6 +122,7 @@ def lab_report(pred_row: np.ndarray, lab_indices: np.ndarray, values: np.ndarray
             'note': 'Lab was never measured for this patient'
         }
         truly_missing_labs[lab_name].update(interval(lab_idx, lab_stat))
+        truly_missing_labs[lab_name].update(raw(lab_idx, lab_stat))
     return {
         'measured_labs': measured_labs,
         'masked_labs': masked_labs,
@@ -119,17 +131,28 @@ def lab_report(pred_row: np.ndarray, lab_indices: np.ndarray, values: np.ndarray
 
 
 def predict_for_patients(patient_ids: Sequence, data, model, device, labs_df, lab_stats, masker, patient_indexer: Dict,
-                         lab_indexer: Dict, intervals=None) -> List[Dict]:
+                         lab_indexer: Dict, intervals=None, stacker=None, stack_features=None) -> List[Dict]:
     """predict_for_patient for many patients from ONE impute_lab_matrix forward -> one dict per id, in order.
-    intervals: a fitted conformal.LabConformal; the bounds of every cell come from one more streaming launch."""
+    intervals: a fitted conformal.LabConformal; the bounds of every cell come from one more streaming launch.
+    stacker: a fitted stacking.LabStacker; the predictions reported (and handed to ``intervals``, which should then have
+    been fitted on stacked predictions) are the stacked ones, the model's own stay under 'raw_prediction'.
+    stack_features: the stacker's predictors after the model's own -- the fitted baselines of
+    ``stacking.fit_stacker(.., return_baselines=True)`` (a dict), or a sequence of [n, L] / [L] tensors."""
     idx = [patient_indexer[str(pid)] for pid in patient_ids]
     data_device = data.to(device)
     rows = torch.tensor(idx, dtype=torch.int64, device=device)
     pred = model.impute_lab_matrix(data_device, rows)
-    lower = upper = None
+    lower = upper = raw = None
+    if stacker is not None and idx:
+        from .evaluate import baseline_matrix
+        extra = stack_features if stack_features is not None else ()
+        if isinstance(extra, dict):
+            extra = [baseline_matrix(bm, rows, int(pred.shape[1])) for bm in extra.values()]
+        raw = pred.cpu().numpy()
+        pred = stacker.predict_matrix([pred] + list(extra), rows)
     if intervals is not None and idx:
-        _, lower, upper = (t.cpu().numpy() for t in intervals.predict_matrix(pred, rows))
-    pred = pred.cpu().numpy()
+        _, lower, upper = (t.cpu().numpy() if torch.is_tensor(t) else t for t in intervals.predict_matrix(pred, rows))
+    pred = pred.cpu().numpy() if torch.is_tensor(pred) else pred
     if not idx:
         return []
     # the requested patients' edges, grouped by patient in edge order (torch.where(edge_index[0] == p) of the reference)
@@ -148,14 +171,15 @@ def predict_for_patients(patient_ids: Sequence, data, model, device, labs_df, la
     for i, p in enumerate(idx):
         lo, hi = np.searchsorted(e_pat, p, "left"), np.searchsorted(e_pat, p, "right")
         out.append(lab_report(pred[i], e_lab[lo:hi], e_val[lo:hi], test_mask[pos[lo:hi]], lab_stats, lab_indexer,
-                              stats_rows, None if lower is None else (lower[i], upper[i])))
+                              stats_rows, None if lower is None else (lower[i], upper[i]),
+                              None if raw is None else raw[i]))
     return out
 
 
 def predict_for_patient(patient_id: int, data, model, device, labs_df, lab_stats, masker, patient_indexer: Dict,
-                        lab_indexer: Dict, intervals=None) -> Dict:
+                        lab_indexer: Dict, intervals=None, stacker=None, stack_features=None) -> Dict:
     """Reference inference.py:53-178 (same arguments, same result): the patient's measured labs, the labs held out in
     the test split (predicted vs actual) and the labs never measured (predicted), denormalised through lab_stats --
     from one row of impute_lab_matrix instead of two whole-graph forwards."""
     return predict_for_patients([patient_id], data, model, device, labs_df, lab_stats, masker, patient_indexer,
-                                lab_indexer, intervals)[0]
+                                lab_indexer, intervals, stacker, stack_features)[0]
