@@ -1,4 +1,5 @@
-"""ctypes binding of libmmgnn.so (C ABI: include/mmgnn.h).
+"""ctypes binding of libmmgnn.so (C ABI: include/mmgnn.h) and, through the same Binding, of the satellite libraries
+libmmgnn_<stem>.so beside it (include/mmgnn_<stem>.h).
 
 The library is REQUIRED: there is no CPU or eager-PyTorch fallback anywhere in this
 package.  If it is missing, importing the ops raises with the build command.
@@ -10,7 +11,7 @@ import os
 import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libmmgnn.so")
+LIB_PATH = os.path.join(_HERE, "libmmgnn.so")          # assigned before the first load(): the library loaded instead
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mmgnn.h")    # as csrc/Makefile finds it
 
 
@@ -35,7 +36,7 @@ _DECLARATOR = re.compile(r"((?:\*\s*(?:const\b\s*)?)*)(\w+)\s*(?:\[\s*(\d+)\s*\]
 def _ctype(base, stars, structs, what, const=False, is_return=False):
     """C type `base` behind `stars` pointer levels -> ctypes type (structs: the structs declared so far)."""
     if base not in _POINTEES and base not in structs:
-        raise MmgError(f"mmgnn.h: unknown type {base!r} in {what!r}")
+        raise MmgError(f"unknown type {base!r} in {what!r}")
     if stars == 0 and base in _SCALARS:
         return _SCALARS[base]
     if stars == 0 and base in structs:
@@ -46,7 +47,7 @@ def _ctype(base, stars, structs, what, const=False, is_return=False):
         return C.c_char_p if (is_return and const and base == "char") else C.c_void_p
     if stars == 2 and base in _POINTEES:
         return C.POINTER(C.c_void_p)
-    raise MmgError(f"mmgnn.h: unsupported type in {what!r}")
+    raise MmgError(f"unsupported type in {what!r}")
 
 
 def _declaration(text, structs, is_param=False):
@@ -55,24 +56,32 @@ def _declaration(text, structs, is_param=False):
     m = re.match(r"\s*(const\s+)?(\w+)\b\s*(?:const\b\s*)?(.*)$", text, re.S)
     names = m.group(3).split(",") if m else []
     if not names or (is_param and len(names) != 1):
-        raise MmgError(f"mmgnn.h: cannot split the declaration {text.strip()!r}")
+        raise MmgError(f"cannot split the declaration {text.strip()!r}")
     out = []
     for decl in names:
         d = _DECLARATOR.match(decl.strip())
         if not d or (is_param and d.group(3)):
-            raise MmgError(f"mmgnn.h: cannot split the declaration {text.strip()!r}")
+            raise MmgError(f"cannot split the declaration {text.strip()!r}")
         stars = d.group(1).count("*")
         t = _ctype(m.group(2), stars, structs, text.strip(), bool(m.group(1)))
         out.append((d.group(2), t * int(d.group(3)) if d.group(3) else t, m.group(2), stars))
     return out
 
 
-def parse_header(text, params=None):
+def parse_header(text, params=None, name="mmgnn.h"):
     """The C subset of include/mmgnn.h -> (defines {name: int}, structs {C name: ctypes.Structure subclass},
-    signatures {name: (restype, [argtypes])}).  Whatever it does not recognise raises MmgError with the offending text.
+    signatures {name: (restype, [argtypes])}).  Whatever it does not recognise raises MmgError with the offending text
+    behind `name`, the file name of the header read.
     params (a dict): also filled with name -> [(parameter name, C base type, pointer depth)] of every function.
     A workspace is always the three parameters ws, ws_bytes (directly behind it) and stream: the call layer fills them
     by name, so a prototype with `ws` that breaks this is refused like unknown C."""
+    try:
+        return _parse(text, params)
+    except MmgError as e:
+        raise MmgError(f"{name}: {e}") from None
+
+
+def _parse(text, params):
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"//[^\n]*", " ", text)
     defines, structs, signatures = {}, {}, {}
@@ -83,7 +92,7 @@ def parse_header(text, params=None):
         if d:
             defines[d.group(1)] = int(d.group(2))
         elif not re.match(r"#\s*(ifndef\s+\w+|ifdef\s+\w+|endif|include\s*<[\w./]+>|define\s+\w+_H)$", line):
-            raise MmgError(f"mmgnn.h: cannot parse the directive {line!r}")
+            raise MmgError(f"cannot parse the directive {line!r}")
         return ""
 
     rest = re.sub(r"^[ \t]*#[^\n]*$", directive, text, flags=re.M).strip()
@@ -98,74 +107,97 @@ def parse_header(text, params=None):
         if m:
             body = m.group(1).split(";")
             if body.pop().strip() or m.group(2) in structs:
-                raise MmgError(f"mmgnn.h: cannot parse the struct {m.group(0)!r}")
+                raise MmgError(f"cannot parse the struct {m.group(0)!r}")
             fields = [f[:2] for decl in body for f in _declaration(decl, structs)]
             py = _PY_NAMES.get(m.group(2)) or "".join(w.capitalize() for w in m.group(2).split("_")[1:])
             structs[m.group(2)] = type(py, (C.Structure,), {"_fields_": fields})
         else:
             m = re.match(r"(const\s+)?(\w+)\s*(\**)\s*(\w+)\s*\(([^;{}()]*)\)\s*;", rest)
             if not m or m.group(4) in signatures:
-                raise MmgError(f"mmgnn.h: cannot parse the declaration {rest[:120]!r}")
+                raise MmgError(f"cannot parse the declaration {rest[:120]!r}")
             what = m.group(0)
             res = _ctype(m.group(2), len(m.group(3)), structs, what, bool(m.group(1)), is_return=True)
             decls = [] if m.group(5).strip() == "void" else m.group(5).split(",")
             decls = [_declaration(p, structs, is_param=True)[0] for p in decls]
             names = [d[0] for d in decls]
             if "ws" in names and (names[names.index("ws") + 1:][:1] != ["ws_bytes"] or "stream" not in names):
-                raise MmgError(f"mmgnn.h: {m.group(4)} takes `ws` without `ws_bytes` directly behind it or without `stream`")
+                raise MmgError(f"{m.group(4)} takes `ws` without `ws_bytes` directly behind it or without `stream`")
             signatures[m.group(4)] = (res, [d[1] for d in decls])
             if params is not None:
                 params[m.group(4)] = [(d[0], d[2], d[3]) for d in decls]
         rest = rest[m.end():].lstrip()
     if depth:
-        raise MmgError('mmgnn.h: unbalanced extern "C" block')
+        raise MmgError('unbalanced extern "C" block')
     return defines, structs, signatures
 
 
-def _read_header():
+def _read_header(path=None):
+    path = path or HEADER_PATH
     try:
-        with open(HEADER_PATH) as f:
+        with open(path) as f:
             return f.read()
     except OSError as e:
-        raise MmgError(f"{HEADER_PATH} not found: the binding is derived from the header the library is built from "
+        raise MmgError(f"{path} not found: the binding is derived from the header the library is built from "
                        f"({e})") from None
 
 
-# Every MMG_* define (an int), every struct (under its Python name, e.g. mmg_bn_fin_t -> BnFinT) and
-# SIGNATURES, name -> (restype, argtypes) of every symbol, with PARAMS, name -> [(parameter name, C base type, pointer
-# depth)], all read from include/mmgnn.h: the header is the only description of the ABI's layout.
-PARAMS = {}
-DEFINES, STRUCTS, SIGNATURES = parse_header(_read_header(), PARAMS)
+class Binding:
+    """One library and the header it is built from: libmmgnn.so and include/mmgnn.h (stem None), or the satellite
+    libmmgnn_<stem>.so and include/mmgnn_<stem>.h beside them.  Making one parses the header -- defines {MMG_* name:
+    int}, structs, signatures {symbol: (restype, argtypes)} and params {symbol: [(parameter name, C base type, pointer
+    depth)]}: the header is the only description of the ABI's layout -- and loads nothing."""
+
+    def __init__(self, stem=None):
+        name = f"mmgnn_{stem}" if stem else "mmgnn"
+        self.stem = stem
+        self.lib_path = os.path.join(_HERE, f"lib{name}.so")
+        self.header_path = os.path.join(os.path.dirname(_HERE), "include", f"{name}.h")    # as csrc/Makefile finds it
+        self.params = {}
+        self.defines, self.structs, self.signatures = parse_header(_read_header(self.header_path), self.params,
+                                                                   f"{name}.h")
+        self._lib = None
+
+    def load(self):
+        """Load the library (once), a satellite after libmmgnn.so, which it uses.  Raises MmgError loudly when it has
+        not been built."""
+        if self._lib is not None:
+            return self._lib
+        if self.stem:
+            load()
+        if not os.path.exists(self.lib_path):
+            raise MmgError(
+                f"{self.lib_path} not found: the HIP library is mandatory (no CPU fallback). Build it with "
+                f"`make -C {os.path.join(_HERE, 'csrc')}` or `python -c 'import __graft_entry__ as g; g.build()'`.")
+        # PyTorch (the package's device-memory plumbing) bundles its own HIP runtime.  It has to be in the process BEFORE the
+        # first library is mapped: libmmgnn.so then binds to it; mapped first, the library pulls in /opt/rocm's runtime, PyTorch
+        # adds its own later, and the second runtime of a process sees no device ("no ROCm-capable device is detected" from the
+        # first library call -- `python __graft_entry__.py smoke`, where build() loaded the library before anything imported torch).
+        try:
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+        lib = C.CDLL(self.lib_path)
+        for name, (res, args) in self.signatures.items():
+            fn = getattr(lib, name)     # AttributeError here = header/library mismatch
+            fn.restype = res
+            fn.argtypes = args
+        self._lib = lib
+        return lib
+
+
+# libmmgnn.so's binding under the names the package reads it by: every MMG_* define (an int), every struct (under its
+# Python name, e.g. mmg_bn_fin_t -> BnFinT), SIGNATURES and PARAMS.
+MAIN = Binding()
+DEFINES, STRUCTS, SIGNATURES, PARAMS = MAIN.defines, MAIN.structs, MAIN.signatures, MAIN.params
 globals().update(DEFINES)
 globals().update({s.__name__: s for s in STRUCTS.values()})
 
-_lib = None
-
 
 def load():
-    """Load libmmgnn.so (once).  Raises MmgError loudly when it has not been built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise MmgError(
-            f"{LIB_PATH} not found: the HIP library is mandatory (no CPU fallback). Build it with "
-            f"`make -C {os.path.join(_HERE, 'csrc')}` or `python -c 'import __graft_entry__ as g; g.build()'`.")
-    # PyTorch (the package's device-memory plumbing) bundles its own HIP runtime.  It has to be in the process BEFORE this
-    # library is mapped: libmmgnn.so then binds to it; mapped first, the library pulls in /opt/rocm's runtime, PyTorch adds
-    # its own later, and the second runtime of a process sees no device ("no ROCm-capable device is detected" from the
-    # first library call -- `python __graft_entry__.py smoke`, where build() loaded the library before anything imported torch).
-    try:
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)     # AttributeError here = header/library mismatch
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    """Load libmmgnn.so (once) from LIB_PATH as it stands at the first call.  Raises MmgError loudly when it has not been
+    built."""
+    MAIN.lib_path = LIB_PATH
+    return MAIN.load()
 
 
 def check(rc: int, what: str = ""):

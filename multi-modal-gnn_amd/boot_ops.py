@@ -1,39 +1,18 @@
 """ctypes binding and typed entry points of libmmgnn_boot.so (C ABI: include/mmgnn_boot.h; csrc/boot.hip): the weighted
 segment sums of the patient-cluster bootstrap, the metrics of every replicate and their summary, a library of its own
-beside libmmgnn.so.  The binding is derived from the header by the same parser as _lib's (``_lib.parse_header``) and the
-calls are marshalled from the prototypes as ``conformal_ops._call`` marshals them.  The library is REQUIRED: there is no
-CPU or eager-PyTorch fallback behind these calls (the numpy restatement of mmgnn/bootstrap.py serves numpy inputs and
-checks the kernels; it is never a silent substitute for them).
+beside libmmgnn.so.  The binding is a ``_lib.Binding`` derived from the header, and every call goes through
+``ops._call``.  The library is REQUIRED: there is no CPU or eager-PyTorch fallback behind these calls (the numpy
+restatement of mmgnn/bootstrap.py serves numpy inputs and checks the kernels; it is never a silent substitute for them).
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
 from typing import Optional
 
 import torch
 
-from . import _lib, ops
-from ._lib import MmgError, check
+from . import ops
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libmmgnn_boot.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mmgnn_boot.h")
-
-
-def _read_header():
-    try:
-        with open(HEADER_PATH) as f:
-            return f.read()
-    except OSError as e:
-        raise MmgError(f"{HEADER_PATH} not found: the binding is derived from the header the library is built from "
-                       f"({e})") from None
-
-
-PARAMS = {}
-DEFINES, STRUCTS, SIGNATURES = _lib.parse_header(_read_header(), PARAMS)
-globals().update(DEFINES)
-_PLANS = {sym: ops._plan(params) for sym, params in PARAMS.items()}
+BINDING = ops.satellite("boot", globals())    # LIB_PATH, HEADER_PATH, DEFINES, SIGNATURES, PARAMS, MMG_*, load, _call
 
 BOOT_SITE = DEFINES["MMG_BOOT_SITE"]
 BOOT_MAX_REPLICATES = DEFINES["MMG_BOOT_MAX_REPLICATES"]
@@ -46,56 +25,6 @@ BOOT_FIELDS_B = DEFINES["MMG_BOOT_FIELDS_B"]
 BOOT_METRICS = DEFINES["MMG_BOOT_METRICS"]
 BOOT_METRICS_B = DEFINES["MMG_BOOT_METRICS_B"]
 BOOT_SUMMARY_FIELDS = DEFINES["MMG_BOOT_SUMMARY_FIELDS"]
-
-_btlib = None
-
-
-def load():
-    """Load libmmgnn_boot.so (once), after libmmgnn.so, which it uses.  Raises MmgError loudly when it has not been
-    built."""
-    global _btlib
-    if _btlib is not None:
-        return _btlib
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise MmgError(f"{LIB_PATH} not found: the HIP library is mandatory (no CPU fallback). Build it with "
-                       f"`make -C {os.path.join(_HERE, 'csrc')}` or `python -c 'import __graft_entry__ as g; g.build()'`.")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)     # AttributeError here = header/library mismatch
-        fn.restype = res
-        fn.argtypes = args
-    _btlib = lib
-    return lib
-
-
-def _call(name, *args, ws=None):
-    """conformal_ops._call for this library: `args` are the parameters of the prototype of `name` without stream, ws and
-    ws_bytes; a torch.Tensor handed to a scalar pointer parameter is converted under the header's dtype and name, tensors
-    on different devices are refused; ws: the call's uint8 workspace tensor."""
-    plan, n_given = _PLANS[name]
-    if len(args) != n_given:
-        raise TypeError(f"{name}: takes {n_given} arguments besides ws and stream, got {len(args)}")
-    out, dev, given = [], None, iter(args)
-    for how in plan:
-        a = (0 if how == "ws_bytes" else None) if isinstance(how, str) else next(given)
-        if how is not None and isinstance(a, torch.Tensor):
-            t, a = a, ops._p(a, how[1], how[0])
-            if dev is None:
-                dev = t.device
-            elif t.device != dev:
-                raise ValueError(f"{name}: {how[0]} is on {t.device}, the tensors before it on {dev}")
-        out.append(a)
-    for i, how in enumerate(plan):
-        if how == "stream":
-            out[i] = ops._stream()
-        elif how == "ws" and ws is not None:
-            out[i], out[i + 1] = ops._p(ws, torch.uint8, "ws"), ws.numel()
-    check(getattr(load(), name)(*out), name)
-
-
-def _ws(nbytes: int, device):
-    return ops.workspace(max(int(nbytes), 256), device)
 
 
 def n_fields(with_b: bool) -> int:
@@ -129,7 +58,7 @@ def boot_sums(pred: torch.Tensor, target: torch.Tensor, unit: torch.Tensor, seg:
     nb = load().mmg_boot_sums_ws_bytes(n, n_seg, replicates, with_b)
     _call("mmg_boot_sums", pred, target, pred_b, with_b, ops._p(unit, unit.dtype, "unit"), ops._p(seg, seg.dtype, "seg"),
           unit.element_size(), n, int(n_units), n_seg, replicates, int(seed) & 0xFFFFFFFFFFFFFFFF, sums, dropped,
-          ws=_ws(nb, dev))
+          ws=ops._ws(nb, dev))
     return sums, dropped
 
 

@@ -1,93 +1,24 @@
-"""ctypes binding and typed entry points of libmmgnn_cluster.so (C ABI: include/mmgnn_cluster.h; csrc/cluster.hip):
-k-means and the cluster scores, a library of its own beside libmmgnn.so.  The binding is derived from the header by the
-same parser as _lib's (``_lib.parse_header``) and the calls are marshalled from the prototypes as ``nn_ops._call``
-marshals them.  The library is REQUIRED: there is no CPU or eager-PyTorch fallback behind these calls.
+"""ctypes binding and typed entry points of libmmgnn_cluster.so (C ABI: include/mmgnn_cluster.h; csrc/cluster.hip): k-means
+and the cluster scores, a library of its own beside libmmgnn.so.  The binding is a ``_lib.Binding`` derived from the
+header, and every call goes through ``ops._call``.  The library is REQUIRED: there is no CPU or eager-PyTorch fallback
+behind these calls.
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
 from typing import Optional
 
 import torch
 
-from . import _lib, ops
-from ._lib import MmgError, check
+from . import ops
+from ._lib import check
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libmmgnn_cluster.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mmgnn_cluster.h")
-
-
-def _read_header():
-    try:
-        with open(HEADER_PATH) as f:
-            return f.read()
-    except OSError as e:
-        raise MmgError(f"{HEADER_PATH} not found: the binding is derived from the header the library is built from "
-                       f"({e})") from None
-
-
-PARAMS = {}
-DEFINES, STRUCTS, SIGNATURES = _lib.parse_header(_read_header(), PARAMS)
-globals().update(DEFINES)
-_PLANS = {sym: ops._plan(params) for sym, params in PARAMS.items()}
+BINDING = ops.satellite("cluster", globals())    # LIB_PATH, HEADER_PATH, DEFINES, SIGNATURES, PARAMS, MMG_*, load, _call
 
 KM_MAX_K = DEFINES["MMG_KM_MAX_K"]                  # csrc/cluster.hip: 1 <= k <= KM_MAX_K
 KM_MAX_D = DEFINES["MMG_KM_MAX_D"]                  # the widest row
 KM_ROW_TILE = DEFINES["MMG_KM_ROW_TILE"]            # rows of a workgroup's block, rows per LDS tile
 KM_MAX_RANGES = DEFINES["MMG_KM_MAX_RANGES"]        # row ranges of the fixed-order sums
 KM_MAX_GRID = DEFINES["MMG_KM_MAX_GRID"]            # workgroups of a launch: each walks work items in strides of the grid
-
-_kmlib = None
-
-
-def load():
-    """Load libmmgnn_cluster.so (once), after libmmgnn.so, which it uses.  Raises MmgError loudly when it has not been
-    built."""
-    global _kmlib
-    if _kmlib is not None:
-        return _kmlib
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise MmgError(f"{LIB_PATH} not found: the HIP library is mandatory (no CPU fallback). Build it with "
-                       f"`make -C {os.path.join(_HERE, 'csrc')}` or `python -c 'import __graft_entry__ as g; g.build()'`.")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)     # AttributeError here = header/library mismatch
-        fn.restype = res
-        fn.argtypes = args
-    _kmlib = lib
-    return lib
-
-
-def _call(name, *args, ws=None):
-    """nn_ops._call for this library: `args` are the parameters of the prototype of `name` without stream, ws and
-    ws_bytes; a torch.Tensor handed to a scalar pointer parameter is converted under the header's dtype and name, tensors
-    on different devices are refused; ws: the call's uint8 workspace tensor."""
-    plan, n_given = _PLANS[name]
-    if len(args) != n_given:
-        raise TypeError(f"{name}: takes {n_given} arguments besides ws and stream, got {len(args)}")
-    out, dev, given = [], None, iter(args)
-    for how in plan:
-        a = (0 if how == "ws_bytes" else None) if isinstance(how, str) else next(given)
-        if how is not None and isinstance(a, torch.Tensor):
-            t, a = a, ops._p(a, how[1], how[0])
-            if dev is None:
-                dev = t.device
-            elif t.device != dev:
-                raise ValueError(f"{name}: {how[0]} is on {t.device}, the tensors before it on {dev}")
-        out.append(a)
-    for i, how in enumerate(plan):
-        if how == "stream":
-            out[i] = ops._stream()
-        elif how == "ws" and ws is not None:
-            out[i], out[i + 1] = ops._p(ws, torch.uint8, "ws"), ws.numel()
-    check(getattr(load(), name)(*out), name)
-
-
-def _ws(nbytes: int, device):
-    return ops.workspace(max(int(nbytes), 256), device)
 
 
 def km_plan(n: int):
@@ -128,7 +59,7 @@ def km_assign(x: torch.Tensor, centers: torch.Tensor, prev_labels: Optional[torc
     if labels.numel() != n or min_s.numel() != n or (prev_labels is not None and prev_labels.numel() != n):
         raise ValueError(f"km_assign: labels, min_s and prev_labels need {n} entries")
     _call("mmg_km_assign", px, n, D, ld, centers, k, prev_labels, labels, min_s, changed,
-          ws=_ws(load().mmg_km_assign_ws_bytes(n, D, k), x.device))
+          ws=ops._ws(load().mmg_km_assign_ws_bytes(n, D, k), x.device))
     return labels, min_s
 
 
@@ -164,7 +95,7 @@ def km_update(x: torch.Tensor, labels: torch.Tensor, min_s: torch.Tensor, center
     if reloc_rows is not None and reloc_rows.numel() != k:
         raise ValueError(f"km_update: reloc_rows needs {k} entries")
     _call("mmg_km_update", px, n, D, ld, labels, min_s, centers_old, k, centers_new, counts, changed, status, reloc_rows,
-          ws=_ws(load().mmg_km_update_ws_bytes(n, D, k), x.device))
+          ws=ops._ws(load().mmg_km_update_ws_bytes(n, D, k), x.device))
     return centers_new, counts, status
 
 
@@ -174,7 +105,7 @@ def km_colstats(x: torch.Tensor):
     px, n, D, ld = ops._rows_matrix(x, "x")
     mean = torch.empty(D, dtype=torch.float64, device=x.device)
     var = torch.empty(1, dtype=torch.float64, device=x.device)
-    _call("mmg_km_colstats", px, n, D, ld, mean, var, ws=_ws(load().mmg_km_colstats_ws_bytes(n, D), x.device))
+    _call("mmg_km_colstats", px, n, D, ld, mean, var, ws=ops._ws(load().mmg_km_colstats_ws_bytes(n, D), x.device))
     return mean, var
 
 
@@ -187,7 +118,7 @@ def km_scores(labels: torch.Tensor, min_s: torch.Tensor, k: int):
     inertia = torch.empty(1, dtype=torch.float64, device=labels.device)
     sdist = torch.empty(k, dtype=torch.float64, device=labels.device)
     counts = torch.empty(k, dtype=torch.int32, device=labels.device)
-    _call("mmg_km_scores", labels, min_s, n, k, inertia, sdist, counts, ws=_ws(load().mmg_km_scores_ws_bytes(n, k), labels.device))
+    _call("mmg_km_scores", labels, min_s, n, k, inertia, sdist, counts, ws=ops._ws(load().mmg_km_scores_ws_bytes(n, k), labels.device))
     return inertia, sdist, counts
 
 
@@ -203,5 +134,5 @@ def km_silhouette(x: torch.Tensor, labels: torch.Tensor, counts: torch.Tensor, q
     sil = torch.empty(nq, dtype=torch.float64, device=x.device)
     mean = torch.empty(1, dtype=torch.float64, device=x.device) if want_mean else None
     _call("mmg_km_silhouette", px, n, D, ld, labels, counts, k, queries, nq, sil, mean,
-          ws=_ws(load().mmg_km_silhouette_ws_bytes(n, D, nq, k), x.device))
+          ws=ops._ws(load().mmg_km_silhouette_ws_bytes(n, D, nq, k), x.device))
     return sil, mean

@@ -1,39 +1,18 @@
-"""ctypes binding and typed entry points of libmmgnn_conformal.so (C ABI: include/mmgnn_conformal.h;
-csrc/conformal.hip): segmented order statistics, the conformal table, the interval epilogues and their coverage counts,
-a library of its own beside libmmgnn.so.  The binding is derived from the header by the same parser as _lib's
-(``_lib.parse_header``) and the calls are marshalled from the prototypes as ``cluster_ops._call`` marshals them.  The
-library is REQUIRED: there is no CPU or eager-PyTorch fallback behind these calls (the numpy restatement of
-mmgnn/conformal.py serves numpy inputs and checks the kernels; it is never a silent substitute for them).
+"""ctypes binding and typed entry points of libmmgnn_conformal.so (C ABI: include/mmgnn_conformal.h; csrc/conformal.hip):
+segmented order statistics, the conformal table, the interval epilogues and their coverage counts, a library of its own
+beside libmmgnn.so.  The binding is a ``_lib.Binding`` derived from the header, and every call goes through
+``ops._call``.  The library is REQUIRED: there is no CPU or eager-PyTorch fallback behind these calls (the numpy
+restatement of mmgnn/conformal.py serves numpy inputs and checks the kernels; it is never a silent substitute for them).
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
 from typing import Optional
 
 import torch
 
-from . import _lib, ops
-from ._lib import MmgError, check
+from . import ops
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libmmgnn_conformal.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mmgnn_conformal.h")
-
-
-def _read_header():
-    try:
-        with open(HEADER_PATH) as f:
-            return f.read()
-    except OSError as e:
-        raise MmgError(f"{HEADER_PATH} not found: the binding is derived from the header the library is built from "
-                       f"({e})") from None
-
-
-PARAMS = {}
-DEFINES, STRUCTS, SIGNATURES = _lib.parse_header(_read_header(), PARAMS)
-globals().update(DEFINES)
-_PLANS = {sym: ops._plan(params) for sym, params in PARAMS.items()}
+BINDING = ops.satellite("conformal", globals())    # LIB_PATH, HEADER_PATH, DEFINES, SIGNATURES, PARAMS, MMG_*, load, _call
 
 CF_SIGNED = DEFINES["MMG_CF_SIGNED"]
 CF_ABSOLUTE = DEFINES["MMG_CF_ABSOLUTE"]
@@ -43,70 +22,6 @@ CF_MAX_CELLS = DEFINES["MMG_CF_MAX_CELLS"]
 CF_DROP_KINDS = DEFINES["MMG_CF_DROP_KINDS"]      # lab out of range, patient out of range, degree in no bin, NaN key
 CF_COV_FIELDS = DEFINES["MMG_CF_COV_FIELDS"]      # n, covered, below, above, infinite, dropped
 MODES = {"signed": CF_SIGNED, "absolute": CF_ABSOLUTE}
-
-_cflib = None
-
-
-def load():
-    """Load libmmgnn_conformal.so (once), after libmmgnn.so, which it uses.  Raises MmgError loudly when it has not been
-    built."""
-    global _cflib
-    if _cflib is not None:
-        return _cflib
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise MmgError(f"{LIB_PATH} not found: the HIP library is mandatory (no CPU fallback). Build it with "
-                       f"`make -C {os.path.join(_HERE, 'csrc')}` or `python -c 'import __graft_entry__ as g; g.build()'`.")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)     # AttributeError here = header/library mismatch
-        fn.restype = res
-        fn.argtypes = args
-    _cflib = lib
-    return lib
-
-
-def _call(name, *args, ws=None):
-    """cluster_ops._call for this library: `args` are the parameters of the prototype of `name` without stream, ws and
-    ws_bytes; a torch.Tensor handed to a scalar pointer parameter is converted under the header's dtype and name, tensors
-    on different devices are refused; ws: the call's uint8 workspace tensor."""
-    plan, n_given = _PLANS[name]
-    if len(args) != n_given:
-        raise TypeError(f"{name}: takes {n_given} arguments besides ws and stream, got {len(args)}")
-    out, dev, given = [], None, iter(args)
-    for how in plan:
-        a = (0 if how == "ws_bytes" else None) if isinstance(how, str) else next(given)
-        if how is not None and isinstance(a, torch.Tensor):
-            t, a = a, ops._p(a, how[1], how[0])
-            if dev is None:
-                dev = t.device
-            elif t.device != dev:
-                raise ValueError(f"{name}: {how[0]} is on {t.device}, the tensors before it on {dev}")
-        out.append(a)
-    for i, how in enumerate(plan):
-        if how == "stream":
-            out[i] = ops._stream()
-        elif how == "ws" and ws is not None:
-            out[i], out[i + 1] = ops._p(ws, torch.uint8, "ws"), ws.numel()
-    check(getattr(load(), name)(*out), name)
-
-
-def _ws(nbytes: int, device):
-    return ops.workspace(max(int(nbytes), 256), device)
-
-
-def _edges(bin_edges):
-    e = [float(x) for x in bin_edges]
-    return (C.c_double * len(e))(*e), len(e) - 1
-
-
-def _index_pair(patient: torch.Tensor, lab: torch.Tensor, n: int, what: str):
-    """The two index tensors of the pairs as untyped pointers + their width; int64 or int32, both the same."""
-    if patient.dtype != lab.dtype or patient.dtype not in (torch.int64, torch.int32):
-        raise TypeError(f"{what}: patient and lab indices must both be int64 or both int32, got {patient.dtype} / {lab.dtype}")
-    if patient.numel() != n or lab.numel() != n:
-        raise ValueError(f"{what}: {patient.numel()} patient and {lab.numel()} lab indices for {n} pairs")
-    return ops._p(patient, patient.dtype, "patient"), ops._p(lab, lab.dtype, "lab"), patient.element_size()
 
 
 def seg_order_stats(keys: torch.Tensor, seg: torch.Tensor, n_seg: int, alpha: float, mode: str = "signed",
@@ -121,7 +36,7 @@ def seg_order_stats(keys: torch.Tensor, seg: torch.Tensor, n_seg: int, alpha: fl
     usable = torch.empty_like(count)
     q_lo, q_hi, shift = (torch.empty(max(n_seg, 0), dtype=torch.float32, device=dev) for _ in range(3))
     _call("mmg_seg_order_stats", keys, seg, n, n_seg, float(alpha), MODES[mode], int(min_count), count, q_lo, q_hi, shift,
-          usable, ws=_ws(load().mmg_seg_order_stats_ws_bytes(n, n_seg), dev))
+          usable, ws=ops._ws(load().mmg_seg_order_stats_ws_bytes(n, n_seg), dev))
     return count, q_lo, q_hi, shift, usable
 
 
@@ -132,8 +47,8 @@ def cf_fit(pred: torch.Tensor, target: torch.Tensor, patient: torch.Tensor, lab:
     n, dev = int(pred.numel()), pred.device
     if target.numel() != n:
         raise ValueError("cf_fit: pred and target need the same length")
-    pp, pl, ib = _index_pair(patient, lab, n, "cf_fit")
-    ed, n_bins = _edges(bin_edges)
+    pp, pl, ib = ops._index_pair(patient, lab, n, "cf_fit")
+    ed, n_bins = ops._edges(bin_edges)
     n_labs = int(n_labs)
     n_cells = max(n_labs * n_bins, 0)
     table = torch.empty(3, n_cells, dtype=torch.float32, device=dev)
@@ -141,7 +56,7 @@ def cf_fit(pred: torch.Tensor, target: torch.Tensor, patient: torch.Tensor, lab:
     n_used = torch.empty(n_cells, dtype=torch.int32, device=dev)
     dropped = torch.empty(CF_DROP_KINDS, dtype=torch.int64, device=dev)
     _call("mmg_cf_fit", pred, target, pp, pl, ib, n, n_labs, deg, int(deg.numel()), ed, n_bins, float(alpha), MODES[mode],
-          int(min_count), table, level, n_used, dropped, ws=_ws(load().mmg_cf_fit_ws_bytes(n, n_labs, n_bins), dev))
+          int(min_count), table, level, n_used, dropped, ws=ops._ws(load().mmg_cf_fit_ws_bytes(n, n_labs, n_bins), dev))
     return table, level, n_used, dropped
 
 
@@ -154,8 +69,8 @@ def cf_apply_pairs(pred: torch.Tensor, patient: torch.Tensor, lab: torch.Tensor,
                    table: torch.Tensor, use_shift: bool = False):
     """(point, lower, upper) fp32 [n] of the pairs under the table (mmg_cf_apply_pairs)."""
     n, dev = int(pred.numel()), pred.device
-    pp, pl, ib = _index_pair(patient, lab, n, "cf_apply_pairs")
-    ed, n_bins = _edges(bin_edges)
+    pp, pl, ib = ops._index_pair(patient, lab, n, "cf_apply_pairs")
+    ed, n_bins = ops._edges(bin_edges)
     _check_table(table, int(n_labs), n_bins, "cf_apply_pairs")
     point, lower, upper = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
     _call("mmg_cf_apply_pairs", pred, pp, pl, ib, n, int(n_labs), deg, int(deg.numel()), ed, n_bins, table,
@@ -169,7 +84,7 @@ def cf_apply_matrix(pred: torch.Tensor, rows: Optional[torch.Tensor], deg: torch
     (mmg_cf_apply_matrix).  rows: int64 / int32 [n_rows] patient index of every row, None: row i is patient i.  out: three
     [n_rows, n_labs] fp32 views with unit column stride and ONE common row stride."""
     px, n_rows, n_labs, ld = ops._rows_matrix(pred, "pred")
-    ed, n_bins = _edges(bin_edges)
+    ed, n_bins = ops._edges(bin_edges)
     _check_table(table, n_labs, n_bins, "cf_apply_matrix")
     pr, ib = None, 8
     if rows is not None:
@@ -199,13 +114,13 @@ def cf_coverage(pred: torch.Tensor, target: torch.Tensor, patient: torch.Tensor,
     n, dev = int(pred.numel()), pred.device
     if target.numel() != n:
         raise ValueError("cf_coverage: pred and target need the same length")
-    pp, pl, ib = _index_pair(patient, lab, n, "cf_coverage")
-    ed, n_bins = _edges(bin_edges)
+    pp, pl, ib = ops._index_pair(patient, lab, n, "cf_coverage")
+    ed, n_bins = ops._edges(bin_edges)
     n_labs = int(n_labs)
     _check_table(table, n_labs, n_bins, "cf_coverage")
     n_cells = n_labs * n_bins
     counts = torch.empty(n_cells + 1, CF_COV_FIELDS, dtype=torch.int64, device=dev)
     width = torch.empty(n_cells + 1, dtype=torch.float64, device=dev)
     _call("mmg_cf_coverage", pred, target, pp, pl, ib, n, n_labs, deg, int(deg.numel()), ed, n_bins, table, counts, width,
-          ws=_ws(load().mmg_cf_coverage_ws_bytes(n, n_labs, n_bins), dev))
+          ws=ops._ws(load().mmg_cf_coverage_ws_bytes(n, n_labs, n_bins), dev))
     return counts, width

@@ -24,6 +24,7 @@
 // fused and the unfused form round alike.
 // Built into libmmgnn_boot.so beside libmmgnn.so and on top of it (mmg_set_error).
 #include "common.h"
+#include "cells.h"
 #include "radix_sort.h"
 #include "../../include/mmgnn_boot.h"
 #include <limits.h>
@@ -54,27 +55,6 @@ __device__ __forceinline__ uint32_t bt_weight(uint32_t key, uint32_t half_unit, 
 #pragma unroll
   for (int j = 0; j < 8; ++j) w += field >= BT_T[j] ? 1u : 0u;
   return w;
-}
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-inline int bits_of(unsigned v) {
-  int b = 0;
-  while (v) { ++b; v >>= 1; }
-  return b;
-}
-inline unsigned bt_grid(int64_t n, int per_thread = 4) {
-  int64_t b = (n + (int64_t)BT_NTHR * per_thread - 1) / ((int64_t)BT_NTHR * per_thread);
-  return (unsigned)(b < 1 ? 1 : b > BT_MAX_GRID ? BT_MAX_GRID : b);
 }
 
 // ---------------------------------------------------------------------------------- keys
@@ -223,16 +203,6 @@ __global__ __launch_bounds__(BT_NTHR) void k_boot_sums(const uint32_t* __restric
   if (cur < (uint32_t)n_seg && live) acc.store(part + bt_slot(c, cur == first ? 0 : 1, r, R1, F));
 }
 
-__device__ __forceinline__ int64_t bt_lower_bound(const uint32_t* __restrict__ K, int64_t n, uint32_t v) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (K[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 template <int F>
 __global__ __launch_bounds__(BT_NTHR) void k_boot_combine(const uint32_t* __restrict__ K, int64_t n, int n_seg,
                                                           int replicates, const double* __restrict__ part,
@@ -241,7 +211,7 @@ __global__ __launch_bounds__(BT_NTHR) void k_boot_combine(const uint32_t* __rest
   __shared__ int s_skip;
   const int R1 = replicates + 1;
   const uint32_t s = blockIdx.x;
-  if (threadIdx.x < 2) s_b[threadIdx.x] = bt_lower_bound(K, n, s + threadIdx.x);
+  if (threadIdx.x < 2) s_b[threadIdx.x] = lower_bound(K, n, s + threadIdx.x);
   __syncthreads();
   const int64_t lo = s_b[0], hi = s_b[1];
   const int64_t c0 = lo / BT_CHUNK, c1 = hi > lo ? (hi - 1) / BT_CHUNK : c0;
@@ -490,13 +460,13 @@ extern "C" int mmg_boot_sums(const float* pred, const float* target, const float
   const unsigned rblocks = (unsigned)((replicates + 1 + BT_RB - 1) / BT_RB);
   if (n > 0) {
     if (index_bytes == 8)
-      hipLaunchKernelGGL(k_boot_keys<int64_t>, dim3(bt_grid(n)), dim3(BT_NTHR), 0, st, pred, target, pred_b,
-                         (const int64_t*)unit, (const int64_t*)seg, n, n_units, n_seg, w.kv.keys, w.kv.vals, w.unit32,
-                         (unsigned long long*)dropped);
+      hipLaunchKernelGGL(k_boot_keys<int64_t>, dim3(launch_grid(n, BT_NTHR, BT_MAX_GRID)), dim3(BT_NTHR), 0, st, pred,
+                         target, pred_b, (const int64_t*)unit, (const int64_t*)seg, n, n_units, n_seg, w.kv.keys, w.kv.vals,
+                         w.unit32, (unsigned long long*)dropped);
     else
-      hipLaunchKernelGGL(k_boot_keys<int32_t>, dim3(bt_grid(n)), dim3(BT_NTHR), 0, st, pred, target, pred_b,
-                         (const int32_t*)unit, (const int32_t*)seg, n, n_units, n_seg, w.kv.keys, w.kv.vals, w.unit32,
-                         (unsigned long long*)dropped);
+      hipLaunchKernelGGL(k_boot_keys<int32_t>, dim3(launch_grid(n, BT_NTHR, BT_MAX_GRID)), dim3(BT_NTHR), 0, st, pred,
+                         target, pred_b, (const int32_t*)unit, (const int32_t*)seg, n, n_units, n_seg, w.kv.keys, w.kv.vals,
+                         w.unit32, (unsigned long long*)dropped);
     MMG_CHECK_LAUNCH("boot_sums(keys)");
     const int passes = (bits_of((unsigned)n_seg) + 7) / 8;               // the key reaches n_seg itself
     for (int ps = 0; ps < passes; ++ps) radix_pass<false>(w.kv, n, 8 * ps, nullptr, w.hist, w.scr, st);
@@ -526,7 +496,7 @@ extern "C" int mmg_boot_metrics(const double* sums, int n_seg, int replicates, i
   if (rc) return rc;
   MMG_CHECK_ARG(sums && metrics, "boot_metrics: null sums or metrics");
   const int64_t cells = (int64_t)(replicates + 1) * (n_seg + 1);
-  const dim3 grid(bt_grid(cells, 1)), block(BT_NTHR);
+  const dim3 grid(launch_grid(cells, BT_NTHR, BT_MAX_GRID, 1)), block(BT_NTHR);
   hipStream_t st = (hipStream_t)stream;
   if (with_b) hipLaunchKernelGGL(k_boot_metrics<true>, grid, block, 0, st, sums, n_seg, replicates, metrics);
   else hipLaunchKernelGGL(k_boot_metrics<false>, grid, block, 0, st, sums, n_seg, replicates, metrics);

@@ -23,6 +23,7 @@
 //                     sums in a fixed order.  No atomics.
 // Built into libmmgnn_conformal.so beside libmmgnn.so and on top of it (mmg_set_error).
 #include "common.h"
+#include "cells.h"
 #include "radix_sort.h"
 #include "../../include/mmgnn_conformal.h"
 #include <limits.h>
@@ -38,9 +39,6 @@ constexpr int CF_BLOCK_CELLS = 8192;      // cells of a block: R = CF_BLOCK_CELL
 static_assert(MMG_CF_MAX_BINS == MMG_AN_MAX_BINS, "the degree bins of mmg_pair_analysis");
 static_assert(MMG_CF_MAX_CELLS <= 65536, "the coverage sort runs over two digits of the cell");
 
-struct CfEdges {
-  double e[MMG_CF_MAX_BINS + 1];
-};
 struct CfRanks {
   double a_lo, a_hi;      // alpha / 2 and 1 - alpha / 2 (signed), unused and 1 - alpha (absolute)
   int mode;
@@ -54,29 +52,6 @@ __device__ __forceinline__ uint32_t cf_orderable(float x) {
 __device__ __forceinline__ float cf_key_value(unsigned long long k) {
   const uint32_t o = (uint32_t)k;
   return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-template <class IT>
-__device__ __forceinline__ int cf_index(const IT* __restrict__ p, int64_t i, int64_t limit) {
-  const int64_t v = (int64_t)p[i];
-  return v >= 0 && v < limit ? (int)v : -1;
-}
-__device__ __forceinline__ int cf_bin(int d, const CfEdges& ed, int B) {
-  const double dd = (double)d;
-  int b = -1;
-  for (int j = 0; j < B; ++j)
-    if (dd >= ed.e[j] && dd < ed.e[j + 1]) b = j;
-  return b;
-}
-// the cell of a pair; -1 - kind for a pair without one (kind 0: lab, 1: patient, 2: degree in no bin)
-template <class IT>
-__device__ __forceinline__ int cf_cell(const IT* __restrict__ patient, const IT* __restrict__ lab, int64_t i, int L,
-                                       const int32_t* __restrict__ deg, int64_t n_pat, const CfEdges& ed, int B) {
-  const int l = cf_index(lab, i, L);
-  if (l < 0) return -1;
-  const int p = cf_index(patient, i, n_pat);
-  if (p < 0) return -2;
-  const int b = cf_bin(deg[p], ed, B);
-  return b < 0 ? -3 : l * B + b;
 }
 
 // ---------------------------------------------------------------------------------- segmented order statistics
@@ -93,17 +68,6 @@ __global__ __launch_bounds__(CF_NTHR) void k_sos_keys(const float* __restrict__ 
   }
 }
 
-// first position in K [0, n) whose key is >= v
-__device__ __forceinline__ int64_t cf_lower_bound(const unsigned long long* __restrict__ K, int64_t n, unsigned long long v) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (K[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(CF_NTHR) void k_sos_pick(const unsigned long long* __restrict__ K, int64_t n, int n_seg,
                                                       CfRanks rk, int32_t* __restrict__ count, float* __restrict__ q_lo,
                                                       float* __restrict__ q_hi, float* __restrict__ shift,
@@ -111,8 +75,8 @@ __global__ __launch_bounds__(CF_NTHR) void k_sos_pick(const unsigned long long* 
 #pragma clang fp contract(off)
   const int s = blockIdx.x * CF_NTHR + threadIdx.x;
   if (s >= n_seg) return;
-  const int64_t lo = cf_lower_bound(K, n, (unsigned long long)s << 32);
-  const int64_t hi = cf_lower_bound(K, n, (unsigned long long)(s + 1) << 32);
+  const int64_t lo = lower_bound(K, n, (unsigned long long)s << 32);
+  const int64_t hi = lower_bound(K, n, (unsigned long long)(s + 1) << 32);
   const int64_t m = hi - lo;
   const double m1 = (double)(m + 1);
   const int64_t k_hi = (int64_t)ceil(m1 * rk.a_hi);
@@ -158,15 +122,6 @@ size_t sos_carve(MmgCarver& c, int64_t n, SosWs* w) {
   w->scr = c.take<uint32_t>(rs.scratch_elems);
   return c.need();
 }
-inline int bits_of(unsigned v) {         // bits needed to write v
-  int b = 0;
-  while (v) { ++b; v >>= 1; }
-  return b;
-}
-inline unsigned cf_grid(int64_t n, int per_thread = 4) {
-  int64_t g = (n + (int64_t)CF_NTHR * per_thread - 1) / ((int64_t)CF_NTHR * per_thread);
-  return (unsigned)(g < 1 ? 1 : g > CF_MAX_GRID ? CF_MAX_GRID : g);
-}
 
 struct SosOut {
   int32_t* count;
@@ -180,7 +135,8 @@ int sos_run(const char* what, const float* keys, const int32_t* seg, int64_t n, 
             const SosOut& o, SosWs w, hipStream_t st) {
   const int n_seg = (n_seg_in + div - 1) / div;
   if (n > 0) {
-    hipLaunchKernelGGL(k_sos_keys, dim3(cf_grid(n)), dim3(CF_NTHR), 0, st, keys, seg, n, n_seg_in, div, n_seg, w.kv.keys);
+    hipLaunchKernelGGL(k_sos_keys, dim3(launch_grid(n, CF_NTHR, CF_MAX_GRID)), dim3(CF_NTHR), 0, st, keys, seg, n, n_seg_in,
+                       div, n_seg, w.kv.keys);
     MMG_CHECK_LAUNCH(what);
     const int passes = 4 + (bits_of((unsigned)n_seg) + 7) / 8;          // segment values reach n_seg itself
     for (int ps = 0; ps < passes; ++ps) radix_pass<false>(w.kv, n, 8 * ps, nullptr, w.hist, w.scr, st);
@@ -206,19 +162,9 @@ int ranks_check(const char* what, double alpha, int mode, int64_t min_count, CfR
 
 // ---------------------------------------------------------------------------------- pairs -> cells
 int pairs_check(const char* what, const void* pred, const void* patient, const void* lab, int index_bytes, int64_t n, int L,
-                const int32_t* deg, int64_t n_pat, const double* edges, int B, CfEdges* ed) {
-  MMG_CHECK_ARG(n >= 0 && n <= INT32_MAX, "%s: n %lld outside [0, 2^31)", what, (long long)n);
-  MMG_CHECK_ARG(L >= 1 && L <= MMG_CF_MAX_LABS, "%s: %d labs outside [1, %d]", what, L, MMG_CF_MAX_LABS);
-  MMG_CHECK_ARG(B >= 1 && B <= MMG_CF_MAX_BINS, "%s: %d degree bins outside [1, %d]", what, B, MMG_CF_MAX_BINS);
-  MMG_CHECK_ARG((int64_t)L * B <= MMG_CF_MAX_CELLS, "%s: %d labs x %d bins, at most %d cells", what, L, B, MMG_CF_MAX_CELLS);
-  MMG_CHECK_ARG(index_bytes == 4 || index_bytes == 8, "%s: indices of %d bytes (int32 or int64)", what, index_bytes);
-  MMG_CHECK_ARG(n_pat >= 0 && n_pat <= INT32_MAX, "%s: %lld patients outside [0, 2^31)", what, (long long)n_pat);
-  MMG_CHECK_ARG(edges, "%s: null bin edges", what);
-  for (int j = 0; j <= B; ++j) {
-    MMG_CHECK_ARG(edges[j] == edges[j] && (j == 0 || edges[j] > edges[j - 1]), "%s: bin edges must be ascending (edge %d)",
-                  what, j);
-    ed->e[j] = edges[j];
-  }
+                const int32_t* deg, int64_t n_pat, const double* edges, int B, CellEdges* ed) {
+  const int rc = cells_check(what, index_bytes, n, L, n_pat, edges, B, ed);
+  if (rc != MMG_OK) return rc;
   MMG_CHECK_ARG(n == 0 || (pred && patient && lab), "%s: null pred, patient or lab", what);
   MMG_CHECK_ARG(n_pat == 0 || deg, "%s: null deg", what);
   return MMG_OK;
@@ -228,13 +174,13 @@ template <class IT>
 __global__ __launch_bounds__(CF_NTHR) void k_cf_prepare(const float* __restrict__ pred, const float* __restrict__ target,
                                                         const IT* __restrict__ patient, const IT* __restrict__ lab,
                                                         int64_t n, int L, const int32_t* __restrict__ deg, int64_t n_pat,
-                                                        int B, CfEdges ed, int mode, float* __restrict__ key,
+                                                        int B, CellEdges ed, int mode, float* __restrict__ key,
                                                         int32_t* __restrict__ cell, unsigned long long* dropped) {
   __shared__ int s_drop[CF_NTHR / WAVE][MMG_CF_DROP_KINDS];
   int drop[MMG_CF_DROP_KINDS] = {0, 0, 0, 0};
   const int64_t step = (int64_t)gridDim.x * CF_NTHR;
   for (int64_t i = (int64_t)blockIdx.x * CF_NTHR + threadIdx.x; i < n; i += step) {
-    int c = cf_cell(patient, lab, i, L, deg, n_pat, ed, B);
+    int c = pair_cell(patient, lab, i, L, deg, n_pat, ed, B);
     const float r = target[i] - pred[i];
     const float k = mode == MMG_CF_SIGNED ? r : fabsf(r);
     if (c >= 0 && k != k) c = -4;
@@ -308,7 +254,7 @@ template <class IT, bool LDS>
 __global__ __launch_bounds__(CF_NTHR) void k_cf_apply_pairs(const float* __restrict__ pred, const IT* __restrict__ patient,
                                                             const IT* __restrict__ lab, int64_t n, int L,
                                                             const int32_t* __restrict__ deg, int64_t n_pat, int B,
-                                                            CfEdges ed, const float* __restrict__ table, int use_shift,
+                                                            CellEdges ed, const float* __restrict__ table, int use_shift,
                                                             float* __restrict__ point, float* __restrict__ lower,
                                                             float* __restrict__ upper) {
   extern __shared__ float cf_lds[];
@@ -322,7 +268,7 @@ __global__ __launch_bounds__(CF_NTHR) void k_cf_apply_pairs(const float* __restr
   const int64_t step = (int64_t)gridDim.x * CF_NTHR;
   for (int64_t i = (int64_t)blockIdx.x * CF_NTHR + threadIdx.x; i < n; i += step) {
     const float p = pred[i];
-    const int c = cf_cell(patient, lab, i, L, deg, n_pat, ed, B);
+    const int c = pair_cell(patient, lab, i, L, deg, n_pat, ed, B);
     float lo = -INFINITY, hi = INFINITY, sh = 0.f;
     if (c >= 0) {
       lo = T[c]; hi = T[n_cells + c]; sh = T[2 * n_cells + c];
@@ -341,7 +287,7 @@ template <> struct CfVec<4> { using type = float4; };
 template <class IT, int VEC, bool LDS>
 __global__ __launch_bounds__(CF_NTHR) void k_cf_apply_matrix(const float* __restrict__ pred, int64_t n_rows, int L, int64_t ld,
                                                              const IT* __restrict__ rows, const int32_t* __restrict__ deg,
-                                                             int64_t n_pat, int B, CfEdges ed,
+                                                             int64_t n_pat, int B, CellEdges ed,
                                                              const float* __restrict__ table, int use_shift,
                                                              float* __restrict__ point, float* __restrict__ lower,
                                                              float* __restrict__ upper, int64_t ld_out, int R,
@@ -363,9 +309,9 @@ __global__ __launch_bounds__(CF_NTHR) void k_cf_apply_matrix(const float* __rest
     const int nr = (int)(n_rows - r0 < R ? n_rows - r0 : R);
     for (int t = threadIdx.x; t < nr; t += CF_NTHR) {      // the degree bin: once per row
       int p;
-      if (rows) p = cf_index(rows, r0 + t, n_pat);
+      if (rows) p = cell_index(rows, r0 + t, n_pat);
       else p = r0 + t < n_pat ? (int)(r0 + t) : -1;
-      rowbin[t] = p >= 0 ? cf_bin(deg[p], ed, B) : -1;
+      rowbin[t] = p >= 0 ? cell_bin(deg[p], ed, B) : -1;
     }
     __syncthreads();
     const unsigned items = (unsigned)nr * cpr;
@@ -417,24 +363,14 @@ __global__ __launch_bounds__(CF_NTHR) void k_cf_apply_matrix(const float* __rest
 template <class IT>
 __global__ __launch_bounds__(CF_NTHR) void k_cf_cov_keys(const IT* __restrict__ patient, const IT* __restrict__ lab,
                                                          int64_t n, int L, const int32_t* __restrict__ deg, int64_t n_pat,
-                                                         int B, CfEdges ed, uint32_t* __restrict__ key,
+                                                         int B, CellEdges ed, uint32_t* __restrict__ key,
                                                          int32_t* __restrict__ id) {
   const int64_t step = (int64_t)gridDim.x * CF_NTHR;
   for (int64_t i = (int64_t)blockIdx.x * CF_NTHR + threadIdx.x; i < n; i += step) {
-    const int c = cf_cell(patient, lab, i, L, deg, n_pat, ed, B);
+    const int c = pair_cell(patient, lab, i, L, deg, n_pat, ed, B);
     key[i] = c >= 0 ? (uint32_t)c : (uint32_t)(L * B);
     id[i] = (int32_t)i;
   }
-}
-
-__device__ __forceinline__ int64_t cf_lower_bound32(const uint32_t* __restrict__ K, int64_t n, uint32_t v) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (K[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
 }
 
 // segment s of the cell-sorted pair ids: s < n_cells a cell, s = n_cells the pairs without one
@@ -448,7 +384,7 @@ __global__ __launch_bounds__(CF_NTHR) void k_cf_cov_cells(const uint32_t* __rest
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   for (int s = blockIdx.x; s <= n_cells; s += gridDim.x) {
     __syncthreads();                                         // the previous segment's shared values are consumed
-    if (threadIdx.x < 2) s_bounds[threadIdx.x] = cf_lower_bound32(K, n, (uint32_t)s + threadIdx.x);
+    if (threadIdx.x < 2) s_bounds[threadIdx.x] = lower_bound(K, n, (uint32_t)s + threadIdx.x);
     __syncthreads();
     const int64_t lo = s_bounds[0], hi = s_bounds[1];
     const bool cell = s < n_cells;
@@ -553,7 +489,7 @@ extern "C" int mmg_cf_fit(const float* pred, const float* target, const void* pa
                           int64_t n, int n_labs, const int32_t* deg, int64_t n_patients, const double* bin_edges, int n_bins,
                           double alpha, int mode, int64_t min_count, float* table, int32_t* level, int32_t* n_used,
                           int64_t* dropped, void* ws, size_t ws_bytes, void* stream) {
-  CfEdges ed = {};
+  CellEdges ed = {};
   int rc = pairs_check("cf_fit", pred, patient, lab, index_bytes, n, n_labs, deg, n_patients, bin_edges, n_bins, &ed);
   if (rc) return rc;
   CfRanks rk;
@@ -568,13 +504,13 @@ extern "C" int mmg_cf_fit(const float* pred, const float* target, const void* pa
   MMG_CHECK_HIP(mmg_zero_async(dropped, MMG_CF_DROP_KINDS * sizeof(int64_t), st), "cf_fit(zero)");
   if (n > 0) {
     if (index_bytes == 8)
-      hipLaunchKernelGGL(k_cf_prepare<int64_t>, dim3(cf_grid(n)), dim3(CF_NTHR), 0, st, pred, target,
-                         (const int64_t*)patient, (const int64_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, mode, w.key,
-                         w.cell, (unsigned long long*)dropped);
+      hipLaunchKernelGGL(k_cf_prepare<int64_t>, dim3(launch_grid(n, CF_NTHR, CF_MAX_GRID)), dim3(CF_NTHR), 0, st, pred,
+                         target, (const int64_t*)patient, (const int64_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, mode,
+                         w.key, w.cell, (unsigned long long*)dropped);
     else
-      hipLaunchKernelGGL(k_cf_prepare<int32_t>, dim3(cf_grid(n)), dim3(CF_NTHR), 0, st, pred, target,
-                         (const int32_t*)patient, (const int32_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, mode, w.key,
-                         w.cell, (unsigned long long*)dropped);
+      hipLaunchKernelGGL(k_cf_prepare<int32_t>, dim3(launch_grid(n, CF_NTHR, CF_MAX_GRID)), dim3(CF_NTHR), 0, st, pred,
+                         target, (const int32_t*)patient, (const int32_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, mode,
+                         w.key, w.cell, (unsigned long long*)dropped);
     MMG_CHECK_LAUNCH("cf_fit(prepare)");
   }
   const int divs[3] = {1, n_bins, n_cells};
@@ -592,7 +528,7 @@ extern "C" int mmg_cf_apply_pairs(const float* pred, const void* patient, const 
                                   int n_labs, const int32_t* deg, int64_t n_patients, const double* bin_edges, int n_bins,
                                   const float* table, int use_shift, float* point, float* lower, float* upper,
                                   void* stream) {
-  CfEdges ed = {};
+  CellEdges ed = {};
   int rc = pairs_check("cf_apply_pairs", pred, patient, lab, index_bytes, n, n_labs, deg, n_patients, bin_edges, n_bins,
                        &ed);
   if (rc) return rc;
@@ -604,7 +540,7 @@ extern "C" int mmg_cf_apply_pairs(const float* pred, const void* patient, const 
   const bool lds = n_cells <= CF_LDS_CELLS;
   const size_t lds_bytes = lds ? (size_t)3 * n_cells * sizeof(float) : 0;
   // a workgroup that stages the table takes at least 8 pairs per thread
-  const dim3 grid(cf_grid(n, lds ? 8 : 4)), block(CF_NTHR);
+  const dim3 grid(launch_grid(n, CF_NTHR, CF_MAX_GRID, lds ? 8 : 4)), block(CF_NTHR);
 #define CF_APPLY_PAIRS(IT, LDS_)                                                                                          \
   hipLaunchKernelGGL((k_cf_apply_pairs<IT, LDS_>), grid, block, lds_bytes, st, pred, (const IT*)patient, (const IT*)lab, n, \
                      n_labs, deg, n_patients, n_bins, ed, table, use_shift, point, lower, upper)
@@ -624,7 +560,7 @@ extern "C" int mmg_cf_apply_matrix(const float* pred, int64_t n_rows, int n_labs
                                    int index_bytes, const int32_t* deg, int64_t n_patients, const double* bin_edges,
                                    int n_bins, const float* table, int use_shift, float* point, float* lower, float* upper,
                                    int64_t ld_out, void* stream) {
-  CfEdges ed = {};
+  CellEdges ed = {};
   int rc = pairs_check("cf_apply_matrix", pred, pred, pred, index_bytes, n_rows, n_labs, deg, n_patients, bin_edges, n_bins,
                        &ed);
   if (rc) return rc;
@@ -679,7 +615,7 @@ extern "C" int mmg_cf_coverage(const float* pred, const float* target, const voi
                                int index_bytes, int64_t n, int n_labs, const int32_t* deg, int64_t n_patients,
                                const double* bin_edges, int n_bins, const float* table, int64_t* counts, double* width,
                                void* ws, size_t ws_bytes, void* stream) {
-  CfEdges ed = {};
+  CellEdges ed = {};
   int rc = pairs_check("cf_coverage", pred, patient, lab, index_bytes, n, n_labs, deg, n_patients, bin_edges, n_bins, &ed);
   if (rc) return rc;
   MMG_CHECK_ARG(n == 0 || target, "cf_coverage: null target");
@@ -690,11 +626,13 @@ extern "C" int mmg_cf_coverage(const float* pred, const float* target, const voi
   const int n_cells = n_labs * n_bins;
   if (n > 0) {
     if (index_bytes == 8)
-      hipLaunchKernelGGL(k_cf_cov_keys<int64_t>, dim3(cf_grid(n)), dim3(CF_NTHR), 0, st, (const int64_t*)patient,
-                         (const int64_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, w.kv.keys, w.kv.vals);
+      hipLaunchKernelGGL(k_cf_cov_keys<int64_t>, dim3(launch_grid(n, CF_NTHR, CF_MAX_GRID)), dim3(CF_NTHR), 0, st,
+                         (const int64_t*)patient, (const int64_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, w.kv.keys,
+                         w.kv.vals);
     else
-      hipLaunchKernelGGL(k_cf_cov_keys<int32_t>, dim3(cf_grid(n)), dim3(CF_NTHR), 0, st, (const int32_t*)patient,
-                         (const int32_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, w.kv.keys, w.kv.vals);
+      hipLaunchKernelGGL(k_cf_cov_keys<int32_t>, dim3(launch_grid(n, CF_NTHR, CF_MAX_GRID)), dim3(CF_NTHR), 0, st,
+                         (const int32_t*)patient, (const int32_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, w.kv.keys,
+                         w.kv.vals);
     MMG_CHECK_LAUNCH("cf_coverage(keys)");
     const int passes = (bits_of((unsigned)n_cells) + 7) / 8;             // the key reaches n_cells itself
     for (int ps = 0; ps < passes; ++ps) radix_pass<false>(w.kv, n, 8 * ps, nullptr, w.hist, w.scr, st);

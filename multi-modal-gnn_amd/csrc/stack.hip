@@ -21,6 +21,7 @@
 // fp64 contraction is OFF for the whole file: the solve and the apply restate numpy arithmetic operation by operation.
 // Built into libmmgnn_stack.so beside libmmgnn.so and on top of it (mmg_set_error).
 #include "common.h"
+#include "cells.h"
 #include "radix_sort.h"
 #include "../../include/mmgnn_conformal.h"
 #include "../../include/mmgnn_stack.h"
@@ -45,41 +46,16 @@ static_assert((int64_t)MMG_ST_MAX_FOLDS * MMG_ST_MAX_CELLS < (1 << 24), "the sor
 
 constexpr int st_fields(int K) { return (K + 1) * (K + 2) / 2 + K + 2; }
 
-struct StEdges {
-  double e[MMG_ST_MAX_BINS + 1];
-};
 struct StFeats {
   const float* f[ST_MAX_K];
   int64_t ld[ST_MAX_K];      // the matrix epilogue's row strides
   int K;
 };
 
-template <class IT>
-__device__ __forceinline__ int st_index(const IT* __restrict__ p, int64_t i, int64_t limit) {
-  const int64_t v = (int64_t)p[i];
-  return v >= 0 && v < limit ? (int)v : -1;
-}
-__device__ __forceinline__ int st_bin(int d, const StEdges& ed, int B) {
-  const double dd = (double)d;
-  int b = -1;
-  for (int j = 0; j < B; ++j)
-    if (dd >= ed.e[j] && dd < ed.e[j + 1]) b = j;
-  return b;
-}
 __device__ __forceinline__ int st_fold(uint32_t key, int patient, int folds) {
   uint32_t w0, w1;
   mmg_rng_group(key, (uint64_t)(uint32_t)patient, &w0, &w1);       // w1 is dead code: only the first word is used
   return (int)(w0 % (uint32_t)folds);
-}
-
-inline int bits_of(unsigned v) {         // bits needed to write v
-  int b = 0;
-  while (v) { ++b; v >>= 1; }
-  return b;
-}
-inline unsigned st_grid(int64_t n, int per_thread = 4) {
-  int64_t g = (n + (int64_t)ST_NTHR * per_thread - 1) / ((int64_t)ST_NTHR * per_thread);
-  return (unsigned)(g < 1 ? 1 : g > ST_MAX_GRID ? ST_MAX_GRID : g);
 }
 
 // ---------------------------------------------------------------------------------- keys
@@ -88,16 +64,16 @@ template <class IT>
 __global__ __launch_bounds__(ST_NTHR) void k_st_keys(StFeats ft, const float* __restrict__ target,
                                                      const IT* __restrict__ patient, const IT* __restrict__ lab, int64_t n,
                                                      int L, const int32_t* __restrict__ deg, int64_t n_pat, int B,
-                                                     StEdges ed, int folds, uint32_t rng_key, uint32_t* __restrict__ key,
+                                                     CellEdges ed, int folds, uint32_t rng_key, uint32_t* __restrict__ key,
                                                      int32_t* __restrict__ id, unsigned long long* __restrict__ dropped) {
   int cnt[MMG_ST_DROP_KINDS] = {0, 0, 0, 0};
   const int n_cells = L * B, n_seg = folds * n_cells;
   const int64_t step = (int64_t)gridDim.x * ST_NTHR;
   for (int64_t i = (int64_t)blockIdx.x * ST_NTHR + threadIdx.x; i < n; i += step) {
     int kind = -1, seg = n_seg;
-    const int l = st_index(lab, i, L);
-    const int p = l >= 0 ? st_index(patient, i, n_pat) : -1;
-    const int b = p >= 0 ? st_bin(deg[p], ed, B) : -1;
+    const int l = cell_index(lab, i, L);
+    const int p = l >= 0 ? cell_index(patient, i, n_pat) : -1;
+    const int b = p >= 0 ? cell_bin(deg[p], ed, B) : -1;
     if (l < 0) kind = 0;
     else if (p < 0) kind = 1;
     else if (b < 0) kind = 2;
@@ -122,21 +98,11 @@ __global__ __launch_bounds__(ST_NTHR) void k_st_keys(StFeats ft, const float* __
   }
 }
 
-__device__ __forceinline__ int64_t st_lower_bound(const uint32_t* __restrict__ K, int64_t n, uint32_t v) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (K[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // seg_lo[s], s = 0 .. n_seg: the first sorted position whose key is >= s (seg_lo[n_seg] = the number of kept pairs)
 __global__ __launch_bounds__(ST_NTHR) void k_st_bounds(const uint32_t* __restrict__ K, int64_t n, int n_seg,
                                                        int64_t* __restrict__ seg_lo) {
   const int s = blockIdx.x * ST_NTHR + threadIdx.x;
-  if (s <= n_seg) seg_lo[s] = st_lower_bound(K, n, (uint32_t)s);
+  if (s <= n_seg) seg_lo[s] = lower_bound(K, n, (uint32_t)s);
 }
 
 // ---------------------------------------------------------------------------------- terms
@@ -356,7 +322,7 @@ __device__ __forceinline__ float st_apply(const double* __restrict__ w, const fl
 template <class IT>
 __global__ __launch_bounds__(ST_NTHR) void k_st_apply_pairs(StFeats ft, const IT* __restrict__ patient,
                                                             const IT* __restrict__ lab, int64_t n, int L,
-                                                            const int32_t* __restrict__ deg, int64_t n_pat, int B, StEdges ed,
+                                                            const int32_t* __restrict__ deg, int64_t n_pat, int B, CellEdges ed,
                                                             const double* __restrict__ coef, int folds, uint32_t rng_key,
                                                             int cross, float* __restrict__ out) {
   const int n_cells = L * B, P = ft.K + 1;
@@ -365,9 +331,9 @@ __global__ __launch_bounds__(ST_NTHR) void k_st_apply_pairs(StFeats ft, const IT
   for (int64_t i = (int64_t)blockIdx.x * ST_NTHR + threadIdx.x; i < n; i += step) {
     float v[ST_MAX_K];
     for (int k = 0; k < ft.K; ++k) v[k] = ft.f[k][i];
-    const int l = st_index(lab, i, L);
-    const int p = l >= 0 ? st_index(patient, i, n_pat) : -1;
-    const int b = p >= 0 ? st_bin(deg[p], ed, B) : -1;
+    const int l = cell_index(lab, i, L);
+    const int p = l >= 0 ? cell_index(patient, i, n_pat) : -1;
+    const int b = p >= 0 ? cell_bin(deg[p], ed, B) : -1;
     float y = v[0];
     if (b >= 0) {
       const int row = cross ? st_fold(rng_key, p, folds) : last;
@@ -380,7 +346,7 @@ __global__ __launch_bounds__(ST_NTHR) void k_st_apply_pairs(StFeats ft, const IT
 template <class IT>
 __global__ __launch_bounds__(ST_NTHR) void k_st_apply_matrix(StFeats ft, int64_t n_rows, int L, const IT* __restrict__ rows,
                                                              const int32_t* __restrict__ deg, int64_t n_pat, int B,
-                                                             StEdges ed, const double* __restrict__ coef, int folds,
+                                                             CellEdges ed, const double* __restrict__ coef, int folds,
                                                              uint32_t rng_key, int cross, float* __restrict__ out,
                                                              int64_t ld_out) {
   const int n_cells = L * B, P = ft.K + 1;
@@ -392,9 +358,9 @@ __global__ __launch_bounds__(ST_NTHR) void k_st_apply_matrix(StFeats ft, int64_t
     float v[ST_MAX_K];
     for (int k = 0; k < ft.K; ++k) v[k] = ft.f[k][r * ft.ld[k] + c];
     int p;
-    if (rows) p = st_index(rows, r, n_pat);
+    if (rows) p = cell_index(rows, r, n_pat);
     else p = r < n_pat ? (int)r : -1;
-    const int b = p >= 0 ? st_bin(deg[p], ed, B) : -1;
+    const int b = p >= 0 ? cell_bin(deg[p], ed, B) : -1;
     float y = v[0];
     if (b >= 0) {
       const int row = cross ? st_fold(rng_key, p, folds) : last;
@@ -411,20 +377,10 @@ bool shape_ok(int64_t n, int L, int B) {
 }
 bool model_ok(int K, int folds) { return K >= 1 && K <= MMG_ST_MAX_FEATURES && folds >= 1 && folds <= MMG_ST_MAX_FOLDS; }
 
-int cells_check(const char* what, const void* patient, const void* lab, int index_bytes, int64_t n, int L, const int32_t* deg,
-                int64_t n_pat, const double* edges, int B, StEdges* ed) {
-  MMG_CHECK_ARG(n >= 0 && n <= INT32_MAX, "%s: n %lld outside [0, 2^31)", what, (long long)n);
-  MMG_CHECK_ARG(L >= 1 && L <= MMG_ST_MAX_LABS, "%s: %d labs outside [1, %d]", what, L, MMG_ST_MAX_LABS);
-  MMG_CHECK_ARG(B >= 1 && B <= MMG_ST_MAX_BINS, "%s: %d degree bins outside [1, %d]", what, B, MMG_ST_MAX_BINS);
-  MMG_CHECK_ARG((int64_t)L * B <= MMG_ST_MAX_CELLS, "%s: %d labs x %d bins, at most %d cells", what, L, B, MMG_ST_MAX_CELLS);
-  MMG_CHECK_ARG(index_bytes == 4 || index_bytes == 8, "%s: indices of %d bytes (int32 or int64)", what, index_bytes);
-  MMG_CHECK_ARG(n_pat >= 0 && n_pat <= INT32_MAX, "%s: %lld patients outside [0, 2^31)", what, (long long)n_pat);
-  MMG_CHECK_ARG(edges, "%s: null bin edges", what);
-  for (int j = 0; j <= B; ++j) {
-    MMG_CHECK_ARG(edges[j] == edges[j] && (j == 0 || edges[j] > edges[j - 1]), "%s: bin edges must be ascending (edge %d)",
-                  what, j);
-    ed->e[j] = edges[j];
-  }
+int pairs_check(const char* what, const void* patient, const void* lab, int index_bytes, int64_t n, int L, const int32_t* deg,
+                int64_t n_pat, const double* edges, int B, CellEdges* ed) {
+  const int rc = cells_check(what, index_bytes, n, L, n_pat, edges, B, ed);      // the limits are equal by the assert above
+  if (rc != MMG_OK) return rc;
   MMG_CHECK_ARG(n == 0 || (patient && lab), "%s: null patient or lab", what);
   MMG_CHECK_ARG(n_pat == 0 || deg, "%s: null deg", what);
   return MMG_OK;
@@ -469,20 +425,20 @@ size_t sums_carve(void* ws, int64_t n, int n_seg, int NF, SumsWs* w) {
 // keys -> sort -> bounds -> chunks -> combine: sums [n_seg][T::NF]
 template <class T>
 int sums_run(const char* what, const StFeats& ft, const float* target, const void* patient, const void* lab, int index_bytes,
-             int64_t n, int L, const int32_t* deg, int64_t n_pat, int B, const StEdges& ed, int folds, uint64_t seed,
+             int64_t n, int L, const int32_t* deg, int64_t n_pat, int B, const CellEdges& ed, int folds, uint64_t seed,
              const T& terms, double* sums, int64_t* dropped, SumsWs w, hipStream_t st) {
   const int n_seg = folds * L * B;
   const uint32_t rng_key = mmg_rng_key(seed, (uint32_t)MMG_ST_SITE);
   MMG_CHECK_HIP(mmg_zero_async(dropped, MMG_ST_DROP_KINDS * sizeof(int64_t), st), what);
   if (n > 0) {
     if (index_bytes == 8)
-      hipLaunchKernelGGL(k_st_keys<int64_t>, dim3(st_grid(n)), dim3(ST_NTHR), 0, st, ft, target, (const int64_t*)patient,
-                         (const int64_t*)lab, n, L, deg, n_pat, B, ed, folds, rng_key, w.kv.keys, w.kv.vals,
-                         (unsigned long long*)dropped);
+      hipLaunchKernelGGL(k_st_keys<int64_t>, dim3(launch_grid(n, ST_NTHR, ST_MAX_GRID)), dim3(ST_NTHR), 0, st, ft, target,
+                         (const int64_t*)patient, (const int64_t*)lab, n, L, deg, n_pat, B, ed, folds, rng_key, w.kv.keys,
+                         w.kv.vals, (unsigned long long*)dropped);
     else
-      hipLaunchKernelGGL(k_st_keys<int32_t>, dim3(st_grid(n)), dim3(ST_NTHR), 0, st, ft, target, (const int32_t*)patient,
-                         (const int32_t*)lab, n, L, deg, n_pat, B, ed, folds, rng_key, w.kv.keys, w.kv.vals,
-                         (unsigned long long*)dropped);
+      hipLaunchKernelGGL(k_st_keys<int32_t>, dim3(launch_grid(n, ST_NTHR, ST_MAX_GRID)), dim3(ST_NTHR), 0, st, ft, target,
+                         (const int32_t*)patient, (const int32_t*)lab, n, L, deg, n_pat, B, ed, folds, rng_key, w.kv.keys,
+                         w.kv.vals, (unsigned long long*)dropped);
     MMG_CHECK_LAUNCH(what);
     const int passes = (bits_of((unsigned)n_seg) + 7) / 8;               // the key reaches n_seg itself
     for (int ps = 0; ps < passes; ++ps) radix_pass<false>(w.kv, n, 8 * ps, nullptr, w.hist, w.scr, st);
@@ -499,15 +455,15 @@ int sums_run(const char* what, const StFeats& ft, const float* target, const voi
     hipLaunchKernelGGL(k_st_chunks<T>, dim3(gx, (unsigned)gy), dim3(ST_NTHR), 0, st, w.kv.vals, w.seg_lo, n_seg, terms, w.part);
     MMG_CHECK_LAUNCH(what);
   }
-  hipLaunchKernelGGL(k_st_combine, dim3(st_grid((int64_t)n_seg * T::NF, 1)), dim3(ST_NTHR), 0, st, w.seg_lo, n_seg, T::NF,
-                     w.part, sums);
+  hipLaunchKernelGGL(k_st_combine, dim3(launch_grid((int64_t)n_seg * T::NF, ST_NTHR, ST_MAX_GRID, 1)), dim3(ST_NTHR), 0, st,
+                     w.seg_lo, n_seg, T::NF, w.part, sums);
   MMG_CHECK_LAUNCH(what);
   return MMG_OK;
 }
 
 template <int K_>
 int fit_sums(const StFeats& ft, const float* target, const void* patient, const void* lab, int index_bytes, int64_t n, int L,
-             const int32_t* deg, int64_t n_pat, int B, const StEdges& ed, int folds, uint64_t seed, double* sums,
+             const int32_t* deg, int64_t n_pat, int B, const CellEdges& ed, int folds, uint64_t seed, double* sums,
              int64_t* dropped, const SumsWs& w, hipStream_t st) {
   FitTerms<K_> terms;
   for (int k = 0; k < K_; ++k) terms.f[k] = ft.f[k];
@@ -540,9 +496,9 @@ extern "C" int mmg_stack_sums(const float* const* feats, int n_features, const f
                               const void* lab, int index_bytes, int64_t n, int n_labs, const int32_t* deg,
                               int64_t n_patients, const double* bin_edges, int n_bins, int folds, uint64_t seed, double* sums,
                               int64_t* dropped, void* ws, size_t ws_bytes, void* stream) {
-  StEdges ed = {};
+  CellEdges ed = {};
   StFeats ft;
-  int rc = cells_check("stack_sums", patient, lab, index_bytes, n, n_labs, deg, n_patients, bin_edges, n_bins, &ed);
+  int rc = pairs_check("stack_sums", patient, lab, index_bytes, n, n_labs, deg, n_patients, bin_edges, n_bins, &ed);
   if (rc) return rc;
   if ((rc = model_check("stack_sums", n_features, folds))) return rc;
   if ((rc = feats_check("stack_sums", feats, n_features, n > 0, &ft))) return rc;
@@ -583,15 +539,16 @@ extern "C" int mmg_stack_solve(const double* sums, int n_labs, int n_bins, int n
   hipStream_t st = (hipStream_t)stream;
   const int n_cells = n_labs * n_bins, F = st_fields(n_features), fo = folds > 1 ? folds + 1 : 1;
   const int64_t per_fold = (int64_t)n_cells * F;
-  hipLaunchKernelGGL(k_st_train, dim3(st_grid(per_fold * fo, 1)), dim3(ST_NTHR), 0, st, sums, per_fold, folds, fo, w.T);
-  hipLaunchKernelGGL(k_st_group, dim3(st_grid((int64_t)fo * n_labs * F, 1)), dim3(ST_NTHR), 0, st, w.T, (int64_t)fo * n_labs,
-                     n_bins, F, w.labs);
-  hipLaunchKernelGGL(k_st_group, dim3(st_grid((int64_t)fo * F, 1)), dim3(ST_NTHR), 0, st, w.labs, (int64_t)fo, n_labs, F,
-                     w.all);
+  hipLaunchKernelGGL(k_st_train, dim3(launch_grid(per_fold * fo, ST_NTHR, ST_MAX_GRID, 1)), dim3(ST_NTHR), 0, st, sums,
+                     per_fold, folds, fo, w.T);
+  hipLaunchKernelGGL(k_st_group, dim3(launch_grid((int64_t)fo * n_labs * F, ST_NTHR, ST_MAX_GRID, 1)), dim3(ST_NTHR), 0, st,
+                     w.T, (int64_t)fo * n_labs, n_bins, F, w.labs);
+  hipLaunchKernelGGL(k_st_group, dim3(launch_grid((int64_t)fo * F, ST_NTHR, ST_MAX_GRID, 1)), dim3(ST_NTHR), 0, st, w.labs,
+                     (int64_t)fo, n_labs, F, w.all);
   MMG_CHECK_LAUNCH("stack_solve(training sums)");
   const int64_t need_i = min_count > n_features + 2 ? min_count : n_features + 2;
   const double need = (double)need_i;
-  const dim3 grid(st_grid((int64_t)fo * n_cells, 1)), block(ST_NTHR);
+  const dim3 grid(launch_grid((int64_t)fo * n_cells, ST_NTHR, ST_MAX_GRID, 1)), block(ST_NTHR);
 #define ST_SOLVE(K_) \
   hipLaunchKernelGGL(k_st_solve<K_>, grid, block, 0, st, w.T, w.labs, w.all, n_cells, n_bins, fo, ridge, need, coef, level, n_used)
   switch (n_features) {
@@ -609,9 +566,9 @@ extern "C" int mmg_stack_apply_pairs(const float* const* feats, int n_features, 
                                      int index_bytes, int64_t n, int n_labs, const int32_t* deg, int64_t n_patients,
                                      const double* bin_edges, int n_bins, const double* coef, int folds, uint64_t seed,
                                      int cross, float* out, void* stream) {
-  StEdges ed = {};
+  CellEdges ed = {};
   StFeats ft;
-  int rc = cells_check("stack_apply_pairs", patient, lab, index_bytes, n, n_labs, deg, n_patients, bin_edges, n_bins, &ed);
+  int rc = pairs_check("stack_apply_pairs", patient, lab, index_bytes, n, n_labs, deg, n_patients, bin_edges, n_bins, &ed);
   if (rc) return rc;
   if ((rc = model_check("stack_apply_pairs", n_features, folds))) return rc;
   if ((rc = feats_check("stack_apply_pairs", feats, n_features, n > 0, &ft))) return rc;
@@ -622,11 +579,13 @@ extern "C" int mmg_stack_apply_pairs(const float* const* feats, int n_features, 
   hipStream_t st = (hipStream_t)stream;
   const uint32_t rng_key = mmg_rng_key(seed, (uint32_t)MMG_ST_SITE);
   if (index_bytes == 8)
-    hipLaunchKernelGGL(k_st_apply_pairs<int64_t>, dim3(st_grid(n)), dim3(ST_NTHR), 0, st, ft, (const int64_t*)patient,
-                       (const int64_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, coef, folds, rng_key, cross, out);
+    hipLaunchKernelGGL(k_st_apply_pairs<int64_t>, dim3(launch_grid(n, ST_NTHR, ST_MAX_GRID)), dim3(ST_NTHR), 0, st, ft,
+                       (const int64_t*)patient, (const int64_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, coef, folds,
+                       rng_key, cross, out);
   else
-    hipLaunchKernelGGL(k_st_apply_pairs<int32_t>, dim3(st_grid(n)), dim3(ST_NTHR), 0, st, ft, (const int32_t*)patient,
-                       (const int32_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, coef, folds, rng_key, cross, out);
+    hipLaunchKernelGGL(k_st_apply_pairs<int32_t>, dim3(launch_grid(n, ST_NTHR, ST_MAX_GRID)), dim3(ST_NTHR), 0, st, ft,
+                       (const int32_t*)patient, (const int32_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, coef, folds,
+                       rng_key, cross, out);
   MMG_CHECK_LAUNCH("stack_apply_pairs");
   return MMG_OK;
 }
@@ -635,10 +594,10 @@ extern "C" int mmg_stack_apply_matrix(const float* const* feats, const int64_t* 
                                       int n_labs, const void* rows, int index_bytes, const int32_t* deg, int64_t n_patients,
                                       const double* bin_edges, int n_bins, const double* coef, int folds, uint64_t seed,
                                       int cross, float* out, int64_t ld_out, void* stream) {
-  StEdges ed = {};
+  CellEdges ed = {};
   StFeats ft;
   const int some = 0;        // (a matrix has no index lists to be null)
-  int rc = cells_check("stack_apply_matrix", &some, &some, index_bytes, n_rows, n_labs, deg, n_patients, bin_edges, n_bins, &ed);
+  int rc = pairs_check("stack_apply_matrix", &some, &some, index_bytes, n_rows, n_labs, deg, n_patients, bin_edges, n_bins, &ed);
   if (rc) return rc;
   if ((rc = model_check("stack_apply_matrix", n_features, folds))) return rc;
   if ((rc = feats_check("stack_apply_matrix", feats, n_features, n_rows > 0, &ft))) return rc;
@@ -655,7 +614,7 @@ extern "C" int mmg_stack_apply_matrix(const float* const* feats, const int64_t* 
   if (n_rows == 0) return MMG_OK;
   hipStream_t st = (hipStream_t)stream;
   const uint32_t rng_key = mmg_rng_key(seed, (uint32_t)MMG_ST_SITE);
-  const dim3 grid(st_grid(n_rows * n_labs)), block(ST_NTHR);
+  const dim3 grid(launch_grid(n_rows * n_labs, ST_NTHR, ST_MAX_GRID)), block(ST_NTHR);
   if (rows && index_bytes == 4)
     hipLaunchKernelGGL(k_st_apply_matrix<int32_t>, grid, block, 0, st, ft, n_rows, n_labs, (const int32_t*)rows, deg,
                        n_patients, n_bins, ed, coef, folds, rng_key, cross, out, ld_out);
@@ -676,8 +635,8 @@ extern "C" int mmg_stack_scores(const float* raw, const float* stacked, const fl
                                 const void* lab, int index_bytes, int64_t n, int n_labs, const int32_t* deg,
                                 int64_t n_patients, const double* bin_edges, int n_bins, double* scores, int64_t* dropped,
                                 void* ws, size_t ws_bytes, void* stream) {
-  StEdges ed = {};
-  int rc = cells_check("stack_scores", patient, lab, index_bytes, n, n_labs, deg, n_patients, bin_edges, n_bins, &ed);
+  CellEdges ed = {};
+  int rc = pairs_check("stack_scores", patient, lab, index_bytes, n, n_labs, deg, n_patients, bin_edges, n_bins, &ed);
   if (rc) return rc;
   MMG_CHECK_ARG(n == 0 || (raw && stacked && target), "stack_scores: null raw, stacked or target");
   MMG_CHECK_ARG(scores && dropped, "stack_scores: null output");
@@ -695,8 +654,8 @@ extern "C" int mmg_stack_scores(const float* raw, const float* stacked, const fl
                 scores, dropped, w, st);
   if (rc) return rc;
   double* lab_rows = scores + (size_t)n_cells * F;
-  hipLaunchKernelGGL(k_st_group, dim3(st_grid((int64_t)n_labs * F, 1)), dim3(ST_NTHR), 0, st, scores, (int64_t)n_labs, n_bins,
-                     F, lab_rows);
+  hipLaunchKernelGGL(k_st_group, dim3(launch_grid((int64_t)n_labs * F, ST_NTHR, ST_MAX_GRID, 1)), dim3(ST_NTHR), 0, st,
+                     scores, (int64_t)n_labs, n_bins, F, lab_rows);
   hipLaunchKernelGGL(k_st_group, dim3(1), dim3(ST_NTHR), 0, st, lab_rows, (int64_t)1, n_labs, F, lab_rows + (size_t)n_labs * F);
   MMG_CHECK_LAUNCH("stack_scores(rows)");
   return MMG_OK;

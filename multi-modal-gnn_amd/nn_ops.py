@@ -1,92 +1,25 @@
 """ctypes binding and typed entry points of libmmgnn_nn.so (C ABI: include/mmgnn_nn.h; csrc/nn.hip): the embedding
-neighbour kernels, a library of its own beside libmmgnn.so.  The binding is derived from the header by the same parser
-as _lib's (``_lib.parse_header``) and the calls are marshalled from the prototypes as ``ops._call`` marshals them
-(``ops._plan``): a tensor handed to a scalar pointer is checked under the header's dtype and name, ws / ws_bytes / stream
-are filled in here.  The library is REQUIRED: there is no CPU or eager-PyTorch fallback behind these calls.
+neighbour kernels, a library of its own beside libmmgnn.so.  The binding is a ``_lib.Binding`` derived from the header,
+and every call goes through ``ops._call``: a tensor handed to a scalar pointer is checked under the header's dtype and
+name, ws / ws_bytes / stream are filled in there.  The library is REQUIRED: there is no CPU or eager-PyTorch fallback
+behind these calls.
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
 from typing import Optional
 
 import torch
 
-from . import _lib, ops
-from ._lib import MmgError, check
+from . import ops
+from ._lib import check
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libmmgnn_nn.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mmgnn_nn.h")
-
-
-def _read_header():
-    try:
-        with open(HEADER_PATH) as f:
-            return f.read()
-    except OSError as e:
-        raise MmgError(f"{HEADER_PATH} not found: the binding is derived from the header the library is built from "
-                       f"({e})") from None
-
-
-PARAMS = {}
-DEFINES, STRUCTS, SIGNATURES = _lib.parse_header(_read_header(), PARAMS)
-globals().update(DEFINES)
-_PLANS = {sym: ops._plan(params) for sym, params in PARAMS.items()}
+BINDING = ops.satellite("nn", globals())    # LIB_PATH, HEADER_PATH, DEFINES, SIGNATURES, PARAMS, MMG_*, load, _call
 
 NN_MAX_K = DEFINES["MMG_NN_MAX_K"]                  # csrc/nn.hip: 1 <= k <= NN_MAX_K
 NN_QUERY_BLOCK = DEFINES["MMG_NN_QUERY_BLOCK"]      # query rows of a workgroup
 NN_TILE = DEFINES["MMG_NN_TILE"]                    # candidate rows per LDS tile
 NN_MAX_GRID = DEFINES["MMG_NN_MAX_GRID"]            # workgroups of a launch: each walks work items in strides of the grid
 NN_MAX_D = DEFINES["MMG_NN_MAX_D"]                  # the widest row
-
-_nnlib = None
-
-
-def load():
-    """Load libmmgnn_nn.so (once), after libmmgnn.so, which it uses.  Raises MmgError loudly when it has not been built."""
-    global _nnlib
-    if _nnlib is not None:
-        return _nnlib
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise MmgError(f"{LIB_PATH} not found: the HIP library is mandatory (no CPU fallback). Build it with "
-                       f"`make -C {os.path.join(_HERE, 'csrc')}` or `python -c 'import __graft_entry__ as g; g.build()'`.")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)     # AttributeError here = header/library mismatch
-        fn.restype = res
-        fn.argtypes = args
-    _nnlib = lib
-    return lib
-
-
-def _call(name, *args, ws=None):
-    """ops._call for this library (ops._call looks its plans and symbols up in libmmgnn.so's tables, so it cannot be
-    handed these): `args` are the parameters of the prototype of `name` without stream, ws and ws_bytes; a torch.Tensor
-    handed to a scalar pointer parameter is converted under the header's dtype and name, tensors on different devices are
-    refused; ws: the call's uint8 workspace tensor."""
-    plan, n_given = _PLANS[name]
-    if len(args) != n_given:
-        raise TypeError(f"{name}: takes {n_given} arguments besides ws and stream, got {len(args)}")
-    if ws is not None and "ws" not in plan:
-        raise TypeError(f"{name}: takes no workspace")
-    out, dev, given = [], None, iter(args)
-    for how in plan:
-        a = (0 if how == "ws_bytes" else None) if isinstance(how, str) else next(given)
-        if how is not None and isinstance(a, torch.Tensor):
-            t, a = a, ops._p(a, how[1], how[0])
-            if dev is None:
-                dev = t.device
-            elif t.device != dev:
-                raise ValueError(f"{name}: {how[0]} is on {t.device}, the tensors before it on {dev}")
-        out.append(a)
-    for i, how in enumerate(plan):
-        if how == "stream":
-            out[i] = ops._stream()
-        elif how == "ws" and ws is not None:
-            out[i], out[i + 1] = ops._p(ws, torch.uint8, "ws"), ws.numel()
-    check(getattr(load(), name)(*out), name)
 
 
 def nn_plan(n: int, nq: Optional[int] = None):
@@ -127,7 +60,7 @@ def nn_search(x: torch.Tensor, k: int, queries: Optional[torch.Tensor] = None, d
     idx_out, ld_i = _nn_out(idx_out, nq, k, torch.int64, x.device, "idx_out")
     _call("mmg_nn_search", px, n, D, ld, pq, nq, ld_q, k, ops._p(dist_out, torch.float32, "dist_out", contiguous=False),
           ld_d, ops._p(idx_out, torch.int64, "idx_out", contiguous=False), ld_i,
-          ws=ops.workspace(max(load().mmg_nn_search_ws_bytes(n, D, nq, k), 256), x.device))
+          ws=ops._ws(load().mmg_nn_search_ws_bytes(n, D, nq, k), x.device))
     return dist_out, idx_out
 
 
@@ -149,5 +82,5 @@ def nn_rank(x: torch.Tensor, nbr: torch.Tensor, want_rank: bool = True, want_pen
     penalty = torch.empty(1, dtype=torch.int64, device=x.device) if want_penalty else None
     _call("mmg_nn_rank", px, n, D, ld, ops._p(nbr, torch.int64, "nbr", contiguous=False), ld_n, k,
           ops._p(rank, torch.int32, "rank_out", contiguous=False), ld_r, penalty,
-          ws=ops.workspace(max(load().mmg_nn_rank_ws_bytes(n, D, k), 256), x.device))
+          ws=ops._ws(load().mmg_nn_rank_ws_bytes(n, D, k), x.device))
     return rank, penalty

@@ -58,17 +58,27 @@ def _plan(params):
     return plan, sum(1 for how in plan if not isinstance(how, str))
 
 
-_PLANS = {sym: _plan(params) for sym, params in _lib.PARAMS.items()}      # decided once, from the header alone
+_BOUND = {}     # binding -> {symbol: _plan of its prototype}
 
 
-def _call(name, *args, ws=None, names=None):
-    """The one path into the library: `args` are the parameters of the prototype of `name` (include/mmgnn.h) without
-    stream, ws and ws_bytes.  A torch.Tensor handed to a scalar pointer parameter is converted under the header's dtype
-    and parameter name (names: {header's name: the name a refusal uses instead}); tensors on different devices are
-    refused; everything else -- None, numbers, ctypes values, a pointer made by _p -- passes through.  ws: a byte count
-    (the shared workspace() on the device of the first tensor argument) or the call's own uint8 tensor.  The stream is the
-    current one; the return code goes through check()."""
-    plan, n_given = _PLANS[name]
+def _plans(binding):
+    """The plans of a binding's prototypes: decided once, from its header alone."""
+    if binding not in _BOUND:
+        _BOUND[binding] = {sym: _plan(params) for sym, params in binding.params.items()}
+    return _BOUND[binding]
+
+
+_PLANS = _plans(_lib.MAIN)
+
+
+def _call(name, *args, ws=None, names=None, binding=None):
+    """The one path into every library: `args` are the parameters of the prototype of `name` (in the header of `binding`;
+    None: libmmgnn.so's, include/mmgnn.h) without stream, ws and ws_bytes.  A torch.Tensor handed to a scalar pointer
+    parameter is converted under the header's dtype and parameter name (names: {header's name: the name a refusal uses
+    instead}); tensors on different devices are refused; everything else -- None, numbers, ctypes values, a pointer made by
+    _p -- passes through.  ws: a byte count (the shared workspace() on the device of the first tensor argument) or the
+    call's own uint8 tensor.  The stream is the current one; the return code goes through check()."""
+    plan, n_given = (_PLANS if binding is None else _plans(binding))[name]
     if len(args) != n_given:
         raise TypeError(f"{name}: takes {n_given} arguments besides ws and stream, got {len(args)}")
     if ws is not None and "ws" not in plan:
@@ -92,7 +102,18 @@ def _call(name, *args, ws=None, names=None):
                     raise _lib.MmgError(f"{name}: no tensor argument names the device of the workspace")
                 ws = workspace(ws, dev)
             out[i], out[i + 1] = _p(ws, torch.uint8, "ws"), ws.numel()
-    check(getattr(_lib.load(), name)(*out), name)
+    check(getattr(binding.load() if binding else _lib.load(), name)(*out), name)
+
+
+def satellite(stem, namespace):
+    """The binding of libmmgnn_<stem>.so, made by the one line of its <stem>_ops.py that hands in its globals(): they
+    get LIB_PATH, HEADER_PATH, DEFINES, STRUCTS, SIGNATURES, PARAMS, every MMG_* define, load (the library, once, after
+    libmmgnn.so) and _call (the _call above into this library).  The header is parsed here; no library is loaded."""
+    b = _lib.Binding(stem)
+    namespace.update(b.defines, LIB_PATH=b.lib_path, HEADER_PATH=b.header_path, DEFINES=b.defines, STRUCTS=b.structs,
+                     SIGNATURES=b.signatures, PARAMS=b.params, load=b.load,
+                     _call=lambda name, *args, **kw: _call(name, *args, binding=b, **kw))
+    return b
 
 
 # ------------------------------------------------------------------------------------------
@@ -213,6 +234,26 @@ def workspace(nbytes: int, device) -> torch.Tensor:
     if capturing:
         ent[1] = True
     return ent[0]
+
+
+def _ws(nbytes: int, device):
+    """The workspace() of a satellite library's call: never under 256 bytes."""
+    return workspace(max(int(nbytes), 256), device)
+
+
+def _edges(bin_edges):
+    """Degree-bin edges -> (host array of doubles, number of bins)."""
+    e = [float(x) for x in bin_edges]
+    return (C.c_double * len(e))(*e), len(e) - 1
+
+
+def _index_pair(patient: torch.Tensor, lab: torch.Tensor, n: int, what: str):
+    """The two index tensors of the pairs as untyped pointers + their width; int64 or int32, both the same."""
+    if patient.dtype != lab.dtype or patient.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"{what}: patient and lab indices must both be int64 or both int32, got {patient.dtype} / {lab.dtype}")
+    if patient.numel() != n or lab.numel() != n:
+        raise ValueError(f"{what}: {patient.numel()} patient and {lab.numel()} lab indices for {n} pairs")
+    return _p(patient, patient.dtype, "patient"), _p(lab, lab.dtype, "lab"), patient.element_size()
 
 
 @dataclass

@@ -1,39 +1,20 @@
 """ctypes binding and typed entry points of libmmgnn_stack.so (C ABI: include/mmgnn_stack.h; csrc/stack.hip): the
 normal-equation sums, the per-cell ridge solve, the two apply epilogues and the before/after scores of the stacked
-recalibration, a library of its own beside libmmgnn.so.  The binding is derived from the header by the same parser as
-_lib's (``_lib.parse_header``) and the calls are marshalled from the prototypes as ``conformal_ops._call`` marshals
-them.  The library is REQUIRED: there is no CPU or eager-PyTorch fallback behind these calls (the numpy restatement of
-mmgnn/stacking.py serves numpy inputs and checks the kernels; it is never a silent substitute for them).
+recalibration, a library of its own beside libmmgnn.so.  The binding is a ``_lib.Binding`` derived from the header, and
+every call goes through ``ops._call``.  The library is REQUIRED: there is no CPU or eager-PyTorch fallback behind these
+calls (the numpy restatement of mmgnn/stacking.py serves numpy inputs and checks the kernels; it is never a silent
+substitute for them).
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional, Sequence
 
 import torch
 
-from . import _lib, ops
-from ._lib import MmgError, check
+from . import ops
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libmmgnn_stack.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mmgnn_stack.h")
-
-
-def _read_header():
-    try:
-        with open(HEADER_PATH) as f:
-            return f.read()
-    except OSError as e:
-        raise MmgError(f"{HEADER_PATH} not found: the binding is derived from the header the library is built from "
-                       f"({e})") from None
-
-
-PARAMS = {}
-DEFINES, STRUCTS, SIGNATURES = _lib.parse_header(_read_header(), PARAMS)
-globals().update(DEFINES)
-_PLANS = {sym: ops._plan(params) for sym, params in PARAMS.items()}
+BINDING = ops.satellite("stack", globals())    # LIB_PATH, HEADER_PATH, DEFINES, SIGNATURES, PARAMS, MMG_*, load, _call
 
 ST_SITE = DEFINES["MMG_ST_SITE"]
 ST_MAX_FEATURES = DEFINES["MMG_ST_MAX_FEATURES"]
@@ -45,70 +26,6 @@ ST_CHUNK = DEFINES["MMG_ST_CHUNK"]
 ST_DROP_KINDS = DEFINES["MMG_ST_DROP_KINDS"]      # lab out of range, patient out of range, degree in no bin, a NaN value
 ST_SCORE_FIELDS = DEFINES["MMG_ST_SCORE_FIELDS"]  # n, sum |t - raw|, sum (t - raw)^2, sum |t - stacked|, sum (t - stacked)^2
 ST_PIVOT_REL = float(f"1e{DEFINES['MMG_ST_PIVOT_REL_LOG10']}")
-
-_stlib = None
-
-
-def load():
-    """Load libmmgnn_stack.so (once), after libmmgnn.so, which it uses.  Raises MmgError loudly when it has not been
-    built."""
-    global _stlib
-    if _stlib is not None:
-        return _stlib
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise MmgError(f"{LIB_PATH} not found: the HIP library is mandatory (no CPU fallback). Build it with "
-                       f"`make -C {os.path.join(_HERE, 'csrc')}` or `python -c 'import __graft_entry__ as g; g.build()'`.")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)     # AttributeError here = header/library mismatch
-        fn.restype = res
-        fn.argtypes = args
-    _stlib = lib
-    return lib
-
-
-def _call(name, *args, ws=None):
-    """conformal_ops._call for this library: `args` are the parameters of the prototype of `name` without stream, ws and
-    ws_bytes; a torch.Tensor handed to a scalar pointer parameter is converted under the header's dtype and name, tensors
-    on different devices are refused; ws: the call's uint8 workspace tensor."""
-    plan, n_given = _PLANS[name]
-    if len(args) != n_given:
-        raise TypeError(f"{name}: takes {n_given} arguments besides ws and stream, got {len(args)}")
-    out, dev, given = [], None, iter(args)
-    for how in plan:
-        a = (0 if how == "ws_bytes" else None) if isinstance(how, str) else next(given)
-        if how is not None and isinstance(a, torch.Tensor):
-            t, a = a, ops._p(a, how[1], how[0])
-            if dev is None:
-                dev = t.device
-            elif t.device != dev:
-                raise ValueError(f"{name}: {how[0]} is on {t.device}, the tensors before it on {dev}")
-        out.append(a)
-    for i, how in enumerate(plan):
-        if how == "stream":
-            out[i] = ops._stream()
-        elif how == "ws" and ws is not None:
-            out[i], out[i + 1] = ops._p(ws, torch.uint8, "ws"), ws.numel()
-    check(getattr(load(), name)(*out), name)
-
-
-def _ws(nbytes: int, device):
-    return ops.workspace(max(int(nbytes), 256), device)
-
-
-def _edges(bin_edges):
-    e = [float(x) for x in bin_edges]
-    return (C.c_double * len(e))(*e), len(e) - 1
-
-
-def _index_pair(patient: torch.Tensor, lab: torch.Tensor, n: int, what: str):
-    """The two index tensors of the pairs as untyped pointers + their width; int64 or int32, both the same."""
-    if patient.dtype != lab.dtype or patient.dtype not in (torch.int64, torch.int32):
-        raise TypeError(f"{what}: patient and lab indices must both be int64 or both int32, got {patient.dtype} / {lab.dtype}")
-    if patient.numel() != n or lab.numel() != n:
-        raise ValueError(f"{what}: {patient.numel()} patient and {lab.numel()} lab indices for {n} pairs")
-    return ops._p(patient, patient.dtype, "patient"), ops._p(lab, lab.dtype, "lab"), patient.element_size()
 
 
 def _feature_list(feats: Sequence[torch.Tensor], what: str):
@@ -145,14 +62,14 @@ def stack_sums(feats, target: torch.Tensor, patient: torch.Tensor, lab: torch.Te
     fp, K, n, dev = _feature_list(feats, "stack_sums")
     if target.numel() != n:
         raise ValueError("stack_sums: features and target need the same length")
-    pp, pl, ib = _index_pair(patient, lab, n, "stack_sums")
-    ed, n_bins = _edges(bin_edges)
+    pp, pl, ib = ops._index_pair(patient, lab, n, "stack_sums")
+    ed, n_bins = ops._edges(bin_edges)
     n_labs, folds = int(n_labs), int(folds)
     sums = torch.empty(max(folds, 0), max(n_labs * n_bins, 0), n_fields(K), dtype=torch.float64, device=dev)
     dropped = torch.empty(ST_DROP_KINDS, dtype=torch.int64, device=dev)
     _call("mmg_stack_sums", fp, K, target, pp, pl, ib, n, n_labs, deg, int(deg.numel()), ed, n_bins, folds,
           int(seed) & 0xFFFFFFFFFFFFFFFF, sums, dropped,
-          ws=_ws(load().mmg_stack_sums_ws_bytes(n, n_labs, n_bins, K, folds), dev))
+          ws=ops._ws(load().mmg_stack_sums_ws_bytes(n, n_labs, n_bins, K, folds), dev))
     return sums, dropped
 
 
@@ -168,7 +85,7 @@ def stack_solve(sums: torch.Tensor, n_labs: int, n_bins: int, n_features: int, r
     level = torch.empty(fo, n_labs * n_bins, dtype=torch.int32, device=dev)
     n_used = torch.empty_like(level)
     _call("mmg_stack_solve", sums, n_labs, n_bins, K, folds, float(ridge), int(min_count), coef, level, n_used,
-          ws=_ws(load().mmg_stack_solve_ws_bytes(n_labs, n_bins, K, folds), dev))
+          ws=ops._ws(load().mmg_stack_solve_ws_bytes(n_labs, n_bins, K, folds), dev))
     return coef, level, n_used
 
 
@@ -184,8 +101,8 @@ def stack_apply_pairs(feats, patient: torch.Tensor, lab: torch.Tensor, n_labs: i
     """The stacked prediction fp32 [n] of the pairs (mmg_stack_apply_pairs); cross: every pair under the coefficients
     fitted without its own patient's fold."""
     fp, K, n, dev = _feature_list(feats, "stack_apply_pairs")
-    pp, pl, ib = _index_pair(patient, lab, n, "stack_apply_pairs")
-    ed, n_bins = _edges(bin_edges)
+    pp, pl, ib = ops._index_pair(patient, lab, n, "stack_apply_pairs")
+    ed, n_bins = ops._edges(bin_edges)
     folds = _check_coef(coef, int(n_labs) * n_bins, K, "stack_apply_pairs")
     out = torch.empty(n, dtype=torch.float32, device=dev)
     _call("mmg_stack_apply_pairs", fp, K, pp, pl, ib, n, int(n_labs), deg, int(deg.numel()), ed, n_bins, coef, folds,
@@ -220,7 +137,7 @@ def stack_apply_matrix(feats, rows: Optional[torch.Tensor], deg: torch.Tensor, b
             ptrs.append(pk.value or 0)
             lds.append(ldk)
     K = len(ptrs)
-    ed, n_bins = _edges(bin_edges)
+    ed, n_bins = ops._edges(bin_edges)
     folds = _check_coef(coef, n_labs * n_bins, K, "stack_apply_matrix")
     pr, ib = None, 8
     if rows is not None:
@@ -244,11 +161,11 @@ def stack_scores(raw: torch.Tensor, stacked: torch.Tensor, target: torch.Tensor,
     n, dev = int(raw.numel()), raw.device
     if stacked.numel() != n or target.numel() != n:
         raise ValueError("stack_scores: raw, stacked and target need the same length")
-    pp, pl, ib = _index_pair(patient, lab, n, "stack_scores")
-    ed, n_bins = _edges(bin_edges)
+    pp, pl, ib = ops._index_pair(patient, lab, n, "stack_scores")
+    ed, n_bins = ops._edges(bin_edges)
     n_labs = int(n_labs)
     scores = torch.empty(max(n_labs * n_bins + n_labs + 1, 1), ST_SCORE_FIELDS, dtype=torch.float64, device=dev)
     dropped = torch.empty(ST_DROP_KINDS, dtype=torch.int64, device=dev)
     _call("mmg_stack_scores", raw, stacked, target, pp, pl, ib, n, n_labs, deg, int(deg.numel()), ed, n_bins, scores,
-          dropped, ws=_ws(load().mmg_stack_scores_ws_bytes(n, n_labs, n_bins), dev))
+          dropped, ws=ops._ws(load().mmg_stack_scores_ws_bytes(n, n_labs, n_bins), dev))
     return scores, dropped
