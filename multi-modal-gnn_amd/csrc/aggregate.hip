@@ -1606,8 +1606,12 @@ extern "C" int mmg_scatter_rows(const mmg_rel_t* rels, int n_rel, int64_t n_rows
   int total_cols = 0;
   for (int r = 0; r < n_rel; ++r) total_cols += rels[r].n_cols;
   if (total_cols == 0) return MMG_OK;
-  if (n_rows == 0 || !p.ok) {
-    // empty input, or more than 512 padded vocab rows: zero + global float atomics
+  // (the bit-plane kernels take simple relations up to 24 tiles: only what neither they nor the count-tile kernel take
+  //  falls back)
+  const StripPlan sp = plan_strip(rels, n_rel, n_rows, D);
+  const UnitsPlan up = plan_units(rels, n_rel, n_rows, D);
+  if (n_rows == 0 || (!p.ok && !sp.ok && !up.ok)) {
+    // empty input, or more than 512 padded vocab rows without a bit-plane plan: zero + global float atomics
     rc = pack(rels, n_rel, &rp, false, true, false);
     if (rc) return rc;
     for (int r = 0; r < n_rel; ++r)
@@ -1627,7 +1631,6 @@ extern "C" int mmg_scatter_rows(const mmg_rel_t* rels, int n_rel, int64_t n_rows
   MMG_CHECK_WS("scatter_rows", need);
   float* slab = MmgCarver(ws).take<float>((need - 256) / sizeof(float));
   // 1. bit-plane strip kernel: simple relations, <= 10 tiles, no rowscale
-  const StripPlan sp = plan_strip(rels, n_rel, n_rows, D);
   if (sp.ok) {
     int rc2 = MMG_OK;
     RelPack rq;                                       // packed accumulator rows: acc_off = items in front of the relation
@@ -1645,7 +1648,6 @@ extern "C" int mmg_scatter_rows(const mmg_rel_t* rels, int n_rel, int64_t n_rows
     return MMG_OK;
   }
   // 2. unit-per-wave kernel: any vocabulary layout of simple relations up to 24 tiles, with or without a rowscale
-  const UnitsPlan up = plan_units(rels, n_rel, n_rows, D);
   if (up.ok) {
     bool has_rs = false;
     for (int r = 0; r < n_rel; ++r) has_rs |= rels[r].rowscale != nullptr;
