@@ -409,7 +409,8 @@ def evaluate_with_intervals(model, graph, masker, config: Dict, output_dir, spli
                             baselines: Sequence[str] = ("global_mean", "per_lab_mean"), confidence: float = 0.95,
                             seed: int = 0) -> Dict:
     """Predict the ``split`` pairs of ``masker``, fit the named baselines ("global_mean", "per_lab_mean",
-    "nearest_neighbor": mmgnn.knn.KNNLabImputer) on its train edges and bootstrap the model's metrics and every paired
+    "nearest_neighbor": mmgnn.knn.KNNLabImputer, "chained_equations": mmgnn.chained.ChainedLabImputer) on its train
+    edges and bootstrap the model's metrics and every paired
     difference ``model - baseline`` over patients.  Writes ``evaluation_intervals.json``, ``per_lab_metrics_ci.csv`` and
     ``baseline_comparison.csv`` (one row per baseline x metric x scope) into ``output_dir``; ``evaluate_model`` and its
     files are untouched."""

@@ -6,6 +6,7 @@ and files written as the reference:
   compute_per_lab_metrics     :89-141    one row per lab with >= 2 samples, sorted by MAE
   GlobalMeanBaseline / PerLabMeanBaseline / evaluate_baselines  :152-230
   evaluate_nearest_neighbor_baseline  the config's "nearest_neighbor" baseline the reference never wrote (mmgnn.knn)
+  evaluate_chained_baseline   chained-equations (MICE) imputation as a fourth baseline (mmgnn.chained)
   stratify_by_patient_degree  :237-287   1-5 / 6-15 / 16+ observed labs
   stratify_by_lab_frequency   :290-342   quartiles of the non-zero lab counts
   evaluate_model              :349-570   predict -> per-lab +-3 sigma winsorisation -> metrics -> json / csv
@@ -140,12 +141,12 @@ def evaluate_baselines(train_data, test_data) -> Dict[str, Dict[str, float]]:
     return results
 
 
-BASELINES = ("global_mean", "per_lab_mean", "nearest_neighbor")
+BASELINES = ("global_mean", "per_lab_mean", "nearest_neighbor", "chained_equations")
 
 
 def fit_baselines(baselines: Sequence[str], tr_ei, tr_v, n_labs: int, n_pat: int, n_neighbors: int = 5) -> dict:
-    """The named baselines ("global_mean", "per_lab_mean", "nearest_neighbor": mmgnn.knn.KNNLabImputer) fitted on the
-    train edges tr_ei [2, m] with values tr_v fp32 [m], all on one device -> {name: model}.  A model is
+    """The named baselines ("global_mean", "per_lab_mean", "nearest_neighbor": mmgnn.knn.KNNLabImputer,
+    "chained_equations": mmgnn.chained.ChainedLabImputer with its defaults) fitted on the train edges tr_ei [2, m] with values tr_v fp32 [m], all on one device -> {name: model}.  A model is
     ``(kind, payload)``; ``baseline_pairs`` and ``baseline_matrix`` evaluate it.  ``bootstrap.evaluate_with_intervals`` and
     the drivers of ``stacking`` share this one fit."""
     for b in baselines:
@@ -161,10 +162,13 @@ def fit_baselines(baselines: Sequence[str], tr_ei, tr_v, n_labs: int, n_pat: int
             cnt = torch.bincount(tr_ei[1], minlength=n_labs).double()
             tot = torch.zeros(n_labs, dtype=torch.float64, device=dev).index_add_(0, tr_ei[1], tr_v.double())
             fitted[b] = ("per_lab_mean", torch.where(cnt > 0, tot / cnt.clamp(min=1), g_mean.double()).float())
-        else:
+        elif b == "nearest_neighbor":
             from .knn import KNNLabImputer
             fitted[b] = ("nearest_neighbor", (KNNLabImputer(n_neighbors=n_neighbors).fit(tr_ei[0], tr_ei[1], tr_v, n_pat,
                                                                                          n_labs), g_mean))
+        else:
+            from .chained import ChainedLabImputer
+            fitted[b] = ("chained_equations", (ChainedLabImputer().fit(tr_ei[0], tr_ei[1], tr_v, n_pat, n_labs), g_mean))
     return fitted
 
 
@@ -181,8 +185,9 @@ def baseline_pairs(model, pi, li) -> torch.Tensor:
 
 
 def baseline_matrix(model, rows, n_labs: int) -> torch.Tensor:
-    """A fitted baseline's dense prediction: a vector [n_labs] to broadcast, or (nearest neighbour) [n_rows, n_labs] --
-    KNNLabImputer.impute_matrix, which passes a patient's own train-edge values through and imputes the rest."""
+    """A fitted baseline's dense prediction: a vector [n_labs] to broadcast, or (nearest neighbour, chained equations)
+    [n_rows, n_labs] -- the imputer's impute_matrix, which passes a patient's own train-edge values through and imputes
+    the rest."""
     kind, payload = model
     if kind == "global_mean":
         return payload.expand(n_labs).contiguous()
@@ -208,6 +213,21 @@ def evaluate_nearest_neighbor_baseline(graph, masker, split: str = "test", n_nei
     pred = imp.predict(ev_ei[0].to(dev), ev_ei[1].to(dev)).cpu().numpy()
     pred = np.where(np.isnan(pred), np.mean(tr_v.cpu().numpy()), pred)
     return {"nearest_neighbor": compute_regression_metrics(pred, ev_v.cpu().numpy())}
+
+
+def evaluate_chained_baseline(graph, masker, split: str = "test", **imputer_kwargs) -> Dict[str, Dict[str, float]]:
+    """The chained-equations baseline (mmgnn.chained.ChainedLabImputer(**imputer_kwargs), sklearn's IterativeImputer over
+    a ridge regression) fitted on the masker's train edges and read at the ``split`` pairs, with the result shape of
+    evaluate_nearest_neighbor_baseline.  Edges on a HIP device run the kernels, edges on the host the numpy restatement.
+    A lab without any train value falls back to the global train mean."""
+    from .chained import ChainedLabImputer
+    tr_ei, tr_v, _, _ = masker.get_masked_data("train", want_mask=False)
+    ev_ei, ev_v, _, _ = masker.get_masked_data(split, want_mask=False)
+    imp = ChainedLabImputer(**imputer_kwargs).fit(tr_ei[0], tr_ei[1], tr_v.reshape(-1), graph["patient"].num_nodes,
+                                                  graph["lab"].num_nodes)
+    pred = imp.predict(ev_ei[0], ev_ei[1]).cpu().numpy()
+    pred = np.where(np.isnan(pred), np.mean(tr_v.cpu().numpy()), pred)
+    return {"chained_equations": compute_regression_metrics(pred, ev_v.cpu().numpy())}
 
 
 def _groups(groups, predictions, targets):
