@@ -7,6 +7,7 @@ and files written as the reference:
   GlobalMeanBaseline / PerLabMeanBaseline / evaluate_baselines  :152-230
   evaluate_nearest_neighbor_baseline  the config's "nearest_neighbor" baseline the reference never wrote (mmgnn.knn)
   evaluate_chained_baseline   chained-equations (MICE) imputation as a fourth baseline (mmgnn.chained)
+  evaluate_lowrank_baseline   low-rank matrix completion (ALS) as a fifth; lowrank_sweep over rank and reg (mmgnn.lowrank)
   stratify_by_patient_degree  :237-287   1-5 / 6-15 / 16+ observed labs
   stratify_by_lab_frequency   :290-342   quartiles of the non-zero lab counts
   evaluate_model              :349-570   predict -> per-lab +-3 sigma winsorisation -> metrics -> json / csv
@@ -141,13 +142,14 @@ def evaluate_baselines(train_data, test_data) -> Dict[str, Dict[str, float]]:
     return results
 
 
-BASELINES = ("global_mean", "per_lab_mean", "nearest_neighbor", "chained_equations")
+BASELINES = ("global_mean", "per_lab_mean", "nearest_neighbor", "chained_equations", "low_rank")
 
 
 def fit_baselines(baselines: Sequence[str], tr_ei, tr_v, n_labs: int, n_pat: int, n_neighbors: int = 5) -> dict:
     """The named baselines ("global_mean", "per_lab_mean", "nearest_neighbor": mmgnn.knn.KNNLabImputer,
-    "chained_equations": mmgnn.chained.ChainedLabImputer with its defaults) fitted on the train edges tr_ei [2, m] with values tr_v fp32 [m], all on one device -> {name: model}.  A model is
-    ``(kind, payload)``; ``baseline_pairs`` and ``baseline_matrix`` evaluate it.  ``bootstrap.evaluate_with_intervals`` and
+    "chained_equations": mmgnn.chained.ChainedLabImputer, "low_rank": mmgnn.lowrank.LowRankLabImputer, each with its
+    defaults) fitted on the train edges tr_ei [2, m] with values tr_v fp32 [m], all on one device -> {name: model}.
+    A model is ``(kind, payload)``; ``baseline_pairs`` and ``baseline_matrix`` evaluate it.  ``bootstrap.evaluate_with_intervals`` and
     the drivers of ``stacking`` share this one fit."""
     for b in baselines:
         if b not in BASELINES:
@@ -166,6 +168,9 @@ def fit_baselines(baselines: Sequence[str], tr_ei, tr_v, n_labs: int, n_pat: int
             from .knn import KNNLabImputer
             fitted[b] = ("nearest_neighbor", (KNNLabImputer(n_neighbors=n_neighbors).fit(tr_ei[0], tr_ei[1], tr_v, n_pat,
                                                                                          n_labs), g_mean))
+        elif b == "low_rank":
+            from .lowrank import LowRankLabImputer
+            fitted[b] = ("low_rank", (LowRankLabImputer().fit(tr_ei[0], tr_ei[1], tr_v, n_pat, n_labs), g_mean))
         else:
             from .chained import ChainedLabImputer
             fitted[b] = ("chained_equations", (ChainedLabImputer().fit(tr_ei[0], tr_ei[1], tr_v, n_pat, n_labs), g_mean))
@@ -228,6 +233,38 @@ def evaluate_chained_baseline(graph, masker, split: str = "test", **imputer_kwar
     pred = imp.predict(ev_ei[0], ev_ei[1]).cpu().numpy()
     pred = np.where(np.isnan(pred), np.mean(tr_v.cpu().numpy()), pred)
     return {"chained_equations": compute_regression_metrics(pred, ev_v.cpu().numpy())}
+
+
+def _lowrank_on_split(graph, masker, split: str, **imputer_kwargs):
+    from .lowrank import LowRankLabImputer
+    tr_ei, tr_v, _, _ = masker.get_masked_data("train", want_mask=False)
+    ev_ei, ev_v, _, _ = masker.get_masked_data(split, want_mask=False)
+    imp = LowRankLabImputer(**imputer_kwargs).fit(tr_ei[0], tr_ei[1], tr_v.reshape(-1), graph["patient"].num_nodes,
+                                                  graph["lab"].num_nodes)
+    pred = imp.predict(ev_ei[0], ev_ei[1]).cpu().numpy()
+    pred = np.where(np.isnan(pred), np.mean(tr_v.cpu().numpy()), pred)
+    return imp, compute_regression_metrics(pred, ev_v.cpu().numpy())
+
+
+def evaluate_lowrank_baseline(graph, masker, split: str = "test", **imputer_kwargs) -> Dict[str, Dict[str, float]]:
+    """The low-rank baseline (mmgnn.lowrank.LowRankLabImputer(**imputer_kwargs): patient and lab embeddings fitted by
+    alternating least squares, the model under test without its message passing) fitted on the masker's train edges and
+    read at the ``split`` pairs, with the result shape of evaluate_chained_baseline.  Edges on a HIP device run the
+    kernels, edges on the host the numpy restatement.  A lab without any train value falls back to the global train
+    mean."""
+    return {"low_rank": _lowrank_on_split(graph, masker, split, **imputer_kwargs)[1]}
+
+
+def lowrank_sweep(graph, masker, ranks=(2, 4, 8, 16), regs=(0.3, 1.0, 3.0), split: str = "val", **imputer_kwargs):
+    """The low-rank baseline fitted on the train edges at every (rank, reg) and read at the ``split`` pairs -> a
+    DataFrame ``rank, reg, n_iter, mae, rmse, r2``, one row per setting."""
+    import pandas as pd
+    rows = []
+    for rank in ranks:
+        for reg in regs:
+            imp, m = _lowrank_on_split(graph, masker, split, rank=int(rank), reg=float(reg), **imputer_kwargs)
+            rows.append(dict(rank=int(rank), reg=float(reg), n_iter=int(imp.n_iter_), mae=m["mae"], rmse=m["rmse"], r2=m["r2"]))
+    return pd.DataFrame(rows, columns=["rank", "reg", "n_iter", "mae", "rmse", "r2"])
 
 
 def _groups(groups, predictions, targets):
