@@ -240,6 +240,30 @@ int mmg_linear_fwd_dual_supported(int64_t M, int N, int K);
 int mmg_linear_fwd_dual(const float* X, const mmg_prologue_t* pro0, const mmg_prologue_t* pro1, const float* W,
                         const float* bias, float* Y0, float* Y1, int64_t M, int N, int K, const mmg_fwd_epi_t* epi0,
                         const mmg_fwd_epi_t* epi1, void* stream);
+/* A compact second problem on the same W and bias that RIDES in a dense MMG_EPI_L2 launch: the third linear + L2 norm of
+ * the two encode_nodes passes of a training step (src/model.py:294,301,103,232).  The first pass only feeds tabular_mlp, so
+ * its tail runs on the n_sel low-degree rows alone -- two launches of a few microseconds of work each, alone on the chip.
+ * mmg_linear_fwd_rider is, in this order,
+ *   mmg_linear_fwd(X, pro, W, bias, Y, M, N, K, 0, epi)                                          the dense launch
+ *   mmg_affine_act_drop_rows(X_a, pro_a, rows, n_sel, act_a, K)                                  masks of the ORIGINAL rows
+ *   mmg_linear_fwd(act_a, NULL, W_a, bias_a, Y_a, n_sel, N, K, 0, epi_a)
+ * in ONE launch, every output bit for bit: the dense launch keeps its grid, its tile-to-workgroup map and its code, and
+ * every workgroup goes on over the rider's 32-row tiles in the same round-robin behind its last dense tile.  X_a [M, K] is
+ * the tensor the listed rows are read from, pro_a its prologue (all four activations), act_a [n_sel, K] the prologue'd rows
+ * (the weight gradient reads them), Y_a [n_sel, N] and epi_a->rnorm [n_sel] the normalised rows and their reciprocal norms.
+ * mmg_linear_fwd_rider_supported: M > 512, N = K = 128, and n_sel = 0 (the dense launch alone) or 512 < n_sel <= M (the
+ * lists the third call above takes with the L2 epilogue; a shorter list goes to the fp32 kernel of the small tables and an
+ * L2 pass, which the caller keeps launching).  Refused with MMG_E_ARG before anything is launched: an unsupported shape, an
+ * epilogue other than MMG_EPI_L2 or two different eps, a dense prologue that is absent or the identity, W_a / bias_a other
+ * than W / bias, a null buffer, a rider output (act_a, Y_a, rnorm) that overlaps another tensor of the call.  rows: ids in
+ * [0, M) (not checked: they are on the device).
+ * Probe row: the dense launch's own (MMG_PROBE_LINEAR_FWD, M, N, K, 4 | 32) with the flag 32768; the rider's rows are
+ * left out of the pricing. */
+int mmg_linear_fwd_rider_supported(int64_t M, int N, int K, int64_t n_sel);
+int mmg_linear_fwd_rider(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias, float* Y, int64_t M,
+                         int N, int K, const mmg_fwd_epi_t* epi, const float* X_a, const mmg_prologue_t* pro_a,
+                         const int64_t* rows, int64_t n_sel, const float* W_a, const float* bias_a, float* act_a, float* Y_a,
+                         const mmg_fwd_epi_t* epi_a, void* stream);
 int mmg_gather_rows(const mmg_rel_t* rels, int n_rel, int64_t n_rows, int D, float* out, int accumulate,
                     const mmg_fwd_epi_t* epi, void* stream);
 
@@ -387,6 +411,28 @@ int mmg_linear_bnbwd_supported(int mode, int64_t M, int N, int K, int with_wgrad
 size_t mmg_linear_bnbwd_wgrad_ws_bytes(int64_t M, int N, int K);
 int mmg_linear_bnbwd(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
                      const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, void* stream);
+/* The backward counterpart of mmg_linear_fwd_rider: the L2 backward + data gradient of the third linear of BOTH
+ * encode_nodes passes in one launch.  mmg_linear_bnbwd_rider is, in this order,
+ *   mmg_linear_bnbwd(b, W, dZ, dX, M, N, K, next, NULL)                                        b->mode == MMG_BNBWD_L2
+ *   mmg_linear_bnbwd(a, W_a, dZ_a, dX_a, n_sel, N, K, NULL, NULL)                              a->mode == MMG_BNBWD_L2
+ *   mmg_bn_bwd_stats_rows(dX_a, next_a->y, rows, n_sel, next_a->pro, next_a->mean, next_a->rstd, next_a->sums, N,
+ *                         next_a->ws, next_a->ws_bytes)                                        (next_a != NULL)
+ * every output bit for bit: the dense launch keeps its grid, tile-to-workgroup map, code and partial statistics (the rider's
+ * tiles take no part in the next-BatchNorm epilogue) and every workgroup goes on over the rider's 32-row tiles behind its
+ * last dense tile; the statistics pass over the listed rows follows, and ONE launch sums the partial rows of `next` and of
+ * the listed rows, each in the order of its own launch.  next_a (nullable) describes the BatchNorm backward that consumes
+ * dX_a AT THE LISTED ROWS: y [M, N] the pre-BatchNorm activation those rows belong to, accumulate = 0, ws of at least
+ * mmg_bn_bwd_stats_rows_ws_bytes(N) bytes that does not overlap next->ws (both hold partial rows until they are summed).
+ * mmg_linear_bnbwd_rider_supported: M > 512, N = K = 128, n_sel = 0 (the dense call alone) or 512 < n_sel <= M (what the
+ * second call above accepts).  Refused with MMG_E_ARG before anything is launched: an unsupported shape, a mode other than
+ * MMG_BNBWD_L2, W_a other than W, different eps, a null buffer, a rider output (dZ_a, dX_a) that overlaps another tensor of
+ * the two problems, overlapping workspaces, and whatever mmg_linear_bnbwd refuses.
+ * Probe row: the dense launch's own (MMG_PROBE_LINEAR_FWD, M, N, K, 64 [| 512]) with the flag 32768; the rider's rows are
+ * left out of the pricing. */
+int mmg_linear_bnbwd_rider_supported(int64_t M, int N, int K, int64_t n_sel);
+int mmg_linear_bnbwd_rider(const mmg_bnbwd_t* b, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
+                           const mmg_next_bn_t* next, const mmg_bnbwd_t* a, const float* W_a, float* dZ_a, float* dX_a,
+                           int64_t n_sel, const int64_t* rows, const mmg_next_bn_t* next_a, void* stream);
 /* mmg_linear_bnbwd(a, W, dZ, dX, M, N, K, NULL, wg, stream) with a MASKED dX store: the dropout that the consumer of dX --
  * the backward of the BatchNorm + activation + dropout in front of this linear, whose prologue is wg->pro -- would apply
  * first is applied by the producer, and a second producer adds its share:
@@ -453,7 +499,8 @@ int mmg_linear_dgrad_wgrad(const float* dY, const float* W, float* dX, int64_t M
  *   2 M N K FLOP more), 8192 = the masked dX store of mmg_linear_bnbwd_masked (beside the mode's own bits; an accumulating
  *   launch reads dX once more than its row prices), 16384 = the dual backward of mmg_linear_bnbwd_dual (beside 16 | 128 | 1024 |
  *   8192: four [M, 128] inputs -- G and y of pass b, y of pass a, X -- and one output price the launch, the listed rows of
- *   pass a's G and the row list left out).
+ *   pass a's G and the row list left out), 32768 = a compact second problem rides in the launch (mmg_linear_fwd_rider,
+ *   mmg_linear_bnbwd_rider: beside the dense launch's own bits; the rider's rows are left out of the pricing).
  * The hook is the library's only process-wide mutable state (mutex-guarded); the product path never arms it. */
 #define MMG_PROBE_LINEAR_FWD 1
 #define MMG_PROBE_LINEAR_WGRAD 2

@@ -340,6 +340,14 @@ __device__ __forceinline__ void next_bn_tile(const NextBnDev& nb, const NextBnCo
 // out[i] (= add[i] +) the sum over n_rows partial rows [n_rows][n], fixed order (add nullable, may alias out)
 extern "C" int mmg_partial_sum(const double* partial, double* out, int n, int n_rows, void* stream);
 extern "C" int mmg_partial_sum_add(const double* partial, double* out, int n, int n_rows, const double* add, void* stream);
+// two such sums in ONE launch (the job index is blockIdx.y): each job summed in the order its own launch gives it
+struct MmgPartialJob { const double* partial; double* out; int n, n_rows; const double* add; };
+extern "C" int mmg_partial_sum_jobs(const MmgPartialJob* a, const MmgPartialJob* b, void* stream);
+// mmg_bn_bwd_stats_rows up to its partial rows: *job receives the sum that finishes it (job->partial == NULL: nothing is
+// left to sum -- an empty list, whose sums are zeroed here)
+extern "C" int mmg_bn_bwd_stats_rows_partial(const float* G_rows, const float* Y, const int64_t* rows, int64_t n_sel,
+                                             const mmg_prologue_t* pro, const float* mean, const float* rstd, double* sums, int N,
+                                             void* ws, size_t ws_bytes, void* stream, MmgPartialJob* job);
 // partial [n_rows][2][N] -> col_sums, + the BatchNorm fold of the sums (fin != NULL)
 extern "C" int mmg_partial_sum_bn(const double* partial, double* col_sums, int N, int n_rows, const mmg_bn_fin_t* fin,
                                   void* stream);

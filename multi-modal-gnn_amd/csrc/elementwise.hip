@@ -123,8 +123,8 @@ __global__ __launch_bounds__(NT) void k_col_reduce(const float* __restrict__ A, 
 }
 
 // one wave per output element: lanes stride over the block partials, then a fixed-order wave reduction
-__global__ __launch_bounds__(256) void k_partial_sum(const double* __restrict__ partial, double* __restrict__ out, int n,
-                                                     int nblk, const double* add = nullptr) {
+__device__ __forceinline__ void partial_sum_element(const double* __restrict__ partial, double* __restrict__ out, int n,
+                                                    int nblk, const double* add) {
   const int lane = threadIdx.x & 63;
   const int i = (blockIdx.x * 256 + threadIdx.x) >> 6;
   if (i >= n) return;
@@ -132,6 +132,15 @@ __global__ __launch_bounds__(256) void k_partial_sum(const double* __restrict__ 
   for (int b = lane; b < nblk; b += 64) s += partial[(size_t)b * n + i];
   s = wave_sum_d(s);
   if (lane == 0) out[i] = add ? add[i] + s : s;     // (add may alias out: one reader-writer per element)
+}
+__global__ __launch_bounds__(256) void k_partial_sum(const double* __restrict__ partial, double* __restrict__ out, int n,
+                                                     int nblk, const double* add = nullptr) {
+  partial_sum_element(partial, out, n, nblk, add);
+}
+// two independent sums in one launch: job = blockIdx.y, each element summed exactly as k_partial_sum sums it
+__global__ __launch_bounds__(256) void k_partial_sum_jobs(MmgPartialJob a, MmgPartialJob b) {
+  const MmgPartialJob& j = blockIdx.y ? b : a;
+  partial_sum_element(j.partial, j.out, j.n, j.n_rows, j.add);
 }
 
 // one column of the BatchNorm fold (shared by k_bn_finalize and k_partial_sum_bn: the same arithmetic, bit for bit)
@@ -696,9 +705,29 @@ extern "C" int mmg_bn_bwd_stats2(const float* G, const float* G2, const float* Y
 
 extern "C" size_t mmg_bn_bwd_stats_rows_ws_bytes(int N) { return (size_t)BSR_MAX_BLOCKS * 2 * (size_t)(N > 0 ? N : 0) * 8 + 256; }
 
+extern "C" int mmg_partial_sum_jobs(const MmgPartialJob* a, const MmgPartialJob* b, void* stream) {
+  const int n = a->n > b->n ? a->n : b->n;
+  hipLaunchKernelGGL(k_partial_sum_jobs, dim3((n + 3) / 4, 2), dim3(256), 0, (hipStream_t)stream, *a, *b);
+  MMG_CHECK_LAUNCH("partial_sum_jobs");
+  return MMG_OK;
+}
+
 extern "C" int mmg_bn_bwd_stats_rows(const float* G_rows, const float* Y, const int64_t* rows, int64_t n_sel,
                                      const mmg_prologue_t* pro, const float* mean, const float* rstd, double* sums, int N,
                                      void* ws, size_t ws_bytes, void* stream) {
+  MmgPartialJob job;
+  const int rc = mmg_bn_bwd_stats_rows_partial(G_rows, Y, rows, n_sel, pro, mean, rstd, sums, N, ws, ws_bytes, stream, &job);
+  if (rc || !job.partial) return rc;
+  hipLaunchKernelGGL(k_partial_sum, dim3((2 * N + 3) / 4), dim3(256), 0, (hipStream_t)stream, job.partial, job.out, job.n,
+                     job.n_rows);
+  MMG_CHECK_LAUNCH("bn_bwd_stats_rows");
+  return MMG_OK;
+}
+
+extern "C" int mmg_bn_bwd_stats_rows_partial(const float* G_rows, const float* Y, const int64_t* rows, int64_t n_sel,
+                                             const mmg_prologue_t* pro, const float* mean, const float* rstd, double* sums, int N,
+                                             void* ws, size_t ws_bytes, void* stream, MmgPartialJob* job) {
+  *job = MmgPartialJob{nullptr, sums, 2 * N, 0, nullptr};
   MMG_CHECK_ARG(n_sel >= 0 && sums && mean && rstd, "bn_bwd_stats_rows: bad args");
   MMG_CHECK_ARG(N > 0 && N % 4 == 0 && N <= 256 && 256 % (N / 4) == 0, "bn_bwd_stats_rows: N=%d unsupported", N);
   hipStream_t st = (hipStream_t)stream;
@@ -711,8 +740,8 @@ extern "C" int mmg_bn_bwd_stats_rows(const float* G_rows, const float* Y, const 
   if (nblk > BSR_MAX_BLOCKS) nblk = BSR_MAX_BLOCKS;
   hipLaunchKernelGGL(k_bn_bwd_stats_rows, dim3((unsigned)nblk), dim3(256), 0, st, G_rows, Y, rows, n_sel, mmg_pro_dev(pro),
                      mean, rstd, partial, N);
-  hipLaunchKernelGGL(k_partial_sum, dim3((2 * N + 3) / 4), dim3(256), 0, st, partial, sums, 2 * N, (int)nblk);
   MMG_CHECK_LAUNCH("bn_bwd_stats_rows");
+  job->partial = partial; job->n_rows = (int)nblk;
   return MMG_OK;
 }
 

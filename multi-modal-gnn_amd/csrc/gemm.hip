@@ -72,12 +72,26 @@ __device__ __forceinline__ void next_bn_load(const NextBnDev& nb, int64_t tile, 
 // holds whole rows (N == 32 * WN), so Y receives  y / max(|y|, eps)  and rn_out[row] = 1 / max(|y|, eps); the separate
 // pass read and wrote the [M, N] tensor once more.
 // NBN: stat_partial receives the statistics of the NEXT BatchNorm backward (nb, see NextBnDev) instead of the forward ones.
-template <int K, int WN, bool PRO, bool ACC, bool L2 = false, bool NBN = false>   // WN waves along N (32 columns each) over a 32-row tile: 64 * WN threads
+// RIDER (L2 instances): a second, compact problem on the SAME W and bias rides in the launch -- the listed rows of another
+// tensor under their own prologue (the first encode_nodes pass of a training step, which only feeds the tabular head: its
+// third linear runs on the low-degree rows alone, mmg_linear_fwd_rider).  A workgroup walks its dense tiles t0, t0 + G, ...
+// exactly as without the rider (same grid, same tile map, same code) and then goes on in the same round-robin over the
+// rider's ceil(n_sel / 32) tiles: tile j of the rider is tile n_tiles + j of the walk.  A rider tile gathers its rows
+// through the int64 list, applies mmg_pro_apply4 with the masks of the ORIGINAL rows (what k_affine_act_drop_rows does,
+// and stores: act), splits, multiplies in the k-step order of the PRO = false instance and runs the same L2 epilogue into
+// the compact outputs: act, Y and rn are bit for bit those of mmg_affine_act_drop_rows + the compact L2 launch.
+struct FwdRiderDev {
+  const float* X; ProDev pr; const int64_t* rows; int64_t n_sel; float* act; float* Y; float* rn;
+};
+static inline FwdRiderDev fwd_rider_none() { return FwdRiderDev{nullptr, mmg_pro_dev(nullptr), nullptr, 0, nullptr, nullptr, nullptr}; }
+
+template <int K, int WN, bool PRO, bool ACC, bool L2 = false, bool NBN = false, bool RIDER = false>   // WN waves along N (32 columns each) over a 32-row tile: 64 * WN threads
 __global__ __launch_bounds__(64 * WN, (WN == 4 && K <= 128) ? 2 : 1) void k_linear_fwd_x6(
     const float* __restrict__ X, ProDev pr, const float* __restrict__ W, const float* __restrict__ bias,
     float* __restrict__ Y, int64_t M, int N, int flags, double* __restrict__ stat_partial, float* __restrict__ rn_out,
-    float l2_eps, NextBnDev nb) {
+    float l2_eps, NextBnDev nb, FwdRiderDev rd) {
   static_assert(!(NBN && L2), "one epilogue at a time");
+  static_assert(!RIDER || (L2 && !ACC), "the rider comes with the L2 instances");
   __shared__ float l2_part[L2 ? WN * 32 : 1], l2_rn[L2 ? 32 : 1];
   if (PRO) pr.resolve();
   double cs1 = 0.0, cs2 = 0.0;          // column statistics of the output (BatchNorm batch stats) ride along: lane = column
@@ -184,6 +198,47 @@ __global__ __launch_bounds__(64 * WN, (WN == 4 && K <= 128) ? 2 : 1) void k_line
   __syncthreads();
   const int yvo = ((4 * h) * N + wn * 32 + l31) * 4;     // C/D map: col = lane&31, row = (i&3) + 8*(i>>2) + 4*(lane>>5)
   const int c0 = bx * BN;
+  // (L2) the epilogue of one tile: acc -> Y rows through ys, 1 / max(norm, eps) of its rows -> rn_dst[r0 .. r0 + rows)
+  auto l2_epilogue = [&](const f32x16& acc, const __amdgpu_buffer_rsrc_t ys, int rows, float* rn_dst, int64_t r0) __attribute__((always_inline)) {
+    // row sums of squares: 32 lanes of a half-wave hold the 32 columns of this wave for 16 rows each; the WN waves'
+    // partials meet in LDS, 32 threads turn them into 1 / max(norm, eps), every lane scales its 16 values
+    float vv[16], ss[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { vv[i] = acc[i] + bv; ss[i] = vv[i] * vv[i]; }
+    // 32-lane sums on the vector ALU's data-parallel primitives (five v_add_f32 with a DPP operand per value; the
+    // first version went through 80 ds_bpermute round trips per tile): xor 1, xor 2 inside a quad, mirror inside 8,
+    // mirror inside 16, then the row total of lanes 0..15 broadcast onto lanes 16..31 -- those hold the half's sum
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      float v = ss[i];
+      v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
+      v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
+      v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));  // row_half_mirror
+      v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));  // row_mirror
+      v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, false)); // row_bcast:15 -> rows 1, 3
+      ss[i] = v;
+    }
+    if (l31 == 31) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) l2_part[wn * 32 + (i & 3) + 8 * (i >> 2) + 4 * h] = ss[i];
+    }
+    __syncthreads();                       // partials complete; also: buf fully read, buf^1 fully written
+    if (tid < 32) {
+      float tot = l2_part[tid];
+#pragma unroll
+      for (int w = 1; w < WN; ++w) tot += l2_part[w * 32 + tid];
+      const float rinv = 1.0f / fmaxf(sqrtf(tot), l2_eps);
+      l2_rn[tid] = rinv;
+      if (tid < rows) rn_dst[r0 + tid] = rinv;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int r = mmg_c_row(i);
+      const float v = vv[i] * l2_rn[r + 4 * h];
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ys, yvo, r * N * 4, MMG_NT_ST);
+    }
+  };
   auto tile_body = [&](int64_t tt, int buf, f32x4* nx) {
     // nx holds tile tt+G (fetched two tiles ago); after staging it, the registers take tile tt+3G
     const int rows = rows_of(tt);
@@ -247,44 +302,7 @@ __global__ __launch_bounds__(64 * WN, (WN == 4 && K <= 128) ? 2 : 1) void k_line
     }
     if constexpr (WEAVE) fetch(tt + 3 * G, nx);  // (its registers are free only now: two tiles stay in flight all the same)
     if constexpr (L2) {
-      // row sums of squares: 32 lanes of a half-wave hold the 32 columns of this wave for 16 rows each; the WN waves'
-      // partials meet in LDS, 32 threads turn them into 1 / max(norm, eps), every lane scales its 16 values
-      float vv[16], ss[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { vv[i] = acc[i] + bv; ss[i] = vv[i] * vv[i]; }
-      // 32-lane sums on the vector ALU's data-parallel primitives (five v_add_f32 with a DPP operand per value; the
-      // first version went through 80 ds_bpermute round trips per tile): xor 1, xor 2 inside a quad, mirror inside 8,
-      // mirror inside 16, then the row total of lanes 0..15 broadcast onto lanes 16..31 -- those hold the half's sum
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        float v = ss[i];
-        v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-        v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-        v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));  // row_half_mirror
-        v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));  // row_mirror
-        v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, false)); // row_bcast:15 -> rows 1, 3
-        ss[i] = v;
-      }
-      if (l31 == 31) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) l2_part[wn * 32 + (i & 3) + 8 * (i >> 2) + 4 * h] = ss[i];
-      }
-      __syncthreads();                       // partials complete; also: buf fully read, buf^1 fully written
-      if (tid < 32) {
-        float tot = l2_part[tid];
-#pragma unroll
-        for (int w = 1; w < WN; ++w) tot += l2_part[w * 32 + tid];
-        const float rinv = 1.0f / fmaxf(sqrtf(tot), l2_eps);
-        l2_rn[tid] = rinv;
-        if (tid < rows) rn_out[tt * BM + tid] = rinv;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int r = mmg_c_row(i);
-        const float v = vv[i] * l2_rn[r + 4 * h];
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ys, yvo, r * N * 4, MMG_NT_ST);
-      }
+      l2_epilogue(acc, ys, rows, rn_out, tt * BM);
       return;
     }
     if constexpr (NBN) {
@@ -317,6 +335,52 @@ __global__ __launch_bounds__(64 * WN, (WN == 4 && K <= 128) ? 2 : 1) void k_line
   for (int i = 2; i < n_my; i += 2) {
     tile_body(t0 + (int64_t)i * G, 0, nxa);
     tile_body(t0 + (int64_t)(i + 1) * G, 1, nxb);
+  }
+  if constexpr (RIDER) {
+    // the rider's tiles, dealt on in the same round-robin: tile j is tile n_tiles + j of the walk.  Every wave is past the
+    // barriers of its last dense tile: the planes are free (what the last staging passes left there is never read).
+    rd.pr.resolve();
+    f32x4 rsc = {1.f, 1.f, 1.f, 1.f}, rsh = {0.f, 0.f, 0.f, 0.f};
+    if (rd.pr.scale) {
+      rsc = *reinterpret_cast<const f32x4*>(rd.pr.scale + kc4 * 4);
+      rsh = *reinterpret_cast<const f32x4*>(rd.pr.shift + kc4 * 4);
+    }
+    const int64_t nt_r = (rd.n_sel + BM - 1) / BM;
+    for (int64_t j = t0 + (int64_t)n_my * G - n_tiles; j < nt_r; j += G) {
+      const int64_t s0 = j * BM;
+      const int rows = rd.n_sel - s0 < BM ? (int)(rd.n_sel - s0) : BM;
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        const int r = p * ROWS_PER_PASS + prow;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};            // rows past the end of the list: what the compact launch reads there
+        if (r < rows) {
+          const int64_t row = rd.rows[s0 + r];
+          v = *reinterpret_cast<const f32x4*>(rd.X + (size_t)row * K + kc4 * 4);
+          mmg_pro_apply4(rd.pr, v, rsc, rsh, row, kc4 * 4, K);
+          *reinterpret_cast<f32x4*>(rd.act + (size_t)(s0 + r) * K + kc4 * 4) = v;
+        }
+        bf16x4 q0, q1, q2;
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) MMG_SPLIT3(v[jj], q0[jj], q1[jj], q2[jj]);
+        *reinterpret_cast<bf16x4*>(planes + (0 * BM + r) * LDP + kc4 * 4) = q0;
+        *reinterpret_cast<bf16x4*>(planes + (1 * BM + r) * LDP + kc4 * 4) = q1;
+        *reinterpret_cast<bf16x4*>(planes + (2 * BM + r) * LDP + kc4 * 4) = q2;
+      }
+      __syncthreads();
+      f32x16 acc;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+      const __bf16* ap = planes + l31 * LDP + 8 * h;
+#pragma unroll
+      for (int ks = 0; ks < NK; ++ks) {
+        const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(ap + ks * 16);
+        const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(ap + BM * LDP + ks * 16);
+        const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(ap + 2 * BM * LDP + ks * 16);
+        MMG_X6_ALO(acc, a1, a2, a3, wb[ks][0], wb[ks][1], wb[ks][2]);
+      }
+      // (the first barrier of the epilogue: the planes are read; its second: the next tile may be staged)
+      l2_epilogue(acc, mmg_rsrc(rd.Y + (size_t)s0 * N + c0, (rows * N - c0) * 4), rows, rd.rn, s0);
+    }
   }
   if (stat_partial) {
     // two partials per column (the lane halves) -> one: partial[row-set][2][N], fixed order
@@ -646,7 +710,19 @@ int launch_fwd_x6_v(const float* X, const ProDev& pr, const float* W, const floa
   MMG_CHECK_HIP((MmgMaxLds<&k_linear_fwd_x6<K, WN, PRO, ACC, L2, NBN>, lds>::set()), "linear_fwd(attr)");
   MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, N, K, (flags & MMG_LIN_ACCUMULATE) | (PRO ? 4 : 0) | (L2 ? 32 : 0) | (NBN ? 512 : 0),
              (k_linear_fwd_x6<K, WN, PRO, ACC, L2, NBN>), dim3((unsigned)n_slices, (unsigned)gy), dim3(64 * WN), lds, st, X,
-             pr, W, bias, Y, M, N, flags, stat_partial, rn_out, l2_eps, nb);
+             pr, W, bias, Y, M, N, flags, stat_partial, rn_out, l2_eps, nb, fwd_rider_none());
+  return 0;
+}
+
+// the L2 launch of a [M, 128] x [128, 128] layer with a rider (mmg_linear_fwd_rider): the dense launch's grid and LDS
+int launch_fwd_x6_rider(const float* X, const ProDev& pr, const float* W, const float* bias, float* Y, int64_t M,
+                        hipStream_t st, float* rn_out, float l2_eps, const FwdRiderDev& rd) {
+  constexpr int K = 128, N = 128;
+  const int64_t gy = fwd_x6_rows(M, N, 128, K);
+  constexpr int lds = 2 * 3 * 32 * (K + 8) * 2;
+  MMG_CHECK_HIP((MmgMaxLds<&k_linear_fwd_x6<128, 4, true, false, true, false, true>, lds>::set()), "linear_fwd_rider(attr)");
+  MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, N, K, 4 | 32 | 32768, (k_linear_fwd_x6<128, 4, true, false, true, false, true>),
+             dim3(1u, (unsigned)gy), dim3(256), lds, st, X, pr, W, bias, Y, M, N, 0, nullptr, rn_out, l2_eps, next_bn_none(), rd);
   return 0;
 }
 
@@ -933,12 +1009,21 @@ struct BnDualDev {
 };
 static inline BnDualDev bn_dual_none() { return BnDualDev{nullptr, BnBwdDev{}, mmg_pro_dev(nullptr), bn_wg_none()}; }
 template <int V> struct PassMode { static constexpr int value = V; };      // a pass's MODE as a compile-time lambda argument
+// RIDER (MODE 1 without FW): a second, compact problem of the same mode on the SAME W rides in the launch -- the L2 backward
+// of the first encode_nodes pass of a training step, which reaches the low-degree rows alone (mmg_linear_bnbwd_rider).  A
+// workgroup walks its dense tiles exactly as without the rider (same grid, same tile map, same code, same partial
+// statistics) and then goes on in the same round-robin over the ceil(n_sel / 32) tiles of (rd.G, rd.bb) -> (rd.bb.dZ, rd.DX):
+// the kernel's own fetch and stage on the rider's tensors, the same products in the same order, a plain store.  The rider's
+// tiles take no part in the next-BatchNorm epilogue.
+struct BnRiderDev { const float* G; BnBwdDev bb; float* DX; int64_t n_sel; };
+static inline BnRiderDev bn_rider_none() { return BnRiderDev{nullptr, BnBwdDev{}, nullptr, 0}; }
 
-template <int K, int WN, int MODE = 0, bool NBN = false, bool FW = false, int MSK = 0>
+template <int K, int WN, int MODE = 0, bool NBN = false, bool FW = false, int MSK = 0, bool RIDER = false>
 __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) void k_linear_bnbwd_x6(
     const float* __restrict__ G, BnBwdDev bb, ProDev pr, const float* __restrict__ W, float* __restrict__ DX, int64_t M,
-    ProDev pr2, NextBnDev nb, double* __restrict__ stat_partial, BnWgDev wg, BnDualDev du) {
+    ProDev pr2, NextBnDev nb, double* __restrict__ stat_partial, BnWgDev wg, BnDualDev du, BnRiderDev rd) {
   static_assert(!FW || (K == 128 && WN == 4), "the fused weight gradient covers K = N = 128");
+  static_assert(!RIDER || (MODE == 1 && !FW && MSK == 0), "the rider comes with the plain L2 backward");
   static_assert(MSK == 0 || (FW && !NBN && (MODE == 0 || MODE == 3)), "the masked dX store rides on the X stagers' hashes");
   static_assert(MSK != 3 || MODE == 0, "the dual form: pass B is MODE 0, pass A MODE 3");
   constexpr bool DUAL = MSK == 3;
@@ -1496,6 +1581,37 @@ __global__ __launch_bounds__(64 * WN * (FW ? 2 : 1), (WN == 4 && !FW) ? 2 : 1) v
         tile_body(t0 + (int64_t)(i + 1) * GY, 1, PassMode<MODE>{});
       }
     }
+    if constexpr (RIDER) {
+      // the rider's tiles, dealt on in the same round-robin: tile j is tile n_tiles + j of the walk.  Every wave is past the
+      // barrier of its last dense tile, so the planes are free; from here on G, bb, DX and M are the rider's (fetch, stage
+      // and rows_of read them by reference), one tile at a time through LDS buffer 0.
+      const int64_t j0 = t0 + (int64_t)n_my * GY - n_tiles, nt_r = (rd.n_sel + BM - 1) / BM;
+      G = rd.G; bb = rd.bb; DX = rd.DX; M = rd.n_sel;
+      for (int64_t j = j0; j < nt_r; j += GY) {
+        fetch(j, PassMode<MODE>{});
+        stage(j, 0, PassMode<MODE>{});
+        __syncthreads();
+        const int rows = rows_of(j);
+        const __amdgpu_buffer_rsrc_t xs = mmg_rsrc(DX + (size_t)j * BM * N, rows * N * 4);
+        f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        const __bf16* ap = planes + l31 * LDP + 8 * h;
+#pragma unroll
+        for (int ks = 0; ks < NK; ++ks) {
+          const bf16x8 a1f = *reinterpret_cast<const bf16x8*>(ap + ks * 16);
+          const bf16x8 a2f = *reinterpret_cast<const bf16x8*>(ap + BM * LDP + ks * 16);
+          const bf16x8 a3f = *reinterpret_cast<const bf16x8*>(ap + 2 * BM * LDP + ks * 16);
+          MMG_X6_ALO(acc, a1f, a2f, a3f, wb[ks][0], wb[ks][1], wb[ks][2]);
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const float v = acc[i];
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), xs, yvo, mmg_c_row(i) * N * 4, MMG_NT_ST);
+        }
+        __syncthreads();                         // buffer 0 fully read: the next tile may be staged
+      }
+    }
     if constexpr (NBN) {
       // two partials per column (the lane halves) -> one: partial[row-set][2][N], fixed order
       double* red = reinterpret_cast<double*>(planes);          // the planes are dead: every wave passed the last barrier
@@ -1546,7 +1662,22 @@ int launch_bnbwd_x6(const float* G, const BnBwdDev& bb, const ProDev& pr, const 
   MMG_CHECK_HIP((MmgMaxLds<&k_linear_bnbwd_x6<K, WN, MODE, NBN>, lds>::set()), "linear_bnbwd(attr)");
   MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, N, K, (MODE == 1 ? 64 : (MODE == 2 ? 16 | 128 : (MODE == 3 ? 16 | 256 : 16))) | (NBN ? 512 : 0),
              (k_linear_bnbwd_x6<K, WN, MODE, NBN>), dim3(1u, (unsigned)gy),
-             dim3(64 * WN), lds, st, G, bb, pr, W, DX, M, pr2, nb, stat_partial, bn_wg_none(), bn_dual_none());
+             dim3(64 * WN), lds, st, G, bb, pr, W, DX, M, pr2, nb, stat_partial, bn_wg_none(), bn_dual_none(), bn_rider_none());
+  return 0;
+}
+
+// the L2 backward of a [M, 128] x [128, 128] layer with a rider (mmg_linear_bnbwd_rider): the dense launch's grid, LDS and
+// probe row + the flag 32768
+template <bool NBN>
+int launch_bnbwd_x6_rider(const float* G, const BnBwdDev& bb, const float* W, float* DX, int64_t M, hipStream_t st,
+                          const NextBnDev& nb, double* stat_partial, const BnRiderDev& rd) {
+  constexpr int K = 128, N = 128;
+  const int64_t gy = bnbwd_x6_rows(M, K);
+  constexpr int lds = 2 * 3 * 32 * (K + 8) * 2;
+  MMG_CHECK_HIP((MmgMaxLds<&k_linear_bnbwd_x6<128, 4, 1, NBN, false, 0, true>, lds>::set()), "linear_bnbwd_rider(attr)");
+  MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, N, K, 64 | (NBN ? 512 : 0) | 32768, (k_linear_bnbwd_x6<128, 4, 1, NBN, false, 0, true>),
+             dim3(1u, (unsigned)gy), dim3(256), lds, st, G, bb, mmg_pro_dev(nullptr), W, DX, M, mmg_pro_dev(nullptr), nb,
+             stat_partial, bn_wg_none(), bn_dual_none(), rd);
   return 0;
 }
 
@@ -2035,7 +2166,7 @@ int launch_bnbwd_fw(const float* G, const BnBwdDev& bb, const ProDev& pr, const 
   MMG_CHECK_HIP((MmgMaxLds<&k_linear_bnbwd_x6<K, 4, MODE, false, true>, lds>::set()), "linear_bnbwd_wgrad(attr)");
   MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, N, K, (MODE == 1 ? 64 : (MODE == 2 ? 16 | 128 : (MODE == 3 ? 16 | 256 : 16))) | 1024,
              (k_linear_bnbwd_x6<K, 4, MODE, false, true>), dim3(1u, (unsigned)gy), dim3(512), lds, st, G, bb, pr, W, DX, M,
-             pr2, next_bn_none(), nullptr, wg, bn_dual_none());
+             pr2, next_bn_none(), nullptr, wg, bn_dual_none(), bn_rider_none());
   return 0;
 }
 
@@ -2050,7 +2181,7 @@ int launch_bnbwd_fw_masked(const float* G, const BnBwdDev& bb, const ProDev& pr,
   MMG_CHECK_HIP((MmgMaxLds<&k_linear_bnbwd_x6<K, 4, MODE, false, true, MSK>, lds>::set()), "linear_bnbwd_masked(attr)");
   MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, N, K, (MODE == 3 ? 16 | 256 : 16) | 1024 | 8192,
              (k_linear_bnbwd_x6<K, 4, MODE, false, true, MSK>), dim3(1u, (unsigned)gy), dim3(512), lds, st, G, bb, pr, W, DX, M,
-             mmg_pro_dev(nullptr), next_bn_none(), nullptr, wg, bn_dual_none());
+             mmg_pro_dev(nullptr), next_bn_none(), nullptr, wg, bn_dual_none(), bn_rider_none());
   return 0;
 }
 
@@ -2066,7 +2197,7 @@ int launch_bnbwd_fw_dual(const float* Gb, const BnBwdDev& bbb, const ProDev& prb
   MMG_CHECK_HIP((MmgMaxLds<&k_linear_bnbwd_x6<K, 4, 0, false, true, 3>, lds>::set()), "linear_bnbwd_dual(attr)");
   MMG_LAUNCH(MMG_PROBE_LINEAR_FWD, M, N, K, 16 | 128 | 1024 | 8192 | 16384, (k_linear_bnbwd_x6<K, 4, 0, false, true, 3>),
              dim3(1u, (unsigned)gy), dim3(512), lds, st, Gb, bbb, prb, W, DX, M, mmg_pro_dev(nullptr), next_bn_none(), nullptr,
-             wgb, BnDualDev{Ga, bba, pra, wga});
+             wgb, BnDualDev{Ga, bba, pra, wga}, bn_rider_none());
   return 0;
 }
 
@@ -2518,6 +2649,60 @@ extern "C" int mmg_linear_fwd_dual(const float* X, const mmg_prologue_t* pro0, c
                              epi1->fin, stream);
 }
 
+extern "C" int mmg_linear_fwd_rider_supported(int64_t M, int N, int K, int64_t n_sel) {
+  // the dense launch: the L2 instance of the 128 x 128 layer; the rider: nothing, or a list the library's own compact
+  // launch would hand to that same instance (up to 512 rows it takes the fp32 kernel of the small tables, whose sums the
+  // matrix-core arithmetic does not reproduce)
+  if (!(M > 512 && N == 128 && K == 128)) return 0;
+  return (n_sel == 0 || (n_sel > 512 && n_sel <= M)) ? 1 : 0;
+}
+
+extern "C" int mmg_linear_fwd_rider(const float* X, const mmg_prologue_t* pro, const float* W, const float* bias, float* Y,
+                                    int64_t M, int N, int K, const mmg_fwd_epi_t* epi, const float* X_a,
+                                    const mmg_prologue_t* pro_a, const int64_t* rows, int64_t n_sel, const float* W_a,
+                                    const float* bias_a, float* act_a, float* Y_a, const mmg_fwd_epi_t* epi_a, void* stream) {
+  const char* what = "linear_fwd_rider";
+  MMG_CHECK_ARG(mmg_linear_fwd_rider_supported(M, N, K, n_sel),
+                "%s: M=%lld N=%d K=%d n_sel=%lld unsupported (M > 512, N = K = 128, n_sel = 0 or 512 < n_sel <= M)", what,
+                (long long)M, N, K, (long long)n_sel);
+  MMG_CHECK_ARG(epi && epi->mode == MMG_EPI_L2 && epi->rnorm, "%s: the dense launch takes the L2 epilogue", what);
+  MMG_CHECK_ARG(X && W && Y, "%s: null buffer", what);
+  MMG_CHECK_ARG(pro && (pro->scale || pro->relu || pro->drop_p > 0.f), "%s: the dense launch needs a prologue", what);
+  MMG_CHECK_ARG(!pro->scale || pro->shift, "%s: prologue scale without shift", what);
+  MMG_CHECK_ARG(pro->relu == MMG_ACT_NONE || pro->relu == MMG_ACT_RELU, "%s: the prologue takes relu only", what);
+  if (n_sel == 0) return mmg_linear_fwd(X, pro, W, bias, Y, M, N, K, 0, epi, stream);
+  MMG_CHECK_ARG(W_a == W && bias_a == bias, "%s: the rider runs on the dense launch's W and bias", what);
+  MMG_CHECK_ARG(epi_a && epi_a->mode == MMG_EPI_L2 && epi_a->rnorm && epi_a->eps == epi->eps,
+                "%s: the rider takes the L2 epilogue with the dense launch's eps", what);
+  MMG_CHECK_ARG(X_a && rows && act_a && Y_a, "%s: null rider buffer", what);
+  MMG_CHECK_ARG(!pro_a || !pro_a->scale || pro_a->shift, "%s: rider prologue scale without shift", what);
+  {
+    // the rider's outputs against the dense launch's outputs and everything either of them reads
+    struct Span { const void* p; size_t n; };
+    const size_t mk = (size_t)M * K * 4, sk = (size_t)n_sel * K * 4;
+    const Span outs[3] = {{act_a, sk}, {Y_a, (size_t)n_sel * N * 4}, {epi_a->rnorm, (size_t)n_sel * 4}};
+    const Span others[6] = {{X, mk}, {Y, (size_t)M * N * 4}, {epi->rnorm, (size_t)M * 4}, {X_a, mk},
+                            {rows, (size_t)n_sel * 8}, {W, (size_t)N * K * 4}};
+    auto overlap = [](const Span& a, const Span& b) {
+      const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+      return a0 < b0 + b.n && b0 < a0 + a.n;
+    };
+    bool alias = false;
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 6; ++j) alias = alias || overlap(outs[i], others[j]);
+      for (int j = i + 1; j < 3; ++j) alias = alias || overlap(outs[i], outs[j]);
+    }
+    MMG_CHECK_ARG(!alias, "%s: a rider output aliases a tensor of the launch", what);
+  }
+  FwdRiderDev rd;
+  rd.X = X_a; rd.pr = mmg_pro_dev(pro_a); rd.rows = rows; rd.n_sel = n_sel;
+  rd.act = act_a; rd.Y = Y_a; rd.rn = epi_a->rnorm;
+  const int rc = launch_fwd_x6_rider(X, mmg_pro_dev(pro), W, bias, Y, M, (hipStream_t)stream, epi->rnorm, epi->eps, rd);
+  if (rc) return rc;
+  MMG_CHECK_LAUNCH(what);
+  return MMG_OK;
+}
+
 extern "C" int mmg_linear_bnbwd_supported(int mode, int64_t M, int N, int K, int with_wgrad) {
   if (mode < MMG_BNBWD_BN || mode > MMG_BNBWD_ROWS || M <= 512) return 0;
   // BN and L2 have instances for K, N in {64, 128}; BN2, ROWS and the FW form only K = N = 128
@@ -2689,6 +2874,98 @@ static int linear_bnbwd_impl(const mmg_bnbwd_t* a, const float* W, float* dZ, fl
 extern "C" int mmg_linear_bnbwd(const mmg_bnbwd_t* a, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
                                 const mmg_next_bn_t* next, const mmg_bnbwd_wgrad_t* wg, void* stream) {
   return linear_bnbwd_impl(a, W, dZ, dX, M, N, K, next, wg, 0, stream);
+}
+
+extern "C" int mmg_linear_bnbwd_rider_supported(int64_t M, int N, int K, int64_t n_sel) {
+  // the dense launch: the L2 backward of the 128 x 128 layer; the rider: nothing, or a list the library's own compact call
+  // hands to that same kernel (mmg_linear_bnbwd_supported: more than 512 rows)
+  if (!(M > 512 && N == 128 && K == 128)) return 0;
+  return (n_sel == 0 || (n_sel > 512 && n_sel <= M)) ? 1 : 0;
+}
+
+extern "C" int mmg_linear_bnbwd_rider(const mmg_bnbwd_t* b, const float* W, float* dZ, float* dX, int64_t M, int N, int K,
+                                      const mmg_next_bn_t* next, const mmg_bnbwd_t* a, const float* W_a, float* dZ_a,
+                                      float* dX_a, int64_t n_sel, const int64_t* rows, const mmg_next_bn_t* next_a,
+                                      void* stream) {
+  const char* what = "linear_bnbwd_rider";
+  MMG_CHECK_ARG(b, "%s: null descriptor", what);
+  MMG_CHECK_ARG(mmg_linear_bnbwd_rider_supported(M, N, K, n_sel),
+                "%s: M=%lld N=%d K=%d n_sel=%lld unsupported (M > 512, N = K = 128, n_sel = 0 or 512 < n_sel <= M)", what,
+                (long long)M, N, K, (long long)n_sel);
+  MMG_CHECK_ARG(b->mode == MMG_BNBWD_L2 && (n_sel == 0 || (a && a->mode == MMG_BNBWD_L2)),
+                "%s: both problems are MMG_BNBWD_L2", what);
+  const bool stats = next_a != nullptr;
+  if (stats)
+    MMG_CHECK_ARG(next_a->sums && next_a->mean && next_a->rstd && !next_a->accumulate,
+                  "%s: statistics of the listed rows: null field, or accumulate", what);
+  hipStream_t st = (hipStream_t)stream;
+  if (n_sel == 0) {             // the dense call alone (+ the statistics of an empty list: zeros)
+    const int rc = mmg_linear_bnbwd(b, W, dZ, dX, M, N, K, next, nullptr, stream);
+    if (rc || !stats) return rc;
+    return mmg_bn_bwd_stats_rows(nullptr, nullptr, nullptr, 0, next_a->pro, next_a->mean, next_a->rstd, next_a->sums, N,
+                                 next_a->ws, next_a->ws_bytes, stream);
+  }
+  MMG_CHECK_ARG(W_a == W, "%s: the rider runs on the dense launch's W", what);
+  MMG_CHECK_ARG(dZ && dZ_a && dX_a, "%s: null buffer", what);
+  MMG_CHECK_ARG(b->eps == a->eps, "%s: the two L2 normalisations have different eps", what);
+  BnBwdCall cb, ca;
+  int rc = bnbwd_marshal(b, W, dZ, dX, M, N, K, next, nullptr, &cb);
+  if (rc) return rc;
+  rc = bnbwd_marshal(a, W, dZ_a, dX_a, n_sel, N, K, nullptr, nullptr, &ca);
+  if (rc) return rc;
+  if (stats)
+    MMG_CHECK_ARG(next_a->y && rows && next_a->ws && next_a->ws_bytes >= mmg_bn_bwd_stats_rows_ws_bytes(N),
+                  "%s: statistics of the listed rows: null buffer or workspace too small", what);
+  if (stats && next && next->ws) {
+    // both sets of partial rows stay in their workspaces until the one launch that sums them
+    const uintptr_t a0 = (uintptr_t)next_a->ws, a1 = a0 + next_a->ws_bytes, b0 = (uintptr_t)next->ws, b1 = b0 + next->ws_bytes;
+    MMG_CHECK_ARG(a1 <= b0 || b1 <= a0, "%s: the statistics of the listed rows share the next BatchNorm's workspace", what);
+  }
+  {
+    // the rider's outputs against the dense launch's outputs and everything either problem reads
+    struct Span { const void* p; size_t n; };
+    const size_t mk = (size_t)M * K * 4, sk = (size_t)n_sel * K * 4;
+    const Span outs[2] = {{dZ_a, sk}, {dX_a, (size_t)n_sel * N * 4}};
+    const Span others[9] = {{b->G, mk}, {b->y, mk}, {b->rnorm, (size_t)M * 4}, {dZ, mk}, {dX, (size_t)M * N * 4},
+                            {a->G, sk}, {a->y, sk}, {a->rnorm, (size_t)n_sel * 4}, {W, (size_t)N * K * 4}};
+    auto overlap = [](const Span& x, const Span& c) {
+      const uintptr_t x0 = (uintptr_t)x.p, c0 = (uintptr_t)c.p;
+      return x0 < c0 + c.n && c0 < x0 + x.n;
+    };
+    bool alias = overlap(outs[0], outs[1]);
+    for (int i = 0; i < 2; ++i)
+      for (int j = 0; j < 9; ++j) alias = alias || overlap(outs[i], others[j]);
+    MMG_CHECK_ARG(!alias, "%s: a rider output aliases a tensor of the launch", what);
+  }
+  const BnRiderDev rd{ca.G, ca.bb, dX_a, n_sel};
+  // the dense launch as bnbwd_run picks it: the NBN instance where the next BatchNorm's statistics fit its epilogue
+  const bool nbn = next && mmg_next_bn_fusable(next);
+  NextBnDev nb = next_bn_none();
+  double* partial = nullptr;
+  if (nbn) {
+    rc = mmg_next_bn_dev(next, M, N, what, &nb, &partial);
+    if (rc) return rc;
+    rc = launch_bnbwd_x6_rider<true>(cb.G, cb.bb, W, dX, M, st, nb, partial, rd);
+  } else {
+    rc = launch_bnbwd_x6_rider<false>(cb.G, cb.bb, W, dX, M, st, nb, nullptr, rd);
+  }
+  if (rc) return rc;
+  MMG_CHECK_LAUNCH(what);
+  // behind it: the statistics of the listed rows up to their partial rows, then ONE launch sums both passes' partial rows
+  MmgPartialJob ja{nullptr, nullptr, 0, 0, nullptr};
+  if (stats) {
+    rc = mmg_bn_bwd_stats_rows_partial(dX_a, next_a->y, rows, n_sel, next_a->pro, next_a->mean, next_a->rstd,
+                                       next_a->sums, N, next_a->ws, next_a->ws_bytes, stream, &ja);
+    if (rc) return rc;
+  }
+  if (nbn && ja.partial) {
+    const MmgPartialJob jb{partial, next->sums, 2 * N, (int)bnbwd_x6_rows(M, K), next->accumulate ? next->sums : nullptr};
+    return mmg_partial_sum_jobs(&jb, &ja, stream);
+  }
+  if (nbn) rc = mmg_next_bn_finish(next, partial, N, (int)bnbwd_x6_rows(M, K), st);
+  else if (next) rc = mmg_next_bn_fallback(dX, M, N, next, what, st);
+  if (rc || !ja.partial) return rc;
+  return mmg_partial_sum(ja.partial, ja.out, ja.n, ja.n_rows, stream);
 }
 
 extern "C" int mmg_linear_bnbwd_masked_supported(int mode, int64_t M, int N, int K, int with_wgrad) {

@@ -161,6 +161,21 @@ def set_dual_enc_bwd(on: bool):
     DUAL_ENC_BWD = bool(on)
 
 
+# The compact tail of pass A -- the first encode_nodes pass of a training step only feeds the tabular head, so its third linear
+# and L2 norm run on the low-degree rows alone: two launches of a few microseconds of work, alone on the chip -- rides in
+# pass B's dense launch of the same layer (ops.FwdRider, mmg_linear_fwd_rider): pass A's tail parks, pass B's launch serves
+# both.  The backward does the same with the L2 backward of the two passes (ops.BwdRider, mmg_linear_bnbwd_rider), which also
+# sums both passes' BatchNorm-backward statistics in one launch.  Every output is bit for bit that of the separate launches.
+# set_enc_tail_rider(False) restores them.
+ENC_TAIL_RIDER = True
+
+
+def set_enc_tail_rider(on: bool):
+    """True (default) | False -- see ENC_TAIL_RIDER (the tests switch it)."""
+    global ENC_TAIL_RIDER
+    ENC_TAIL_RIDER = bool(on)
+
+
 def _mangle(et: EdgeType) -> str:
     return "<" + "___".join(et) + ">"
 
@@ -600,6 +615,7 @@ class _Run:
         self.fused_wgrad = FUSED_WGRAD
         self.masked_handdown = MASKED_HANDDOWN
         self.dual_enc_bwd = DUAL_ENC_BWD
+        self.enc_tail_rider = ENC_TAIL_RIDER
         self.overlap = mode == "on" or (mode == "auto" and self.plan.n_rows >= 16384)
         if self.overlap:
             if getattr(model, "_side_stream", None) is None:
@@ -757,8 +773,12 @@ class _Run:
                 self.allreduce(both)
                 m0.stats, m1.stats, m0.reduced, m1.reduced = both[0], both[1], True, True
             lists = self.pairs.lists                 # the first pass feeds the tabular head only: low-degree rows
-            enc0 = self.enc_fwd(0, 1, first, rows=lists.low_rows, row_pos=lists.low_pos, mid=m0)
-            enc1 = self.enc_fwd(1, 1, first, mid=m1)
+            # (one launch for both tails where enc_tail_rider_applies: pass A's parks, pass B's launches)
+            rider = ops.FwdRider() if self.enc_tail_rider_applies(first[1].shape[0], lists.low_rows) else None
+            enc0 = self.enc_fwd(0, 1, first, rows=lists.low_rows, row_pos=lists.low_pos, mid=m0, rider=rider)
+            enc1 = self.enc_fwd(1, 1, first, mid=m1, rider=rider)
+            if rider is not None:
+                rider.require_consumed()
         else:
             enc0 = enc1 = self.enc_fwd(0, 2)
         init = self.enc_dict(enc0)
@@ -808,8 +828,13 @@ class _Run:
                     tot = gp if gi is None else gp.index_add_(0, gi[0], gi[1])
                 self.enc_bwd(enc0, tot)
             else:
-                a1 = self.enc_bwd_a(enc1, g.get(ROW_TYPE))
-                a0 = self.enc_bwd_a(enc0, gi if enc0.rows is not None else dense(gi))
+                # (one launch for both L2 backwards where enc_tail_bwd_rider_applies: pass A's parks, pass B's launches)
+                brider = ops.BwdRider() if self.enc_tail_bwd_rider_applies(enc1, g.get(ROW_TYPE), enc0, gi) else None
+                parked = self.enc_bwd_a_park(enc0, gi, brider, enc1.z2.shape[0]) if brider is not None else None
+                a1 = self.enc_bwd_a(enc1, g.get(ROW_TYPE), rider=brider)
+                if brider is not None:
+                    brider.require_consumed()
+                a0 = self.enc_bwd_a(enc0, gi if enc0.rows is not None else dense(gi), parked=parked)
                 if self.comm is not None:        # sharded: the BatchNorm statistics of both passes in ONE all-reduce
                     live = [a for a in (a1, a0) if a is not None]
                     if len(live) == 2:
@@ -936,11 +961,22 @@ class _Run:
         r0, r1 = ops.linear_fwd_dual(z1, w, pt[4].bias.detach(), pros[0], pros[1], bn0=spec, bn1=spec)
         return _EncMid(pros[0], r0[0], r0[-1]), _EncMid(pros[1], r1[0], r1[-1])
 
-    def enc_fwd(self, call, n_updates, first=None, rows=None, row_pos=None, mid: Optional[_EncMid] = None) -> _EncPass:
+    def enc_tail_rider_applies(self, n_rows: int, rows) -> bool:
+        """Whether pass A's compact tail rides in pass B's dense launch (ENC_TAIL_RIDER): the switch, training mode with
+        dropout (the two passes exist and the dense launch has a prologue), a row list, and the shape the library takes."""
+        if not self.enc_tail_rider or not self.T or not self.p > 0 or rows is None:
+            return False
+        N, K = self.m.patient_transform[8].weight.shape
+        return ops.linear_fwd_rider_supported(n_rows, N, K, rows.numel())
+
+    def enc_fwd(self, call, n_updates, first=None, rows=None, row_pos=None, mid: Optional[_EncMid] = None,
+                rider: Optional[ops.FwdRider] = None) -> _EncPass:
         """rows (int64 ids; row_pos = every row's position among them or -1): everything after the last BatchNorm -- third
         linear, L2 norm -- is evaluated for these rows only and x0 / rn are compact [len(rows), .] (the first encode_nodes
         pass of a training step only feeds the tabular head, which only sees the low-degree patients; its BatchNorm
-        statistics still need every row)."""
+        statistics still need every row).
+        rider: the holder of a step whose compact tail rides in the dense launch (enc_tail_rider_applies): the pass with
+        rows parks on it and launches nothing, the dense pass launches both."""
         pt = self.m.patient_transform
         if first is None:
             first = self.enc_first(n_updates)
@@ -951,9 +987,13 @@ class _Run:
         f2 = self.bn_fold(z2, pt[5], n_updates, sharded=True, sums=mid.stats, reduced=mid.reduced)
         pro2 = Pro(f2.scale, f2.shift, True, self.p, self.seed, 2 * call + 1, self.plan.row_offset, self.seed_dev)
         act = None
-        if rows is not None:
+        if rows is not None and rider is not None:
+            act, x0, rn = rider.park_rows(z2, pro2, rows, pt[8].weight.detach(), pt[8].bias.detach())
+        elif rows is not None:
             act = ops.affine_act_drop_rows(z2, pro2, rows)       # the dropout masks of the ORIGINAL rows
             x0, rn = ops.linear_l2norm_fwd(act, pt[8].weight.detach(), pt[8].bias.detach())
+        elif rider is not None:
+            x0, rn = ops.linear_l2norm_fwd_rider(z2, pt[8].weight.detach(), pt[8].bias.detach(), pro2, rider)
         else:
             x0, rn = ops.linear_l2norm_fwd(z2, pt[8].weight.detach(), pt[8].bias.detach(), pro=pro2)   # third linear + L2 norm
         return _EncPass(E, z1, z2, x0, rn, f1, f2, mid.pro1, pro2, rows, act, row_pos)
@@ -1026,7 +1066,8 @@ class _Run:
         return ops.FusedWgrad(x, pro, defer=self.wgrad_jobs, keep_dz=keep_dz, **self.wgrad_target(wname, bname))
 
     def bn_lin_bwd(self, form, args, bn_prefix: Optional[str], x, pro: Optional[Pro], wname, bname, W,
-                   next_bn: Optional[_NextStats] = None, keep_dz=False, masked: Optional[ops.MaskedDx] = None):
+                   next_bn: Optional[_NextStats] = None, keep_dz=False, masked: Optional[ops.MaskedDx] = None,
+                   rider: Optional[ops.BwdRider] = None):
         """Backward of  x' = dropout(relu(BN(y))),  y = pro(x) W^T + b  as ONE kernel (mmg_linear_bnbwd): the BatchNorm
         backward dz, the data gradient dx = dz @ W, the BatchNorm's bias / weight gradients (bn_prefix; None: no BatchNorm)
         and the linear's weight / bias gradients (wname / bname, per-shard partial sums; a tuple of names: parameters that
@@ -1039,7 +1080,9 @@ class _Run:
         next_bn: holder of the statistics of the BatchNorm backward that consumes dx (that BatchNorm's prologue is `pro`):
         taken in the kernel's epilogue, or (holder.ride False) by the separate pass right behind it.
         masked ("plain" / "rows", no next_bn): dx is stored under a dropout mask (ops.MaskedDx); the caller has made sure
-        that the fused launch applies (masked_handdown_applies)."""
+        that the fused launch applies (masked_handdown_applies).
+        rider ("l2"): the other pass's compact L2 backward is parked on this holder and rides in the launch; the caller has
+        made sure that no fused weight gradient applies (enc_tail_bwd_rider_applies)."""
         K, N = W.shape
         if form == "l2":
             (g, y, rn), fold, sums = args, None, None
@@ -1055,6 +1098,8 @@ class _Run:
             sums = self.bn_bwd_sums(g, y, ypro, fold, more[0])
         if masked is not None and (fw is None or nb is not None or form not in ("plain", "rows")):
             raise RuntimeError(f"bn_lin_bwd: no masked dx store for form {form!r} here")
+        if rider is not None and (fw is not None or form != "l2"):
+            raise RuntimeError(f"bn_lin_bwd: no rider for form {form!r} here")
         mk = dict(masked=masked) if masked is not None else {}
         bn = self.bn_param_grads(fold, bn_prefix, sums, K)
         if form == "plain":
@@ -1064,7 +1109,7 @@ class _Run:
         elif form == "two":
             out = ops.linear_bnbwd2(g, more[0], y, ypro, more[1], fold, W, *bn, wgrad=fw)
         else:
-            out = ops.linear_l2bwd(g, y, rn, W, next_bn=nb, wgrad=fw)
+            out = ops.linear_l2bwd(g, y, rn, W, next_bn=nb, wgrad=fw, rider=rider)
         if next_bn is not None:
             next_bn.took(out[2] if nb is not None else ops.bn_bwd_stats(out[1], next_bn.y, pro, next_bn.fold))
         if fw is not None:
@@ -1075,12 +1120,40 @@ class _Run:
             self.lin_bwd(out[0], x, pro, wname, bname, need_dx=False, partial=True)
         return out[0], out[1]
 
-    def enc_bwd_a(self, enc: _EncPass, g_x0):
+    def enc_tail_bwd_rider_applies(self, enc_b: _EncPass, g_b, enc_a: _EncPass, g_a) -> bool:
+        """Whether pass A's compact L2 backward rides in pass B's dense one (ENC_TAIL_RIDER): the switch, training, both
+        gradients live, pass B dense and pass A on listed rows, a dense launch without the fused weight gradient (the
+        next-BatchNorm site "enc2" rides there, or the fused form is off or does not take the shape), and the shape the
+        library takes."""
+        if not self.enc_tail_rider or not self.T or g_b is None or g_a is None:
+            return False
+        if enc_b.rows is not None or enc_a.rows is None or enc_a.act is None:
+            return False
+        K, N = self.W("patient_transform.8.weight").shape
+        M = enc_b.z2.shape[0]
+        if "enc2" not in self.next_bn_sites and self.fused_wgrad and enc_b.z2.is_contiguous() and \
+                ops.linear_bnbwd_wgrad_supported(M, N, K):
+            return False
+        return ops.linear_bnbwd_rider_supported(M, N, K, enc_a.rows.numel())
+
+    def enc_bwd_a_park(self, enc: _EncPass, g_x0, rider: ops.BwdRider, n_rows: int):
+        """The compact branch of enc_bwd_a up to its launches, parked on `rider` -> (dz3, g, sums) for enc_bwd_a(parked=)."""
+        rows, g_rows = g_x0
+        return rider.park(g_rows.contiguous(), enc.x0, enc.rn, self.W("patient_transform.8.weight"), n_rows,
+                          stats=(enc.z2, rows, enc.pro2, enc.f2))
+
+    def enc_bwd_a(self, enc: _EncPass, g_x0, rider: Optional[ops.BwdRider] = None, parked=None):
         """Backward of one encoder pass down to the statistics of its last BatchNorm (local sums, not yet all-reduced):
-        -> (upstream gradient of that BatchNorm [dense, or the listed rows], fp64 sums) or None."""
+        -> (upstream gradient of that BatchNorm [dense, or the listed rows], fp64 sums) or None.
+        rider (the dense pass): the holder pass A's L2 backward is parked on -- this pass's launch serves both;
+        parked (the pass with rows): what enc_bwd_a_park returned, filled by that launch."""
         if g_x0 is None:
             return None
         pt = "patient_transform"
+        if enc.rows is not None and parked is not None:
+            dz3, g, sums = parked
+            self.lin_bwd(dz3, enc.act, None, f"{pt}.8.weight", f"{pt}.8.bias", need_dx=False, partial=True)
+            return g, sums
         if enc.rows is not None:             # compact tail: g_x0 = (row ids, gradient rows)
             rows, g_rows = g_x0
             # L2-norm backward inside the data-gradient GEMM of the third linear; the weight gradient reads dz3 afterwards
@@ -1091,7 +1164,7 @@ class _Run:
         # gradient where that site is on; the third linear's weight gradient rides in the launch where it can (no dz3 then)
         nstats = _NextStats(enc.z2, enc.f2, ride="enc2" in self.next_bn_sites)
         _, g = self.bn_lin_bwd("l2", (g_x0.contiguous(), enc.x0, enc.rn), None, enc.z2, enc.pro2, f"{pt}.8.weight",
-                               f"{pt}.8.bias", self.W(f"{pt}.8.weight"), next_bn=nstats)
+                               f"{pt}.8.bias", self.W(f"{pt}.8.weight"), next_bn=nstats, rider=rider)
         return g, nstats.sums
 
     def masked_handdown_applies(self, enc_b: _EncPass, state_b, enc_a: _EncPass, state_a) -> bool:

@@ -184,7 +184,7 @@ PROBE_NAME_LEN = _lib.MMG_PROBE_NAME_LEN
 
 
 def probe_read(cap: int = 1 << 16):
-    """-> list of (ms, family name, M, N, K, flags, kernel symbol) of the probed launches (flags: 1 accumulate, 4 prologue, 8 rowscale, 16 BatchNorm backward staged in the GEMM, 32 L2-norm epilogue, 64 L2-norm backward staged, 128 two upstream gradients, 256 row-list upstream gradient, 2048 the dual linear forward: N = both outputs, 4096 the weight gradient rides along the data gradient: linear_dgrad_wgrad, 8192 the masked dx store, 16384 the dual backward: linear_bnbwd_dual)."""
+    """-> list of (ms, family name, M, N, K, flags, kernel symbol) of the probed launches (flags: 1 accumulate, 4 prologue, 8 rowscale, 16 BatchNorm backward staged in the GEMM, 32 L2-norm epilogue, 64 L2-norm backward staged, 128 two upstream gradients, 256 row-list upstream gradient, 2048 the dual linear forward: N = both outputs, 4096 the weight gradient rides along the data gradient: linear_dgrad_wgrad, 8192 the masked dx store, 16384 the dual backward: linear_bnbwd_dual, 32768 a compact second problem rides in the launch: linear_l2norm_fwd_rider / linear_l2bwd with a rider)."""
     import numpy as np
     ms = np.zeros(cap, np.float32); tag = np.zeros(cap, np.int32); M = np.zeros(cap, np.int64)
     N = np.zeros(cap, np.int32); K = np.zeros(cap, np.int32); fl = np.zeros(cap, np.int32)
@@ -820,6 +820,64 @@ def linear_l2norm_fwd(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Ten
     return _linear_fwd(x, W, bias, pro, None, False, False, l2=True)
 
 
+def linear_fwd_rider_supported(M: int, N: int, K: int, n_sel: int) -> bool:
+    return bool(_lib.load().mmg_linear_fwd_rider_supported(int(M), int(N), int(K), int(n_sel)))
+
+
+@dataclass
+class FwdRider:
+    """Pairs the compact tail of one pass -- affine_act_drop_rows(y, pro, rows) + linear_l2norm_fwd(act, W, bias) -- with the
+    dense linear_l2norm_fwd(x, W, bias, pro=...) of the other pass into ONE launch (mmg_linear_fwd_rider): hand the same
+    holder to park_rows and then to linear_l2norm_fwd_rider.  park_rows validates, allocates act / x0 / rn and parks its
+    descriptor here WITHOUT launching; the dense call launches both and fills them.  Nothing falls back: a second park on a
+    holder that still holds a descriptor, a dense call on an empty holder or with another W or bias raises."""
+    parked: Optional[tuple] = None
+
+    def park_rows(self, y: torch.Tensor, pro: Pro, rows: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor]):
+        """-> (act, x0, rn) of the listed rows, filled by the dense call that takes this holder."""
+        if self.parked is not None:
+            raise RuntimeError("FwdRider: the holder already holds a parked tail")
+        M, K = y.shape
+        N, n = W.shape[0], rows.numel()
+        if W.shape[1] != K or not linear_fwd_rider_supported(M, N, K, n):
+            raise ValueError(f"FwdRider: no rider for y {tuple(y.shape)}, W {tuple(W.shape)}, {n} rows")
+        act = torch.empty(n, K, dtype=torch.float32, device=y.device)
+        x0 = torch.empty(n, N, dtype=torch.float32, device=y.device)
+        rn = torch.empty(n, dtype=torch.float32, device=y.device)
+        self.parked = (y, pro, rows, W, bias, act, x0, rn)
+        return act, x0, rn
+
+    def require_consumed(self):
+        if self.parked is not None:
+            raise RuntimeError("FwdRider: the parked tail was never launched (no dense call followed it)")
+
+
+def linear_l2norm_fwd_rider(x: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], pro: Pro, rider: FwdRider):
+    """linear_l2norm_fwd(x, W, bias, pro) -> (normalised rows, rn), and in the same launch the tail `rider` parked: its
+    act, x0 and rn are bit for bit those of affine_act_drop_rows + linear_l2norm_fwd on the listed rows."""
+    if rider.parked is None:
+        raise RuntimeError("linear_l2norm_fwd_rider: nothing is parked on the holder")
+    y, rpro, rows, rW, rbias, act, x0, rn_a = rider.parked
+    same_bias = (bias is None and rbias is None) or (bias is not None and rbias is not None and
+                                                     bias.data_ptr() == rbias.data_ptr())
+    if W.data_ptr() != rW.data_ptr() or W.shape != rW.shape or not same_bias:
+        raise RuntimeError("linear_l2norm_fwd_rider: the parked tail belongs to another W or bias")
+    M, K = x.shape
+    N = W.shape[0]
+    if tuple(y.shape) != (M, K):
+        raise ValueError("linear_l2norm_fwd_rider: the parked tail reads a tensor of another shape")
+    out = torch.empty(M, N, dtype=torch.float32, device=x.device)
+    rn = torch.empty(M, device=x.device)
+    epi = FwdEpiT(EPI_L2, rnorm=_p(rn), eps=L2_EPS)
+    epi_a = FwdEpiT(EPI_L2, rnorm=_p(rn_a), eps=L2_EPS)
+    _tok = _pb("linear_fwd")
+    _call("mmg_linear_fwd_rider", x, _pro(pro), W, bias, out, M, N, K, C.byref(epi), y, _pro(rpro), rows, rows.numel(), W, bias,
+          act, x0, C.byref(epi_a), names={"X": "x", "Y": "out", "X_a": "rider.y", "rows": "rider.rows"})
+    _pe(_tok, "linear_fwd", 4 * (M * K + N * K + M * N), 2 * M * N * K)
+    rider.parked = None
+    return out, rn
+
+
 # mmg_bnbwd_t.mode: linear_bnbwd / _l2bwd / _bnbwd2 / _bnbwd_rows
 BNBWD_BN, BNBWD_L2, BNBWD_BN2, BNBWD_ROWS = (_lib.MMG_BNBWD_BN, _lib.MMG_BNBWD_L2, _lib.MMG_BNBWD_BN2,
                                              _lib.MMG_BNBWD_ROWS)
@@ -1059,15 +1117,84 @@ def linear_bnbwd_rows(g_rows: torch.Tensor, row_pos: torch.Tensor, y: torch.Tens
                          masked=masked)
 
 
+def linear_bnbwd_rider_supported(M: int, N: int, K: int, n_sel: int) -> bool:
+    return bool(_lib.load().mmg_linear_bnbwd_rider_supported(int(M), int(N), int(K), int(n_sel)))
+
+
+@dataclass
+class BwdRider:
+    """Pairs the compact L2 backward of one pass -- linear_l2bwd(g_rows, out, rn, W) on its listed rows, and optionally the
+    bn_bwd_stats_rows of its dx -- with the dense linear_l2bwd of the other pass into ONE launch (mmg_linear_bnbwd_rider):
+    park, then hand the holder to the dense linear_l2bwd.  park validates, allocates dz / dx (/ sums) and parks WITHOUT
+    launching; the dense call launches both and fills them.  Nothing falls back: a second park on a holder that still holds a
+    descriptor, a dense call on an empty holder, with another W or with a weight gradient raises."""
+    parked: Optional[tuple] = None
+
+    def park(self, g_rows: torch.Tensor, out: torch.Tensor, rn: torch.Tensor, W: torch.Tensor, n_rows: int, stats=None):
+        """n_rows: the rows of the dense problem.  stats = (y, rows, pro, fold) of bn_bwd_stats_rows(dx, y, rows, pro, fold),
+        or None -> (dz, dx, sums or None), filled by the dense call that takes this holder."""
+        if self.parked is not None:
+            raise RuntimeError("BwdRider: the holder already holds a parked call")
+        n, K = out.shape
+        N = W.shape[1]
+        if W.shape[0] != K or tuple(g_rows.shape) != (n, K) or not linear_bnbwd_rider_supported(n_rows, N, K, n):
+            raise ValueError(f"BwdRider: no rider for out {tuple(out.shape)}, W {tuple(W.shape)} beside {n_rows} dense rows")
+        dz, dx = torch.empty_like(out), torch.empty(n, N, device=out.device)
+        sums = torch.empty(2, N, dtype=torch.float64, device=out.device) if stats is not None else None
+        self.parked = (g_rows, out, rn, W, n_rows, stats, dz, dx, sums)
+        return dz, dx, sums
+
+    def require_consumed(self):
+        if self.parked is not None:
+            raise RuntimeError("BwdRider: the parked call was never launched (no dense call followed it)")
+
+
+def _linear_l2bwd_rider(g, out, rn, W, next_bn, rider: BwdRider):
+    """The dense linear_l2bwd and the call parked on `rider` as one launch -> (dz, dx[, the next BatchNorm's sums])."""
+    M, K = out.shape
+    N = W.shape[1]
+    if rider.parked is None:
+        raise RuntimeError("linear_l2bwd: nothing is parked on the holder")
+    g_a, out_a, rn_a, W_a, n_rows, stats, dz_a, dx_a, sums_a = rider.parked
+    if W.data_ptr() != W_a.data_ptr() or W.shape != W_a.shape:
+        raise RuntimeError("linear_l2bwd: the parked call belongs to another W")
+    if n_rows != M:
+        raise ValueError("linear_l2bwd: the parked call was made for a dense problem of another size")
+    dz, dx = torch.empty_like(out), torch.empty(M, N, device=out.device)
+    nbt, nsums = _next_bn(next_bn, M, N) if next_bn is not None else (None, None)
+    desc = BnBwdT(BNBWD_L2, _p(g), None, None, 0, _p(out), None, None, None, None, None, 1.0, None, None, _p(rn), L2_EPS)
+    desc_a = BnBwdT(BNBWD_L2, _p(g_a), None, None, 0, _p(out_a), None, None, None, None, None, 1.0, None, None, _p(rn_a), L2_EPS)
+    nbt_a = None
+    if stats is not None:
+        y, rows, pro, fold = stats
+        pc = pro.c()
+        # (its own buffer: the shared workspace() holds the dense launch's partial rows until the one launch that sums both)
+        ws = torch.empty(_lib.load().mmg_bn_bwd_stats_rows_ws_bytes(N), dtype=torch.uint8, device=out.device)
+        nbt_a = NextBnT(_p(y), C.pointer(pc), _p(fold.mean), _p(fold.rstd), _p(sums_a, torch.float64), 0, _p(ws, torch.uint8),
+                        ws.numel())
+    _tok = _pb("linear_l2bwd")
+    _call("mmg_linear_bnbwd_rider", C.byref(desc), W, dz, dx, M, N, K, C.byref(nbt) if nbt is not None else None,
+          C.byref(desc_a), W, dz_a, dx_a, out_a.shape[0], stats[1] if stats is not None else None,
+          C.byref(nbt_a) if nbt_a is not None else None, names={"rows": "rider.rows"})
+    _pe(_tok, "linear_l2bwd", 4 * (3 * M * K + M * N * (2 if next_bn is not None else 1)), 2 * M * N * K)
+    rider.parked = None
+    return (dz, dx, nsums) if next_bn is not None else (dz, dx)
+
+
 def linear_l2bwd(g: torch.Tensor, out: torch.Tensor, rn: torch.Tensor, W: torch.Tensor, next_bn: Optional["NextBN"] = None,
-                 wgrad: Optional[FusedWgrad] = None):
+                 wgrad: Optional[FusedWgrad] = None, rider: Optional[BwdRider] = None):
     """l2norm_bwd(g, out, rn) and the data gradient dz @ W of the linear in front of the normalisation -> (dz, dx): ONE
     kernel where linear_bnbwd_supported (W [K, N] = the forward weight in place), the two launches elsewhere.
-    next_bn / wgrad: as for linear_bnbwd (the caller checks linear_bnbwd_wgrad_supported)."""
+    next_bn / wgrad: as for linear_bnbwd (the caller checks linear_bnbwd_wgrad_supported).
+    rider: the call parked on this holder rides in the launch (see BwdRider; no wgrad)."""
     M, K = out.shape
     N = W.shape[1]
     if W.shape[0] != K:
         raise ValueError(f"linear_l2bwd: W has {W.shape[0]} rows, out has {K} columns")
+    if rider is not None:
+        if wgrad is not None:
+            raise ValueError("linear_l2bwd: a rider excludes the fused weight gradient")
+        return _linear_l2bwd_rider(g, out, rn, W, next_bn, rider)
     if not linear_bnbwd_supported(M, N, K, BNBWD_L2, wgrad is not None):
         if wgrad is not None:
             raise ValueError(f"linear_l2bwd: no fused weight gradient for M={M} N={N} K={K}")
