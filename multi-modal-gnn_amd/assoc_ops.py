@@ -7,8 +7,6 @@ never a silent substitute for them).
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import ops
@@ -23,22 +21,13 @@ AS_PLANES = DEFINES["MMG_AS_PLANES"]              # N, SX, SXX, SXY
 
 def assoc_plan(n: int, n_labs: int):
     """The slab plan of assoc_moments (mmg_assoc_plan, a host function) -> (rows per slab, slabs)."""
-    rows, slabs = C.c_int64(0), C.c_int(0)
-    ops.check(load().mmg_assoc_plan(int(n), int(n_labs), C.byref(rows), C.byref(slabs)), "mmg_assoc_plan")
-    return int(rows.value), int(slabs.value)
-
-
-def _matrix(X: torch.Tensor, what: str):
-    """An fp32 [n, L] matrix whose rows may be strided -> (pointer, n, L, row stride)."""
-    if not torch.is_tensor(X) or X.dim() != 2:
-        raise ValueError(f"{what}: X must be a 2-D tensor [patients, labs]")
-    return ops._rows_matrix(X, "X")
+    return ops.slab_plan(BINDING, "mmg_assoc_plan", n, n_labs)
 
 
 def assoc_colstats(X: torch.Tensor):
     """Per lab the observed count (int64 [L]) and the fp64 mean of its observed values (0 for a lab nobody has), and
     the number of infinite cells (int64 [1]) (mmg_assoc_colstats), on the device."""
-    px, n, L, ld = _matrix(X, "assoc_colstats")
+    px, n, L, ld = ops._lab_matrix(X, "assoc_colstats")
     dev = X.device
     count = torch.empty(max(L, 0), dtype=torch.int64, device=dev)
     mean = torch.empty(max(L, 0), dtype=torch.float64, device=dev)
@@ -50,7 +39,7 @@ def assoc_colstats(X: torch.Tensor):
 
 def assoc_moments(X: torch.Tensor, center: torch.Tensor):
     """The planes N, SX, SXX, SXY (fp64 [4, L, L]) of X about `center` (fp64 [L] on the device) (mmg_assoc_moments)."""
-    px, n, L, ld = _matrix(X, "assoc_moments")
+    px, n, L, ld = ops._lab_matrix(X, "assoc_moments")
     if center.dim() != 1 or center.numel() != L:
         raise ValueError(f"assoc_moments: center must hold {L} values, got {tuple(center.shape)}")
     if center.device != X.device:

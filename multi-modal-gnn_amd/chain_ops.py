@@ -7,8 +7,6 @@ substitute for them).
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import ops
@@ -23,16 +21,7 @@ CH_APPLY_ROWS = DEFINES["MMG_CH_APPLY_ROWS"]
 
 def chain_plan(n: int, n_labs: int):
     """The slab plan of chain_moments (mmg_chain_plan, a host function) -> (rows per slab, slabs)."""
-    rows, slabs = C.c_int64(0), C.c_int(0)
-    ops.check(load().mmg_chain_plan(int(n), int(n_labs), C.byref(rows), C.byref(slabs)), "mmg_chain_plan")
-    return int(rows.value), int(slabs.value)
-
-
-def _matrix(X: torch.Tensor, what: str):
-    """An fp32 [n, L] matrix whose rows may be strided -> (pointer, n, L, row stride)."""
-    if not torch.is_tensor(X) or X.dim() != 2:
-        raise ValueError(f"{what}: X must be a 2-D tensor [patients, labs]")
-    return ops._rows_matrix(X, "X")
+    return ops.slab_plan(BINDING, "mmg_chain_plan", n, n_labs)
 
 
 def _working(W: torch.Tensor, n: int, L: int, what: str):
@@ -47,7 +36,7 @@ def _vector(v: torch.Tensor, L: int, name: str, what: str):
 
 def chain_init(X: torch.Tensor, center: torch.Tensor) -> torch.Tensor:
     """W fp64 [n, L]: X where observed, else center (mmg_chain_init)."""
-    px, n, L, ld = _matrix(X, "chain_init")
+    px, n, L, ld = ops._lab_matrix(X, "chain_init")
     _vector(center, L, "center", "chain_init")
     W = torch.empty(n, L, dtype=torch.float64, device=X.device)
     _call("mmg_chain_init", px, n, L, ld, center, W)
@@ -57,7 +46,7 @@ def chain_init(X: torch.Tensor, center: torch.Tensor) -> torch.Tensor:
 def chain_moments(W: torch.Tensor, X: torch.Tensor, j: int, center: torch.Tensor, out=None):
     """-> (n_j int64 [1], s fp64 [L], G fp64 [L, L]) of u = W - center over the rows that have lab j
     (mmg_chain_moments).  out: the three tensors of an earlier call, written again."""
-    px, n, L, ld = _matrix(X, "chain_moments")
+    px, n, L, ld = ops._lab_matrix(X, "chain_moments")
     _working(W, n, L, "chain_moments")
     _vector(center, L, "center", "chain_moments")
     if out is None:
@@ -85,7 +74,7 @@ def chain_apply(W: torch.Tensor, X: torch.Tensor, j: int, count: torch.Tensor, c
                 mu: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor, delta: torch.Tensor, accumulate: bool = False):
     """Rewrite column j of W on the rows without lab j; delta (fp64 [1]) = the largest |new - old|, folded into its
     value when ``accumulate`` (mmg_chain_apply)."""
-    px, n, L, ld = _matrix(X, "chain_apply")
+    px, n, L, ld = ops._lab_matrix(X, "chain_apply")
     _working(W, n, L, "chain_apply")
     for v, name in ((count, "count"), (center, "center"), (w, "w"), (mu, "mu"), (lo, "lo"), (hi, "hi")):
         _vector(v, L, name, "chain_apply")
@@ -95,7 +84,7 @@ def chain_apply(W: torch.Tensor, X: torch.Tensor, j: int, count: torch.Tensor, c
 
 def chain_finish(W: torch.Tensor, X: torch.Tensor, count: torch.Tensor) -> torch.Tensor:
     """fp32 [n, L]: observed cells bit for bit, NaN for a lab nobody has, else W rounded once (mmg_chain_finish)."""
-    px, n, L, ld = _matrix(X, "chain_finish")
+    px, n, L, ld = ops._lab_matrix(X, "chain_finish")
     _working(W, n, L, "chain_finish")
     _vector(count, L, "count", "chain_finish")
     out = torch.empty(n, L, dtype=torch.float32, device=X.device)

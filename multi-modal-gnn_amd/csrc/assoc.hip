@@ -3,7 +3,7 @@
 // what pandas.DataFrame.corr / .cov(min_periods=) compute pair by pair on the host -- and the co-observation counts M^T M.
 //   k_as_colsum   one read of X: per (64 columns, row slab) the fp64 sum, the count and the infinite cells of a column.
 //   k_as_colfin   one workgroup: the slabs of a column in ascending order, ONE division; the infinite cells of all columns.
-//   k_as_moments  grid (64 x 64 block pairs of the upper block triangle, row slabs), the shape of k_pca_gram (pca.hip).  A
+//   k_as_moments  grid (64 x 64 block pairs of the upper block triangle, row slabs): the walk of gram64.h.  A
 //                 chunk of 32 rows is staged in LDS as ONE fp64 array per side: v = observed ? (double)x - center : NaN.
 //                 The three operands of a side are derived from it in registers -- m = [v == v], u = m ? v : 0, q = u * u --
 //                 so a side costs 32 x 66 doubles instead of three times that (two sides: 33,792 bytes; six staged operands
@@ -15,9 +15,9 @@
 //   k_as_sum      one thread per cell and plane: the slabs in ascending order; N and SXY from a <= b to both (a, b), (b, a).
 //   k_as_finish   one thread per cell: r, cov, jaccard, lift.
 // fp64 contraction is OFF for the whole file: k_as_finish restates numpy arithmetic operation by operation, and q = u * u
-// is a product rounded on its own.  The f64 MFMA's C/D layout is its own: lane l, register g hold row (l >> 4) + 4 g, column
-// l & 15.  Built into libmmgnn_assoc.so beside libmmgnn.so and on top of it (mmg_set_error).
+// is a product rounded on its own.  Built into libmmgnn_assoc.so beside libmmgnn.so and on top of it (mmg_set_error).
 #include "common.h"
+#include "gram64.h"
 #include "../../include/mmgnn_assoc.h"
 #include <limits.h>
 #include <math.h>
@@ -26,39 +26,25 @@
 
 namespace {
 
-constexpr int AS_NTHR = 256;
-constexpr int AS_BT = MMG_AS_TILE;           // a workgroup's block of the table
-constexpr int AS_RC = MMG_AS_CHUNK;          // rows per LDS chunk
-constexpr int AS_LD = AS_BT + 2;             // LDS row stride (doubles)
+constexpr int AS_NTHR = GRAM64_NTHR;
 constexpr int AS_PLANES = MMG_AS_PLANES;
-static_assert(AS_BT == 64 && AS_RC % 4 == 0 && AS_NTHR == 256, "four waves, one 16 x 64 strip each, four rows per MFMA");
+static_assert(MMG_AS_TILE == GRAM64_TILE && MMG_AS_CHUNK == GRAM64_CHUNK, "the header publishes gram64.h's tile and chunk");
 static_assert(MMG_AS_MIN_ROWS % MMG_AS_CHUNK == 0, "a slab is whole chunks");
 static_assert(MMG_AS_MAX_LABS <= 512, "k_as_colfin is one workgroup of 512 threads");
 
-typedef double as_d4 __attribute__((ext_vector_type(4)));
-
-struct AsPlan {
-  int64_t rows, stat_rows;
-  int slabs, stat_slabs, nb, pairs;
+struct AsPlan : Gram64Plan {
+  int64_t stat_rows;
+  int stat_slabs;
 };
 inline AsPlan as_plan(int64_t n, int L) {
   AsPlan p;
-  p.nb = (L + AS_BT - 1) / AS_BT;
-  p.pairs = p.nb * (p.nb + 1) / 2;                                    // <= 36
-  const int64_t target = MMG_AS_BLOCKS / p.pairs;
-  int64_t rows = (n + target - 1) / target;
-  rows = (rows + AS_RC - 1) / AS_RC * AS_RC;
-  if (rows < MMG_AS_MIN_ROWS) rows = MMG_AS_MIN_ROWS;
-  p.rows = rows;
-  p.slabs = (int)((n + rows - 1) / rows);
+  static_cast<Gram64Plan&>(p) = gram64_plan(n, L, MMG_AS_BLOCKS, MMG_AS_MIN_ROWS);      // pairs <= 36
   p.stat_rows = (n + MMG_AS_STAT_SLABS - 1) / MMG_AS_STAT_SLABS;
   if (p.stat_rows < MMG_AS_STAT_MIN_ROWS) p.stat_rows = MMG_AS_STAT_MIN_ROWS;
   p.stat_slabs = (int)((n + p.stat_rows - 1) / p.stat_rows);
   return p;
 }
 inline bool as_shape_ok(int64_t n, int L) { return n >= 1 && n < INT32_MAX && L >= 1 && L <= MMG_AS_MAX_LABS; }
-
-__device__ __forceinline__ bool as_finite(float x) { return fabsf(x) <= 3.402823466e+38f; }     // false for NaN and inf
 
 // ---- column statistics: grid (64-column blocks, slabs)
 __global__ __launch_bounds__(AS_NTHR) void k_as_colsum(const float* __restrict__ X, int64_t n, int L, int64_t ld,
@@ -77,7 +63,7 @@ __global__ __launch_bounds__(AS_NTHR) void k_as_colsum(const float* __restrict__
     const float* __restrict__ xc = X + col;
     for (int64_t r = r0 + lr; r < r1; r += 4) {
       const float x = xc[r * ld];
-      if (as_finite(x)) { s += (double)x; ++c; }
+      if (mmg_finite(x)) { s += (double)x; ++c; }
       else if (x == x) ++inf;
     }
   }
@@ -132,121 +118,67 @@ __global__ __launch_bounds__(512) void k_as_colfin(const double* __restrict__ ps
 
 // ---- moments: grid (block pairs of the upper triangle, slabs).  Two workgroups per CU: the 96 accumulator doubles of a
 // lane and the rest fit 256 registers without scratch, and a second workgroup covers the other's staging of a chunk.
+struct AsAcc {
+  gram64_d4 aN[4] = {}, aX[4] = {}, aXX[4] = {}, aXY[4] = {}, tX[4] = {}, tXX[4] = {};
+  double am, au, aq;
+  __device__ __forceinline__ void row(double av, bool) {
+    const bool ao = av == av;
+    am = ao ? 1.0 : 0.0;
+    au = ao ? av : 0.0;
+    aq = au * au;
+  }
+  __device__ __forceinline__ void tile(int j, double bv, bool both) {
+    const bool bo = bv == bv;
+    const double bm = bo ? 1.0 : 0.0, bu = bo ? bv : 0.0;
+    aN[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(am, bm, aN[j], 0, 0, 0);
+    aX[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(au, bm, aX[j], 0, 0, 0);
+    aXX[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(aq, bm, aXX[j], 0, 0, 0);
+    aXY[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(au, bu, aXY[j], 0, 0, 0);
+    if (both) {
+      const double bq = bu * bu;
+      tX[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(am, bu, tX[j], 0, 0, 0);
+      tXX[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(am, bq, tXX[j], 0, 0, 0);
+    }
+  }
+};
+
 __global__ __launch_bounds__(AS_NTHR, 2) void k_as_moments(const float* __restrict__ X, int64_t n, int L, int64_t ld,
                                                         const double* __restrict__ center, int64_t rows_per_slab, int nb,
                                                         double* __restrict__ partial) {
-  __shared__ double As[AS_RC * AS_LD];
-  __shared__ double Bs[AS_RC * AS_LD];
-  int p = (int)blockIdx.x, bi = 0;
-  while (p >= nb - bi) { p -= nb - bi; ++bi; }                  // pair -> (bi, bj), bi <= bj < nb
-  const int bj = bi + p;
-  const bool diag = bi == bj;
-  const int A0 = AS_BT * bi, B0 = AS_BT * bj;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int lc = tid & 63, lr = tid >> 6;                       // the loader's column and first row of a chunk
-  const int ca = A0 + lc, cb = B0 + lc;
-  const bool a_in = ca < L, b_in = cb < L;
-  const double mua = a_in ? center[ca] : 0.0, mub = b_in ? center[cb] : 0.0;
+  __shared__ double As[GRAM64_SIDE], Bs[GRAM64_SIDE];
+  const Gram64Tile t(nb, L, n, rows_per_slab);
+  const double mua = t.a_in ? center[t.ca] : 0.0, mub = t.b_in ? center[t.cb] : 0.0;
   const double missing = __builtin_nan("");
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per_slab;
-  const int64_t r1 = r0 + rows_per_slab < n ? r0 + rows_per_slab : n;
-  const int kr = lane >> 4, kc = lane & 15;
-  const bool strip = A0 + 16 * w < L;                           // wave-uniform
-  as_d4 aN[4], aX[4], aXX[4], aXY[4], tX[4], tXX[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    aN[j] = as_d4{0.0, 0.0, 0.0, 0.0}; aX[j] = aN[j]; aXX[j] = aN[j]; aXY[j] = aN[j]; tX[j] = aN[j]; tXX[j] = aN[j];
-  }
-  const double* Bp = diag ? As : Bs;
-
-  for (int64_t rc = r0; rc < r1; rc += AS_RC) {
-    __syncthreads();                                            // the previous chunk has been consumed
-#pragma unroll
-    for (int i = 0; i < AS_RC / 4; ++i) {
-      const int row = lr + 4 * i;
-      const int64_t r = rc + row;
-      const bool live = r < r1;
-      float xa = 0.f, xb = 0.f;
-      if (live && a_in) xa = X[r * ld + ca];
-      if (!diag && live && b_in) xb = X[r * ld + cb];
-      As[row * AS_LD + lc] = (live && a_in && as_finite(xa)) ? (double)xa - mua : missing;
-      if (!diag) Bs[row * AS_LD + lc] = (live && b_in && as_finite(xb)) ? (double)xb - mub : missing;
-    }
-    __syncthreads();
-    if (strip) {
-#pragma unroll
-      for (int ks = 0; ks < AS_RC / 4; ++ks) {
-        const int row = 4 * ks + kr;
-        const double av = As[row * AS_LD + 16 * w + kc];
-        const bool ao = av == av;
-        const double am = ao ? 1.0 : 0.0, au = ao ? av : 0.0, aq = au * au;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (B0 + 16 * j < L && (!diag || j >= w)) {           // wave-uniform
-            const double bv = Bp[row * AS_LD + 16 * j + kc];
-            const bool bo = bv == bv;
-            const double bm = bo ? 1.0 : 0.0, bu = bo ? bv : 0.0;
-            aN[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(am, bm, aN[j], 0, 0, 0);
-            aX[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(au, bm, aX[j], 0, 0, 0);
-            aXX[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(aq, bm, aXX[j], 0, 0, 0);
-            aXY[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(au, bu, aXY[j], 0, 0, 0);
-            if (!diag || j > w) {
-              const double bq = bu * bu;
-              tX[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(am, bu, tX[j], 0, 0, 0);
-              tXX[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(am, bq, tXX[j], 0, 0, 0);
-            }
-          }
-        }
-      }
-    }
-  }
-  if (!strip) return;
+  AsAcc acc;
+  gram64_walk(t, L, As, Bs, acc, [=](int64_t r, bool live, double& a, double& b) {
+    float xa = 0.f, xb = 0.f;
+    if (live && t.a_in) xa = X[r * ld + t.ca];
+    if (!t.diag && live && t.b_in) xb = X[r * ld + t.cb];
+    a = (live && t.a_in && mmg_finite(xa)) ? (double)xa - mua : missing;
+    if (!t.diag) b = (live && t.b_in && mmg_finite(xb)) ? (double)xb - mub : missing;
+  });
   const size_t ll = (size_t)L * L;
   double* __restrict__ out = partial + (size_t)blockIdx.y * AS_PLANES * ll;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (B0 + 16 * j < L && (!diag || j >= w)) {
-      const int b = B0 + 16 * j + kc;
-      const bool both = !diag || j > w;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int a = A0 + 16 * w + kr + 4 * g;                 // the f64 MFMA's own C/D map
-        if (a < L && b < L) {
-          const size_t ab = (size_t)a * L + b, ba = (size_t)b * L + a;
-          out[ab] = aN[j][g];                                   // (a diagonal tile's a > b half is never read)
-          out[ll + ab] = aX[j][g];
-          out[2 * ll + ab] = aXX[j][g];
-          out[3 * ll + ab] = aXY[j][g];
-          if (both) {
-            out[ll + ba] = tX[j][g];
-            out[2 * ll + ba] = tXX[j][g];
-          }
-        }
-      }
+  gram64_store_tiles(t, L, [&](int j, bool both) {
+    gram64_put(t, L, j, acc.aN[j], out);
+    gram64_put(t, L, j, acc.aX[j], out + ll);
+    gram64_put(t, L, j, acc.aXX[j], out + 2 * ll);
+    gram64_put(t, L, j, acc.aXY[j], out + 3 * ll);
+    if (both) {                                                 // the lower halves of SX and SXX
+      gram64_put(t, L, j, acc.tX[j], out + ll, true);
+      gram64_put(t, L, j, acc.tXX[j], out + 2 * ll, true);
     }
-  }
+  });
 }
 
-// grid (cells / 256, planes): every cell of SX and SXX lies in a computed tile of every slab, of N and SXY every a <= b
+// grid (cells / 256, planes): N and SXY are symmetric, SX and SXX are not
 __global__ __launch_bounds__(AS_NTHR) void k_as_sum(const double* __restrict__ partial, int slabs, int L,
                                                     double* __restrict__ out) {
   const int idx = (int)blockIdx.x * AS_NTHR + threadIdx.x;
   const int plane = (int)blockIdx.y;
-  if (idx >= L * L) return;
-  const int a = idx / L, b = idx % L;
+  const size_t ll = (size_t)L * L;
   const bool sym = plane == 0 || plane == 3;
-  if (sym && a > b) return;
-  const size_t ll = (size_t)L * L, step = AS_PLANES * ll;
-  const double* __restrict__ src = partial + plane * ll + idx;
-  double s = 0.0;
-  int q = 0;
-  for (; q + 3 < slabs; q += 4) {
-    const double v0 = src[q * step], v1 = src[(q + 1) * step], v2 = src[(q + 2) * step], v3 = src[(q + 3) * step];
-    s += v0; s += v1; s += v2; s += v3;
-  }
-  for (; q < slabs; ++q) s += src[q * step];
-  out[plane * ll + idx] = s;
-  if (sym && a < b) out[plane * ll + (size_t)b * L + a] = s;
+  if (idx < L * L) gram64_sum_cell<4>(partial + plane * ll, AS_PLANES * ll, slabs, L, idx, sym, out + plane * ll);
 }
 
 // ---- r, cov, jaccard, lift: one thread per cell, every operation rounded on its own

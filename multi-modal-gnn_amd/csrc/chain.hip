@@ -2,8 +2,8 @@
 // ridge regression over the rows that have it, on all the other labs of the fp64 working matrix W, and its missing cells
 // are rewritten from the fit -- sklearn.impute.IterativeImputer(Ridge(alpha), skip_complete=False).
 //   k_ch_init     W = observed ? (double)X : center.
-//   k_ch_moments  grid (64 x 64 block pairs of the upper block triangle, row slabs), the shape of k_as_moments
-//                 (assoc.hip).  The mask is one bit per ROW here: a chunk of 32 rows is staged in LDS as u = W - center,
+//   k_ch_moments  grid (64 x 64 block pairs of the upper block triangle, row slabs): the walk of gram64.h.
+//                 The mask is one bit per ROW here: a chunk of 32 rows is staged in LDS as u = W - center,
 //                 zeros for a row without the target lab, so one accumulation per 16 x 16 tile on v_mfma_f64_16x16x4_f64
 //                 is G; the diagonal block pairs add s as the product with a column of ones, block pair 0 counts n_j.
 //   k_ch_sum      one thread per cell of G (a <= b, written to both halves), of s and of n_j: slabs in ascending order.
@@ -12,10 +12,10 @@
 //   k_ch_apply    one thread per row without the target lab: the prediction in ascending predictor order, clipped; the
 //                 block's largest |new - old| to ws.  k_ch_maxfin: one workgroup folds the blocks' maxima into delta.
 //   k_ch_finish   fp32 out: observed cells bit for bit, NaN for a lab nobody has, else (float)W.
-// fp64 contraction is OFF for the whole file: solve and apply restate numpy arithmetic operation by operation.  The f64
-// MFMA's C/D layout is its own: lane l, register g hold row (l >> 4) + 4 g, column l & 15.  Built into libmmgnn_chain.so
-// beside libmmgnn.so and on top of it (mmg_set_error).
+// fp64 contraction is OFF for the whole file: solve and apply restate numpy arithmetic operation by operation.  Built
+// into libmmgnn_chain.so beside libmmgnn.so and on top of it (mmg_set_error).
 #include "common.h"
+#include "gram64.h"
 #include "../../include/mmgnn_chain.h"
 #include <limits.h>
 #include <math.h>
@@ -24,40 +24,18 @@
 
 namespace {
 
-constexpr int CH_NTHR = 256;
-constexpr int CH_BT = MMG_CH_TILE;           // a workgroup's block of the table
-constexpr int CH_RC = MMG_CH_CHUNK;          // rows per LDS chunk
-constexpr int CH_LD = CH_BT + 2;             // LDS row stride (doubles)
+constexpr int CH_NTHR = GRAM64_NTHR;
 constexpr int CH_ML = MMG_CH_MAX_LABS;
 constexpr int CH_SOLVE_NTHR = 512;           // 16 rows x 32 columns of the trailing update at a time
 constexpr int CH_TRI = (CH_ML - 1) * CH_ML / 2;                                   // packed lower triangle, 127 x 127
 constexpr int CH_SOLVE_LDS = (CH_TRI + 3 * CH_ML) * (int)sizeof(double) + CH_ML * (int)sizeof(int);
-static_assert(CH_BT == 64 && CH_RC % 4 == 0 && CH_NTHR == 256, "four waves, one 16 x 64 strip each, four rows per MFMA");
+static_assert(MMG_CH_TILE == GRAM64_TILE && MMG_CH_CHUNK == GRAM64_CHUNK, "the header publishes gram64.h's tile and chunk");
 static_assert(MMG_CH_MIN_ROWS % MMG_CH_CHUNK == 0, "a slab is whole chunks");
 static_assert(MMG_CH_APPLY_ROWS == CH_NTHR, "one thread per row");
 static_assert(CH_SOLVE_LDS <= 160 * 1024, "the solve's system lives in one CU's LDS");
 
-typedef double ch_d4 __attribute__((ext_vector_type(4)));
-
-struct ChPlan {
-  int64_t rows;
-  int slabs, nb, pairs;
-};
-inline ChPlan ch_plan(int64_t n, int L) {
-  ChPlan p;
-  p.nb = (L + CH_BT - 1) / CH_BT;
-  p.pairs = p.nb * (p.nb + 1) / 2;                                    // <= 3
-  const int64_t target = MMG_CH_BLOCKS / p.pairs;
-  int64_t rows = (n + target - 1) / target;
-  rows = (rows + CH_RC - 1) / CH_RC * CH_RC;
-  if (rows < MMG_CH_MIN_ROWS) rows = MMG_CH_MIN_ROWS;
-  p.rows = rows;
-  p.slabs = (int)((n + rows - 1) / rows);
-  return p;
-}
+inline Gram64Plan ch_plan(int64_t n, int L) { return gram64_plan(n, L, MMG_CH_BLOCKS, MMG_CH_MIN_ROWS); }     // pairs <= 3
 inline bool ch_shape_ok(int64_t n, int L) { return n >= 1 && n < INT32_MAX && L >= 1 && L <= CH_ML; }
-
-__device__ __forceinline__ bool ch_finite(float x) { return fabsf(x) <= 3.402823466e+38f; }     // false for NaN and inf
 
 // ---- W = observed ? X : center
 __global__ __launch_bounds__(CH_NTHR) void k_ch_init(const float* __restrict__ X, int64_t n, int L, int64_t ld,
@@ -67,115 +45,55 @@ __global__ __launch_bounds__(CH_NTHR) void k_ch_init(const float* __restrict__ X
     const int64_t r = e / L;
     const int a = (int)(e - r * L);
     const float x = X[r * ld + a];
-    W[e] = ch_finite(x) ? (double)x : center[a];
+    W[e] = mmg_finite(x) ? (double)x : center[a];
   }
 }
 
 // ---- moments: grid (block pairs of the upper triangle, slabs)
+struct ChAcc {
+  gram64_d4 aG[4] = {}, aS = {};
+  double av;
+  __device__ __forceinline__ void row(double a, bool diag) {
+    av = a;
+    if (diag) aS = __builtin_amdgcn_mfma_f64_16x16x4f64(av, 1.0, aS, 0, 0, 0);     // s: the product with ones
+  }
+  __device__ __forceinline__ void tile(int t, double bv, bool) {
+    aG[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, aG[t], 0, 0, 0);
+  }
+};
+
 __global__ __launch_bounds__(CH_NTHR, 2) void k_ch_moments(const double* __restrict__ W, const float* __restrict__ X,
                                                         int64_t n, int L, int64_t ld, int j,
                                                         const double* __restrict__ center, int64_t rows_per_slab, int nb,
                                                         double* __restrict__ pG, double* __restrict__ ps,
                                                         long long* __restrict__ pn) {
-  __shared__ double As[CH_RC * CH_LD];
-  __shared__ double Bs[CH_RC * CH_LD];
+  __shared__ double As[GRAM64_SIDE], Bs[GRAM64_SIDE];
   __shared__ int scnt[4];
-  int p = (int)blockIdx.x, bi = 0;
-  while (p >= nb - bi) { p -= nb - bi; ++bi; }                  // pair -> (bi, bj), bi <= bj < nb
-  const int bj = bi + p;
-  const bool diag = bi == bj;
-  const int A0 = CH_BT * bi, B0 = CH_BT * bj;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int lc = tid & 63, lr = tid >> 6;                       // the loader's column and first row of a chunk
-  const int ca = A0 + lc, cb = B0 + lc;
-  const bool a_in = ca < L, b_in = cb < L;
-  const double mua = a_in ? center[ca] : 0.0, mub = b_in ? center[cb] : 0.0;
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per_slab;
-  const int64_t r1 = r0 + rows_per_slab < n ? r0 + rows_per_slab : n;
-  const int kr = lane >> 4, kc = lane & 15;
-  const bool strip = A0 + 16 * w < L;                           // wave-uniform
-  ch_d4 aG[4], aS = ch_d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int t = 0; t < 4; ++t) aG[t] = ch_d4{0.0, 0.0, 0.0, 0.0};
-  const double* Bp = diag ? As : Bs;
+  const Gram64Tile t(nb, L, n, rows_per_slab);
+  const double mua = t.a_in ? center[t.ca] : 0.0, mub = t.b_in ? center[t.cb] : 0.0;
   int cnt = 0;                                                  // a slab has fewer than 2^31 rows
-
-  for (int64_t rc = r0; rc < r1; rc += CH_RC) {
-    __syncthreads();                                            // the previous chunk has been consumed
-#pragma unroll
-    for (int i = 0; i < CH_RC / 4; ++i) {
-      const int row = lr + 4 * i;
-      const int64_t r = rc + row;
-      bool in = false;                                          // the row has the target lab
-      if (r < r1) in = ch_finite(X[r * ld + j]);
-      if (in && lc == 0) ++cnt;
-      double ua = 0.0, ub = 0.0;
-      if (in && a_in) ua = W[r * L + ca] - mua;
-      As[row * CH_LD + lc] = ua;
-      if (!diag) {
-        if (in && b_in) ub = W[r * L + cb] - mub;
-        Bs[row * CH_LD + lc] = ub;
-      }
-    }
-    __syncthreads();
-    if (strip) {
-#pragma unroll
-      for (int ks = 0; ks < CH_RC / 4; ++ks) {
-        const int row = 4 * ks + kr;
-        const double av = As[row * CH_LD + 16 * w + kc];
-        if (diag) aS = __builtin_amdgcn_mfma_f64_16x16x4f64(av, 1.0, aS, 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          if (B0 + 16 * t < L && (!diag || t >= w)) {           // wave-uniform
-            const double bv = Bp[row * CH_LD + 16 * t + kc];
-            aG[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, aG[t], 0, 0, 0);
-          }
-        }
-      }
-    }
-  }
-  if (lc == 0) scnt[lr] = cnt;
+  ChAcc acc;
+  gram64_walk(t, L, As, Bs, acc, [=, &cnt](int64_t r, bool live, double& a, double& b) {
+    bool in = false;                                            // the row has the target lab
+    if (live) in = mmg_finite(X[r * ld + j]);
+    if (in && t.lc == 0) ++cnt;
+    a = 0.0, b = 0.0;
+    if (in && t.a_in) a = W[r * L + t.ca] - mua;
+    if (!t.diag && in && t.b_in) b = W[r * L + t.cb] - mub;
+  });
+  if (t.lc == 0) scnt[t.lr] = cnt;
   __syncthreads();
-  if (tid == 0 && blockIdx.x == 0) pn[blockIdx.y] = (long long)scnt[0] + scnt[1] + scnt[2] + scnt[3];
-  if (!strip) return;
+  if (threadIdx.x == 0 && blockIdx.x == 0) pn[blockIdx.y] = (long long)scnt[0] + scnt[1] + scnt[2] + scnt[3];
   double* __restrict__ out = pG + (size_t)blockIdx.y * L * L;
+  gram64_store_tiles(t, L, [&](int k, bool) { gram64_put(t, L, k, acc.aG[k], out); });
+  if (t.strip && t.diag && t.kc == 0) {
 #pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    if (B0 + 16 * t < L && (!diag || t >= w)) {
-      const int b = B0 + 16 * t + kc;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int a = A0 + 16 * w + kr + 4 * g;                 // the f64 MFMA's own C/D map
-        if (a < L && b < L) out[(size_t)a * L + b] = aG[t][g];  // (a diagonal tile's a > b half is never read)
-      }
-    }
-  }
-  if (diag && kc == 0) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int a = A0 + 16 * w + kr + 4 * g;
-      if (a < L) ps[(size_t)blockIdx.y * L + a] = aS[g];
-    }
+    for (int g = 0; g < 4; ++g)
+      if (t.row(g) < L) ps[(size_t)blockIdx.y * L + t.row(g)] = acc.aS[g];
   }
 }
 
-// one thread per cell of G, of s and of n_j.  The adds are serial in slab order; sixteen loads are in flight at a time
-// (at 478 slabs the kernel is the latency of its dependent loads, not their bytes).
-template <class T>
-__device__ __forceinline__ T ch_sum_slabs(const T* __restrict__ src, size_t stride, int slabs) {
-  T t = 0;
-  int q = 0;
-  for (; q + 15 < slabs; q += 16) {
-    T v[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) v[k] = src[(size_t)(q + k) * stride];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) t += v[k];
-  }
-  for (; q < slabs; ++q) t += src[(size_t)q * stride];
-  return t;
-}
-
+// one thread per cell of G, of s and of n_j; sixteen loads in flight (at 478 slabs the kernel is their latency)
 __global__ __launch_bounds__(CH_NTHR) void k_ch_sum(const double* __restrict__ pG, const double* __restrict__ ps,
                                                     const long long* __restrict__ pn, int slabs, int L,
                                                     double* __restrict__ G, double* __restrict__ s,
@@ -183,16 +101,12 @@ __global__ __launch_bounds__(CH_NTHR) void k_ch_sum(const double* __restrict__ p
   const int idx = (int)blockIdx.x * CH_NTHR + threadIdx.x;
   const int ll = L * L;
   if (idx < ll) {
-    const int a = idx / L, b = idx % L;
-    if (a > b) return;
-    const double t = ch_sum_slabs(pG + idx, (size_t)ll, slabs);
-    G[idx] = t;
-    if (a < b) G[(size_t)b * L + a] = t;
+    gram64_sum_cell<16>(pG, (size_t)ll, slabs, L, idx, true, G);
   } else if (idx < ll + L) {
     const int a = idx - ll;
-    s[a] = ch_sum_slabs(ps + a, (size_t)L, slabs);
+    s[a] = gram64_sum_slabs<double, 16>(ps + a, (size_t)L, slabs);
   } else if (idx == ll + L) {
-    n_j[0] = ch_sum_slabs(pn, (size_t)1, slabs);
+    n_j[0] = gram64_sum_slabs<long long, 16>(pn, (size_t)1, slabs);
   }
 }
 
@@ -292,7 +206,7 @@ __global__ __launch_bounds__(CH_NTHR) void k_ch_apply(double* __restrict__ W, co
   const int m = sm_m;
   const int64_t r = (int64_t)blockIdx.x * CH_NTHR + tid;
   double d = 0.0;
-  if (r < n && !ch_finite(X[r * ld + j])) {
+  if (r < n && !mmg_finite(X[r * ld + j])) {
     double* __restrict__ row = W + r * L;
     double t = 0.0;
     for (int k = 0; k < m; ++k) {
@@ -339,7 +253,7 @@ __global__ __launch_bounds__(CH_NTHR) void k_ch_finish(const double* __restrict_
     const int a = (int)(e - r * L);
     const float x = X[r * ld + a];
     float v;
-    if (ch_finite(x)) v = x;
+    if (mmg_finite(x)) v = x;
     else if (!(count[a] > 0)) v = __builtin_nanf("");
     else v = (float)W[e];
     out[r * ld_out + a] = v;
@@ -347,7 +261,7 @@ __global__ __launch_bounds__(CH_NTHR) void k_ch_finish(const double* __restrict_
 }
 
 size_t moments_carve(void* ws, int64_t n, int L, double** pG, double** ps, long long** pn) {
-  const ChPlan p = ch_plan(n, L);
+  const Gram64Plan p = ch_plan(n, L);
   MmgCarver c(ws);
   *pG = c.take<double>((size_t)p.slabs * L * L);
   *ps = c.take<double>((size_t)p.slabs * L);
@@ -378,7 +292,7 @@ extern "C" int mmg_chain_plan(int64_t n, int L, int64_t* rows_per_slab, int* sla
   MMG_CHECK_ARG(ch_shape_ok(n, L), "chain_plan: n %lld outside [1, 2^31) or %d labs outside [1, %d]", (long long)n, L,
                 CH_ML);
   MMG_CHECK_ARG(rows_per_slab && slabs, "chain_plan: null pointer (rows_per_slab, slabs)");
-  const ChPlan p = ch_plan(n, L);
+  const Gram64Plan p = ch_plan(n, L);
   *rows_per_slab = p.rows;
   *slabs = p.slabs;
   return MMG_OK;
@@ -410,7 +324,7 @@ extern "C" int mmg_chain_moments(const double* W, const float* X, int64_t n, int
   double *pG, *ps;
   long long* pn;
   MMG_CHECK_WS("chain_moments", moments_carve(ws, n, L, &pG, &ps, &pn));
-  const ChPlan p = ch_plan(n, L);
+  const Gram64Plan p = ch_plan(n, L);
   hipStream_t st = (hipStream_t)stream;
   MMG_LAUNCH(MMG_PROBE_ELEMENTWISE, n, L, L, 0, k_ch_moments, dim3((unsigned)p.pairs, (unsigned)p.slabs), dim3(CH_NTHR), 0,
              st, W, X, n, L, ld_x, j, center, p.rows, p.nb, pG, ps, pn);

@@ -19,24 +19,20 @@
 //          written to both (a, b) and (b, a): S is exactly symmetric.
 //   rows   16 lanes per row: lane s adds columns s, s + 16, ... in ascending order by fma, then an xor butterfly 8, 4,
 //          2, 1 (a + b == b + a bit for bit: every lane holds the same sum).
-// The f64 MFMA's C/D layout is its own: lane l, register g hold row (l >> 4) + 4 g, column l & 15 -- not the f32 map.
+// The Gram kernel is the walk of gram64.h, which also explains the f64 MFMA's C/D layout.
 #include "common.h"
+#include "gram64.h"
 
 namespace {
 
-constexpr int PCA_NTHR = 256;
+constexpr int PCA_NTHR = GRAM64_NTHR;
 constexpr int PCA_MAX_D = 256;
 constexpr int PCA_MAX_K = 8;
 constexpr int PCA_MAX_GRID = 256;
-constexpr int PCA_BT = 64;                   // a workgroup's block of S
-constexpr int PCA_RC = 32;                   // rows per LDS chunk
-constexpr int PCA_LD = PCA_BT + 2;           // LDS row stride (doubles)
 constexpr int PCA_MEAN_SLABS = 512;
 constexpr int PCA_MEAN_MIN_ROWS = 256;
 constexpr int PCA_GRAM_BLOCKS = 768;         // workgroups aimed at: about three per CU
 constexpr int PCA_GRAM_MIN_ROWS = 64;
-
-typedef double pca_d4 __attribute__((ext_vector_type(4)));
 
 struct PcaPlan {
   int64_t mean_rows, gram_rows;
@@ -47,14 +43,11 @@ inline PcaPlan pca_plan(int64_t n, int D) {
   p.mean_rows = (n + PCA_MEAN_SLABS - 1) / PCA_MEAN_SLABS;
   if (p.mean_rows < PCA_MEAN_MIN_ROWS) p.mean_rows = PCA_MEAN_MIN_ROWS;
   p.mean_slabs = (int)((n + p.mean_rows - 1) / p.mean_rows);
-  p.nb = (D + PCA_BT - 1) / PCA_BT;
-  p.pairs = p.nb * (p.nb + 1) / 2;
-  const int64_t target = PCA_GRAM_BLOCKS / p.pairs;                   // pairs <= 10
-  int64_t rows = (n + target - 1) / target;
-  rows = (rows + PCA_RC - 1) / PCA_RC * PCA_RC;
-  if (rows < PCA_GRAM_MIN_ROWS) rows = PCA_GRAM_MIN_ROWS;
-  p.gram_rows = rows;
-  p.gram_slabs = (int)((n + rows - 1) / rows);
+  const Gram64Plan g = gram64_plan(n, D, PCA_GRAM_BLOCKS, PCA_GRAM_MIN_ROWS);           // pairs <= 10
+  p.gram_rows = g.rows;
+  p.gram_slabs = g.slabs;
+  p.nb = g.nb;
+  p.pairs = g.pairs;
   return p;
 }
 inline bool pca_shape_ok(int64_t n, int D) {
@@ -97,90 +90,36 @@ __global__ __launch_bounds__(PCA_NTHR) void k_pca_mean(const double* __restrict_
   mean[c] = s / (double)n;
 }
 
-// ---- Gram: grid (block pairs of the upper triangle, slabs)
+// ---- Gram: grid (block pairs of the upper triangle, slabs), the walk of gram64.h.  Staged: x - mean, zeros for the rows
+// past the end and the columns past D; one product per tile.
+struct PcaAcc {
+  gram64_d4 acc[4] = {};
+  double av;
+  __device__ __forceinline__ void row(double a, bool) { av = a; }
+  __device__ __forceinline__ void tile(int j, double bv, bool) {
+    acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[j], 0, 0, 0);
+  }
+};
+
 __global__ __launch_bounds__(PCA_NTHR) void k_pca_gram(const float* __restrict__ X, int64_t n, int D, int64_t ld,
                                                        const double* __restrict__ mean, int64_t rows_per_slab, int nb,
                                                        double* __restrict__ partial) {
-  __shared__ double As[PCA_RC * PCA_LD];
-  __shared__ double Bs[PCA_RC * PCA_LD];
-  int p = (int)blockIdx.x, bi = 0;
-  while (p >= nb - bi) { p -= nb - bi; ++bi; }                  // pair -> (bi, bj), bi <= bj < nb
-  const int bj = bi + p;
-  const bool diag = bi == bj;
-  const int A0 = PCA_BT * bi, B0 = PCA_BT * bj;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int lc = tid & 63, lr = tid >> 6;                       // the loader's column and first row of a chunk
-  const int ca = A0 + lc, cb = B0 + lc;
-  const bool a_in = ca < D, b_in = cb < D;
-  const double mua = a_in ? mean[ca] : 0.0, mub = b_in ? mean[cb] : 0.0;
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per_slab;
-  const int64_t r1 = r0 + rows_per_slab < n ? r0 + rows_per_slab : n;
-  const int kr = lane >> 4, kc = lane & 15;
-  const bool strip = A0 + 16 * w < D;                           // wave-uniform
-  pca_d4 acc[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) acc[j] = pca_d4{0.0, 0.0, 0.0, 0.0};
-  const double* Bp = diag ? As : Bs;
-
-  for (int64_t rc = r0; rc < r1; rc += PCA_RC) {
-    __syncthreads();                                            // the previous chunk has been consumed
-#pragma unroll
-    for (int i = 0; i < PCA_RC / 4; ++i) {
-      const int row = lr + 4 * i;
-      const int64_t r = rc + row;
-      const bool live = r < r1;
-      As[row * PCA_LD + lc] = (live && a_in) ? (double)X[r * ld + ca] - mua : 0.0;
-      if (!diag) Bs[row * PCA_LD + lc] = (live && b_in) ? (double)X[r * ld + cb] - mub : 0.0;
-    }
-    __syncthreads();
-    if (strip) {
-#pragma unroll
-      for (int ks = 0; ks < PCA_RC / 4; ++ks) {
-        const int row = 4 * ks + kr;
-        const double a = As[row * PCA_LD + 16 * w + kc];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (B0 + 16 * j < D && (!diag || j >= w)) {           // wave-uniform
-            const double b = Bp[row * PCA_LD + 16 * j + kc];
-            acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
-          }
-        }
-      }
-    }
-  }
-  if (!strip) return;
+  __shared__ double As[GRAM64_SIDE], Bs[GRAM64_SIDE];
+  const Gram64Tile t(nb, D, n, rows_per_slab);
+  const double mua = t.a_in ? mean[t.ca] : 0.0, mub = t.b_in ? mean[t.cb] : 0.0;
+  PcaAcc acc;
+  gram64_walk(t, D, As, Bs, acc, [=](int64_t r, bool live, double& a, double& b) {
+    a = (live && t.a_in) ? (double)X[r * ld + t.ca] - mua : 0.0;
+    if (!t.diag) b = (live && t.b_in) ? (double)X[r * ld + t.cb] - mub : 0.0;
+  });
   double* __restrict__ out = partial + (size_t)blockIdx.y * (size_t)D * (size_t)D;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (B0 + 16 * j < D && (!diag || j >= w)) {
-      const int b = B0 + 16 * j + kc;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int a = A0 + 16 * w + kr + 4 * g;                 // the f64 MFMA's own C/D map
-        if (a < D && b < D) out[(size_t)a * D + b] = acc[j][g];
-      }
-    }
-  }
+  gram64_store_tiles(t, D, [&](int j, bool) { gram64_put(t, D, j, acc.acc[j], out); });
 }
 
-// element (a, b), a <= b, lies in a computed tile of every slab: summed in slab order and mirrored
 __global__ __launch_bounds__(PCA_NTHR) void k_pca_gram_sum(const double* __restrict__ partial, int slabs, int D,
                                                            double* __restrict__ gram) {
   const int idx = (int)blockIdx.x * PCA_NTHR + threadIdx.x;
-  if (idx >= D * D) return;
-  const int a = idx / D, b = idx % D;
-  if (a > b) return;
-  const size_t dd = (size_t)D * D;
-  const double* __restrict__ src = partial + idx;
-  double s = 0.0;
-  int q = 0;
-  for (; q + 3 < slabs; q += 4) {
-    const double v0 = src[q * dd], v1 = src[(q + 1) * dd], v2 = src[(q + 2) * dd], v3 = src[(q + 3) * dd];
-    s += v0; s += v1; s += v2; s += v3;
-  }
-  for (; q < slabs; ++q) s += src[q * dd];
-  gram[(size_t)a * D + b] = s;
-  gram[(size_t)b * D + a] = s;
+  if (idx < D * D) gram64_sum_cell<4>(partial, (size_t)D * D, slabs, D, idx, true, gram);
 }
 
 // ---- projection: 16 lanes per row, 16 rows per workgroup pass

@@ -2097,6 +2097,21 @@ def _rows_matrix(x: torch.Tensor, name: str):
     return px, n, D, ld
 
 
+def _lab_matrix(X: torch.Tensor, what: str):
+    """An fp32 [patients, labs] matrix whose rows may be strided -> (pointer, n, L, row stride)."""
+    if not torch.is_tensor(X) or X.dim() != 2:
+        raise ValueError(f"{what}: X must be a 2-D tensor [patients, labs]")
+    return _rows_matrix(X, "X")
+
+
+def slab_plan(binding, symbol: str, n: int, n_labs: int):
+    """The slab plan of a satellite's fp64 Gram kernel (csrc/gram64.h) from its host function `symbol`
+    -> (rows per slab, slabs)."""
+    rows, slabs = C.c_int64(0), C.c_int(0)
+    check(getattr(binding.load(), symbol)(int(n), int(n_labs), C.byref(rows), C.byref(slabs)), symbol)
+    return int(rows.value), int(slabs.value)
+
+
 def centered_gram(x: torch.Tensor):
     """Column means and the centred Gram matrix of fp32 [n, D] rows (mmg_centered_gram) -> (mean fp64 [D], S fp64
     [D, D] = sum_i (x_i - mean)(x_i - mean)^T, exactly symmetric), on the device.  Fixed-order fp64 sums: bitwise

@@ -18,27 +18,14 @@ from mmgnn.model import build_model
 from mmgnn.synth import make_graph
 from mmgnn.train import EdgeMasker
 import assoc_ref as ref
+from gram_shapes import DEV, F32, PAD, dv, padded
+import gram_shapes
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-F32 = np.float32
-CH = ao.AS_CHUNK
-PAD = 5                                          # padding columns behind the L labs: ld_x = L + 5
-
-
-def dv(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
 
 
 def row_counts(L):
-    """The n of one lab count, from the slab plan: one row; a chunk minus and plus a row; exactly one slab; a slab and a
-    row; three slabs, the last ragged."""
-    rows, slabs = ao.assoc_plan(1, L)
-    assert slabs == 1 and rows % CH == 0
-    ns = [1, CH - 1, CH + 1, rows, rows + 1, 2 * rows + 77]
-    for n, want in zip(ns, (1, 1, 1, 1, 2, 3)):
-        assert ao.assoc_plan(n, L) == (rows, want), (n, L)
-    return ns
+    return gram_shapes.row_counts(ao.assoc_plan, ao.AS_CHUNK, L)
 
 
 def shapes():
@@ -67,11 +54,8 @@ def case(L, n, lattice):
         center = ref.lattice_center(L, L + n)
     else:
         center = asc.host_colstats(X)[1]
-    buf = np.full((n, L + PAD), np.nan, F32)
-    buf[:, L::2] = F32(1e30)
-    buf[:, :L] = X
     want, ab = ref.moments(X, center)
-    return X, dv(buf)[:, :L], center, want, ab
+    return X, padded(X), center, want, ab
 
 
 # ---------------------------------------------------------------------------------- moments
@@ -165,10 +149,7 @@ def test_colstats(L, n):
     X = ref.make_matrix(n, L, seed=L + n, density=0.6).copy()
     if n > 40:
         X[7, 0], X[11, L - 1], X[n - 1, L // 2] = np.inf, -np.inf, np.inf
-    buf = np.full((n, L + PAD), np.nan, F32)
-    buf[:, L::2] = F32(1e30)
-    buf[:, :L] = X
-    count, mean, n_inf = ao.assoc_colstats(dv(buf)[:, :L])
+    count, mean, n_inf = ao.assoc_colstats(padded(X))
     want_count, s, sa, want_inf = ref.colstats(X)
     assert np.array_equal(count.cpu().numpy(), want_count) and count.dtype == torch.int64
     assert int(n_inf.item()) == want_inf == (3 if n > 40 else 0)

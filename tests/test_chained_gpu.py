@@ -22,44 +22,15 @@ from mmgnn.synth import make_graph
 from mmgnn.train import EdgeMasker
 import assoc_ref
 import chain_ref as ref
+from gram_shapes import DEV, F32, bits, dv, padded
+import gram_shapes
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-F32 = np.float32
-CH = co.CH_CHUNK
-PAD = 5                                          # padding columns behind the L labs: ld_x = L + 5
 LABS = (1, 2, 3, 16, 17, 50, 64, 65, 128)
 
 
-def dv(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
-
-
-def padded(X):
-    """The device copy of X as the [:, :L] view of a buffer whose padding columns hold NaN and 1e30: poison that must
-    never be read."""
-    n, L = X.shape
-    buf = np.full((n, L + PAD), np.nan, F32)
-    buf[:, L::2] = F32(1e30)
-    buf[:, :L] = X
-    view = dv(buf)[:, :L]
-    assert view.stride(0) == L + PAD
-    return view
-
-
-def bits(t):
-    return t.contiguous().view(torch.int64 if t.element_size() == 8 else torch.int32)
-
-
 def row_counts(L):
-    """The n of one lab count, from the slab plan: one row; a chunk minus and plus a row; exactly one slab; a slab and a
-    row; three slabs, the last ragged."""
-    rows, slabs = co.chain_plan(1, L)
-    assert slabs == 1 and rows % CH == 0
-    ns = [1, CH - 1, CH + 1, rows, rows + 1, 2 * rows + 77]
-    for n, want in zip(ns, (1, 1, 1, 1, 2, 3)):
-        assert co.chain_plan(n, L) == (rows, want), (n, L)
-    return ns
+    return gram_shapes.row_counts(co.chain_plan, co.CH_CHUNK, L)
 
 
 def shapes():

@@ -40,6 +40,47 @@ def test_centered_gram_and_means_against_80_bit(n, D, ld):
     assert dg <= bg
 
 
+def _second_slab_at(D):
+    """The first n at which the Gram of D columns takes a second slab, read off the workspace size (the means' slabs are
+    256 rows and longer)."""
+    from mmgnn import _lib
+    ws = _lib.load().mmg_centered_gram_ws_bytes
+    n = 2
+    while ws(n + 1, D) == ws(2, D):
+        n += 1
+    assert n % 32 == 0 and n < 256, "a slab is whole chunks, and shorter than the means' first slab"
+    return n + 1
+
+
+@pytest.mark.parametrize("D, n", [(68, 64), (68, 65), (132, None)])
+def test_lattice_gram_equals_the_loop_reference(D, n):
+    """Multiples of 1/8 (assoc_ref.make_matrix) whose column means are exact: one slab of 64 = 2^6 rows, whose means are
+    multiples of 1/512, and -- 65 rows, a second slab of one row; 132 columns, three blocks with a ragged last one, a
+    slab and a row -- a last row chosen so that every mean IS the lattice centre.  Every difference, product and sum is
+    then exact in fp64 in any order, so the mean and S EQUAL the loop reference, S about the device's returned mean."""
+    import math
+    import assoc_ref
+    n = n or _second_slab_at(D)
+    x = assoc_ref.make_matrix(n, D, seed=D + n, density=1.0, lattice=True, special=False)
+    assert np.all(np.isfinite(x))
+    if n == 64:
+        want_mean = x.astype(np.float64).sum(axis=0) / n
+    else:
+        assert n == _second_slab_at(D) == 65
+        want_mean = assoc_ref.lattice_center(D, D + n)
+        x[-1] = (n * want_mean - x[:-1].astype(np.float64).sum(axis=0)).astype(np.float32)
+        assert np.array_equal(x.astype(np.float64).sum(axis=0), n * want_mean) and np.abs(x).max() < 256
+    mean, gram = ops.centered_gram(torch.from_numpy(x).to(DEV))
+    mean, gram = mean.cpu().numpy(), gram.cpu().numpy()
+    assert np.array_equal(mean, want_mean)
+    u = x.astype(np.float64) - mean[None, :]
+    want = np.zeros((D, D))
+    for a in range(D):
+        for b in range(a, D):
+            want[a, b] = want[b, a] = math.fsum((u[:, a] * u[:, b]).tolist())
+    assert np.array_equal(gram, want), float(np.abs(gram - want).max())
+
+
 def test_non_finite_input_stays_in_its_own_row_and_column():
     """A NaN in column 5 and an inf in column 66 of the (300, 68, 72) case (the second 64-block is 4 columns wide): the
     two columns' means, and rows and columns 5 and 66 of S, are non-finite; every other entry is what the case gives
