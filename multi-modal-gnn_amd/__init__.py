@@ -34,4 +34,7 @@ def __getattr__(name):
     if name in ("BootstrapResult", "bootstrap_metrics", "evaluate_with_intervals", "poisson_weights"):
         from . import bootstrap
         return getattr(bootstrap, name)
+    if name in ("ShiftResult", "two_sample", "split_shift", "residual_shift", "triples_shift"):
+        from . import shift
+        return getattr(shift, name)
     raise AttributeError(name)
