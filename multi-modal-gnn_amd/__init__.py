@@ -37,4 +37,7 @@ def __getattr__(name):
     if name in ("ShiftResult", "two_sample", "split_shift", "residual_shift", "triples_shift"):
         from . import shift
         return getattr(shift, name)
+    if name in ("LabPropensity", "measurement_features", "missingness_report", "ipw_metrics", "IpwMetrics"):
+        from . import missingness
+        return getattr(missingness, name)
     raise AttributeError(name)
