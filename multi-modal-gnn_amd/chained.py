@@ -17,7 +17,7 @@ arithmetic):
 * one step for target ``j`` over ``S_j``, the rows that have lab ``j`` (every active lab, complete ones included):
   ``host_moments`` -> ``host_solve`` -> ``host_apply``.  With ``u = W - center``: ``s_a = sum u_ia``, ``G_ab = sum u_ia
   u_ib`` over ``S_j``; ``C = G - s s^T / n_j``; ``(C[P, P] + alpha I) w = C[P, j]`` over the predictors ``P`` (the
-  active labs but ``j``) by a right-looking Cholesky and two column-oriented substitutions, no fused multiply-add;
+  active labs but ``j``) by the package's one Cholesky solve (``cholesky.host_cholesky_solve``), no fused multiply-add;
   ``mu = s / n_j``; every row outside ``S_j`` gets ``W_ij = clip((center_j + mu_j) + sum_a w_a ((W_ia - center_a) -
   mu_a), lo_j, hi_j)``, the sum over ``P`` ascending from 0.
 * a round is one step per active lab; ``delta`` is the largest ``|new - old|`` of the round.  The fit stops after the
@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from .analysis import _is_dev
+from .cholesky import host_cholesky_solve
 
 MAX_LABS = 128                        # MMG_CH_MAX_LABS
 ORDERS = ("ascending", "descending", "roman", "arabic")
@@ -81,33 +82,19 @@ def host_moments(W, X, j: int, center):
 
 
 def host_solve(G, s, n_j, count, j: int, alpha: float):
-    """The arithmetic of mmg_chain_solve, operation by operation -> (w fp64 [L], mu fp64 [L], pivots not > 0)."""
+    """The arithmetic of mmg_chain_solve, operation by operation -> (w fp64 [L], mu fp64 [L], pivots not > 0): the
+    ridge system over the predictors, then ``host_cholesky_solve``."""
     G, s = np.asarray(G, np.float64), np.asarray(s, np.float64)
-    L = s.size
     P = predictors(count, j)
     m = P.size
     nj = np.float64(int(n_j))
-    bad = 0
     with np.errstate(all="ignore"):
         C = G - (s[:, None] * s[None, :]) / nj
         A = C[np.ix_(P, P)].copy()
         A[np.arange(m), np.arange(m)] = A[np.arange(m), np.arange(m)] + np.float64(alpha)
-        y = C[P, j].copy()
-        d = np.zeros(m)
-        for k in range(m):
-            if not A[k, k] > 0.0:
-                bad += 1
-            d[k] = np.sqrt(A[k, k])
-            A[k + 1:, k] = A[k + 1:, k] / d[k]
-            A[k + 1:, k + 1:] = A[k + 1:, k + 1:] - A[k + 1:, k, None] * A[None, k + 1:, k]
-        for k in range(m):
-            y[k] = y[k] / d[k]
-            y[k + 1:] = y[k + 1:] - A[k + 1:, k] * y[k]
-        for k in range(m - 1, -1, -1):
-            y[k] = y[k] / d[k]
-            y[:k] = y[:k] - A[k, :k] * y[k]
-        w = np.zeros(L)
-        w[P] = y
+        y, bad = host_cholesky_solve(A[None], C[P, j][None])
+        w = np.zeros(s.size)
+        w[P] = y[0]
         mu = s / nj
     return w, mu, bad
 

@@ -8,13 +8,14 @@
 //                 is G; the diagonal block pairs add s as the product with a column of ones, block pair 0 counts n_j.
 //   k_ch_sum      one thread per cell of G (a <= b, written to both halves), of s and of n_j: slabs in ascending order.
 //   k_ch_solve    one workgroup: C = G - s s^T / n_j over the predictors, + alpha, packed lower triangle in LDS (127 x 128
-//                 / 2 doubles = 65,024 bytes), right-looking Cholesky, column-oriented forward and back substitution.
+//                 / 2 doubles = 65,024 bytes), the solve of chol64.h.
 //   k_ch_apply    one thread per row without the target lab: the prediction in ascending predictor order, clipped; the
 //                 block's largest |new - old| to ws.  k_ch_maxfin: one workgroup folds the blocks' maxima into delta.
 //   k_ch_finish   fp32 out: observed cells bit for bit, NaN for a lab nobody has, else (float)W.
-// fp64 contraction is OFF for the whole file: solve and apply restate numpy arithmetic operation by operation.  Built
-// into libmmgnn_chain.so beside libmmgnn.so and on top of it (mmg_set_error).
+// fp64 contraction is OFF for the whole file (chol64.h switches it off for itself): solve and apply restate numpy
+// arithmetic operation by operation.  Built into libmmgnn_chain.so beside libmmgnn.so and on top of it (mmg_set_error).
 #include "common.h"
+#include "chol64.h"
 #include "gram64.h"
 #include "../../include/mmgnn_chain.h"
 #include <limits.h>
@@ -27,7 +28,7 @@ namespace {
 constexpr int CH_NTHR = GRAM64_NTHR;
 constexpr int CH_ML = MMG_CH_MAX_LABS;
 constexpr int CH_SOLVE_NTHR = 512;           // 16 rows x 32 columns of the trailing update at a time
-constexpr int CH_TRI = (CH_ML - 1) * CH_ML / 2;                                   // packed lower triangle, 127 x 127
+constexpr int CH_TRI = chol64_packed_size(CH_ML - 1);                             // packed lower triangle, 127 x 127
 constexpr int CH_SOLVE_LDS = (CH_TRI + 3 * CH_ML) * (int)sizeof(double) + CH_ML * (int)sizeof(int);
 static_assert(MMG_CH_TILE == GRAM64_TILE && MMG_CH_CHUNK == GRAM64_CHUNK, "the header publishes gram64.h's tile and chunk");
 static_assert(MMG_CH_MIN_ROWS % MMG_CH_CHUNK == 0, "a slab is whole chunks");
@@ -111,8 +112,6 @@ __global__ __launch_bounds__(CH_NTHR) void k_ch_sum(const double* __restrict__ p
 }
 
 // ---- the ridge system of one target: one workgroup, the packed lower triangle in LDS
-__device__ __forceinline__ int ch_tri(int i, int l) { return i * (i + 1) / 2 + l; }        // l <= i
-
 __global__ __launch_bounds__(CH_SOLVE_NTHR) void k_ch_solve(const double* __restrict__ G, const double* __restrict__ s,
                                                             const long long* __restrict__ n_j,
                                                             const long long* __restrict__ count, int L, int j,
@@ -142,41 +141,14 @@ __global__ __launch_bounds__(CH_SOLVE_NTHR) void k_ch_solve(const double* __rest
       const int a = pidx[i], b = pidx[l];
       double c = G[(size_t)a * L + b] - (s[a] * s[b]) / nj;
       if (i == l) c = c + alpha;
-      tri[ch_tri(i, l)] = c;
+      tri[chol64_packed()(i, l)] = c;
     }
   }
   if (tid < m) {
     const int a = pidx[tid];
     y[tid] = G[(size_t)a * L + j] - (s[a] * sj) / nj;
   }
-  int nbad = 0;
-  const int ty = tid >> 5, tx = tid & 31;
-  for (int k = 0; k < m; ++k) {
-    __syncthreads();                         // the trailing update of step k - 1 is complete
-    const double piv = tri[ch_tri(k, k)];
-    if (!(piv > 0.0)) ++nbad;
-    const double d = sqrt(piv);
-    if (tid == 0) dg[k] = d;
-    for (int i = k + 1 + tid; i < m; i += CH_SOLVE_NTHR) tri[ch_tri(i, k)] = tri[ch_tri(i, k)] / d;
-    __syncthreads();
-    for (int i = k + 1 + ty; i < m; i += CH_SOLVE_NTHR / 32) {
-      const double aik = tri[ch_tri(i, k)];
-      for (int l = k + 1 + tx; l <= i; l += 32) tri[ch_tri(i, l)] = tri[ch_tri(i, l)] - aik * tri[ch_tri(l, k)];
-    }
-  }
-  for (int k = 0; k < m; ++k) {              // forward: L z = rhs
-    __syncthreads();
-    const double yk = y[k] / dg[k];
-    if (tid == 0) z[k] = yk;
-    for (int i = k + 1 + tid; i < m; i += CH_SOLVE_NTHR) y[i] = y[i] - tri[ch_tri(i, k)] * yk;
-  }
-  for (int k = m - 1; k >= 0; --k) {         // back: L^T y = z
-    __syncthreads();
-    const double wk = z[k] / dg[k];
-    if (tid == 0) y[k] = wk;
-    for (int i = tid; i < k; i += CH_SOLVE_NTHR) z[i] = z[i] - tri[ch_tri(k, i)] * wk;
-  }
-  __syncthreads();
+  const int nbad = chol64_solve<CH_SOLVE_NTHR>(tri, chol64_packed(), m, dg, y, z);
   if (tid < m) w[pidx[tid]] = y[tid];
   for (int a = tid; a < L; a += CH_SOLVE_NTHR) {
     if (a == j || !(count[a] > 0)) w[a] = 0.0;

@@ -289,7 +289,8 @@ __global__ __launch_bounds__(WAVE) void k_mf_segment(const long long* __restrict
     double* __restrict__ no = normal_out + s * (int64_t)(r * r + r);
     for (int x = lane; x < r * r + r; x += WAVE) no[x] = x < r * r ? A[(x / r) * MF_LD + x % r] : bv[x - r * r];
   }
-  // right-looking Cholesky on the lower triangle, then the two column-oriented substitutions (lowrank.host_solve)
+  // the arithmetic of chol64.h (mmgnn/cholesky.py) on the lower triangle, element for element, in a mapping of its own:
+  // every lane takes cells of the whole trailing block, where chol64.h's 32-column rows would leave most of a wave idle
   int nbad = 0;
   for (int k = 0; k < r; ++k) {
     __syncthreads();                                          // the trailing update of step k - 1 is complete

@@ -10,14 +10,16 @@
 //                   block pair too (the weight sits on ONE side), whose tiles below the diagonal are skipped.
 //   k_pr_sum        one thread per cell a <= b: slabs in ascending order; g from row 0, H mirrored.
 //   k_pr_solve      one workgroup per lab: H + diag(1 / C, 0), packed lower triangle in LDS (129 x 130 / 2 doubles =
-//                   67,080 bytes), right-looking Cholesky, column-oriented forward and back substitution, the decrement.
+//                   67,080 bytes), the solve of chol64.h, the decrement.
 //   k_pr_update     one thread per lab: accept or halve, test convergence, freeze, count.
 //   k_pr_pkeys .. k_pr_pall   the weighted error sums over pairs: one stable radix sort by lab (radix_sort.h), the labs'
 //                   bounds and chunk bases by one workgroup, one workgroup per chunk of 256 pairs of one lab (a fixed tree
 //                   in LDS), a lab's chunk sums in ascending order, the labs' sums in ascending order.
-// fp64 contraction is OFF for the whole file: link, solve and update restate numpy arithmetic operation by operation.
+// fp64 contraction is OFF for the whole file (chol64.h switches it off for itself): link, solve and update restate numpy
+// arithmetic operation by operation.
 // Built into libmmgnn_prop.so beside libmmgnn.so and on top of it (mmg_set_error).
 #include "common.h"
+#include "chol64.h"
 #include "gram64.h"
 #include "radix_sort.h"
 #include "../../include/mmgnn_prop.h"
@@ -34,7 +36,7 @@ constexpr int PR_MM = PR_MD + 1;                                                
 constexpr int PR_ROWS = MMG_PR_LINK_ROWS;
 constexpr int PR_XLD = PR_MD + 1;                                                 // odd: a lane per row, no bank conflict
 constexpr int PR_SOLVE_NTHR = 512;           // 16 rows x 32 columns of the trailing update at a time
-constexpr int PR_TRI = PR_MM * (PR_MM + 1) / 2;
+constexpr int PR_TRI = chol64_packed_size(PR_MM);
 constexpr int PR_SOLVE_LDS = (PR_TRI + 4 * PR_MM) * (int)sizeof(double);
 static_assert(MMG_PR_TILE == GRAM64_TILE && MMG_PR_CHUNK == GRAM64_CHUNK, "the header publishes gram64.h's tile and chunk");
 static_assert(MMG_PR_MIN_ROWS % MMG_PR_CHUNK == 0, "a slab is whole chunks");
@@ -197,8 +199,6 @@ __global__ __launch_bounds__(PR_NTHR) void k_pr_sum(const double* __restrict__ p
 }
 
 // ---- the Newton system of one lab: one workgroup, the packed lower triangle in LDS
-__device__ __forceinline__ int pr_tri(int i, int l) { return i * (i + 1) / 2 + l; }        // l <= i
-
 __global__ __launch_bounds__(PR_SOLVE_NTHR) void k_pr_solve(const double* __restrict__ H, const double* __restrict__ g,
                                                             const double* __restrict__ trial, int D, int j0, double C,
                                                             int* __restrict__ state, double* __restrict__ delta,
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(PR_SOLVE_NTHR) void k_pr_solve(const double* __rest
     if (l <= i) {
       double c = Hk[(size_t)i * m + l];
       if (i == l && i < D) c = c + ridge;
-      tri[pr_tri(i, l)] = c;
+      tri[chol64_packed()(i, l)] = c;
     }
   }
   if (tid < m) {
@@ -228,34 +228,7 @@ __global__ __launch_bounds__(PR_SOLVE_NTHR) void k_pr_solve(const double* __rest
     y[tid] = v;
     rhs[tid] = v;
   }
-  int nbad = 0;
-  const int ty = tid >> 5, tx = tid & 31;
-  for (int c = 0; c < m; ++c) {
-    __syncthreads();                         // the trailing update of step c - 1 is complete
-    const double piv = tri[pr_tri(c, c)];
-    if (!(piv > 0.0)) ++nbad;
-    const double d = sqrt(piv);
-    if (tid == 0) dg[c] = d;
-    for (int i = c + 1 + tid; i < m; i += PR_SOLVE_NTHR) tri[pr_tri(i, c)] = tri[pr_tri(i, c)] / d;
-    __syncthreads();
-    for (int i = c + 1 + ty; i < m; i += PR_SOLVE_NTHR / 32) {
-      const double aic = tri[pr_tri(i, c)];
-      for (int l = c + 1 + tx; l <= i; l += 32) tri[pr_tri(i, l)] = tri[pr_tri(i, l)] - aic * tri[pr_tri(l, c)];
-    }
-  }
-  for (int c = 0; c < m; ++c) {              // forward: L z = rhs
-    __syncthreads();
-    const double yc = y[c] / dg[c];
-    if (tid == 0) z[c] = yc;
-    for (int i = c + 1 + tid; i < m; i += PR_SOLVE_NTHR) y[i] = y[i] - tri[pr_tri(i, c)] * yc;
-  }
-  for (int c = m - 1; c >= 0; --c) {         // back: L^T y = z
-    __syncthreads();
-    const double wc = z[c] / dg[c];
-    if (tid == 0) y[c] = wc;
-    for (int i = tid; i < c; i += PR_SOLVE_NTHR) z[i] = z[i] - tri[pr_tri(c, i)] * wc;
-  }
-  __syncthreads();
+  const int nbad = chol64_solve<PR_SOLVE_NTHR>(tri, chol64_packed(), m, dg, y, z);
   if (tid < m) delta[(size_t)k * m + tid] = y[tid];
   if (tid == 0) {
     double v = 0.0;

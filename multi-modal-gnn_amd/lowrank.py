@@ -15,7 +15,7 @@ Definitions (this module's numpy functions are the definition; ``tests/mf_ref.py
   ascending, each with row pointers.
 * one half-sweep (``host_half_sweep``) solves for every segment ``s`` of one ordering, with ``F`` the factors of the
   other side, ``A_s = sum f f^T + reg I``, ``b_s = sum f y``, ``x_s = A_s^{-1} b_s`` (``host_normal``, ``host_solve``:
-  the right-looking Cholesky and the two substitutions of ``chained.host_solve``, operation by operation, no fused
+  the package's one Cholesky solve, ``cholesky.host_cholesky_solve``, operation by operation, no fused
   multiply-add).  An empty segment gets the zero vector; a pivot that is not ``> 0`` is counted.  The patient side and
   the lab side are the same computation.
 * a round is the patient half-sweep, then the lab half-sweep, then the objective (``host_objective``: the squared
@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from .analysis import _is_dev
+from .cholesky import host_cholesky_solve
 
 MAX_LABS = 2048                       # MMG_MF_MAX_LABS
 MAX_RANK = 32                         # MMG_MF_MAX_RANK
@@ -86,26 +87,9 @@ def host_normal(ptr, idx, y, other, reg: float):
 
 
 def host_solve(A, b):
-    """x = A^{-1} b for every system of A [S, r, r], b [S, r]: the arithmetic of mmg_mf_half_sweep's solve (and of
-    ``chained.host_solve``), operation by operation -> (x fp64 [S, r], pivots not > 0).  Rounding: a backward-stable
-    Cholesky solve, |A x - b| <= 8 r^2 2^-53 |A| |x| to first order."""
-    A, y = np.array(A, np.float64), np.array(b, np.float64)
-    S, r = y.shape
-    d = np.zeros((S, r))
-    bad = 0
-    with np.errstate(all="ignore"):
-        for k in range(r):
-            bad += int((~(A[:, k, k] > 0.0)).sum())
-            d[:, k] = np.sqrt(A[:, k, k])
-            A[:, k + 1:, k] = A[:, k + 1:, k] / d[:, k, None]
-            A[:, k + 1:, k + 1:] = A[:, k + 1:, k + 1:] - A[:, k + 1:, k, None] * A[:, None, k + 1:, k]
-        for k in range(r):
-            y[:, k] = y[:, k] / d[:, k]
-            y[:, k + 1:] = y[:, k + 1:] - A[:, k + 1:, k] * y[:, k, None]
-        for k in range(r - 1, -1, -1):
-            y[:, k] = y[:, k] / d[:, k]
-            y[:, :k] = y[:, :k] - A[:, k, :k] * y[:, k, None]
-    return y, bad
+    """x = A^{-1} b for every system of A [S, r, r], b [S, r]: the arithmetic of mmg_mf_half_sweep's solve, operation
+    by operation (``host_cholesky_solve``) -> (x fp64 [S, r], pivots not > 0)."""
+    return host_cholesky_solve(A, b)
 
 
 def host_half_sweep(ptr, idx, y, other, reg: float):

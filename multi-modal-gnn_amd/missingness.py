@@ -41,6 +41,7 @@ import pandas as pd
 import torch
 
 from .analysis import _is_dev
+from .cholesky import host_cholesky_solve
 
 MAX_FEATURES = 128                    # MMG_PR_MAX_FEATURES
 MAX_LABS = 512                        # MMG_PR_MAX_LABS
@@ -99,33 +100,19 @@ def host_moments(X, mean, s, r):
 
 
 def host_solve(H, g, trial, C: float):
-    """The arithmetic of mmg_prop_solve, operation by operation -> (delta fp64 [M], decrement, pivots not > 0)."""
+    """The arithmetic of mmg_prop_solve, operation by operation -> (delta fp64 [M], decrement, pivots not > 0): the
+    Newton system, ``host_cholesky_solve``, then the decrement in ascending order."""
     A = np.array(H, np.float64)
-    m = A.shape[0]
-    D = m - 1
+    D = A.shape[0] - 1
     C = np.float64(C)
-    bad = 0
     with np.errstate(all="ignore"):
         idx = np.arange(D)
         A[idx, idx] = A[idx, idx] + np.float64(1.0) / C
-        y = np.array(g, np.float64)
-        y[:D] = y[:D] + np.asarray(trial, np.float64)[:D] / C
-        rhs = y.copy()
-        d = np.zeros(m)
-        for k in range(m):
-            if not A[k, k] > 0.0:
-                bad += 1
-            d[k] = np.sqrt(A[k, k])
-            A[k + 1:, k] = A[k + 1:, k] / d[k]
-            A[k + 1:, k + 1:] = A[k + 1:, k + 1:] - A[k + 1:, k, None] * A[None, k + 1:, k]
-        for k in range(m):
-            y[k] = y[k] / d[k]
-            y[k + 1:] = y[k + 1:] - A[k + 1:, k] * y[k]
-        for k in range(m - 1, -1, -1):
-            y[k] = y[k] / d[k]
-            y[:k] = y[:k] - A[k, :k] * y[k]
-        dec = serial_sum(rhs * y)
-    return y, dec, bad
+        rhs = np.array(g, np.float64)
+        rhs[:D] = rhs[:D] + np.asarray(trial, np.float64)[:D] / C
+        y, bad = host_cholesky_solve(A[None], rhs[None])
+        dec = serial_sum(rhs * y[0])
+    return y[0], dec, bad
 
 
 def host_update(loss_blocks, delta, dec, C: float, threshold: float, max_iter: int, beta, trial, step, fstate, state):
