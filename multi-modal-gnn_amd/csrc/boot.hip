@@ -2,21 +2,20 @@
 // weighted updates of the seven (ten, with a second predictor) additive terms of mmg_seg_metrics, the metrics of every
 // replicate, and their summary (mean, standard error, percentile interval).
 //   k_boot_keys     ONE read of the indices: sort key = the segment (n_seg for a dropped pair: sorts last), payload = the
-//                   pair's position, the unit as uint32, the three kinds of dropped pairs (integer counts: per-wave sums,
-//                   one integer atomic per wave and kind).
-//   radix_pass      the stable LSD sort of radix_sort.h over the 1-2 digits of the segment.
+//                   pair's position, the unit as uint32, the three kinds of dropped pairs (drop_flush of segsort.h).
+//   segsort_run     the stable sort of segsort.h over the 1-2 digits of the segment.
 //   k_boot_sums     workgroup (c, y) walks chunk c (BT_CHUNK consecutive sorted pairs) for the BT_RB replicates
 //                   y * BT_RB + thread: tiles of BT_TILE pairs are gathered into LDS once (terms formed in fp32 / fp64 as
 //                   k_seg_metrics forms them), then every thread walks the tile -- all threads read the same LDS word
 //                   (broadcast), hash once per pair, count the thresholds, and add weight * term to registers.  Every
 //                   thread of the workgroup sees the same segment boundaries: no divergence.  A tile whose first and last
 //                   key agree (sorted keys: one segment) is walked unrolled, without reading the keys -- the same
-//                   additions in the same order.  At a boundary the registers
-//                   go to the chunk's HEAD slot (the chunk's first segment), straight to `sums` (a segment that begins and
-//                   ends inside the chunk, first excepted) or, at the end of the chunk, to its TAIL slot.
-//   k_boot_combine  one thread per (segment, replicate): the segment's chunks' slots added in chunk order; a segment
-//                   without pairs gets zeros; a segment k_boot_sums wrote itself is left alone.  Every element of `sums`
-//                   is written exactly once: nothing is zero-filled, nothing is accumulated in memory.
+//                   additions in the same order.  At a boundary the registers go to the chunk's HEAD slot, straight to
+//                   `sums` or to the chunk's TAIL slot: the chunk protocol stated at SegChunks (segsort.h).
+//   k_boot_combine  one thread per (segment, replicate): the segment's bounds and the number of kept pairs by three binary
+//                   searches, then SegChunks: the segment's chunks' slots added in chunk order; a segment without pairs
+//                   gets zeros; a segment k_boot_sums wrote itself is left alone.  Every element of `sums` is written
+//                   exactly once: nothing is zero-filled, nothing is accumulated in memory.
 //   k_boot_metrics  one thread per (replicate, row).   k_boot_summary  one workgroup per (row, metric): sums in a fixed
 //                   order, a bitonic sort of up to 4096 doubles in LDS, numpy's "linear" percentile.
 // fp64 contraction is OFF for the whole file (the metric rules and the percentile restate Python arithmetic operation by
@@ -79,11 +78,7 @@ __global__ __launch_bounds__(BT_NTHR) void k_boot_keys(const float* __restrict__
     id[i] = (int32_t)i;
     unit32[i] = kind < 0 ? (uint32_t)u : 0u;
   }
-#pragma unroll
-  for (int k = 0; k < MMG_BOOT_DROP_KINDS; ++k) {
-    const int t = wave_sum_i(cnt[k]);
-    if ((threadIdx.x & 63) == 0 && t) atomicAdd(dropped + k, (unsigned long long)t);
-  }
+  drop_flush(cnt, dropped);
 }
 
 // ---------------------------------------------------------------------------------- sums
@@ -160,7 +155,7 @@ __global__ __launch_bounds__(BT_NTHR) void k_boot_sums(const uint32_t* __restric
     __syncthreads();
     if (base == begin) first = s_seg[0];
     auto flush_to = [&](uint32_t s) {                                // the open segment ends in front of a pair of s
-      if (cur < (uint32_t)n_seg && live)
+      if (cur < (uint32_t)n_seg && live)                             // HEAD slot or direct: the protocol at SegChunks
         acc.store(cur == first ? part + bt_slot(c, 0, r, R1, F) : sums + ((size_t)r * n_seg + cur) * F);
       acc.clear();
       cur = s;
@@ -207,27 +202,20 @@ template <int F>
 __global__ __launch_bounds__(BT_NTHR) void k_boot_combine(const uint32_t* __restrict__ K, int64_t n, int n_seg,
                                                           int replicates, const double* __restrict__ part,
                                                           double* __restrict__ sums) {
-  __shared__ int64_t s_b[2];
-  __shared__ int s_skip;
+  __shared__ int64_t s_b[3];                                         // the segment's bounds and the number of kept pairs
   const int R1 = replicates + 1;
   const uint32_t s = blockIdx.x;
-  if (threadIdx.x < 2) s_b[threadIdx.x] = lower_bound(K, n, s + threadIdx.x);
+  if (threadIdx.x < 3) s_b[threadIdx.x] = lower_bound(K, n, threadIdx.x < 2 ? s + threadIdx.x : (uint32_t)n_seg);
   __syncthreads();
-  const int64_t lo = s_b[0], hi = s_b[1];
-  const int64_t c0 = lo / BT_CHUNK, c1 = hi > lo ? (hi - 1) / BT_CHUNK : c0;
-  if (threadIdx.x == 0) {
-    // written by k_boot_sums itself: inside one chunk, not its first segment, and a kept pair of the chunk follows it
-    s_skip = hi > lo && c0 == c1 && K[c0 * BT_CHUNK] != s && hi < n && hi < (c0 + 1) * BT_CHUNK && K[hi] < (uint32_t)n_seg;
-  }
-  __syncthreads();
-  if (s_skip) return;
+  const SegChunks<BT_CHUNK> ch(s_b[0], s_b[1], s_b[2]);
+  if (ch.written_by_walk()) return;                                  // the whole workgroup
   for (int r = blockIdx.y * BT_NTHR + threadIdx.x; r < R1; r += gridDim.y * BT_NTHR) {
     double a[F];
 #pragma unroll
     for (int f = 0; f < F; ++f) a[f] = 0.0;
-    if (hi > lo)
-      for (int64_t c = c0; c <= c1; ++c) {
-        const double* __restrict__ src = part + bt_slot(c, K[c * BT_CHUNK] == s ? 0 : 1, r, R1, F);
+    if (!ch.empty())
+      for (int64_t c = ch.c0; c <= ch.c1; ++c) {
+        const double* __restrict__ src = part + bt_slot(c, ch.which(c), r, R1, F);
 #pragma unroll
         for (int f = 0; f < F; ++f) a[f] += src[f];
       }
@@ -402,22 +390,15 @@ __global__ __launch_bounds__(BT_NTHR) void k_boot_summary(const double* __restri
 }
 
 struct BootWs {
-  RadixPairs<uint32_t> kv;
-  uint32_t *hist, *scr, *unit32;
+  SegSortWs<uint32_t> sort;
+  uint32_t* unit32;
   double* part;
 };
 inline int64_t bt_chunks(int64_t n) { return n > 0 ? (n + BT_CHUNK - 1) / BT_CHUNK : 1; }
 size_t boot_carve(void* ws, int64_t n, int replicates, int F, BootWs* w) {
   MmgCarver c(ws);
-  const RadixSizes rs = radix_sizes(n);
-  const size_t nn = (size_t)(n > 0 ? n : 1);
-  w->kv.keys = c.take<uint32_t>(nn);
-  w->kv.keys_alt = c.take<uint32_t>(nn);
-  w->kv.vals = c.take<int32_t>(nn);
-  w->kv.vals_alt = c.take<int32_t>(nn);
-  w->hist = c.take<uint32_t>(rs.hist_elems);
-  w->scr = c.take<uint32_t>(rs.scratch_elems);
-  w->unit32 = c.take<uint32_t>(nn);
+  segsort_carve(c, n, &w->sort);
+  w->unit32 = c.take<uint32_t>((size_t)(n > 0 ? n : 1));
   w->part = c.take<double>((size_t)bt_chunks(n) * 2 * (size_t)(replicates + 1) * F);
   return c.need();
 }
@@ -455,37 +436,35 @@ extern "C" int mmg_boot_sums(const float* pred, const float* target, const float
   const int F = with_b ? MMG_BOOT_FIELDS_B : MMG_BOOT_FIELDS;
   BootWs w;
   MMG_CHECK_WS("boot_sums", boot_carve(ws, n, replicates, F, &w));
+  const RadixPairs<uint32_t>& kv = w.sort.kv;       // the sort leaves its result here
   hipStream_t st = (hipStream_t)stream;
   MMG_CHECK_HIP(mmg_zero_async(dropped, MMG_BOOT_DROP_KINDS * sizeof(int64_t), st), "boot_sums(zero)");
   const unsigned rblocks = (unsigned)((replicates + 1 + BT_RB - 1) / BT_RB);
   if (n > 0) {
-    if (index_bytes == 8)
-      hipLaunchKernelGGL(k_boot_keys<int64_t>, dim3(launch_grid(n, BT_NTHR, BT_MAX_GRID)), dim3(BT_NTHR), 0, st, pred,
-                         target, pred_b, (const int64_t*)unit, (const int64_t*)seg, n, n_units, n_seg, w.kv.keys, w.kv.vals,
-                         w.unit32, (unsigned long long*)dropped);
-    else
-      hipLaunchKernelGGL(k_boot_keys<int32_t>, dim3(launch_grid(n, BT_NTHR, BT_MAX_GRID)), dim3(BT_NTHR), 0, st, pred,
-                         target, pred_b, (const int32_t*)unit, (const int32_t*)seg, n, n_units, n_seg, w.kv.keys, w.kv.vals,
-                         w.unit32, (unsigned long long*)dropped);
+    index_dispatch(index_bytes, [&](auto it) {
+      using IT = decltype(it);
+      hipLaunchKernelGGL(k_boot_keys<IT>, dim3(launch_grid(n, BT_NTHR, BT_MAX_GRID)), dim3(BT_NTHR), 0, st, pred, target,
+                         pred_b, (const IT*)unit, (const IT*)seg, n, n_units, n_seg, kv.keys, kv.vals, w.unit32,
+                         (unsigned long long*)dropped);
+    });
     MMG_CHECK_LAUNCH("boot_sums(keys)");
-    const int passes = (bits_of((unsigned)n_seg) + 7) / 8;               // the key reaches n_seg itself
-    for (int ps = 0; ps < passes; ++ps) radix_pass<false>(w.kv, n, 8 * ps, nullptr, w.hist, w.scr, st);
+    segsort_run(w.sort, n, bits_of((unsigned)n_seg), st);                // the key reaches n_seg itself
     MMG_CHECK_LAUNCH("boot_sums(sort)");
     const dim3 grid((unsigned)bt_chunks(n), rblocks);
     if (with_b)
-      hipLaunchKernelGGL(k_boot_sums<true>, grid, dim3(BT_NTHR), 0, st, w.kv.keys, w.kv.vals, w.unit32, n, n_seg, pred,
-                         target, pred_b, replicates, seed, w.part, sums);
+      hipLaunchKernelGGL(k_boot_sums<true>, grid, dim3(BT_NTHR), 0, st, kv.keys, kv.vals, w.unit32, n, n_seg, pred, target,
+                         pred_b, replicates, seed, w.part, sums);
     else
-      hipLaunchKernelGGL(k_boot_sums<false>, grid, dim3(BT_NTHR), 0, st, w.kv.keys, w.kv.vals, w.unit32, n, n_seg, pred,
-                         target, pred_b, replicates, seed, w.part, sums);
+      hipLaunchKernelGGL(k_boot_sums<false>, grid, dim3(BT_NTHR), 0, st, kv.keys, kv.vals, w.unit32, n, n_seg, pred, target,
+                         pred_b, replicates, seed, w.part, sums);
     MMG_CHECK_LAUNCH("boot_sums(chunks)");
   }
   const dim3 grid((unsigned)n_seg, rblocks);
   if (with_b)
-    hipLaunchKernelGGL(k_boot_combine<MMG_BOOT_FIELDS_B>, grid, dim3(BT_NTHR), 0, st, w.kv.keys, n, n_seg, replicates,
-                       w.part, sums);
+    hipLaunchKernelGGL(k_boot_combine<MMG_BOOT_FIELDS_B>, grid, dim3(BT_NTHR), 0, st, kv.keys, n, n_seg, replicates, w.part,
+                       sums);
   else
-    hipLaunchKernelGGL(k_boot_combine<MMG_BOOT_FIELDS>, grid, dim3(BT_NTHR), 0, st, w.kv.keys, n, n_seg, replicates, w.part,
+    hipLaunchKernelGGL(k_boot_combine<MMG_BOOT_FIELDS>, grid, dim3(BT_NTHR), 0, st, kv.keys, n, n_seg, replicates, w.part,
                        sums);
   MMG_CHECK_LAUNCH("boot_sums(combine)");
   return MMG_OK;

@@ -1,34 +1,12 @@
-// What conformal.hip, stack.hip and boot.hip share around a sorted list of (patient, lab) pairs: the launch grid, the
-// binary search of a segment's bounds, the bounds-checked index load, the degree bins and the cell of a pair (lab x
-// degree bin: the cells of include/mmgnn_conformal.h), and the host check of a call that names cells.  Only for the
+// What conformal.hip, stack.hip and boot.hip share around the cells of a (patient, lab) pair: the bounds-checked index
+// load, the degree bins and the cell of a pair (lab x degree bin: the cells of include/mmgnn_conformal.h), and the host
+// check of a call that names cells.  The sorted pair list itself is segsort.h, which this header includes.  Only for the
 // satellite libraries: no source of libmmgnn.so includes it.
 #pragma once
 #include "common.h"
+#include "segsort.h"
 #include "../../include/mmgnn_conformal.h"
 #include <limits.h>
-
-inline int bits_of(unsigned v) {         // bits needed to write v
-  int b = 0;
-  while (v) { ++b; v >>= 1; }
-  return b;
-}
-// workgroups of `threads` for n items, per_thread items to a thread, at most max_grid (the kernels stride by the grid)
-inline unsigned launch_grid(int64_t n, int threads, int max_grid, int per_thread = 4) {
-  int64_t g = (n + (int64_t)threads * per_thread - 1) / ((int64_t)threads * per_thread);
-  return (unsigned)(g < 1 ? 1 : g > max_grid ? max_grid : g);
-}
-
-// first position in the ascending K [0, n) whose key is >= v
-template <class KT>
-__device__ __forceinline__ int64_t lower_bound(const KT* __restrict__ K, int64_t n, KT v) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (K[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // p[i] as an index below limit; -1 for one outside [0, limit)
 template <class IT>

@@ -1,10 +1,10 @@
 // Split-conformal prediction intervals for imputed labs (include/mmgnn_conformal.h; mmgnn/conformal.py): exact order
 // statistics of the residuals per (lab, degree bin) cell, per lab and over all pairs, the table that takes the first
 // usable of the three, and the epilogues that turn predictions into (point, lower, upper) and count their coverage.
-//   k_sos_keys        key = (segment << 32) | orderable(fp32 bits); rows of no segment (and NaN keys) go under segment
+//   k_sos_keys        key = (segment << 32) | float_orderable (segsort.h); rows of no segment (and NaN keys) go under segment
 //                     n_seg and sort last.  The lab and the all-pairs level of a fit are the cell ids divided by n_bins
 //                     and by n_cells: one array of cell ids serves the three sorts.
-//   radix_pass        the stable LSD sort of radix_sort.h over the 4 key digits and the 1-2 segment digits that can
+//   segsort_run       the stable sort of segsort.h over the 4 key digits and the 1-2 segment digits that can
 //                     differ (the host knows n_seg: the digits above it are never sorted).  The int32 payload the sort
 //                     carries is not used here and is never initialised.
 //   k_sos_pick        one thread per segment: two binary searches for its bounds in the sorted keys, the fp64 rank
@@ -45,14 +45,8 @@ struct CfRanks {
   long long min_count;
 };
 
-__device__ __forceinline__ uint32_t cf_orderable(float x) {
-  const uint32_t u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float cf_key_value(unsigned long long k) {
-  const uint32_t o = (uint32_t)k;
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
+// the fp32 value in the low half of a sort key
+__device__ __forceinline__ float cf_key_value(unsigned long long k) { return orderable_float((uint32_t)k); }
 
 // ---------------------------------------------------------------------------------- segmented order statistics
 __global__ __launch_bounds__(CF_NTHR) void k_sos_keys(const float* __restrict__ keys, const int32_t* __restrict__ seg,
@@ -64,7 +58,7 @@ __global__ __launch_bounds__(CF_NTHR) void k_sos_keys(const float* __restrict__ 
     const int s = seg[i];
     const bool ok = s >= 0 && s < n_seg_in && x == x;
     const uint32_t se = ok ? (uint32_t)(s / div) : (uint32_t)n_seg;
-    out[i] = ((unsigned long long)se << 32) | (unsigned long long)(ok ? cf_orderable(x) : 0u);
+    out[i] = ((unsigned long long)se << 32) | (unsigned long long)(ok ? float_orderable(x) : 0u);
   }
 }
 
@@ -107,19 +101,9 @@ __global__ __launch_bounds__(CF_NTHR) void k_sos_pick(const unsigned long long* 
   usable[s] = (ok && m >= rk.min_count) ? 1 : 0;
 }
 
-struct SosWs {
-  RadixPairs<unsigned long long> kv;
-  uint32_t *hist, *scr;
-};
+using SosWs = SegSortWs<unsigned long long>;
 size_t sos_carve(MmgCarver& c, int64_t n, SosWs* w) {
-  const RadixSizes rs = radix_sizes(n);
-  const size_t nn = (size_t)(n > 0 ? n : 1);
-  w->kv.keys = c.take<unsigned long long>(nn);
-  w->kv.keys_alt = c.take<unsigned long long>(nn);
-  w->kv.vals = c.take<int32_t>(nn);
-  w->kv.vals_alt = c.take<int32_t>(nn);
-  w->hist = c.take<uint32_t>(rs.hist_elems);
-  w->scr = c.take<uint32_t>(rs.scratch_elems);
+  segsort_carve(c, n, w);
   return c.need();
 }
 
@@ -138,8 +122,7 @@ int sos_run(const char* what, const float* keys, const int32_t* seg, int64_t n, 
     hipLaunchKernelGGL(k_sos_keys, dim3(launch_grid(n, CF_NTHR, CF_MAX_GRID)), dim3(CF_NTHR), 0, st, keys, seg, n, n_seg_in,
                        div, n_seg, w.kv.keys);
     MMG_CHECK_LAUNCH(what);
-    const int passes = 4 + (bits_of((unsigned)n_seg) + 7) / 8;          // segment values reach n_seg itself
-    for (int ps = 0; ps < passes; ++ps) radix_pass<false>(w.kv, n, 8 * ps, nullptr, w.hist, w.scr, st);
+    segsort_run(w, n, 32 + bits_of((unsigned)n_seg), st);              // segment values reach n_seg itself
     MMG_CHECK_LAUNCH(what);
   }
   hipLaunchKernelGGL(k_sos_pick, dim3((n_seg + CF_NTHR - 1) / CF_NTHR), dim3(CF_NTHR), 0, st, w.kv.keys, n, n_seg, rk,
@@ -429,20 +412,10 @@ __global__ __launch_bounds__(CF_NTHR) void k_cf_cov_cells(const uint32_t* __rest
   }
 }
 
-struct CovWs {
-  RadixPairs<uint32_t> kv;
-  uint32_t *hist, *scr;
-};
+using CovWs = SegSortWs<uint32_t>;
 size_t cov_carve(void* ws, int64_t n, CovWs* w) {
   MmgCarver c(ws);
-  const RadixSizes rs = radix_sizes(n);
-  const size_t nn = (size_t)(n > 0 ? n : 1);
-  w->kv.keys = c.take<uint32_t>(nn);
-  w->kv.keys_alt = c.take<uint32_t>(nn);
-  w->kv.vals = c.take<int32_t>(nn);
-  w->kv.vals_alt = c.take<int32_t>(nn);
-  w->hist = c.take<uint32_t>(rs.hist_elems);
-  w->scr = c.take<uint32_t>(rs.scratch_elems);
+  segsort_carve(c, n, w);
   return c.need();
 }
 
@@ -503,14 +476,12 @@ extern "C" int mmg_cf_fit(const float* pred, const float* target, const void* pa
   const int n_cells = n_labs * n_bins;
   MMG_CHECK_HIP(mmg_zero_async(dropped, MMG_CF_DROP_KINDS * sizeof(int64_t), st), "cf_fit(zero)");
   if (n > 0) {
-    if (index_bytes == 8)
-      hipLaunchKernelGGL(k_cf_prepare<int64_t>, dim3(launch_grid(n, CF_NTHR, CF_MAX_GRID)), dim3(CF_NTHR), 0, st, pred,
-                         target, (const int64_t*)patient, (const int64_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, mode,
-                         w.key, w.cell, (unsigned long long*)dropped);
-    else
-      hipLaunchKernelGGL(k_cf_prepare<int32_t>, dim3(launch_grid(n, CF_NTHR, CF_MAX_GRID)), dim3(CF_NTHR), 0, st, pred,
-                         target, (const int32_t*)patient, (const int32_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, mode,
-                         w.key, w.cell, (unsigned long long*)dropped);
+    index_dispatch(index_bytes, [&](auto it) {
+      using IT = decltype(it);
+      hipLaunchKernelGGL(k_cf_prepare<IT>, dim3(launch_grid(n, CF_NTHR, CF_MAX_GRID)), dim3(CF_NTHR), 0, st, pred, target,
+                         (const IT*)patient, (const IT*)lab, n, n_labs, deg, n_patients, n_bins, ed, mode, w.key, w.cell,
+                         (unsigned long long*)dropped);
+    });
     MMG_CHECK_LAUNCH("cf_fit(prepare)");
   }
   const int divs[3] = {1, n_bins, n_cells};
@@ -541,17 +512,15 @@ extern "C" int mmg_cf_apply_pairs(const float* pred, const void* patient, const 
   const size_t lds_bytes = lds ? (size_t)3 * n_cells * sizeof(float) : 0;
   // a workgroup that stages the table takes at least 8 pairs per thread
   const dim3 grid(launch_grid(n, CF_NTHR, CF_MAX_GRID, lds ? 8 : 4)), block(CF_NTHR);
-#define CF_APPLY_PAIRS(IT, LDS_)                                                                                          \
+  index_dispatch(index_bytes, [&](auto it) {
+    using IT = decltype(it);
+#define CF_APPLY_PAIRS(LDS_)                                                                                              \
   hipLaunchKernelGGL((k_cf_apply_pairs<IT, LDS_>), grid, block, lds_bytes, st, pred, (const IT*)patient, (const IT*)lab, n, \
                      n_labs, deg, n_patients, n_bins, ed, table, use_shift, point, lower, upper)
-  if (index_bytes == 8) {
-    if (lds) CF_APPLY_PAIRS(int64_t, true);
-    else CF_APPLY_PAIRS(int64_t, false);
-  } else {
-    if (lds) CF_APPLY_PAIRS(int32_t, true);
-    else CF_APPLY_PAIRS(int32_t, false);
-  }
+    if (lds) CF_APPLY_PAIRS(true);
+    else CF_APPLY_PAIRS(false);
 #undef CF_APPLY_PAIRS
+  });
   MMG_CHECK_LAUNCH("cf_apply_pairs");
   return MMG_OK;
 }
@@ -596,8 +565,10 @@ extern "C" int mmg_cf_apply_matrix(const float* pred, int64_t n_rows, int n_labs
     else if (vec == 2) CF_APPLY_MATRIX_VEC(IT, 2); \
     else CF_APPLY_MATRIX_VEC(IT, 1);           \
   } while (0)
-  if (rows && index_bytes == 4) CF_APPLY_MATRIX_IT(int32_t);
-  else CF_APPLY_MATRIX_IT(int64_t);
+  index_dispatch(rows ? index_bytes : 8, [&](auto it) {           // no row list: the int64 instance, which never reads it
+    using IT = decltype(it);
+    CF_APPLY_MATRIX_IT(IT);
+  });
 #undef CF_APPLY_MATRIX_IT
 #undef CF_APPLY_MATRIX_VEC
 #undef CF_APPLY_MATRIX
@@ -625,17 +596,13 @@ extern "C" int mmg_cf_coverage(const float* pred, const float* target, const voi
   hipStream_t st = (hipStream_t)stream;
   const int n_cells = n_labs * n_bins;
   if (n > 0) {
-    if (index_bytes == 8)
-      hipLaunchKernelGGL(k_cf_cov_keys<int64_t>, dim3(launch_grid(n, CF_NTHR, CF_MAX_GRID)), dim3(CF_NTHR), 0, st,
-                         (const int64_t*)patient, (const int64_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, w.kv.keys,
-                         w.kv.vals);
-    else
-      hipLaunchKernelGGL(k_cf_cov_keys<int32_t>, dim3(launch_grid(n, CF_NTHR, CF_MAX_GRID)), dim3(CF_NTHR), 0, st,
-                         (const int32_t*)patient, (const int32_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, w.kv.keys,
-                         w.kv.vals);
+    index_dispatch(index_bytes, [&](auto it) {
+      using IT = decltype(it);
+      hipLaunchKernelGGL(k_cf_cov_keys<IT>, dim3(launch_grid(n, CF_NTHR, CF_MAX_GRID)), dim3(CF_NTHR), 0, st,
+                         (const IT*)patient, (const IT*)lab, n, n_labs, deg, n_patients, n_bins, ed, w.kv.keys, w.kv.vals);
+    });
     MMG_CHECK_LAUNCH("cf_coverage(keys)");
-    const int passes = (bits_of((unsigned)n_cells) + 7) / 8;             // the key reaches n_cells itself
-    for (int ps = 0; ps < passes; ++ps) radix_pass<false>(w.kv, n, 8 * ps, nullptr, w.hist, w.scr, st);
+    segsort_run(w, n, bits_of((unsigned)n_cells), st);                   // the key reaches n_cells itself
     MMG_CHECK_LAUNCH("cf_coverage(sort)");
   }
   const unsigned grid = (unsigned)(n_cells + 1 < CF_MAX_GRID ? n_cells + 1 : CF_MAX_GRID);

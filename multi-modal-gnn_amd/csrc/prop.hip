@@ -12,7 +12,7 @@
 //   k_pr_solve      one workgroup per lab: H + diag(1 / C, 0), packed lower triangle in LDS (129 x 130 / 2 doubles =
 //                   67,080 bytes), the solve of chol64.h, the decrement.
 //   k_pr_update     one thread per lab: accept or halve, test convergence, freeze, count.
-//   k_pr_pkeys .. k_pr_pall   the weighted error sums over pairs: one stable radix sort by lab (radix_sort.h), the labs'
+//   k_pr_pkeys .. k_pr_pall   the weighted error sums over pairs: one stable sort by lab (segsort.h), the labs'
 //                   bounds and chunk bases by one workgroup, one workgroup per chunk of 256 pairs of one lab (a fixed tree
 //                   in LDS), a lab's chunk sums in ascending order, the labs' sums in ascending order.
 // fp64 contraction is OFF for the whole file (chol64.h switches it off for itself): link, solve and update restate numpy
@@ -21,7 +21,7 @@
 #include "common.h"
 #include "chol64.h"
 #include "gram64.h"
-#include "radix_sort.h"
+#include "segsort.h"
 #include "../../include/mmgnn_prop.h"
 #include <limits.h>
 #include <math.h>
@@ -298,24 +298,16 @@ __global__ __launch_bounds__(64) void k_pr_update(const double* __restrict__ los
 constexpr int PR_PC = MMG_PR_PAIR_CHUNK;
 constexpr int PR_PF = MMG_PR_PAIR_FIELDS;
 static_assert(PR_PC == PR_NTHR, "one thread per pair of a chunk");
-inline int pr_lab_bits(int L) { int b = 1; while ((1 << b) <= L) ++b; return b; }          // keys 0 .. L
 inline int64_t pr_chunk_cap(int64_t m, int L) { return m / PR_PC + L + 1; }
 
 struct PairWs {
-  uint32_t *keys, *keys_alt, *hist, *scratch, *start, *cbase;
-  int32_t *vals, *vals_alt;
+  SegSortWs<uint32_t> sort;
+  uint32_t *start, *cbase;
   double* part;
 };
 size_t pair_carve(void* ws, int64_t m, int L, PairWs* w) {
-  const size_t n = (size_t)(m > 0 ? m : 1);
-  const RadixSizes rs = radix_sizes(m);
   MmgCarver c(ws);
-  w->keys = c.take<uint32_t>(n);
-  w->keys_alt = c.take<uint32_t>(n);
-  w->vals = c.take<int32_t>(n);
-  w->vals_alt = c.take<int32_t>(n);
-  w->hist = c.take<uint32_t>(rs.hist_elems);
-  w->scratch = c.take<uint32_t>(rs.scratch_elems);
+  segsort_carve(c, m, &w->sort);
   w->start = c.take<uint32_t>((size_t)L + 2);
   w->cbase = c.take<uint32_t>((size_t)L + 2);
   w->part = c.take<double>((size_t)pr_chunk_cap(m, L) * PR_PF);
@@ -337,14 +329,7 @@ __global__ __launch_bounds__(PR_NTHR) void k_pr_pkeys(const long long* __restric
 // one workgroup: start[j] = the first sorted position with key >= j (j = 0 .. L + 1), cbase[j] = the chunks before lab j
 __global__ __launch_bounds__(PR_NTHR) void k_pr_pbounds(const uint32_t* __restrict__ keys, int64_t m, int L,
                                                         uint32_t* __restrict__ start, uint32_t* __restrict__ cbase) {
-  for (int j = threadIdx.x; j <= L + 1; j += PR_NTHR) {
-    int64_t lo = 0, hi = m;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (keys[mid] < (uint32_t)j) lo = mid + 1; else hi = mid;
-    }
-    start[j] = (uint32_t)lo;
-  }
+  for (int j = threadIdx.x; j <= L + 1; j += PR_NTHR) start[j] = (uint32_t)lower_bound(keys, m, (uint32_t)j);
   __syncthreads();
   if (threadIdx.x == 0) {
     uint32_t c = 0;
@@ -584,11 +569,11 @@ extern "C" int mmg_prop_pair_sums(const float* pred, const float* target, const 
   PairWs w;
   MMG_CHECK_WS("prop_pair_sums", pair_carve(ws, m, L, &w));
   hipStream_t st = (hipStream_t)stream;
-  RadixPairs<uint32_t> b{w.keys, w.keys_alt, w.vals, w.vals_alt};
+  const RadixPairs<uint32_t>& b = w.sort.kv;        // the sort leaves its result here
   if (m > 0) {
     MMG_LAUNCH(MMG_PROBE_ELEMENTWISE, m, L, 0, 0, k_pr_pkeys, dim3(cell_grid(m, 1)), dim3(PR_NTHR), 0, st,
                (const long long*)patient, (const long long*)lab, m, n, L, b.keys, b.vals);
-    for (int shift = 0; shift < pr_lab_bits(L); shift += 8) radix_pass<false>(b, m, shift, nullptr, w.hist, w.scratch, st);
+    segsort_run(w.sort, m, bits_of((unsigned)L), st);            // keys 0 .. L
   }
   MMG_LAUNCH(MMG_PROBE_ELEMENTWISE, m, L, 1, 0, k_pr_pbounds, dim3(1), dim3(PR_NTHR), 0, st, b.keys, m, L, w.start, w.cbase);
   MMG_LAUNCH(MMG_PROBE_ELEMENTWISE, m, L, 2, 0, k_pr_pchunk, dim3((unsigned)pr_chunk_cap(m, L)), dim3(PR_NTHR), 0, st, pred,

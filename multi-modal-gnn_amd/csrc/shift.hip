@@ -6,15 +6,15 @@
 //                    histogram in LDS (integer atomics), the digit picked by one thread's walk over the bins.
 //   k_sh_keys        ONE read of the pairs: sort key = lab << 32 | orderable(value) (n_seg << 32 for a dropped pair: sorts
 //                    last), payload = the pair's position; the unit as uint32 with the given label in bit 31; the four
-//                    kinds of dropped pairs (per-wave sums, one integer atomic per wave and kind).
-//   radix_pass       the stable LSD sort of radix_sort.h over the four digits of the value and the 1-2 of the lab.
-//   k_sh_bounds      bounds[s] = the first sorted position of lab s (s = n_seg: the number of kept pairs).
+//                    kinds of dropped pairs (drop_flush of segsort.h).
+//   segsort_run      the stable sort of segsort.h over the four digits of the value and the 1-2 of the lab.
+//   k_seg_bounds     (segsort.h) bounds[s] = the first sorted position of lab s (s = n_seg: the number of kept pairs).
 //   k_sh_walk<false> the counting pass: workgroup (c, y) walks chunk c (SH_CHUNK consecutive sorted pairs) for the SH_RB
 //                    replicates y * SH_RB + thread.  Tiles of SH_TILE pairs are staged in LDS once; every thread reads
 //                    the same LDS word (broadcast), hashes once per pair, compares with its threshold and counts.  All
 //                    threads see the same lab boundaries: no divergence.  At a boundary the count goes to the chunk's
-//                    HEAD slot (the chunk's first lab), straight to n_a (a lab that begins and ends inside the chunk,
-//                    first excepted) or, at the chunk's end, to its TAIL slot.
+//                    HEAD slot, straight to n_a or to the chunk's TAIL slot: the chunk protocol stated at SegChunks
+//                    (segsort.h).
 //   k_sh_combine<false>  one thread per (lab, replicate): n_a = the slots in chunk order, and on the way the running
 //                    count at the start of every chunk the lab heads.
 //   k_sh_walk<true>  the same walk with the statistics: the running d = c_a n_b - c_b n_a = c_a n - c n_a moves by
@@ -54,14 +54,6 @@ __device__ __forceinline__ uint32_t sh_hash(uint32_t key, uint32_t u) {
   uint32_t w0, w1;
   mmg_rng_group(key, (uint64_t)u, &w0, &w1);       // w1 is dead code: only the first word is used
   return w0;
-}
-__device__ __forceinline__ uint32_t sh_orderable(float v) {
-  uint32_t b = __float_as_uint(v);
-  if ((b << 1) == 0u) b = 0u;                      // -0.0 is taken as +0.0
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float sh_value(uint32_t o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
 
 // ---------------------------------------------------------------------------------- thresholds
@@ -160,21 +152,13 @@ __global__ __launch_bounds__(SH_NTHR) void k_sh_keys(const float* __restrict__ v
       if (g > 1u) kind = 3;
     }
     if (kind >= 0) cnt[kind] += 1;
-    key[i] = kind < 0 ? ((unsigned long long)s << 32) | sh_orderable(v) : (unsigned long long)n_seg << 32;
+    uint32_t vb = __float_as_uint(v);
+    if ((vb << 1) == 0u) vb = 0u;                    // -0.0 is taken as +0.0
+    key[i] = kind < 0 ? ((unsigned long long)s << 32) | bits_orderable(vb) : (unsigned long long)n_seg << 32;
     id[i] = (int32_t)i;
     unit32[i] = kind < 0 ? (uint32_t)u | (g << 31) : 0u;
   }
-#pragma unroll
-  for (int k = 0; k < MMG_SHIFT_DROP_KINDS; ++k) {
-    const int t = wave_sum_i(cnt[k]);
-    if ((threadIdx.x & 63) == 0 && t) atomicAdd(dropped + k, (unsigned long long)t);
-  }
-}
-
-__global__ __launch_bounds__(SH_NTHR) void k_sh_bounds(const unsigned long long* __restrict__ K, int64_t n, int n_seg,
-                                                       int32_t* __restrict__ bounds) {
-  const int s = blockIdx.x * SH_NTHR + threadIdx.x;
-  if (s <= n_seg) bounds[s] = (int32_t)lower_bound(K, n, (unsigned long long)s << 32);
+  drop_flush(cnt, dropped);
 }
 
 // ---------------------------------------------------------------------------------- the walk
@@ -231,11 +215,11 @@ __global__ __launch_bounds__(SH_NTHR) void k_sh_walk(const unsigned long long* _
         if (STATS) {
           const unsigned long long kn = j + 1 < nk ? K[j + 1] : (unsigned long long)n_seg << 32;
           const bool same_lab = (uint32_t)(kn >> 32) == lab;
-          const double v = (double)sh_value((uint32_t)kj);
+          const double v = (double)orderable_float((uint32_t)kj);
           s_v[threadIdx.x] = v;
           s_q[threadIdx.x] = v * v;
           s_end[threadIdx.x] = kn != kj ? 1 : 0;                     // equal keys: equal values of one lab
-          s_dv[threadIdx.x] = same_lab ? (double)sh_value((uint32_t)kn) - v : 0.0;
+          s_dv[threadIdx.x] = same_lab ? (double)orderable_float((uint32_t)kn) - v : 0.0;
         }
       }
       s_lab[threadIdx.x] = lab;
@@ -245,6 +229,7 @@ __global__ __launch_bounds__(SH_NTHR) void k_sh_walk(const unsigned long long* _
     for (int j = 0; j < m; ++j) {
       const uint32_t s = s_lab[j];                                   // the same word for every thread
       if (s != cur) {                                                // the open lab ends in front of a pair of s
+        // HEAD slot or direct: the protocol at SegChunks
         if (cur < (uint32_t)n_seg && live) {
           if (!STATS) {
             if (cur == first) cpart[sh_cslot(c, 0, r, R1)] = ca;
@@ -327,16 +312,14 @@ __global__ __launch_bounds__(SH_NTHR) void k_sh_combine(const int32_t* __restric
                                                         long long* __restrict__ counts, double* __restrict__ sums) {
   const int R1 = replicates + 1;
   const int s = blockIdx.x;
-  const int64_t lo = bounds[s], hi = bounds[s + 1], nk = bounds[n_seg];
-  const int64_t c0 = lo / SH_CHUNK, c1 = hi > lo ? (hi - 1) / SH_CHUNK : c0;
-  // written by k_sh_walk itself: inside one chunk, not its first lab, and a kept pair of the chunk follows it
-  if (hi > lo && c0 == c1 && lo > c0 * SH_CHUNK && hi < (c0 + 1) * SH_CHUNK && hi < nk) return;
+  const SegChunks<SH_CHUNK> ch(bounds[s], bounds[s + 1], bounds[n_seg]);
+  if (ch.written_by_walk()) return;
   for (int r = blockIdx.y * SH_NTHR + threadIdx.x; r < R1; r += gridDim.y * SH_NTHR) {
     if (!STATS) {
       uint32_t run = 0u;
-      if (hi > lo)
-        for (int64_t c = c0; c <= c1; ++c) {
-          const int which = lo <= c * SH_CHUNK ? 0 : 1;               // the lab heads the chunk, or ends it
+      if (!ch.empty())
+        for (int64_t c = ch.c0; c <= ch.c1; ++c) {
+          const int which = ch.which(c);
           if (which == 0) start[(size_t)c * R1 + r] = run;
           run += cpart[sh_cslot(c, which, r, R1)];
         }
@@ -344,9 +327,9 @@ __global__ __launch_bounds__(SH_NTHR) void k_sh_combine(const int32_t* __restric
     } else {
       ShStat a;
       a.clear();
-      if (hi > lo)
-        for (int64_t c = c0; c <= c1; ++c) {
-          const int which = lo <= c * SH_CHUNK ? 0 : 1;
+      if (!ch.empty())
+        for (int64_t c = ch.c0; c <= ch.c1; ++c) {
+          const int which = ch.which(c);
           const long long kp = __double_as_longlong(spart[sh_sslot(c, which, 0, r, R1)]);
           const long long km = __double_as_longlong(spart[sh_sslot(c, which, 1, r, R1)]);
           a.kp = kp > a.kp ? kp : a.kp;
@@ -357,11 +340,11 @@ __global__ __launch_bounds__(SH_NTHR) void k_sh_combine(const int32_t* __restric
           a.qa += spart[sh_sslot(c, which, 5, r, R1)];
           a.qb += spart[sh_sslot(c, which, 6, r, R1)];
         }
-      const long long n_a = hi > lo ? (long long)na[(size_t)s * R1 + r] : 0ll;
+      const long long n_a = !ch.empty() ? (long long)na[(size_t)s * R1 + r] : 0ll;
       long long* __restrict__ ci = counts + ((size_t)r * n_seg + s) * MMG_SHIFT_INT_FIELDS;
       double* __restrict__ cd = sums + ((size_t)r * n_seg + s) * MMG_SHIFT_SUM_FIELDS;
       ci[0] = n_a;
-      ci[1] = (long long)(hi - lo) - n_a;
+      ci[1] = (long long)(ch.hi - ch.lo) - n_a;
       ci[2] = a.kp;
       ci[3] = a.km;
       cd[0] = a.w;
@@ -483,22 +466,16 @@ __global__ __launch_bounds__(SH_NTHR) void k_sh_summary(const double* __restrict
 }
 
 struct ShiftWs {
-  RadixPairs<unsigned long long> kv;
-  uint32_t *hist, *scr, *unit32, *cpart, *start;
+  SegSortWs<unsigned long long> sort;
+  uint32_t *unit32, *cpart, *start;
   int32_t *bounds, *na;
   double* spart;
 };
 inline int64_t sh_chunks(int64_t n) { return n > 0 ? (n + SH_CHUNK - 1) / SH_CHUNK : 1; }
 size_t shift_carve(void* ws, int64_t n, int n_seg, int replicates, ShiftWs* w) {
   MmgCarver c(ws);
-  const RadixSizes rs = radix_sizes(n);
   const size_t nn = (size_t)(n > 0 ? n : 1), R1 = (size_t)replicates + 1, ch = (size_t)sh_chunks(n);
-  w->kv.keys = c.take<unsigned long long>(nn);
-  w->kv.keys_alt = c.take<unsigned long long>(nn);
-  w->kv.vals = c.take<int32_t>(nn);
-  w->kv.vals_alt = c.take<int32_t>(nn);
-  w->hist = c.take<uint32_t>(rs.hist_elems);
-  w->scr = c.take<uint32_t>(rs.scratch_elems);
+  segsort_carve(c, n, &w->sort);
   w->unit32 = c.take<uint32_t>(nn);
   w->bounds = c.take<int32_t>((size_t)n_seg + 2);
   w->na = c.take<int32_t>((size_t)n_seg * R1);
@@ -553,36 +530,33 @@ extern "C" int mmg_shift_stats(const float* value, const void* seg, const void* 
   MMG_CHECK_ARG(counts && sums && dropped, "shift_stats: null output");
   ShiftWs w;
   MMG_CHECK_WS("shift_stats", shift_carve(ws, n, n_seg, replicates, &w));
+  const RadixPairs<unsigned long long>& kv = w.sort.kv;       // the sort leaves its result here
   hipStream_t st = (hipStream_t)stream;
   MMG_CHECK_HIP(mmg_zero_async(dropped, MMG_SHIFT_DROP_KINDS * sizeof(int64_t), st), "shift_stats(zero)");
   const unsigned rblocks = (unsigned)((replicates + 1 + SH_RB - 1) / SH_RB);
   if (n > 0) {
-    if (index_bytes == 8)
-      hipLaunchKernelGGL(k_sh_keys<int64_t>, dim3(launch_grid(n, SH_NTHR, SH_MAX_GRID)), dim3(SH_NTHR), 0, st, value,
-                         (const int64_t*)seg, (const int64_t*)unit, group, n, n_units, n_seg, w.kv.keys, w.kv.vals, w.unit32,
+    index_dispatch(index_bytes, [&](auto it) {
+      using IT = decltype(it);
+      hipLaunchKernelGGL(k_sh_keys<IT>, dim3(launch_grid(n, SH_NTHR, SH_MAX_GRID)), dim3(SH_NTHR), 0, st, value,
+                         (const IT*)seg, (const IT*)unit, group, n, n_units, n_seg, kv.keys, kv.vals, w.unit32,
                          (unsigned long long*)dropped);
-    else
-      hipLaunchKernelGGL(k_sh_keys<int32_t>, dim3(launch_grid(n, SH_NTHR, SH_MAX_GRID)), dim3(SH_NTHR), 0, st, value,
-                         (const int32_t*)seg, (const int32_t*)unit, group, n, n_units, n_seg, w.kv.keys, w.kv.vals, w.unit32,
-                         (unsigned long long*)dropped);
+    });
     MMG_CHECK_LAUNCH("shift_stats(keys)");
-    const int passes = 4 + (bits_of((unsigned)n_seg) + 7) / 8;           // the value, and a lab digit that reaches n_seg
-    for (int ps = 0; ps < passes; ++ps) radix_pass<false>(w.kv, n, 8 * ps, nullptr, w.hist, w.scr, st);
+    segsort_run(w.sort, n, 32 + bits_of((unsigned)n_seg), st);           // the value, and a lab digit that reaches n_seg
     MMG_CHECK_LAUNCH("shift_stats(sort)");
   }
-  hipLaunchKernelGGL(k_sh_bounds, dim3((unsigned)((n_seg + 1 + SH_NTHR - 1) / SH_NTHR)), dim3(SH_NTHR), 0, st, w.kv.keys, n,
-                     n_seg, w.bounds);
+  seg_bounds(kv.keys, n, n_seg, 32, w.bounds, st);
   MMG_CHECK_LAUNCH("shift_stats(bounds)");
   const dim3 wgrid((unsigned)sh_chunks(n), rblocks), cgrid((unsigned)n_seg, rblocks), block(SH_NTHR);
   const unsigned long long* Tu = (const unsigned long long*)T;
   if (n > 0) {
-    hipLaunchKernelGGL(k_sh_walk<false>, wgrid, block, 0, st, w.kv.keys, w.kv.vals, w.unit32, w.bounds, n_seg, replicates, seed,
+    hipLaunchKernelGGL(k_sh_walk<false>, wgrid, block, 0, st, kv.keys, kv.vals, w.unit32, w.bounds, n_seg, replicates, seed,
                        Tu, w.cpart, w.na, w.start, w.spart, (long long*)counts, sums);
     MMG_CHECK_LAUNCH("shift_stats(count)");
     hipLaunchKernelGGL(k_sh_combine<false>, cgrid, block, 0, st, w.bounds, n_seg, replicates, w.cpart, w.na, w.start, w.spart,
                        (long long*)counts, sums);
     MMG_CHECK_LAUNCH("shift_stats(prefix)");
-    hipLaunchKernelGGL(k_sh_walk<true>, wgrid, block, 0, st, w.kv.keys, w.kv.vals, w.unit32, w.bounds, n_seg, replicates, seed,
+    hipLaunchKernelGGL(k_sh_walk<true>, wgrid, block, 0, st, kv.keys, kv.vals, w.unit32, w.bounds, n_seg, replicates, seed,
                        Tu, w.cpart, w.na, w.start, w.spart, (long long*)counts, sums);
     MMG_CHECK_LAUNCH("shift_stats(walk)");
   }

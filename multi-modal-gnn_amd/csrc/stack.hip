@@ -2,10 +2,9 @@
 // sums of a ridge regression of the target on K predictors per (fold, lab, degree bin), the coefficients of every cell
 // from the first usable of (cell, lab, all pairs), and the epilogues that apply them and score the result.
 //   k_st_keys        ONE read of the indices and values: sort key = fold * n_cells + cell (n_seg for a dropped pair: sorts
-//                    last), payload = the pair's position, the four kinds of dropped pairs (integer counts: per-wave sums,
-//                    one integer atomic per wave and kind).
-//   radix_pass       the stable LSD sort of radix_sort.h over the 1-3 digits of the segment.
-//   k_st_bounds      one thread per segment: where it begins in the sorted keys (a binary search).
+//                    last), payload = the pair's position, the four kinds of dropped pairs (drop_flush of segsort.h).
+//   segsort_run      the stable sort of segsort.h over the 1-3 digits of the segment.
+//   k_seg_bounds     (segsort.h) one thread per segment: where it begins in the sorted keys (a binary search).
 //   k_st_chunks      workgroup (x, y) walks the chunks y, y + grid.y, .. of the segments x, x + grid.x, ..: a chunk is
 //                    ST_CHUNK consecutive sorted pairs of ONE segment, so no thread ever looks at a key.  Thread t gathers
 //                    the pairs t, t + 256, .. of the chunk, forms their terms in fp64 (each a product of two fp32 values:
@@ -91,18 +90,7 @@ __global__ __launch_bounds__(ST_NTHR) void k_st_keys(StFeats ft, const float* __
     key[i] = (uint32_t)seg;
     id[i] = (int32_t)i;
   }
-#pragma unroll
-  for (int q = 0; q < MMG_ST_DROP_KINDS; ++q) {
-    const int t = wave_sum_i(cnt[q]);            // a thread takes at most 2^31 / (grid x 256) pairs: no overflow
-    if ((threadIdx.x & 63) == 0 && t) atomicAdd(dropped + q, (unsigned long long)t);   // integer: any order, one result
-  }
-}
-
-// seg_lo[s], s = 0 .. n_seg: the first sorted position whose key is >= s (seg_lo[n_seg] = the number of kept pairs)
-__global__ __launch_bounds__(ST_NTHR) void k_st_bounds(const uint32_t* __restrict__ K, int64_t n, int n_seg,
-                                                       int64_t* __restrict__ seg_lo) {
-  const int s = blockIdx.x * ST_NTHR + threadIdx.x;
-  if (s <= n_seg) seg_lo[s] = lower_bound(K, n, (uint32_t)s);
+  drop_flush(cnt, dropped);
 }
 
 // ---------------------------------------------------------------------------------- terms
@@ -402,21 +390,13 @@ int feats_check(const char* what, const float* const* feats, int K, bool need, S
 }
 
 struct SumsWs {
-  RadixPairs<uint32_t> kv;
-  uint32_t *hist, *scr;
-  int64_t* seg_lo;
+  SegSortWs<uint32_t> sort;
+  int64_t* seg_lo;           // [n_seg + 1]: seg_lo[n_seg] = the number of kept pairs
   double* part;
 };
 size_t sums_carve(void* ws, int64_t n, int n_seg, int NF, SumsWs* w) {
   MmgCarver c(ws);
-  const RadixSizes rs = radix_sizes(n);
-  const size_t nn = (size_t)(n > 0 ? n : 1);
-  w->kv.keys = c.take<uint32_t>(nn);
-  w->kv.keys_alt = c.take<uint32_t>(nn);
-  w->kv.vals = c.take<int32_t>(nn);
-  w->kv.vals_alt = c.take<int32_t>(nn);
-  w->hist = c.take<uint32_t>(rs.hist_elems);
-  w->scr = c.take<uint32_t>(rs.scratch_elems);
+  segsort_carve(c, n, &w->sort);
   w->seg_lo = c.take<int64_t>((size_t)n_seg + 1);
   w->part = c.take<double>(((size_t)(n / ST_CHUNK) + (size_t)n_seg + 1) * NF);      // slot < n / C + n_seg
   return c.need();
@@ -429,30 +409,27 @@ int sums_run(const char* what, const StFeats& ft, const float* target, const voi
              const T& terms, double* sums, int64_t* dropped, SumsWs w, hipStream_t st) {
   const int n_seg = folds * L * B;
   const uint32_t rng_key = mmg_rng_key(seed, (uint32_t)MMG_ST_SITE);
+  const RadixPairs<uint32_t>& kv = w.sort.kv;       // the sort leaves its result here (w is a copy: its buffers swap)
   MMG_CHECK_HIP(mmg_zero_async(dropped, MMG_ST_DROP_KINDS * sizeof(int64_t), st), what);
   if (n > 0) {
-    if (index_bytes == 8)
-      hipLaunchKernelGGL(k_st_keys<int64_t>, dim3(launch_grid(n, ST_NTHR, ST_MAX_GRID)), dim3(ST_NTHR), 0, st, ft, target,
-                         (const int64_t*)patient, (const int64_t*)lab, n, L, deg, n_pat, B, ed, folds, rng_key, w.kv.keys,
-                         w.kv.vals, (unsigned long long*)dropped);
-    else
-      hipLaunchKernelGGL(k_st_keys<int32_t>, dim3(launch_grid(n, ST_NTHR, ST_MAX_GRID)), dim3(ST_NTHR), 0, st, ft, target,
-                         (const int32_t*)patient, (const int32_t*)lab, n, L, deg, n_pat, B, ed, folds, rng_key, w.kv.keys,
-                         w.kv.vals, (unsigned long long*)dropped);
+    index_dispatch(index_bytes, [&](auto it) {
+      using IT = decltype(it);
+      hipLaunchKernelGGL(k_st_keys<IT>, dim3(launch_grid(n, ST_NTHR, ST_MAX_GRID)), dim3(ST_NTHR), 0, st, ft, target,
+                         (const IT*)patient, (const IT*)lab, n, L, deg, n_pat, B, ed, folds, rng_key, kv.keys, kv.vals,
+                         (unsigned long long*)dropped);
+    });
     MMG_CHECK_LAUNCH(what);
-    const int passes = (bits_of((unsigned)n_seg) + 7) / 8;               // the key reaches n_seg itself
-    for (int ps = 0; ps < passes; ++ps) radix_pass<false>(w.kv, n, 8 * ps, nullptr, w.hist, w.scr, st);
+    segsort_run(w.sort, n, bits_of((unsigned)n_seg), st);                // the key reaches n_seg itself
     MMG_CHECK_LAUNCH(what);
   }
-  hipLaunchKernelGGL(k_st_bounds, dim3((unsigned)((n_seg + 1 + ST_NTHR - 1) / ST_NTHR)), dim3(ST_NTHR), 0, st, w.kv.keys, n,
-                     n_seg, w.seg_lo);
+  seg_bounds(kv.keys, n, n_seg, 0, w.seg_lo, st);
   MMG_CHECK_LAUNCH(what);
   if (n > 0) {
     const int64_t max_chunks = (n + ST_CHUNK - 1) / ST_CHUNK;
     const unsigned gx = (unsigned)(n_seg < 4096 ? n_seg : 4096);
     int64_t gy = 8192 / gx;
     gy = gy < 1 ? 1 : gy > max_chunks ? max_chunks : gy;
-    hipLaunchKernelGGL(k_st_chunks<T>, dim3(gx, (unsigned)gy), dim3(ST_NTHR), 0, st, w.kv.vals, w.seg_lo, n_seg, terms, w.part);
+    hipLaunchKernelGGL(k_st_chunks<T>, dim3(gx, (unsigned)gy), dim3(ST_NTHR), 0, st, kv.vals, w.seg_lo, n_seg, terms, w.part);
     MMG_CHECK_LAUNCH(what);
   }
   hipLaunchKernelGGL(k_st_combine, dim3(launch_grid((int64_t)n_seg * T::NF, ST_NTHR, ST_MAX_GRID, 1)), dim3(ST_NTHR), 0, st,
@@ -578,14 +555,12 @@ extern "C" int mmg_stack_apply_pairs(const float* const* feats, int n_features, 
   if (n == 0) return MMG_OK;
   hipStream_t st = (hipStream_t)stream;
   const uint32_t rng_key = mmg_rng_key(seed, (uint32_t)MMG_ST_SITE);
-  if (index_bytes == 8)
-    hipLaunchKernelGGL(k_st_apply_pairs<int64_t>, dim3(launch_grid(n, ST_NTHR, ST_MAX_GRID)), dim3(ST_NTHR), 0, st, ft,
-                       (const int64_t*)patient, (const int64_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, coef, folds,
-                       rng_key, cross, out);
-  else
-    hipLaunchKernelGGL(k_st_apply_pairs<int32_t>, dim3(launch_grid(n, ST_NTHR, ST_MAX_GRID)), dim3(ST_NTHR), 0, st, ft,
-                       (const int32_t*)patient, (const int32_t*)lab, n, n_labs, deg, n_patients, n_bins, ed, coef, folds,
-                       rng_key, cross, out);
+  index_dispatch(index_bytes, [&](auto it) {
+    using IT = decltype(it);
+    hipLaunchKernelGGL(k_st_apply_pairs<IT>, dim3(launch_grid(n, ST_NTHR, ST_MAX_GRID)), dim3(ST_NTHR), 0, st, ft,
+                       (const IT*)patient, (const IT*)lab, n, n_labs, deg, n_patients, n_bins, ed, coef, folds, rng_key,
+                       cross, out);
+  });
   MMG_CHECK_LAUNCH("stack_apply_pairs");
   return MMG_OK;
 }
@@ -615,12 +590,11 @@ extern "C" int mmg_stack_apply_matrix(const float* const* feats, const int64_t* 
   hipStream_t st = (hipStream_t)stream;
   const uint32_t rng_key = mmg_rng_key(seed, (uint32_t)MMG_ST_SITE);
   const dim3 grid(launch_grid(n_rows * n_labs, ST_NTHR, ST_MAX_GRID)), block(ST_NTHR);
-  if (rows && index_bytes == 4)
-    hipLaunchKernelGGL(k_st_apply_matrix<int32_t>, grid, block, 0, st, ft, n_rows, n_labs, (const int32_t*)rows, deg,
-                       n_patients, n_bins, ed, coef, folds, rng_key, cross, out, ld_out);
-  else
-    hipLaunchKernelGGL(k_st_apply_matrix<int64_t>, grid, block, 0, st, ft, n_rows, n_labs, (const int64_t*)rows, deg,
-                       n_patients, n_bins, ed, coef, folds, rng_key, cross, out, ld_out);
+  index_dispatch(rows ? index_bytes : 8, [&](auto it) {           // no row list: the int64 instance, which never reads it
+    using IT = decltype(it);
+    hipLaunchKernelGGL(k_st_apply_matrix<IT>, grid, block, 0, st, ft, n_rows, n_labs, (const IT*)rows, deg, n_patients,
+                       n_bins, ed, coef, folds, rng_key, cross, out, ld_out);
+  });
   MMG_CHECK_LAUNCH("stack_apply_matrix");
   return MMG_OK;
 }

@@ -104,7 +104,10 @@ def check_case(c, R, seed, itype, with_b, confidence=0.95, spread=True):
     # replicate 0 is what the reducer it extends computes
     if len(c["pred"]):
         d = lambda k, dt: torch.from_numpy(np.ascontiguousarray(c[k])).to(DEV, dt)      # noqa: E731
-        s8 = ops.seg_sums(d("pred", torch.float32), d("target", torch.float32), d("seg", torch.int64), c["n_seg"])[0]
+        # the reducer knows no units and adds a NaN: a pair the bootstrap drops is outside its segments (-1)
+        ok = ~np.isnan(bt.host_terms(c["pred"], c["target"], pb)).any(1) & (c["unit"] >= 0) & (c["unit"] < c["n_units"])
+        seg8 = torch.from_numpy(np.where(ok, c["seg"], -1)).to(DEV, torch.int64)
+        s8 = ops.seg_sums(d("pred", torch.float32), d("target", torch.float32), seg8, c["n_seg"])[0]
         s8 = s8.cpu().numpy()
         assert same(got[0, :, 0], s8[:, 0]) and same(got[0, :, 6], s8[:, 6])
         assert (np.abs(got[0, :, :7] - s8[:, :7]) <= bound[0, :, :7]).all()
@@ -171,6 +174,62 @@ def test_all_pairs_in_one_unit():
     w = ref.weights_at(8, [0], 40)[:, 0]
     assert same(got[:, :, 0], w[:, None] * got[0:1, :, 0])
     assert np.isnan(gm[1:][w[1:] == 0]).all() and (w[1:] == 0).any()
+
+
+# ---------------------------------------------------------------------------------- the chunk protocol
+# kept (segment, pairs) runs in sorted order and the dropped pairs behind them; 6 segments, segment 1 always empty
+CHUNK_LAYOUTS = {
+    "ends_on_chunk_end_then_only_dropped": ([(0, 37), (2, C - 37)], 5),
+    "ends_on_chunk_end_then_a_kept_pair": ([(0, 60), (2, C - 60), (4, 1)], 0),
+    "direct_then_last_kept_mid_chunk": ([(0, 100), (2, 300), (3, 50)], 40),        # 3: not first, only dropped follow: TAIL
+    "one_segment_over_three_chunks": ([(0, 100), (2, 2 * C - 98), (3, 1)], 0),
+    "a_whole_chunk_of_dropped": ([(5, 10)], C),
+    "all_dropped": ([], 7),
+}
+
+
+def layout_case(kept, n_dropped, seed):
+    """The pairs of a layout, shuffled.  A dropped pair is, in turn, of segment -1, of segment n_seg, of a unit out of
+    range (below, above), of a NaN target."""
+    n_seg, n_units = 6, 97
+    rng = np.random.default_rng(seed)
+    seg = np.concatenate([np.full(m, s, np.int64) for s, m in kept] + [np.full(n_dropped, 4, np.int64)])
+    n = len(seg)
+    t = rng.normal(1.0, 2.0, n).astype(F32)
+    t[rng.random(n) < 0.05] = 0
+    unit = rng.integers(0, n_units, n)
+    j = np.arange(n - n_dropped, n)
+    seg[j[0::4]] = -1
+    seg[j[1::4]] = n_seg
+    unit[j[2::8]] = -2
+    unit[j[6::8]] = n_units
+    t[j[3::4]] = np.nan
+    p = (t + rng.normal(0, 0.7, n)).astype(F32)
+    pb = (t + rng.normal(0.2, 1.1, n)).astype(F32)
+    o = rng.permutation(n)
+    dropped = [len(j[0::4]) + len(j[1::4]), len(j[2::4]), len(j[3::4])]
+    return {"pred": p[o], "target": t[o], "pred_b": pb[o], "unit": unit[o], "seg": seg[o], "n_units": n_units,
+            "n_seg": n_seg}, dropped
+
+
+@pytest.mark.parametrize("name,R", [(k, 5) for k in CHUNK_LAYOUTS] + [("direct_then_last_kept_mid_chunk", RB + 1)])
+def test_head_tail_and_direct_segments_where_walk_and_combine_must_agree(name, R):
+    """k_boot_sums closes a segment into its chunk's HEAD slot, its TAIL slot or straight into `sums`, and k_boot_combine
+    must skip exactly the last kind (SegChunks, csrc/segsort.h).  The layouts sit where the two could disagree: the last
+    kept segment followed only by dropped pairs, a segment that ends on a chunk's end, one over three chunks, a chunk
+    without a kept pair, no kept pair at all.  `sums` is prefilled with NaN: an element nobody writes cannot pass, one
+    written twice holds the combine's value and fails the bound or the counts."""
+    kept, n_dropped = CHUNK_LAYOUTS[name]
+    i = list(CHUNK_LAYOUTS).index(name)
+    c, dropped = layout_case(kept, n_dropped, seed=100 + i)
+    got, _, _ = check_case(c, R, 23 + i, torch.int64 if i % 2 else torch.int32, with_b=bool(i % 2))
+    want_n = np.zeros(6)
+    for s, m in kept:
+        want_n[s] = m
+    assert same(got[0, :, 0], want_n) and sum(dropped) == n_dropped
+    assert dev_sums(c, 1, 0, torch.int64, False)[1].tolist() == dropped
+    if not kept:
+        assert not got.any(), "every element of sums is zero"
 
 
 # ---------------------------------------------------------------------------------- weights

@@ -51,7 +51,8 @@ def bits(t):
 
 def make_case(layout, n_seg, n_units=97, seed=0, n_a_units=None):
     """layout: (lab, pairs, kind) in sorted order; kind "rand" (normal values), "lattice" (small integers: long tie
-    groups), "equal" (one value), "one" (pairs of cohort A only).  The pairs are shuffled: the sort has work to do."""
+    groups), "equal" (one value), "one" (pairs of cohort A only), "drop" (lab -1: dropped pairs -- in turn of lab -1, of
+    lab n_seg, of a unit out of range, of a value that is not finite).  The pairs are shuffled: the sort has work to do."""
     rng = np.random.default_rng(seed)
     group = np.zeros(n_units, np.uint8)
     group[rng.permutation(n_units)[:n_units // 3 if n_a_units is None else n_a_units]] = 1
@@ -61,7 +62,12 @@ def make_case(layout, n_seg, n_units=97, seed=0, n_a_units=None):
         s.append(np.full(m, lab, np.int64))
         u.append(in_a[rng.integers(0, in_a.size, m)] if kind == "one" else rng.integers(0, n_units, m))
         v.append({"rand": rng.normal(0.5, 2.0, m), "one": rng.normal(0.0, 1.0, m), "equal": np.full(m, 1.25),
-                  "lattice": rng.integers(-3, 4, m).astype(np.float64)}[kind].astype(F32))
+                  "lattice": rng.integers(-3, 4, m).astype(np.float64), "drop": rng.normal(0.5, 2.0, m)}[kind].astype(F32))
+        if kind == "drop":
+            s[-1][1::4] = n_seg
+            s[-1][2::4], s[-1][3::4] = 4, 4
+            u[-1][2::8], u[-1][6::8] = -2, n_units
+            v[-1][3::8], v[-1][7::8] = np.nan, np.inf
     cat = lambda x, dt: np.concatenate(x).astype(dt) if x else np.zeros(0, dt)      # noqa: E731
     v, s, u = cat(v, F32), cat(s, np.int64), cat(u, np.int64)
     p = rng.permutation(v.size)
@@ -151,15 +157,23 @@ LAYOUTS = {
     C: [(0, 37, "rand"), (2, C - 37, "rand")],                                 # lab 2 ends exactly on the chunk's end
     C + 1: [(0, 60, "rand"), (2, C - 60, "lattice"), (4, 1, "rand")],          # ... and a pair follows in the next chunk
     2 * C + 3: [(0, 100, "rand"), (2, 2 * C - 98, "rand"), (3, 1, "one")],     # lab 2 spans three chunks
+    # where k_sh_walk and k_sh_combine must agree on who writes a lab (SegChunks, csrc/segsort.h), with dropped pairs last
+    C + 5: [(0, 37, "rand"), (2, C - 37, "rand"), (-1, 5, "drop")],            # ... and only dropped pairs follow
+    490: [(0, 100, "rand"), (2, 300, "lattice"), (3, 50, "rand"), (-1, 40, "drop")],   # 2 direct; 3 mid-chunk, last kept: TAIL
+    C + 10: [(5, 10, "rand"), (-1, C, "drop")],                                # a whole chunk without a kept pair
+    7: [(-1, 7, "drop")],                                                      # no kept pair at all: zeros everywhere
 }
+ORDER = [0, 1, C - 1, C, C + 1, 2 * C + 3, C + 5, 490, C + 10, 7]             # a layout's seed and index width
 
 
 @pytest.mark.parametrize("n", sorted(LAYOUTS))
 def test_tables_finish_summary_at_every_chunk_count(n):
-    i = sorted(LAYOUTS).index(n)
+    i = ORDER.index(n)
     c = make_case(LAYOUTS[n], 6, seed=n)
     assert len(c["value"]) == n
     counts, sums, stats, _ = check_case(c, 5, 11 + i, torch.int64 if i % 2 else torch.int32)
+    if n == 7:
+        assert not counts.any() and not sums.any(), "all pairs dropped"
     tot = counts[0, :, 0] + counts[0, :, 1]
     assert tot.tolist() == [sum(m for lab, m, _ in LAYOUTS[n] if lab == s) for s in range(6)]
     assert tot[1] == 0 and not counts[:, 1].any() and not sums[:, 1].any(), "the empty lab between two filled ones"
